@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- pose-refinements/sec (4 iterations, 480x640) of the HIP refinement path.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" = one 4-iteration refinement of one batch of BATCH_PAIRS=16 synthetic LINEMOD-'ape' pairs per
@@ -9,13 +9,20 @@ GPU (BASELINE.json configs[1]: FlowNetS-backbone forward x4 + SE(3) compose x4 +
 zoom x4), inputs resident in HBM, whole loop replayed as one hipGraph.  Pairs are independent, so ranks
 shard them with no data-path collective ("weak" scaling: 16 pairs per GPU).
 
-Prints ONE JSON line (rank 0) with the contract keys plus
+A plain run sets up (seeded weights, pose head trained untimed: --head-epochs), warms up, times --steps
+steps and prints ONE JSON line (rank 0) with the contract keys ("ms_per_step" = one timed step).
+--dump-outputs DIR then writes what the last timed step computed (poses_iter, se3_iter, status_iter of
+the refiner) as DIR/<name>.npy; the inputs are seeded, so two builds can be compared output for output.
+
+--full adds everything beyond the headline figure (each object still switchable off by its --no-* option):
   "roofline":     dominant kernel's algorithmic TFLOP/s vs its matrix-pipe roof -- the dense f32 MFMA peak for the f32-pipe
                   kernels; for the three-term plane GEMMs (f32 operands split into three bf16 terms, six MFMA products per
                   multiply, f32 accumulate: csrc/wino_gemm_split.hip) the dense bf16 peak / 6 -- from HIP events on the
                   launch stream, averaged over the timed launches of that kernel,
   "cpu_baseline": the CPU oracle (torch-CPU convs + numpy zoom + C rasteriser, batch 1 like the reference
-                  loop) timed on this box's host cores on a bounded sample (rank 0, N == 1 only).
+                  loop) timed on this box's host cores on a bounded sample (rank 0, N == 1 only),
+  "pose_error_vs_gt", "parity" (the checker leg; over its bar = exit code 4), "f32_pipe", "fresh_batch",
+  "full_graph", "modelnet_lit", "train", "train_fresh_batch": see the functions below.
 """
 import argparse
 import glob
@@ -69,7 +76,26 @@ def parse_args():
     ap.add_argument("--f32-pipe", action="store_true", help="Winograd plane GEMMs on the f32 matrix pipe (v_mfma_f32_32x32x2_f32) instead of "
                     "the default three-bf16-term arithmetic (csrc/wino_gemm_split.hip); the default run reports this variant as `f32_pipe`")
     ap.add_argument("--profile-steps", type=int, default=3, help="eager steps with per-layer HIP events for the roofline object")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="also run every non-headline object (roofline, pose_error_vs_gt, f32_pipe, fresh_batch, "
+                    "full_graph, modelnet_lit, train, train_fresh_batch, cpu_baseline, parity); off: set up, warm up, time, print the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last timed step computed "
+                    "(poses_iter, se3_iter, status_iter) as DIR/<name>.npy (float32 / float64; rank r > 0: <name>_rank<r>.npy)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    if args.warmup < 0:
+        ap.error("--warmup must be >= 0")
+    return args
+
+
+def dump_outputs(dirname, refiner, rank):
+    """the refiner's outputs after the last timed step -- what a caller of Refiner.refine() reads -- one .npy per array"""
+    os.makedirs(dirname, exist_ok=True)
+    sfx = "" if rank == 0 else "_rank{}".format(rank)
+    arrays = {"poses_iter": refiner.poses_iter.float(), "se3_iter": refiner.se3_iter.float(),
+              "status_iter": refiner.status_iter.double()}   # int32 status flags, exact in float64
+    for name, t in arrays.items():
+        np.save(os.path.join(dirname, name + sfx + ".npy"), t.cpu().numpy())
 
 
 def host_cores():
@@ -735,10 +761,8 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     status = int(refiner.status_iter.abs().sum().item())
-    poses_hip, se3_hip = refiner.poses_iter.cpu().numpy().copy(), refiner.se3_iter.cpu().numpy().copy()
-    pose_err = pose_error_vs_gt(batch["src_pose"], refiner.poses_iter, batch["pose_gt"])
-
-    roofline = encoder_roofline(pred.net, refiner.batch, test_iter, args.profile_steps)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, refiner, rank)
     net = pred.net
 
     total_pairs = B * world * args.steps
@@ -757,121 +781,124 @@ def main():
                        "; phase images + minimal filtering F(4,1) x F(4,2): " + " ".join(net.wino3s2) if net.wino3s2 else ""),
                    "plane_gemm_arithmetic": "f32 pipe (v_mfma_f32_32x32x2_f32)" if args.f32_pipe or args.no_winograd else
                    "f32 operands as three bf16 terms, six products per multiply on v_mfma_f32_32x32x16_bf16, f32 accumulate (f32 in HBM, "
-                   "f32-level error: tests/test_split_terms.py, parity object below)",
+                   "f32-level error: tests/test_split_terms.py, parity object of --full)",
                    "gflop_per_refinement": round(net.flops_per_forward() * test_iter / B / 1e9, 2), "status_flags": status,
                    "conv_plan": {k: list(v) for k, v in net.conv_plan.items()}},
-        "roofline": roofline,
-        "weights": weights_info, "pose_error_vs_gt": pose_err,
+        "weights": weights_info,
         "ranks": ranks, "ms_per_step_per_rank": per_rank_ms, "dist_backend": args.dist_backend if world > 1 else None,
         "distinct_devices": len({(r["host"], r["uuid"] or r["pci_bus_id"] or r["device"]) for r in ranks}),
     }
-    if world == 1 and not args.no_variants and not args.no_graph and not args.f32_pipe and not args.no_winograd:
-        # the same loop, same batch, same weights with every plane GEMM on the f32 matrix pipe: the A/B of the default arithmetic in
-        # the same process (timed like the headline), and how far the two arithmetics' poses lie apart
-        try:
-            ops.set_winograd_split(False)
-            pred_f = Predictor(cfg, params, B, device=dev, winograd=True)
-            ref_f = Refiner(cfg, pred_f, rm, B, capture_graph=True)
-            ref_f.load(batch["image_observed"], batch["image_rendered"], batch["mask_observed"], batch["mask_rendered"], batch["src_pose"],
-                       batch["class_index"])
-            for _ in range(args.warmup):
-                ref_f.refine()
-            torch.cuda.synchronize()
-            t1 = time.perf_counter()
-            for _ in range(args.steps):
-                ref_f.refine()
-            torch.cuda.synchronize()
-            dt = time.perf_counter() - t1
-            se3_f = ref_f.se3_iter.cpu().numpy()
-            out["f32_pipe"] = {"value": round(B * args.steps / dt, 2), "unit": "pose-refinements/sec", "ms_per_step": round(dt / args.steps * 1e3, 3),
-                               "headline_over_this": round(value / (B * args.steps / dt), 4),
-                               "first_iteration_se3_max_abs_diff_to_headline": float(np.abs(se3_f[0] - se3_hip[0]).max())}
-            del ref_f, pred_f
-        except Exception as e:
-            out["f32_pipe"] = {"error": "{}: {}".format(type(e).__name__, e)}
-        finally:
-            ops.set_winograd_split(True)
-    if world == 1 and not args.no_fresh_batch and not args.no_graph:
-        try:
-            out["fresh_batch"] = fresh_batch_bench(cfg, rm, refiner, B, dev, args.steps, args.warmup)
-        except Exception as e:
-            out["fresh_batch"] = {"error": "{}: {}".format(type(e).__name__, e)}
-    if world == 1 and not args.no_variants and not args.no_graph:
-        for kind in ("full_graph", "modelnet_lit"):
-            try:   # non-headline objects: a failure must not cost the headline line
-                out[kind] = variant_bench(kind, cfg, dev, rank, max(5, args.steps // 2), args.warmup, 1, args.subdiv)
-            except Exception as e:
-                out[kind] = {"error": "{}: {}".format(type(e).__name__, e)}
-    if not args.no_train:
-        del refiner, pred
-        torch.cuda.empty_cache()
-
-        progress = {}
-
-        def run_train():
-            try:
-                torch.cuda.set_device(dev_index)
-                out["train"] = train_bench(cfg, models, rm, int(cfg.TRAIN.BATCH_PAIRS) if args.batch_pairs is None else B, dev, rank, world,
-                                           dist, args.train_steps, progress=progress)
-            except Exception as e:  # the non-headline object must never take the headline line down with it
-                out["train"] = {"error": "{}: {}".format(type(e).__name__, e)}
-
-        if world == 1:
-            run_train()
-        else:
-            # With several ranks the training object is the only part of this program that posts data-path collectives (the gradient
-            # all-reduce).  An exception is caught above; a collective that never completes is not an exception, so the object runs
-            # under a deadline: past it rank 0 still prints the headline line and the process leaves without waiting for the thread.
-            import threading
-
-            th = threading.Thread(target=run_train, daemon=True)
-            th.start()
-            th.join(args.train_deadline)
-            if th.is_alive():
-                # a hang, not a result: rank 0 still prints the headline line (measured before the training object started), every
-                # rank says what it was waiting for, and EVERY rank leaves with a non-zero code so that the launcher and the driver
-                # record the failure.  No retry, no restart in-process: kernels / RCCL work may still be in flight.
-                mod = progress.get("module")
-                pend = None
-                try:
-                    pend = [{"begin": a, "end": b, "completed": c} for a, b, c in mod.pending_buckets()] if mod is not None else None
-                except Exception as e:  # querying a wedged communicator may itself fail
-                    pend = "unavailable: {}".format(e)
-                out["train"] = {"error": "no result within {} s (a collective of the training object did not complete)".format(args.train_deadline),
-                                "rank": rank, "phase": progress.get("phase"), "dtype": progress.get("dtype"), "pending_buckets": pend}
-                sys.stderr.write("bench.py rank {}: train object hung: {}\n".format(rank, json.dumps(out["train"])))
-                sys.stderr.flush()
-                if rank == 0:
-                    print(json.dumps(out), flush=True)
-                os._exit(3)
-    if world == 1 and not args.no_train and not args.no_train_files:
-        try:
-            out["train_fresh_batch"] = train_fresh_batch_bench(cfg, models, rm, int(cfg.TRAIN.BATCH_PAIRS) if args.batch_pairs is None else B, dev)
-        except Exception as e:
-            out["train_fresh_batch"] = {"error": "{}: {}".format(type(e).__name__, e)}
     parity_failed = False
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
-        out["cpu_baseline"] = cpu_baseline(cfg, params, models, batch, args.cpu_pairs)
-    if rank == 0 and world == 1 and args.parity_pairs > 0:
-        # the metric's second clause ("ADD(-S) vs reference"), checker leg: never inside the timed region
-        trained = args.head_epochs > 0
-        out["parity"] = parity_leg(cfg, params, models, batch, poses_hip, se3_hip, min(args.parity_pairs, B), trained)
-        finals = getattr(cpu_baseline, "final_poses", None)
-        if finals is not None:
-            # the cpu_baseline leg refined the batch's pairs free-running (cyclically, if its sample is larger than the batch): ADD of
-            # the HIP loop's final poses against the oracle's
-            from oracle import pose_error
+    if args.full:   # everything beyond the headline figure, after its timed region
+        poses_hip, se3_hip = refiner.poses_iter.cpu().numpy().copy(), refiner.se3_iter.cpu().numpy().copy()
+        out["pose_error_vs_gt"] = pose_error_vs_gt(batch["src_pose"], refiner.poses_iter, batch["pose_gt"])
+        out["roofline"] = encoder_roofline(pred.net, refiner.batch, test_iter, args.profile_steps)
+        if world == 1 and not args.no_variants and not args.no_graph and not args.f32_pipe and not args.no_winograd:
+            # the same loop, same batch, same weights with every plane GEMM on the f32 matrix pipe: the A/B of the default arithmetic in
+            # the same process (timed like the headline), and how far the two arithmetics' poses lie apart
+            try:
+                ops.set_winograd_split(False)
+                pred_f = Predictor(cfg, params, B, device=dev, winograd=True)
+                ref_f = Refiner(cfg, pred_f, rm, B, capture_graph=True)
+                ref_f.load(batch["image_observed"], batch["image_rendered"], batch["mask_observed"], batch["mask_rendered"], batch["src_pose"],
+                           batch["class_index"])
+                for _ in range(args.warmup):
+                    ref_f.refine()
+                torch.cuda.synchronize()
+                t1 = time.perf_counter()
+                for _ in range(args.steps):
+                    ref_f.refine()
+                torch.cuda.synchronize()
+                dt = time.perf_counter() - t1
+                se3_f = ref_f.se3_iter.cpu().numpy()
+                out["f32_pipe"] = {"value": round(B * args.steps / dt, 2), "unit": "pose-refinements/sec", "ms_per_step": round(dt / args.steps * 1e3, 3),
+                                   "headline_over_this": round(value / (B * args.steps / dt), 4),
+                                   "first_iteration_se3_max_abs_diff_to_headline": float(np.abs(se3_f[0] - se3_hip[0]).max())}
+                del ref_f, pred_f
+            except Exception as e:
+                out["f32_pipe"] = {"error": "{}: {}".format(type(e).__name__, e)}
+            finally:
+                ops.set_winograd_split(True)
+        if world == 1 and not args.no_fresh_batch and not args.no_graph:
+            try:
+                out["fresh_batch"] = fresh_batch_bench(cfg, rm, refiner, B, dev, args.steps, args.warmup)
+            except Exception as e:
+                out["fresh_batch"] = {"error": "{}: {}".format(type(e).__name__, e)}
+        if world == 1 and not args.no_variants and not args.no_graph:
+            for kind in ("full_graph", "modelnet_lit"):
+                try:   # non-headline objects: a failure must not cost the headline line
+                    out[kind] = variant_bench(kind, cfg, dev, rank, max(5, args.steps // 2), args.warmup, 1, args.subdiv)
+                except Exception as e:
+                    out[kind] = {"error": "{}: {}".format(type(e).__name__, e)}
+        if not args.no_train:
+            del refiner, pred
+            torch.cuda.empty_cache()
 
-            adds = []
-            for b in range(min(args.cpu_pairs, B)):
-                pts = models[int(batch["class_index"][b])][0].astype(np.float64)
-                ph, po = poses_hip[-1, b].astype(np.float64), finals[b]
-                adds.append(pose_error.add(ph[:, :3], ph[:, 3], po[:, :3], po[:, 3], pts) / float(np.linalg.norm(pts.max(0) - pts.min(0))))
-            out["parity"]["add_free_over_d_cpu_baseline_pairs"] = {"pairs": int(min(args.cpu_pairs, B)), "max": float(max(adds)), "median": float(np.median(adds)),
-                                                                  "within_0.02": int(sum(a < 0.02 for a in adds))}
-            if trained:
-                out["parity"]["ok"] = bool(out["parity"]["ok"] and max(adds) < 0.02)
-        parity_failed = not out["parity"]["ok"]
+            progress = {}
+
+            def run_train():
+                try:
+                    torch.cuda.set_device(dev_index)
+                    out["train"] = train_bench(cfg, models, rm, int(cfg.TRAIN.BATCH_PAIRS) if args.batch_pairs is None else B, dev, rank, world,
+                                               dist, args.train_steps, progress=progress)
+                except Exception as e:  # the non-headline object must never take the headline line down with it
+                    out["train"] = {"error": "{}: {}".format(type(e).__name__, e)}
+
+            if world == 1:
+                run_train()
+            else:
+                # With several ranks the training object is the only part of this program that posts data-path collectives (the gradient
+                # all-reduce).  An exception is caught above; a collective that never completes is not an exception, so the object runs
+                # under a deadline: past it rank 0 still prints the headline line and the process leaves without waiting for the thread.
+                import threading
+
+                th = threading.Thread(target=run_train, daemon=True)
+                th.start()
+                th.join(args.train_deadline)
+                if th.is_alive():
+                    # a hang, not a result: rank 0 still prints the headline line (measured before the training object started), every
+                    # rank says what it was waiting for, and EVERY rank leaves with a non-zero code so that the launcher and the driver
+                    # record the failure.  No retry, no restart in-process: kernels / RCCL work may still be in flight.
+                    mod = progress.get("module")
+                    pend = None
+                    try:
+                        pend = [{"begin": a, "end": b, "completed": c} for a, b, c in mod.pending_buckets()] if mod is not None else None
+                    except Exception as e:  # querying a wedged communicator may itself fail
+                        pend = "unavailable: {}".format(e)
+                    out["train"] = {"error": "no result within {} s (a collective of the training object did not complete)".format(args.train_deadline),
+                                    "rank": rank, "phase": progress.get("phase"), "dtype": progress.get("dtype"), "pending_buckets": pend}
+                    sys.stderr.write("bench.py rank {}: train object hung: {}\n".format(rank, json.dumps(out["train"])))
+                    sys.stderr.flush()
+                    if rank == 0:
+                        print(json.dumps(out), flush=True)
+                    os._exit(3)
+        if world == 1 and not args.no_train and not args.no_train_files:
+            try:
+                out["train_fresh_batch"] = train_fresh_batch_bench(cfg, models, rm, int(cfg.TRAIN.BATCH_PAIRS) if args.batch_pairs is None else B, dev)
+            except Exception as e:
+                out["train_fresh_batch"] = {"error": "{}: {}".format(type(e).__name__, e)}
+        if rank == 0 and world == 1 and not args.no_cpu_baseline:
+            out["cpu_baseline"] = cpu_baseline(cfg, params, models, batch, args.cpu_pairs)
+        if rank == 0 and world == 1 and args.parity_pairs > 0:
+            # the metric's second clause ("ADD(-S) vs reference"), checker leg: never inside the timed region
+            trained = args.head_epochs > 0
+            out["parity"] = parity_leg(cfg, params, models, batch, poses_hip, se3_hip, min(args.parity_pairs, B), trained)
+            finals = getattr(cpu_baseline, "final_poses", None)
+            if finals is not None:
+                # the cpu_baseline leg refined the batch's pairs free-running (cyclically, if its sample is larger than the batch): ADD of
+                # the HIP loop's final poses against the oracle's
+                from oracle import pose_error
+
+                adds = []
+                for b in range(min(args.cpu_pairs, B)):
+                    pts = models[int(batch["class_index"][b])][0].astype(np.float64)
+                    ph, po = poses_hip[-1, b].astype(np.float64), finals[b]
+                    adds.append(pose_error.add(ph[:, :3], ph[:, 3], po[:, :3], po[:, 3], pts) / float(np.linalg.norm(pts.max(0) - pts.min(0))))
+                out["parity"]["add_free_over_d_cpu_baseline_pairs"] = {"pairs": int(min(args.cpu_pairs, B)), "max": float(max(adds)), "median": float(np.median(adds)),
+                                                                      "within_0.02": int(sum(a < 0.02 for a in adds))}
+                if trained:
+                    out["parity"]["ok"] = bool(out["parity"]["ok"] and max(adds) < 0.02)
+            parity_failed = not out["parity"]["ok"]
     if rank == 0:
         print(json.dumps(out))
     if dist is not None:

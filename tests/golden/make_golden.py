@@ -302,6 +302,40 @@ def epe_vectors():
     np.savez_compressed(os.path.join(HERE, "epe_golden.npz"), pred=np.array(preds), out=np.array(outs, dtype=np.float64))
 
 
+def flow_cpp_vectors():
+    """The reference's compiled CPU flow kernel (lib/flow_c/cpu_flow_kernel.cpp, built into oracle/_ref by oracle/ref_build.py) on the
+    six pairs of flow_golden.npz, one pair per call: its float32 outputs, so that tests/test_oracle_ref.py needs neither the library
+    nor the reference's sources."""
+    sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
+    from oracle import ref_build, se3 as ose3
+
+    g = np.load(os.path.join(HERE, "flow_golden.npz"))
+    Kf = g["K"].astype(np.float32)
+    Kinv = np.linalg.inv(Kf).astype(np.float32)
+    flows = []
+    for i in range(len(g["depth_src"])):
+        R, t = ose3.calc_se3(g["pose_src"][i], g["pose_tgt"][i])
+        KT = np.dot(Kf, np.concatenate([R, t.reshape(3, 1)], axis=1)).astype(np.float32)
+        flows.append(ref_build.flow_cpp(g["depth_src"][i].astype(np.float32), g["depth_tgt"][i].astype(np.float32), KT, Kinv))
+    np.savez_compressed(os.path.join(HERE, "flow_cpp_golden.npz"), flow=np.array(flows, dtype=np.float32))
+
+
+def cfg_files():
+    """The reference's experiment YAML files (settings only) -> cfgs/ next to this file: tests/test_config.py and
+    tests/test_config0_plumbing.py load them through update_config."""
+    import shutil
+
+    sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
+    from oracle import ref_build
+
+    src = os.path.join(os.path.dirname(os.path.dirname(ref_build.REF_DIR)), "experiments", "deepim", "cfgs")
+    dst = os.path.join(HERE, "cfgs")
+    os.makedirs(dst, exist_ok=True)
+    for f in sorted(os.listdir(src)):
+        if f.endswith(".yaml"):
+            shutil.copyfile(os.path.join(src, f), os.path.join(dst, f))
+
+
 if __name__ == "__main__":
     if "--epe-only" in sys.argv:
         epe_vectors()
@@ -315,6 +349,12 @@ if __name__ == "__main__":
     if "--callback-only" in sys.argv:
         callback_vectors()
         sys.exit(0)
+    if "--flow-cpp-only" in sys.argv:
+        flow_cpp_vectors()
+        sys.exit(0)
+    if "--cfgs-only" in sys.argv:
+        cfg_files()
+        sys.exit(0)
     se3_vectors()
     se3_euler_vectors()
     flow_vectors()
@@ -323,6 +363,8 @@ if __name__ == "__main__":
     data_layer_vectors()
     callback_vectors()
     epe_vectors()
+    flow_cpp_vectors()
+    cfg_files()
     for f in sorted(os.listdir(HERE)):
         if f.endswith(".npz"):
             print(f, os.path.getsize(os.path.join(HERE, f)))

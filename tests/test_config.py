@@ -32,13 +32,16 @@ def test_unknown_top_level_key_raises(tmp_path):
     reset_config()
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference"), reason="reference YAMLs only exist in the build container")
-def test_reference_yaml_files_load():
-    for f in sorted(glob.glob("/root/reference/experiments/deepim/cfgs/*LM_SIXD*.yaml")):
+def test_reference_yaml_files_load(golden_dir):
+    # the reference's own experiment YAMLs, stored as fixtures (tests/golden/make_golden.py:cfg_files)
+    lm = sorted(glob.glob(os.path.join(golden_dir, "cfgs", "*LM_SIXD*.yaml")))
+    mn = sorted(glob.glob(os.path.join(golden_dir, "cfgs", "*ModelNet*.yaml")))
+    assert len(lm) == 3 and len(mn) == 2
+    for f in lm:
         reset_config()
         update_config(f)
         assert config.symbol == "deepIM_flownet" and config.network.INPUT_MASK and config.TEST.test_iter == 4
-    for f in sorted(glob.glob("/root/reference/experiments/deepim/cfgs/*ModelNet*.yaml")):
+    for f in mn:
         reset_config()
         with pytest.raises(ValueError):  # stale top-level NUM_GPUS key: raises in the reference too
             update_config(f)

@@ -9,8 +9,7 @@ from oracle import flownet as oflow, refine as orefine
 from scene import make_scene
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SHIPPED = "/root/reference/experiments/deepim/cfgs/deepim_flownet_LM_SIXD_v1_ape_RFMx4_8epoch.yaml"
-OURS = os.path.join(ROOT, "mx-deepim_amd", "experiments", "deepim", "cfgs", "deepim_hip_LM_ape_test.yaml")
+SHIPPED = os.path.join(ROOT, "tests", "golden", "cfgs", "deepim_flownet_LM_SIXD_v1_ape_RFMx4_8epoch.yaml")   # make_golden.py:cfg_files
 
 
 def test_single_pair_one_iteration_cpu():
@@ -18,7 +17,7 @@ def test_single_pair_one_iteration_cpu():
     from deepim.symbols.deepIM_flownet import deepIM_flownet, input_channels
 
     reset_config()
-    update_config(SHIPPED if os.path.exists(SHIPPED) else OURS)   # the reference's own YAML when it is present (build container)
+    update_config(SHIPPED)   # the reference's own YAML
     assert config.symbol == "deepIM_flownet" and config.dataset.class_name == ["ape"] and int(config.TEST.test_iter) == 4
     assert config.network.INPUT_MASK and config.network.PRED_MASK and config.network.PRED_FLOW and config.network.ROT_COORD == "CAMERA"
     assert input_channels(config) == 8

@@ -105,7 +105,7 @@ def test_bench_gpus_2_one_command_two_ranks_on_one_card(hip_lib):
     import json
 
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dist-backend", "gloo", "--steps", "3", "--warmup", "1",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--dist-backend", "gloo", "--steps", "3", "--warmup", "1",
                         "--train-steps", "1", "--profile-steps", "1"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
                        universal_newlines=True, timeout=1200)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
@@ -131,7 +131,7 @@ def test_bench_gpus_2_one_command_two_ranks_on_one_card(hip_lib):
 def test_bench_line_names_the_arithmetic_and_times_the_f32_pipe_beside_it(hip_lib):
     """one rank, short run: the dominant kernel is a three-term kernel priced against the bf16 peak / 6, the same loop on the f32 pipe
     is timed in the same process, both arithmetics give the same first step to f32 rounding, and the parity object is green"""
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "5", "--warmup", "2", "--head-epochs", "0", "--no-train",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "5", "--warmup", "2", "--head-epochs", "0", "--no-train",
                         "--no-train-files", "--no-fresh-batch", "--cpu-pairs", "2", "--parity-pairs", "2", "--profile-steps", "1"],
                        capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
@@ -144,3 +144,34 @@ def test_bench_line_names_the_arithmetic_and_times_the_f32_pipe_beside_it(hip_li
     assert "error" not in f32 and f32["value"] > 0 and out["value"] > f32["value"]          # the three-term arithmetic is the faster one
     assert f32["first_iteration_se3_max_abs_diff_to_headline"] < 1e-4                         # ... and the same one, to f32 rounding
     assert out["parity"]["ok"] and out["parity"]["max_step_err"] <= out["parity"]["step_err_bar"]
+
+
+def test_bench_plain_run_times_its_steps_and_dumps_the_same_outputs_twice(hip_lib, tmp_path):
+    """a plain run (no --full) is the headline alone: --steps timed steps, ms_per_step consistent with the value, none of the
+    non-headline objects; --dump-outputs writes the refiner's outputs of the last timed step, and a second run with the same arguments
+    (seeded inputs) writes the same arrays"""
+    import numpy as np
+
+    dumps = []
+    for k in range(2):
+        d = str(tmp_path / "out{}".format(k))
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--head-epochs", "0",
+                            "--dump-outputs", d], capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:]
+        out = json.loads(lines[0])
+        assert out["metric"] == "pose-refinements/sec (4 iters, 480x640)" and out["unit"] == "pose-refinements/sec"
+        assert out["higher_is_better"] is True and out["dtype"] == "f32" and out["steps"] == 3 and out["warmup"] == 1
+        B = out["config"]["pairs_per_gpu"]
+        assert out["ms_per_step"] > 0 and out["value"] == pytest.approx(B * 1e3 / out["ms_per_step"], rel=1e-3)
+        for key in ("roofline", "pose_error_vs_gt", "f32_pipe", "fresh_batch", "full_graph", "modelnet_lit", "train", "train_fresh_batch",
+                    "cpu_baseline", "parity"):
+            assert key not in out, key
+        arrs = {n: np.load(os.path.join(d, n + ".npy")) for n in ("poses_iter", "se3_iter", "status_iter")}
+        assert arrs["poses_iter"].shape == (4, B, 3, 4) and arrs["se3_iter"].shape == (4, B, 7) and arrs["status_iter"].shape == (4, B)
+        assert arrs["poses_iter"].dtype == np.float32 and arrs["se3_iter"].dtype == np.float32 and arrs["status_iter"].dtype == np.float64
+        assert np.isfinite(arrs["poses_iter"]).all() and np.isfinite(arrs["se3_iter"]).all()
+        dumps.append(arrs)
+    for n in dumps[0]:
+        np.testing.assert_array_equal(dumps[0][n], dumps[1][n], err_msg=n)

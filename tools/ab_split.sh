@@ -1,5 +1,5 @@
 mkdir -p gpurun_out/r4
-F="--no-train --no-train-files --no-variants --no-fresh-batch --no-cpu-baseline --parity-pairs 4 --head-epochs 0 --steps 40 --warmup 5"
+F="--full --no-train --no-train-files --no-variants --no-fresh-batch --no-cpu-baseline --parity-pairs 4 --head-epochs 0 --steps 40 --warmup 5"
 for w in 1 0 1 0; do
   DIM_WINO_SPLIT=$w python bench.py $F 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('split=$w', d['value'], d['ms_per_step'], d['roofline']['achieved'], d.get('parity'))"
 done > gpurun_out/r4/ab_split.log 2>&1
