@@ -38,6 +38,7 @@ extern "C" {
 #define DIM_STATUS_REN_BOX_EMPTY 2 /* dim_zoom_factor: rendered box empty */
 #define DIM_STATUS_BAD_CLASS 4     /* dim_raster_render*: class_index outside [0, n_classes): sample rendered as background */
 #define DIM_STATUS_BAD_FACE 8      /* dim_raster_render*: a z-buffer key named a face outside the mesh (pixel left black) */
+#define DIM_STATUS_BAD_K 16        /* dim_raster_render_k: the sample's K has fx <= 0, fy <= 0 or a non-finite entry (rendered as background) */
 
 const char* dim_last_error(void);
 /* library / device probe: fills name (<= n bytes), returns number of compute units or <0 */
@@ -213,6 +214,19 @@ int dim_raster_render_dirty(const float* verts, const float* normals, const floa
                             const float* light_pos, const float* light_int, float brightness_ratio, const float* plane_means3,
                             float mask_thr, void* workspace, float* image, float* depth, float* mask, float* bgr, int* bbox, int* status,
                             const int* clean_bbox, void* stream);
+/* dim_raster_render_dirty with one camera per sample.  The reference's test loop starts from K = config.dataset.INTRINSIC_MATRIX
+ * (deepim/core/tester.py:165) and, before every re-render, replaces it with np.loadtxt(image_observed[:-10] + "-K.txt") when that
+ * file exists (:560-562), passing it to render(..., K=K).  K_per_sample: device (B,9) f32, row-major 3x3 per sample; sample b projects
+ * with its fx = K[0], fy = K[4], cx = K[2], cy = K[5].  NULL = K9 for every sample (then this is dim_raster_render_dirty, same kernels,
+ * same arguments); K9 is required either way.  A sample rendered in a batch is bit-identical to the same sample rendered alone with
+ * K9 = its row.  A row with fx <= 0, fy <= 0 or a non-finite entry renders that sample as background and ORs DIM_STATUS_BAD_K into
+ * status[b]; the other samples are unaffected. */
+int dim_raster_render_k(const float* verts, const float* normals, const float* uvs, const int* faces, const int* mesh_table, int n_classes,
+                        int vmax, int fmax, const unsigned char* textures, const int* tex_table, const int* class_index, const float* poses,
+                        const float* K9, int B, int H, int W, float znear, float zfar, int tex_bilinear, const float* light_pos,
+                        const float* light_int, float brightness_ratio, const float* plane_means3, float mask_thr, void* workspace,
+                        float* image, float* depth, float* mask, float* bgr, int* bbox, int* status, const int* clean_bbox,
+                        const float* K_per_sample, void* stream);
 
 /* deepim/core/tester.py:204-225 (and batch_updater_py_multi.py:233-255): light_pos[b] = 0.5*(dx,dy,dz) + (tx,-ty,-tz) of poses[b]. */
 int dim_modelnet_light_position(const float* poses, float dx, float dy, float dz, float* light_pos, int B, void* stream);
@@ -525,6 +539,13 @@ int dim_refiner_create(dim_refiner** out, const dim_refiner_desc* desc, const ch
 int dim_refiner_run(dim_refiner* r, const float* image_observed, const float* image_rendered, const float* mask_observed,
                     const float* mask_rendered, const float* src_pose, const int* class_index, float* poses_iter, float* se3_iter,
                     int* status_iter, void* stream);
+/* dim_refiner_run with one camera per pair (deepim/core/tester.py:165, :560-562: each re-render uses the pair's -K.txt when the
+ * dataset ships one).  K_per_pair: device (B,9) f32, row-major; NULL = the desc's K9 (then this is dim_refiner_run).  As in the
+ * reference, only the re-render reads it: ZoomMask / dim_zoom_factor keep desc.K9 (the reference's op attribute).  The array is read
+ * when the kernels run, so a captured graph replayed after new values are written there renders with the new cameras. */
+int dim_refiner_run_k(dim_refiner* r, const float* image_observed, const float* image_rendered, const float* mask_observed,
+                      const float* mask_rendered, const float* src_pose, const int* class_index, float* poses_iter, float* se3_iter,
+                      int* status_iter, const float* K_per_pair, void* stream);
 int dim_refiner_destroy(dim_refiner* r);
 
 #ifdef __cplusplus

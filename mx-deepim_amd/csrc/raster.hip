@@ -81,20 +81,33 @@ __device__ __forceinline__ bool zbuf_known_clear(const ResolveHdr* hdr, int B, i
   return hdr->magic0 == kZbMagic0 && hdr->magic1 == kZbMagic1 && hdr->B == B && hdr->H == H && hdr->W == W && hdr->vmax == vmax;
 }
 
+// Per-sample intrinsics (dim_raster_render_k, deepim/core/tester.py:560-562 of the reference: each pair re-rendered with its own
+// `-K.txt`): K_per_sample (B,9) f32 row-major on the device.  The PERK = false instantiation of every pass below is the code of the
+// uniform render (fx, fy, cx, cy kernel scalars); PERK = true reads sample b's four values once per workgroup (b = blockIdx.y) in the
+// vertex and triangle passes, and per shaded pixel of a near-clipped face in the resolve.  A sample whose K is unusable (fx <= 0,
+// fy <= 0 or any entry not finite) renders as background and ORs DIM_STATUS_BAD_K into its status word.
+__device__ __forceinline__ bool k_usable(const float* __restrict__ k) {
+  bool ok = k[0] > 0.f && k[4] > 0.f;
+#pragma unroll
+  for (int j = 0; j < 9; ++j) ok = ok && isfinite(k[j]);
+  return ok;
+}
+
 // scr[b][i] = (u, v, Zc) for vertex i of the sample's mesh
-__global__ __launch_bounds__(256) void raster_vertex_kernel(const float* __restrict__ verts, const int* __restrict__ mesh_table,
-                                                            const int* __restrict__ class_index, const float* __restrict__ poses,
-                                                            float fx, float fy, float cx, float cy, int vmax, int n_classes,
-                                                            int* __restrict__ status, float* __restrict__ scr, ResolveHdr* __restrict__ hdr,
-                                                            unsigned long long* __restrict__ zbuf, int B, int H, int W, int* __restrict__ bbox,
-                                                            int wide) {
+template <bool PERK>
+__device__ __forceinline__ void raster_vertex_body(const unsigned bdim, const float* __restrict__ verts, const int* __restrict__ mesh_table,
+                                                   const int* __restrict__ class_index, const float* __restrict__ poses, float fx, float fy,
+                                                   float cx, float cy, const float* __restrict__ K_per_sample, int vmax, int n_classes,
+                                                   int* __restrict__ status, float* __restrict__ scr, ResolveHdr* __restrict__ hdr,
+                                                   unsigned long long* __restrict__ zbuf, int B, int H, int W, int* __restrict__ bbox,
+                                                   int wide) {
   const int b = blockIdx.y;
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  const int i = blockIdx.x * bdim + threadIdx.x;
   // ---- what the separate clear / init launches did.  (The header is only READ here -- every block must see the same answer; the
   // triangle pass, which runs when all of these blocks are done, stamps it.)
   if (!zbuf_known_clear(hdr, B, H, W, vmax)) {
-    const long n = (long)B * H * W, stride = (long)gridDim.x * gridDim.y * blockDim.x;
-    const long k0 = ((long)blockIdx.y * gridDim.x + blockIdx.x) * blockDim.x + threadIdx.x;
+    const long n = (long)B * H * W, stride = (long)gridDim.x * gridDim.y * bdim;
+    const long k0 = ((long)blockIdx.y * gridDim.x + blockIdx.x) * bdim + threadIdx.x;
     if (wide) {   // 16-byte stores (the workspace is 16-byte aligned, B H W even)
       ulonglong2* z2 = reinterpret_cast<ulonglong2*>(zbuf);
       for (long k = k0; k < n / 2; k += stride) z2[k] = make_ulonglong2(0xFFFFFFFFFFFFFFFFull, 0xFFFFFFFFFFFFFFFFull);
@@ -111,6 +124,14 @@ __global__ __launch_bounds__(256) void raster_vertex_kernel(const float* __restr
     if (i == 0 && status) atomicOr(status + b, DIM_STATUS_BAD_CLASS);
     return;
   }
+  if (PERK) {
+    const float* k = K_per_sample + 9 * b;
+    if (!k_usable(k)) {   // no projection: background, like a bad class (the triangle pass makes the same test and draws nothing)
+      if (i == 0 && status) atomicOr(status + b, DIM_STATUS_BAD_K);
+      return;
+    }
+    fx = k[0]; fy = k[4]; cx = k[2]; cy = k[5];
+  }
   const int* mt = mesh_table + 4 * cls;
   if (i >= mt[1]) return;
   const float* p = verts + 3 * (long)(mt[0] + i);
@@ -122,6 +143,26 @@ __global__ __launch_bounds__(256) void raster_vertex_kernel(const float* __restr
   s[0] = __fmaf_rn(fx, __fdiv_rn(xc, zc), cx);
   s[1] = __fmaf_rn(fy, __fdiv_rn(yc, zc), cy);
   s[2] = zc;
+}
+
+__global__ __launch_bounds__(256) void raster_vertex_kernel(const float* __restrict__ verts, const int* __restrict__ mesh_table,
+                                                            const int* __restrict__ class_index, const float* __restrict__ poses,
+                                                            float fx, float fy, float cx, float cy, int vmax, int n_classes,
+                                                            int* __restrict__ status, float* __restrict__ scr, ResolveHdr* __restrict__ hdr,
+                                                            unsigned long long* __restrict__ zbuf, int B, int H, int W, int* __restrict__ bbox,
+                                                            int wide) {
+  raster_vertex_body<false>(blockDim.x, verts, mesh_table, class_index, poses, fx, fy, cx, cy, nullptr, vmax, n_classes, status, scr, hdr,
+                            zbuf, B, H, W, bbox, wide);
+}
+
+__global__ __launch_bounds__(256) void raster_vertex_k_kernel(const float* __restrict__ verts, const int* __restrict__ mesh_table,
+                                                              const int* __restrict__ class_index, const float* __restrict__ poses,
+                                                              const float* __restrict__ K_per_sample, int vmax, int n_classes,
+                                                              int* __restrict__ status, float* __restrict__ scr, ResolveHdr* __restrict__ hdr,
+                                                              unsigned long long* __restrict__ zbuf, int B, int H, int W,
+                                                              int* __restrict__ bbox, int wide) {
+  raster_vertex_body<true>(blockDim.x, verts, mesh_table, class_index, poses, 0.f, 0.f, 0.f, 0.f, K_per_sample, vmax, n_classes, status,
+                           scr, hdr, zbuf, B, H, W, bbox, wide);
 }
 
 __device__ inline bool load_tri(const float* scr_b, const int* face, int X[3], int Y[3], float iz[3]) {
@@ -224,19 +265,25 @@ __device__ inline void raster_one(const int X[3], const int Y[3], const float iz
     }
 }
 
-__global__ __launch_bounds__(256) void raster_tri_kernel(const int* __restrict__ faces, const int* __restrict__ mesh_table,
-                                                         const int* __restrict__ class_index, const float* __restrict__ scr,
-                                                         const float* __restrict__ verts, const float* __restrict__ poses, float fx,
-                                                         float fy, float cx, float cy, int vmax, int H, int W, float znear, float zfar,
-                                                         int n_classes, unsigned long long* __restrict__ zbuf, ResolveHdr* __restrict__ hdr,
-                                                         int B) {
+template <bool PERK>
+__device__ __forceinline__ void raster_tri_body(const unsigned bdim, const int* __restrict__ faces, const int* __restrict__ mesh_table,
+                                                const int* __restrict__ class_index, const float* __restrict__ scr,
+                                                const float* __restrict__ verts, const float* __restrict__ poses, float fx, float fy, float cx,
+                                                float cy, const float* __restrict__ K_per_sample, int vmax, int H, int W, float znear,
+                                                float zfar, int n_classes, unsigned long long* __restrict__ zbuf, ResolveHdr* __restrict__ hdr,
+                                                int B) {
   const int b = blockIdx.y;
-  const int f = blockIdx.x * blockDim.x + threadIdx.x;
+  const int f = blockIdx.x * bdim + threadIdx.x;
   if (b == 0 && f == 0) {   // the z-buffer was clear when this pass started; the resolve passes of this render restore that
     hdr->magic0 = kZbMagic0; hdr->magic1 = kZbMagic1; hdr->B = B; hdr->H = H; hdr->W = W; hdr->vmax = vmax;
   }
   const int cls = class_index[b];
   if ((unsigned)cls >= (unsigned)n_classes) return;
+  if (PERK) {
+    const float* k = K_per_sample + 9 * b;
+    if (!k_usable(k)) return;   // the vertex pass flagged it and wrote no projected vertex
+    fx = k[0]; fy = k[4]; cx = k[2]; cy = k[5];
+  }
   const int* mt = mesh_table + 4 * cls;
   if (f >= mt[3]) return;
   const int* face = faces + 3 * (long)(mt[2] + f);
@@ -276,6 +323,26 @@ __global__ __launch_bounds__(256) void raster_tri_kernel(const int* __restrict__
   raster_one(X, Y, iz, f, H, W, znear, zfar, false, zc, zb);
 }
 
+__global__ __launch_bounds__(256) void raster_tri_kernel(const int* __restrict__ faces, const int* __restrict__ mesh_table,
+                                                         const int* __restrict__ class_index, const float* __restrict__ scr,
+                                                         const float* __restrict__ verts, const float* __restrict__ poses, float fx,
+                                                         float fy, float cx, float cy, int vmax, int H, int W, float znear, float zfar,
+                                                         int n_classes, unsigned long long* __restrict__ zbuf, ResolveHdr* __restrict__ hdr,
+                                                         int B) {
+  raster_tri_body<false>(blockDim.x, faces, mesh_table, class_index, scr, verts, poses, fx, fy, cx, cy, nullptr, vmax, H, W, znear, zfar,
+                         n_classes, zbuf, hdr, B);
+}
+
+__global__ __launch_bounds__(256) void raster_tri_k_kernel(const int* __restrict__ faces, const int* __restrict__ mesh_table,
+                                                           const int* __restrict__ class_index, const float* __restrict__ scr,
+                                                           const float* __restrict__ verts, const float* __restrict__ poses,
+                                                           const float* __restrict__ K_per_sample, int vmax, int H, int W, float znear,
+                                                           float zfar, int n_classes, unsigned long long* __restrict__ zbuf,
+                                                           ResolveHdr* __restrict__ hdr, int B) {
+  raster_tri_body<true>(blockDim.x, faces, mesh_table, class_index, scr, verts, poses, 0.f, 0.f, 0.f, 0.f, K_per_sample, vmax, H, W, znear,
+                        zfar, n_classes, zbuf, hdr, B);
+}
+
 __device__ inline int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 // One thread per pixel.  Outputs (any may be null):
@@ -297,8 +364,9 @@ struct LitArgs {
 
 // Colour of pixel (x, y) of sample b whose z-buffer key names face f (the heavy path: exact edge functions again, perspective-correct
 // barycentrics, three dependent gathers, texel fetch, optional Lambert term).  Returns false for a face id outside the mesh.
-template <bool LIT>
-__device__ __forceinline__ bool shade_pixel(const LitArgs& lit, const float* __restrict__ uvs, const int* __restrict__ faces,
+template <bool LIT, bool PERK>
+__device__ __forceinline__ bool shade_pixel(const LitArgs& lit, const float* __restrict__ K_per_sample, const float* __restrict__ uvs,
+                                            const int* __restrict__ faces,
                                             const int* __restrict__ mesh_table, const unsigned char* __restrict__ tex,
                                             const int* __restrict__ tex_table, int cls, const float* __restrict__ scr_b, int b, int x, int y,
                                             unsigned f_id, float z_key, int tex_bilinear, float& r, float& g, float& bl) {
@@ -321,7 +389,12 @@ __device__ __forceinline__ bool shade_pixel(const LitArgs& lit, const float* __r
     float cam[3][3], wb[3];
 #pragma unroll
     for (int k = 0; k < 3; ++k) cam_point(lit.poses + 12 * b, lit.verts + 3 * (long)(mt[0] + face[k]), cam[k]);
-    cam_bary(cam, x, y, z_key, lit.fx, lit.fy, lit.cx, lit.cy, wb);
+    if (PERK) {
+      const float* k = K_per_sample + 9 * b;
+      cam_bary(cam, x, y, z_key, k[0], k[4], k[2], k[5], wb);
+    } else {
+      cam_bary(cam, x, y, z_key, lit.fx, lit.fy, lit.cx, lit.cy, wb);
+    }
     w0 = wb[0]; w1 = wb[1]; w2 = wb[2]; z = 1.0f;
   } else {
     load_tri(scr_b, face, X, Y, iz);
@@ -539,21 +612,21 @@ __device__ __forceinline__ void raster_bbox_reduce(const int4* __restrict__ wave
 //   * the first B blocks fold the wave extents of the stream pass into bbox[b] (was a launch of its own);
 //   * EVERY listed key is reset to "clear" by the thread that consumed it, so the z-buffer is clear again when the render ends and the
 //     next one needs no clear pass (ResolveHdr).
-template <bool LIT, bool SHADE>
-__global__ __launch_bounds__(256) void raster_resolve_shade_kernel(LitArgs lit, const float* __restrict__ uvs, const int* __restrict__ faces,
-                                                                   const int* __restrict__ mesh_table,
-                                                                   const unsigned char* __restrict__ tex, const int* __restrict__ tex_table,
-                                                                   const int* __restrict__ class_index, const float* __restrict__ scr,
-                                                                   unsigned long long* __restrict__ zbuf, int vmax, int H, int W,
-                                                                   int tex_bilinear, float pm0, float pm1, float pm2,
-                                                                   float* __restrict__ image, float* __restrict__ bgr,
-                                                                   int* __restrict__ status, const ResolveHdr* __restrict__ hdr,
-                                                                   const unsigned* __restrict__ list, const int4* __restrict__ wave_ext,
-                                                                   int waves_per_sample, int B, int* __restrict__ bbox) {
+template <bool LIT, bool SHADE, bool PERK>
+__device__ __forceinline__ void raster_resolve_shade_body(const unsigned bdim, const LitArgs& lit, const float* __restrict__ K_per_sample,
+                                                          const float* __restrict__ uvs, const int* __restrict__ faces,
+                                                          const int* __restrict__ mesh_table, const unsigned char* __restrict__ tex,
+                                                          const int* __restrict__ tex_table, const int* __restrict__ class_index,
+                                                          const float* __restrict__ scr, unsigned long long* __restrict__ zbuf, int vmax,
+                                                          int H, int W, int tex_bilinear, float pm0, float pm1, float pm2,
+                                                          float* __restrict__ image, float* __restrict__ bgr, int* __restrict__ status,
+                                                          const ResolveHdr* __restrict__ hdr, const unsigned* __restrict__ list,
+                                                          const int4* __restrict__ wave_ext, int waves_per_sample, int B,
+                                                          int* __restrict__ bbox) {
   if (bbox && (int)blockIdx.x < B) raster_bbox_reduce(wave_ext, waves_per_sample, H, W, bbox, (int)blockIdx.x);
   const unsigned n = hdr->count;
   const unsigned plane = (unsigned)(H * W);
-  for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+  for (unsigned i = blockIdx.x * bdim + threadIdx.x; i < n; i += gridDim.x * bdim) {
     const unsigned e = list[i];
     const unsigned long long key = zbuf[e];
     zbuf[e] = 0xFFFFFFFFFFFFFFFFull;
@@ -564,8 +637,8 @@ __global__ __launch_bounds__(256) void raster_resolve_shade_kernel(LitArgs lit, 
     const float z = __uint_as_float((unsigned)(key >> 32));
     float r = 0.f, g = 0.f, bl = 0.f;
     // (class_index was range-checked by the vertex pass: a sample with a bad class has no covered pixel)
-    const bool ok = shade_pixel<LIT>(lit, uvs, faces, mesh_table, tex, tex_table, class_index[b], scr + (long)b * vmax * 3, b, x, y,
-                                     (unsigned)(key & 0xFFFFFFFFu), z, tex_bilinear, r, g, bl);
+    const bool ok = shade_pixel<LIT, PERK>(lit, K_per_sample, uvs, faces, mesh_table, tex, tex_table, class_index[b], scr + (long)b * vmax * 3,
+                                           b, x, y, (unsigned)(key & 0xFFFFFFFFu), z, tex_bilinear, r, g, bl);
     if (!ok && status) atomicOr(status + b, DIM_STATUS_BAD_FACE);  // a corrupt key: the pixel keeps z but is coloured black, loudly
     if (image) {
       float* im = image + (long)b * 3 * plane + pix;
@@ -580,19 +653,46 @@ __global__ __launch_bounds__(256) void raster_resolve_shade_kernel(LitArgs lit, 
   }
 }
 
-// One-pass resolve (one thread per pixel): kept for image widths that are not a multiple of 4.
+template <bool LIT, bool SHADE>
+__global__ __launch_bounds__(256) void raster_resolve_shade_kernel(LitArgs lit, const float* __restrict__ uvs,
+                             const int* __restrict__ faces, const int* __restrict__ mesh_table, const unsigned char* __restrict__ tex,
+                             const int* __restrict__ tex_table, const int* __restrict__ class_index, const float* __restrict__ scr,
+                             unsigned long long* __restrict__ zbuf, int vmax, int H, int W, int tex_bilinear, float pm0, float pm1,
+                             float pm2, float* __restrict__ image, float* __restrict__ bgr, int* __restrict__ status,
+                             const ResolveHdr* __restrict__ hdr, const unsigned* __restrict__ list, const int4* __restrict__ wave_ext,
+                             int waves_per_sample, int B, int* __restrict__ bbox) {
+  raster_resolve_shade_body<LIT, SHADE, false>(blockDim.x, lit, nullptr, uvs, faces, mesh_table, tex, tex_table, class_index, scr, zbuf,
+                                               vmax, H, W, tex_bilinear, pm0, pm1, pm2, image, bgr, status, hdr, list, wave_ext,
+                                               waves_per_sample, B, bbox);
+}
+
+// the same with per-sample intrinsics (only a shading launch reads them: near-clipped faces)
 template <bool LIT>
-__global__ __launch_bounds__(256) void raster_resolve_kernel(LitArgs lit, const float* __restrict__ uvs, const int* __restrict__ faces,
-                                                             const int* __restrict__ mesh_table, const unsigned char* __restrict__ tex,
-                                                             const int* __restrict__ tex_table, const int* __restrict__ class_index,
-                                                             const float* __restrict__ scr, unsigned long long* __restrict__ zbuf,
-                                                             int vmax, int H, int W, int tex_bilinear, float pm0, float pm1, float pm2,
-                                                             float mask_thr, float* __restrict__ image, float* __restrict__ depth,
-                                                             float* __restrict__ mask, float* __restrict__ bgr, int* __restrict__ bbox,
-                                                             int* __restrict__ status) {
+__global__ __launch_bounds__(256) void raster_resolve_shade_k_kernel(LitArgs lit, const float* __restrict__ K_per_sample,
+                             const float* __restrict__ uvs, const int* __restrict__ faces, const int* __restrict__ mesh_table,
+                             const unsigned char* __restrict__ tex, const int* __restrict__ tex_table, const int* __restrict__ class_index,
+                             const float* __restrict__ scr, unsigned long long* __restrict__ zbuf, int vmax, int H, int W, int tex_bilinear,
+                             float pm0, float pm1, float pm2, float* __restrict__ image, float* __restrict__ bgr, int* __restrict__ status,
+                             const ResolveHdr* __restrict__ hdr, const unsigned* __restrict__ list, const int4* __restrict__ wave_ext,
+                             int waves_per_sample, int B, int* __restrict__ bbox) {
+  raster_resolve_shade_body<LIT, true, true>(blockDim.x, lit, K_per_sample, uvs, faces, mesh_table, tex, tex_table, class_index, scr, zbuf,
+                                             vmax, H, W, tex_bilinear, pm0, pm1, pm2, image, bgr, status, hdr, list, wave_ext,
+                                             waves_per_sample, B, bbox);
+}
+
+// One-pass resolve (one thread per pixel): kept for image widths that are not a multiple of 4.
+template <bool LIT, bool PERK>
+__device__ __forceinline__ void raster_resolve_body(const unsigned bdim, const LitArgs& lit, const float* __restrict__ K_per_sample,
+                                                    const float* __restrict__ uvs, const int* __restrict__ faces,
+                                                    const int* __restrict__ mesh_table, const unsigned char* __restrict__ tex,
+                                                    const int* __restrict__ tex_table, const int* __restrict__ class_index,
+                                                    const float* __restrict__ scr, unsigned long long* __restrict__ zbuf, int vmax, int H,
+                                                    int W, int tex_bilinear, float pm0, float pm1, float pm2, float mask_thr,
+                                                    float* __restrict__ image, float* __restrict__ depth, float* __restrict__ mask,
+                                                    float* __restrict__ bgr, int* __restrict__ bbox, int* __restrict__ status) {
   const int b = blockIdx.z;
   const int y = blockIdx.y;
-  const int x = blockIdx.x * blockDim.x + threadIdx.x;
+  const int x = blockIdx.x * bdim + threadIdx.x;
   const long plane = (long)H * W;
   float r = 0.f, g = 0.f, bl = 0.f, z = 0.f;
   bool in_img = x < W;
@@ -601,8 +701,8 @@ __global__ __launch_bounds__(256) void raster_resolve_kernel(LitArgs lit, const 
     if (key != 0xFFFFFFFFFFFFFFFFull) {
       zbuf[(long)b * plane + (long)y * W + x] = 0xFFFFFFFFFFFFFFFFull;   // leave the z-buffer clear (ResolveHdr)
       z = __uint_as_float((unsigned)(key >> 32));
-      const bool ok = shade_pixel<LIT>(lit, uvs, faces, mesh_table, tex, tex_table, class_index[b], scr + (long)b * vmax * 3, b, x, y,
-                                       (unsigned)(key & 0xFFFFFFFFu), z, tex_bilinear, r, g, bl);
+      const bool ok = shade_pixel<LIT, PERK>(lit, K_per_sample, uvs, faces, mesh_table, tex, tex_table, class_index[b],
+                                             scr + (long)b * vmax * 3, b, x, y, (unsigned)(key & 0xFFFFFFFFu), z, tex_bilinear, r, g, bl);
       if (!ok && status) atomicOr(status + b, DIM_STATUS_BAD_FACE);
     }
     const long o = (long)y * W + x;
@@ -626,7 +726,7 @@ __global__ __launch_bounds__(256) void raster_resolve_kernel(LitArgs lit, const 
     if (ball) {
       const int lane = threadIdx.x & 63;
       if (lane == 0) {
-        int wave_x0 = blockIdx.x * blockDim.x + (threadIdx.x & ~63);
+        int wave_x0 = blockIdx.x * bdim + (threadIdx.x & ~63);
         int lo = __ffsll((long long)ball) - 1;
         int hi = 63 - __clzll((long long)ball);
         atomicMin(&bbox[4 * b + 0], wave_x0 + lo);
@@ -636,6 +736,28 @@ __global__ __launch_bounds__(256) void raster_resolve_kernel(LitArgs lit, const 
       }
     }
   }
+}
+
+template <bool LIT>
+__global__ __launch_bounds__(256) void raster_resolve_kernel(LitArgs lit, const float* __restrict__ uvs, const int* __restrict__ faces,
+                             const int* __restrict__ mesh_table, const unsigned char* __restrict__ tex, const int* __restrict__ tex_table,
+                             const int* __restrict__ class_index, const float* __restrict__ scr, unsigned long long* __restrict__ zbuf,
+                             int vmax, int H, int W, int tex_bilinear, float pm0, float pm1, float pm2, float mask_thr,
+                             float* __restrict__ image, float* __restrict__ depth, float* __restrict__ mask, float* __restrict__ bgr,
+                             int* __restrict__ bbox, int* __restrict__ status) {
+  raster_resolve_body<LIT, false>(blockDim.x, lit, nullptr, uvs, faces, mesh_table, tex, tex_table, class_index, scr, zbuf, vmax, H, W,
+                                  tex_bilinear, pm0, pm1, pm2, mask_thr, image, depth, mask, bgr, bbox, status);
+}
+
+template <bool LIT>
+__global__ __launch_bounds__(256) void raster_resolve_k_kernel(LitArgs lit, const float* __restrict__ K_per_sample,
+                             const float* __restrict__ uvs, const int* __restrict__ faces, const int* __restrict__ mesh_table,
+                             const unsigned char* __restrict__ tex, const int* __restrict__ tex_table, const int* __restrict__ class_index,
+                             const float* __restrict__ scr, unsigned long long* __restrict__ zbuf, int vmax, int H, int W, int tex_bilinear,
+                             float pm0, float pm1, float pm2, float mask_thr, float* __restrict__ image, float* __restrict__ depth,
+                             float* __restrict__ mask, float* __restrict__ bgr, int* __restrict__ bbox, int* __restrict__ status) {
+  raster_resolve_body<LIT, true>(blockDim.x, lit, K_per_sample, uvs, faces, mesh_table, tex, tex_table, class_index, scr, zbuf, vmax, H, W,
+                                 tex_bilinear, pm0, pm1, pm2, mask_thr, image, depth, mask, bgr, bbox, status);
 }
 
 // mask[b] = filled rectangle [y0:y1, x0:x1] (END-EXCLUSIVE: lib/pair_matching/data_pair.py:103-114)
@@ -695,7 +817,7 @@ static int raster_render_impl(const float* verts, const float* normals, const fl
                               const int* class_index, const float* poses, const float* K9, int B, int H, int W, float znear, float zfar,
                               int tex_bilinear, const float* light_pos, const float* light_int, float ratio, const float* plane_means3,
                               float mask_thr, void* workspace, float* image, float* depth, float* mask, float* bgr, int* bbox, int* status,
-                              const int* clean_bbox, void* stream) {
+                              const int* clean_bbox, const float* K_per_sample, void* stream) {
   if (B == 0) return DIM_OK;  // empty batch: nothing to do, pointers may be NULL
   DIM_REQUIRE(verts && uvs && faces && mesh_table && textures && tex_table && class_index && poses && K9 && workspace, "null pointer");
   DIM_REQUIRE(vmax > 0 && fmax > 0 && H > 0 && W > 0 && n_classes > 0, "bad sizes");
@@ -715,14 +837,23 @@ static int raster_render_impl(const float* verts, const float* normals, const fl
   // triangle pass and the last pass would leave a dirty z-buffer behind a header that calls it clear.)
   const bool two_pass = W % 4 == 0 && aligned16(workspace) && aligned16(image) && aligned16(depth) && aligned16(mask) && aligned16(bgr);
   DIM_REQUIRE(!clean_bbox || two_pass, "clean_bbox needs the two-pass resolve: W %% 4 == 0 and 16-byte aligned planes and workspace");
+  DIM_REQUIRE((reinterpret_cast<uintptr_t>(K_per_sample) & 3) == 0, "K_per_sample must be 4-byte aligned (B,9) f32");
+  const float* Kps = K_per_sample;   // NULL: every sample uses K9 (the uniform kernels, unchanged)
   // No clear pass and no init launch (round 4): the z-buffer is clear when a render ends (the pass that consumes a key resets it) and
   // the header in front of it says so; a header that does not match this call makes the vertex pass clear the z-buffer first.  (A
   // clear by hipMemsetAsync was never an option: inside a captured hipGraph the memset node was seen overlapping the resolve pass.)
-  hipLaunchKernelGGL(raster_vertex_kernel, dim3(ceil_div(vmax, 256), B), dim3(256), 0, st, verts, mesh_table, class_index, poses,
-                     K9[0], K9[4], K9[2], K9[5], vmax, n_classes, status, scr, hdr, zbuf, B, H, W, bbox,
-                     (int)(aligned16(workspace) && nkeys % 2 == 0));
-  hipLaunchKernelGGL(raster_tri_kernel, dim3(ceil_div(fmax, 256), B), dim3(256), 0, st, faces, mesh_table, class_index, scr, verts, poses,
-                     K9[0], K9[4], K9[2], K9[5], vmax, H, W, znear, zfar, n_classes, zbuf, hdr, B);
+  const int wide = (int)(aligned16(workspace) && nkeys % 2 == 0);
+  if (Kps) {
+    hipLaunchKernelGGL(raster_vertex_k_kernel, dim3(ceil_div(vmax, 256), B), dim3(256), 0, st, verts, mesh_table, class_index, poses, Kps,
+                       vmax, n_classes, status, scr, hdr, zbuf, B, H, W, bbox, wide);
+    hipLaunchKernelGGL(raster_tri_k_kernel, dim3(ceil_div(fmax, 256), B), dim3(256), 0, st, faces, mesh_table, class_index, scr, verts,
+                       poses, Kps, vmax, H, W, znear, zfar, n_classes, zbuf, hdr, B);
+  } else {
+    hipLaunchKernelGGL(raster_vertex_kernel, dim3(ceil_div(vmax, 256), B), dim3(256), 0, st, verts, mesh_table, class_index, poses,
+                       K9[0], K9[4], K9[2], K9[5], vmax, n_classes, status, scr, hdr, zbuf, B, H, W, bbox, wide);
+    hipLaunchKernelGGL(raster_tri_kernel, dim3(ceil_div(fmax, 256), B), dim3(256), 0, st, faces, mesh_table, class_index, scr, verts, poses,
+                       K9[0], K9[4], K9[2], K9[5], vmax, H, W, znear, zfar, n_classes, zbuf, hdr, B);
+  }
   float p0 = plane_means3 ? plane_means3[0] : 0.f, p1 = plane_means3 ? plane_means3[1] : 0.f, p2 = plane_means3 ? plane_means3[2] : 0.f;
   LitArgs lit = {verts, normals, poses, light_pos, light_int, ratio, K9[0], K9[4], K9[2], K9[5], fmaxf(znear, kZClipMin)};
   if (two_pass) {
@@ -738,6 +869,14 @@ static int raster_render_impl(const float* verts, const float* normals, const fl
       hipLaunchKernelGGL((raster_resolve_shade_kernel<false, false>), dim3(grid), dim3(256), 0, st, lit, uvs, faces, mesh_table, textures,
                          tex_table, class_index, scr, zbuf, vmax, H, W, tex_bilinear, p0, p1, p2, image, bgr, status, hdr, list, wave_ext,
                          wps, B, bbox);
+    else if (Kps && normals)
+      hipLaunchKernelGGL((raster_resolve_shade_k_kernel<true>), dim3(grid), dim3(256), 0, st, lit, Kps, uvs, faces, mesh_table, textures,
+                         tex_table, class_index, scr, zbuf, vmax, H, W, tex_bilinear, p0, p1, p2, image, bgr, status, hdr, list, wave_ext,
+                         wps, B, bbox);
+    else if (Kps)
+      hipLaunchKernelGGL((raster_resolve_shade_k_kernel<false>), dim3(grid), dim3(256), 0, st, lit, Kps, uvs, faces, mesh_table, textures,
+                         tex_table, class_index, scr, zbuf, vmax, H, W, tex_bilinear, p0, p1, p2, image, bgr, status, hdr, list, wave_ext,
+                         wps, B, bbox);
     else if (normals)
       hipLaunchKernelGGL((raster_resolve_shade_kernel<true, true>), dim3(grid), dim3(256), 0, st, lit, uvs, faces, mesh_table, textures,
                          tex_table, class_index, scr, zbuf, vmax, H, W, tex_bilinear, p0, p1, p2, image, bgr, status, hdr, list, wave_ext,
@@ -746,6 +885,15 @@ static int raster_render_impl(const float* verts, const float* normals, const fl
       hipLaunchKernelGGL((raster_resolve_shade_kernel<false, true>), dim3(grid), dim3(256), 0, st, lit, uvs, faces, mesh_table, textures,
                          tex_table, class_index, scr, zbuf, vmax, H, W, tex_bilinear, p0, p1, p2, image, bgr, status, hdr, list, wave_ext,
                          wps, B, bbox);
+  } else if (Kps) {
+    if (normals)
+      hipLaunchKernelGGL(raster_resolve_k_kernel<true>, dim3(ceil_div(W, 256), H, B), dim3(256), 0, st, lit, Kps, uvs, faces, mesh_table,
+                         textures, tex_table, class_index, scr, zbuf, vmax, H, W, tex_bilinear, p0, p1, p2, mask_thr, image, depth, mask, bgr,
+                         bbox, status);
+    else
+      hipLaunchKernelGGL(raster_resolve_k_kernel<false>, dim3(ceil_div(W, 256), H, B), dim3(256), 0, st, lit, Kps, uvs, faces, mesh_table,
+                         textures, tex_table, class_index, scr, zbuf, vmax, H, W, tex_bilinear, p0, p1, p2, mask_thr, image, depth, mask, bgr,
+                         bbox, status);
   } else {
     if (normals)
       hipLaunchKernelGGL(raster_resolve_kernel<true>, dim3(ceil_div(W, 256), H, B), dim3(256), 0, st, lit, uvs, faces, mesh_table, textures,
@@ -766,7 +914,7 @@ int dim_raster_render(const float* verts, const float* uvs, const int* faces, co
                       void* stream) {
   return raster_render_impl(verts, nullptr, uvs, faces, mesh_table, n_classes, vmax, fmax, textures, tex_table, class_index, poses, K9, B,
                             H, W, znear, zfar, tex_bilinear, nullptr, nullptr, 0.f, plane_means3, mask_thr, workspace, image, depth, mask,
-                            bgr, bbox, status, nullptr, stream);
+                            bgr, bbox, status, nullptr, nullptr, stream);
 }
 
 int dim_raster_render_lit(const float* verts, const float* normals, const float* uvs, const int* faces, const int* mesh_table,
@@ -779,7 +927,7 @@ int dim_raster_render_lit(const float* verts, const float* normals, const float*
   DIM_REQUIRE(normals && light_pos && light_int, "null pointer");
   return raster_render_impl(verts, normals, uvs, faces, mesh_table, n_classes, vmax, fmax, textures, tex_table, class_index, poses, K9, B,
                             H, W, znear, zfar, tex_bilinear, light_pos, light_int, brightness_ratio, plane_means3, mask_thr, workspace,
-                            image, depth, mask, bgr, bbox, status, nullptr, stream);
+                            image, depth, mask, bgr, bbox, status, nullptr, nullptr, stream);
 }
 
 int dim_raster_render_dirty(const float* verts, const float* normals, const float* uvs, const int* faces, const int* mesh_table,
@@ -793,7 +941,23 @@ int dim_raster_render_dirty(const float* verts, const float* normals, const floa
   DIM_REQUIRE(!clean_bbox || clean_bbox != bbox, "clean_bbox and bbox must be different arrays (the stream pass reads one while the last pass writes the other)");
   return raster_render_impl(verts, normals, uvs, faces, mesh_table, n_classes, vmax, fmax, textures, tex_table, class_index, poses, K9, B,
                             H, W, znear, zfar, tex_bilinear, light_pos, light_int, brightness_ratio, plane_means3, mask_thr, workspace,
-                            image, depth, mask, bgr, bbox, status, clean_bbox, stream);
+                            image, depth, mask, bgr, bbox, status, clean_bbox, nullptr, stream);
+}
+
+// dim_raster_render_dirty with per-sample intrinsics (the reference's test loop re-renders pair b with its own -K.txt:
+// deepim/core/tester.py:165, :560-562).  K_per_sample NULL = K9 for every sample.
+int dim_raster_render_k(const float* verts, const float* normals, const float* uvs, const int* faces, const int* mesh_table, int n_classes,
+                        int vmax, int fmax, const unsigned char* textures, const int* tex_table, const int* class_index, const float* poses,
+                        const float* K9, int B, int H, int W, float znear, float zfar, int tex_bilinear, const float* light_pos,
+                        const float* light_int, float brightness_ratio, const float* plane_means3, float mask_thr, void* workspace,
+                        float* image, float* depth, float* mask, float* bgr, int* bbox, int* status, const int* clean_bbox,
+                        const float* K_per_sample, void* stream) {
+  if (B == 0) return DIM_OK;
+  DIM_REQUIRE(!normals || (light_pos && light_int), "lit render: null light pointer");
+  DIM_REQUIRE(!clean_bbox || clean_bbox != bbox, "clean_bbox and bbox must be different arrays (the stream pass reads one while the last pass writes the other)");
+  return raster_render_impl(verts, normals, uvs, faces, mesh_table, n_classes, vmax, fmax, textures, tex_table, class_index, poses, K9, B,
+                            H, W, znear, zfar, tex_bilinear, light_pos, light_int, brightness_ratio, plane_means3, mask_thr, workspace,
+                            image, depth, mask, bgr, bbox, status, clean_bbox, K_per_sample, stream);
 }
 
 int dim_modelnet_light_position(const float* poses, float dx, float dy, float dz, float* light_pos, int B, void* stream) {

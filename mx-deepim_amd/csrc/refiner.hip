@@ -189,6 +189,14 @@ int dim_refiner_create(dim_refiner** out, const dim_refiner_desc* desc, const ch
 int dim_refiner_run(dim_refiner* r, const float* image_observed, const float* image_rendered, const float* mask_observed,
                     const float* mask_rendered, const float* src_pose, const int* class_index, float* poses_iter, float* se3_iter,
                     int* status_iter, void* stream) {
+  return dim_refiner_run_k(r, image_observed, image_rendered, mask_observed, mask_rendered, src_pose, class_index, poses_iter, se3_iter,
+                           status_iter, nullptr, stream);
+}
+
+// K_per_pair (B,9) device or NULL: the camera of each pair's re-render (tester.py:560-562); the zoom keeps d.K9 (tester.py:165)
+int dim_refiner_run_k(dim_refiner* r, const float* image_observed, const float* image_rendered, const float* mask_observed,
+                      const float* mask_rendered, const float* src_pose, const int* class_index, float* poses_iter, float* se3_iter,
+                      int* status_iter, const float* K_per_pair, void* stream) {
   DIM_REQUIRE(r && image_observed && image_rendered && mask_observed && mask_rendered && src_pose && class_index && poses_iter && se3_iter &&
                   status_iter,
               "null pointer");
@@ -248,10 +256,10 @@ int dim_refiner_run(dim_refiner* r, const float* image_observed, const float* im
       // (from the second render on, the planes hold the previous render: background outside ITS box, which is not written again)
       int* bb_new = (it & 1) ? r->bbox_ras2 : r->bbox_ras;
       const int* bb_prev = it == 0 ? nullptr : ((it & 1) ? r->bbox_ras : r->bbox_ras2);
-      TRY(dim_raster_render_dirty(d.verts, nullptr, d.uvs, d.faces, d.mesh_table, d.n_classes, d.vmax, d.fmax, d.textures, d.tex_table,
-                                  class_index, pose_out, d.K9, B, H, W, d.znear, d.zfar, d.tex_bilinear, nullptr, nullptr, 0.f, r->plane_means,
-                                  0.2f, r->raster_ws, r->image_rendered, nullptr, r->mask_rendered, nullptr, bb_new, status,
-                                  d.znear > 0.2f ? bb_prev : nullptr, stream));
+      TRY(dim_raster_render_k(d.verts, nullptr, d.uvs, d.faces, d.mesh_table, d.n_classes, d.vmax, d.fmax, d.textures, d.tex_table,
+                              class_index, pose_out, d.K9, B, H, W, d.znear, d.zfar, d.tex_bilinear, nullptr, nullptr, 0.f, r->plane_means,
+                              0.2f, r->raster_ws, r->image_rendered, nullptr, r->mask_rendered, nullptr, bb_new, status,
+                              d.znear > 0.2f ? bb_prev : nullptr, K_per_pair, stream));
       TRY(dim_box_mask(bb_new, r->mask_observed, B, H, W, r->bbox_box, stream));
       img_ren = r->image_rendered;
       m_obs = r->mask_observed;

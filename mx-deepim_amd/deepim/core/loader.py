@@ -36,6 +36,30 @@ import torch
 from lib.hip import ops
 
 
+# ------------------------------------------------------------------------------------------------------------------ intrinsics (test)
+def resolve_pair_intrinsics(pairdb, K_default):
+    """The camera the reference's test loop re-renders each pair with (deepim/core/tester.py:165, :560-562): K starts as the config K,
+    and before a pair's re-render it is replaced by np.loadtxt(image_observed[:-10] + "-K.txt") when that file exists.  K is never
+    reset between pairs, so a pair without a file keeps the last K loaded.  Applied here once, in pairdb order.
+    -> (K (N,3,3) float32, has_file (N,) bool).  A file that is not a readable 3x3 matrix raises ValueError naming its path."""
+    K = np.asarray(K_default, dtype=np.float32).reshape(3, 3)
+    out = np.empty((len(pairdb), 3, 3), dtype=np.float32)
+    has_file = np.zeros((len(pairdb),), dtype=bool)
+    for i, rec in enumerate(pairdb):
+        path = rec["image_observed"][:-10] + "-K.txt"
+        if os.path.exists(path):
+            try:
+                k = np.loadtxt(path, dtype=np.float64)
+            except Exception as e:
+                raise ValueError("{}: not a readable 3x3 camera matrix ({})".format(path, e))
+            if k.shape != (3, 3) or not np.all(np.isfinite(k)):
+                raise ValueError("{}: expected a finite 3x3 camera matrix, got shape {}".format(path, k.shape))
+            K = k.astype(np.float32)
+            has_file[i] = True
+        out[i] = K
+    return out, has_file
+
+
 # ------------------------------------------------------------------------------------------------------------------ sources (test)
 class RawPairSource(object):
     """len() pairs; fill(i, obs_bgr (H,W,3) u8, ren_bgr (H,W,3) u8, depth (H,W) u16) writes pair i's pixels into the given (pinned)
@@ -135,7 +159,7 @@ class _Staging(object):
             self.d[f] = torch.empty_like(self.h[f], device=device)
         meta = {"pose": ((B, 3, 4), torch.float32), "cls": ((B,), torch.int32), "gt": ((B, 3, 4), torch.float32),
                 "mask_idx": ((B,), torch.int32), "use_bg": ((B,), torch.int32), "thick": ((B, 4), torch.int32),
-                "P12": ((B, 3, 4), torch.float64), "tab_off": ((B,), torch.int32)}
+                "P12": ((B, 3, 4), torch.float64), "tab_off": ((B,), torch.int32), "K": ((B, 9), torch.float32)}
         if n_points:
             meta["pt_idx"] = ((B, n_points), torch.int32)
         self.mh = {k: pin(s, dt) for k, (s, dt) in meta.items()}
@@ -153,6 +177,7 @@ class _Staging(object):
     d_pose = property(lambda self: self.md["pose"])
     d_cls = property(lambda self: self.md["cls"])
     d_gt = property(lambda self: self.md["gt"])
+    d_K = property(lambda self: self.md["K"])
 
 
 class _DeviceLoader(object):
@@ -335,6 +360,11 @@ class TestDataLoader(_DeviceLoader):
             raise NotImplementedError("a RawPairSource carries colour + rendered depth only: INIT_MASK 'box_rendered' without INPUT_DEPTH")
         self.source = source
         self.pairdb, self.config = pairdb, config
+        # per-pair cameras of the re-render, resolved over the whole pairdb before any shuffle or split (the rule is sticky in pair order)
+        self.per_pair_K = False
+        if source is None:
+            self.K_pairs, has_file = resolve_pair_intrinsics(pairdb, cfg.dataset.INTRINSIC_MATRIX)
+            self.per_pair_K = bool(has_file.any())
         fields = ["obs", "ren", "depth"] + (["label"] if self.label_key else []) + (["depth_obs"] if self.input_depth else [])
         self._setup(len(source) if source is not None else len(pairdb), batch_size, shuffle, device, workers, height, width, fields, cache=cache)
         self.data_name = ["image_observed", "image_rendered", "src_pose", "class_index"]
@@ -405,11 +435,13 @@ class TestDataLoader(_DeviceLoader):
                 hm[j] = int(rec.get("mask_idx", 1)) if metas[("depth", j)] else -1
                 if st.has_gt:
                     hg[j] = np.asarray(rec["pose_observed"], np.float32)
+                if self.per_pair_K:
+                    st.mh["K"].numpy()[j] = self.K_pairs[int(i)].reshape(9)
         if self.dilate and self.input_mask:
             for j in range(len(ids)):
                 ht[j] = draw_dilate_thickness(10)   # get_pair_mask: mask_dilate(cur_mask_observed, max_thickness=10), pair by pair
         st.n = len(ids)
-        self._upload_meta(st, ("pose", "cls", "gt", "mask_idx", "thick"))
+        self._upload_meta(st, ("pose", "cls", "gt", "mask_idx", "thick") + (("K",) if self.per_pair_K else ()))
         return st
 
     def build_blobs(self, st, out=None):
@@ -439,11 +471,14 @@ class TestDataLoader(_DeviceLoader):
         st = self.next_raw()
         b = dict(self.build_blobs(st))
         # the small per-pair arrays leave the staging set too (it is re-staged while this batch may still be in use)
-        for name, src in (("src_pose", st.d_pose), ("class_index", st.d_cls)) + ((("pose_observed", st.d_gt),) if st.has_gt else ()):
+        for name, src in (("src_pose", st.d_pose), ("class_index", st.d_cls)) + ((("pose_observed", st.d_gt),) if st.has_gt else ()) \
+                + ((("K", st.d_K),) if self.per_pair_K else ()):
             if name not in self._meta_out:
                 self._meta_out[name] = torch.empty_like(src)
             ops.copy(self._meta_out[name], src)
             b[name] = self._meta_out[name]
+        if self.per_pair_K:   # the camera of each pair's re-render (tester.py:560-562), only when the pairdb ships -K.txt files
+            b["K"] = b["K"].view(self.batch_size, 3, 3)
         self.release(st)
         return b
 

@@ -69,6 +69,11 @@ class Refiner(object):
         self.bbox2 = torch.zeros((B, 4), dtype=torch.int32, device=d)   # consecutive renders alternate: one box is the next render's dirty-box hint
         self.bbox_obs = torch.zeros((B, 4), dtype=torch.int32, device=d)
         self.status_iter = torch.zeros((self.test_iter, B), dtype=torch.int32, device=d)
+        # the camera of each pair's re-render (reference tester.py:165, :560-562: a pair's own -K.txt replaces the config K there, and
+        # only there -- ZoomMask and the flow error keep the config K).  Resident so that a captured graph reads whatever load() put in
+        # it; `per_pair_K` False (no K loaded) keeps the uniform render with the config K, the launches of a loop without the feature.
+        self.K_pair = torch.from_numpy(np.tile(np.asarray(cfg.dataset.INTRINSIC_MATRIX, np.float32).reshape(1, 9), (B, 1))).to(d)
+        self.per_pair_K = False
         # per-iteration head outputs of the full (not FAST_TEST) graph, read by the reference at tester.py:485-491
         self.with_heads = bool(self.net.has_decoder and not cfg.TEST.FAST_TEST)
         self.mask_pred_iter = self.flow_est_iter = None
@@ -83,12 +88,16 @@ class Refiner(object):
         self.lit = hasattr(render_machine, "normals")
         self.light_int = torch.ones((max(self.test_iter - 1, 1), B, 3), dtype=torch.float32, device=d) if self.lit else None
         self.graph = None
+        self._graph_per_pair_K = None   # which render the captured graph holds (a different one is captured again)
         self._want_graph = capture_graph
 
     # ------------------------------------------------------------------------------------------
     def load(self, image_observed, image_rendered, mask_observed, mask_rendered, src_pose, class_index, depth_observed=None,
-             depth_rendered=None):
-        """copy one batch of blobs (any device) into the resident buffers (the depth planes: INPUT_DEPTH graphs only)"""
+             depth_rendered=None, K=None):
+        """copy one batch of blobs (any device) into the resident buffers (the depth planes: INPUT_DEPTH graphs only).
+        K: None (every re-render uses the config K) or the camera of each pair, (B,3,3) or (B,9), any device: the unlit re-renders of
+        this batch use it (the lit ModelNet render ignores K, as the reference's render() closure does)"""
+        self._load_K(K)
         b = self.batch
         if self.input_depth:
             assert depth_observed is not None and depth_rendered is not None, "INPUT_DEPTH: the loop needs depth_observed / depth_rendered"
@@ -105,6 +114,16 @@ class Refiner(object):
             li = np.stack([[np.random.uniform(0.9, 1.1, size=(3,)) for _ in range(self.test_iter - 1)] for _ in range(self.B)])
             self.light_int.copy_(torch.from_numpy(li.transpose(1, 0, 2).astype(np.float32)))
 
+    def _load_K(self, K):
+        if K is None:
+            self.per_pair_K = False
+            return
+        K = torch.as_tensor(K)
+        if tuple(K.shape) not in ((self.B, 3, 3), (self.B, 9)):
+            raise ValueError("per-pair K must be ({0},3,3) or ({0},9), got {1}".format(self.B, tuple(K.shape)))
+        self.K_pair.copy_(K.reshape(self.B, 9))
+        self.per_pair_K = True
+
     def load_staged(self, loader, staged):
         """take the next batch straight from a deepim.core.loader.TestDataLoader staging set: the raw pixels it uploaded are turned
         into the resident blobs by dim_test_blobs_from_raw / dim_box_mask on the current stream -- no host blobs, no extra copies"""
@@ -112,6 +131,9 @@ class Refiner(object):
                                         "mask_rendered": self.init["mask_rendered"], "mask_observed": self.init["mask_observed"]})
         ops.copy(self.pose_init, staged.d_pose)
         ops.copy(self.batch["class_index"], staged.d_cls)
+        self.per_pair_K = bool(getattr(loader, "per_pair_K", False))
+        if self.per_pair_K:
+            ops.copy(self.K_pair, staged.d_K)
         loader.release(staged)   # the last read of the staging set's device mirrors is enqueued
         if self.lit and self.test_iter > 1:
             li = np.stack([[np.random.uniform(0.9, 1.1, size=(3,)) for _ in range(self.test_iter - 1)] for _ in range(self.B)])
@@ -147,6 +169,8 @@ class Refiner(object):
             if it < self.test_iter - 1:
                 # render(render_machine, pose_rendered_update, cls_idx) + update_data_batch  (:563-590)
                 extra = {"light_intensity": self.light_int[it]} if self.lit else {}
+                if self.per_pair_K and not self.lit:
+                    extra["K"] = self.K_pair   # read where it lies: a replayed graph renders with the K of the latest load
                 # (the loop needs the depth only for mask_rendered = depth > 0.2, tester.py:575-577: the resolve pass writes the mask itself
                 # and the depth plane is not materialised -- 1.2 MB per pair and render less to write)
                 if self.input_depth:
@@ -170,6 +194,8 @@ class Refiner(object):
 
     def refine(self):
         """run test_iter iterations on the loaded batch; returns poses_iter (test_iter,B,3,4) (device)."""
+        if self.graph is not None and self._graph_per_pair_K != self.per_pair_K:
+            self.graph = None   # captured with the other render (uniform / per-pair K): capture this one
         if self._want_graph and self.graph is None:
             s = torch.cuda.Stream(device=self.net.device)
             s.wait_stream(torch.cuda.current_stream())
@@ -181,6 +207,7 @@ class Refiner(object):
             with torch.cuda.graph(g):
                 self._loop()
             self.graph = g
+            self._graph_per_pair_K = self.per_pair_K
         if self.graph is not None:
             self.graph.replay()
         else:
@@ -268,7 +295,7 @@ def pred_eval(config, refiner, batches, evaluator, result_file=None, logger=None
     epe = FlowEPE(config, refiner.B, refiner.net.device) if (config.network.PRED_FLOW and not config.TEST.FAST_TEST) else None
     for batch in batches:
         refiner.load(batch["image_observed"], batch["image_rendered"], batch["mask_observed"], batch["mask_rendered"], batch["src_pose"],
-                     batch["class_index"])
+                     batch["class_index"], K=batch.get("K"))
         poses = refiner.refine().cpu().numpy().astype(np.float64)     # ONE device->host copy per batch: (iter, B, 3, 4)
         cls = torch.as_tensor(batch["class_index"]).cpu().numpy().astype(int)
         gt = torch.as_tensor(batch["pose_observed"]).cpu().numpy().astype(np.float64)

@@ -42,6 +42,7 @@ SIGNATURES = {
     "dim_flow_epe_sums": (I, [P, P, P, P, I, I, I, P, P, I, P]),
     "dim_refiner_create": (I, [P, P, P, P, I, P]),
     "dim_refiner_run": (I, [P, P, P, P, P, P, P, P, P, P, P]),
+    "dim_refiner_run_k": (I, [P, P, P, P, P, P, P, P, P, P, P, P]),
     "dim_refiner_destroy": (I, [P]),
     "dim_test_blobs_from_raw": (I, [P, P, P, I, I, I, F, P, F, P, P, P, P, P]),
     "dim_pair_blobs_from_raw": (I, [P, P, P, P, P, P, P, P, P, I, I, I, F, P, F, P, P, P, P, P, P, P, P, P, P, P]),
@@ -52,6 +53,7 @@ SIGNATURES = {
     "dim_raster_render": (I, [P, P, P, P, I, I, I, P, P, P, P, P, I, I, I, F, F, I, P, F, P, P, P, P, P, P, P, P]),
     "dim_raster_render_lit": (I, [P, P, P, P, P, I, I, I, P, P, P, P, P, I, I, I, F, F, I, P, P, F, P, F, P, P, P, P, P, P, P, P]),
     "dim_raster_render_dirty": (I, [P, P, P, P, P, I, I, I, P, P, P, P, P, I, I, I, F, F, I, P, P, F, P, F, P, P, P, P, P, P, P, P, P]),
+    "dim_raster_render_k": (I, [P, P, P, P, P, I, I, I, P, P, P, P, P, I, I, I, F, F, I, P, P, F, P, F, P, P, P, P, P, P, P, P, P, P]),
     "dim_modelnet_light_position": (I, [P, F, F, F, P, I, P]),
     "dim_box_mask": (I, [P, P, I, I, I, P, P]),
     "dim_conv2d_packed_weight_floats": (L, [I, I, I, I]),

@@ -204,6 +204,47 @@ def flow_epe_sums(flow_pred, flow_gt, visible, depth_rendered, sums=None, accumu
     return sums
 
 
+STATUS_BAD_K = 16   # DIM_STATUS_BAD_K: dim_raster_render_k drew the sample as background (fx <= 0, fy <= 0 or a non-finite entry)
+
+
+def intrinsics_per_sample(K, B, device):
+    """the K argument of a batched render -> None (one camera for the batch: None or nine values, the uniform path) or a contiguous
+    (B,9) f32 CUDA tensor for dim_raster_render_k.  K: (B,3,3) or (B,9), a host array or a CUDA tensor; a CUDA f32 tensor that is
+    already contiguous is used where it lies (a captured graph then renders with whatever it holds at replay).  Any other shape
+    raises ValueError before anything is launched."""
+    if K is None:
+        return None
+    if isinstance(K, torch.Tensor) and K.is_cuda:
+        if tuple(K.shape) in ((B, 3, 3), (B, 9)):
+            return K.to(device=device, dtype=f32).reshape(B, 9).contiguous()
+        if K.numel() == 9:
+            return None
+        raise ValueError("per-sample K must be (B,3,3) or (B,9) with B = {}, got {}".format(B, tuple(K.shape)))
+    a = np.asarray(K, dtype=np.float32)
+    if a.size == 9:
+        return None
+    if a.shape not in ((B, 3, 3), (B, 9)):
+        raise ValueError("K must be a 3x3 matrix or per-sample (B,3,3) / (B,9) with B = {}, got {}".format(B, a.shape))
+    return torch.from_numpy(np.ascontiguousarray(a.reshape(B, 9))).to(device)
+
+
+def raster_render_k(rm, class_index, poses, K_per_sample, workspace, light_position=None, light_intensity=None, brightness_ratio=0.0,
+                    plane_means=None, mask_thr=0.2, image=None, depth=None, mask=None, bgr=None, bbox=None, status=None, clean_bbox=None):
+    """dim_raster_render_k: render machine `rm` (lib/render_hip: its mesh table, K, znear / zfar; lit when it has normals) with one
+    camera per sample.  K_per_sample: (B,9) f32 CUDA (intrinsics_per_sample) or None (rm.K for all).  workspace: rm's for this B."""
+    B = poses.shape[0]
+    keep, k9 = host_f32(rm.K, 9)   # (keeps the host array alive through the call)
+    normals = getattr(rm, "normals", None)
+    pm = host_f32(plane_means, 3) if plane_means is not None else (None, None)
+    opt = lambda t, dt=f32: dptr(t, dt) if t is not None else None  # noqa: E731
+    check(lib().dim_raster_render_k(
+        dptr(rm.verts), opt(normals), dptr(rm.uvs), dptr(rm.faces), dptr(rm.mesh_table), int(rm.mesh_table.shape[0]), rm.vmax, rm.fmax,
+        dptr(rm.textures), dptr(rm.tex_table), dptr(class_index, i32), dptr(poses, f32), k9, B, rm.height, rm.width, float(rm.zNear),
+        float(rm.zFar), int(rm.tex_bilinear), opt(light_position), opt(light_intensity), float(brightness_ratio), pm[1], float(mask_thr),
+        workspace.data_ptr(), dptr(image), dptr(depth), dptr(mask), dptr(bgr), opt(bbox, i32), opt(status, i32), opt(clean_bbox, i32),
+        opt(K_per_sample), current_stream()))
+
+
 def box_mask(bbox, mask, bbox_of_mask=None):
     """mask <- filled rectangle of bbox (end-exclusive); bbox_of_mask (B,4) int32: optional bbox of that rectangle"""
     B, _, H, W = mask.shape

@@ -1,4 +1,4 @@
-"""ctypes face of the resident-loop C entry points (include/deepim_hip.h: dim_refiner_create / _run / _destroy).
+"""ctypes face of the resident-loop C entry points (include/deepim_hip.h: dim_refiner_create / _run / _run_k / _destroy).
 
 This is what a host WITHOUT torch binds (INTEGRATION.md shows the same struct for C / cgo callers); torch is used here only to own
 the device memory of the arguments, exactly as in the rest of lib/hip."""
@@ -50,11 +50,19 @@ class CRefiner(object):
         self.se3_iter = torch.zeros((self.T, self.B, 7), dtype=torch.float32, device=self.device)
         self.status_iter = torch.zeros((self.T, self.B), dtype=torch.int32, device=self.device)
 
-    def refine(self, image_observed, image_rendered, mask_observed, mask_rendered, src_pose, class_index):
+    def refine(self, image_observed, image_rendered, mask_observed, mask_rendered, src_pose, class_index, K_per_pair=None):
+        """K_per_pair: None (dim_refiner_run: the desc's K9) or a (B,9) / (B,3,3) f32 CUDA tensor, the camera of each pair's re-render
+        (dim_refiner_run_k)"""
         f32 = torch.float32
-        check(lib().dim_refiner_run(self._h, dptr(image_observed, f32), dptr(image_rendered, f32), dptr(mask_observed, f32),
-                                    dptr(mask_rendered, f32), dptr(src_pose, f32), dptr(class_index, torch.int32), dptr(self.poses_iter, f32),
-                                    dptr(self.se3_iter, f32), dptr(self.status_iter, torch.int32), current_stream()))
+        args = (self._h, dptr(image_observed, f32), dptr(image_rendered, f32), dptr(mask_observed, f32), dptr(mask_rendered, f32),
+                dptr(src_pose, f32), dptr(class_index, torch.int32), dptr(self.poses_iter, f32), dptr(self.se3_iter, f32),
+                dptr(self.status_iter, torch.int32))
+        if K_per_pair is None:
+            check(lib().dim_refiner_run(*args, current_stream()))
+        else:
+            if tuple(K_per_pair.shape) not in ((self.B, 9), (self.B, 3, 3)):
+                raise ValueError("K_per_pair must be ({0},9) or ({0},3,3), got {1}".format(self.B, tuple(K_per_pair.shape)))
+            check(lib().dim_refiner_run_k(*args, dptr(K_per_pair, f32), current_stream()))
         return self.poses_iter
 
     def close(self):

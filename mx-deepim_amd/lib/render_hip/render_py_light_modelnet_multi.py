@@ -10,6 +10,7 @@ All meshes (256 for the ModelNet-unseen configuration) are resident in one HBM t
 import numpy as np
 import torch
 
+from lib.hip import ops
 from lib.hip.capi import check, current_stream, dptr, host_f32, lib
 from lib.render_hip.render_py_multi import Render_Py, quat2mat
 
@@ -113,17 +114,23 @@ class Render_Py_Light_ModelNet_Multi(Render_Py):
     def render_batch(self, class_index, poses, light_position=None, light_intensity=None, brightness_k=0, K=None, image=None,
                      depth=None, mask=None, bgr=None, bbox=None, plane_means=None, mask_thr=0.2, status=None, clean_bbox=None):
         """class_index (B,) int32, poses (B,3,4), light_position / light_intensity (B,3) f32, all cuda.
-        light_position None = the loop's rule (idx 2); light_intensity None = white (1,1,1).  clean_bbox: as Render_Py.render_batch."""
+        light_position None = the loop's rule (idx 2); light_intensity None = white (1,1,1).  K, clean_bbox: as Render_Py.render_batch."""
         B = poses.shape[0]
+        kps = ops.intrinsics_per_sample(K, B, self.device)   # (a wrong shape raises before the light kernel is launched)
         if light_position is None:
             light_position = self.light_position(poses)
         if light_intensity is None:
             light_intensity = torch.ones((B, 3), dtype=torch.float32, device=self.device)
-        keep, kp = host_f32(self.K if K is None else K, 9)
-        pm = host_f32(plane_means, 3) if plane_means is not None else (None, None)
         ws = self._workspace(B)
         if clean_bbox is not None and not mask_thr < self.zNear:
             clean_bbox = None
+        if kps is not None:
+            ops.raster_render_k(self, class_index, poses, kps, ws, light_position=light_position, light_intensity=light_intensity,
+                                brightness_ratio=self.brightness_ratios[brightness_k], plane_means=plane_means, mask_thr=mask_thr,
+                                image=image, depth=depth, mask=mask, bgr=bgr, bbox=bbox, status=status, clean_bbox=clean_bbox)
+            return
+        keep, kp = host_f32(self.K if K is None else K, 9)
+        pm = host_f32(plane_means, 3) if plane_means is not None else (None, None)
         check(lib().dim_raster_render_dirty(
             dptr(self.verts), dptr(self.normals), dptr(self.uvs), dptr(self.faces), dptr(self.mesh_table), int(self.mesh_table.shape[0]),
             self.vmax, self.fmax,

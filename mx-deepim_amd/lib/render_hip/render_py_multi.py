@@ -12,7 +12,7 @@ import os
 import numpy as np
 import torch
 
-from lib.hip import capi
+from lib.hip import capi, ops
 from lib.hip.capi import check, current_stream, dptr, host_f32, lib
 
 
@@ -139,15 +139,22 @@ class Render_Py(object):
     def render_batch(self, class_index, poses, K=None, image=None, depth=None, mask=None, bgr=None, bbox=None,
                      plane_means=None, mask_thr=0.2, status=None, clean_bbox=None):
         """class_index (B,) int32 cuda, poses (B,3,4) f32 cuda.  Any of the output tensors may be None.
-        status: optional (B,) int32 cuda; DIM_STATUS_BAD_CLASS (4) / DIM_STATUS_BAD_FACE (8) are OR-ed in.
+        K: None (self.K), one 3x3, or one camera per sample, (B,3,3) or (B,9), host array or cuda tensor (the reference's test loop
+        renders each pair with its own -K.txt: tester.py:560-562); each sample then renders as it would alone with its own K.
+        status: optional (B,) int32 cuda; DIM_STATUS_BAD_CLASS (4) / DIM_STATUS_BAD_FACE (8) / DIM_STATUS_BAD_K (16) are OR-ed in.
         clean_bbox: optional (B,4) int32 cuda, the bbox a PREVIOUS render_batch into the same output tensors returned (another tensor
         than `bbox`): the planes hold background outside it, and pixels out there that this render does not cover are not rewritten."""
         B = poses.shape[0]
-        keep, kp = host_f32(self.K if K is None else K, 9)
-        pm = host_f32(plane_means, 3) if plane_means is not None else (None, None)
+        kps = ops.intrinsics_per_sample(K, B, self.device)
         ws = self._workspace(B)
         if clean_bbox is not None and not mask_thr < self.zNear:
             clean_bbox = None   # the mask's box is the box of everything drawn only if every fragment passes the mask threshold
+        if kps is not None:
+            ops.raster_render_k(self, class_index, poses, kps, ws, plane_means=plane_means, mask_thr=mask_thr, image=image, depth=depth,
+                                mask=mask, bgr=bgr, bbox=bbox, status=status, clean_bbox=clean_bbox)
+            return
+        keep, kp = host_f32(self.K if K is None else K, 9)
+        pm = host_f32(plane_means, 3) if plane_means is not None else (None, None)
         check(lib().dim_raster_render_dirty(
             dptr(self.verts), None, dptr(self.uvs), dptr(self.faces), dptr(self.mesh_table), int(self.mesh_table.shape[0]), self.vmax, self.fmax,
             dptr(self.textures), dptr(self.tex_table), dptr(class_index, torch.int32), dptr(poses, torch.float32), kp, B, self.height,
