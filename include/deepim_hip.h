@@ -39,6 +39,7 @@ extern "C" {
 #define DIM_STATUS_BAD_CLASS 4     /* dim_raster_render*: class_index outside [0, n_classes): sample rendered as background */
 #define DIM_STATUS_BAD_FACE 8      /* dim_raster_render*: a z-buffer key named a face outside the mesh (pixel left black) */
 #define DIM_STATUS_BAD_K 16        /* dim_raster_render_k: the sample's K has fx <= 0, fy <= 0 or a non-finite entry (rendered as background) */
+#define DIM_STATUS_ICP_FEW_POINTS 32 /* dim_icp_refine: an iteration found fewer than 64 inliers or a singular system (no update) */
 
 const char* dim_last_error(void);
 /* library / device probe: fills name (<= n bytes), returns number of compute units or <0 */
@@ -134,6 +135,30 @@ int dim_depth_to_flow(const float* depth_src, const float* depth_tgt, const floa
 long dim_flow_epe_workspace_bytes(int B);
 int dim_flow_epe_sums(const float* flow_pred, const float* flow_gt, const float* visible, const float* depth_rendered, int B, int H,
                       int W, void* workspace, double* sums, int accumulate, void* stream);
+
+/* ---------------------------------------------------------------- depth ICP after the refinement loop (RGB-D test time)
+ * Projective point-to-plane ICP, model to frame, `iters` fixed iterations (no early exit: graph-capturable), restated in float64 by
+ * tests/icp_reference.py.  Per pair b:
+ *   source = the pixels of depth_rendered (B,1,H,W) metres > 0 inside bbox[b] (B,4 int32 {min_x,max_x,min_y,max_y} inclusive, as
+ *   dim_raster_render* returns it; NULL = whole frame), back-projected with the pair's camera: p0 = d ((x-cx)/fx, (y-cy)/fy, 1).
+ *   pose_in (B,3,4) = T0, the pose depth_rendered was rendered at.  Each iteration moves p0 by the correction T_delta (identity at the
+ *   start), projects it to the integer pixel floor(fx px/pz + cx + 0.5), floor(fy py/pz + cy + 0.5) inside [1,W-2] x [1,H-2] of
+ *   depth_observed (B,1,H,W) metres, 0 = no reading, gated by mask_observed (B,1,H,W) >= 0.5 when given (NULL = none); the
+ *   observed point q and its four neighbours (depth > 0, |depth - depth(q)| < max_dist) give the normal n (n . q < 0); pairs with
+ *   |p - q| > max_dist are rejected.  r = n . (p - q), J = (p x n, n); (A + 1e-9 tr(A)/6 I) xi = -sum J r by float64 Cholesky,
+ *   T_delta <- [Rodrigues(omega) | v] T_delta.  Fewer than 64 inliers or a non-positive-definite A: no update, and
+ *   DIM_STATUS_ICP_FEW_POINTS is OR-ed into status[b] (B int32, may be NULL).
+ * pose_out (B,3,4) = T_delta T0 in float32; a pair that never updated gets pose_in bit for bit.  stats (B,iters,2) f32 or NULL =
+ * (inliers, rms residual in metres) of every iteration before its update.  Camera: K_per_sample (B,9) device f32 (fx = [0],
+ * fy = [4], cx = [2], cy = [5]) or NULL = K9 (host, 9 floats) for every pair; a non-positive or non-finite focal length gives the
+ * pair no source points.  workspace: dim_icp_workspace_bytes(B, H, W) bytes, 8-byte aligned, no initialisation needed.
+ * Sums: float32 per lane, float64 across lanes, waves and workgroups in a fixed order (no atomics): a replay is bit-identical.
+ * 2 launches per iteration; iters == 0 copies pose_in to pose_out.  B <= 0, iters < 0, max_dist <= 0, H or W < 3 or a NULL
+ * required pointer return DIM_ERR_ARG before anything is enqueued. */
+long dim_icp_workspace_bytes(int B, int H, int W);
+int dim_icp_refine(const float* depth_rendered, const float* depth_observed, const float* mask_observed, const int* bbox, const float* pose_in,
+                   const float* K9, const float* K_per_sample, int B, int H, int W, int iters, float max_dist, void* workspace,
+                   float* pose_out, float* stats, int* status, void* stream);
 
 /* ---------------------------------------------------------------- data layer (test batches from raw file pixels)
  * The loader uploads what the image files hold -- obs_bgr / ren_bgr (B,H,W,3) uint8 in B,G,R order (cv2.IMREAD_COLOR), depth_rendered

@@ -344,7 +344,8 @@ TEST_LABEL_OF_KIND = {"mask_gt_observed": "mask_gt_observed", "box_gt_observed":
 
 class TestDataLoader(_DeviceLoader):
     """reference deepim/core/loader.py:20-117.  Every TEST.INIT_MASK kind of get_pair_mask (image.py:367-476), TEST.MASK_DILATE and
-    INPUT_DEPTH are built on the device; `source` (a RawPairSource) replaces the files for the shipped kind 'box_rendered' only."""
+    INPUT_DEPTH are built on the device; `source` (a RawPairSource) replaces the files for the shipped kind 'box_rendered' only.
+    depth_observed is staged for INPUT_DEPTH and for the depth ICP after the loop (TEST.ICP_ITER > 0)."""
 
     def __init__(self, pairdb, config, batch_size=1, shuffle=False, device="cuda:0", workers=8, source=None, height=480, width=640,
                  cache=None):
@@ -356,8 +357,11 @@ class TestDataLoader(_DeviceLoader):
         if self.input_mask and self.init_mask not in ("box_rendered",) + tuple(TEST_LABEL_OF_KIND):
             raise Exception("Unknown init mask type: {}".format(self.init_mask))
         self.label_key = TEST_LABEL_OF_KIND.get(self.init_mask) if self.input_mask else None
+        self.stage_depth_observed = self.input_depth or int(cfg.TEST.get("ICP_ITER", 0) or 0) > 0
         if source is not None and (self.label_key or self.input_depth):
             raise NotImplementedError("a RawPairSource carries colour + rendered depth only: INIT_MASK 'box_rendered' without INPUT_DEPTH")
+        if source is not None and self.stage_depth_observed:
+            raise NotImplementedError("a RawPairSource carries colour + rendered depth only: no observed depth for TEST.ICP_ITER > 0")
         self.source = source
         self.pairdb, self.config = pairdb, config
         # per-pair cameras of the re-render, resolved over the whole pairdb before any shuffle or split (the rule is sticky in pair order)
@@ -365,7 +369,7 @@ class TestDataLoader(_DeviceLoader):
         if source is None:
             self.K_pairs, has_file = resolve_pair_intrinsics(pairdb, cfg.dataset.INTRINSIC_MATRIX)
             self.per_pair_K = bool(has_file.any())
-        fields = ["obs", "ren", "depth"] + (["label"] if self.label_key else []) + (["depth_obs"] if self.input_depth else [])
+        fields = ["obs", "ren", "depth"] + (["label"] if self.label_key else []) + (["depth_obs"] if self.stage_depth_observed else [])
         self._setup(len(source) if source is not None else len(pairdb), batch_size, shuffle, device, workers, height, width, fields, cache=cache)
         self.data_name = ["image_observed", "image_rendered", "src_pose", "class_index"]
         if self.input_depth:
@@ -378,8 +382,10 @@ class TestDataLoader(_DeviceLoader):
         B, f32, d = self.batch_size, torch.float32, self.device
         plane = lambda c: torch.empty((B, c, self.H, self.W), dtype=f32, device=d)  # noqa: E731
         self.blobs = {"image_observed": plane(3), "image_rendered": plane(3), "mask_observed": plane(1), "mask_rendered": plane(1)}
+        if self.stage_depth_observed:
+            self.blobs["depth_observed"] = plane(1)
         if self.input_depth:
-            self.blobs["depth_observed"], self.blobs["depth_rendered"] = plane(1), plane(1)
+            self.blobs["depth_rendered"] = plane(1)
         self.mask_tmp = plane(1) if self.dilate else None
         self.bbox = torch.empty((B, 4), dtype=torch.int32, device=d)
         self.bbox_label = torch.empty((B, 4), dtype=torch.int32, device=d)
@@ -422,7 +428,7 @@ class TestDataLoader(_DeviceLoader):
                              lambda a: bool(a.any())))
                 if self.label_key:
                     jobs.append(("label", j, (rec[self.label_key], "u"), lambda p=rec[self.label_key]: _imread_unchanged(p), None))
-                if self.input_depth:
+                if self.stage_depth_observed:
                     jobs.append(("depth_obs", j, (rec["depth_observed"], "u"), lambda p=rec["depth_observed"]: _imread_unchanged(p), None))
             metas = self._fill_files(st, jobs)
             st.has_gt = all("pose_observed" in self.pairdb[int(i)] for i in ids)
@@ -456,7 +462,7 @@ class TestDataLoader(_DeviceLoader):
                                 mask_idx=st.md["mask_idx"] if by_label else None, image_observed=out["image_observed"],
                                 image_rendered=out["image_rendered"], mask_rendered=out.get("mask_rendered") if self.input_mask else None,
                                 depth_rendered=out.get("depth_rendered") if self.input_depth else None,
-                                depth_b_out=out.get("depth_observed") if self.input_depth else None,
+                                depth_b_out=out.get("depth_observed") if self.stage_depth_observed else None,
                                 mask_label=first if mask_direct else None, bbox_ren=self.bbox,
                                 bbox_label=self.bbox_label if (by_label and not mask_direct) else None)
         if self.input_mask:

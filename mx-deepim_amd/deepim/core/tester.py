@@ -83,6 +83,18 @@ class Refiner(object):
             self.flow_est_iter = torch.zeros((self.test_iter, B, 2, H, W), dtype=torch.float32, device=d)
         self.T_means = np.asarray(cfg.dataset.trans_means, dtype=np.float32)
         self.T_stds = np.asarray(cfg.dataset.trans_stds, dtype=np.float32)
+        # depth ICP after the loop (TEST.ICP_ITER > 0): the depth rendered at the last pose, its box, and the polished pose per pair
+        self.icp_iter = int(cfg.TEST.get("ICP_ITER", 0) or 0)
+        self.icp_max_dist = float(cfg.TEST.get("ICP_MAX_DIST", 0.02))
+        self.depth_observed = self.pose_icp = self.icp_stats = self.status_icp = None
+        if self.icp_iter > 0:
+            self.depth_observed = self.batch["depth_observed"] if self.input_depth else torch.zeros((B, 1, H, W), dtype=torch.float32, device=d)
+            self.depth_icp = torch.zeros((B, 1, H, W), dtype=torch.float32, device=d)
+            self.bbox_icp = torch.zeros((B, 4), dtype=torch.int32, device=d)
+            self.pose_icp = torch.zeros((B, 3, 4), dtype=torch.float32, device=d)
+            self.icp_stats = torch.zeros((B, self.icp_iter, 2), dtype=torch.float32, device=d)
+            self.status_icp = torch.zeros((B,), dtype=torch.int32, device=d)
+            self.icp_work = ops.icp_workspace(B, H, W, d)
         render_machine.reserve(B)
         # ModelNet: the lit renderer takes a per-render light intensity drawn on the host (tester.py:227-230)
         self.lit = hasattr(render_machine, "normals")
@@ -94,7 +106,8 @@ class Refiner(object):
     # ------------------------------------------------------------------------------------------
     def load(self, image_observed, image_rendered, mask_observed, mask_rendered, src_pose, class_index, depth_observed=None,
              depth_rendered=None, K=None):
-        """copy one batch of blobs (any device) into the resident buffers (the depth planes: INPUT_DEPTH graphs only).
+        """copy one batch of blobs (any device) into the resident buffers (the depth planes: INPUT_DEPTH graphs only; depth_observed
+        also when TEST.ICP_ITER > 0).
         K: None (every re-render uses the config K) or the camera of each pair, (B,3,3) or (B,9), any device: the unlit re-renders of
         this batch use it (the lit ModelNet render ignores K, as the reference's render() closure does)"""
         self._load_K(K)
@@ -103,6 +116,10 @@ class Refiner(object):
             assert depth_observed is not None and depth_rendered is not None, "INPUT_DEPTH: the loop needs depth_observed / depth_rendered"
             b["depth_observed"].copy_(torch.as_tensor(depth_observed))
             self.init["depth_rendered"].copy_(torch.as_tensor(depth_rendered))
+        elif self.icp_iter > 0:
+            if depth_observed is None:
+                raise ValueError("TEST.ICP_ITER > 0: the ICP stage needs depth_observed")
+            self.depth_observed.copy_(torch.as_tensor(depth_observed))
         b["image_observed"].copy_(torch.as_tensor(image_observed))
         self.init["image_rendered"].copy_(torch.as_tensor(image_rendered))
         self.init["mask_observed"].copy_(torch.as_tensor(mask_observed))
@@ -127,8 +144,13 @@ class Refiner(object):
     def load_staged(self, loader, staged):
         """take the next batch straight from a deepim.core.loader.TestDataLoader staging set: the raw pixels it uploaded are turned
         into the resident blobs by dim_test_blobs_from_raw / dim_box_mask on the current stream -- no host blobs, no extra copies"""
-        loader.build_blobs(staged, out={"image_observed": self.batch["image_observed"], "image_rendered": self.init["image_rendered"],
-                                        "mask_rendered": self.init["mask_rendered"], "mask_observed": self.init["mask_observed"]})
+        out = {"image_observed": self.batch["image_observed"], "image_rendered": self.init["image_rendered"],
+               "mask_rendered": self.init["mask_rendered"], "mask_observed": self.init["mask_observed"]}
+        if self.icp_iter > 0:
+            if not getattr(loader, "stage_depth_observed", False):
+                raise ValueError("TEST.ICP_ITER > 0: the loader does not stage depth_observed")
+            out["depth_observed"] = self.depth_observed
+        loader.build_blobs(staged, out=out)
         ops.copy(self.pose_init, staged.d_pose)
         ops.copy(self.batch["class_index"], staged.d_cls)
         self.per_pair_K = bool(getattr(loader, "per_pair_K", False))
@@ -191,9 +213,26 @@ class Refiner(object):
                 pose = self.poses_iter[it]
                 bbox_ren = bb_new
         ops.copy(b["src_pose"], pose)  # the blob ends up as the reference leaves it: the pose the last forward used
+        if self.icp_iter > 0:
+            self._icp(self.poses_iter[self.test_iter - 1])
+
+    def _icp(self, pose):
+        """depth ICP from the loop's last pose: render its depth and box (the pair's K when loaded), then dim_icp_refine against
+        depth_observed -> pose_icp, icp_stats (B,ICP_ITER,2), status_icp (render bits and DIM_STATUS_ICP_FEW_POINTS)"""
+        b = self.batch
+        ops.fill(self.status_icp, 0)
+        extra = {"light_intensity": self.light_int[0]} if self.lit else {}
+        K_pair = self.K_pair if (self.per_pair_K and not self.lit) else None
+        if K_pair is not None:
+            extra["K"] = K_pair
+        self.render_machine.render_batch(b["class_index"], pose, depth=self.depth_icp, bbox=self.bbox_icp, mask_thr=0.0,
+                                         status=self.status_icp, **extra)
+        ops.icp_refine(self.depth_icp, self.depth_observed, pose, self.render_machine.K, self.icp_iter, self.icp_max_dist, bbox=self.bbox_icp,
+                       K_per_sample=K_pair, pose_out=self.pose_icp, stats=self.icp_stats, status=self.status_icp, workspace=self.icp_work)
 
     def refine(self):
-        """run test_iter iterations on the loaded batch; returns poses_iter (test_iter,B,3,4) (device)."""
+        """run test_iter iterations on the loaded batch; returns poses_iter (test_iter,B,3,4) (device).  With TEST.ICP_ITER > 0 the
+        ICP stage runs after them (inside the same graph) and leaves its pose in pose_icp (B,3,4)."""
         if self.graph is not None and self._graph_per_pair_K != self.per_pair_K:
             self.graph = None   # captured with the other render (uniform / per-pair K): capture this one
         if self._want_graph and self.graph is None:
@@ -281,7 +320,10 @@ def pred_eval(config, refiner, batches, evaluator, result_file=None, logger=None
     Collects all_poses_est[cls][iter] / all_poses_gt[cls][iter] and the rotation / translation errors per iteration exactly as
     the reference does (:497-560), writes the result cache [all_rot_err, all_trans_err, all_poses_est, all_poses_gt] with
     pickle protocol 2 (:650-654) and runs evaluate_pose / evaluate_pose_add / evaluate_pose_arp_2d (:664-673).
-    evaluator: lib.dataset.evaluation.PoseEvaluator.  Returns the three result dicts."""
+    evaluator: lib.dataset.evaluation.PoseEvaluator.  Returns the three result dicts.
+    With TEST.ICP_ITER > 0 the refiner's ICP poses are scored too, as the one-row table of the reference's PRECOMPUTED_ICP branch
+    (tester.py:253-330), under out["icp"] = {pose, add, arp_2d}; every other output and the result cache are those of ICP off."""
+    import copy
     import pickle
 
     from lib.utils.pose_error import calc_rt_dist_m
@@ -291,12 +333,16 @@ def pred_eval(config, refiner, batches, evaluator, result_file=None, logger=None
     all_trans_err = [[[] for _ in range(n_it)] for _ in range(n_cls)]
     all_poses_est = [[[] for _ in range(n_it)] for _ in range(n_cls)]
     all_poses_gt = [[[] for _ in range(n_it)] for _ in range(n_cls)]
+    # depth ICP after the loop: its own one-row lists [rot_err, trans_err, poses_est, poses_gt][cls][0]
+    with_icp = int(config.TEST.get("ICP_ITER", 0) or 0) > 0
+    icp_lists = tuple([[[]] for _ in range(n_cls)] for _ in range(4)) if with_icp else None
     # flow error of the first forward (:500-512): only the full test graph emits the flow head's output
     epe = FlowEPE(config, refiner.B, refiner.net.device) if (config.network.PRED_FLOW and not config.TEST.FAST_TEST) else None
     for batch in batches:
         refiner.load(batch["image_observed"], batch["image_rendered"], batch["mask_observed"], batch["mask_rendered"], batch["src_pose"],
-                     batch["class_index"], K=batch.get("K"))
+                     batch["class_index"], depth_observed=batch.get("depth_observed"), K=batch.get("K"))
         poses = refiner.refine().cpu().numpy().astype(np.float64)     # ONE device->host copy per batch: (iter, B, 3, 4)
+        poses_icp = refiner.pose_icp.cpu().numpy().astype(np.float64) if with_icp else None
         cls = torch.as_tensor(batch["class_index"]).cpu().numpy().astype(int)
         gt = torch.as_tensor(batch["pose_observed"]).cpu().numpy().astype(np.float64)
         src = torch.as_tensor(batch["src_pose"]).cpu().numpy().astype(np.float64)
@@ -313,6 +359,11 @@ def pred_eval(config, refiner, batches, evaluator, result_file=None, logger=None
                 all_poses_gt[cls[b]][it].append(gt[b])
                 all_rot_err[cls[b]][it].append(r_dist)
                 all_trans_err[cls[b]][it].append(t_dist)
+            if with_icp:   # an undetected object is scored as the loop scores it
+                est = src[b] if undetected else poses_icp[b]
+                r_dist, t_dist = (1000, 1000) if undetected else calc_rt_dist_m(est, gt[b])
+                for k, v in enumerate((r_dist, t_dist, est, gt[b])):
+                    icp_lists[k][cls[b]][0].append(v)
     # several ranks refine disjoint shards (one process per GPU): the metrics are over ALL pairs, so the per-class lists are merged in
     # rank order on every rank before scoring (the reference scores one list in one process)
     import torch.distributed as dist
@@ -320,11 +371,15 @@ def pred_eval(config, refiner, batches, evaluator, result_file=None, logger=None
     merged = False
     if merge_ranks and dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
         parts = [None] * dist.get_world_size()
-        dist.all_gather_object(parts, (all_rot_err, all_trans_err, all_poses_est, all_poses_gt))
+        dist.all_gather_object(parts, (all_rot_err, all_trans_err, all_poses_est, all_poses_gt, icp_lists))
         for k, mine in enumerate((all_rot_err, all_trans_err, all_poses_est, all_poses_gt)):
             for c in range(n_cls):
                 for it in range(n_it):
                     mine[c][it] = [x for part in parts for x in part[k][c][it]]
+        if with_icp:
+            for k, mine in enumerate(icp_lists):
+                for c in range(n_cls):
+                    mine[c][0] = [x for part in parts for x in part[4][k][c][0]]
         merged = True
         if dist.get_rank() != 0:
             result_file = None   # one result cache, written by rank 0
@@ -345,4 +400,18 @@ def pred_eval(config, refiner, batches, evaluator, result_file=None, logger=None
     out["arp_2d"] = evaluator.evaluate_pose_arp_2d(config, all_poses_est, all_poses_gt, output_dir=None, logger=logger)
     out["all_rot_err"], out["all_trans_err"] = all_rot_err, all_trans_err
     out["merged_over_ranks"] = merged
+    if with_icp:
+        # one row, as the reference's PRECOMPUTED_ICP branch scores it (tester.py:253-330) -- on a copy of the config, since that
+        # branch sets the global config.TEST.test_iter = 1
+        cfg1 = copy.deepcopy(config)
+        cfg1.TEST.test_iter = 1
+        icp_rot, icp_trans, icp_est, icp_gt = icp_lists
+        line = "evaluate ICP ({} iterations, gate {} m):".format(int(config.TEST.ICP_ITER), float(config.TEST.ICP_MAX_DIST))
+        print(line)
+        if logger:
+            logger.info(line)
+        out["icp"] = {"pose": evaluator.evaluate_pose(cfg1, icp_est, icp_gt, logger),
+                      "add": evaluator.evaluate_pose_add(cfg1, icp_est, icp_gt, output_dir=None, logger=logger),
+                      "arp_2d": evaluator.evaluate_pose_arp_2d(cfg1, icp_est, icp_gt, output_dir=None, logger=logger),
+                      "all_rot_err": icp_rot, "all_trans_err": icp_trans}
     return out

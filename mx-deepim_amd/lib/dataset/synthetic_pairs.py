@@ -3,11 +3,14 @@ procedural textured meshes, GT pose uniform on SO(3) with z ~ U(0.6, 1.2) m, ini
 over uniform noise.  Batches are built ON the device by the HIP rasteriser (lib/utils/synthetic.py) with the reference's blob names
 (deepim/core/loader.py:35-41, :164-193), one list entry per batch of `batch_pairs` pairs of this rank's shard."""
 import numpy as np
+import torch
 
 from lib.dataset.evaluation import PoseEvaluator
 from lib.render_hip.render_py_multi import Render_Py
 from lib.utils import synthetic as syn
 from lib.utils.dist_utils import even_shard_range, shard_range
+
+ICP_WALL_M = 1.5   # observed background depth of the synthetic pairs when the depth ICP is on
 
 
 class SyntheticPairs(object):
@@ -39,9 +42,17 @@ class SyntheticPairs(object):
     def test_batches(self):
         # the full test graph also scores the flow head (tester.py:500-512): its labels need the two depth planes of the pair record
         with_depth = bool(self.config.network.PRED_FLOW and not self.config.TEST.FAST_TEST)
+        # the depth ICP after the loop (TEST.ICP_ITER > 0) reads an observed depth: the GT render over a flat wall at ICP_WALL_M, which
+        # gives its gate something to reject
+        icp = int(self.config.TEST.get("ICP_ITER", 0) or 0) > 0
         for i in self.batch_ids:
             b = syn.build_device_batch(self.render_machine, self.batch_pairs, seed=self.seed + 1000 * (i + 1), n_classes=len(self.classes),
-                                       pixel_means=self.config.network.PIXEL_MEANS, device=self.device, with_depth=with_depth)
+                                       pixel_means=self.config.network.PIXEL_MEANS, device=self.device, with_depth=with_depth or icp)
+            if icp:
+                d = b["depth_gt_observed"]
+                b["depth_observed"] = torch.where(d > 0, d, torch.full_like(d, ICP_WALL_M))
+                if not with_depth:
+                    del b["depth_gt_observed"], b["depth_rendered"]
             b["pose_observed"] = b["pose_gt"]
             yield b
 

@@ -40,6 +40,8 @@ SIGNATURES = {
     "dim_depth_to_flow": (I, [P, P, P, P, I, I, I, P, P, P]),
     "dim_flow_epe_workspace_bytes": (L, [I]),
     "dim_flow_epe_sums": (I, [P, P, P, P, I, I, I, P, P, I, P]),
+    "dim_icp_workspace_bytes": (L, [I, I, I]),
+    "dim_icp_refine": (I, [P, P, P, P, P, P, P, I, I, I, I, F, P, P, P, P, P]),
     "dim_refiner_create": (I, [P, P, P, P, I, P]),
     "dim_refiner_run": (I, [P, P, P, P, P, P, P, P, P, P, P]),
     "dim_refiner_run_k": (I, [P, P, P, P, P, P, P, P, P, P, P, P]),

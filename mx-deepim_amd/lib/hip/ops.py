@@ -204,6 +204,34 @@ def flow_epe_sums(flow_pred, flow_gt, visible, depth_rendered, sums=None, accumu
     return sums
 
 
+STATUS_ICP_FEW_POINTS = 32   # DIM_STATUS_ICP_FEW_POINTS: an ICP iteration found < 64 inliers or a singular system (no update)
+
+
+def icp_workspace(B, H, W, device):
+    return torch.empty((max(lib().dim_icp_workspace_bytes(B, H, W), 8) // 8,), dtype=torch.float64, device=device)
+
+
+def icp_refine(depth_rendered, depth_observed, pose_in, K, iters, max_dist, mask_observed=None, bbox=None, K_per_sample=None,
+               pose_out=None, stats=None, status=None, workspace=None):
+    """projective point-to-plane ICP of dim_icp_refine (restated by tests/icp_reference.py): depth_rendered (B,1,H,W) rendered at
+    pose_in (B,3,4), depth_observed (B,1,H,W) metres; K: the host 3x3 used for every pair unless K_per_sample ((B,3,3) / (B,9),
+    as render_batch takes it) is given; bbox (B,4) int32 of the render (None = whole frame).  -> pose_out (B,3,4);
+    stats (B,iters,2) = (inliers, rms residual) per iteration, status (B,) int32: DIM_STATUS_ICP_FEW_POINTS is OR-ed in."""
+    B, _, H, W = depth_rendered.shape
+    assert depth_observed.shape == depth_rendered.shape and tuple(pose_in.shape) == (B, 3, 4)
+    assert mask_observed is None or mask_observed.shape == depth_rendered.shape
+    pose_out = pose_out if pose_out is not None else _new((B, 3, 4), pose_in)
+    if workspace is None:
+        workspace = icp_workspace(B, H, W, pose_in.device)
+    kps = intrinsics_per_sample(K_per_sample, B, pose_in.device)
+    keep, kp = host_f32(K, 9)
+    opt = lambda t, dt=f32: dptr(t, dt) if t is not None else None  # noqa: E731
+    check(lib().dim_icp_refine(dptr(depth_rendered, f32), dptr(depth_observed, f32), opt(mask_observed), opt(bbox, i32), dptr(pose_in, f32),
+                               kp, opt(kps), B, H, W, int(iters), float(max_dist), dptr(workspace, torch.float64), dptr(pose_out, f32),
+                               opt(stats), opt(status, i32), current_stream()))
+    return pose_out
+
+
 STATUS_BAD_K = 16   # DIM_STATUS_BAD_K: dim_raster_render_k drew the sample as background (fx <= 0, fy <= 0 or a non-finite entry)
 
 
