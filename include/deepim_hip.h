@@ -40,6 +40,7 @@ extern "C" {
 #define DIM_STATUS_BAD_FACE 8      /* dim_raster_render*: a z-buffer key named a face outside the mesh (pixel left black) */
 #define DIM_STATUS_BAD_K 16        /* dim_raster_render_k: the sample's K has fx <= 0, fy <= 0 or a non-finite entry (rendered as background) */
 #define DIM_STATUS_ICP_FEW_POINTS 32 /* dim_icp_refine: an iteration found fewer than 64 inliers or a singular system (no update) */
+#define DIM_STATUS_HYP_NO_SCORE 64  /* dim_pose_score: fewer than 64 counted pixels, a constant plane or a non-finite sum (score -inf) */
 
 const char* dim_last_error(void);
 /* library / device probe: fills name (<= n bytes), returns number of compute units or <0 */
@@ -159,6 +160,38 @@ long dim_icp_workspace_bytes(int B, int H, int W);
 int dim_icp_refine(const float* depth_rendered, const float* depth_observed, const float* mask_observed, const int* bbox, const float* pose_in,
                    const float* K9, const float* K_per_sample, int B, int H, int W, int iters, float max_dist, void* workspace,
                    float* pose_out, float* stats, int* status, void* stream);
+
+/* ---------------------------------------------------------------- multi-hypothesis refinement (several starting poses per pair)
+ * Samples are pair-major: sample b = p * N + h of P pairs with N hypotheses each.  Restated in float64 by tests/hyp_reference.py.
+ * dim_hyp_expand: pose_out (P*N,3,4) from pose_in (P,3,4) and rot_table (N,3,3) device f32: pose_out[p*N+h] = [R_h R_p | t_p]
+ *   (a rotation about the object origin in the camera frame, products in float64); h = 0 is a bit-exact copy (rot_table[0] is
+ *   not read).
+ * dim_hyp_broadcast: dst[(p*N+h) * row_words + k] = src[p * row_words + k] for 4-byte words (a plane, a K row, a class index):
+ *   every pair's row into its N sample rows in one launch; float4 when row_words % 4 == 0 and both pointers are 16-byte aligned.
+ * dim_pose_score: one score per sample over S = {pixels inside bbox[b] (B,4 int32 {min_x,max_x,min_y,max_y} inclusive, clipped to
+ *   the frame; NULL = whole frame) with depth_rendered (B,1,H,W) > 0}:
+ *     DIM_HYP_SCORE_RGB:   zero-mean normalised cross-correlation of a = sum_c image_observed and r = sum_c image_rendered
+ *                          (both (B,3,H,W)), in [-1, 1];
+ *     DIM_HYP_SCORE_DEPTH: among the pixels of S with depth_observed (B,1,H,W) > 0, the fraction with |D_r - D_o| < tau (metres).
+ *   Fewer than 64 counted pixels, for RGB a plane that is constant over S, or a non-finite result give score[b] = -inf and OR
+ *   DIM_STATUS_HYP_NO_SCORE into status[b] (B int32, may be NULL).  Sums: float64 per lane (shifted by the bbox's first pixel),
+ *   across lanes, waves and workgroups in a fixed order, no atomics: a replay is bit-identical.  workspace:
+ *   dim_pose_score_workspace_bytes(B, H, W) bytes, 8-byte aligned, no initialisation.  2 launches.
+ * dim_hyp_select: per pair, choice[p] = the h of the largest finite score[p*N+h] (ties: the smaller h; none finite: 0, and
+ *   DIM_STATUS_HYP_NO_SCORE is OR-ed into the selected last status row); then gathers poses_iter (T,P*N,3,4) -> poses_sel (T,P,3,4),
+ *   status_iter (T,P*N) -> status_sel (T,P) int32 and pose_icp (P*N,3,4) -> pose_icp_sel (P,3,4) (each pair optional: NULL, NULL).
+ *   status_load (P*N int32 or NULL): bits of the load-time hypothesis renders, OR-ed into the selected last status row (the loop
+ *   rewrites status_iter, so they would be lost there).  One launch.
+ * Bad sizes, an unknown mode, tau <= 0 for the depth score or a NULL required pointer return DIM_ERR_ARG before anything is enqueued. */
+#define DIM_HYP_SCORE_RGB 0
+#define DIM_HYP_SCORE_DEPTH 1
+int dim_hyp_expand(const float* rot_table, const float* pose_in, int P, int N, float* pose_out, void* stream);
+int dim_hyp_broadcast(void* dst, const void* src, int P, int N, long row_words, void* stream);
+long dim_pose_score_workspace_bytes(int B, int H, int W);
+int dim_pose_score(const float* image_observed, const float* image_rendered, const float* depth_observed, const float* depth_rendered,
+                   const int* bbox, int B, int H, int W, int mode, float tau, void* workspace, float* score, int* status, void* stream);
+int dim_hyp_select(const float* score, int P, int N, int T, const float* poses_iter, const int* status_iter, const int* status_load,
+                   const float* pose_icp, int* choice, float* poses_sel, int* status_sel, float* pose_icp_sel, void* stream);
 
 /* ---------------------------------------------------------------- data layer (test batches from raw file pixels)
  * The loader uploads what the image files hold -- obs_bgr / ren_bgr (B,H,W,3) uint8 in B,G,R order (cv2.IMREAD_COLOR), depth_rendered

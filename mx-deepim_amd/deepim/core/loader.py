@@ -345,7 +345,8 @@ TEST_LABEL_OF_KIND = {"mask_gt_observed": "mask_gt_observed", "box_gt_observed":
 class TestDataLoader(_DeviceLoader):
     """reference deepim/core/loader.py:20-117.  Every TEST.INIT_MASK kind of get_pair_mask (image.py:367-476), TEST.MASK_DILATE and
     INPUT_DEPTH are built on the device; `source` (a RawPairSource) replaces the files for the shipped kind 'box_rendered' only.
-    depth_observed is staged for INPUT_DEPTH and for the depth ICP after the loop (TEST.ICP_ITER > 0)."""
+    depth_observed is staged for INPUT_DEPTH, for the depth ICP after the loop (TEST.ICP_ITER > 0) and for the depth score of several
+    hypotheses per pair (TEST.HYP_NUM > 1, TEST.HYP_SCORE 'depth')."""
 
     def __init__(self, pairdb, config, batch_size=1, shuffle=False, device="cuda:0", workers=8, source=None, height=480, width=640,
                  cache=None):
@@ -357,11 +358,13 @@ class TestDataLoader(_DeviceLoader):
         if self.input_mask and self.init_mask not in ("box_rendered",) + tuple(TEST_LABEL_OF_KIND):
             raise Exception("Unknown init mask type: {}".format(self.init_mask))
         self.label_key = TEST_LABEL_OF_KIND.get(self.init_mask) if self.input_mask else None
-        self.stage_depth_observed = self.input_depth or int(cfg.TEST.get("ICP_ITER", 0) or 0) > 0
+        hyp_depth = int(cfg.TEST.get("HYP_NUM", 1) or 1) > 1 and cfg.TEST.get("HYP_SCORE", "rgb") == "depth"
+        self.stage_depth_observed = self.input_depth or int(cfg.TEST.get("ICP_ITER", 0) or 0) > 0 or hyp_depth
         if source is not None and (self.label_key or self.input_depth):
             raise NotImplementedError("a RawPairSource carries colour + rendered depth only: INIT_MASK 'box_rendered' without INPUT_DEPTH")
         if source is not None and self.stage_depth_observed:
-            raise NotImplementedError("a RawPairSource carries colour + rendered depth only: no observed depth for TEST.ICP_ITER > 0")
+            raise NotImplementedError("a RawPairSource carries colour + rendered depth only: no observed depth for TEST.ICP_ITER > 0 "
+                                      "or TEST.HYP_SCORE 'depth'")
         self.source = source
         self.pairdb, self.config = pairdb, config
         # per-pair cameras of the re-render, resolved over the whole pairdb before any shuffle or split (the rule is sticky in pair order)

@@ -19,6 +19,41 @@ import torch
 from lib.hip import ops
 from deepim.symbols.deepIM_flownet import FlowNetHip
 
+HYP_SCORES = ("rgb", "depth")
+
+
+def hyp_settings(cfg):
+    """-> (HYP_NUM, HYP_ROT_DEG, HYP_SCORE, HYP_DEPTH_TAU) of cfg.TEST, checked; ValueError names the bad key"""
+    T = cfg.TEST
+    n = T.get("HYP_NUM", 1)
+    if isinstance(n, bool) or not float(n).is_integer() or int(n) < 1:
+        raise ValueError("TEST.HYP_NUM must be an integer >= 1 (1 = one hypothesis per pair, off), got {!r}".format(n))
+    deg = float(T.get("HYP_ROT_DEG", 30.0))
+    if not np.isfinite(deg):
+        raise ValueError("TEST.HYP_ROT_DEG must be finite, got {!r}".format(T.get("HYP_ROT_DEG")))
+    score = T.get("HYP_SCORE", "rgb")
+    if score not in HYP_SCORES:
+        raise ValueError("TEST.HYP_SCORE must be one of {}, got {!r}".format(HYP_SCORES, score))
+    tau = float(T.get("HYP_DEPTH_TAU", 0.02))
+    if not (np.isfinite(tau) and tau > 0):
+        raise ValueError("TEST.HYP_DEPTH_TAU must be a finite distance > 0 (metres), got {!r}".format(T.get("HYP_DEPTH_TAU")))
+    return int(n), deg, score, tau
+
+
+def hypothesis_rotations(N, rot_deg):
+    """(N,3,3) float64: R_0 = I; R_h (h >= 1) = the Rodrigues rotation by rot_deg about axis h-1 of a Fibonacci sphere of N-1 points,
+    z = 1 - (2k+1)/(N-1), r = sqrt(1-z^2), phi = k pi (3 - sqrt 5), axis = (r cos phi, r sin phi, z).  Hypothesis h starts the
+    loop from [R_h R_p | t_p]: the pair's pose turned about the object origin in the camera frame."""
+    R = np.tile(np.eye(3), (N, 1, 1))
+    M, th = N - 1, np.radians(rot_deg)
+    for k in range(M):
+        z = 1.0 - (2.0 * k + 1.0) / M
+        r, phi = np.sqrt(max(0.0, 1.0 - z * z)), k * np.pi * (3.0 - np.sqrt(5.0))
+        a = np.array([r * np.cos(phi), r * np.sin(phi), z])
+        Kx = np.array([[0.0, -a[2], a[1]], [a[2], 0.0, -a[0]], [-a[1], a[0], 0.0]])
+        R[k + 1] = np.eye(3) + np.sin(th) * Kx + (1.0 - np.cos(th)) * (Kx @ Kx)
+    return R
+
 
 class Predictor(object):
     """Reference: binds a MutableModule and calls forward (tester.py:27-56).  Here: owns a FlowNetHip."""
@@ -34,19 +69,31 @@ class Predictor(object):
 
 
 class Refiner(object):
+    """batch_size = P pairs per loaded batch.  With TEST.HYP_NUM = N > 1 every pair is refined from N starting poses, as the samples
+    b = p * N + h of one batch (the Predictor is built for P * N samples); after the loop each sample's last pose is rendered and
+    scored against the observed image (TEST.HYP_SCORE) and the best hypothesis of each pair is selected, all inside the same graph."""
+
     def __init__(self, config, predictor, render_machine, batch_size, capture_graph=False):
         cfg = config
         if cfg.network.INPUT_MASK and cfg.network.PRED_MASK and cfg.TEST.UPDATE_MASK not in ("box_rendered", "init"):
             # same restriction as the released loop (tester.py:579-587)
             raise Exception("Unknown UPDATE_MASK type: {}".format(cfg.TEST.UPDATE_MASK))
+        self.hyp_num, self.hyp_rot_deg, self.hyp_score_mode, self.hyp_tau = hyp_settings(cfg)
+        N = self.hyp_num
+        if N > 1 and predictor.net.B != batch_size * N:
+            raise ValueError("Refiner: {} pairs x TEST.HYP_NUM {} = {} samples, but the Predictor was built for {} samples".format(
+                batch_size, N, batch_size * N, predictor.net.B))
+        if N > 1 and hasattr(render_machine, "normals"):
+            raise ValueError("TEST.HYP_NUM > 1 is not supported with the lit ModelNet renderer")
         self.cfg = cfg
         self.predictor = predictor
         self.net = predictor.net
         self.render_machine = render_machine
-        self.B = batch_size
+        self.P, self.N = batch_size, N
+        self.B = batch_size * N   # samples
         self.test_iter = int(cfg.TEST.test_iter)
         d = self.net.device
-        B, H, W = batch_size, 480, 640
+        B, H, W = self.B, 480, 640
         self.batch = {
             "image_observed": torch.zeros((B, 3, H, W), dtype=torch.float32, device=d),
             "image_rendered": torch.zeros((B, 3, H, W), dtype=torch.float32, device=d),
@@ -87,14 +134,43 @@ class Refiner(object):
         self.icp_iter = int(cfg.TEST.get("ICP_ITER", 0) or 0)
         self.icp_max_dist = float(cfg.TEST.get("ICP_MAX_DIST", 0.02))
         self.depth_observed = self.pose_icp = self.icp_stats = self.status_icp = None
-        if self.icp_iter > 0:
+        hyp_depth = N > 1 and self.hyp_score_mode == "depth"
+        if self.icp_iter > 0 or hyp_depth:
             self.depth_observed = self.batch["depth_observed"] if self.input_depth else torch.zeros((B, 1, H, W), dtype=torch.float32, device=d)
+        if self.icp_iter > 0:
             self.depth_icp = torch.zeros((B, 1, H, W), dtype=torch.float32, device=d)
             self.bbox_icp = torch.zeros((B, 4), dtype=torch.int32, device=d)
             self.pose_icp = torch.zeros((B, 3, 4), dtype=torch.float32, device=d)
             self.icp_stats = torch.zeros((B, self.icp_iter, 2), dtype=torch.float32, device=d)
             self.status_icp = torch.zeros((B,), dtype=torch.int32, device=d)
             self.icp_work = ops.icp_workspace(B, H, W, d)
+        # several hypotheses per pair (TEST.HYP_NUM > 1): the loaded pairs land in `pair` (P rows) and are expanded into the B = P*N
+        # sample rows by load(); after the loop: the render at the last pose, the scores, the choice and the selected outputs
+        self.pair = self.hyp_score = self.hyp_choice = self.poses_sel = self.status_sel = self.pose_icp_sel = None
+        if N > 1:
+            P = batch_size
+            plane = lambda c: torch.zeros((P, c, H, W), dtype=torch.float32, device=d)  # noqa: E731
+            self.pair = {"image_observed": plane(3), "image_rendered": plane(3), "mask_observed": plane(1), "mask_rendered": plane(1),
+                         "src_pose": torch.zeros((P, 3, 4), dtype=torch.float32, device=d),
+                         "class_index": torch.zeros((P,), dtype=torch.int32, device=d),
+                         "K": torch.zeros((P, 9), dtype=torch.float32, device=d)}
+            if self.depth_observed is not None or self.input_depth:
+                self.pair["depth_observed"] = plane(1)
+            if self.input_depth:
+                self.pair["depth_rendered"] = plane(1)
+            self.hyp_table = torch.from_numpy(hypothesis_rotations(N, self.hyp_rot_deg).astype(np.float32).reshape(N, 9)).to(d)
+            self.bbox_hyp = torch.zeros((B, 4), dtype=torch.int32, device=d)
+            self.status_hyp = torch.zeros((B,), dtype=torch.int32, device=d)   # render bits of the load-time hypothesis renders
+            self.image_sc = torch.zeros((B, 3, H, W), dtype=torch.float32, device=d)
+            self.depth_sc = torch.zeros((B, 1, H, W), dtype=torch.float32, device=d)
+            self.bbox_sc = torch.zeros((B, 4), dtype=torch.int32, device=d)
+            self.score_work = ops.pose_score_workspace(B, H, W, d)
+            self.hyp_score = torch.zeros((B,), dtype=torch.float32, device=d)
+            self.hyp_choice = torch.zeros((P,), dtype=torch.int32, device=d)
+            self.poses_sel = torch.zeros((self.test_iter, P, 3, 4), dtype=torch.float32, device=d)
+            self.status_sel = torch.zeros((self.test_iter, P), dtype=torch.int32, device=d)
+            if self.icp_iter > 0:
+                self.pose_icp_sel = torch.zeros((P, 3, 4), dtype=torch.float32, device=d)
         render_machine.reserve(B)
         # ModelNet: the lit renderer takes a per-render light intensity drawn on the host (tester.py:227-230)
         self.lit = hasattr(render_machine, "normals")
@@ -105,27 +181,34 @@ class Refiner(object):
 
     # ------------------------------------------------------------------------------------------
     def load(self, image_observed, image_rendered, mask_observed, mask_rendered, src_pose, class_index, depth_observed=None,
-             depth_rendered=None, K=None):
+             depth_rendered=None, K=None, hyp_poses=None):
         """copy one batch of blobs (any device) into the resident buffers (the depth planes: INPUT_DEPTH graphs only; depth_observed
-        also when TEST.ICP_ITER > 0).
+        also when TEST.ICP_ITER > 0 or the depth hypothesis score is on).
         K: None (every re-render uses the config K) or the camera of each pair, (B,3,3) or (B,9), any device: the unlit re-renders of
-        this batch use it (the lit ModelNet render ignores K, as the reference's render() closure does)"""
+        this batch use it (the lit ModelNet render ignores K, as the reference's render() closure does)
+        hyp_poses: TEST.HYP_NUM > 1 only: None (hypothesis 0 = the loaded pair, the others generated from it) or (P,N,3,4) starting
+        poses given by the caller, all of them rendered"""
+        self._check_hyp_poses(hyp_poses)
         self._load_K(K)
         b = self.batch
+        dst = self._load_targets()
         if self.input_depth:
             assert depth_observed is not None and depth_rendered is not None, "INPUT_DEPTH: the loop needs depth_observed / depth_rendered"
-            b["depth_observed"].copy_(torch.as_tensor(depth_observed))
-            self.init["depth_rendered"].copy_(torch.as_tensor(depth_rendered))
-        elif self.icp_iter > 0:
+            dst["depth_observed"].copy_(torch.as_tensor(depth_observed))
+            dst["depth_rendered"].copy_(torch.as_tensor(depth_rendered))
+        elif self.depth_observed is not None:
             if depth_observed is None:
-                raise ValueError("TEST.ICP_ITER > 0: the ICP stage needs depth_observed")
-            self.depth_observed.copy_(torch.as_tensor(depth_observed))
-        b["image_observed"].copy_(torch.as_tensor(image_observed))
-        self.init["image_rendered"].copy_(torch.as_tensor(image_rendered))
-        self.init["mask_observed"].copy_(torch.as_tensor(mask_observed))
-        self.init["mask_rendered"].copy_(torch.as_tensor(mask_rendered))
-        self.pose_init.copy_(torch.as_tensor(src_pose))
-        b["class_index"].copy_(torch.as_tensor(class_index).to(torch.int32))
+                raise ValueError("TEST.ICP_ITER > 0: the ICP stage needs depth_observed" if self.icp_iter > 0 else
+                                 "TEST.HYP_SCORE 'depth': the hypothesis score needs depth_observed")
+            dst["depth_observed"].copy_(torch.as_tensor(depth_observed))
+        dst["image_observed"].copy_(torch.as_tensor(image_observed))
+        dst["image_rendered"].copy_(torch.as_tensor(image_rendered))
+        dst["mask_observed"].copy_(torch.as_tensor(mask_observed))
+        dst["mask_rendered"].copy_(torch.as_tensor(mask_rendered))
+        dst["src_pose"].copy_(torch.as_tensor(src_pose))
+        dst["class_index"].copy_(torch.as_tensor(class_index).to(torch.int32))
+        if self.N > 1:
+            self._expand(hyp_poses)
         if self.lit and self.test_iter > 1:
             # same draws, same order as the reference: sample by sample, one np.random.uniform(0.9,1.1,3) per re-render
             li = np.stack([[np.random.uniform(0.9, 1.1, size=(3,)) for _ in range(self.test_iter - 1)] for _ in range(self.B)])
@@ -136,26 +219,83 @@ class Refiner(object):
             self.per_pair_K = False
             return
         K = torch.as_tensor(K)
-        if tuple(K.shape) not in ((self.B, 3, 3), (self.B, 9)):
-            raise ValueError("per-pair K must be ({0},3,3) or ({0},9), got {1}".format(self.B, tuple(K.shape)))
-        self.K_pair.copy_(K.reshape(self.B, 9))
+        if tuple(K.shape) not in ((self.P, 3, 3), (self.P, 9)):
+            raise ValueError("per-pair K must be ({0},3,3) or ({0},9), got {1}".format(self.P, tuple(K.shape)))
+        (self.K_pair if self.N == 1 else self.pair["K"]).copy_(K.reshape(self.P, 9))
         self.per_pair_K = True
+
+    def _load_targets(self):
+        """where load() puts each blob: the resident loop buffers, or with several hypotheses the P pair rows that _expand reads"""
+        if self.N > 1:
+            return self.pair
+        t = {"image_observed": self.batch["image_observed"], "image_rendered": self.init["image_rendered"],
+             "mask_observed": self.init["mask_observed"], "mask_rendered": self.init["mask_rendered"], "src_pose": self.pose_init,
+             "class_index": self.batch["class_index"]}
+        if self.depth_observed is not None or self.input_depth:
+            t["depth_observed"] = self.batch["depth_observed"] if self.input_depth else self.depth_observed
+        if self.input_depth:
+            t["depth_rendered"] = self.init["depth_rendered"]
+        return t
+
+    def _check_hyp_poses(self, hyp_poses):
+        if hyp_poses is None:
+            return
+        if self.N == 1:
+            raise ValueError("hyp_poses needs TEST.HYP_NUM > 1")
+        if tuple(torch.as_tensor(hyp_poses).shape) != (self.P, self.N, 3, 4):
+            raise ValueError("hyp_poses must be ({},{},3,4), got {}".format(self.P, self.N, tuple(torch.as_tensor(hyp_poses).shape)))
+
+    def _expand(self, hyp_poses=None):
+        """TEST.HYP_NUM > 1, eagerly once per batch: the P loaded pairs -> the B = P*N samples.  Starting poses (dim_hyp_expand, or the
+        caller's), the observed blobs, class and K broadcast (dim_hyp_broadcast), and the hypotheses rendered as the loop re-renders
+        (their mask_observed: the box of their own render under INIT_MASK 'box_rendered').  Without hyp_poses hypothesis 0 keeps the
+        loaded planes.  Everything lands in the pristine buffers (`init`, pose_init) a replayed graph starts from.  The render's status
+        bits stay in status_hyp; the selection ORs the winner's into its last status row (status_iter itself is rewritten by the loop)."""
+        N, P, pr, b, init = self.N, self.P, self.pair, self.batch, self.init
+        if hyp_poses is not None:
+            self.pose_init.copy_(torch.as_tensor(hyp_poses).reshape(self.B, 3, 4))
+        else:
+            ops.hyp_expand(self.hyp_table, pr["src_pose"], N, out=self.pose_init)
+        ops.hyp_broadcast(b["image_observed"], pr["image_observed"], N)
+        ops.hyp_broadcast(b["class_index"], pr["class_index"], N)
+        if "depth_observed" in pr:
+            ops.hyp_broadcast(b["depth_observed"] if self.input_depth else self.depth_observed, pr["depth_observed"], N)
+        extra = {}
+        if self.per_pair_K:
+            ops.hyp_broadcast(self.K_pair, pr["K"], N)
+            extra["K"] = self.K_pair
+        if self.input_depth:
+            extra["depth"] = init["depth_rendered"]
+        ops.fill(self.status_hyp, 0)
+        self.render_machine.render_batch(b["class_index"], self.pose_init, image=init["image_rendered"], mask=init["mask_rendered"],
+                                         bbox=self.bbox_hyp, plane_means=self.net.plane_means, mask_thr=0.2, status=self.status_hyp, **extra)
+        if self.cfg.TEST.INIT_MASK == "box_rendered":
+            ops.box_mask(self.bbox_hyp, init["mask_observed"])
+        else:
+            ops.hyp_broadcast(init["mask_observed"], pr["mask_observed"], N)
+        if hyp_poses is None:   # hypothesis 0: the loaded planes and masks
+            for k in ("image_rendered", "mask_rendered", "mask_observed") + (("depth_rendered",) if self.input_depth else ()):
+                row = pr[k].numel() // P
+                ops.copy_rows(init[k], N * row, pr[k], row, P, row)
 
     def load_staged(self, loader, staged):
         """take the next batch straight from a deepim.core.loader.TestDataLoader staging set: the raw pixels it uploaded are turned
         into the resident blobs by dim_test_blobs_from_raw / dim_box_mask on the current stream -- no host blobs, no extra copies"""
-        out = {"image_observed": self.batch["image_observed"], "image_rendered": self.init["image_rendered"],
-               "mask_rendered": self.init["mask_rendered"], "mask_observed": self.init["mask_observed"]}
-        if self.icp_iter > 0:
+        dst = self._load_targets()
+        out = {k: dst[k] for k in ("image_observed", "image_rendered", "mask_rendered", "mask_observed")}
+        if self.depth_observed is not None:
             if not getattr(loader, "stage_depth_observed", False):
-                raise ValueError("TEST.ICP_ITER > 0: the loader does not stage depth_observed")
-            out["depth_observed"] = self.depth_observed
+                raise ValueError(("TEST.ICP_ITER > 0" if self.icp_iter > 0 else "TEST.HYP_SCORE 'depth'") +
+                                 ": the loader does not stage depth_observed")
+            out["depth_observed"] = dst["depth_observed"]
         loader.build_blobs(staged, out=out)
-        ops.copy(self.pose_init, staged.d_pose)
-        ops.copy(self.batch["class_index"], staged.d_cls)
+        ops.copy(dst["src_pose"], staged.d_pose)
+        ops.copy(dst["class_index"], staged.d_cls)
         self.per_pair_K = bool(getattr(loader, "per_pair_K", False))
         if self.per_pair_K:
-            ops.copy(self.K_pair, staged.d_K)
+            ops.copy(self.K_pair if self.N == 1 else self.pair["K"], staged.d_K)
+        if self.N > 1:
+            self._expand()
         loader.release(staged)   # the last read of the staging set's device mirrors is enqueued
         if self.lit and self.test_iter > 1:
             li = np.stack([[np.random.uniform(0.9, 1.1, size=(3,)) for _ in range(self.test_iter - 1)] for _ in range(self.B)])
@@ -215,6 +355,22 @@ class Refiner(object):
         ops.copy(b["src_pose"], pose)  # the blob ends up as the reference leaves it: the pose the last forward used
         if self.icp_iter > 0:
             self._icp(self.poses_iter[self.test_iter - 1])
+        if self.N > 1:
+            self._select(self.poses_iter[self.test_iter - 1])
+
+    def _select(self, pose):
+        """several hypotheses: render the last pose of every sample (image, depth and the box of every drawn pixel; the pair's K when
+        loaded), score it against the observed image (dim_pose_score) and keep the best hypothesis of each pair (dim_hyp_select)"""
+        b, last = self.batch, self.status_iter[self.test_iter - 1]
+        extra = {"K": self.K_pair} if self.per_pair_K else {}
+        self.render_machine.render_batch(b["class_index"], pose, image=self.image_sc, depth=self.depth_sc, bbox=self.bbox_sc,
+                                         plane_means=self.net.plane_means, mask_thr=0.0, status=last, **extra)
+        depth_mode = self.hyp_score_mode == "depth"
+        ops.pose_score(b["image_observed"], self.image_sc, self.depth_sc, self.hyp_score_mode, self.hyp_tau,
+                       depth_observed=self.depth_observed if depth_mode else None, bbox=self.bbox_sc, score=self.hyp_score, status=last,
+                       workspace=self.score_work)
+        ops.hyp_select(self.hyp_score, self.N, self.poses_iter, status_iter=self.status_iter, status_load=self.status_hyp, pose_icp=self.pose_icp,
+                       choice=self.hyp_choice, poses_sel=self.poses_sel, status_sel=self.status_sel, pose_icp_sel=self.pose_icp_sel)
 
     def _icp(self, pose):
         """depth ICP from the loop's last pose: render its depth and box (the pair's K when loaded), then dim_icp_refine against
@@ -232,7 +388,9 @@ class Refiner(object):
 
     def refine(self):
         """run test_iter iterations on the loaded batch; returns poses_iter (test_iter,B,3,4) (device).  With TEST.ICP_ITER > 0 the
-        ICP stage runs after them (inside the same graph) and leaves its pose in pose_icp (B,3,4)."""
+        ICP stage runs after them (inside the same graph) and leaves its pose in pose_icp (B,3,4).  With TEST.HYP_NUM > 1 it returns
+        the selected hypothesis of each pair, poses_sel (test_iter,P,3,4); poses_iter (all P*N samples), hyp_score (P*N,),
+        hyp_choice (P,), status_sel (test_iter,P) and pose_icp_sel (P,3,4) stay readable on the Refiner."""
         if self.graph is not None and self._graph_per_pair_K != self.per_pair_K:
             self.graph = None   # captured with the other render (uniform / per-pair K): capture this one
         if self._want_graph and self.graph is None:
@@ -251,7 +409,7 @@ class Refiner(object):
             self.graph.replay()
         else:
             self._loop()
-        return self.poses_iter
+        return self.poses_iter if self.N == 1 else self.poses_sel
 
 
 class FlowEPE(object):
@@ -322,7 +480,10 @@ def pred_eval(config, refiner, batches, evaluator, result_file=None, logger=None
     pickle protocol 2 (:650-654) and runs evaluate_pose / evaluate_pose_add / evaluate_pose_arp_2d (:664-673).
     evaluator: lib.dataset.evaluation.PoseEvaluator.  Returns the three result dicts.
     With TEST.ICP_ITER > 0 the refiner's ICP poses are scored too, as the one-row table of the reference's PRECOMPUTED_ICP branch
-    (tester.py:253-330), under out["icp"] = {pose, add, arp_2d}; every other output and the result cache are those of ICP off."""
+    (tester.py:253-330), under out["icp"] = {pose, add, arp_2d}; every other output and the result cache are those of ICP off.
+    With TEST.HYP_NUM = N > 1 every table, the result cache and out["icp"] score the selected hypothesis of each pair, and out["hyp"]
+    holds per pair the N scores, the choice and the last-iteration rotation / translation error of every hypothesis, plus the rate
+    at which the chosen hypothesis is also the one with the least rotation error.  A batch may carry "hyp_poses" (P,N,3,4)."""
     import copy
     import pickle
 
@@ -336,18 +497,33 @@ def pred_eval(config, refiner, batches, evaluator, result_file=None, logger=None
     # depth ICP after the loop: its own one-row lists [rot_err, trans_err, poses_est, poses_gt][cls][0]
     with_icp = int(config.TEST.get("ICP_ITER", 0) or 0) > 0
     icp_lists = tuple([[[]] for _ in range(n_cls)] for _ in range(4)) if with_icp else None
+    # several hypotheses per pair: [score, choice, rot_err, trans_err, undetected] per pair
+    n_hyp = int(getattr(refiner, "N", 1))
+    hyp_lists = tuple([] for _ in range(5)) if n_hyp > 1 else None
     # flow error of the first forward (:500-512): only the full test graph emits the flow head's output
-    epe = FlowEPE(config, refiner.B, refiner.net.device) if (config.network.PRED_FLOW and not config.TEST.FAST_TEST) else None
+    epe = FlowEPE(config, getattr(refiner, "P", refiner.B), refiner.net.device) if (config.network.PRED_FLOW and not config.TEST.FAST_TEST) else None
     for batch in batches:
+        extra = {"hyp_poses": batch["hyp_poses"]} if batch.get("hyp_poses") is not None else {}
         refiner.load(batch["image_observed"], batch["image_rendered"], batch["mask_observed"], batch["mask_rendered"], batch["src_pose"],
-                     batch["class_index"], depth_observed=batch.get("depth_observed"), K=batch.get("K"))
+                     batch["class_index"], depth_observed=batch.get("depth_observed"), K=batch.get("K"), **extra)
         poses = refiner.refine().cpu().numpy().astype(np.float64)     # ONE device->host copy per batch: (iter, B, 3, 4)
-        poses_icp = refiner.pose_icp.cpu().numpy().astype(np.float64) if with_icp else None
+        if with_icp:
+            poses_icp = (refiner.pose_icp if n_hyp == 1 else refiner.pose_icp_sel).cpu().numpy().astype(np.float64)
         cls = torch.as_tensor(batch["class_index"]).cpu().numpy().astype(int)
         gt = torch.as_tensor(batch["pose_observed"]).cpu().numpy().astype(np.float64)
         src = torch.as_tensor(batch["src_pose"]).cpu().numpy().astype(np.float64)
-        if epe is not None:
-            epe.add(batch, refiner.flow_est_iter[0], skip=np.sum(src.reshape(src.shape[0], -1), axis=1) == -12)
+        if epe is not None:   # defined on hypothesis 0, the loaded render
+            flow0 = refiner.flow_est_iter[0] if n_hyp == 1 else refiner.flow_est_iter[0][::n_hyp].contiguous()
+            epe.add(batch, flow0, skip=np.sum(src.reshape(src.shape[0], -1), axis=1) == -12)
+        if n_hyp > 1:
+            scores = refiner.hyp_score.cpu().numpy().reshape(-1, n_hyp).astype(np.float64)
+            choice = refiner.hyp_choice.cpu().numpy().astype(int)
+            last = refiner.poses_iter[-1].cpu().numpy().astype(np.float64).reshape(-1, n_hyp, 3, 4)
+            for b in range(poses.shape[1]):
+                undetected = bool(np.sum(src[b]) == -12)
+                errs = [(1000, 1000) if undetected else calc_rt_dist_m(last[b, h], gt[b]) for h in range(n_hyp)]
+                for k, v in enumerate((scores[b].tolist(), int(choice[b]), [e[0] for e in errs], [e[1] for e in errs], undetected)):
+                    hyp_lists[k].append(v)
         for b in range(poses.shape[1]):
             # "NO POINT VALID IN INIT POSE" (:419-445): an undetected object comes with pose_rendered = -1 everywhere (sum -12); it is
             # scored with its initial pose and 1000 deg / 1000 m at every iteration instead of being refined
@@ -371,7 +547,7 @@ def pred_eval(config, refiner, batches, evaluator, result_file=None, logger=None
     merged = False
     if merge_ranks and dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
         parts = [None] * dist.get_world_size()
-        dist.all_gather_object(parts, (all_rot_err, all_trans_err, all_poses_est, all_poses_gt, icp_lists))
+        dist.all_gather_object(parts, (all_rot_err, all_trans_err, all_poses_est, all_poses_gt, icp_lists, hyp_lists))
         for k, mine in enumerate((all_rot_err, all_trans_err, all_poses_est, all_poses_gt)):
             for c in range(n_cls):
                 for it in range(n_it):
@@ -380,6 +556,9 @@ def pred_eval(config, refiner, batches, evaluator, result_file=None, logger=None
             for k, mine in enumerate(icp_lists):
                 for c in range(n_cls):
                     mine[c][0] = [x for part in parts for x in part[4][k][c][0]]
+        if hyp_lists is not None:
+            for k, mine in enumerate(hyp_lists):
+                mine[:] = [x for part in parts for x in part[5][k]]
         merged = True
         if dist.get_rank() != 0:
             result_file = None   # one result cache, written by rank 0
@@ -414,4 +593,14 @@ def pred_eval(config, refiner, batches, evaluator, result_file=None, logger=None
                       "add": evaluator.evaluate_pose_add(cfg1, icp_est, icp_gt, output_dir=None, logger=logger),
                       "arp_2d": evaluator.evaluate_pose_arp_2d(cfg1, icp_est, icp_gt, output_dir=None, logger=logger),
                       "all_rot_err": icp_rot, "all_trans_err": icp_trans}
+    if hyp_lists is not None:
+        score, choice, rot, trans, undet = hyp_lists
+        best = [c == int(np.argmin(r)) for c, r, u in zip(choice, rot, undet) if not u]
+        out["hyp"] = {"num": n_hyp, "score": score, "choice": choice, "rot_err": rot, "trans_err": trans, "undetected": undet,
+                      "chosen_is_least_rot_err": float(np.mean(best)) if best else float("nan")}
+        line = "hypotheses: {} per pair, the chosen one has the least rotation error in {:.1f} % of {} pairs".format(
+            n_hyp, 100.0 * out["hyp"]["chosen_is_least_rot_err"], len(best))
+        print(line)
+        if logger:
+            logger.info(line)
     return out

@@ -81,7 +81,8 @@ def test_deepim(args):
 
     B = int(config.TEST.BATCH_PAIRS)
     data = SyntheticPairs(config, args.num_pairs, B, device=device, rank=rank, world=world)
-    predictor = Predictor(config, arg_params, B, device=device)
+    # TEST.HYP_NUM hypotheses per pair are refined side by side: the network runs B pairs x HYP_NUM samples
+    predictor = Predictor(config, arg_params, B * int(config.TEST.get("HYP_NUM", 1) or 1), device=device)
     refiner = Refiner(config, predictor, data.render_machine, B, capture_graph=True)
     result_file = os.path.join(final_output_path, "{}_results.pkl".format(image_set))
     out = pred_eval(config, refiner, data.test_batches(), data.evaluator(), result_file=result_file, logger=logger)

@@ -42,6 +42,11 @@ SIGNATURES = {
     "dim_flow_epe_sums": (I, [P, P, P, P, I, I, I, P, P, I, P]),
     "dim_icp_workspace_bytes": (L, [I, I, I]),
     "dim_icp_refine": (I, [P, P, P, P, P, P, P, I, I, I, I, F, P, P, P, P, P]),
+    "dim_hyp_expand": (I, [P, P, I, I, P, P]),
+    "dim_hyp_broadcast": (I, [P, P, I, I, L, P]),
+    "dim_pose_score_workspace_bytes": (L, [I, I, I]),
+    "dim_pose_score": (I, [P, P, P, P, P, I, I, I, I, F, P, P, P, P]),
+    "dim_hyp_select": (I, [P, I, I, I, P, P, P, P, P, P, P, P, P]),
     "dim_refiner_create": (I, [P, P, P, P, I, P]),
     "dim_refiner_run": (I, [P, P, P, P, P, P, P, P, P, P, P]),
     "dim_refiner_run_k": (I, [P, P, P, P, P, P, P, P, P, P, P, P]),

@@ -232,6 +232,78 @@ def icp_refine(depth_rendered, depth_observed, pose_in, K, iters, max_dist, mask
     return pose_out
 
 
+STATUS_HYP_NO_SCORE = 64   # DIM_STATUS_HYP_NO_SCORE: dim_pose_score had < 64 counted pixels, a constant plane or a non-finite sum
+HYP_SCORE_ID = {"rgb": 0, "depth": 1}   # DIM_HYP_SCORE_RGB / DIM_HYP_SCORE_DEPTH
+
+
+def hyp_expand(rot_table, pose_in, N, out=None):
+    """dim_hyp_expand: rot_table (N,3,3) or (N,9) f32 CUDA, pose_in (P,3,4) -> (P*N,3,4), sample p*N+h = [R_h R_p | t_p], h = 0 the
+    pair's pose bit for bit"""
+    P = pose_in.shape[0]
+    assert rot_table.numel() == 9 * N and tuple(pose_in.shape) == (P, 3, 4)
+    out = out if out is not None else _new((P * N, 3, 4), pose_in)
+    assert tuple(out.shape) == (P * N, 3, 4)
+    check(lib().dim_hyp_expand(dptr(rot_table, f32), dptr(pose_in, f32), P, int(N), dptr(out, f32), current_stream()))
+    return out
+
+
+def hyp_broadcast(dst, src, N):
+    """dim_hyp_broadcast: the rows of src (P, ...) into dst (P*N, ...), row p into rows p*N .. p*N+N-1 (contiguous 4-byte tensors)"""
+    P = src.shape[0]
+    assert dst.shape[0] == P * N and tuple(dst.shape[1:]) == tuple(src.shape[1:]) and dst.dtype == src.dtype and src.element_size() == 4
+    assert dst.is_contiguous() and src.is_contiguous() and dst.is_cuda and src.is_cuda
+    check(lib().dim_hyp_broadcast(dptr(dst), dptr(src), P, int(N), src.numel() // P, current_stream()))
+    return dst
+
+
+def pose_score_workspace(B, H, W, device):
+    return torch.empty((max(lib().dim_pose_score_workspace_bytes(B, H, W), 8) // 8,), dtype=torch.float64, device=device)
+
+
+def pose_score(image_observed, image_rendered, depth_rendered, mode="rgb", tau=0.02, depth_observed=None, bbox=None, score=None,
+               status=None, workspace=None):
+    """dim_pose_score (restated by tests/hyp_reference.py): one score per sample over the drawn pixels of the render inside bbox (B,4)
+    int32 (None = whole frame).  mode "rgb": ZNCC of the channel sums of image_observed and image_rendered (B,3,H,W); "depth": the
+    fraction of pixels with depth_observed > 0 where |depth_rendered - depth_observed| < tau.  -> score (B,) f32, -inf when it is
+    undefined (and DIM_STATUS_HYP_NO_SCORE is OR-ed into status (B,) int32 when given)"""
+    B, _, H, W = depth_rendered.shape
+    if mode not in HYP_SCORE_ID:
+        raise ValueError("pose score mode must be 'rgb' or 'depth', got {!r}".format(mode))
+    if mode == "depth" and depth_observed is None:
+        raise ValueError("the depth pose score needs depth_observed")
+    assert tuple(image_observed.shape) == (B, 3, H, W) and tuple(image_rendered.shape) == (B, 3, H, W)
+    assert depth_observed is None or depth_observed.shape == depth_rendered.shape
+    score = score if score is not None else _new((B,), depth_rendered)
+    if workspace is None:
+        workspace = pose_score_workspace(B, H, W, depth_rendered.device)
+    opt = lambda t, dt=f32: dptr(t, dt) if t is not None else None  # noqa: E731
+    check(lib().dim_pose_score(dptr(image_observed, f32), dptr(image_rendered, f32), opt(depth_observed), dptr(depth_rendered, f32),
+                               opt(bbox, i32), B, H, W, HYP_SCORE_ID[mode], float(tau), dptr(workspace, torch.float64), dptr(score, f32),
+                               opt(status, i32), current_stream()))
+    return score
+
+
+def hyp_select(score, N, poses_iter, status_iter=None, pose_icp=None, choice=None, poses_sel=None, status_sel=None, pose_icp_sel=None,
+               status_load=None):
+    """dim_hyp_select: score (P*N,), poses_iter (T,P*N,3,4) -> choice (P,) int32 (largest finite score, ties: smaller h, none: 0),
+    poses_sel (T,P,3,4); status_iter (T,P*N) -> status_sel (T,P) and pose_icp (P*N,3,4) -> pose_icp_sel (P,3,4) when given.
+    status_load (P*N,) int32: bits OR-ed into the selected last status row (the load-time hypothesis renders)"""
+    T, B = poses_iter.shape[0], poses_iter.shape[1]
+    assert B % N == 0 and score.numel() == B
+    P = B // N
+    choice = choice if choice is not None else _new((P,), score, i32)
+    poses_sel = poses_sel if poses_sel is not None else _new((T, P, 3, 4), poses_iter)
+    if status_iter is not None and status_sel is None:
+        status_sel = _new((T, P), status_iter, i32)
+    if pose_icp is not None and pose_icp_sel is None:
+        pose_icp_sel = _new((P, 3, 4), pose_icp)
+    opt = lambda t, dt=f32: dptr(t, dt) if t is not None else None  # noqa: E731
+    check(lib().dim_hyp_select(dptr(score, f32), P, int(N), T, dptr(poses_iter, f32), opt(status_iter, i32), opt(status_load, i32), opt(pose_icp),
+                               dptr(choice, i32),
+                               dptr(poses_sel, f32), opt(status_sel, i32), opt(pose_icp_sel), current_stream()))
+    return choice, poses_sel, status_sel, pose_icp_sel
+
+
 STATUS_BAD_K = 16   # DIM_STATUS_BAD_K: dim_raster_render_k drew the sample as background (fx <= 0, fy <= 0 or a non-finite entry)
 
 
@@ -374,6 +446,14 @@ def copy(dst, src):
     (hipMemcpyAsync nodes inside captured graphs are avoided, see include/deepim_hip.h dim_copy_words)."""
     assert dst.shape == src.shape and dst.dtype == src.dtype and dst.element_size() == 4, (dst.shape, src.shape, dst.dtype, src.dtype)
     check(lib().dim_copy_words(dptr(dst), dptr(src), dst.numel(), current_stream()))
+    return dst
+
+
+def copy_rows(dst, dst_pitch, src, src_pitch, rows, width):
+    """dim_copy_rows on two contiguous 4-byte tensors: `rows` runs of `width` words, dst_pitch / src_pitch words apart"""
+    assert dst.is_contiguous() and src.is_contiguous() and dst.element_size() == 4 and src.element_size() == 4
+    assert (rows - 1) * dst_pitch + width <= dst.numel() and (rows - 1) * src_pitch + width <= src.numel()
+    check(lib().dim_copy_rows(dptr(dst), int(dst_pitch), dptr(src), int(src_pitch), int(rows), int(width), current_stream()))
     return dst
 
 
