@@ -232,7 +232,7 @@ inline void wtile_launch(const WTileArgs& a, int gx, int gy, hipStream_t st) {
 int conv2d_unpack_weight_slabs(const float* w_packed, int nslab, long slab_stride, float* w_oihw, int Cout, int CoutPad, int Cin, int KH, int KW,
                                float scale, int accumulate, void* stream);
 
-// ---- plane GEMMs of the Winograd layers (wino_gemm.hip): launch plan, shared with the input-transform kernels of conv.hip, whose
+// ---- plane GEMMs of the Winograd layers (wino_gemm.hip): launch plan, shared with the input-transform kernels of winograd.hip, whose
 // spare blocks zero the output tiles that two stream-K workgroups share (saves a launch per layer)
 struct WGemmArgs {
   const float* V;

@@ -8,13 +8,13 @@
 //   MakeLoss backward = grad_scale * d(loss)/dx (normalization 'null'); LogisticRegressionOutput backward =
 //   grad_scale / num_output * (sigmoid(x) - y) with num_output = label.size / batch; gradients are SUMMED over the batch
 //   (rescale_grad = 1.0, deepim/train.py:383); SGD: mom = momentum*mom - lr*(g + wd*w), w += mom, wd_mult = 0 for biases.
-#include "common.h"
+#include "conv_impl.h"   // reserve_lds
 
 namespace dim {
 
 // ---------------------------------------------------------------------------------------------- weight layout converters
 // packed [chunk][Cout][32] (chunk = (32-channel slice, kh, kw) | first layer: 4 consecutive flat taps) -> OIHW.  Inverse of
-// pack_conv_weight_kernel (conv.hip); used to bring wgrad's output into the flat MXNet-layout gradient bucket.
+// pack_conv_weight_kernel (conv_pack.hip); used to bring wgrad's output into the flat MXNet-layout gradient bucket.
 __global__ void unpack_conv_weight_kernel(const float* __restrict__ wp, float* __restrict__ w, int Cout, int CoutPad, int Cin, int KH, int KW,
                                           int cin8, float scale, int accumulate) {
   long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -768,13 +768,8 @@ int dim_fc_wgrad_nhwc(const float* dz, const float* x, float* dW, int B, int Out
 #define DIM_FC_WGRAD(CBc, BMc, OBc, VECc)                                                                                               \
   {                                                                                                                                     \
     const size_t lds = (size_t)(BMc * CBc * HW + BMc * OBc) * 4;                                                                        \
-    static bool attr = false;                                                                                                           \
-    if (!attr) {                                                                                                                        \
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&fc_wgrad_nhwc_kernel<CBc, BMc, OBc, VECc>),                     \
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)((size_t)(BMc * CBc * 80 + BMc * OBc) * 4));  \
-      if (e != hipSuccess) return set_err(DIM_ERR_LAUNCH, "hipFuncSetAttribute(LDS): %s", hipGetErrorString(e));                        \
-      attr = true;                                                                                                                      \
-    }                                                                                                                                   \
+    const int rc = reserve_lds<&fc_wgrad_nhwc_kernel<CBc, BMc, OBc, VECc>>((size_t)(BMc * CBc * 80 + BMc * OBc) * 4); /* H * W <= 80 */ \
+    if (rc != DIM_OK) return rc;                                                                                                        \
     hipLaunchKernelGGL((fc_wgrad_nhwc_kernel<CBc, BMc, OBc, VECc>), dim3(C / CBc, ceil_div(Out, OBc)), dim3(256), lds, st, dz, x, dW, B, \
                        Out, C, HW);                                                                                                     \
   }

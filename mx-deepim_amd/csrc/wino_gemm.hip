@@ -1,5 +1,5 @@
 // The P independent GEMMs of a Winograd layer (P = 16 or 36 planes:  M_p[T x Cout] = V_p[T x K] . U_p[K x Cout]) as ONE persistent
-// launch.  (deepim/symbols/deepIM_flownet.py:95-191 are the layers; see conv.hip for the transforms around this kernel.)
+// launch.  (deepim/symbols/deepIM_flownet.py:95-191 are the layers; see winograd.hip for the transforms around this kernel.)
 //
 // Why not blockIdx.y = plane on conv_fwd_kernel (the first version): a plane's K loop is only K / 32 = 8 or 16 chunks long, so
 // every workgroup paid its pipeline fill (first global loads -> LDS -> barrier) and its drain (epilogue stores, exit, dispatch of
@@ -58,7 +58,7 @@ __global__ __launch_bounds__(WM * WN * 64) __attribute__((amdgpu_waves_per_eu(BN
   constexpr int BK = 32;
   constexpr int NT = WM * WN * 64;
   constexpr int RP = NT / 8;   // rows staged per pass (8 threads x float4 = one 32-float row)
-  constexpr int LDK = BK + 4;  // conflict-free for ds_write_b128 staging and ds_read_b128 fragments (see conv.hip)
+  constexpr int LDK = BK + 4;  // conflict-free for ds_write_b128 staging and ds_read_b128 fragments (see conv_gather.hip)
   constexpr int TM = BM / WM / 32;
   constexpr int TN = BN / WN / 32;
   constexpr int NSTG = BM / RP;  // staging loads per thread and chunk

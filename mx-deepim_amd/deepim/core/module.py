@@ -62,7 +62,7 @@ class MutableModule(object):
         self.B = batch_size
         self.device = torch.device(device)
         with torch.cuda.device(self.device):
-            # compute units of THIS device, as the library reads them (conv.hip sizes its grids from the same number): the split plans
+            # compute units of THIS device, as the library reads them (conv.hip and conv_first.hip size their grids from the same number): the split plans
             # of the weight and input gradients fill "resident workgroup slots" = a small multiple of it
             self.n_cu = int(ops.lib().dim_device_info(None, 0))
         if self.n_cu <= 0:

@@ -2,7 +2,7 @@
 
 Mirror of /root/reference/deepim/symbols/deepIM_flownet.py (class deepIM_flownet): the same layer
 names, parameter names/shapes (MXNet layouts) and test-graph outputs (`se3`, `zoom_factor`), but the
-"symbol" is executed directly: zoom (csrc/zoom.hip) -> 10 direct convolutions + fc6 (csrc/conv.hip,
+"symbol" is executed directly: zoom (csrc/zoom.hip) -> 10 direct convolutions + fc6 (csrc/conv*.hip,
 f32 MFMA, NHWC) -> pose head -> se3.  Weights are packed once into the kernels' layout.
 
   get_convs            :32-301   -> FlowNetHip.encoder()
@@ -256,7 +256,7 @@ class FlowNetHip(object):
                 # 608 workgroups).  tools/fwd_bf16_sweep.py at B = 16, splits: us incl. the slab sum -- conv5 3: 54, 4: 62; conv5_1 3: 52,
                 # 4: 59; conv6 3: 32, 4: 39, 6: 36; conv6_1 3: 50, 4: 61, 6: 49
                 self.conv_plan[name] = (bf16_tile(cout) if c != 8 else 3, 1 if (tiles == 0 or tiles >= 256) else max(1, min(3, 512 // tiles)))
-                # 3x3 / stride-1 layers on large maps: the LDS-halo kernel (conv.hip conv_bf16_halo_kernel, tile 7).  Measured at B = 16
+                # 3x3 / stride-1 layers on large maps: the LDS-halo kernel (conv_bf16_tiles.hip conv_bf16_halo_kernel, tile 7).  Measured at B = 16
                 # against the gathered-tap kernel: conv3_1 0.150 vs 0.161 ms, conv4_1 0.175 vs 0.177; the stride-2 layers lose (conv2
                 # 0.366 vs 0.256, conv3 0.286 vs 0.247, conv4 0.143 vs 0.102: their 45-53 KB patches + 41 KB of weight buffers leave
                 # one 4-wave workgroup per CU), so they stay where they were.  DIM_BF16_HALO=0: gathered-tap kernel everywhere; =2: every
@@ -266,7 +266,7 @@ class FlowNetHip(object):
                     self.conv_plan[name] = (7, 1)
                 if BF16_PATCH and c % 32 == 0 and cout % 128 == 0 and h * w >= 1200 and (
                         (k == 3 and s == 1) or (s == 2 and k in BF16_PATCH_S2_KERNELS)):
-                    self.conv_plan[name] = (9, 1)   # patch kernel (conv.hip conv_bf16_patch_kernel): 3x3 / stride 1, 3x3 and 5x5 / stride 2
+                    self.conv_plan[name] = (9, 1)   # patch kernel (conv_bf16_tiles.hip conv_bf16_patch_kernel): 3x3 / stride 1, 3x3 and 5x5 / stride 2
                 c = cout
         if conv_plan:
             self.conv_plan.update(conv_plan)
@@ -283,7 +283,7 @@ class FlowNetHip(object):
             nchunks = -(-k * k // 4) if c == 8 else k * k * (c // 32)
             tile, splits = self.conv_plan.get(name, ops.conv_auto_plan(B * ho * wo, cout, nchunks, cin=c))
             if name == "flow_conv1" and name not in (conv_plan or {}) and os.environ.get("DIM_CONV1_HALO", "1") != "0":
-                # LDS-halo first-layer kernel (conv.hip conv1_halo_kernel, on the bf16 pipe conv1_halo_bf16_kernel: 0.26 -> ~0.12 ms at
+                # LDS-halo first-layer kernel (conv_first.hip conv1_halo_kernel, on the bf16 pipe conv1_halo_bf16_kernel: 0.26 -> ~0.12 ms at
                 # B = 16, the layer's HBM bytes once); DIM_CONV1_HALO=0: the gathered-tap kernel
                 tile, splits = 6, 1
             self.conv_plan[name] = (tile, splits)

@@ -5,7 +5,7 @@ set -e
 cd "$(dirname "$0")/../mx-deepim_amd/csrc"
 make -s
 mkdir -p ../../gpurun_exp
-# FILE=conv.hip MACRO=DIM_C1_EXP tools/split_exp.sh 1 2 ... : the same for another source file / experiment macro
+# FILE=conv_first.hip MACRO=DIM_C1_EXP tools/split_exp.sh 1 2 ... : the same for another source file / experiment macro
 FILE=${FILE:-wino_gemm_split.hip}
 MACRO=${MACRO:-DIM_SPLIT_EXP}
 OTHERS=$(ls build/*.o | grep -v "/${FILE%.hip}.o")
