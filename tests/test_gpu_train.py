@@ -194,6 +194,64 @@ def test_adam_two_steps_and_optimizer_state_checkpoint(setup, tmp_path):
         cfg.TRAIN.optimizer = old
 
 
+def test_sgd_three_steps_momentum_and_weight_decay(setup):
+    """MutableModule.update's SGD branch with a momentum buffer that is not zero and a weight decay large enough to see (TRAIN.wd 0.05;
+    TRAIN.momentum as shipped): three forward_backward + update(lr_k) rounds against the float64 restatement
+    (tests/train_head_reference.py) fed the module's own gradients.  The reference keeps its own momentum (its rounding bar carried from
+    step to step) and continues from the module's parameters.  Bar per element: 14 U (|w| + |momentum mom| + |lr g| + |lr wd w|) plus the
+    carried momentum bar.  Biases get no decay (MXNet: wd_mult 0 for *_bias) and lie outside the bar of the decay-on-bias mutant."""
+    import copy
+
+    import train_head_reference as R
+    from deepim.core.module import FROZEN, MutableModule
+
+    cfg0, params0, scene = setup
+    cfg = copy.deepcopy(cfg0)
+    cfg.TRAIN.wd = 0.05
+    rng = np.random.RandomState(3)
+    # biases start at zero in init_weights: give them values, so that decay on a bias would show from the first step on
+    params = {k: ((0.01 * rng.randn(*v.shape)).astype(np.float32) if k.endswith("_bias") else v.copy()) for k, v in params0.items()}
+    B = 2
+    mod = MutableModule(cfg, params, B)
+    batch = {k: torch.as_tensor(np.ascontiguousarray(v)).to(DEV) for k, v in scene["blobs"].items()}
+    used = torch.zeros(mod.flat_w.numel(), dtype=torch.bool, device=DEV)
+    for n, off in mod.offset_of.items():
+        used[off:off + int(np.prod(mod.shapes[n]))] = True
+    gaps = ~used
+    assert int(gaps.sum()) > 0
+    zeros = {k: np.zeros(v.shape) for k, v in params.items()}
+    moms, mom_bars, mut_moms, mut_bars = dict(zeros), dict(zeros), dict(zeros), dict(zeros)
+    prev = {k: v.copy() for k, v in params.items()}
+    momentum = float(cfg.TRAIN.momentum)
+    for step, lr in enumerate((1e-3, 2.5e-4, 5e-4)):
+        mod.forward_backward(batch)
+        g = mod.get_grads()
+        ref, moms, mom_bars, bars = R.sgd_params_step(prev, g, moms, mom_bars, lr, momentum, 0.05, FROZEN)
+        mut, mut_moms, mut_bars, _ = R.sgd_params_step(prev, g, mut_moms, mut_bars, lr, momentum, 0.05, FROZEN, mutant="wd_on_bias")
+        mod.update(lr)
+        new = mod.get_params()
+        visible = 0
+        for k in new:
+            if k in FROZEN:
+                np.testing.assert_array_equal(new[k], params[k])       # lr_mult 0: bit-identical
+                continue
+            assert np.all(np.isfinite(new[k])), (k, step)
+            ratio = R.worst_ratio(new[k], ref[k], bars[k])
+            assert ratio <= 1.0, "{} step {}: {:.3g} x its bar".format(k, step, ratio)
+            assert np.abs(R.f64(new[k]) - R.f64(prev[k])).max() > 0, (k, step)
+            if k.endswith("_weight"):
+                visible += int((lr * 0.05 * np.abs(prev[k]) > 10.0 * bars[k]).sum())
+            else:
+                wrong = R.worst_ratio(new[k], mut[k], bars[k])
+                print("step {} {:28s} {:.3f} bars; decay-on-bias mutant {:.1f} bars".format(step, k, ratio, wrong))
+                assert wrong > 1.0, (k, step, wrong)
+        assert visible > 1000, (step, visible)                          # the decay term is far above the bar on many weights
+        for vec in (mod.flat_w, mod.flat_g, mod.flat_m):
+            assert float(vec[gaps].abs().max()) == 0.0                 # the padding between tensors stays zero
+        prev = {k: v.copy() for k, v in new.items()}
+    assert mod.num_update == 3
+
+
 def test_batch_updater_multiclass(hip_lib):
     """BASELINE configs[2] shape at test size: several object classes in one training batch -- the between-iteration update renders
     every sample with ITS mesh and re-labels it (pose residual, flow, masks) like the per-sample loop of the reference does."""
