@@ -36,7 +36,7 @@ extern "C" {
  * caller that wants both kinds of bits in one word calls dim_zoom_factor BEFORE the render, as the loop does. */
 #define DIM_STATUS_OBS_BOX_EMPTY 1 /* dim_zoom_factor: observed box empty (the reference raises) */
 #define DIM_STATUS_REN_BOX_EMPTY 2 /* dim_zoom_factor: rendered box empty */
-#define DIM_STATUS_BAD_CLASS 4     /* dim_raster_render*: class_index outside [0, n_classes): sample rendered as background */
+#define DIM_STATUS_BAD_CLASS 4     /* dim_raster_render*: class_index outside [0, n_classes): sample rendered as background; dim_pose_errors: NaN row */
 #define DIM_STATUS_BAD_FACE 8      /* dim_raster_render*: a z-buffer key named a face outside the mesh (pixel left black) */
 #define DIM_STATUS_BAD_K 16        /* dim_raster_render_k: the sample's K has fx <= 0, fy <= 0 or a non-finite entry (rendered as background) */
 #define DIM_STATUS_ICP_FEW_POINTS 32 /* dim_icp_refine: an iteration found fewer than 64 inliers or a singular system (no update) */
@@ -192,6 +192,32 @@ int dim_pose_score(const float* image_observed, const float* image_rendered, con
                    const int* bbox, int B, int H, int W, int mode, float tau, void* workspace, float* score, int* status, void* stream);
 int dim_hyp_select(const float* score, int P, int N, int T, const float* poses_iter, const int* status_iter, const int* status_load,
                    const float* pose_icp, int* choice, float* poses_sel, int* status_sel, float* pose_icp_sel, void* stream);
+
+/* ---------------------------------------------------------------- pose errors of the evaluation (lib/utils/pose_error.py) on the device
+ * For T pose sets of B pairs: errors (T,B,5) float64 = {re (degrees), te, add, adi, arp_2d} of poses_est[t][b] against pose_gt[b]
+ * (B,3,4) float64, computed in float64 with numpy's operations in numpy's order (sums of the means in a fixed tree instead of
+ * numpy's pairwise one: ~1e-13 relative at 500 points).
+ *   points (Ntot,3) float64 device: the model points of all classes concatenated; table_off (n_classes+1) int32 device: class c owns
+ *   points [table_off[c], table_off[c+1]); class_flags (n_classes) int32 device: DIM_POSE_ERR_ADI fills the adi column of the class
+ *   (NaN without it), DIM_POSE_ERR_FLIP_Z180 is the eggbox rule of lib/dataset/evaluation.py: when the raw rotation error exceeds
+ *   90 degrees, re, te and arp_2d are those of est . RT_Z = [R diag(-1,-1,1) | t]; add and adi always use the estimate itself.
+ *   class_index (B) int32 device.  poses_est (T,B,3,4) float32 as the loop leaves it, or poses_est_f64 the same in float64: exactly
+ *   one of the two is non-NULL.  K9_f64: HOST pointer, 9 doubles row-major, read before the call returns.
+ *   add = mean |(R_e p + t_e) - (R_g p + t_g)|; adi = mean over the ground-truth points of the distance to the nearest estimate
+ *   point, by exhaustive search (no tree, no float32 stage); arp_2d = mean pixel distance of the projections K (R p + t).
+ * A class index outside [0, n_classes) gives a NaN row and ORs DIM_STATUS_BAD_CLASS into status[b] (B int32, may be NULL); a class
+ * without points gives a NaN row.  A non-finite pose gives non-finite values in its own row only.
+ * workspace: dim_pose_errors_workspace_bytes(T, B, max_points) bytes, 8-byte aligned, no initialisation needed (max_points: the
+ * largest class; the candidates are staged in LDS, so it does not enter the size).  Sums: float64 per lane, across lanes, waves and
+ * workgroups in a fixed order, no atomics: a second call is bit-identical.  2 launches, nothing allocated, no synchronisation.
+ * T or B outside [1, 65535], n_classes <= 0, both or neither pose pointers, or a NULL required pointer return DIM_ERR_ARG before
+ * anything is enqueued. */
+#define DIM_POSE_ERR_ADI 1
+#define DIM_POSE_ERR_FLIP_Z180 2
+long dim_pose_errors_workspace_bytes(int T, int B, int max_points);
+int dim_pose_errors(const double* points, const int* table_off, const int* class_flags, int n_classes, const int* class_index,
+                    const float* poses_est, const double* poses_est_f64, const double* pose_gt, const double* K9_f64, int T, int B,
+                    void* workspace, double* errors, int* status, void* stream);
 
 /* ---------------------------------------------------------------- data layer (test batches from raw file pixels)
  * The loader uploads what the image files hold -- obs_bgr / ren_bgr (B,H,W,3) uint8 in B,G,R order (cv2.IMREAD_COLOR), depth_rendered

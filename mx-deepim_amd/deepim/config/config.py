@@ -68,7 +68,10 @@ def _defaults():
                    ICP_ITER=0, ICP_MAX_DIST=0.02,   # depth ICP after the loop: iterations (0 = off), gate in metres
                    # several starting poses per pair, scored after the loop (1 = off): rotation of the generated ones (degrees), the
                    # score ("rgb" ZNCC or "depth" inlier fraction) and the depth score's inlier gate (metres)
-                   HYP_NUM=1, HYP_ROT_DEG=30.0, HYP_SCORE="rgb", HYP_DEPTH_TAU=0.02)
+                   HYP_NUM=1, HYP_ROT_DEG=30.0, HYP_SCORE="rgb", HYP_DEPTH_TAU=0.02,
+                   # pred_eval: the pose errors (re, te, ADD, ADD-S, arp_2d) from dim_pose_errors on the device instead of
+                   # lib/utils/pose_error.py on the host, one pose at a time
+                   DEVICE_EVAL=False)
     c.train_iter = edict(SE3_DIST_LOSS=False, LW_ROT=0.0, LW_TRANS=0.0, TRANS_LOSS_TYPE="L2", TRANS_SMOOTH_L1_SCALAR=3.0,
                          SE3_PM_LOSS=False, LW_PM=0.0, SE3_PM_LOSS_TYPE="L1", SE3_PM_SL1_SCALAR=1.0, NUM_3D_SAMPLE=-1, LW_FLOW=0.0,
                          LW_MASK=0.0)

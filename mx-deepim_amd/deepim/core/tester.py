@@ -20,6 +20,7 @@ from lib.hip import ops
 from deepim.symbols.deepIM_flownet import FlowNetHip
 
 HYP_SCORES = ("rgb", "depth")
+ERR_KEYS = ("re", "te", "add", "arp_2d")   # the per-pose error lists lib.dataset.evaluation.PoseEvaluator takes as `errors=`
 
 
 def hyp_settings(cfg):
@@ -483,7 +484,10 @@ def pred_eval(config, refiner, batches, evaluator, result_file=None, logger=None
     (tester.py:253-330), under out["icp"] = {pose, add, arp_2d}; every other output and the result cache are those of ICP off.
     With TEST.HYP_NUM = N > 1 every table, the result cache and out["icp"] score the selected hypothesis of each pair, and out["hyp"]
     holds per pair the N scores, the choice and the last-iteration rotation / translation error of every hypothesis, plus the rate
-    at which the chosen hypothesis is also the one with the least rotation error.  A batch may carry "hyp_poses" (P,N,3,4)."""
+    at which the chosen hypothesis is also the one with the least rotation error.  A batch may carry "hyp_poses" (P,N,3,4).
+    With TEST.DEVICE_EVAL the errors behind the three tables (and out["icp"]) come from dim_pose_errors on the poses where refine()
+    left them, and reach the host in the batch's one copy next to the poses; pairs that were not refined (undetected) are scored on the
+    host as before.  Every output keeps its meaning; out["device_eval"] = True is added."""
     import copy
     import pickle
 
@@ -500,15 +504,43 @@ def pred_eval(config, refiner, batches, evaluator, result_file=None, logger=None
     # several hypotheses per pair: [score, choice, rot_err, trans_err, undetected] per pair
     n_hyp = int(getattr(refiner, "N", 1))
     hyp_lists = tuple([] for _ in range(5)) if n_hyp > 1 else None
+    # TEST.DEVICE_EVAL: the per-pose errors the evaluator reads, err_lists[key][cls][iter] (the ICP row: its own one-iteration lists)
+    device_eval = bool(config.TEST.get("DEVICE_EVAL", False))
+    err_lists = icp_err_lists = None
+    if device_eval:
+        from lib.dataset.evaluation import SYM_CLASSES
+
+        err_lists = {k: [[[] for _ in range(n_it)] for _ in range(n_cls)] for k in ERR_KEYS}
+        icp_err_lists = {k: [[[]] for _ in range(n_cls)] for k in ERR_KEYS} if with_icp else None
+        dev = refiner.net.device
+        tables = evaluator.device_tables(dev)
+        K_eval = np.asarray(config.dataset.INTRINSIC_MATRIX, dtype=np.float64)
+        uses_adi = [c in SYM_CLASSES for c in evaluator.classes]
     # flow error of the first forward (:500-512): only the full test graph emits the flow head's output
     epe = FlowEPE(config, getattr(refiner, "P", refiner.B), refiner.net.device) if (config.network.PRED_FLOW and not config.TEST.FAST_TEST) else None
     for batch in batches:
         extra = {"hyp_poses": batch["hyp_poses"]} if batch.get("hyp_poses") is not None else {}
         refiner.load(batch["image_observed"], batch["image_rendered"], batch["mask_observed"], batch["mask_rendered"], batch["src_pose"],
                      batch["class_index"], depth_observed=batch.get("depth_observed"), K=batch.get("K"), **extra)
-        poses = refiner.refine().cpu().numpy().astype(np.float64)     # ONE device->host copy per batch: (iter, B, 3, 4)
-        if with_icp:
-            poses_icp = (refiner.pose_icp if n_hyp == 1 else refiner.pose_icp_sel).cpu().numpy().astype(np.float64)
+        if device_eval:
+            # the errors of every pose on the device, packed behind the poses (float32 -> float64 is exact): rows (iter [+ 1 for ICP],
+            # B, 12 + 5), ONE device->host copy per batch
+            poses_dev = refiner.refine()
+            gt_dev = torch.as_tensor(batch["pose_observed"]).to(dev, torch.float64).contiguous()
+            cls_dev = refiner.batch["class_index"] if n_hyp == 1 else refiner.pair["class_index"]
+            rows = [(poses_dev, ops.pose_errors(tables[0], tables[1], tables[2], cls_dev, poses_dev, gt_dev, K_eval))]
+            if with_icp:
+                p_icp = refiner.pose_icp if n_hyp == 1 else refiner.pose_icp_sel
+                rows.append((p_icp, ops.pose_errors(tables[0], tables[1], tables[2], cls_dev, p_icp, gt_dev, K_eval)))
+            packed = torch.cat([torch.cat([p.to(torch.float64).reshape(-1, gt_dev.shape[0], 12), e.reshape(-1, gt_dev.shape[0], 5)], dim=2)
+                                for p, e in rows], dim=0).cpu().numpy()
+            poses, dev_err = packed[:n_it, :, :12].reshape(n_it, -1, 3, 4), packed[:n_it, :, 12:]
+            if with_icp:
+                poses_icp, dev_err_icp = packed[n_it, :, :12].reshape(-1, 3, 4), packed[n_it, :, 12:]
+        else:
+            poses = refiner.refine().cpu().numpy().astype(np.float64)     # ONE device->host copy per batch: (iter, B, 3, 4)
+            if with_icp:
+                poses_icp = (refiner.pose_icp if n_hyp == 1 else refiner.pose_icp_sel).cpu().numpy().astype(np.float64)
         cls = torch.as_tensor(batch["class_index"]).cpu().numpy().astype(int)
         gt = torch.as_tensor(batch["pose_observed"]).cpu().numpy().astype(np.float64)
         src = torch.as_tensor(batch["src_pose"]).cpu().numpy().astype(np.float64)
@@ -540,6 +572,15 @@ def pred_eval(config, refiner, batches, evaluator, result_file=None, logger=None
                 r_dist, t_dist = (1000, 1000) if undetected else calc_rt_dist_m(est, gt[b])
                 for k, v in enumerate((r_dist, t_dist, est, gt[b])):
                     icp_lists[k][cls[b]][0].append(v)
+            if device_eval:   # {re, te, add, adi, arp_2d} -> the four lists; a pair that was not refined: the host functions on its row
+                host = evaluator.host_pose_errors(config, evaluator.classes[cls[b]], src[b], gt[b]) if undetected else None
+                pick = lambda e: (e[0], e[1], e[3] if uses_adi[cls[b]] else e[2], e[4])  # noqa: E731
+                for it in range(n_it):
+                    for k, v in zip(ERR_KEYS, host or pick(dev_err[it, b])):
+                        err_lists[k][cls[b]][it].append(float(v))
+                if with_icp:
+                    for k, v in zip(ERR_KEYS, host or pick(dev_err_icp[b])):
+                        icp_err_lists[k][cls[b]][0].append(float(v))
     # several ranks refine disjoint shards (one process per GPU): the metrics are over ALL pairs, so the per-class lists are merged in
     # rank order on every rank before scoring (the reference scores one list in one process)
     import torch.distributed as dist
@@ -547,7 +588,7 @@ def pred_eval(config, refiner, batches, evaluator, result_file=None, logger=None
     merged = False
     if merge_ranks and dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
         parts = [None] * dist.get_world_size()
-        dist.all_gather_object(parts, (all_rot_err, all_trans_err, all_poses_est, all_poses_gt, icp_lists, hyp_lists))
+        dist.all_gather_object(parts, (all_rot_err, all_trans_err, all_poses_est, all_poses_gt, icp_lists, hyp_lists, err_lists, icp_err_lists))
         for k, mine in enumerate((all_rot_err, all_trans_err, all_poses_est, all_poses_gt)):
             for c in range(n_cls):
                 for it in range(n_it):
@@ -559,6 +600,11 @@ def pred_eval(config, refiner, batches, evaluator, result_file=None, logger=None
         if hyp_lists is not None:
             for k, mine in enumerate(hyp_lists):
                 mine[:] = [x for part in parts for x in part[5][k]]
+        for slot, lists, iters in ((6, err_lists, n_it), (7, icp_err_lists, 1)):
+            for k in (lists or {}):
+                for c in range(n_cls):
+                    for it in range(iters):
+                        lists[k][c][it] = [x for part in parts for x in part[slot][k][c][it]]
         merged = True
         if dist.get_rank() != 0:
             result_file = None   # one result cache, written by rank 0
@@ -574,9 +620,12 @@ def pred_eval(config, refiner, batches, evaluator, result_file=None, logger=None
             print(line)
             if logger:
                 logger.info(line)
-    out["pose"] = evaluator.evaluate_pose(config, all_poses_est, all_poses_gt, logger)
-    out["add"] = evaluator.evaluate_pose_add(config, all_poses_est, all_poses_gt, output_dir=None, logger=logger)
-    out["arp_2d"] = evaluator.evaluate_pose_arp_2d(config, all_poses_est, all_poses_gt, output_dir=None, logger=logger)
+    given = {"errors": err_lists} if device_eval else {}   # flag off: the evaluator is called as before
+    out["pose"] = evaluator.evaluate_pose(config, all_poses_est, all_poses_gt, logger, **given)
+    out["add"] = evaluator.evaluate_pose_add(config, all_poses_est, all_poses_gt, output_dir=None, logger=logger, **given)
+    out["arp_2d"] = evaluator.evaluate_pose_arp_2d(config, all_poses_est, all_poses_gt, output_dir=None, logger=logger, **given)
+    if device_eval:
+        out["device_eval"] = True
     out["all_rot_err"], out["all_trans_err"] = all_rot_err, all_trans_err
     out["merged_over_ranks"] = merged
     if with_icp:
@@ -589,9 +638,10 @@ def pred_eval(config, refiner, batches, evaluator, result_file=None, logger=None
         print(line)
         if logger:
             logger.info(line)
-        out["icp"] = {"pose": evaluator.evaluate_pose(cfg1, icp_est, icp_gt, logger),
-                      "add": evaluator.evaluate_pose_add(cfg1, icp_est, icp_gt, output_dir=None, logger=logger),
-                      "arp_2d": evaluator.evaluate_pose_arp_2d(cfg1, icp_est, icp_gt, output_dir=None, logger=logger),
+        given = {"errors": icp_err_lists} if device_eval else {}
+        out["icp"] = {"pose": evaluator.evaluate_pose(cfg1, icp_est, icp_gt, logger, **given),
+                      "add": evaluator.evaluate_pose_add(cfg1, icp_est, icp_gt, output_dir=None, logger=logger, **given),
+                      "arp_2d": evaluator.evaluate_pose_arp_2d(cfg1, icp_est, icp_gt, output_dir=None, logger=logger, **given),
                       "all_rot_err": icp_rot, "all_trans_err": icp_trans}
     if hyp_lists is not None:
         score, choice, rot, trans, undet = hyp_lists

@@ -4,7 +4,9 @@ rotation / translation / joint accuracies at (k deg, k cm), ADD(-S) at 0.02 / 0.
 
 Inputs have the reference's layout: all_poses_est[cls][iter] and all_poses_gt[cls][0] are lists of 3x4 poses.  Every method
 returns its numbers as a dict and logs the reference's lines through `logger` / print.  Thresholding is vectorised (the
-reference loops over 1000 thresholds per pose); pose errors come from lib/utils/pose_error.py."""
+reference loops over 1000 thresholds per pose); pose errors come from lib/utils/pose_error.py, or -- `errors=` -- from the caller:
+{"re", "te", "add", "arp_2d"} -> errors[key][cls][iter] = one number per pose of all_poses_est[cls][iter], as host_pose_errors
+computes them (pred_eval with TEST.DEVICE_EVAL passes the device's, lib/hip/ops.py pose_errors)."""
 from __future__ import print_function, division
 
 import os
@@ -44,11 +46,45 @@ class PoseEvaluator(object):
         self._points = points
         self._diameters = diameters
 
+    def device_tables(self, device):
+        """-> (points (Ntot,3) float64, table_off (n_classes+1,) int32, class_flags (n_classes,) int32) resident on `device`, the model
+        tables dim_pose_errors reads: ADD-S for SYM_CLASSES, the 180-degree rule for eggbox.  Built once per device."""
+        import torch
+
+        from lib.hip import ops
+
+        key = str(torch.device(device))
+        cache = self.__dict__.setdefault("_device_tables", {})
+        if key not in cache:
+            pts = [np.asarray(self._points[c], dtype=np.float64).reshape(-1, 3) for c in self.classes]
+            off = np.concatenate([[0], np.cumsum([len(p) for p in pts])]).astype(np.int32)
+            flags = np.array([(ops.POSE_ERR_ADI if c in SYM_CLASSES else 0) | (ops.POSE_ERR_FLIP_Z180 if c == "eggbox" else 0)
+                              for c in self.classes], dtype=np.int32)
+            allp = np.ascontiguousarray(np.concatenate(pts, axis=0)) if pts else np.zeros((0, 3))
+            cache[key] = (torch.from_numpy(allp).to(device), torch.from_numpy(off).to(device), torch.from_numpy(flags).to(device))
+        return cache[key]
+
+    def host_pose_errors(self, config, cls_name, RT, pose_gt):
+        """the four numbers the three tables below read for one pose: (re, te) of evaluate_pose, ADD or ADD-S, arp_2d"""
+        K = np.asarray(config.dataset.INTRINSIC_MATRIX, dtype=np.float64)
+        flipped = se3_mul(RT, RT_Z) if cls_name == "eggbox" and re(RT[:3, :3], pose_gt[:3, :3]) > 90 else RT
+        r, t = calc_rt_dist_m(flipped, pose_gt)
+        fn = adi if cls_name in SYM_CLASSES else add
+        return (r, t, fn(RT[:3, :3], RT[:, 3], pose_gt[:3, :3], pose_gt[:, 3], self._points[cls_name]),
+                arp_2d(flipped[:3, :3], flipped[:, 3], pose_gt[:3, :3], pose_gt[:, 3], self._points[cls_name], K))
+
+    @staticmethod
+    def _given(errors, key, cls_idx, iter_i, n):
+        err = np.asarray(errors[key][cls_idx][iter_i], dtype=np.float64)
+        if err.shape != (n,):
+            raise ValueError("errors['{}'][{}][{}]: {} values for {} poses".format(key, cls_idx, iter_i, err.shape, n))
+        return err
+
     def _valid(self, all_poses_est, all_poses_gt, cls_idx):
         return bool(len(all_poses_est[cls_idx][0]) and len(all_poses_gt[cls_idx][0]))
 
     # ------------------------------------------------------------------------------------------------ :329-459
-    def evaluate_pose(self, config, all_poses_est, all_poses_gt, logger=None):
+    def evaluate_pose(self, config, all_poses_est, all_poses_gt, logger=None, errors=None):
         print_and_log("evaluating pose", logger)
         rot_thresh_list = np.arange(1, 11, 1)
         trans_thresh_list = np.arange(0.01, 0.11, 0.01)
@@ -67,11 +103,14 @@ class PoseEvaluator(object):
             for iter_i in range(num_iter):
                 ests = all_poses_est[cls_idx][iter_i]
                 rd, td = np.zeros(len(gts)), np.zeros(len(gts))
-                for j in range(len(gts)):
-                    r, t = calc_rt_dist_m(ests[j], gts[j])
-                    if cls_name == "eggbox" and r > 90:
-                        r, t = calc_rt_dist_m(se3_mul(ests[j], RT_Z), gts[j])
-                    rd[j], td[j] = r, t
+                if errors is not None:
+                    rd, td = self._given(errors, "re", cls_idx, iter_i, len(gts)), self._given(errors, "te", cls_idx, iter_i, len(gts))
+                else:
+                    for j in range(len(gts)):
+                        r, t = calc_rt_dist_m(ests[j], gts[j])
+                        if cls_name == "eggbox" and r > 90:
+                            r, t = calc_rt_dist_m(se3_mul(ests[j], RT_Z), gts[j])
+                        rd[j], td[j] = r, t
                 r_ok = rd[:, None] < rot_thresh_list[None, :]
                 t_ok = td[:, None] < trans_thresh_list[None, :]
                 rot_acc[cls_idx, iter_i] = r_ok.mean(0)
@@ -110,7 +149,7 @@ class PoseEvaluator(object):
 
     # ------------------------------------------------------------------------------------------------ shared by ADD / ARP-2D
     def _threshold_eval(self, config, all_poses_est, all_poses_gt, error_fn, fixed, curve, curve_scale, area_norm, fmt, header,
-                        overall_title, output_dir, pkl_name, logger):
+                        overall_title, output_dir, pkl_name, logger, given=None):
         num_iter = config.TEST.test_iter
         count_all = np.zeros((self.num_classes,), dtype=np.float32)
         count_correct = {k: np.zeros((self.num_classes, num_iter), dtype=np.float32) for k in fixed}
@@ -128,7 +167,10 @@ class PoseEvaluator(object):
             thr_curve = (curve * np.float32(scale)).astype(np.float32)
             for iter_i in range(num_iter):
                 ests = all_poses_est[cls_idx][iter_i]
-                err = np.array([error_fn(cls_name, ests[j], gts[j]) for j in range(len(gts))])
+                if given is not None:
+                    err = self._given(given[0], given[1], cls_idx, iter_i, len(gts))
+                else:
+                    err = np.array([error_fn(cls_name, ests[j], gts[j]) for j in range(len(gts))])
                 errors[(cls_name, iter_i)] = err
                 for k, frac in fixed.items():
                     count_correct[k][cls_idx, iter_i] = np.sum(err < np.float32(frac * scale))
@@ -174,7 +216,7 @@ class PoseEvaluator(object):
                 "num_valid_class": num_valid_class}
 
     # ------------------------------------------------------------------------------------------------ :461-681
-    def evaluate_pose_add(self, config, all_poses_est, all_poses_gt, output_dir=None, logger=None):
+    def evaluate_pose_add(self, config, all_poses_est, all_poses_gt, output_dir=None, logger=None, errors=None):
         def err(cls_name, RT, pose_gt):
             fn = adi if cls_name in SYM_CLASSES else add
             return fn(RT[:3, :3], RT[:, 3], pose_gt[:3, :3], pose_gt[:, 3], self._points[cls_name])
@@ -183,10 +225,11 @@ class PoseEvaluator(object):
         return self._threshold_eval(
             config, all_poses_est, all_poses_gt, err, {"0.02": 0.02, "0.05": 0.05, "0.10": 0.10},
             np.arange(0, 0.1, 0.0001).astype(np.float32), lambda c: self._diameters[c], 0.1, {"range": "0.10", "dx": 0.0001},
-            "evaluating pose add", "add", output_dir, "{}_xys.pkl".format("adi" if uses_adi else "add"), logger)
+            "evaluating pose add", "add", output_dir, "{}_xys.pkl".format("adi" if uses_adi else "add"), logger,
+            given=None if errors is None else (errors, "add"))
 
     # ------------------------------------------------------------------------------------------------ :683-
-    def evaluate_pose_arp_2d(self, config, all_poses_est, all_poses_gt, output_dir=None, logger=None):
+    def evaluate_pose_arp_2d(self, config, all_poses_est, all_poses_gt, output_dir=None, logger=None, errors=None):
         K = np.asarray(config.dataset.INTRINSIC_MATRIX, dtype=np.float64)
 
         def err(cls_name, RT, pose_gt):
@@ -197,4 +240,5 @@ class PoseEvaluator(object):
         return self._threshold_eval(
             config, all_poses_est, all_poses_gt, err, {"2": 2.0, "5": 5.0, "10": 10.0, "20": 20.0},
             np.arange(0, 50, 0.1).astype(np.float32), lambda c: 1.0, 50.0, {"range": "50", "dx": 0.1},
-            "evaluating pose average re-projection 2d error", "arp_2d", output_dir, "arp_2d_xys.pkl", logger)
+            "evaluating pose average re-projection 2d error", "arp_2d", output_dir, "arp_2d_xys.pkl", logger,
+            given=None if errors is None else (errors, "arp_2d"))

@@ -304,6 +304,47 @@ def hyp_select(score, N, poses_iter, status_iter=None, pose_icp=None, choice=Non
     return choice, poses_sel, status_sel, pose_icp_sel
 
 
+STATUS_BAD_CLASS = 4     # DIM_STATUS_BAD_CLASS: dim_pose_errors gave the pair a NaN row (class index outside the table)
+POSE_ERR_ADI = 1         # DIM_POSE_ERR_ADI: the class's adi column is filled
+POSE_ERR_FLIP_Z180 = 2   # DIM_POSE_ERR_FLIP_Z180: the eggbox rule of lib/dataset/evaluation.py
+POSE_ERR_COLUMNS = ("re", "te", "add", "adi", "arp_2d")
+
+
+def pose_errors_workspace(T, B, max_points, device):
+    return torch.empty((max(lib().dim_pose_errors_workspace_bytes(T, B, max_points), 8) // 8,), dtype=torch.float64, device=device)
+
+
+def pose_errors(points, table_off, class_flags, class_index, poses_est, pose_gt, K, errors=None, status=None, workspace=None):
+    """dim_pose_errors: the five errors of lib/utils/pose_error.py in float64 on the device.  points (Ntot,3) f64, table_off
+    (n_classes+1,) and class_flags (n_classes,) int32 as PoseEvaluator.device_tables returns them, class_index (B,) int32, poses_est
+    (T,B,3,4) or (B,3,4) (= T 1) float32 or float64, pose_gt (B,3,4) f64, K the host 3x3.  -> errors (T,B,5) f64 (POSE_ERR_COLUMNS;
+    (B,5) for a (B,3,4) input); DIM_STATUS_BAD_CLASS is OR-ed into status (B,) int32 when given"""
+    f64 = torch.float64
+    if poses_est.dtype not in (f32, f64):
+        raise capi.DeepIMHipError("pose_errors: poses_est must be float32 or float64, got {}".format(poses_est.dtype))
+    single = poses_est.dim() == 3
+    T = 1 if single else poses_est.shape[0]
+    B = poses_est.shape[-3]
+    n_classes = class_flags.numel()
+    assert tuple(poses_est.shape[-3:]) == (B, 3, 4) and poses_est.dim() in (3, 4) and tuple(pose_gt.shape) == (B, 3, 4)
+    assert points.dim() == 2 and points.shape[1] == 3 and table_off.numel() == n_classes + 1 and class_index.numel() == B
+    if errors is None:
+        errors = torch.empty((B, 5) if single else (T, B, 5), dtype=f64, device=poses_est.device)
+    assert errors.numel() == T * B * 5 and (status is None or status.numel() == B)
+    if workspace is None:
+        workspace = pose_errors_workspace(T, B, points.shape[0], poses_est.device)
+    assert workspace.numel() * workspace.element_size() >= lib().dim_pose_errors_workspace_bytes(T, B, points.shape[0])
+    keep = np.ascontiguousarray(np.asarray(K, dtype=np.float64).reshape(-1))
+    if keep.size != 9:
+        raise ValueError("expected a 3x3 K, got {} numbers".format(keep.size))
+    is32 = poses_est.dtype == f32
+    check(lib().dim_pose_errors(dptr(points, f64), dptr(table_off, i32), dptr(class_flags, i32), n_classes, dptr(class_index, i32),
+                                dptr(poses_est, f32) if is32 else None, None if is32 else dptr(poses_est, f64), dptr(pose_gt, f64),
+                                keep.ctypes.data, T, B, dptr(workspace), dptr(errors, f64), dptr(status, i32) if status is not None else None,
+                                current_stream()))
+    return errors
+
+
 STATUS_BAD_K = 16   # DIM_STATUS_BAD_K: dim_raster_render_k drew the sample as background (fx <= 0, fy <= 0 or a non-finite entry)
 
 
