@@ -219,6 +219,35 @@ int dim_pose_errors(const double* points, const int* table_off, const int* class
                     const float* poses_est, const double* poses_est_f64, const double* pose_gt, const double* K9_f64, int T, int B,
                     void* workspace, double* errors, int* status, void* stream);
 
+/* ---------------------------------------------------------------- visible surface discrepancy (VSD) on the device
+ * The error the reference ships the two halves of (lib/utils/visibility.py: estimate_visib_mask, _gt, _est; lib/utils/misc.py:
+ * depth_im_to_dist_im) and never joins; restated in numpy by lib/utils/pose_error.py vsd().  For T pose sets of B pairs:
+ *   depth_obs (B,H,W) the observed depth, depth_gt (B,H,W) the model rendered at the ground truth, depth_est (T,B,H,W) the model
+ *   rendered at the estimates; float32 metres, 0 = no surface.  Camera: K_per_sample_f64 (B,9) device float64 or NULL = K9_f64 (HOST,
+ *   9 doubles row-major, read before the call returns) for every pair.
+ *   Per pixel (x, y), in float64: S = sqrt((X X + Y Y) + d d), X = ((x - cx) d) (1 / fx), Y = ((y - cy) d) (1 / fy) for each of the
+ *   three depths.  visible(S_m) = S_m > 0 and S_obs > 0 and float32(S_m) - float32(S_obs) <= delta, compared in float32.
+ *   visib_gt = visible(S_gt); visib_est = visible(S_est) or (visib_gt and S_est > 0).  On visib_gt & visib_est the cost of
+ *   c = |S_gt - S_est| is (c >= tau) for DIM_VSD_COST_STEP and min(c (1 / tau), 1) for DIM_VSD_COST_TLINEAR; then
+ *   e = (sum of costs + (|union| - |inter|)) / |union|, and e = 1 when the union is empty.  A NaN depth fails every `> 0`.
+ *   taus: HOST, n_tau doubles (1 <= n_tau <= DIM_VSD_MAX_TAU), all scored from one read of the planes.
+ *   errors (T,B,n_tau) float64; counts (T,B,4) int32 = {|visib_gt|, |union|, |inter|, pixels with S_gt > 0}.
+ *   bbox_gt (B,4) / bbox_est (T,B,4) int32 device {min_x, max_x, min_y, max_y} (empty = {W,-1,H,-1}) as the rasteriser returns them for
+ *   the two renders, both or neither: rows and columns outside their union are not read.  Both renders are 0 there, so the result is
+ *   the one of NULL boxes bit for bit (a pixel keeps its lane and its place in the lane's sum).
+ * workspace: dim_vsd_workspace_bytes(T, B) bytes, 8-byte aligned, no initialisation needed.  Sums: int32 / float64 per lane, float64
+ * across lanes and workgroups in a fixed order, no atomics: a second call is bit-identical.  16-byte loads when W % 4 == 0 and the
+ * planes are 16-byte aligned.  2 launches, nothing allocated, no synchronisation.  T or B outside [1, 65535], H or W <= 0, n_tau
+ * outside [1, 8], an unknown cost_type, one box without the other or a NULL required pointer return DIM_ERR_ARG before anything is
+ * enqueued. */
+#define DIM_VSD_MAX_TAU 8
+#define DIM_VSD_COST_STEP 0
+#define DIM_VSD_COST_TLINEAR 1
+long dim_vsd_workspace_bytes(int T, int B);
+int dim_vsd_errors(const float* depth_obs, const float* depth_gt, const float* depth_est, const double* K9_f64,
+                   const double* K_per_sample_f64, const int* bbox_gt, const int* bbox_est, int T, int B, int H, int W, float delta,
+                   const double* taus, int n_tau, int cost_type, void* workspace, double* errors, int* counts, void* stream);
+
 /* ---------------------------------------------------------------- data layer (test batches from raw file pixels)
  * The loader uploads what the image files hold -- obs_bgr / ren_bgr (B,H,W,3) uint8 in B,G,R order (cv2.IMREAD_COLOR), depth_rendered
  * (B,H,W) uint16 = metres * depth_factor -- and the blobs of get_data_pair_test_batch are built on the device:

@@ -71,7 +71,11 @@ def _defaults():
                    HYP_NUM=1, HYP_ROT_DEG=30.0, HYP_SCORE="rgb", HYP_DEPTH_TAU=0.02,
                    # pred_eval: the pose errors (re, te, ADD, ADD-S, arp_2d) from dim_pose_errors on the device instead of
                    # lib/utils/pose_error.py on the host, one pose at a time
-                   DEVICE_EVAL=False)
+                   DEVICE_EVAL=False,
+                   # pred_eval: the visible surface discrepancy of every scored pose against depth_observed (dim_vsd_errors): the
+                   # visibility tolerance and the misalignment tolerances (metres; up to 8, scored together), the cost ("step" or
+                   # "tlinear") and the error below which a pose counts as correct
+                   VSD=False, VSD_DELTA=0.015, VSD_TAU=[0.02], VSD_COST="step", VSD_THRESH=0.3)
     c.train_iter = edict(SE3_DIST_LOSS=False, LW_ROT=0.0, LW_TRANS=0.0, TRANS_LOSS_TYPE="L2", TRANS_SMOOTH_L1_SCALAR=3.0,
                          SE3_PM_LOSS=False, LW_PM=0.0, SE3_PM_LOSS_TYPE="L1", SE3_PM_SL1_SCALAR=1.0, NUM_3D_SAMPLE=-1, LW_FLOW=0.0,
                          LW_MASK=0.0)

@@ -21,6 +21,7 @@ from deepim.symbols.deepIM_flownet import FlowNetHip
 
 HYP_SCORES = ("rgb", "depth")
 ERR_KEYS = ("re", "te", "add", "arp_2d")   # the per-pose error lists lib.dataset.evaluation.PoseEvaluator takes as `errors=`
+VSD_KEYS = ("vsd", "visib_gt", "union", "inter", "drawn_gt")   # per pose: the errors (one per tau) and dim_vsd_errors' four counts
 
 
 def hyp_settings(cfg):
@@ -413,6 +414,73 @@ class Refiner(object):
         return self.poses_iter if self.N == 1 else self.poses_sel
 
 
+class VsdScorer(object):
+    """TEST.VSD: the visible surface discrepancy of every pose pred_eval scores, against the batch's observed depth.  Per batch the
+    ground truth is rendered once (depth and box only, float32 pose, the pair's K when one was loaded) with the refiner's render
+    machine; per scored pose set the estimate is rendered into one reused plane and dim_vsd_errors fills that set's row of `errors`
+    (rows, P, n_tau) float64 and `counts` (rows, P, 4) int32.  Nothing leaves the device here."""
+
+    def __init__(self, config, refiner, rows):
+        T = config.TEST
+        if getattr(refiner, "lit", False):
+            raise ValueError("TEST.VSD is not supported with the lit ModelNet renderer")
+        self.taus = [float(t) for t in np.asarray(T.VSD_TAU, dtype=np.float64).reshape(-1)]
+        if not 1 <= len(self.taus) <= ops.VSD_MAX_TAU or not all(np.isfinite(t) and t > 0 for t in self.taus):
+            raise ValueError("TEST.VSD_TAU must hold 1 to {} finite distances > 0 (metres), got {!r}".format(ops.VSD_MAX_TAU, T.VSD_TAU))
+        self.delta, self.cost = float(T.VSD_DELTA), T.VSD_COST
+        if self.cost not in ops.VSD_COST_ID:
+            raise ValueError("TEST.VSD_COST must be 'step' or 'tlinear', got {!r}".format(self.cost))
+        self.refiner, self.rm = refiner, refiner.render_machine
+        P, H, W, d = refiner.P, self.rm.height, self.rm.width, refiner.net.device
+        self.K = np.asarray(self.rm.K, dtype=np.float64)   # the camera the planes are rendered with
+        self.depth_gt = torch.zeros((P, 1, H, W), dtype=torch.float32, device=d)
+        self.depth_est = torch.zeros((P, 1, H, W), dtype=torch.float32, device=d)
+        self.depth_obs = None   # allocated only when the refiner keeps no observed depth of its own
+        self.bbox_gt = torch.zeros((P, 4), dtype=torch.int32, device=d)
+        self.bbox_est = torch.zeros((P, 4), dtype=torch.int32, device=d)
+        self.errors = torch.zeros((rows, P, len(self.taus)), dtype=torch.float64, device=d)
+        self.counts = torch.zeros((rows, P, 4), dtype=torch.int32, device=d)
+        self.work = ops.vsd_workspace(1, P, d)
+        self.rm.reserve(P)
+
+    @staticmethod
+    def check(batch):
+        if batch.get("depth_observed") is None:
+            raise KeyError("TEST.VSD needs the blob 'depth_observed' (the test image's depth in metres)")
+
+    def _observed(self, batch):
+        """the pairs' observed depth where the refiner already holds it (ICP, the depth hypothesis score, INPUT_DEPTH), else a copy"""
+        r = self.refiner
+        if r.N > 1 and "depth_observed" in r.pair:
+            return r.pair["depth_observed"]
+        if r.N == 1 and (r.depth_observed is not None or r.input_depth):
+            return r.batch["depth_observed"] if r.input_depth else r.depth_observed
+        if self.depth_obs is None:
+            self.depth_obs = torch.zeros_like(self.depth_gt)
+        self.depth_obs.copy_(torch.as_tensor(batch["depth_observed"]).reshape(self.depth_gt.shape))
+        return self.depth_obs
+
+    def score(self, batch, pose_sets):
+        """pose_sets: list of (P,3,4) float32 device poses, one per row of errors / counts"""
+        r = self.refiner
+        cls = r.batch["class_index"] if r.N == 1 else r.pair["class_index"]
+        K_pair = (r.K_pair if r.N == 1 else r.pair["K"]) if r.per_pair_K else None
+        extra = {"K": K_pair} if K_pair is not None else {}
+        K64 = K_pair.to(torch.float64) if K_pair is not None else None
+        obs = self._observed(batch)
+        gt = torch.as_tensor(batch["pose_observed"]).to(self.depth_gt.device, torch.float32).contiguous()
+        self.rm.render_batch(cls, gt, depth=self.depth_gt, bbox=self.bbox_gt, mask_thr=0.0, **extra)
+        for row, pose in enumerate(pose_sets):
+            self.rm.render_batch(cls, pose, depth=self.depth_est, bbox=self.bbox_est, mask_thr=0.0, **extra)
+            ops.vsd_errors(obs, self.depth_gt, self.depth_est, self.K, self.delta, self.taus, self.cost, K_per_sample=K64,
+                           bbox_gt=self.bbox_gt, bbox_est=self.bbox_est, errors=self.errors[row], counts=self.counts[row],
+                           workspace=self.work)
+
+    def packed(self):
+        """(rows, P, n_tau + 4) float64: the errors and, behind them, the counts (exact in float64)"""
+        return torch.cat([self.errors, self.counts.to(torch.float64)], dim=2)
+
+
 class FlowEPE(object):
     """Test-time flow error, reference deepim/core/tester.py:500-512 (accumulation), :675-716 (par_generate_gt) and :719-736
     (calc_EPE_one_pair), active when `PRED_FLOW and not FAST_TEST`: the flow head's output of the FIRST forward of every pair
@@ -487,7 +555,12 @@ def pred_eval(config, refiner, batches, evaluator, result_file=None, logger=None
     at which the chosen hypothesis is also the one with the least rotation error.  A batch may carry "hyp_poses" (P,N,3,4).
     With TEST.DEVICE_EVAL the errors behind the three tables (and out["icp"]) come from dim_pose_errors on the poses where refine()
     left them, and reach the host in the batch's one copy next to the poses; pairs that were not refined (undetected) are scored on the
-    host as before.  Every output keeps its meaning; out["device_eval"] = True is added."""
+    host as before.  Every output keeps its meaning; out["device_eval"] = True is added.
+    With TEST.VSD every scored pose (and the ICP pose) also gets its visible surface discrepancy against the batch's "depth_observed"
+    (VsdScorer, dim_vsd_errors): out["vsd"] = the table of PoseEvaluator.evaluate_pose_vsd plus "errors", the per-pose lists
+    {vsd, visib_gt, union, inter, drawn_gt}[cls][iter] in the order of all_poses_est; out["icp"]["vsd"] the same for the ICP row.  A
+    pair that was not refined scores 1.0.  The numbers ride in the device-to-host copy of TEST.DEVICE_EVAL, or come in one copy of
+    their own per batch.  Every other output and the result cache are those of VSD off."""
     import copy
     import pickle
 
@@ -516,16 +589,27 @@ def pred_eval(config, refiner, batches, evaluator, result_file=None, logger=None
         tables = evaluator.device_tables(dev)
         K_eval = np.asarray(config.dataset.INTRINSIC_MATRIX, dtype=np.float64)
         uses_adi = [c in SYM_CLASSES for c in evaluator.classes]
+    # TEST.VSD: vsd_lists[key][cls][iter] (the ICP row: its own one-iteration lists)
+    vsd = vsd_lists = icp_vsd_lists = None
+    if bool(config.TEST.get("VSD", False)):
+        vsd = VsdScorer(config, refiner, n_it + (1 if with_icp else 0))
+        vsd_lists = {k: [[[] for _ in range(n_it)] for _ in range(n_cls)] for k in VSD_KEYS}
+        icp_vsd_lists = {k: [[[]] for _ in range(n_cls)] for k in VSD_KEYS} if with_icp else None
+        n_tau = len(vsd.taus)
     # flow error of the first forward (:500-512): only the full test graph emits the flow head's output
     epe = FlowEPE(config, getattr(refiner, "P", refiner.B), refiner.net.device) if (config.network.PRED_FLOW and not config.TEST.FAST_TEST) else None
     for batch in batches:
         extra = {"hyp_poses": batch["hyp_poses"]} if batch.get("hyp_poses") is not None else {}
+        if vsd is not None:
+            vsd.check(batch)
         refiner.load(batch["image_observed"], batch["image_rendered"], batch["mask_observed"], batch["mask_rendered"], batch["src_pose"],
                      batch["class_index"], depth_observed=batch.get("depth_observed"), K=batch.get("K"), **extra)
         if device_eval:
             # the errors of every pose on the device, packed behind the poses (float32 -> float64 is exact): rows (iter [+ 1 for ICP],
             # B, 12 + 5), ONE device->host copy per batch
             poses_dev = refiner.refine()
+            if vsd is not None:
+                vsd.score(batch, list(poses_dev) + ([refiner.pose_icp if n_hyp == 1 else refiner.pose_icp_sel] if with_icp else []))
             gt_dev = torch.as_tensor(batch["pose_observed"]).to(dev, torch.float64).contiguous()
             cls_dev = refiner.batch["class_index"] if n_hyp == 1 else refiner.pair["class_index"]
             rows = [(poses_dev, ops.pose_errors(tables[0], tables[1], tables[2], cls_dev, poses_dev, gt_dev, K_eval))]
@@ -533,12 +617,21 @@ def pred_eval(config, refiner, batches, evaluator, result_file=None, logger=None
                 p_icp = refiner.pose_icp if n_hyp == 1 else refiner.pose_icp_sel
                 rows.append((p_icp, ops.pose_errors(tables[0], tables[1], tables[2], cls_dev, p_icp, gt_dev, K_eval)))
             packed = torch.cat([torch.cat([p.to(torch.float64).reshape(-1, gt_dev.shape[0], 12), e.reshape(-1, gt_dev.shape[0], 5)], dim=2)
-                                for p, e in rows], dim=0).cpu().numpy()
+                                for p, e in rows], dim=0)
+            if vsd is not None:
+                packed = torch.cat([packed, vsd.packed()], dim=2)
+            packed = packed.cpu().numpy()
+            vsd_host = packed[:, :, 17:]
+            packed = packed[:, :, :17]
             poses, dev_err = packed[:n_it, :, :12].reshape(n_it, -1, 3, 4), packed[:n_it, :, 12:]
             if with_icp:
                 poses_icp, dev_err_icp = packed[n_it, :, :12].reshape(-1, 3, 4), packed[n_it, :, 12:]
         else:
-            poses = refiner.refine().cpu().numpy().astype(np.float64)     # ONE device->host copy per batch: (iter, B, 3, 4)
+            poses_dev = refiner.refine()
+            poses = poses_dev.cpu().numpy().astype(np.float64)     # ONE device->host copy per batch: (iter, B, 3, 4)
+            if vsd is not None:   # and one more for the VSD rows
+                vsd.score(batch, list(poses_dev) + ([refiner.pose_icp if n_hyp == 1 else refiner.pose_icp_sel] if with_icp else []))
+                vsd_host = vsd.packed().cpu().numpy()
             if with_icp:
                 poses_icp = (refiner.pose_icp if n_hyp == 1 else refiner.pose_icp_sel).cpu().numpy().astype(np.float64)
         cls = torch.as_tensor(batch["class_index"]).cpu().numpy().astype(int)
@@ -572,6 +665,12 @@ def pred_eval(config, refiner, batches, evaluator, result_file=None, logger=None
                 r_dist, t_dist = (1000, 1000) if undetected else calc_rt_dist_m(est, gt[b])
                 for k, v in enumerate((r_dist, t_dist, est, gt[b])):
                     icp_lists[k][cls[b]][0].append(v)
+            if vsd is not None:   # a pair that was not refined: e = 1.0 and no counts, whatever its -1 pose rendered
+                for lists, rows_b in ((vsd_lists, vsd_host[:n_it, b]), (icp_vsd_lists, vsd_host[n_it:, b])):
+                    for it, row in enumerate(rows_b):
+                        e, cnt = ([1.0] * n_tau, [0] * 4) if undetected else (row[:n_tau].tolist(), [int(v) for v in row[n_tau:]])
+                        for k, v in zip(VSD_KEYS, [e] + cnt):
+                            lists[k][cls[b]][it].append(v)
             if device_eval:   # {re, te, add, adi, arp_2d} -> the four lists; a pair that was not refined: the host functions on its row
                 host = evaluator.host_pose_errors(config, evaluator.classes[cls[b]], src[b], gt[b]) if undetected else None
                 pick = lambda e: (e[0], e[1], e[3] if uses_adi[cls[b]] else e[2], e[4])  # noqa: E731
@@ -588,7 +687,8 @@ def pred_eval(config, refiner, batches, evaluator, result_file=None, logger=None
     merged = False
     if merge_ranks and dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
         parts = [None] * dist.get_world_size()
-        dist.all_gather_object(parts, (all_rot_err, all_trans_err, all_poses_est, all_poses_gt, icp_lists, hyp_lists, err_lists, icp_err_lists))
+        dist.all_gather_object(parts, (all_rot_err, all_trans_err, all_poses_est, all_poses_gt, icp_lists, hyp_lists, err_lists, icp_err_lists,
+                                       vsd_lists, icp_vsd_lists))
         for k, mine in enumerate((all_rot_err, all_trans_err, all_poses_est, all_poses_gt)):
             for c in range(n_cls):
                 for it in range(n_it):
@@ -600,7 +700,7 @@ def pred_eval(config, refiner, batches, evaluator, result_file=None, logger=None
         if hyp_lists is not None:
             for k, mine in enumerate(hyp_lists):
                 mine[:] = [x for part in parts for x in part[5][k]]
-        for slot, lists, iters in ((6, err_lists, n_it), (7, icp_err_lists, 1)):
+        for slot, lists, iters in ((6, err_lists, n_it), (7, icp_err_lists, 1), (8, vsd_lists, n_it), (9, icp_vsd_lists, 1)):
             for k in (lists or {}):
                 for c in range(n_cls):
                     for it in range(iters):
@@ -626,6 +726,8 @@ def pred_eval(config, refiner, batches, evaluator, result_file=None, logger=None
     out["arp_2d"] = evaluator.evaluate_pose_arp_2d(config, all_poses_est, all_poses_gt, output_dir=None, logger=logger, **given)
     if device_eval:
         out["device_eval"] = True
+    if vsd is not None:
+        out["vsd"] = dict(evaluator.evaluate_pose_vsd(config, vsd_lists, logger), errors=vsd_lists)
     out["all_rot_err"], out["all_trans_err"] = all_rot_err, all_trans_err
     out["merged_over_ranks"] = merged
     if with_icp:
@@ -643,6 +745,8 @@ def pred_eval(config, refiner, batches, evaluator, result_file=None, logger=None
                       "add": evaluator.evaluate_pose_add(cfg1, icp_est, icp_gt, output_dir=None, logger=logger, **given),
                       "arp_2d": evaluator.evaluate_pose_arp_2d(cfg1, icp_est, icp_gt, output_dir=None, logger=logger, **given),
                       "all_rot_err": icp_rot, "all_trans_err": icp_trans}
+        if vsd is not None:
+            out["icp"]["vsd"] = dict(evaluator.evaluate_pose_vsd(config, icp_vsd_lists, logger), errors=icp_vsd_lists)
     if hyp_lists is not None:
         score, choice, rot, trans, undet = hyp_lists
         best = [c == int(np.argmin(r)) for c, r, u in zip(choice, rot, undet) if not u]

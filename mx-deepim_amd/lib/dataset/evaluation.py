@@ -242,3 +242,48 @@ class PoseEvaluator(object):
             np.arange(0, 50, 0.1).astype(np.float32), lambda c: 1.0, 50.0, {"range": "50", "dx": 0.1},
             "evaluating pose average re-projection 2d error", "arp_2d", output_dir, "arp_2d_xys.pkl", logger,
             given=None if errors is None else (errors, "arp_2d"))
+
+    # ------------------------------------------------------------------------------------------------ visible surface discrepancy
+    def evaluate_pose_vsd(self, config, errors, logger=None):
+        """errors: {"vsd": errors["vsd"][cls][iter] = one list of len(VSD_TAU) errors per pose, "visib_gt" / "drawn_gt":
+        [cls][iter] = per pose the visible and the drawn pixels of the ground-truth render} (pred_eval with TEST.VSD fills them from
+        dim_vsd_errors).  Per class and iteration: the share of poses with e < VSD_THRESH for every tau, and the mean visible
+        fraction |visib_gt| / drawn_gt over the poses whose ground truth draws anything."""
+        taus = [float(t) for t in np.asarray(config.TEST.VSD_TAU, dtype=np.float64).reshape(-1)]
+        thresh = float(config.TEST.VSD_THRESH)
+        num_iter = len(errors["vsd"][0]) if len(errors["vsd"]) else 0
+        acc = np.zeros((self.num_classes, num_iter, len(taus)))
+        visib = np.full((self.num_classes, num_iter), np.nan)
+        count_all = np.zeros((self.num_classes,), dtype=np.float32)
+        print_and_log("evaluating pose vsd (delta {}, cost {}, correct below {})".format(
+            float(config.TEST.VSD_DELTA), config.TEST.VSD_COST, thresh), logger)
+        num_valid_class = 0
+        for cls_idx, cls_name in enumerate(self.classes):
+            if not len(errors["vsd"][cls_idx][0]):
+                continue
+            num_valid_class += 1
+            count_all[cls_idx] = len(errors["vsd"][cls_idx][0])
+            for iter_i in range(num_iter):
+                e = np.asarray(errors["vsd"][cls_idx][iter_i], dtype=np.float64).reshape(-1, len(taus))
+                acc[cls_idx, iter_i] = (e < thresh).mean(0)
+                vis = np.asarray(errors["visib_gt"][cls_idx][iter_i], dtype=np.float64)
+                drawn = np.asarray(errors["drawn_gt"][cls_idx][iter_i], dtype=np.float64)
+                if np.any(drawn > 0):
+                    visib[cls_idx, iter_i] = np.mean(vis[drawn > 0] / drawn[drawn > 0])
+                print_and_log("** {}, iter {} **".format(cls_name, iter_i + 1), logger)
+                print_and_log("visible fraction of the ground truth: {:.3f}".format(visib[cls_idx, iter_i]), logger)
+                for k, tau in enumerate(taus):
+                    print_and_log("tau={}, correct poses: {}, all poses: {}, accuracy: {:.2f}".format(
+                        tau, int((e[:, k] < thresh).sum()), count_all[cls_idx], acc[cls_idx, iter_i, k] * 100), logger)
+        overall = []
+        n = max(num_valid_class, 1)
+        for iter_i in range(num_iter):
+            print_and_log("---------- vsd performance over {} classes -----------".format(num_valid_class), logger)
+            print_and_log("** iter {} **".format(iter_i + 1), logger)
+            row = {}
+            for k, tau in enumerate(taus):
+                row[tau] = np.sum(acc[:, iter_i, k]) / n * 100
+                print_and_log("tau={}, mean accuracy: {:.2f}".format(tau, row[tau]), logger)
+            overall.append(row)
+        return {"acc": acc, "visible_fraction": visib, "overall": overall, "count_all": count_all, "taus": taus, "thresh": thresh,
+                "num_valid_class": num_valid_class}

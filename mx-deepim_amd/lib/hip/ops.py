@@ -345,6 +345,61 @@ def pose_errors(points, table_off, class_flags, class_index, poses_est, pose_gt,
     return errors
 
 
+VSD_COST_ID = {"step": 0, "tlinear": 1}   # DIM_VSD_COST_STEP / DIM_VSD_COST_TLINEAR
+VSD_MAX_TAU = 8                            # DIM_VSD_MAX_TAU
+VSD_COUNT_COLUMNS = ("visib_gt", "union", "inter", "drawn_gt")
+
+
+def vsd_workspace(T, B, device):
+    return torch.empty((max(lib().dim_vsd_workspace_bytes(T, B), 8) // 8,), dtype=torch.float64, device=device)
+
+
+def vsd_errors(depth_obs, depth_gt, depth_est, K, delta, taus, cost_type="step", K_per_sample=None, bbox_gt=None, bbox_est=None,
+               errors=None, counts=None, workspace=None):
+    """dim_vsd_errors (restated by lib/utils/pose_error.py vsd): the visible surface discrepancy of T pose sets of B pairs.
+    depth_obs, depth_gt (B,H,W) or (B,1,H,W) and depth_est (T,B,H,W), (T,B,1,H,W) or one set shaped like depth_gt (= T 1): float32
+    metres.  K: the host 3x3 used for every pair unless K_per_sample ((B,3,3) / (B,9), host array or CUDA tensor, made float64) is
+    given.  taus: one number or up to 8, all scored from one read of the planes.  bbox_gt (B,4) / bbox_est (T,B,4) int32: the boxes
+    the two renders returned, both or neither.  -> errors (T,B,n_tau) f64, counts (T,B,4) int32 (VSD_COUNT_COLUMNS); without the T
+    axis for a single set"""
+    f64 = torch.float64
+    if cost_type not in VSD_COST_ID:
+        raise ValueError("vsd cost_type must be 'step' or 'tlinear', got {!r}".format(cost_type))
+    tau = np.ascontiguousarray(np.asarray(taus, dtype=np.float64).reshape(-1))
+    if not 1 <= tau.size <= VSD_MAX_TAU or not np.all(tau > 0):
+        raise ValueError("vsd taus: 1 to {} distances > 0, got {!r}".format(VSD_MAX_TAU, taus))
+    H, W = depth_gt.shape[-2:]
+    B = depth_gt.shape[0]
+    assert depth_gt.numel() == B * H * W and tuple(depth_obs.shape) == tuple(depth_gt.shape)
+    single = depth_est.dim() == depth_gt.dim()
+    T = 1 if single else depth_est.shape[0]
+    assert depth_est.numel() == T * B * H * W and tuple(depth_est.shape[-2:]) == (H, W)
+    dev = depth_gt.device
+    if errors is None:
+        errors = torch.empty((B, tau.size) if single else (T, B, tau.size), dtype=f64, device=dev)
+    if counts is None:
+        counts = torch.empty((B, 4) if single else (T, B, 4), dtype=i32, device=dev)
+    assert errors.numel() == T * B * tau.size and counts.numel() == T * B * 4
+    assert (bbox_gt is None) == (bbox_est is None), "vsd_errors: both boxes or neither"
+    assert bbox_gt is None or (bbox_gt.numel() == 4 * B and bbox_est.numel() == 4 * T * B)
+    if workspace is None:
+        workspace = vsd_workspace(T, B, dev)
+    assert workspace.numel() * workspace.element_size() >= lib().dim_vsd_workspace_bytes(T, B)
+    keep = np.ascontiguousarray(np.asarray(K, dtype=np.float64).reshape(-1))
+    if keep.size != 9:
+        raise ValueError("expected a 3x3 K, got {} numbers".format(keep.size))
+    kps = None
+    if K_per_sample is not None:
+        kps = torch.as_tensor(K_per_sample).to(dev, f64).reshape(-1, 9).contiguous()
+        if kps.shape[0] != B:
+            raise ValueError("vsd K_per_sample must be ({0},3,3) or ({0},9), got {1}".format(B, tuple(torch.as_tensor(K_per_sample).shape)))
+    opt = lambda t, dt: dptr(t, dt) if t is not None else None  # noqa: E731
+    check(lib().dim_vsd_errors(dptr(depth_obs, f32), dptr(depth_gt, f32), dptr(depth_est, f32), keep.ctypes.data, opt(kps, f64),
+                               opt(bbox_gt, i32), opt(bbox_est, i32), T, B, H, W, float(delta), tau.ctypes.data, int(tau.size),
+                               VSD_COST_ID[cost_type], dptr(workspace), dptr(errors, f64), dptr(counts, i32), current_stream()))
+    return errors, counts
+
+
 STATUS_BAD_K = 16   # DIM_STATUS_BAD_K: dim_raster_render_k drew the sample as background (fx <= 0, fy <= 0 or a non-finite entry)
 
 

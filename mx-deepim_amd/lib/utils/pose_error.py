@@ -50,3 +50,29 @@ def te(t_est, t_gt):
 def calc_rt_dist_m(pose_src, pose_tgt):
     """lib/pair_matching/RT_transform.py:172-183: (rotation distance in degrees, translation distance)"""
     return re(pose_src[:, :3], pose_tgt[:, :3]), np.linalg.norm(pose_tgt[:, 3] - pose_src[:, 3])
+
+
+VSD_COSTS = ("step", "tlinear")
+
+
+def vsd(depth_est, depth_gt, depth_test, K, delta, tau, cost_type="step"):
+    """Visible surface discrepancy (Hodan et al.) of one pose from three depth planes (metres, 0 = no surface): the model rendered
+    at the estimate and at the ground truth, and the test image.  Only the surface visible in the test image is compared
+    (lib/utils/visibility.py): on the pixels visible under both poses the cost of c = |S_gt - S_est| is 1 where c >= tau ("step") or
+    min(c / tau, 1) ("tlinear"), a pixel visible under one pose only costs 1, and the error is the mean cost over the union.
+    -> (e, (|visib_gt|, |union|, |inter|)); e = 1.0 when nothing is visible.  dim_vsd_errors (csrc/vsd.hip) is the device's."""
+    from lib.utils.misc import depth_im_to_dist_im
+    from lib.utils.visibility import estimate_visib_mask_est, estimate_visib_mask_gt
+
+    if cost_type not in VSD_COSTS:
+        raise ValueError("vsd cost_type must be one of {}, got {!r}".format(VSD_COSTS, cost_type))
+    s_test, s_gt, s_est = (depth_im_to_dist_im(d, K) for d in (depth_test, depth_gt, depth_est))
+    visib_gt = estimate_visib_mask_gt(s_test, s_gt, delta)
+    visib_est = estimate_visib_mask_est(s_test, s_est, visib_gt, delta)
+    inter, union = visib_gt & visib_est, visib_gt | visib_est
+    n_gt, n_union, n_inter = int(visib_gt.sum()), int(union.sum()), int(inter.sum())
+    if n_union == 0:
+        return 1.0, (n_gt, 0, 0)
+    c = np.abs(s_gt[inter] - s_est[inter])
+    costs = (c >= tau).astype(np.float64) if cost_type == "step" else np.minimum(c * (1.0 / tau), 1.0)
+    return float((costs.sum() + (n_union - n_inter)) / float(n_union)), (n_gt, n_union, n_inter)
