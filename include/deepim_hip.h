@@ -36,7 +36,7 @@ extern "C" {
  * caller that wants both kinds of bits in one word calls dim_zoom_factor BEFORE the render, as the loop does. */
 #define DIM_STATUS_OBS_BOX_EMPTY 1 /* dim_zoom_factor: observed box empty (the reference raises) */
 #define DIM_STATUS_REN_BOX_EMPTY 2 /* dim_zoom_factor: rendered box empty */
-#define DIM_STATUS_BAD_CLASS 4     /* dim_raster_render*: class_index outside [0, n_classes): sample rendered as background; dim_pose_errors: NaN row */
+#define DIM_STATUS_BAD_CLASS 4     /* dim_raster_render*: class_index outside [0, n_classes): sample rendered as background; dim_pose_errors, dim_bop_errors: NaN row */
 #define DIM_STATUS_BAD_FACE 8      /* dim_raster_render*: a z-buffer key named a face outside the mesh (pixel left black) */
 #define DIM_STATUS_BAD_K 16        /* dim_raster_render_k: the sample's K has fx <= 0, fy <= 0 or a non-finite entry (rendered as background) */
 #define DIM_STATUS_ICP_FEW_POINTS 32 /* dim_icp_refine: an iteration found fewer than 64 inliers or a singular system (no update) */
@@ -247,6 +247,34 @@ long dim_vsd_workspace_bytes(int T, int B);
 int dim_vsd_errors(const float* depth_obs, const float* depth_gt, const float* depth_est, const double* K9_f64,
                    const double* K_per_sample_f64, const int* bbox_gt, const int* bbox_est, int T, int B, int H, int W, float delta,
                    const double* taus, int n_tau, int cost_type, void* workspace, double* errors, int* counts, void* stream);
+
+/* ---------------------------------------------------------------- BOP symmetry-aware pose errors (MSSD, MSPD) on the device
+ * lib/utils/pose_error.py mssd / mspd for T pose sets of B pairs: errors (T,B,2) float64 = {mssd, mspd} of poses_est[t][b] against
+ * pose_gt[b] (B,3,4) float64 under the symmetry set of the pair's class,
+ *   mssd = min over S of max over x of |(R_e x + t_e) - (R_g (S_R x + S_t) + t_g)|      (the unit of the model points)
+ *   mspd = the same with both points projected by K (R p + t) and divided by the third row   (pixels)
+ * computed in float64 with numpy's operations in numpy's order, except that pose_gt . S is composed once per (pose, symmetry) and
+ * applied to the point in one step (about 1e-16 relative against transforming the point twice).
+ *   points, table_off: the tables of dim_pose_errors.  sym (Stot,3,4) float64 device: the symmetry transformations [S_R | S_t] of all
+ *   classes concatenated; sym_off (n_classes+1) int32 device: class c owns sym [sym_off[c], sym_off[c+1])
+ *   (lib/utils/symmetry.py, PoseEvaluator.device_sym_tables).  class_index (B) int32 device.  poses_est (T,B,3,4) float32 as the loop
+ *   leaves it, or poses_est_f64 the same in float64: exactly one of the two is non-NULL.  Camera: K_per_sample_f64 (B,9) device
+ *   float64 or NULL = K9_f64 (HOST, 9 doubles row-major, read before the call returns) for every pair.
+ *   best_sym (T,B,2) int32 (may be NULL): the index within the class's set that attains each minimum; ties go to the smaller index.
+ * A class index outside [0, n_classes) gives a NaN row with best_sym -1 and ORs DIM_STATUS_BAD_CLASS into status[b] (B int32, may be
+ * NULL); a class without points, without symmetries or with more than max_sym symmetries gives a NaN row with best_sym -1.  A
+ * non-finite pose or a point at depth <= 0 gives what numpy gives (a NaN wins the maximum over the points and the minimum over the
+ * symmetries, best_sym = the first such symmetry), in its own row only.
+ * workspace: dim_bop_errors_workspace_bytes(T, B, max_sym) bytes, 8-byte aligned, no initialisation needed.  Maxima per lane, wave
+ * and workgroup, then the minimum: exact in any order, no atomics: a second call is bit-identical and the result does not depend on
+ * how the points are dealt to workgroups.  2 launches, nothing allocated, no synchronisation.
+ * T or B outside [1, 65535], n_classes <= 0, max_sym <= 0, both or neither pose pointers, or a NULL required pointer return
+ * DIM_ERR_ARG before anything is enqueued. */
+long dim_bop_errors_workspace_bytes(int T, int B, int max_sym);
+int dim_bop_errors(const double* points, const int* table_off, const double* sym, const int* sym_off, int n_classes,
+                   const int* class_index, const float* poses_est, const double* poses_est_f64, const double* pose_gt,
+                   const double* K9_f64, const double* K_per_sample_f64, int T, int B, int max_sym, void* workspace, double* errors,
+                   int* best_sym, int* status, void* stream);
 
 /* ---------------------------------------------------------------- data layer (test batches from raw file pixels)
  * The loader uploads what the image files hold -- obs_bgr / ren_bgr (B,H,W,3) uint8 in B,G,R order (cv2.IMREAD_COLOR), depth_rendered

@@ -75,7 +75,13 @@ def _defaults():
                    # pred_eval: the visible surface discrepancy of every scored pose against depth_observed (dim_vsd_errors): the
                    # visibility tolerance and the misalignment tolerances (metres; up to 8, scored together), the cost ("step" or
                    # "tlinear") and the error below which a pose counts as correct
-                   VSD=False, VSD_DELTA=0.015, VSD_TAU=[0.02], VSD_COST="step", VSD_THRESH=0.3)
+                   VSD=False, VSD_DELTA=0.015, VSD_TAU=[0.02], VSD_COST="step", VSD_THRESH=0.3,
+                   # pred_eval: the BOP symmetry-aware errors MSSD and MSPD of every scored pose (dim_bop_errors) under the symmetry
+                   # sets of the evaluator: the discretisation step of continuous symmetries (radians of arc, BOP's
+                   # max_sym_disc_step), and the thresholds of correctness -- fractions of the class diameter for MSSD, pixels at a
+                   # 640-pixel-wide image (scaled by W / 640) for MSPD
+                   BOP=False, BOP_SYM_STEP=0.01, BOP_MSSD_THRESH=[round(0.05 * k, 2) for k in range(1, 11)],
+                   BOP_MSPD_THRESH=[5 * k for k in range(1, 11)])
     c.train_iter = edict(SE3_DIST_LOSS=False, LW_ROT=0.0, LW_TRANS=0.0, TRANS_LOSS_TYPE="L2", TRANS_SMOOTH_L1_SCALAR=3.0,
                          SE3_PM_LOSS=False, LW_PM=0.0, SE3_PM_LOSS_TYPE="L1", SE3_PM_SL1_SCALAR=1.0, NUM_3D_SAMPLE=-1, LW_FLOW=0.0,
                          LW_MASK=0.0)

@@ -22,6 +22,7 @@ from deepim.symbols.deepIM_flownet import FlowNetHip
 HYP_SCORES = ("rgb", "depth")
 ERR_KEYS = ("re", "te", "add", "arp_2d")   # the per-pose error lists lib.dataset.evaluation.PoseEvaluator takes as `errors=`
 VSD_KEYS = ("vsd", "visib_gt", "union", "inter", "drawn_gt")   # per pose: the errors (one per tau) and dim_vsd_errors' four counts
+BOP_KEYS = ("mssd", "mspd", "sym_mssd", "sym_mspd")             # per pose: dim_bop_errors' two errors and the symmetries that attain them
 
 
 def hyp_settings(cfg):
@@ -481,6 +482,47 @@ class VsdScorer(object):
         return torch.cat([self.errors, self.counts.to(torch.float64)], dim=2)
 
 
+class BopScorer(object):
+    """TEST.BOP: the BOP symmetry-aware errors MSSD and MSPD of every pose pred_eval scores, under the evaluator's symmetry sets
+    (PoseEvaluator.device_sym_tables at TEST.BOP_SYM_STEP).  One dim_bop_errors call per batch on the float32 poses where refine()
+    left them (the ICP pose as one more row), with the pair's K when one was loaded and the config K otherwise: `errors`
+    (rows, P, 2) float64 and `best_sym` (rows, P, 2) int32.  Nothing leaves the device here."""
+
+    def __init__(self, config, refiner, evaluator, rows):
+        step = float(config.TEST.BOP_SYM_STEP)
+        if not (np.isfinite(step) and step > 0):
+            raise ValueError("TEST.BOP_SYM_STEP must be a finite step > 0, got {!r}".format(config.TEST.BOP_SYM_STEP))
+        self.refiner = refiner
+        P, d = refiner.P, refiner.net.device
+        self.points, self.table_off = evaluator.device_tables(d)[:2]
+        self.sym, self.sym_off = evaluator.device_sym_tables(d, step)
+        self.max_sym = evaluator.max_sym(step)
+        self.K = np.asarray(config.dataset.INTRINSIC_MATRIX, dtype=np.float64)
+        self.rows = rows
+        self.poses = torch.zeros((rows, P, 3, 4), dtype=torch.float32, device=d)
+        self.errors = torch.zeros((rows, P, 2), dtype=torch.float64, device=d)
+        self.best_sym = torch.zeros((rows, P, 2), dtype=torch.int32, device=d)
+        self.work = ops.bop_errors_workspace(rows, P, self.max_sym, d)
+
+    def score(self, batch, poses, pose_icp=None):
+        """poses (rows [- 1], P, 3, 4) float32 on the device, pose_icp (P,3,4) the last row when given"""
+        r = self.refiner
+        if pose_icp is not None:   # one call needs the rows in one array
+            self.poses[:-1].copy_(poses)
+            self.poses[-1].copy_(pose_icp)
+            poses = self.poses
+        assert poses.shape[0] == self.rows
+        cls = r.batch["class_index"] if r.N == 1 else r.pair["class_index"]
+        K_pair = (r.K_pair if r.N == 1 else r.pair["K"]) if r.per_pair_K else None
+        gt = torch.as_tensor(batch["pose_observed"]).to(self.errors.device, torch.float64).contiguous()
+        ops.bop_errors(self.points, self.table_off, self.sym, self.sym_off, cls, poses.contiguous(), gt, self.K, self.max_sym,
+                       K_per_sample=K_pair, errors=self.errors, best_sym=self.best_sym, workspace=self.work)
+
+    def packed(self):
+        """(rows, P, 4) float64: {mssd, mspd} and, behind them, the two symmetry indices (exact in float64)"""
+        return torch.cat([self.errors, self.best_sym.to(torch.float64)], dim=2)
+
+
 class FlowEPE(object):
     """Test-time flow error, reference deepim/core/tester.py:500-512 (accumulation), :675-716 (par_generate_gt) and :719-736
     (calc_EPE_one_pair), active when `PRED_FLOW and not FAST_TEST`: the flow head's output of the FIRST forward of every pair
@@ -560,7 +602,12 @@ def pred_eval(config, refiner, batches, evaluator, result_file=None, logger=None
     (VsdScorer, dim_vsd_errors): out["vsd"] = the table of PoseEvaluator.evaluate_pose_vsd plus "errors", the per-pose lists
     {vsd, visib_gt, union, inter, drawn_gt}[cls][iter] in the order of all_poses_est; out["icp"]["vsd"] the same for the ICP row.  A
     pair that was not refined scores 1.0.  The numbers ride in the device-to-host copy of TEST.DEVICE_EVAL, or come in one copy of
-    their own per batch.  Every other output and the result cache are those of VSD off."""
+    their own per batch.  Every other output and the result cache are those of VSD off.
+    With TEST.BOP every scored pose (and the ICP pose) also gets the BOP symmetry-aware errors MSSD and MSPD under the evaluator's
+    symmetry sets (BopScorer, one dim_bop_errors call per batch): out["bop"] = the table of PoseEvaluator.evaluate_pose_bop plus
+    "errors", the per-pose lists {mssd, mspd, sym_mssd, sym_mspd}[cls][iter] in the order of all_poses_est; out["icp"]["bop"] the same
+    for the ICP row.  A pair that was not refined scores inf for both (symmetry -1).  The numbers travel like the VSD ones.  Every
+    other output and the result cache are those of BOP off."""
     import copy
     import pickle
 
@@ -596,6 +643,12 @@ def pred_eval(config, refiner, batches, evaluator, result_file=None, logger=None
         vsd_lists = {k: [[[] for _ in range(n_it)] for _ in range(n_cls)] for k in VSD_KEYS}
         icp_vsd_lists = {k: [[[]] for _ in range(n_cls)] for k in VSD_KEYS} if with_icp else None
         n_tau = len(vsd.taus)
+    # TEST.BOP: bop_lists[key][cls][iter] (the ICP row: its own one-iteration lists)
+    bop = bop_lists = icp_bop_lists = None
+    if bool(config.TEST.get("BOP", False)):
+        bop = BopScorer(config, refiner, evaluator, n_it + (1 if with_icp else 0))
+        bop_lists = {k: [[[] for _ in range(n_it)] for _ in range(n_cls)] for k in BOP_KEYS}
+        icp_bop_lists = {k: [[[]] for _ in range(n_cls)] for k in BOP_KEYS} if with_icp else None
     # flow error of the first forward (:500-512): only the full test graph emits the flow head's output
     epe = FlowEPE(config, getattr(refiner, "P", refiner.B), refiner.net.device) if (config.network.PRED_FLOW and not config.TEST.FAST_TEST) else None
     for batch in batches:
@@ -620,8 +673,12 @@ def pred_eval(config, refiner, batches, evaluator, result_file=None, logger=None
                                 for p, e in rows], dim=0)
             if vsd is not None:
                 packed = torch.cat([packed, vsd.packed()], dim=2)
+            if bop is not None:
+                bop.score(batch, poses_dev, (refiner.pose_icp if n_hyp == 1 else refiner.pose_icp_sel) if with_icp else None)
+                packed = torch.cat([packed, bop.packed()], dim=2)
             packed = packed.cpu().numpy()
-            vsd_host = packed[:, :, 17:]
+            n_vsd = packed.shape[2] - 17 - (4 if bop is not None else 0)
+            vsd_host, bop_host = packed[:, :, 17:17 + n_vsd], packed[:, :, 17 + n_vsd:]
             packed = packed[:, :, :17]
             poses, dev_err = packed[:n_it, :, :12].reshape(n_it, -1, 3, 4), packed[:n_it, :, 12:]
             if with_icp:
@@ -632,6 +689,9 @@ def pred_eval(config, refiner, batches, evaluator, result_file=None, logger=None
             if vsd is not None:   # and one more for the VSD rows
                 vsd.score(batch, list(poses_dev) + ([refiner.pose_icp if n_hyp == 1 else refiner.pose_icp_sel] if with_icp else []))
                 vsd_host = vsd.packed().cpu().numpy()
+            if bop is not None:   # and one for the BOP rows
+                bop.score(batch, poses_dev, (refiner.pose_icp if n_hyp == 1 else refiner.pose_icp_sel) if with_icp else None)
+                bop_host = bop.packed().cpu().numpy()
             if with_icp:
                 poses_icp = (refiner.pose_icp if n_hyp == 1 else refiner.pose_icp_sel).cpu().numpy().astype(np.float64)
         cls = torch.as_tensor(batch["class_index"]).cpu().numpy().astype(int)
@@ -671,6 +731,12 @@ def pred_eval(config, refiner, batches, evaluator, result_file=None, logger=None
                         e, cnt = ([1.0] * n_tau, [0] * 4) if undetected else (row[:n_tau].tolist(), [int(v) for v in row[n_tau:]])
                         for k, v in zip(VSD_KEYS, [e] + cnt):
                             lists[k][cls[b]][it].append(v)
+            if bop is not None:   # a pair that was not refined: inf, attained by no symmetry
+                for lists, rows_b in ((bop_lists, bop_host[:n_it, b]), (icp_bop_lists, bop_host[n_it:, b])):
+                    for it, row in enumerate(rows_b):
+                        vals = (float("inf"), float("inf"), -1, -1) if undetected else (float(row[0]), float(row[1]), int(row[2]), int(row[3]))
+                        for k, v in zip(BOP_KEYS, vals):
+                            lists[k][cls[b]][it].append(v)
             if device_eval:   # {re, te, add, adi, arp_2d} -> the four lists; a pair that was not refined: the host functions on its row
                 host = evaluator.host_pose_errors(config, evaluator.classes[cls[b]], src[b], gt[b]) if undetected else None
                 pick = lambda e: (e[0], e[1], e[3] if uses_adi[cls[b]] else e[2], e[4])  # noqa: E731
@@ -688,7 +754,7 @@ def pred_eval(config, refiner, batches, evaluator, result_file=None, logger=None
     if merge_ranks and dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
         parts = [None] * dist.get_world_size()
         dist.all_gather_object(parts, (all_rot_err, all_trans_err, all_poses_est, all_poses_gt, icp_lists, hyp_lists, err_lists, icp_err_lists,
-                                       vsd_lists, icp_vsd_lists))
+                                       vsd_lists, icp_vsd_lists, bop_lists, icp_bop_lists))
         for k, mine in enumerate((all_rot_err, all_trans_err, all_poses_est, all_poses_gt)):
             for c in range(n_cls):
                 for it in range(n_it):
@@ -700,7 +766,8 @@ def pred_eval(config, refiner, batches, evaluator, result_file=None, logger=None
         if hyp_lists is not None:
             for k, mine in enumerate(hyp_lists):
                 mine[:] = [x for part in parts for x in part[5][k]]
-        for slot, lists, iters in ((6, err_lists, n_it), (7, icp_err_lists, 1), (8, vsd_lists, n_it), (9, icp_vsd_lists, 1)):
+        for slot, lists, iters in ((6, err_lists, n_it), (7, icp_err_lists, 1), (8, vsd_lists, n_it), (9, icp_vsd_lists, 1),
+                                   (10, bop_lists, n_it), (11, icp_bop_lists, 1)):
             for k in (lists or {}):
                 for c in range(n_cls):
                     for it in range(iters):
@@ -728,6 +795,8 @@ def pred_eval(config, refiner, batches, evaluator, result_file=None, logger=None
         out["device_eval"] = True
     if vsd is not None:
         out["vsd"] = dict(evaluator.evaluate_pose_vsd(config, vsd_lists, logger), errors=vsd_lists)
+    if bop is not None:
+        out["bop"] = dict(evaluator.evaluate_pose_bop(config, bop_lists, logger), errors=bop_lists)
     out["all_rot_err"], out["all_trans_err"] = all_rot_err, all_trans_err
     out["merged_over_ranks"] = merged
     if with_icp:
@@ -747,6 +816,8 @@ def pred_eval(config, refiner, batches, evaluator, result_file=None, logger=None
                       "all_rot_err": icp_rot, "all_trans_err": icp_trans}
         if vsd is not None:
             out["icp"]["vsd"] = dict(evaluator.evaluate_pose_vsd(config, icp_vsd_lists, logger), errors=icp_vsd_lists)
+        if bop is not None:
+            out["icp"]["bop"] = dict(evaluator.evaluate_pose_bop(config, icp_bop_lists, logger), errors=icp_bop_lists)
     if hyp_lists is not None:
         score, choice, rot, trans, undet = hyp_lists
         best = [c == int(np.argmin(r)) for c, r, u in zip(choice, rot, undet) if not u]

@@ -39,12 +39,52 @@ def print_and_log(s, logger=None):
 
 
 class PoseEvaluator(object):
-    def __init__(self, classes, points, diameters):
-        """points: dict class -> (N,3) model points; diameters: dict class -> metres (LM6D_REFINE._points / ._diameters)"""
+    def __init__(self, classes, points, diameters, symmetries=None):
+        """points: dict class -> (N,3) model points; diameters: dict class -> metres (LM6D_REFINE._points / ._diameters);
+        symmetries: dict class -> a BOP model_info ({"symmetries_discrete": ..., "symmetries_continuous": ...}, lib/utils/symmetry.py)
+        or a ready (S,3,4) set, read by the symmetry-aware errors (MSSD, MSPD).  A class without an entry has the identity only,
+        except eggbox: {I, RT_Z}, the rule stated above."""
         self.classes = list(classes)
         self.num_classes = len(self.classes)
         self._points = points
         self._diameters = diameters
+        self._symmetries = dict(symmetries or {})
+
+    def symmetry_sets(self, max_sym_disc_step=0.01):
+        """-> one (S,3,4) float64 set per class, in class order, the identity first"""
+        from lib.utils.symmetry import as_symmetry_set
+
+        cache = self.__dict__.setdefault("_symmetry_sets", {})
+        key = float(max_sym_disc_step)
+        if key not in cache:
+            sets = []
+            for c in self.classes:
+                if c in self._symmetries:
+                    sets.append(as_symmetry_set(self._symmetries[c], key))
+                elif c == "eggbox":
+                    sets.append(np.stack([np.eye(4)[:3], RT_Z]))
+                else:
+                    sets.append(np.eye(4)[None, :3].copy())
+            cache[key] = sets
+        return cache[key]
+
+    def max_sym(self, max_sym_disc_step=0.01):
+        """the size of the largest symmetry set (dim_bop_errors' max_sym)"""
+        return max([len(s) for s in self.symmetry_sets(max_sym_disc_step)] or [1])
+
+    def device_sym_tables(self, device, max_sym_disc_step=0.01):
+        """-> (sym (Stot,3,4) float64, sym_off (n_classes+1,) int32) resident on `device`: the symmetry sets of all classes
+        concatenated, as dim_bop_errors reads them next to device_tables.  Built once per device (and discretisation step)."""
+        import torch
+
+        key = (str(torch.device(device)), float(max_sym_disc_step))
+        cache = self.__dict__.setdefault("_device_sym_tables", {})
+        if key not in cache:
+            sets = self.symmetry_sets(max_sym_disc_step)
+            off = np.concatenate([[0], np.cumsum([len(s) for s in sets])]).astype(np.int32)
+            alls = np.ascontiguousarray(np.concatenate(sets, axis=0)) if sets else np.zeros((0, 3, 4))
+            cache[key] = (torch.from_numpy(alls).to(device), torch.from_numpy(off).to(device))
+        return cache[key]
 
     def device_tables(self, device):
         """-> (points (Ntot,3) float64, table_off (n_classes+1,) int32, class_flags (n_classes,) int32) resident on `device`, the model
@@ -286,4 +326,48 @@ class PoseEvaluator(object):
                 print_and_log("tau={}, mean accuracy: {:.2f}".format(tau, row[tau]), logger)
             overall.append(row)
         return {"acc": acc, "visible_fraction": visib, "overall": overall, "count_all": count_all, "taus": taus, "thresh": thresh,
+                "num_valid_class": num_valid_class}
+
+    # ------------------------------------------------------------------------------------------------ BOP: MSSD / MSPD
+    def evaluate_pose_bop(self, config, errors, logger=None):
+        """errors: {"mssd", "mspd"}: errors[key][cls][iter] = one number per pose (pred_eval with TEST.BOP fills them from
+        dim_bop_errors; inf = a pair that was not refined).  Per class and iteration: the recall (share of poses with e < threshold)
+        at every TEST.BOP_MSSD_THRESH (fractions of the class diameter) and TEST.BOP_MSPD_THRESH (pixels at width 640, scaled by
+        W / 640 with W of config.SCALES), their means AR_MSSD and AR_MSPD as the BOP protocol averages them, and the mean over the
+        classes per iteration."""
+        th_s = np.asarray(config.TEST.BOP_MSSD_THRESH, dtype=np.float64).reshape(-1)
+        scales = getattr(config, "SCALES", None)
+        width = float(scales[0][1]) if scales else 640.0
+        th_p = np.asarray(config.TEST.BOP_MSPD_THRESH, dtype=np.float64).reshape(-1) * (width / 640.0)
+        num_iter = len(errors["mssd"][0]) if len(errors["mssd"]) else 0
+        rec_s = np.zeros((self.num_classes, num_iter, len(th_s)))
+        rec_p = np.zeros((self.num_classes, num_iter, len(th_p)))
+        count_all = np.zeros((self.num_classes,), dtype=np.float32)
+        print_and_log("evaluating pose bop (mssd below {} of the diameter, mspd below {} px)".format(th_s.tolist(), th_p.tolist()), logger)
+        num_valid_class = 0
+        for cls_idx, cls_name in enumerate(self.classes):
+            if not len(errors["mssd"][cls_idx][0]):
+                continue
+            num_valid_class += 1
+            count_all[cls_idx] = len(errors["mssd"][cls_idx][0])
+            for iter_i in range(num_iter):
+                e_s = np.asarray(errors["mssd"][cls_idx][iter_i], dtype=np.float64)
+                e_p = np.asarray(errors["mspd"][cls_idx][iter_i], dtype=np.float64)
+                rec_s[cls_idx, iter_i] = (e_s[:, None] < th_s[None, :] * self._diameters[cls_name]).mean(0)
+                rec_p[cls_idx, iter_i] = (e_p[:, None] < th_p[None, :]).mean(0)
+                print_and_log("** {}, iter {} **".format(cls_name, iter_i + 1), logger)
+                print_and_log("all poses: {}, AR_MSSD: {:.2f}, AR_MSPD: {:.2f}".format(
+                    count_all[cls_idx], rec_s[cls_idx, iter_i].mean() * 100, rec_p[cls_idx, iter_i].mean() * 100), logger)
+        ar_s = rec_s.mean(2) if len(th_s) else np.zeros((self.num_classes, num_iter))
+        ar_p = rec_p.mean(2) if len(th_p) else np.zeros((self.num_classes, num_iter))
+        overall = []
+        n = max(num_valid_class, 1)
+        for iter_i in range(num_iter):
+            row = {"AR_MSSD": np.sum(ar_s[:, iter_i]) / n * 100, "AR_MSPD": np.sum(ar_p[:, iter_i]) / n * 100}
+            overall.append(row)
+            print_and_log("---------- bop performance over {} classes -----------".format(num_valid_class), logger)
+            print_and_log("** iter {} **".format(iter_i + 1), logger)
+            print_and_log("AR_MSSD: {:.2f}, AR_MSPD: {:.2f}".format(row["AR_MSSD"], row["AR_MSPD"]), logger)
+        return {"recall_mssd": rec_s, "recall_mspd": rec_p, "AR_MSSD": ar_s, "AR_MSPD": ar_p, "overall": overall,
+                "count_all": count_all, "thresh_mssd": th_s.tolist(), "thresh_mspd": th_p.tolist(),
                 "num_valid_class": num_valid_class}

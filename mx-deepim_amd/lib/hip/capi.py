@@ -51,6 +51,8 @@ SIGNATURES = {
     "dim_pose_errors": (I, [P, P, P, I, P, P, P, P, P, I, I, P, P, P, P]),
     "dim_vsd_workspace_bytes": (L, [I, I]),
     "dim_vsd_errors": (I, [P, P, P, P, P, P, P, I, I, I, I, F, P, I, I, P, P, P, P]),
+    "dim_bop_errors_workspace_bytes": (L, [I, I, I]),
+    "dim_bop_errors": (I, [P, P, P, P, I, P, P, P, P, P, P, I, I, I, P, P, P, P, P]),
     "dim_refiner_create": (I, [P, P, P, P, I, P]),
     "dim_refiner_run": (I, [P, P, P, P, P, P, P, P, P, P, P]),
     "dim_refiner_run_k": (I, [P, P, P, P, P, P, P, P, P, P, P, P]),

@@ -400,6 +400,59 @@ def vsd_errors(depth_obs, depth_gt, depth_est, K, delta, taus, cost_type="step",
     return errors, counts
 
 
+BOP_ERR_COLUMNS = ("mssd", "mspd")
+
+
+def bop_errors_workspace(T, B, max_sym, device):
+    return torch.empty((max(lib().dim_bop_errors_workspace_bytes(T, B, max_sym), 8) // 8,), dtype=torch.float64, device=device)
+
+
+def bop_errors(points, table_off, sym, sym_off, class_index, poses_est, pose_gt, K, max_sym, K_per_sample=None, errors=None,
+               best_sym=None, status=None, workspace=None):
+    """dim_bop_errors (restated by lib/utils/pose_error.py mssd / mspd): the BOP symmetry-aware errors in float64 on the device.
+    points (Ntot,3) f64 and table_off (n_classes+1,) int32 as PoseEvaluator.device_tables returns them, sym (Stot,3,4) f64 and
+    sym_off (n_classes+1,) int32 as PoseEvaluator.device_sym_tables does, class_index (B,) int32, poses_est (T,B,3,4) or (B,3,4)
+    (= T 1) float32 or float64, pose_gt (B,3,4) f64.  K: the host 3x3 used for every pair unless K_per_sample ((B,3,3) / (B,9), host
+    array or CUDA tensor, made float64) is given.  max_sym: at least the largest set of a class that occurs (a larger set gives a NaN
+    row); it sizes the workspace.  -> errors (T,B,2) f64 (BOP_ERR_COLUMNS), best_sym (T,B,2) int32: the index within the class's set
+    that attains each minimum; without the T axis for a (B,3,4) input.  DIM_STATUS_BAD_CLASS is OR-ed into status (B,) int32 when given"""
+    f64 = torch.float64
+    if poses_est.dtype not in (f32, f64):
+        raise capi.DeepIMHipError("bop_errors: poses_est must be float32 or float64, got {}".format(poses_est.dtype))
+    single = poses_est.dim() == 3
+    T = 1 if single else poses_est.shape[0]
+    B = poses_est.shape[-3]
+    n_classes = table_off.numel() - 1
+    max_sym = int(max_sym)
+    assert tuple(poses_est.shape[-3:]) == (B, 3, 4) and poses_est.dim() in (3, 4) and tuple(pose_gt.shape) == (B, 3, 4)
+    assert points.dim() == 2 and points.shape[1] == 3 and sym_off.numel() == n_classes + 1 and class_index.numel() == B
+    assert sym.dim() == 3 and tuple(sym.shape[1:]) == (3, 4)
+    dev = poses_est.device
+    if errors is None:
+        errors = torch.empty((B, 2) if single else (T, B, 2), dtype=f64, device=dev)
+    if best_sym is None:
+        best_sym = torch.empty((B, 2) if single else (T, B, 2), dtype=i32, device=dev)
+    assert errors.numel() == T * B * 2 and best_sym.numel() == T * B * 2 and (status is None or status.numel() == B)
+    if workspace is None:
+        workspace = bop_errors_workspace(T, B, max_sym, dev)
+    assert max_sym <= 0 or workspace.numel() * workspace.element_size() >= lib().dim_bop_errors_workspace_bytes(T, B, max_sym)
+    keep = np.ascontiguousarray(np.asarray(K, dtype=np.float64).reshape(-1))
+    if keep.size != 9:
+        raise ValueError("expected a 3x3 K, got {} numbers".format(keep.size))
+    kps = None
+    if K_per_sample is not None:
+        kps = torch.as_tensor(K_per_sample).to(dev, f64).reshape(-1, 9).contiguous()
+        if kps.shape[0] != B:
+            raise ValueError("bop K_per_sample must be ({0},3,3) or ({0},9), got {1}".format(B, tuple(torch.as_tensor(K_per_sample).shape)))
+    is32 = poses_est.dtype == f32
+    check(lib().dim_bop_errors(dptr(points, f64), dptr(table_off, i32), dptr(sym, f64), dptr(sym_off, i32), n_classes,
+                               dptr(class_index, i32), dptr(poses_est, f32) if is32 else None, None if is32 else dptr(poses_est, f64),
+                               dptr(pose_gt, f64), keep.ctypes.data, dptr(kps, f64) if kps is not None else None, T, B, max_sym,
+                               dptr(workspace), dptr(errors, f64), dptr(best_sym, i32), dptr(status, i32) if status is not None else None,
+                               current_stream()))
+    return errors, best_sym
+
+
 STATUS_BAD_K = 16   # DIM_STATUS_BAD_K: dim_raster_render_k drew the sample as background (fx <= 0, fy <= 0 or a non-finite entry)
 
 

@@ -35,6 +35,30 @@ def adi(R_est, t_est, R_gt, t_gt, pts):
     return nn_dists.mean()
 
 
+def _transform_pts_sym(pts, R, t, sym):
+    """the model points moved by the symmetry [S_R | S_t], then by the pose"""
+    sym = np.asarray(sym, dtype=np.float64)
+    return transform_pts_Rt(transform_pts_Rt(pts, sym[:, :3], sym[:, 3]), R, t)
+
+
+def mssd(R_est, t_est, R_gt, t_gt, pts, syms):
+    """Maximum Symmetry-Aware Surface Distance (Hodan et al., BOP 2019): the largest distance between a model point under the
+    estimate and under the ground truth, minimised over the symmetries syms (S,3,4) of the model"""
+    pts_est = transform_pts_Rt(pts, R_est, t_est)
+    return min(np.linalg.norm(pts_est - _transform_pts_sym(pts, R_gt, t_gt, sym), axis=1).max() for sym in syms)
+
+
+def mspd(R_est, t_est, R_gt, t_gt, K, pts, syms):
+    """Maximum Symmetry-Aware Projection Distance (BOP 2019), pixels: mssd on the projections K (R p + t) / z"""
+    proj_est = transform_pts_Rt_2d(pts, R_est, t_est, K)
+    es = []
+    for sym in syms:
+        sym = np.asarray(sym, dtype=np.float64)
+        proj_gt = transform_pts_Rt_2d(transform_pts_Rt(pts, sym[:, :3], sym[:, 3]), R_gt, t_gt, K)
+        es.append(np.linalg.norm(proj_est - proj_gt, axis=1).max())
+    return min(es)
+
+
 def re(R_est, R_gt):
     """rotation error in degrees"""
     assert R_est.shape == R_gt.shape == (3, 3)
