@@ -41,6 +41,7 @@ extern "C" {
 #define DIM_STATUS_BAD_K 16        /* dim_raster_render_k: the sample's K has fx <= 0, fy <= 0 or a non-finite entry (rendered as background) */
 #define DIM_STATUS_ICP_FEW_POINTS 32 /* dim_icp_refine: an iteration found fewer than 64 inliers or a singular system (no update) */
 #define DIM_STATUS_HYP_NO_SCORE 64  /* dim_pose_score: fewer than 64 counted pixels, a constant plane or a non-finite sum (score -inf) */
+#define DIM_STATUS_FLOW_PNP_FEW_POINTS 128 /* dim_flow_pnp: an iteration had fewer than 64 weighted points or a singular system (no update) */
 
 const char* dim_last_error(void);
 /* library / device probe: fills name (<= n bytes), returns number of compute units or <0 */
@@ -160,6 +161,38 @@ long dim_icp_workspace_bytes(int B, int H, int W);
 int dim_icp_refine(const float* depth_rendered, const float* depth_observed, const float* mask_observed, const int* bbox, const float* pose_in,
                    const float* K9, const float* K_per_sample, int B, int H, int W, int iters, float max_dist, void* workspace,
                    float* pose_out, float* stats, int* status, void* stream);
+
+/* ---------------------------------------------------------------- pose from predicted flow (a deterministic robust PnP)
+ * The device form of flow2se3 (lib/pair_matching/flow2se3.py:13-56): back-project the rendered depth, add the flow to every pixel,
+ * solve for the pose that maps the 3-D points onto the flowed pixels.  The reference's cv2.solvePnPRansac draws random samples and
+ * exits early; here `iters` fixed Gauss-Newton iterations with a Huber weight under a hard gate (graph-capturable), restated in
+ * float64 by tests/flow_pnp_reference.py.  Per pair b:
+ *   a source pixel (x, y) is taken when it lies inside bbox[b] (B,4 int32 {min_x,max_x,min_y,max_y} inclusive, clipped to the frame,
+ *   as dim_raster_render* returns it; NULL = whole frame), depth_rendered (B,1,H,W) metres > 0, both components of flow (B,2,H,W)
+ *   are finite and valid (B,1,H,W; NULL = none) is >= 0.5 AT THE SOURCE PIXEL (flow2se3 indexes mask_image by source pixel too).
+ *   It gives the point p = d ((x-cx)/fx, (y-cy)/fy, 1) and the target (u, v) = (x + flow_x, y + flow_y); flow[:,0] is dy and
+ *   flow[:,1] dx unless standard_rep != 0 (lib/pair_matching/flow.py, dim_depth_to_flow).  A target outside
+ *   [-0.5, W-0.5] x [-0.5, H-0.5] is dropped.
+ *   T = [R|t] starts at the identity.  Each iteration: m = R p + t (m_z <= 0: dropped), r = (fx m_x/m_z + cx - u,
+ *   fy m_y/m_z + cy - v), e = |r|; weight w = 1 in the first `warm` iterations (at the identity the residual is the flow itself, so
+ *   nothing may be gated yet), afterwards w = 0 when e > max_px, 1 when e <= huber_px and huber_px / e between; Jacobian rows in
+ *   the left twist xi = (omega, v), dm = omega x m + v; (A + 1e-9 tr(A)/6 I) xi = -sum w J^T r by float64 Cholesky,
+ *   T <- [Rodrigues(omega) | v] T.  Fewer than 64 points with w > 0 or a non-positive-definite A: no update, and
+ *   DIM_STATUS_FLOW_PNP_FEW_POINTS is OR-ed into status[b] (B int32, may be NULL).
+ * pose_out (B,3,4) f32 = T pose_src (pose_src (B,3,4): the pose depth_rendered was rendered at); a pair that never updated gets
+ * pose_src bit for bit.  se3_q (B,7) f32 or NULL = [mat2quat(R), t] as flow2se3 returns it ([1,0,0,0,0,0,0] for a pair that never
+ * updated, flow2se3's "not convex" answer).  stats (B,iters,2) f32 or NULL = (points with w > 0, rms of e over them in pixels) of every
+ * iteration before its update.  Camera as dim_icp_refine: K_per_sample (B,9) device f32 or NULL = K9 (host, 9 floats) for every
+ * pair; a non-positive or non-finite focal length gives the pair no points.
+ * workspace: dim_flow_pnp_workspace_bytes(B, H, W) bytes, 8-byte aligned, no initialisation needed.
+ * Arithmetic: float64 per point, per lane, across lanes, waves and workgroups in a fixed order (no atomics): a replay is
+ * bit-identical.  Four pixels per lane, as 16-byte loads when W % 4 == 0 and the planes are 16-byte aligned.  2 launches per
+ * iteration; iters == 0 copies pose_src to pose_out (and writes the identity se3_q).  B <= 0, iters < 0, warm < 0, huber_px <= 0,
+ * max_px < huber_px, H or W < 1 or a NULL required pointer return DIM_ERR_ARG before anything is enqueued. */
+long dim_flow_pnp_workspace_bytes(int B, int H, int W);
+int dim_flow_pnp(const float* depth_rendered, const float* flow, const float* valid, const int* bbox, const float* pose_src, const float* K9,
+                 const float* K_per_sample, int B, int H, int W, int standard_rep, int iters, int warm, float huber_px, float max_px,
+                 void* workspace, float* pose_out, float* se3_q, float* stats, int* status, void* stream);
 
 /* ---------------------------------------------------------------- multi-hypothesis refinement (several starting poses per pair)
  * Samples are pair-major: sample b = p * N + h of P pairs with N hypotheses each.  Restated in float64 by tests/hyp_reference.py.

@@ -10,6 +10,7 @@
 //                          stats / status, and after the last iteration pose_out = T_delta T0
 // Two launches per iteration; nothing allocates or synchronises, so the stage is graph-capturable.
 #include "common.h"
+#include "twist_solve.h"
 
 namespace dim {
 
@@ -135,50 +136,6 @@ __global__ __launch_bounds__(256) void icp_accumulate_kernel(const float* __rest
   }
 }
 
-__device__ void icp_rodrigues(const double* w, double* Rw) {
-  const double th = sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]);
-  const double Wx[9] = {0.0, -w[2], w[1], w[2], 0.0, -w[0], -w[1], w[0], 0.0};
-  double a = 1.0, bq = 0.0;
-  if (th >= 1e-12) {
-    a = sin(th) / th;
-    bq = (1.0 - cos(th)) / (th * th);
-  }
-  for (int i = 0; i < 3; ++i)
-    for (int j = 0; j < 3; ++j) {
-      double w2 = 0.0;
-      for (int k = 0; k < 3; ++k) w2 += Wx[3 * i + k] * Wx[3 * k + j];
-      Rw[3 * i + j] = (i == j ? 1.0 : 0.0) + a * Wx[3 * i + j] + bq * w2;
-    }
-}
-
-// -> false when A is not positive definite
-__device__ bool icp_cholesky_solve(const double* A, const double* rhs, double* x) {
-  double L[36] = {};
-  for (int j = 0; j < 6; ++j) {
-    double s = A[6 * j + j];
-    for (int k = 0; k < j; ++k) s -= L[6 * j + k] * L[6 * j + k];
-    if (!(s > 0.0)) return false;
-    L[6 * j + j] = sqrt(s);
-    for (int i = j + 1; i < 6; ++i) {
-      double v = A[6 * i + j];
-      for (int k = 0; k < j; ++k) v -= L[6 * i + k] * L[6 * j + k];
-      L[6 * i + j] = v / L[6 * j + j];
-    }
-  }
-  double y[6];
-  for (int i = 0; i < 6; ++i) {
-    double v = rhs[i];
-    for (int k = 0; k < i; ++k) v -= L[6 * i + k] * y[k];
-    y[i] = v / L[6 * i + i];
-  }
-  for (int i = 5; i >= 0; --i) {
-    double v = y[i];
-    for (int k = i + 1; k < 6; ++k) v -= L[6 * k + i] * x[k];
-    x[i] = v / L[6 * i + i];
-  }
-  return true;
-}
-
 __global__ __launch_bounds__(64) void icp_solve_kernel(const double* __restrict__ partial, double* __restrict__ state, int it, int iters,
                                                       const float* __restrict__ pose_in, float* __restrict__ pose_out,
                                                       float* __restrict__ stats, int* __restrict__ status) {
@@ -215,11 +172,11 @@ __global__ __launch_bounds__(64) void icp_solve_kernel(const double* __restrict_
       A[6 * a + a] += damp;
       g[a] = -s[21 + a];
     }
-    ok = icp_cholesky_solve(A, g, xi);
+    ok = cholesky_solve6(A, g, xi);
   }
   if (ok) {
     double Rw[9], Rn[9], tn[3];
-    icp_rodrigues(xi, Rw);
+    twist_rodrigues(xi, Rw);
     for (int i = 0; i < 3; ++i) {
       for (int j = 0; j < 3; ++j) Rn[3 * i + j] = Rw[3 * i] * R[j] + Rw[3 * i + 1] * R[3 + j] + Rw[3 * i + 2] * R[6 + j];
       tn[i] = Rw[3 * i] * t[0] + Rw[3 * i + 1] * t[1] + Rw[3 * i + 2] * t[2] + xi[3 + i];

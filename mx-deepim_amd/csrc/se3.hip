@@ -6,6 +6,7 @@
 // Keeping these on the GPU removes the asnumpy() sync + numpy + re-upload between refinement iterations
 // (deepim/core/tester.py:523-532, lib/pair_matching/batch_updater_py_multi.py:211-312).
 #include "common.h"
+#include "twist_solve.h"
 
 namespace dim {
 
@@ -29,26 +30,6 @@ __device__ inline void quat2mat_d(const double q[4], double M[9]) {
 __device__ inline void mat3_mul(const double A[9], const double B[9], double C[9]) {
   for (int i = 0; i < 3; ++i)
     for (int j = 0; j < 3; ++j) C[3 * i + j] = A[3 * i] * B[j] + A[3 * i + 1] * B[3 + j] + A[3 * i + 2] * B[6 + j];
-}
-
-// rotation matrix -> (w,x,y,z), w >= 0.  The reference takes the dominant eigenvector of the
-// Bar-Itzhack matrix (mat2quat, RT_transform.py:446-523); for a rotation matrix that vector is
-// the usual quaternion, computed here with Shepperd's branch selection and normalised.
-__device__ inline void mat2quat_d(const double M[9], double q[4]) {
-  double tr = M[0] + M[4] + M[8];
-  double w, x, y, z;
-  if (tr > M[0] && tr > M[4] && tr > M[8]) {
-    w = 1.0 + tr; x = M[7] - M[5]; y = M[2] - M[6]; z = M[3] - M[1];
-  } else if (M[0] > M[4] && M[0] > M[8]) {
-    x = 1.0 + M[0] - M[4] - M[8]; w = M[7] - M[5]; y = M[1] + M[3]; z = M[2] + M[6];
-  } else if (M[4] > M[8]) {
-    y = 1.0 - M[0] + M[4] - M[8]; w = M[2] - M[6]; x = M[1] + M[3]; z = M[5] + M[7];
-  } else {
-    z = 1.0 - M[0] - M[4] + M[8]; w = M[3] - M[1]; x = M[2] + M[6]; y = M[5] + M[7];
-  }
-  double n = sqrt(w * w + x * x + y * y + z * z);
-  if (w < 0) n = -n;
-  q[0] = w / n; q[1] = x / n; q[2] = y / n; q[3] = z / n;
 }
 
 // Euler angles of the reference's EULER deltas: euler2mat / mat2euler with their default axes "sxyz" (RT_transform.py:250-383; the only

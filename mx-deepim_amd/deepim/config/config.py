@@ -66,6 +66,9 @@ def _defaults():
     c.TEST = edict(BATCH_PAIRS=1, test_epoch=0, VISUALIZE=False, test_iter=1, INIT_MASK="box_rendered", UPDATE_MASK="box_rendered",
                    FAST_TEST=False, PRECOMPUTED_ICP=False, BEFORE_ICP=False,
                    ICP_ITER=0, ICP_MAX_DIST=0.02,   # depth ICP after the loop: iterations (0 = off), gate in metres
+                   # pose from the flow head's output at every loop iteration (dim_flow_pnp; needs PRED_FLOW and the full graph):
+                   # Gauss-Newton iterations (0 = off), how many of them are unweighted, the Huber knee and the hard gate (pixels)
+                   FLOW_PNP_ITER=0, FLOW_PNP_WARM=2, FLOW_PNP_HUBER_PX=2.0, FLOW_PNP_MAX_PX=8.0,
                    # several starting poses per pair, scored after the loop (1 = off): rotation of the generated ones (degrees), the
                    # score ("rgb" ZNCC or "depth" inlier fraction) and the depth score's inlier gate (metres)
                    HYP_NUM=1, HYP_ROT_DEG=30.0, HYP_SCORE="rgb", HYP_DEPTH_TAU=0.02,

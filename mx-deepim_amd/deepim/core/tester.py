@@ -43,6 +43,32 @@ def hyp_settings(cfg):
     return int(n), deg, score, tau
 
 
+def flow_pnp_settings(cfg):
+    """-> (FLOW_PNP_ITER, FLOW_PNP_WARM, FLOW_PNP_HUBER_PX, FLOW_PNP_MAX_PX) of cfg.TEST, checked; ValueError names the bad key(s).
+    The stage reads the flow head's output of every loop iteration, so it needs PRED_FLOW and the full (not FAST_TEST) graph; choosing
+    among per-hypothesis flow poses is not defined, so it is refused together with HYP_NUM > 1."""
+    T = cfg.TEST
+    n = T.get("FLOW_PNP_ITER", 0) or 0
+    if isinstance(n, bool) or not float(n).is_integer() or int(n) < 0:
+        raise ValueError("TEST.FLOW_PNP_ITER must be an integer >= 0 (0 = off), got {!r}".format(n))
+    warm = T.get("FLOW_PNP_WARM", 2)
+    if isinstance(warm, bool) or not float(warm).is_integer() or int(warm) < 0:
+        raise ValueError("TEST.FLOW_PNP_WARM must be an integer >= 0, got {!r}".format(warm))
+    huber, gate = float(T.get("FLOW_PNP_HUBER_PX", 2.0)), float(T.get("FLOW_PNP_MAX_PX", 8.0))
+    if not (np.isfinite(huber) and huber > 0):
+        raise ValueError("TEST.FLOW_PNP_HUBER_PX must be a finite number of pixels > 0, got {!r}".format(T.get("FLOW_PNP_HUBER_PX")))
+    if not (np.isfinite(gate) and gate >= huber):
+        raise ValueError("TEST.FLOW_PNP_MAX_PX must be finite and >= TEST.FLOW_PNP_HUBER_PX, got {!r}".format(T.get("FLOW_PNP_MAX_PX")))
+    if int(n) > 0:
+        if not cfg.network.PRED_FLOW:
+            raise ValueError("TEST.FLOW_PNP_ITER > 0 needs network.PRED_FLOW (the stage reads the flow head's output)")
+        if T.FAST_TEST:
+            raise ValueError("TEST.FLOW_PNP_ITER > 0 needs TEST.FAST_TEST off (the fast graph has no flow head)")
+        if int(T.get("HYP_NUM", 1)) > 1:
+            raise ValueError("TEST.FLOW_PNP_ITER > 0 cannot be combined with TEST.HYP_NUM > 1")
+    return int(n), int(warm), huber, gate
+
+
 def hypothesis_rotations(N, rot_deg):
     """(N,3,3) float64: R_0 = I; R_h (h >= 1) = the Rodrigues rotation by rot_deg about axis h-1 of a Fibonacci sphere of N-1 points,
     z = 1 - (2k+1)/(N-1), r = sqrt(1-z^2), phi = k pi (3 - sqrt 5), axis = (r cos phi, r sin phi, z).  Hypothesis h starts the
@@ -82,6 +108,7 @@ class Refiner(object):
             # same restriction as the released loop (tester.py:579-587)
             raise Exception("Unknown UPDATE_MASK type: {}".format(cfg.TEST.UPDATE_MASK))
         self.hyp_num, self.hyp_rot_deg, self.hyp_score_mode, self.hyp_tau = hyp_settings(cfg)
+        self.flow_pnp_iter, self.flow_pnp_warm, self.flow_pnp_huber, self.flow_pnp_gate = flow_pnp_settings(cfg)
         N = self.hyp_num
         if N > 1 and predictor.net.B != batch_size * N:
             raise ValueError("Refiner: {} pairs x TEST.HYP_NUM {} = {} samples, but the Predictor was built for {} samples".format(
@@ -147,6 +174,20 @@ class Refiner(object):
             self.icp_stats = torch.zeros((B, self.icp_iter, 2), dtype=torch.float32, device=d)
             self.status_icp = torch.zeros((B,), dtype=torch.int32, device=d)
             self.icp_work = ops.icp_workspace(B, H, W, d)
+        # pose from the flow head's output at every iteration (TEST.FLOW_PNP_ITER > 0): the depth of the render each forward looked
+        # at (INPUT_DEPTH graphs hold it already), the box of the initial render, and the per-iteration outputs
+        self.pose_flow_iter = self.se3_flow_iter = self.flow_pnp_stats = self.status_flow = None
+        if self.flow_pnp_iter > 0:
+            if self.flow_est_iter is None:
+                raise ValueError("TEST.FLOW_PNP_ITER > 0: the network has no flow head (network.PRED_FLOW with a decoder)")
+            if not self.input_depth:
+                self.depth_flow = torch.zeros((B, 1, H, W), dtype=torch.float32, device=d)
+                self.bbox_flow = torch.zeros((B, 4), dtype=torch.int32, device=d)
+            self.pose_flow_iter = torch.zeros((self.test_iter, B, 3, 4), dtype=torch.float32, device=d)
+            self.se3_flow_iter = torch.zeros((self.test_iter, B, 7), dtype=torch.float32, device=d)
+            self.flow_pnp_stats = torch.zeros((self.test_iter, B, self.flow_pnp_iter, 2), dtype=torch.float32, device=d)
+            self.status_flow = torch.zeros((self.test_iter, B), dtype=torch.int32, device=d)
+            self.flow_work = ops.flow_pnp_workspace(B, H, W, d)
         # several hypotheses per pair (TEST.HYP_NUM > 1): the loaded pairs land in `pair` (P rows) and are expanded into the B = P*N
         # sample rows by load(); after the loop: the render at the last pose, the scores, the choice and the selected outputs
         self.pair = self.hyp_score = self.hyp_choice = self.poses_sel = self.status_sel = self.pose_icp_sel = None
@@ -321,6 +362,18 @@ class Refiner(object):
                 cur[k] = b[k]
         bbox_ren = bbox_obs = None
         pose = self.pose_init
+        flow_on = self.flow_pnp_iter > 0
+        if flow_on:
+            # the first forward looks at the loaded render, whose depth is not among the blobs: render pose_init once more, depth and
+            # box only (an INPUT_DEPTH graph has the plane; its box is not known, so the first stage scans the whole frame)
+            K_flow = self.K_pair if (self.per_pair_K and not self.lit) else None
+            ops.fill(self.status_flow, 0)
+            if not self.input_depth:
+                extra = {"light_intensity": self.light_int[0]} if self.lit else {}
+                if K_flow is not None:
+                    extra["K"] = K_flow
+                self.render_machine.render_batch(b["class_index"], pose, depth=self.depth_flow, bbox=self.bbox_flow, mask_thr=0.0,
+                                                 status=self.status_flow[0], **extra)
         for it in range(self.test_iter):
             # se3 and status land directly in their per-iteration rows; the pose of the previous iteration is read where it lies
             out = net.forward_test(cur, bbox_ren=bbox_ren, bbox_obs=bbox_obs, src_pose=pose, se3_out=self.se3_iter[it],
@@ -329,6 +382,15 @@ class Refiner(object):
                 ops.copy(self.mask_pred_iter[it], out["mask_observed_pred_output"])
             if self.flow_est_iter is not None:
                 ops.copy(self.flow_est_iter[it], out["flow_est_crop_output"])
+            if flow_on:
+                # flow2se3 on what this forward saw: the render's depth and box, the flow it predicted, mask_observed as it read it.
+                # The result is recorded only: the next iteration starts from the head's pose
+                ops.flow_pnp(cur["depth_rendered"] if self.input_depth else self.depth_flow, self.flow_est_iter[it], pose,
+                             self.render_machine.K, self.flow_pnp_iter, self.flow_pnp_warm, self.flow_pnp_huber, self.flow_pnp_gate,
+                             standard_rep=bool(cfg.network.STANDARD_FLOW_REP), valid=cur["mask_observed"],
+                             bbox=bbox_ren if it > 0 else (None if self.input_depth else self.bbox_flow), K_per_sample=K_flow,
+                             pose_out=self.pose_flow_iter[it], se3_q=self.se3_flow_iter[it], stats=self.flow_pnp_stats[it],
+                             status=self.status_flow[it], workspace=self.flow_work)
             # pose_rendered_update = RT_transform(pose_rendered, se3[:-3], se3[-3:], ...)   (:525-532)
             ops.se3_compose(pose, self.se3_iter[it], cfg.network.ROT_COORD, self.T_means, self.T_stds, out=self.poses_iter[it])
             if it < self.test_iter - 1:
@@ -340,6 +402,8 @@ class Refiner(object):
                 # and the depth plane is not materialised -- 1.2 MB per pair and render less to write)
                 if self.input_depth:
                     extra["depth"] = b["depth_rendered"]   # INPUT_DEPTH: the rendered depth is a network input (tester.py:573-574)
+                elif flow_on:
+                    extra["depth"] = self.depth_flow       # the next iteration's flow stage back-projects it
                 # from the second render on the planes hold the previous render: background outside ITS box, which is not written again
                 bb_new, bb_prev = (self.bbox, self.bbox2) if it % 2 == 0 else (self.bbox2, self.bbox)
                 self.render_machine.render_batch(b["class_index"], self.poses_iter[it], image=b["image_rendered"],
@@ -391,7 +455,10 @@ class Refiner(object):
 
     def refine(self):
         """run test_iter iterations on the loaded batch; returns poses_iter (test_iter,B,3,4) (device).  With TEST.ICP_ITER > 0 the
-        ICP stage runs after them (inside the same graph) and leaves its pose in pose_icp (B,3,4).  With TEST.HYP_NUM > 1 it returns
+        ICP stage runs after them (inside the same graph) and leaves its pose in pose_icp (B,3,4).  With TEST.FLOW_PNP_ITER > 0 every
+        iteration also solves the pose from its flow head's output (dim_flow_pnp, inside the same graph): pose_flow_iter
+        (test_iter,B,3,4), se3_flow_iter (test_iter,B,7), flow_pnp_stats (test_iter,B,FLOW_PNP_ITER,2), status_flow (test_iter,B);
+        the loop itself never reads them.  With TEST.HYP_NUM > 1 it returns
         the selected hypothesis of each pair, poses_sel (test_iter,P,3,4); poses_iter (all P*N samples), hyp_score (P*N,),
         hyp_choice (P,), status_sel (test_iter,P) and pose_icp_sel (P,3,4) stay readable on the Refiner."""
         if self.graph is not None and self._graph_per_pair_K != self.per_pair_K:
@@ -607,7 +674,12 @@ def pred_eval(config, refiner, batches, evaluator, result_file=None, logger=None
     symmetry sets (BopScorer, one dim_bop_errors call per batch): out["bop"] = the table of PoseEvaluator.evaluate_pose_bop plus
     "errors", the per-pose lists {mssd, mspd, sym_mssd, sym_mspd}[cls][iter] in the order of all_poses_est; out["icp"]["bop"] the same
     for the ICP row.  A pair that was not refined scores inf for both (symmetry -1).  The numbers travel like the VSD ones.  Every
-    other output and the result cache are those of BOP off."""
+    other output and the result cache are those of BOP off.
+    With TEST.FLOW_PNP_ITER > 0 the refiner's poses from flow (pose_flow_iter, one per loop iteration) are scored next to the head's,
+    by the same error code (the host functions, or dim_pose_errors under TEST.DEVICE_EVAL): out["flow_pnp"] = {pose, add: the tables
+    of evaluate_pose / evaluate_pose_add; all_rot_err, all_trans_err; inliers, rms: per loop iteration the mean over the refined pairs
+    of the stage's last weighted point count and pixel rms; flagged: per loop iteration the number of pairs with
+    DIM_STATUS_FLOW_PNP_FEW_POINTS}.  Every other output and the result cache are those of the stage off."""
     import copy
     import pickle
 
@@ -649,12 +721,20 @@ def pred_eval(config, refiner, batches, evaluator, result_file=None, logger=None
         bop = BopScorer(config, refiner, evaluator, n_it + (1 if with_icp else 0))
         bop_lists = {k: [[[] for _ in range(n_it)] for _ in range(n_cls)] for k in BOP_KEYS}
         icp_bop_lists = {k: [[[]] for _ in range(n_cls)] for k in BOP_KEYS} if with_icp else None
+    # pose from flow at every iteration: [rot_err, trans_err, poses_est, poses_gt][cls][iter], and per refined pair (iter, 3) =
+    # (weighted points, rms, flagged) of the stage's last Gauss-Newton iteration
+    with_flow = int(config.TEST.get("FLOW_PNP_ITER", 0) or 0) > 0
+    flow_lists = tuple([[[] for _ in range(n_it)] for _ in range(n_cls)] for _ in range(4)) if with_flow else None
+    flow_err_lists = {k: [[[] for _ in range(n_it)] for _ in range(n_cls)] for k in ERR_KEYS} if (with_flow and device_eval) else None
+    flow_rows = [] if with_flow else None
     # flow error of the first forward (:500-512): only the full test graph emits the flow head's output
     epe = FlowEPE(config, getattr(refiner, "P", refiner.B), refiner.net.device) if (config.network.PRED_FLOW and not config.TEST.FAST_TEST) else None
     for batch in batches:
         extra = {"hyp_poses": batch["hyp_poses"]} if batch.get("hyp_poses") is not None else {}
         if vsd is not None:
             vsd.check(batch)
+        if with_flow and "pose_observed" not in batch:
+            raise KeyError("pose from flow (TEST.FLOW_PNP_ITER > 0) needs the blob 'pose_observed' to be scored")
         refiner.load(batch["image_observed"], batch["image_rendered"], batch["mask_observed"], batch["mask_rendered"], batch["src_pose"],
                      batch["class_index"], depth_observed=batch.get("depth_observed"), K=batch.get("K"), **extra)
         if device_eval:
@@ -694,6 +774,13 @@ def pred_eval(config, refiner, batches, evaluator, result_file=None, logger=None
                 bop_host = bop.packed().cpu().numpy()
             if with_icp:
                 poses_icp = (refiner.pose_icp if n_hyp == 1 else refiner.pose_icp_sel).cpu().numpy().astype(np.float64)
+        if with_flow:   # one more copy per batch: the flow poses [and their device errors], and the stage's last stats / status
+            pf = refiner.pose_flow_iter.to(torch.float64).reshape(n_it, -1, 12)
+            if device_eval:
+                pf = torch.cat([pf, ops.pose_errors(tables[0], tables[1], tables[2], cls_dev, refiner.pose_flow_iter, gt_dev, K_eval)], dim=2)
+            pf = torch.cat([pf, refiner.flow_pnp_stats[:, :, -1].to(torch.float64),
+                            (refiner.status_flow & ops.STATUS_FLOW_PNP_FEW_POINTS).ne(0).to(torch.float64)[:, :, None]], dim=2).cpu().numpy()
+            poses_flow, flow_dev_err, flow_stat = pf[:, :, :12].reshape(n_it, -1, 3, 4), pf[:, :, 12:-3], pf[:, :, -3:]
         cls = torch.as_tensor(batch["class_index"]).cpu().numpy().astype(int)
         gt = torch.as_tensor(batch["pose_observed"]).cpu().numpy().astype(np.float64)
         src = torch.as_tensor(batch["src_pose"]).cpu().numpy().astype(np.float64)
@@ -720,6 +807,14 @@ def pred_eval(config, refiner, batches, evaluator, result_file=None, logger=None
                 all_poses_gt[cls[b]][it].append(gt[b])
                 all_rot_err[cls[b]][it].append(r_dist)
                 all_trans_err[cls[b]][it].append(t_dist)
+            if with_flow:   # scored as the loop's poses are; the stage's statistics count refined pairs only
+                for it in range(n_it):
+                    est = src[b] if undetected else poses_flow[it, b]
+                    r_dist, t_dist = (1000, 1000) if undetected else calc_rt_dist_m(est, gt[b])
+                    for k, v in enumerate((r_dist, t_dist, est, gt[b])):
+                        flow_lists[k][cls[b]][it].append(v)
+                if not undetected:
+                    flow_rows.append(flow_stat[:, b].tolist())
             if with_icp:   # an undetected object is scored as the loop scores it
                 est = src[b] if undetected else poses_icp[b]
                 r_dist, t_dist = (1000, 1000) if undetected else calc_rt_dist_m(est, gt[b])
@@ -746,6 +841,10 @@ def pred_eval(config, refiner, batches, evaluator, result_file=None, logger=None
                 if with_icp:
                     for k, v in zip(ERR_KEYS, host or pick(dev_err_icp[b])):
                         icp_err_lists[k][cls[b]][0].append(float(v))
+                if with_flow:
+                    for it in range(n_it):
+                        for k, v in zip(ERR_KEYS, host or pick(flow_dev_err[it, b])):
+                            flow_err_lists[k][cls[b]][it].append(float(v))
     # several ranks refine disjoint shards (one process per GPU): the metrics are over ALL pairs, so the per-class lists are merged in
     # rank order on every rank before scoring (the reference scores one list in one process)
     import torch.distributed as dist
@@ -754,7 +853,7 @@ def pred_eval(config, refiner, batches, evaluator, result_file=None, logger=None
     if merge_ranks and dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
         parts = [None] * dist.get_world_size()
         dist.all_gather_object(parts, (all_rot_err, all_trans_err, all_poses_est, all_poses_gt, icp_lists, hyp_lists, err_lists, icp_err_lists,
-                                       vsd_lists, icp_vsd_lists, bop_lists, icp_bop_lists))
+                                       vsd_lists, icp_vsd_lists, bop_lists, icp_bop_lists, flow_lists, flow_err_lists, flow_rows))
         for k, mine in enumerate((all_rot_err, all_trans_err, all_poses_est, all_poses_gt)):
             for c in range(n_cls):
                 for it in range(n_it):
@@ -772,6 +871,16 @@ def pred_eval(config, refiner, batches, evaluator, result_file=None, logger=None
                 for c in range(n_cls):
                     for it in range(iters):
                         lists[k][c][it] = [x for part in parts for x in part[slot][k][c][it]]
+        if with_flow:
+            for k, mine in enumerate(flow_lists):
+                for c in range(n_cls):
+                    for it in range(n_it):
+                        mine[c][it] = [x for part in parts for x in part[12][k][c][it]]
+            for k in (flow_err_lists or {}):
+                for c in range(n_cls):
+                    for it in range(n_it):
+                        flow_err_lists[k][c][it] = [x for part in parts for x in part[13][k][c][it]]
+            flow_rows[:] = [x for part in parts for x in part[14]]
         merged = True
         if dist.get_rank() != 0:
             result_file = None   # one result cache, written by rank 0
@@ -818,6 +927,26 @@ def pred_eval(config, refiner, batches, evaluator, result_file=None, logger=None
             out["icp"]["vsd"] = dict(evaluator.evaluate_pose_vsd(config, icp_vsd_lists, logger), errors=icp_vsd_lists)
         if bop is not None:
             out["icp"]["bop"] = dict(evaluator.evaluate_pose_bop(config, icp_bop_lists, logger), errors=icp_bop_lists)
+    if with_flow:
+        flow_rot, flow_trans, flow_est, flow_gt = flow_lists
+        line = "evaluate pose from flow ({} iterations, {} unweighted, Huber {} px, gate {} px):".format(
+            int(config.TEST.FLOW_PNP_ITER), int(config.TEST.FLOW_PNP_WARM), float(config.TEST.FLOW_PNP_HUBER_PX), float(config.TEST.FLOW_PNP_MAX_PX))
+        print(line)
+        if logger:
+            logger.info(line)
+        given = {"errors": flow_err_lists} if device_eval else {}
+        rows = np.asarray(flow_rows, dtype=np.float64).reshape(-1, n_it, 3)
+        mean = rows.mean(axis=0) if len(rows) else np.full((n_it, 3), np.nan)
+        out["flow_pnp"] = {"pose": evaluator.evaluate_pose(config, flow_est, flow_gt, logger, **given),
+                           "add": evaluator.evaluate_pose_add(config, flow_est, flow_gt, output_dir=None, logger=logger, **given),
+                           "all_rot_err": flow_rot, "all_trans_err": flow_trans, "inliers": mean[:, 0].tolist(), "rms": mean[:, 1].tolist(),
+                           "flagged": [int(v) for v in rows[:, :, 2].sum(axis=0)]}
+        for it in range(n_it):
+            line = "iter {}: {:.1f} weighted points, rms {:.3f} px, {} of {} pairs flagged".format(
+                it + 1, mean[it, 0], mean[it, 1], out["flow_pnp"]["flagged"][it], len(rows))
+            print(line)
+            if logger:
+                logger.info(line)
     if hyp_lists is not None:
         score, choice, rot, trans, undet = hyp_lists
         best = [c == int(np.argmin(r)) for c, r, u in zip(choice, rot, undet) if not u]

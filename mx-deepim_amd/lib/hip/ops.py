@@ -232,6 +232,37 @@ def icp_refine(depth_rendered, depth_observed, pose_in, K, iters, max_dist, mask
     return pose_out
 
 
+STATUS_FLOW_PNP_FEW_POINTS = 128   # DIM_STATUS_FLOW_PNP_FEW_POINTS: a flow-PnP iteration had < 64 weighted points or a singular system
+
+
+def flow_pnp_workspace(B, H, W, device):
+    return torch.empty((max(lib().dim_flow_pnp_workspace_bytes(B, H, W), 8) // 8,), dtype=torch.float64, device=device)
+
+
+def flow_pnp(depth_rendered, flow, pose_src, K, iters, warm=2, huber_px=2.0, max_px=8.0, standard_rep=False, valid=None, bbox=None,
+             K_per_sample=None, pose_out=None, se3_q=None, stats=None, status=None, workspace=None):
+    """pose from flow, dim_flow_pnp (restated by tests/flow_pnp_reference.py; the reference's flow2se3): depth_rendered (B,1,H,W)
+    rendered at pose_src (B,3,4), flow (B,2,H,W) from the rendered image to the observed one in full-image pixels ((dy,dx) unless
+    standard_rep), valid (B,1,H,W) read at the source pixel (None = every pixel), bbox (B,4) int32 of the render (None = whole frame);
+    K / K_per_sample as icp_refine.  -> (pose_out (B,3,4), se3_q (B,7) = [quat, t] of the estimated transform); stats (B,iters,2) =
+    (weighted points, rms pixel residual) per iteration, status (B,) int32: DIM_STATUS_FLOW_PNP_FEW_POINTS is OR-ed in."""
+    B, _, H, W = depth_rendered.shape
+    assert tuple(flow.shape) == (B, 2, H, W) and tuple(pose_src.shape) == (B, 3, 4)
+    assert valid is None or valid.shape == depth_rendered.shape
+    pose_out = pose_out if pose_out is not None else _new((B, 3, 4), pose_src)
+    se3_q = se3_q if se3_q is not None else _new((B, 7), pose_src)
+    if workspace is None:
+        workspace = flow_pnp_workspace(B, H, W, pose_src.device)
+    kps = intrinsics_per_sample(K_per_sample, B, pose_src.device)
+    keep, kp = host_f32(K, 9)
+    opt = lambda t, dt=f32: dptr(t, dt) if t is not None else None  # noqa: E731
+    check(lib().dim_flow_pnp(dptr(depth_rendered, f32), dptr(flow, f32), opt(valid), opt(bbox, i32), dptr(pose_src, f32), kp, opt(kps), B, H,
+                             W, int(bool(standard_rep)), int(iters), int(warm), float(huber_px), float(max_px),
+                             dptr(workspace, torch.float64), dptr(pose_out, f32), dptr(se3_q, f32), opt(stats), opt(status, i32),
+                             current_stream()))
+    return pose_out, se3_q
+
+
 STATUS_HYP_NO_SCORE = 64   # DIM_STATUS_HYP_NO_SCORE: dim_pose_score had < 64 counted pixels, a constant plane or a non-finite sum
 HYP_SCORE_ID = {"rgb": 0, "depth": 1}   # DIM_HYP_SCORE_RGB / DIM_HYP_SCORE_DEPTH
 
