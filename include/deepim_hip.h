@@ -42,6 +42,7 @@ extern "C" {
 #define DIM_STATUS_ICP_FEW_POINTS 32 /* dim_icp_refine: an iteration found fewer than 64 inliers or a singular system (no update) */
 #define DIM_STATUS_HYP_NO_SCORE 64  /* dim_pose_score: fewer than 64 counted pixels, a constant plane or a non-finite sum (score -inf) */
 #define DIM_STATUS_FLOW_PNP_FEW_POINTS 128 /* dim_flow_pnp: an iteration had fewer than 64 weighted points or a singular system (no update) */
+#define DIM_STATUS_LAYER_HIDDEN 256 /* dim_scene_compose: a used layer won no pixel (empty or wholly hidden); per layer, (N*S) words */
 
 const char* dim_last_error(void);
 /* library / device probe: fills name (<= n bytes), returns number of compute units or <0 */
@@ -402,12 +403,44 @@ int dim_raster_render_k(const float* verts, const float* normals, const float* u
                         float* image, float* depth, float* mask, float* bgr, int* bbox, int* status, const int* clean_bbox,
                         const float* K_per_sample, void* stream);
 
+/* dim_raster_render_k under the LINEMOD light rule: Render_Py_Light.render / Render_Py_Light_MultiProgram.render
+ * (lib/render_glumpy/render_py_light.py:74, render_py_light_multi_program.py:76).  The light colour scales the diffuse term only:
+ *   colour = texel/255 * ((1-ratio) + ratio*clamp(cos(normal, light-position),0,1)*light_int)
+ * where dim_raster_render_lit (ModelNet) computes texel/255 * ((1-ratio) + ratio*cos) * light_int.  Normal, light vector, clamp and
+ * 8-bit quantisation are the same; with light_int = (1,1,1) or ratio = 1 the two rules give the same bytes.  Always lit: normals,
+ * light_pos and light_int are required.  Every other argument as in dim_raster_render_k. */
+int dim_raster_render_lit_lm(const float* verts, const float* normals, const float* uvs, const int* faces, const int* mesh_table,
+                             int n_classes, int vmax, int fmax, const unsigned char* textures, const int* tex_table, const int* class_index,
+                             const float* poses, const float* K9, int B, int H, int W, float znear, float zfar, int tex_bilinear,
+                             const float* light_pos, const float* light_int, float brightness_ratio, const float* plane_means3,
+                             float mask_thr, void* workspace, float* image, float* depth, float* mask, float* bgr, int* bbox, int* status,
+                             const int* clean_bbox, const float* K_per_sample, void* stream);
+
 /* deepim/core/tester.py:204-225 (and batch_updater_py_multi.py:233-255): light_pos[b] = 0.5*(dx,dy,dz) + (tx,-ty,-tz) of poses[b]. */
 int dim_modelnet_light_position(const float* poses, float dx, float dy, float dz, float* light_pos, int B, void* stream);
 /* mask[b] = rectangle [y0:y1, x0:x1] (end-exclusive) of bbox[b]  (data_pair.py:103-114, UPDATE_MASK box_rendered) */
 /* bbox_of_mask (optional, (B,4)): bbox {min_x,max_x,min_y,max_y} of the rectangle just written, in dim_mask_bbox's convention --
  * the next iteration's ZoomMask then needs no scan of mask_observed. */
 int dim_box_mask(const int* bbox, float* mask, int B, int H, int W, int* bbox_of_mask, void* stream);
+
+/* ---------------------------------------------------------------- scene composition (csrc/scene.hip)
+ * N scenes of S layers (1 <= S <= 16); one layer = one single-object render as dim_raster_render* returns it:
+ *   layer_bgr (N*S,H,W,3), layer_depth (N*S,1,H,W) metres, layer_label (N*S) int32 (device); a label <= 0 marks an unused slot, which
+ *   is ignored (its planes are not read).
+ * Per pixel the winner is the used layer with the smallest depth that is finite and > 0; equal depths go to the lower slot; no
+ * candidate = background.  Outputs (each may be NULL): scene_bgr (N,H,W,3) background 0, scene_depth (N,1,H,W), scene_label
+ * (N,1,H,W) = the winner's label as a float, background 0; vis_mask (N*S,1,H,W) = 1 where that layer wins; counts (N*S,2) int32 =
+ * {full, visible} pixel counts, full = the layer's own depth > 0; vis_bbox (N*S,4) int32 = box of vis_mask in dim_mask_bbox's
+ * convention (empty = {W,-1,H,-1}); status (N*S int32): DIM_STATUS_LAYER_HIDDEN is OR-ed in for a used layer that wins no pixel.
+ * workspace: dim_scene_compose_workspace_bytes(), 4-byte aligned, needed for counts / vis_bbox / status; its contents before the
+ * call do not matter, and neither do the outputs'.  16-byte accesses when W % 4 == 0 and every plane is 16-byte aligned.
+ * Deviation: toolkit/LM6d_occ_dsm_1_gen_observed_light.py:219-236 paints whole objects in order of their mean depth (an order it
+ * also scrambles by indexing a reversed array); the per-pixel depth test here is what that approximates -- the same result whenever
+ * objects do not interpenetrate and the order is the intended one. */
+long dim_scene_compose_workspace_bytes(int N, int S, int H, int W);
+int dim_scene_compose(const float* layer_bgr, const float* layer_depth, const int* layer_label, int N, int S, int H, int W,
+                      void* workspace, float* scene_bgr, float* scene_depth, float* scene_label, float* vis_mask, int* counts,
+                      int* vis_bbox, int* status, void* stream);
 
 /* ---------------------------------------------------------------- convolution stack (NHWC, f32 MFMA)
  * weights: pack once from the reference layout (Cout,Cin,KH,KW).  Cin must be 8 or a multiple of 32,

@@ -364,7 +364,10 @@ struct LitArgs {
 
 // Colour of pixel (x, y) of sample b whose z-buffer key names face f (the heavy path: exact edge functions again, perspective-correct
 // barycentrics, three dependent gathers, texel fetch, optional Lambert term).  Returns false for a face id outside the mesh.
-template <bool LIT, bool PERK>
+// LM (only with LIT): the LINEMOD light rule, render_py_light.py:74 / render_py_light_multi_program.py:76 -- the light colour scales the
+// diffuse term only, colour = texel * ((1 - ratio) + ratio * brightness * intensity); LM = false is the ModelNet rule,
+// colour = texel * ((1 - ratio) + ratio * brightness) * intensity.  Normal, light vector, clamp and quantisation are shared.
+template <bool LIT, bool PERK, bool LM = false>
 __device__ __forceinline__ bool shade_pixel(const LitArgs& lit, const float* __restrict__ K_per_sample, const float* __restrict__ uvs,
                                             const int* __restrict__ faces,
                                             const int* __restrict__ mesh_table, const unsigned char* __restrict__ tex,
@@ -467,11 +470,20 @@ __device__ __forceinline__ bool shade_pixel(const LitArgs& lit, const float* __r
     float ln = __fsqrt_rn(__fmaf_rn(Ng[2], Ng[2], __fmaf_rn(Ng[1], Ng[1], __fmul_rn(Ng[0], Ng[0]))));
     float br = __fdiv_rn(dotv, __fmul_rn(ls, ln));
     br = fmaxf(fminf(br, 1.0f), 0.0f);
-    float kk = __fmaf_rn(lit.ratio, br, __fsub_rn(1.0f, lit.ratio));
     const float* I = lit.light_int + 3 * b;
-    float c0 = __fmul_rn(__fdiv_rn(r, 255.0f), __fmul_rn(kk, I[0]));
-    float c1 = __fmul_rn(__fdiv_rn(g, 255.0f), __fmul_rn(kk, I[1]));
-    float c2 = __fmul_rn(__fdiv_rn(bl, 255.0f), __fmul_rn(kk, I[2]));
+    float c0, c1, c2;
+    if (LM) {
+      // ratio * (brightness * I) + (1 - ratio), fused like the ModelNet branch: with I = 1 or ratio = 1 the two give the same bits
+      const float amb = __fsub_rn(1.0f, lit.ratio);
+      c0 = __fmul_rn(__fdiv_rn(r, 255.0f), __fmaf_rn(lit.ratio, __fmul_rn(br, I[0]), amb));
+      c1 = __fmul_rn(__fdiv_rn(g, 255.0f), __fmaf_rn(lit.ratio, __fmul_rn(br, I[1]), amb));
+      c2 = __fmul_rn(__fdiv_rn(bl, 255.0f), __fmaf_rn(lit.ratio, __fmul_rn(br, I[2]), amb));
+    } else {
+      float kk = __fmaf_rn(lit.ratio, br, __fsub_rn(1.0f, lit.ratio));
+      c0 = __fmul_rn(__fdiv_rn(r, 255.0f), __fmul_rn(kk, I[0]));
+      c1 = __fmul_rn(__fdiv_rn(g, 255.0f), __fmul_rn(kk, I[1]));
+      c2 = __fmul_rn(__fdiv_rn(bl, 255.0f), __fmul_rn(kk, I[2]));
+    }
     // 8-bit framebuffer: clamp to [0,1], round to nearest
     r = floorf(__fmaf_rn(fminf(fmaxf(c0, 0.f), 1.f), 255.0f, 0.5f));
     g = floorf(__fmaf_rn(fminf(fmaxf(c1, 0.f), 1.f), 255.0f, 0.5f));
@@ -612,7 +624,7 @@ __device__ __forceinline__ void raster_bbox_reduce(const int4* __restrict__ wave
 //   * the first B blocks fold the wave extents of the stream pass into bbox[b] (was a launch of its own);
 //   * EVERY listed key is reset to "clear" by the thread that consumed it, so the z-buffer is clear again when the render ends and the
 //     next one needs no clear pass (ResolveHdr).
-template <bool LIT, bool SHADE, bool PERK>
+template <bool LIT, bool SHADE, bool PERK, bool LM = false>
 __device__ __forceinline__ void raster_resolve_shade_body(const unsigned bdim, const LitArgs& lit, const float* __restrict__ K_per_sample,
                                                           const float* __restrict__ uvs, const int* __restrict__ faces,
                                                           const int* __restrict__ mesh_table, const unsigned char* __restrict__ tex,
@@ -637,8 +649,8 @@ __device__ __forceinline__ void raster_resolve_shade_body(const unsigned bdim, c
     const float z = __uint_as_float((unsigned)(key >> 32));
     float r = 0.f, g = 0.f, bl = 0.f;
     // (class_index was range-checked by the vertex pass: a sample with a bad class has no covered pixel)
-    const bool ok = shade_pixel<LIT, PERK>(lit, K_per_sample, uvs, faces, mesh_table, tex, tex_table, class_index[b], scr + (long)b * vmax * 3,
-                                           b, x, y, (unsigned)(key & 0xFFFFFFFFu), z, tex_bilinear, r, g, bl);
+    const bool ok = shade_pixel<LIT, PERK, LM>(lit, K_per_sample, uvs, faces, mesh_table, tex, tex_table, class_index[b], scr + (long)b * vmax * 3,
+                                               b, x, y, (unsigned)(key & 0xFFFFFFFFu), z, tex_bilinear, r, g, bl);
     if (!ok && status) atomicOr(status + b, DIM_STATUS_BAD_FACE);  // a corrupt key: the pixel keeps z but is coloured black, loudly
     if (image) {
       float* im = image + (long)b * 3 * plane + pix;
@@ -680,8 +692,22 @@ __global__ __launch_bounds__(256) void raster_resolve_shade_k_kernel(LitArgs lit
                                              waves_per_sample, B, bbox);
 }
 
+// the LINEMOD light rule (dim_raster_render_lit_lm): kernels of its own, so that the instantiations above stay what they were
+template <bool PERK>
+__global__ __launch_bounds__(256) void raster_resolve_shade_lm_kernel(LitArgs lit, const float* __restrict__ K_per_sample,
+                             const float* __restrict__ uvs, const int* __restrict__ faces, const int* __restrict__ mesh_table,
+                             const unsigned char* __restrict__ tex, const int* __restrict__ tex_table, const int* __restrict__ class_index,
+                             const float* __restrict__ scr, unsigned long long* __restrict__ zbuf, int vmax, int H, int W, int tex_bilinear,
+                             float pm0, float pm1, float pm2, float* __restrict__ image, float* __restrict__ bgr, int* __restrict__ status,
+                             const ResolveHdr* __restrict__ hdr, const unsigned* __restrict__ list, const int4* __restrict__ wave_ext,
+                             int waves_per_sample, int B, int* __restrict__ bbox) {
+  raster_resolve_shade_body<true, true, PERK, true>(blockDim.x, lit, K_per_sample, uvs, faces, mesh_table, tex, tex_table, class_index, scr,
+                                                    zbuf, vmax, H, W, tex_bilinear, pm0, pm1, pm2, image, bgr, status, hdr, list, wave_ext,
+                                                    waves_per_sample, B, bbox);
+}
+
 // One-pass resolve (one thread per pixel): kept for image widths that are not a multiple of 4.
-template <bool LIT, bool PERK>
+template <bool LIT, bool PERK, bool LM = false>
 __device__ __forceinline__ void raster_resolve_body(const unsigned bdim, const LitArgs& lit, const float* __restrict__ K_per_sample,
                                                     const float* __restrict__ uvs, const int* __restrict__ faces,
                                                     const int* __restrict__ mesh_table, const unsigned char* __restrict__ tex,
@@ -701,8 +727,8 @@ __device__ __forceinline__ void raster_resolve_body(const unsigned bdim, const L
     if (key != 0xFFFFFFFFFFFFFFFFull) {
       zbuf[(long)b * plane + (long)y * W + x] = 0xFFFFFFFFFFFFFFFFull;   // leave the z-buffer clear (ResolveHdr)
       z = __uint_as_float((unsigned)(key >> 32));
-      const bool ok = shade_pixel<LIT, PERK>(lit, K_per_sample, uvs, faces, mesh_table, tex, tex_table, class_index[b],
-                                             scr + (long)b * vmax * 3, b, x, y, (unsigned)(key & 0xFFFFFFFFu), z, tex_bilinear, r, g, bl);
+      const bool ok = shade_pixel<LIT, PERK, LM>(lit, K_per_sample, uvs, faces, mesh_table, tex, tex_table, class_index[b],
+                                                 scr + (long)b * vmax * 3, b, x, y, (unsigned)(key & 0xFFFFFFFFu), z, tex_bilinear, r, g, bl);
       if (!ok && status) atomicOr(status + b, DIM_STATUS_BAD_FACE);
     }
     const long o = (long)y * W + x;
@@ -758,6 +784,17 @@ __global__ __launch_bounds__(256) void raster_resolve_k_kernel(LitArgs lit, cons
                              float* __restrict__ mask, float* __restrict__ bgr, int* __restrict__ bbox, int* __restrict__ status) {
   raster_resolve_body<LIT, true>(blockDim.x, lit, K_per_sample, uvs, faces, mesh_table, tex, tex_table, class_index, scr, zbuf, vmax, H, W,
                                  tex_bilinear, pm0, pm1, pm2, mask_thr, image, depth, mask, bgr, bbox, status);
+}
+
+template <bool PERK>
+__global__ __launch_bounds__(256) void raster_resolve_lm_kernel(LitArgs lit, const float* __restrict__ K_per_sample,
+                             const float* __restrict__ uvs, const int* __restrict__ faces, const int* __restrict__ mesh_table,
+                             const unsigned char* __restrict__ tex, const int* __restrict__ tex_table, const int* __restrict__ class_index,
+                             const float* __restrict__ scr, unsigned long long* __restrict__ zbuf, int vmax, int H, int W, int tex_bilinear,
+                             float pm0, float pm1, float pm2, float mask_thr, float* __restrict__ image, float* __restrict__ depth,
+                             float* __restrict__ mask, float* __restrict__ bgr, int* __restrict__ bbox, int* __restrict__ status) {
+  raster_resolve_body<true, PERK, true>(blockDim.x, lit, K_per_sample, uvs, faces, mesh_table, tex, tex_table, class_index, scr, zbuf, vmax,
+                                        H, W, tex_bilinear, pm0, pm1, pm2, mask_thr, image, depth, mask, bgr, bbox, status);
 }
 
 // mask[b] = filled rectangle [y0:y1, x0:x1] (END-EXCLUSIVE: lib/pair_matching/data_pair.py:103-114)
@@ -817,7 +854,7 @@ static int raster_render_impl(const float* verts, const float* normals, const fl
                               const int* class_index, const float* poses, const float* K9, int B, int H, int W, float znear, float zfar,
                               int tex_bilinear, const float* light_pos, const float* light_int, float ratio, const float* plane_means3,
                               float mask_thr, void* workspace, float* image, float* depth, float* mask, float* bgr, int* bbox, int* status,
-                              const int* clean_bbox, const float* K_per_sample, void* stream) {
+                              const int* clean_bbox, const float* K_per_sample, void* stream, bool lm = false) {
   if (B == 0) return DIM_OK;  // empty batch: nothing to do, pointers may be NULL
   DIM_REQUIRE(verts && uvs && faces && mesh_table && textures && tex_table && class_index && poses && K9 && workspace, "null pointer");
   DIM_REQUIRE(vmax > 0 && fmax > 0 && H > 0 && W > 0 && n_classes > 0, "bad sizes");
@@ -865,7 +902,16 @@ static int raster_render_impl(const float* verts, const float* normals, const fl
                        mask_thr, image, depth, mask, bgr, wave_ext, wps, hdr, list, clean_bbox);
     int grid = (int)(nkeys / 256 < 2048 ? (nkeys + 255) / 256 : 2048);
     if (grid < B) grid = B;
-    if (!(image || bgr))
+    if (lm && (image || bgr)) {   // the LINEMOD light rule (the caller has checked normals and lights)
+      if (Kps)
+        hipLaunchKernelGGL((raster_resolve_shade_lm_kernel<true>), dim3(grid), dim3(256), 0, st, lit, Kps, uvs, faces, mesh_table, textures,
+                           tex_table, class_index, scr, zbuf, vmax, H, W, tex_bilinear, p0, p1, p2, image, bgr, status, hdr, list, wave_ext,
+                           wps, B, bbox);
+      else
+        hipLaunchKernelGGL((raster_resolve_shade_lm_kernel<false>), dim3(grid), dim3(256), 0, st, lit, Kps, uvs, faces, mesh_table, textures,
+                           tex_table, class_index, scr, zbuf, vmax, H, W, tex_bilinear, p0, p1, p2, image, bgr, status, hdr, list, wave_ext,
+                           wps, B, bbox);
+    } else if (!(image || bgr))
       hipLaunchKernelGGL((raster_resolve_shade_kernel<false, false>), dim3(grid), dim3(256), 0, st, lit, uvs, faces, mesh_table, textures,
                          tex_table, class_index, scr, zbuf, vmax, H, W, tex_bilinear, p0, p1, p2, image, bgr, status, hdr, list, wave_ext,
                          wps, B, bbox);
@@ -885,6 +931,15 @@ static int raster_render_impl(const float* verts, const float* normals, const fl
       hipLaunchKernelGGL((raster_resolve_shade_kernel<false, true>), dim3(grid), dim3(256), 0, st, lit, uvs, faces, mesh_table, textures,
                          tex_table, class_index, scr, zbuf, vmax, H, W, tex_bilinear, p0, p1, p2, image, bgr, status, hdr, list, wave_ext,
                          wps, B, bbox);
+  } else if (lm) {
+    if (Kps)
+      hipLaunchKernelGGL(raster_resolve_lm_kernel<true>, dim3(ceil_div(W, 256), H, B), dim3(256), 0, st, lit, Kps, uvs, faces, mesh_table,
+                         textures, tex_table, class_index, scr, zbuf, vmax, H, W, tex_bilinear, p0, p1, p2, mask_thr, image, depth, mask, bgr,
+                         bbox, status);
+    else
+      hipLaunchKernelGGL(raster_resolve_lm_kernel<false>, dim3(ceil_div(W, 256), H, B), dim3(256), 0, st, lit, Kps, uvs, faces, mesh_table,
+                         textures, tex_table, class_index, scr, zbuf, vmax, H, W, tex_bilinear, p0, p1, p2, mask_thr, image, depth, mask, bgr,
+                         bbox, status);
   } else if (Kps) {
     if (normals)
       hipLaunchKernelGGL(raster_resolve_k_kernel<true>, dim3(ceil_div(W, 256), H, B), dim3(256), 0, st, lit, Kps, uvs, faces, mesh_table,
@@ -958,6 +1013,21 @@ int dim_raster_render_k(const float* verts, const float* normals, const float* u
   return raster_render_impl(verts, normals, uvs, faces, mesh_table, n_classes, vmax, fmax, textures, tex_table, class_index, poses, K9, B,
                             H, W, znear, zfar, tex_bilinear, light_pos, light_int, brightness_ratio, plane_means3, mask_thr, workspace,
                             image, depth, mask, bgr, bbox, status, clean_bbox, K_per_sample, stream);
+}
+
+// dim_raster_render_k under the LINEMOD light rule (Render_Py_Light / Render_Py_Light_MultiProgram): always lit
+int dim_raster_render_lit_lm(const float* verts, const float* normals, const float* uvs, const int* faces, const int* mesh_table,
+                             int n_classes, int vmax, int fmax, const unsigned char* textures, const int* tex_table, const int* class_index,
+                             const float* poses, const float* K9, int B, int H, int W, float znear, float zfar, int tex_bilinear,
+                             const float* light_pos, const float* light_int, float brightness_ratio, const float* plane_means3,
+                             float mask_thr, void* workspace, float* image, float* depth, float* mask, float* bgr, int* bbox, int* status,
+                             const int* clean_bbox, const float* K_per_sample, void* stream) {
+  if (B == 0) return DIM_OK;
+  DIM_REQUIRE(normals && light_pos && light_int, "null pointer");
+  DIM_REQUIRE(!clean_bbox || clean_bbox != bbox, "clean_bbox and bbox must be different arrays (the stream pass reads one while the last pass writes the other)");
+  return raster_render_impl(verts, normals, uvs, faces, mesh_table, n_classes, vmax, fmax, textures, tex_table, class_index, poses, K9, B,
+                            H, W, znear, zfar, tex_bilinear, light_pos, light_int, brightness_ratio, plane_means3, mask_thr, workspace,
+                            image, depth, mask, bgr, bbox, status, clean_bbox, K_per_sample, stream, true);
 }
 
 int dim_modelnet_light_position(const float* poses, float dx, float dy, float dz, float* light_pos, int B, void* stream) {

@@ -58,7 +58,10 @@ def _defaults():
         root_path="./data", test_image_set="val_ape", model_dir="", model_file="./data/ModelNet/render_v1/models.txt",
         pose_file="./data/ModelNet/render_v1/poses.txt", DEPTH_FACTOR=1000, NORMALIZE_FLOW=1.0, NORMALIZE_3D_POINT=0.1,
         INTRINSIC_MATRIX=np.array([[572.4114, 0, 325.2611], [0, 573.57043, 242.04899], [0, 0, 1]]), ZNEAR=0.25, ZFAR=6.0,
-        class_name_file="", class_name=[], trans_means=np.array([0.0, 0.0, 0.0]), trans_stds=np.array([1.0, 1.0, 1.0]))
+        class_name_file="", class_name=[], trans_means=np.array([0.0, 0.0, 0.0]), trans_stds=np.array([1.0, 1.0, 1.0]),
+        # synthetic training pairs (lib/dataset/synthetic_pairs.py): occluding objects per pair, the share of the target that may be
+        # hidden (toolkit/LM6d_occ_dsm_3_remove_low_visible.py), LINEMOD light model (toolkit/LM6d_occ_dsm_1_gen_observed_light.py)
+        SYN_OCC_OBJECTS=0, SYN_OCC_MAX_RATE=0.85, SYN_LIGHT=False)
     c.TRAIN = edict(
         optimizer="sgd", warmup=False, warmup_lr=0, warmup_step=0, begin_epoch=0, end_epoch=0, lr=0.0001, lr_step="4, 6",
         momentum=0.975, wd=0.0005, model_prefix="deepim", RESUME=False, SHUFFLE=True, BATCH_PAIRS=1, FLOW_WEIGHT_TYPE="all",

@@ -24,6 +24,17 @@ class SyntheticPairs(object):
         self.render_machine = Render_Py(None, self.classes, self.K, zNear=config.dataset.ZNEAR, zFar=config.dataset.ZFAR, device=device,
                                         meshes=self.models)
         self.batch_pairs, self.device, self.seed = int(batch_pairs), device, seed
+        # occluded / lit training scenes (dataset.SYN_OCC_OBJECTS, SYN_OCC_MAX_RATE, SYN_LIGHT); all off = the batches of before
+        self.occluders = int(config.dataset.get("SYN_OCC_OBJECTS", 0) or 0)
+        self.occ_max_rate = float(config.dataset.get("SYN_OCC_MAX_RATE", 0.85))
+        self.lit = bool(config.dataset.get("SYN_LIGHT", False))
+        self.light_machine = None
+        if self.lit:
+            from lib.render_hip.render_py_light_multi_program import Render_Py_Light_MultiProgram
+
+            self.light_machine = Render_Py_Light_MultiProgram(self.classes, None, self.K, zNear=config.dataset.ZNEAR, zFar=config.dataset.ZFAR,
+                                                              brightness_ratios=syn.LM_BRIGHTNESS_RATIOS, device=device,
+                                                              meshes=[(v, None, t, f, tex) for v, t, f, tex in self.models])
         n_batches = int(num_pairs) // self.batch_pairs  # whole batches only
         lo, hi = (even_shard_range if equal_shards else shard_range)(n_batches, rank, world)
         if equal_shards and hi == lo:
@@ -65,4 +76,6 @@ class SyntheticPairs(object):
             i = self.batch_ids[int(j)]
             yield syn.build_device_train_batch(self.render_machine, self.batch_pairs, seed=self.seed + 1000 * (i + 1), models=self.models,
                                                n_classes=len(self.classes), pixel_means=self.config.network.PIXEL_MEANS,
-                                               npts=int(self.config.train_iter.NUM_3D_SAMPLE), device=self.device)
+                                               npts=int(self.config.train_iter.NUM_3D_SAMPLE), device=self.device,
+                                               occluders=self.occluders, lit=self.lit, occ_max_rate=self.occ_max_rate,
+                                               light_machine=self.light_machine)

@@ -525,6 +525,49 @@ def raster_render_k(rm, class_index, poses, K_per_sample, workspace, light_posit
         opt(K_per_sample), current_stream()))
 
 
+def raster_render_lit_lm(rm, class_index, poses, K_per_sample, workspace, light_position, light_intensity, brightness_ratio,
+                         plane_means=None, mask_thr=0.2, image=None, depth=None, mask=None, bgr=None, bbox=None, status=None,
+                         clean_bbox=None):
+    """dim_raster_render_lit_lm: raster_render_k under the LINEMOD light rule (the light colour scales the diffuse term only); `rm`
+    must have normals, and both light tensors (B,3) f32 CUDA are required."""
+    B = poses.shape[0]
+    keep, k9 = host_f32(rm.K, 9)
+    pm = host_f32(plane_means, 3) if plane_means is not None else (None, None)
+    opt = lambda t, dt=f32: dptr(t, dt) if t is not None else None  # noqa: E731
+    check(lib().dim_raster_render_lit_lm(
+        dptr(rm.verts), dptr(rm.normals), dptr(rm.uvs), dptr(rm.faces), dptr(rm.mesh_table), int(rm.mesh_table.shape[0]), rm.vmax, rm.fmax,
+        dptr(rm.textures), dptr(rm.tex_table), dptr(class_index, i32), dptr(poses, f32), k9, B, rm.height, rm.width, float(rm.zNear),
+        float(rm.zFar), int(rm.tex_bilinear), dptr(light_position, f32), dptr(light_intensity, f32), float(brightness_ratio), pm[1],
+        float(mask_thr), workspace.data_ptr(), dptr(image), dptr(depth), dptr(mask), dptr(bgr), opt(bbox, i32), opt(status, i32),
+        opt(clean_bbox, i32), opt(K_per_sample), current_stream()))
+
+
+STATUS_LAYER_HIDDEN = 256   # DIM_STATUS_LAYER_HIDDEN: dim_scene_compose, a used layer won no pixel
+
+
+def scene_compose_workspace(N, S, H, W, device):
+    """the partial-row workspace of scene_compose (needed for counts / vis_bbox / status); allocate before a graph capture"""
+    n = lib().dim_scene_compose_workspace_bytes(N, S, H, W)
+    return torch.empty(((n + 3) // 4,), dtype=i32, device=device)
+
+
+def scene_compose(layer_bgr, layer_depth, layer_label, S, scene_bgr=None, scene_depth=None, scene_label=None, vis_mask=None, counts=None,
+                  vis_bbox=None, status=None, workspace=None):
+    """dim_scene_compose: N scenes of S layers.  layer_bgr (N*S,H,W,3) f32 or None, layer_depth (N*S,1,H,W) f32, layer_label (N*S,)
+    int32 (<= 0: unused slot).  Every output is written only when its tensor is given: scene_bgr (N,H,W,3), scene_depth / scene_label
+    (N,1,H,W), vis_mask (N*S,1,H,W), counts (N*S,2) int32 {full, visible}, vis_bbox (N*S,4) int32, status (N*S,) int32 (OR-ed into).
+    workspace: scene_compose_workspace(...); allocated here when counts / vis_bbox / status are asked for and none is given."""
+    NS, _, H, W = layer_depth.shape
+    if S < 1 or NS % S:
+        raise ValueError("{} layers cannot be split into scenes of S = {}".format(NS, S))
+    N = NS // S
+    if workspace is None and (counts is not None or vis_bbox is not None or status is not None):
+        workspace = scene_compose_workspace(N, S, H, W, layer_depth.device)
+    check(lib().dim_scene_compose(dptr(layer_bgr, f32), dptr(layer_depth, f32), dptr(layer_label, i32), N, S, H, W, dptr(workspace, i32),
+                                  dptr(scene_bgr, f32), dptr(scene_depth, f32), dptr(scene_label, f32), dptr(vis_mask, f32),
+                                  dptr(counts, i32), dptr(vis_bbox, i32), dptr(status, i32), current_stream()))
+
+
 def box_mask(bbox, mask, bbox_of_mask=None):
     """mask <- filled rectangle of bbox (end-exclusive); bbox_of_mask (B,4) int32: optional bbox of that rectangle"""
     B, _, H, W = mask.shape

@@ -194,9 +194,12 @@ def build_device_batch(render_machine, B, seed, n_classes=1, pixel_means=PIXEL_M
     return out
 
 
-def build_device_train_batch(render_machine, B, seed, models, n_classes=1, pixel_means=PIXEL_MEANS, npts=3000, device="cuda:0", noise=None):
+def build_device_train_batch(render_machine, B, seed, models, n_classes=1, pixel_means=PIXEL_MEANS, npts=3000, device="cuda:0", noise=None,
+                             occluders=0, lit=False, occ_max_rate=0.85, light_machine=None, distractors=None):
     """build_device_batch + the training blobs/labels (reference names, deepim/core/loader.py:164-193): mask_gt_observed, tgt_pose,
-    depth_gt_observed, rot/trans labels, flow/flow_weights (depth->flow kernel), point clouds."""
+    depth_gt_observed, rot/trans labels, flow/flow_weights (depth->flow kernel), point clouds.
+    occluders = k > 0 and / or lit: the observed side becomes an occluded and / or lit scene (build_device_scene_batch, which
+    documents the remaining arguments); with both at their defaults nothing else is launched or allocated."""
     import torch
 
     from lib.hip import ops
@@ -227,4 +230,144 @@ def build_device_train_batch(render_machine, B, seed, models, n_classes=1, pixel
     b.update(mask_gt_observed=mask_gt, tgt_pose=gt.clone(), depth_gt_observed=depth_gt, rot=rot, trans=trans, flow=flow,
              flow_weights=valid.repeat(1, 2, 1, 1).contiguous(), point_cloud_model=torch.from_numpy(np.concatenate(pm)).to(d),
              point_cloud_weights=torch.ones((B, 3, npts), device=d), point_cloud_observed=torch.from_numpy(np.concatenate(po)).to(d))
+    if int(occluders) > 0 or lit:
+        b.update(build_device_scene_batch(render_machine, b, seed, models, occluders=int(occluders), lit=bool(lit), n_classes=n_classes,
+                                          pixel_means=pixel_means, device=device, occ_max_rate=occ_max_rate, light_machine=light_machine,
+                                          distractors=distractors))
     return b
+
+
+# toolkit/LM6d_occ_dsm_1_gen_observed_light.py:98, :130-156
+LM_BRIGHTNESS_RATIOS = [0.2, 0.25, 0.3, 0.35, 0.4]
+LM_LIGHT_DIRS = [[1, 0, 1], [1, 1, 1], [0, 1, 1], [-1, 1, 1], [-1, 0, 1], [0, 0, 1]]
+LM_LIGHT_COLORS = [[0, 0, 1], [0, 1, 0], [0, 1, 1], [1, 0, 0], [1, 0, 1], [1, 1, 0], [1, 1, 1]]
+
+
+def lm_light_draw(seed, idx, pose_0, n_ratios=len(LM_BRIGHTNESS_RATIOS)):
+    """The light of one "deep synthetic" LINEMOD scene (toolkit/LM6d_occ_dsm_1_gen_observed_light.py:130-162, :187-192).
+    -> light_position (3,) f64 in GL camera coordinates, light_intensity (3,) f64, brightness ratio index.
+      position  = LM_LIGHT_DIRS[idx % 6] * 0.5 + (tx, -ty, -tz) of pose_0, the scene's first pose (3x4)
+      intensity = LM_LIGHT_COLORS[c] * U(0.8, 1.2)^3
+    Draws, in this order, from np.random.default_rng(seed) (the reference draws from the global numpy / random state):
+      1. intensity factors  rng.uniform(0.8, 1.2, size=3)
+      2. colour row         c = rng.integers(0, 7)
+      3. ratio index        rng.integers(0, n_ratios)"""
+    rng = np.random.default_rng(seed)
+    factors = rng.uniform(0.8, 1.2, size=3)
+    c = int(rng.integers(0, len(LM_LIGHT_COLORS)))
+    k = int(rng.integers(0, n_ratios))
+    pose_0 = np.asarray(pose_0, dtype=np.float64)
+    lp = np.array(LM_LIGHT_DIRS[idx % 6], dtype=np.float64) * 0.5
+    lp[0] += pose_0[0, 3]
+    lp[1] -= pose_0[1, 3]
+    lp[2] -= pose_0[2, 3]
+    return lp, np.array(LM_LIGHT_COLORS[c], dtype=np.float64) * factors, k
+
+
+def target_box(verts, pose, K=LINEMOD_K, W=640, H=480):
+    """(x0, x1, y0, y1) of the projected model vertices, clipped to the image (host side: no device round trip)"""
+    P = np.asarray(verts, np.float64) @ np.asarray(pose[:, :3], np.float64).T + np.asarray(pose[:, 3], np.float64)
+    u = K[0, 0] * P[:, 0] / P[:, 2] + K[0, 2]
+    v = K[1, 1] * P[:, 1] / P[:, 2] + K[1, 2]
+    return (float(np.clip(u.min(), 0, W - 1)), float(np.clip(u.max(), 0, W - 1)), float(np.clip(v.min(), 0, H - 1)),
+            float(np.clip(v.max(), 0, H - 1)))
+
+
+def sample_distractors(seed, cls, gt, models, k, n_classes=1, K=LINEMOD_K, W=640, H=480, z_min=0.4):
+    """k occluding objects per pair -> classes (B,k) int32, poses (B,k,3,4) f32.  Draws from np.random.default_rng(seed), per pair
+    and distractor in order: class (another one than the target's: rng.integers(0, n_classes - 1), skipping the target's; the same
+    class when there is only one), rotation (random_rotation: 4 normals), depth z = z_target + U(-0.3, 0.3) (not below z_min), projected
+    centre u ~ U(x0, x1), v ~ U(y0, y1) inside the target's box (target_box)."""
+    rng = np.random.default_rng(seed)
+    B = len(cls)
+    dc = np.zeros((B, k), np.int32)
+    dp = np.zeros((B, k, 3, 4), np.float32)
+    for b in range(B):
+        x0, x1, y0, y1 = target_box(models[int(cls[b])][0], gt[b], K, W, H)
+        for j in range(k):
+            if n_classes > 1:
+                c = int(rng.integers(0, n_classes - 1))
+                c += int(c >= int(cls[b]))
+            else:
+                c = int(cls[b])
+            R = random_rotation(rng)
+            z = max(float(gt[b][2, 3]) + rng.uniform(-0.3, 0.3), z_min)
+            u, v = rng.uniform(x0, x1), rng.uniform(y0, y1)
+            t = np.array([(u - K[0, 2]) * z / K[0, 0], (v - K[1, 2]) * z / K[1, 1], z])
+            dc[b, j] = c
+            dp[b, j] = np.concatenate([R, t[:, None]], axis=1).astype(np.float32)
+    return dc, dp
+
+
+def build_device_scene_batch(render_machine, batch, seed, models, occluders=0, lit=False, n_classes=1, pixel_means=PIXEL_MEANS,
+                             device="cuda:0", occ_max_rate=0.85, light_machine=None, distractors=None):
+    """The observed side of a training batch as an occluded, lit multi-object scene, composed on the device (stands in for
+    toolkit/LM6d_occ_dsm_1_gen_observed_light.py and LM6d_occ_dsm_3_remove_low_visible.py).  `batch`: what build_device_train_batch
+    built for the same seed (class_index, pose_gt, depth_gt_observed, mask_gt_observed).  Per pair the target is layer 0 at the
+    ground-truth pose and `occluders` distractors (sample_distractors, seed + 29; or `distractors` = (classes (B,k), poses
+    (B,k,3,4)) host arrays) are layers 1..k; all B*(k+1) layers are rendered in one render_batch -- by `light_machine` (a
+    Render_Py_Light_MultiProgram over the same meshes) under lm_light_draw((seed, b), b, target pose) when lit; the brightness ratio
+    of the batch is pair 0's draw, being one kernel argument -- and composed by dim_scene_compose.
+    -> the blobs to replace, with the reference's meaning:
+       image_observed    the scene over the seeded noise background of build_device_batch
+       mask_gt_observed  the target's visible mask (the reference: label == mask_idx)
+       depth_observed    the scene depth           (depth_gt_observed stays the target's own unoccluded render)
+    plus scene_label (B,1,H,W), occ_counts (B,2) int32 {full, visible} of the target and occ_kept (B,) bool.
+    A pair whose target has visible < (1 - occ_max_rate) * full keeps its unoccluded image, mask and depth; the choice is made on
+    the device from the counts (no host round trip)."""
+    import torch
+
+    from lib.hip import ops
+
+    d = torch.device(device)
+    k = int(occluders)
+    S = k + 1
+    rm = light_machine if lit else render_machine
+    if lit and light_machine is None:
+        raise ValueError("lit scenes need light_machine (lib.render_hip.render_py_light_multi_program.Render_Py_Light_MultiProgram)")
+    H, W = rm.height, rm.width
+    B = batch["pose_gt"].shape[0]
+    cls = batch["class_index"].cpu().numpy()
+    gt = batch["pose_gt"].cpu().numpy()
+    if k > 0:
+        dc, dp = distractors if distractors is not None else sample_distractors(seed + 29, cls, gt, models, k, n_classes, rm.K, W, H)
+        lc = np.concatenate([cls.reshape(B, 1), np.asarray(dc, np.int32).reshape(B, k)], axis=1)
+        lp = np.concatenate([gt.reshape(B, 1, 3, 4), np.asarray(dp, np.float32).reshape(B, k, 3, 4)], axis=1)
+    else:
+        lc, lp = cls.reshape(B, 1), gt.reshape(B, 1, 3, 4)
+    cls_l = torch.from_numpy(np.ascontiguousarray(lc.reshape(B * S).astype(np.int32))).to(d)
+    pose_l = torch.from_numpy(np.ascontiguousarray(lp.reshape(B * S, 3, 4).astype(np.float32))).to(d)
+    layer_bgr = torch.empty((B * S, H, W, 3), device=d)
+    layer_depth = torch.empty((B * S, 1, H, W), device=d)
+    if lit:
+        draws = [lm_light_draw((seed, b), b, gt[b], len(rm.brightness_ratios)) for b in range(B)]
+        pos = np.repeat(np.stack([x[0] for x in draws]), S, axis=0).astype(np.float32)
+        inten = np.repeat(np.stack([x[1] for x in draws]), S, axis=0).astype(np.float32)
+        rm.render_batch(cls_l, pose_l, torch.from_numpy(pos).to(d), torch.from_numpy(inten).to(d), brightness_k=draws[0][2], bgr=layer_bgr,
+                        depth=layer_depth)
+    else:
+        rm.render_batch(cls_l, pose_l, bgr=layer_bgr, depth=layer_depth)
+    scene_bgr = torch.empty((B, H, W, 3), device=d)
+    scene_depth = torch.empty((B, 1, H, W), device=d)
+    scene_label = torch.empty((B, 1, H, W), device=d)
+    vis = torch.empty((B * S, 1, H, W), device=d)
+    counts = torch.empty((B * S, 2), dtype=torch.int32, device=d)
+    ops.scene_compose(layer_bgr, layer_depth, cls_l + 1, S, scene_bgr=scene_bgr, scene_depth=scene_depth, scene_label=scene_label,
+                      vis_mask=vis, counts=counts)
+    cnt = counts.view(B, S, 2)[:, 0].contiguous()
+    kept = ~(cnt[:, 1].double() < (1.0 - float(occ_max_rate)) * cnt[:, 0].double())
+    sel = kept.view(B, 1, 1, 1)
+    pm = torch.from_numpy(plane_means(pixel_means)).to(d).view(1, 3, 1, 1)
+    g = torch.Generator(device=d)
+    g.manual_seed(seed)   # the background of build_device_batch, bit for bit
+    noise = torch.randint(0, 256, (B, 3, H, W), generator=g, device=d).float() - pm
+    layer0_bgr = layer_bgr.view(B, S, H, W, 3)[:, 0]
+    layer0_depth = layer_depth.view(B, S, 1, H, W)[:, 0]
+    to_blob = lambda bgr: bgr.permute(0, 3, 1, 2).flip(1) - pm  # noqa: E731  (plane c = bgr[..., 2 - c] - plane mean c)
+    occluded = torch.where(scene_depth > 0, to_blob(scene_bgr), noise)
+    alone = torch.where(layer0_depth > 0, to_blob(layer0_bgr), noise)
+    return {"image_observed": torch.where(sel, occluded, alone).contiguous(),
+            "mask_gt_observed": torch.where(sel, vis.view(B, S, 1, H, W)[:, 0], batch["mask_gt_observed"]).contiguous(),
+            "depth_observed": torch.where(sel, scene_depth, layer0_depth).contiguous(),
+            "scene_label": torch.where(sel, scene_label, (layer0_depth > 0).float() * (cls_l.view(B, S)[:, :1] + 1).float().view(B, 1, 1, 1)),
+            "occ_counts": cnt, "occ_kept": kept}
