@@ -19,10 +19,11 @@
 // Maximum and minimum are exact in any order, so the result does not depend on how the points are dealt to lanes and workgroups; a NaN
 // wins every maximum and every minimum as in numpy (np.max, np.argmin: the first NaN), ties go to the smaller index.  Squared
 // distances are reduced and the square root is taken of the result only (monotone and correctly rounded: the same bits).
-// Products and sums are plain operators (the Makefile's -ffp-contract=off keeps them un-fused) in pose_err_kernel's order:
-// ((R0 x + R1 y) + R2 z) + t, the projection K (R p + t) row by row and two divisions.  No atomics, nothing allocates or synchronises:
-// the entry is graph-capturable, and the workspace needs no initialisation (only what this call wrote is read).
+// Transforms and projections are pose_err_kernel's, from pose_geom.h (see there for the order of operations).  No atomics, nothing
+// allocates or synchronises: the entry is graph-capturable, and the workspace needs no initialisation (only what this call wrote is
+// read).
 #include "common.h"
+#include "pose_geom.h"
 
 namespace dim {
 
@@ -32,30 +33,6 @@ constexpr int kBopQPL = 2;                           // points per lane: two ind
 constexpr int kBopTile = kBopThreads * kBopQPL;      // points per workgroup pass
 constexpr int kBopBlocks = 16;                       // workgroups per (t, b): the host does not know the class sizes
 constexpr int kBopChunk = 64;                        // symmetries composed into LDS at a time
-
-struct BopK {
-  double k[9];
-};
-
-template <typename PT>
-__device__ __forceinline__ void bop_load_pose(const PT* __restrict__ p, double* o) {
-#pragma unroll
-  for (int k = 0; k < 12; ++k) o[k] = (double)p[k];
-}
-
-__device__ __forceinline__ void bop_transform(const double* P, double x, double y, double z, double& ox, double& oy, double& oz) {
-  ox = ((P[0] * x + P[1] * y) + P[2] * z) + P[3];
-  oy = ((P[4] * x + P[5] * y) + P[6] * z) + P[7];
-  oz = ((P[8] * x + P[9] * y) + P[10] * z) + P[11];
-}
-
-__device__ __forceinline__ void bop_project(const BopK& K, double x, double y, double z, double& u, double& v) {
-  const double a = (K.k[0] * x + K.k[1] * y) + K.k[2] * z;
-  const double b = (K.k[3] * x + K.k[4] * y) + K.k[5] * z;
-  const double c = (K.k[6] * x + K.k[7] * y) + K.k[8] * z;
-  u = a / c;
-  v = b / c;
-}
 
 // np.max of two: a NaN on either side stays
 __device__ __forceinline__ double bop_nanmax(double a, double b) { return (b > a || b != b) ? b : a; }
@@ -67,22 +44,12 @@ struct BopClass {
 // class of pair b -> its points and its symmetries; 0: fine, 1: NaN row, 2: NaN row and DIM_STATUS_BAD_CLASS
 __device__ __forceinline__ int bop_class(const int* __restrict__ table_off, const int* __restrict__ sym_off, int n_classes, int max_sym,
                                          int cls, BopClass& c) {
-  c.off = c.n = c.soff = c.ns = 0;
-  if (cls < 0 || cls >= n_classes) return 2;
-  c.off = table_off[cls];
-  c.n = table_off[cls + 1] - c.off;
+  c.soff = c.ns = 0;
+  if (!class_points(table_off, n_classes, cls, c.off, c.n)) return 2;
   c.soff = sym_off[cls];
   c.ns = sym_off[cls + 1] - c.soff;
   if (c.off < 0 || c.n <= 0 || c.soff < 0 || c.ns <= 0 || c.ns > max_sym) return 1;
   return 0;
-}
-
-__device__ __forceinline__ BopK bop_camera(const BopK& K, const double* __restrict__ K_per_sample, int b) {
-  if (!K_per_sample) return K;
-  BopK o;
-#pragma unroll
-  for (int k = 0; k < 9; ++k) o.k[k] = K_per_sample[9L * b + k];
-  return o;
 }
 
 template <typename PT>
@@ -90,7 +57,7 @@ __global__ __launch_bounds__(kBopThreads) void bop_err_kernel(const double* __re
                                                               const double* __restrict__ sym, const int* __restrict__ sym_off,
                                                               int n_classes, const int* __restrict__ class_index,
                                                               const PT* __restrict__ poses_est, const double* __restrict__ pose_gt,
-                                                              BopK K_all, const double* __restrict__ K_per_sample, int B, int max_sym,
+                                                              CamK K_all, const double* __restrict__ K_per_sample, int B, int max_sym,
                                                               double* __restrict__ partial) {
   __shared__ double M[kBopChunk][12];
   __shared__ double red[kBopChunk][2][kBopWaves];
@@ -100,9 +67,9 @@ __global__ __launch_bounds__(kBopThreads) void bop_err_kernel(const double* __re
   if (bop_class(table_off, sym_off, n_classes, max_sym, class_index[b], c) != 0) return;
   const int ntiles = (c.n + kBopTile - 1) / kBopTile;
   if ((int)blockIdx.x >= ntiles) return;   // workgroup-uniform, like the return above: the barriers below are reached by all or none
-  const BopK K = bop_camera(K_all, K_per_sample, b);
+  const CamK K = cam_k_pick(K_all, K_per_sample, b);
   double Pe[12];
-  bop_load_pose(poses_est + 12L * ((long)t * B + b), Pe);
+  load_pose(poses_est + 12L * ((long)t * B + b), Pe);
   const double* pts = points + 3L * c.off;
   const double* Pg = pose_gt + 12L * b;
   const double* S_cls = sym + 12L * c.soff;
@@ -118,8 +85,8 @@ __global__ __launch_bounds__(kBopThreads) void bop_err_kernel(const double* __re
       x[q] = pts[3L * i];
       y[q] = pts[3L * i + 1];
       z[q] = pts[3L * i + 2];
-      bop_transform(Pe, x[q], y[q], z[q], ex[q], ey[q], ez[q]);
-      bop_project(K, ex[q], ey[q], ez[q], ue[q], ve[q]);
+      transform(Pe, x[q], y[q], z[q], ex[q], ey[q], ez[q]);
+      project(K, ex[q], ey[q], ez[q], ue[q], ve[q]);
     }
     for (int s0 = 0; s0 < c.ns; s0 += kBopChunk) {
       const int m = min(kBopChunk, c.ns - s0);
@@ -142,8 +109,8 @@ __global__ __launch_bounds__(kBopThreads) void bop_err_kernel(const double* __re
 #pragma unroll
         for (int q = 0; q < kBopQPL; ++q) {
           double gx, gy, gz, ug, vg;
-          bop_transform(Ms, x[q], y[q], z[q], gx, gy, gz);
-          bop_project(K, gx, gy, gz, ug, vg);
+          transform(Ms, x[q], y[q], z[q], gx, gy, gz);
+          project(K, gx, gy, gz, ug, vg);
           const double dx = ex[q] - gx, dy = ey[q] - gy, dz = ez[q] - gz, du = ue[q] - ug, dv = ve[q] - vg;
           d3 = bop_nanmax(d3, (dx * dx + dy * dy) + dz * dz);
           d2 = bop_nanmax(d2, du * du + dv * dv);
@@ -259,7 +226,7 @@ extern "C" int dim_bop_errors(const double* points, const int* table_off, const 
   DIM_REQUIRE((poses_est != nullptr) != (poses_est_f64 != nullptr), "bop_errors: exactly one of poses_est / poses_est_f64");
   DIM_REQUIRE(points && table_off && sym && sym_off && class_index && pose_gt && K9_f64 && workspace && errors, "bop_errors: null pointer");
   DIM_REQUIRE(((uintptr_t)workspace % 8) == 0, "bop_errors: workspace must be 8-byte aligned");
-  BopK K;
+  CamK K;
   for (int k = 0; k < 9; ++k) K.k[k] = K9_f64[k];
   double* partial = (double*)workspace;
   const dim3 grid(kBopBlocks, B, T), fin(B, T);

@@ -7,29 +7,20 @@
 // (dropped outside [-0.5, W - 0.5] x [-0.5, H - 0.5]).  Gauss-Newton on T = [R | t] from the identity: m = R p + t,
 // r = (fx m_x/m_z + cx - u, fy m_y/m_z + cy - v), weights 1 in the first `warm` iterations (at the identity the residual is the
 // flow itself), then Huber (huber_px) under a hard gate (max_px); Jacobian in the left twist (omega, v), dm = omega x m + v.
-//   flow_pnp_accumulate_kernel  grid (kPnpBlocks, B): four pixels per lane (16-byte loads where the rows allow them), float64 per
-//                               point and per lane, summed across lanes and (in the solve kernel) workgroups in a fixed order:
-//                               no atomics, a replay is bit-identical
-//   flow_pnp_solve_kernel       one workgroup per pair: sums the partials, Cholesky in float64, T <- [Rodrigues(omega) | v] T,
-//                               stats / status, and after the last iteration pose_out = T pose_src and se3_q = [quat(R), t]
+//   flow_pnp_accumulate_kernel  grid (kGnBlocks, B): four pixels per lane (16-byte loads where the rows allow them), float64 per
+//                               point and per lane, summed across lanes (block_sum.h) and, in the solve kernel, workgroups in a
+//                               fixed order: no atomics, a replay is bit-identical
+//   gn_solve_kernel             (twist_solve.h) one workgroup per pair: sums the partials, Cholesky in float64,
+//                               T <- [Rodrigues(omega) | v] T, stats / status, and after the last iteration pose_out = T pose_src
+//                               and se3_q = [quat(R), t]
 // Two launches per iteration; nothing allocates or synchronises, so the stage is graph-capturable.
 // Float64 per point, not float32: the stage is bound by its 2 x iters dependent launches, not by arithmetic (a pair has 5k-80k
 // points), and the gate decision e > max_px then agrees with the restatement's, so the inlier counts are equal, not close.
+#include "block_sum.h"
 #include "common.h"
 #include "twist_solve.h"
 
 namespace dim {
-
-constexpr int kPnpBlocks = 16;   // workgroups per pair: 4096 lanes x 4 pixels over the bbox
-constexpr int kPnpTerms = 29;    // 21 upper-triangle entries of sum w J^T J, 6 of sum w J^T r, count of w > 0, sum e^2 over them
-constexpr int kPnpSlot = 32;     // doubles per partial (padded)
-constexpr int kPnpState = 16;    // doubles per pair: R (9), t (3), updated (1), pad
-constexpr int kPnpMinPoints = 64;
-constexpr int kPnpRow = 8 * 33;  // LDS doubles per term in the cross-lane sum
-
-struct PnpCam {
-  float fx, fy, cx, cy;
-};
 
 typedef float v4f __attribute__((ext_vector_type(4)));
 
@@ -37,33 +28,25 @@ typedef float v4f __attribute__((ext_vector_type(4)));
 template <bool VEC>
 __global__ __launch_bounds__(256) void flow_pnp_accumulate_kernel(const float* __restrict__ depth_r, const float* __restrict__ flow,
                                                                   const float* __restrict__ valid, const int* __restrict__ bbox,
-                                                                  PnpCam k9, const float* __restrict__ K_per_sample, int H, int W,
+                                                                  PinholeCam k9, const float* __restrict__ K_per_sample, int H, int W,
                                                                   int comp_x, int it, int warm, float huber_px, float max_px,
                                                                   const double* __restrict__ state, double* __restrict__ partial) {
   const int b = blockIdx.y, tid = threadIdx.x;
-  PnpCam c = k9;
-  if (K_per_sample) {
-    const float* k = K_per_sample + 9 * b;
-    c = PnpCam{k[0], k[4], k[2], k[5]};
-  }
-  const bool cam_ok = c.fx > 0.f && c.fy > 0.f && isfinite(c.fx) && isfinite(c.fy) && isfinite(c.cx) && isfinite(c.cy);
+  const PinholeCam c = cam_pick(K_per_sample, k9, b);
   const double fx = c.fx, fy = c.fy, cx = c.cx, cy = c.cy;
   double R[9] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0}, t[3] = {0.0, 0.0, 0.0};
   if (it > 0) {
-    const double* s = state + (long)b * kPnpState;
+    const double* s = state + (long)b * kGnState;
 #pragma unroll
     for (int k = 0; k < 9; ++k) R[k] = s[k];
 #pragma unroll
     for (int k = 0; k < 3; ++k) t[k] = s[9 + k];
   }
-  int x0 = 0, x1 = W - 1, y0 = 0, y1 = H - 1;
-  if (bbox) {
-    x0 = max(bbox[4 * b + 0], 0); x1 = min(bbox[4 * b + 1], W - 1);
-    y0 = max(bbox[4 * b + 2], 0); y1 = min(bbox[4 * b + 3], H - 1);
-  }
+  const PixelBox box = clamp_bbox(bbox, b, H, W);
+  const int x0 = box.x0, x1 = box.x1, y0 = box.y0, y1 = box.y1;
   const int xq0 = x0 & ~3;                       // the quads are aligned to 4 pixels in the row
   const int nq = ((x1 | 3) + 1 - xq0) >> 2;      // quads per row
-  const int n = (cam_ok && x1 >= x0 && y1 >= y0) ? nq * (y1 - y0 + 1) : 0;
+  const int n = (cam_ok(c) && x1 >= x0 && y1 >= y0) ? nq * (y1 - y0 + 1) : 0;
   const long plane = (long)H * W;
   const float* dr = depth_r + (long)b * plane;
   const float* fxp = flow + ((long)b * 2 + comp_x) * plane;         // the x component: plane 1 in (dy, dx) order
@@ -72,10 +55,10 @@ __global__ __launch_bounds__(256) void flow_pnp_accumulate_kernel(const float* _
   const bool gated = it >= warm;
   const double hub = huber_px, gate = max_px;
   const double u_hi = (double)W - 0.5, v_hi = (double)H - 0.5;
-  double acc[kPnpTerms];
+  double acc[kGnTerms];
 #pragma unroll
-  for (int k = 0; k < kPnpTerms; ++k) acc[k] = 0.0;
-  for (int i = blockIdx.x * blockDim.x + tid; i < n; i += kPnpBlocks * blockDim.x) {
+  for (int k = 0; k < kGnTerms; ++k) acc[k] = 0.0;
+  for (int i = blockIdx.x * blockDim.x + tid; i < n; i += kGnBlocks * blockDim.x) {
     const int qy = i / nq;
     const int y = y0 + qy, x4 = xq0 + 4 * (i - qy * nq);
     const long o = (long)y * W + x4;
@@ -138,104 +121,8 @@ __global__ __launch_bounds__(256) void flow_pnp_accumulate_kernel(const float* _
       acc[28] += e2;
     }
   }
-  // the cross-lane sum of icp.hip: 8 chunks of 32 lanes per term (a chunk row padded to 33 doubles against bank conflicts), then the
-  // 8 chunk sums, always in the same order
-  __shared__ double red[kPnpTerms * kPnpRow];
-  __shared__ double red8[kPnpTerms * 8];
-  const int slot = (tid >> 5) * 33 + (tid & 31);
-#pragma unroll
-  for (int k = 0; k < kPnpTerms; ++k) red[k * kPnpRow + slot] = acc[k];
-  __syncthreads();
-  if (tid < kPnpTerms * 8) {
-    const double* r = red + (tid >> 3) * kPnpRow + (tid & 7) * 33;
-    double s = 0.0;
-    for (int j = 0; j < 32; ++j) s += r[j];
-    red8[tid] = s;
-  }
-  __syncthreads();
-  if (tid < kPnpTerms) {
-    double s = red8[8 * tid];
-    for (int w = 1; w < 8; ++w) s += red8[8 * tid + w];
-    partial[((long)b * kPnpBlocks + blockIdx.x) * kPnpSlot + tid] = s;
-  }
-}
-
-__global__ __launch_bounds__(64) void flow_pnp_solve_kernel(const double* __restrict__ partial, double* __restrict__ state, int it,
-                                                           int iters, const float* __restrict__ pose_src, float* __restrict__ pose_out,
-                                                           float* __restrict__ se3_q, float* __restrict__ stats,
-                                                           int* __restrict__ status) {
-  const int b = blockIdx.x, tid = threadIdx.x;
-  __shared__ double s[kPnpTerms];
-  if (tid < kPnpTerms) {
-    double v = 0.0;
-    for (int k = 0; k < kPnpBlocks; ++k) v += partial[((long)b * kPnpBlocks + k) * kPnpSlot + tid];
-    s[tid] = v;
-  }
-  __syncthreads();
-  if (tid != 0) return;
-  double* st = state + (long)b * kPnpState;
-  double R[9] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0}, t[3] = {0.0, 0.0, 0.0}, updated = 0.0;
-  if (it > 0) {
-    for (int k = 0; k < 9; ++k) R[k] = st[k];
-    for (int k = 0; k < 3; ++k) t[k] = st[9 + k];
-    updated = st[12];
-  }
-  const double N = s[27], ee = s[28];
-  if (stats) {
-    stats[((long)b * iters + it) * 2 + 0] = (float)N;
-    stats[((long)b * iters + it) * 2 + 1] = N > 0.0 ? (float)sqrt(ee / N) : 0.f;
-  }
-  bool ok = N >= (double)kPnpMinPoints;
-  double xi[6];
-  if (ok) {
-    double A[36], g[6];
-    int k = 0;
-    for (int a = 0; a < 6; ++a)
-      for (int e = a; e < 6; ++e, ++k) A[6 * a + e] = A[6 * e + a] = s[k];
-    const double damp = 1e-9 * (A[0] + A[7] + A[14] + A[21] + A[28] + A[35]) / 6.0;
-    for (int a = 0; a < 6; ++a) {
-      A[6 * a + a] += damp;
-      g[a] = -s[21 + a];
-    }
-    ok = cholesky_solve6(A, g, xi);
-  }
-  if (ok) {
-    double Rw[9], Rn[9], tn[3];
-    twist_rodrigues(xi, Rw);
-    for (int i = 0; i < 3; ++i) {
-      for (int j = 0; j < 3; ++j) Rn[3 * i + j] = Rw[3 * i] * R[j] + Rw[3 * i + 1] * R[3 + j] + Rw[3 * i + 2] * R[6 + j];
-      tn[i] = Rw[3 * i] * t[0] + Rw[3 * i + 1] * t[1] + Rw[3 * i + 2] * t[2] + xi[3 + i];
-    }
-    for (int k = 0; k < 9; ++k) R[k] = Rn[k];
-    for (int k = 0; k < 3; ++k) t[k] = tn[k];
-    updated = 1.0;
-  } else if (status) {
-    status[b] |= DIM_STATUS_FLOW_PNP_FEW_POINTS;
-  }
-  for (int k = 0; k < 9; ++k) st[k] = R[k];
-  for (int k = 0; k < 3; ++k) st[9 + k] = t[k];
-  st[12] = updated;
-  if (it != iters - 1) return;
-  const float* T0 = pose_src + 12 * (long)b;
-  float* out = pose_out + 12 * (long)b;
-  float* sq = se3_q ? se3_q + 7 * (long)b : nullptr;
-  if (updated == 0.0) {   // never moved: the input pose, bit for bit, and the identity
-    for (int k = 0; k < 12; ++k) out[k] = T0[k];
-    if (sq)
-      for (int k = 0; k < 7; ++k) sq[k] = k == 0 ? 1.f : 0.f;
-    return;
-  }
-  for (int i = 0; i < 3; ++i) {
-    for (int j = 0; j < 3; ++j)
-      out[4 * i + j] = (float)(R[3 * i] * (double)T0[j] + R[3 * i + 1] * (double)T0[4 + j] + R[3 * i + 2] * (double)T0[8 + j]);
-    out[4 * i + 3] = (float)(R[3 * i] * (double)T0[3] + R[3 * i + 1] * (double)T0[7] + R[3 * i + 2] * (double)T0[11] + t[i]);
-  }
-  if (sq) {
-    double q[4];
-    mat2quat_d(R, q);
-    for (int k = 0; k < 4; ++k) sq[k] = (float)q[k];
-    for (int k = 0; k < 3; ++k) sq[4 + k] = (float)t[k];
-  }
+  const double total = block_sum(acc);
+  if (tid < kGnTerms) partial[((long)b * kGnBlocks + blockIdx.x) * kGnSlot + tid] = total;
 }
 
 // iters == 0: se3_q of a pair that never updated
@@ -251,8 +138,7 @@ using namespace dim;
 extern "C" long dim_flow_pnp_workspace_bytes(int B, int H, int W) {
   (void)H;
   (void)W;
-  if (B <= 0) return 0;
-  return (long)B * (kPnpState + kPnpBlocks * kPnpSlot) * (long)sizeof(double);
+  return gn_workspace_bytes(B);
 }
 
 extern "C" int dim_flow_pnp(const float* depth_rendered, const float* flow, const float* valid, const int* bbox, const float* pose_src,
@@ -270,18 +156,18 @@ extern "C" int dim_flow_pnp(const float* depth_rendered, const float* flow, cons
     if (se3_q) hipLaunchKernelGGL(flow_pnp_identity_kernel, dim3(ceil_div(7L * B, 256)), dim3(256), 0, as_stream(stream), se3_q, B);
     return dim_copy_words(pose_out, pose_src, 12L * B, stream);
   }
-  const PnpCam k9{K9[0], K9[4], K9[2], K9[5]};
+  const PinholeCam k9 = cam_of_k9(K9);
   double* state = (double*)workspace;
-  double* partial = state + (long)B * kPnpState;
+  double* partial = state + (long)B * kGnState;
   auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
   const bool vec = W % 4 == 0 && al16(depth_rendered) && al16(flow) && (!valid || al16(valid));
   const int comp_x = standard_rep ? 0 : 1;   // (dy, dx) unless standard_rep
   for (int it = 0; it < iters; ++it) {
-    hipLaunchKernelGGL(vec ? flow_pnp_accumulate_kernel<true> : flow_pnp_accumulate_kernel<false>, dim3(kPnpBlocks, B), dim3(256), 0,
+    hipLaunchKernelGGL(vec ? flow_pnp_accumulate_kernel<true> : flow_pnp_accumulate_kernel<false>, dim3(kGnBlocks, B), dim3(256), 0,
                        as_stream(stream), depth_rendered, flow, valid, bbox, k9, K_per_sample, H, W, comp_x, it, warm, huber_px, max_px,
                        (const double*)state, partial);
-    hipLaunchKernelGGL(flow_pnp_solve_kernel, dim3(B), dim3(64), 0, as_stream(stream), (const double*)partial, state, it, iters, pose_src,
-                       pose_out, se3_q, stats, status);
+    hipLaunchKernelGGL(gn_solve_kernel<DIM_STATUS_FLOW_PNP_FEW_POINTS>, dim3(B), dim3(64), 0, as_stream(stream), (const double*)partial,
+                       state, it, iters, pose_src, pose_out, se3_q, stats, status);
   }
   return check_launch("flow_pnp");
 }

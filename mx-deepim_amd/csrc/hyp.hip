@@ -9,6 +9,7 @@
 //   pose_score_finish      one lane per sample: the kScoreBlocks partials in order, the score in float64, the status bit
 //   hyp_select_kernel      one lane per pair: argmax of the finite scores (ties: smaller h), then the gathers
 // Nothing allocates or synchronises: every entry is graph-capturable.
+#include "block_sum.h"
 #include "common.h"
 
 namespace dim {
@@ -81,22 +82,6 @@ __device__ __forceinline__ void score_pixel(ScoreAcc& a, float o0, float o1, flo
     a.cnt += 1.0;
     if (fabsf(dr - dob) < tau) a.hit += 1.0;
   }
-}
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ double wave_min(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmin(v, __shfl_xor(v, o, 64));
-  return v;
-}
-__device__ __forceinline__ double wave_max(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
-  return v;
 }
 
 // VEC: W % 4 == 0 and every plane 16-byte aligned -> the bbox columns are covered by aligned float4 groups, masked at both ends

@@ -9,10 +9,12 @@
 //                     8-byte broadcasts and keeps min_j |g - e_j|^2 for its two queries (sqrt is monotone: one sqrt per query).
 //                     Lane sums -> xor butterfly -> waves in order -> one partial per workgroup (no atomics).
 //   pose_err_finish   one lane per (t, b): the kErrBlocks partials in order, the means, re / te, NaN rows and the status bit.
-// Products and sums are plain operators in numpy's order (the Makefile's -ffp-contract=off keeps them un-fused): the transforms are
-// ((R0 x + R1 y) + R2 z) + t, the projection K (R p + t) row by row, the norms sqrt of the sum of squares.
+// Transforms and projections in numpy's order of operations come from pose_geom.h (see there); the norms are sqrt of the sum of
+// squares.
 // Nothing allocates or synchronises: the entry is graph-capturable.
+#include "block_sum.h"
 #include "common.h"
+#include "pose_geom.h"
 
 namespace dim {
 
@@ -22,16 +24,6 @@ constexpr int kErrQTile = kErrThreads * kErrQPL;     // query points per workgro
 constexpr int kErrCTile = kErrThreads;               // candidates staged per LDS tile, one per lane
 constexpr int kErrBlocks = 16;                       // workgroups per (t, b): the host does not know the class sizes
 constexpr int kErrSlot = 4;                          // doubles per partial: add, arp_2d, adi, pad
-
-struct ErrK {
-  double k[9];
-};
-
-template <typename PT>
-__device__ __forceinline__ void err_load_pose(const PT* __restrict__ p, double* o) {
-#pragma unroll
-  for (int k = 0; k < 12; ++k) o[k] = (double)p[k];
-}
 
 // pose_error.re: degrees(arccos(clip((trace(R_est^T R_gt) - 1) / 2, -1, 1))); a NaN stays a NaN as np.clip keeps it
 __device__ __forceinline__ double err_rot_deg(const double* Pe, const double* Pg) {
@@ -52,33 +44,11 @@ __device__ __forceinline__ void err_flip_z180(double* P) {
   }
 }
 
-__device__ __forceinline__ void err_transform(const double* P, double x, double y, double z, double& ox, double& oy, double& oz) {
-  ox = ((P[0] * x + P[1] * y) + P[2] * z) + P[3];
-  oy = ((P[4] * x + P[5] * y) + P[6] * z) + P[7];
-  oz = ((P[8] * x + P[9] * y) + P[10] * z) + P[11];
-}
-
-__device__ __forceinline__ void err_project(const ErrK& K, double x, double y, double z, double& u, double& v) {
-  const double a = (K.k[0] * x + K.k[1] * y) + K.k[2] * z;
-  const double b = (K.k[3] * x + K.k[4] * y) + K.k[5] * z;
-  const double c = (K.k[6] * x + K.k[7] * y) + K.k[8] * z;
-  u = a / c;
-  v = b / c;
-}
-
-__device__ __forceinline__ double err_wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // class of pair b -> first point, point count and flags; false: the row is NaN (index out of range, or a table that runs backwards)
 __device__ __forceinline__ bool err_class(const int* __restrict__ table_off, const int* __restrict__ class_flags, int n_classes, int cls,
                                           int& off, int& n, int& flags) {
-  off = n = flags = 0;
-  if (cls < 0 || cls >= n_classes) return false;
-  off = table_off[cls];
-  n = table_off[cls + 1] - off;
+  flags = 0;
+  if (!class_points(table_off, n_classes, cls, off, n)) return false;
   flags = class_flags[cls];
   if (off < 0 || n < 0) n = 0;
   return true;
@@ -88,7 +58,7 @@ template <typename PT>
 __global__ __launch_bounds__(kErrThreads) void pose_err_kernel(const double* __restrict__ points, const int* __restrict__ table_off,
                                                                const int* __restrict__ class_flags, int n_classes,
                                                                const int* __restrict__ class_index, const PT* __restrict__ poses_est,
-                                                               const double* __restrict__ pose_gt, ErrK K, int B,
+                                                               const double* __restrict__ pose_gt, CamK K, int B,
                                                                double* __restrict__ partial) {
   __shared__ double cand[3][kErrCTile];
   __shared__ double red[kErrThreads / kWave][3];
@@ -99,8 +69,8 @@ __global__ __launch_bounds__(kErrThreads) void pose_err_kernel(const double* __r
   const int ntiles = valid ? (n + kErrQTile - 1) / kErrQTile : 0;
   if ((int)blockIdx.x < ntiles) {   // workgroup-uniform: the barriers below are reached by every lane or by none
     double Pe[12], Pg[12], Pf[12];
-    err_load_pose(poses_est + 12L * ((long)t * B + b), Pe);
-    err_load_pose(pose_gt + 12L * b, Pg);
+    load_pose(poses_est + 12L * ((long)t * B + b), Pe);
+    load_pose(pose_gt + 12L * b, Pg);
 #pragma unroll
     for (int k = 0; k < 12; ++k) Pf[k] = Pe[k];
     if ((flags & DIM_POSE_ERR_FLIP_Z180) && err_rot_deg(Pe, Pg) > 90.0) err_flip_z180(Pf);
@@ -115,11 +85,11 @@ __global__ __launch_bounds__(kErrThreads) void pose_err_kernel(const double* __r
         ok[q] = i < n;
         const double x = ok[q] ? pts[3L * i] : 0.0, y = ok[q] ? pts[3L * i + 1] : 0.0, z = ok[q] ? pts[3L * i + 2] : 0.0;
         double ex, ey, ez, fx, fy, fz, ue, ve, ug, vg;
-        err_transform(Pg, x, y, z, gx[q], gy[q], gz[q]);
-        err_transform(Pe, x, y, z, ex, ey, ez);
-        err_transform(Pf, x, y, z, fx, fy, fz);
-        err_project(K, fx, fy, fz, ue, ve);
-        err_project(K, gx[q], gy[q], gz[q], ug, vg);
+        transform(Pg, x, y, z, gx[q], gy[q], gz[q]);
+        transform(Pe, x, y, z, ex, ey, ez);
+        transform(Pf, x, y, z, fx, fy, fz);
+        project(K, fx, fy, fz, ue, ve);
+        project(K, gx[q], gy[q], gz[q], ug, vg);
         const double dx = ex - gx[q], dy = ey - gy[q], dz = ez - gz[q], du = ue - ug, dv = ve - vg;
         if (ok[q]) {
           s_add += sqrt((dx * dx + dy * dy) + dz * dz);
@@ -133,7 +103,7 @@ __global__ __launch_bounds__(kErrThreads) void pose_err_kernel(const double* __r
           const int j = c0 + tid;
           if (j < n) {
             double ex, ey, ez;
-            err_transform(Pe, pts[3L * j], pts[3L * j + 1], pts[3L * j + 2], ex, ey, ez);
+            transform(Pe, pts[3L * j], pts[3L * j + 1], pts[3L * j + 2], ex, ey, ez);
             cand[0][tid] = ex;
             cand[1][tid] = ey;
             cand[2][tid] = ez;
@@ -157,7 +127,7 @@ __global__ __launch_bounds__(kErrThreads) void pose_err_kernel(const double* __r
     }
   }
   // lanes: xor butterfly (the same order on every run); waves: in wave order through LDS
-  const double w_add = err_wave_sum(s_add), w_arp = err_wave_sum(s_arp), w_adi = err_wave_sum(s_adi);
+  const double w_add = wave_sum(s_add), w_arp = wave_sum(s_arp), w_adi = wave_sum(s_adi);
   const int wave = tid / kWave, lane = tid % kWave;
   if (lane == 0) {
     red[wave][0] = w_add;
@@ -195,8 +165,8 @@ __global__ __launch_bounds__(64) void pose_err_finish(const int* __restrict__ ta
     for (int k = 0; k < 3; ++k) s[k] += q[k];
   }
   double Pe[12], Pg[12];
-  err_load_pose(poses_est + 12L * i, Pe);
-  err_load_pose(pose_gt + 12L * b, Pg);
+  load_pose(poses_est + 12L * i, Pe);
+  load_pose(pose_gt + 12L * b, Pg);
   double re = err_rot_deg(Pe, Pg);
   if ((flags & DIM_POSE_ERR_FLIP_Z180) && re > 90.0) {
     err_flip_z180(Pe);   // the translation of est . RT_Z is the estimate's
@@ -226,7 +196,7 @@ extern "C" int dim_pose_errors(const double* points, const int* table_off, const
   DIM_REQUIRE((poses_est != nullptr) != (poses_est_f64 != nullptr), "pose_errors: exactly one of poses_est / poses_est_f64");
   DIM_REQUIRE(points && table_off && class_flags && class_index && pose_gt && K9_f64 && workspace && errors, "pose_errors: null pointer");
   DIM_REQUIRE(((uintptr_t)workspace % 8) == 0, "pose_errors: workspace must be 8-byte aligned");
-  ErrK K;
+  CamK K;
   for (int k = 0; k < 9; ++k) K.k[k] = K9_f64[k];
   double* partial = (double*)workspace;
   const dim3 grid(kErrBlocks, B, T), fin(ceil_div((long)T * B, 64));

@@ -1,9 +1,44 @@
 // Float64 device helpers shared by the Gauss-Newton pose stages (icp.hip, flow_pnp.hip) and the pose algebra (se3.hip): the 6x6
-// Cholesky solve of the normal equations, the Rodrigues rotation of a twist's omega, and rotation matrix -> quaternion.
+// Cholesky solve of the normal equations, the Rodrigues rotation of a twist's omega, and rotation matrix -> quaternion; and what
+// the two Gauss-Newton stages have in common: the workspace layout, the camera and box of a pair, and the solve kernel.
 #pragma once
 #include "common.h"
 
 namespace dim {
+
+// ---- layout of a Gauss-Newton stage: per iteration an accumulate kernel, grid (kGnBlocks, B), writes one partial per workgroup,
+// and gn_solve_kernel, one workgroup per pair, adds them in order.  Workspace: [state B x kGnState][partial B x kGnBlocks x kGnSlot]
+constexpr int kGnBlocks = 16;      // workgroups per pair: 4096 lanes over the bbox (a LINEMOD object covers 5k-80k pixels)
+constexpr int kGnTerms = 29;       // 21 upper-triangle entries of sum J J^T, 6 of sum J r, point count, sum of squared residuals
+constexpr int kGnSlot = 32;        // doubles per partial (padded)
+constexpr int kGnState = 16;       // doubles per pair: R (9), t (3), updated (1), pad
+constexpr int kGnMinPoints = 64;   // fewer points: no update, the stage's status bit
+
+inline long gn_workspace_bytes(int B) { return B <= 0 ? 0 : (long)B * (kGnState + kGnBlocks * kGnSlot) * (long)sizeof(double); }
+
+struct PinholeCam {
+  float fx, fy, cx, cy;
+};
+
+__host__ __device__ inline PinholeCam cam_of_k9(const float* K9) { return PinholeCam{K9[0], K9[4], K9[2], K9[5]}; }
+
+// the pair's camera: row b of K_per_sample (B, 9) when given, else the one K of the call
+__device__ __forceinline__ PinholeCam cam_pick(const float* __restrict__ K_per_sample, PinholeCam k9, int b) {
+  return K_per_sample ? cam_of_k9(K_per_sample + 9 * b) : k9;
+}
+
+__device__ __forceinline__ bool cam_ok(const PinholeCam& c) {
+  return c.fx > 0.f && c.fy > 0.f && isfinite(c.fx) && isfinite(c.fy) && isfinite(c.cx) && isfinite(c.cy);
+}
+
+// bbox row b = {min_x, max_x, min_y, max_y} clamped to the frame (no bbox: the frame); empty when x1 < x0 or y1 < y0
+struct PixelBox {
+  int x0, x1, y0, y1;
+};
+__device__ __forceinline__ PixelBox clamp_bbox(const int* __restrict__ bbox, int b, int H, int W) {
+  if (!bbox) return PixelBox{0, W - 1, 0, H - 1};
+  return PixelBox{max(bbox[4 * b + 0], 0), min(bbox[4 * b + 1], W - 1), max(bbox[4 * b + 2], 0), min(bbox[4 * b + 3], H - 1)};
+}
 
 __device__ inline void twist_rodrigues(const double* w, double* Rw) {
   const double th = sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]);
@@ -67,6 +102,89 @@ __device__ inline void mat2quat_d(const double M[9], double q[4]) {
   double n = sqrt(w * w + x * x + y * y + z * z);
   if (w < 0) n = -n;
   q[0] = w / n; q[1] = x / n; q[2] = y / n; q[3] = z / n;
+}
+
+// One Gauss-Newton step of pair b = blockIdx.x (64 lanes): sums the kGnBlocks partials in order, solves the damped normal equations
+// by Cholesky, T <- [Rodrigues(omega) | v] T, writes stats (B, iters, 2) = (points, rms residual) when given, and ORs FAIL_BIT into
+// status[b] when the step was skipped (fewer than kGnMinPoints points or a singular system).  After the last iteration
+// pose_out = T pose_in and, when se3_q is given, se3_q = [quat(R), t]; a pair that never updated gets pose_in bit for bit and the
+// identity.
+template <int FAIL_BIT>
+__global__ __launch_bounds__(64) void gn_solve_kernel(const double* __restrict__ partial, double* __restrict__ state, int it, int iters,
+                                                     const float* __restrict__ pose_in, float* __restrict__ pose_out,
+                                                     float* __restrict__ se3_q, float* __restrict__ stats, int* __restrict__ status) {
+  const int b = blockIdx.x, tid = threadIdx.x;
+  __shared__ double s[kGnTerms];
+  if (tid < kGnTerms) {
+    double v = 0.0;
+    for (int k = 0; k < kGnBlocks; ++k) v += partial[((long)b * kGnBlocks + k) * kGnSlot + tid];
+    s[tid] = v;
+  }
+  __syncthreads();
+  if (tid != 0) return;
+  double* st = state + (long)b * kGnState;
+  double R[9] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0}, t[3] = {0.0, 0.0, 0.0}, updated = 0.0;
+  if (it > 0) {
+    for (int k = 0; k < 9; ++k) R[k] = st[k];
+    for (int k = 0; k < 3; ++k) t[k] = st[9 + k];
+    updated = st[12];
+  }
+  const double N = s[27], rr = s[28];
+  if (stats) {
+    stats[((long)b * iters + it) * 2 + 0] = (float)N;
+    stats[((long)b * iters + it) * 2 + 1] = N > 0.0 ? (float)sqrt(rr / N) : 0.f;
+  }
+  bool ok = N >= (double)kGnMinPoints;
+  double xi[6];
+  if (ok) {
+    double A[36], g[6];
+    int k = 0;
+    for (int a = 0; a < 6; ++a)
+      for (int e = a; e < 6; ++e, ++k) A[6 * a + e] = A[6 * e + a] = s[k];
+    const double damp = 1e-9 * (A[0] + A[7] + A[14] + A[21] + A[28] + A[35]) / 6.0;
+    for (int a = 0; a < 6; ++a) {
+      A[6 * a + a] += damp;
+      g[a] = -s[21 + a];
+    }
+    ok = cholesky_solve6(A, g, xi);
+  }
+  if (ok) {
+    double Rw[9], Rn[9], tn[3];
+    twist_rodrigues(xi, Rw);
+    for (int i = 0; i < 3; ++i) {
+      for (int j = 0; j < 3; ++j) Rn[3 * i + j] = Rw[3 * i] * R[j] + Rw[3 * i + 1] * R[3 + j] + Rw[3 * i + 2] * R[6 + j];
+      tn[i] = Rw[3 * i] * t[0] + Rw[3 * i + 1] * t[1] + Rw[3 * i + 2] * t[2] + xi[3 + i];
+    }
+    for (int k = 0; k < 9; ++k) R[k] = Rn[k];
+    for (int k = 0; k < 3; ++k) t[k] = tn[k];
+    updated = 1.0;
+  } else if (status) {
+    status[b] |= FAIL_BIT;
+  }
+  for (int k = 0; k < 9; ++k) st[k] = R[k];
+  for (int k = 0; k < 3; ++k) st[9 + k] = t[k];
+  st[12] = updated;
+  if (it != iters - 1) return;
+  const float* T0 = pose_in + 12 * (long)b;
+  float* out = pose_out + 12 * (long)b;
+  float* sq = se3_q ? se3_q + 7 * (long)b : nullptr;
+  if (updated == 0.0) {   // never moved: the input pose, bit for bit, and the identity
+    for (int k = 0; k < 12; ++k) out[k] = T0[k];
+    if (sq)
+      for (int k = 0; k < 7; ++k) sq[k] = k == 0 ? 1.f : 0.f;
+    return;
+  }
+  for (int i = 0; i < 3; ++i) {
+    for (int j = 0; j < 3; ++j)
+      out[4 * i + j] = (float)(R[3 * i] * (double)T0[j] + R[3 * i + 1] * (double)T0[4 + j] + R[3 * i + 2] * (double)T0[8 + j]);
+    out[4 * i + 3] = (float)(R[3 * i] * (double)T0[3] + R[3 * i + 1] * (double)T0[7] + R[3 * i + 2] * (double)T0[11] + t[i]);
+  }
+  if (sq) {
+    double q[4];
+    mat2quat_d(R, q);
+    for (int k = 0; k < 4; ++k) sq[k] = (float)q[k];
+    for (int k = 0; k < 3; ++k) sq[4 + k] = (float)t[k];
+  }
 }
 
 }  // namespace dim

@@ -15,11 +15,11 @@
 //                             pixel adds nothing, and every sum keeps its order: boxes or none, the result is the same bit for bit.
 //                             V = 4: one 16-byte load per plane (W % 4 == 0 and 16-byte aligned planes), V = 1 otherwise.
 //                             One read of the three planes serves all n_tau costs; no distance is ever written to memory.
-//                             Lane sums (int32 counts, float64 costs) -> LDS, 8 chunks of 32 lanes, then the 8 chunk sums, as
-//                             icp_accumulate_kernel reduces: a fixed order, no atomics.
+//                             Lane sums (int32 counts, float64 costs) -> block_sum.h: a fixed order, no atomics.
 //   vsd_finish_kernel         one lane per (t, b): the kVsdBlocks partials in order -> counts and e per tau.
 // Plain operators in numpy's order (the Makefile's -ffp-contract=off keeps them un-fused).  Nothing allocates or synchronises:
 // the entry is graph-capturable.
+#include "block_sum.h"
 #include "common.h"
 
 namespace dim {
@@ -29,7 +29,6 @@ constexpr int kVsdBlocks = 16;                    // workgroups per (t, b)
 constexpr int kVsdCounts = 4;                     // |visib_gt|, |union|, |inter|, |D_gt drawn|
 constexpr int kVsdTerms = DIM_VSD_MAX_TAU + kVsdCounts;
 constexpr int kVsdSlot = 12;                      // doubles per partial: 8 cost sums, 4 counts (exact in float64)
-constexpr int kVsdRow = 8 * 33;                   // LDS doubles per term in the cross-lane sum
 
 struct VsdParams {
   double K[9];
@@ -128,30 +127,16 @@ __global__ __launch_bounds__(kVsdThreads) void vsd_accumulate_kernel(const float
       }
     }
   }
-  // float64 in a fixed order: 8 chunks of 32 lanes per term (a chunk row padded to 33 doubles against bank conflicts), then the 8 chunk
-  // sums.  The counts ride along as float64: a plane has fewer than 2^31 pixels, so they stay exact.
-  __shared__ double red[kVsdTerms * kVsdRow];
-  __shared__ double red8[kVsdTerms * 8];
-  const int slot = (tid >> 5) * 33 + (tid & 31);
+  // the counts ride along as float64: a plane has fewer than 2^31 pixels, so they stay exact
+  double v[kVsdTerms];
 #pragma unroll
-  for (int k = 0; k < DIM_VSD_MAX_TAU; ++k) red[k * kVsdRow + slot] = a.cost[k];
-  red[(DIM_VSD_MAX_TAU + 0) * kVsdRow + slot] = (double)a.n_gt;
-  red[(DIM_VSD_MAX_TAU + 1) * kVsdRow + slot] = (double)a.n_union;
-  red[(DIM_VSD_MAX_TAU + 2) * kVsdRow + slot] = (double)a.n_inter;
-  red[(DIM_VSD_MAX_TAU + 3) * kVsdRow + slot] = (double)a.n_drawn;
-  __syncthreads();
-  if (tid < kVsdTerms * 8) {
-    const double* r = red + (tid >> 3) * kVsdRow + (tid & 7) * 33;
-    double s = 0.0;
-    for (int j = 0; j < 32; ++j) s += r[j];
-    red8[tid] = s;
-  }
-  __syncthreads();
-  if (tid < kVsdTerms) {
-    double s = red8[8 * tid];
-    for (int w = 1; w < 8; ++w) s += red8[8 * tid + w];
-    partial[((((long)t * B + b) * kVsdBlocks) + blockIdx.x) * kVsdSlot + tid] = s;
-  }
+  for (int k = 0; k < DIM_VSD_MAX_TAU; ++k) v[k] = a.cost[k];
+  v[DIM_VSD_MAX_TAU + 0] = (double)a.n_gt;
+  v[DIM_VSD_MAX_TAU + 1] = (double)a.n_union;
+  v[DIM_VSD_MAX_TAU + 2] = (double)a.n_inter;
+  v[DIM_VSD_MAX_TAU + 3] = (double)a.n_drawn;
+  const double total = block_sum(v);
+  if (tid < kVsdTerms) partial[((((long)t * B + b) * kVsdBlocks) + blockIdx.x) * kVsdSlot + tid] = total;
 }
 
 __global__ __launch_bounds__(64) void vsd_finish_kernel(const double* __restrict__ partial, int T, int B, int n_tau,

@@ -204,11 +204,39 @@ def flow_epe_sums(flow_pred, flow_gt, visible, depth_rendered, sums=None, accumu
     return sums
 
 
+def _opt(t, dt=f32):
+    """device pointer of an optional tensor (None -> a null pointer)"""
+    return dptr(t, dt) if t is not None else None
+
+
+def _host_k9_f64(K):
+    """the host 3x3 K -> nine contiguous float64 (the caller keeps the array alive through the call)"""
+    keep = np.ascontiguousarray(np.asarray(K, dtype=np.float64).reshape(-1))
+    if keep.size != 9:
+        raise ValueError("expected a 3x3 K, got {} numbers".format(keep.size))
+    return keep
+
+
+def _kps_f64(K_per_sample, B, dev, who):
+    """K_per_sample ((B,3,3) / (B,9), host array or CUDA tensor) -> None or a contiguous (B,9) float64 tensor on dev"""
+    if K_per_sample is None:
+        return None
+    kps = torch.as_tensor(K_per_sample).to(dev, torch.float64).reshape(-1, 9).contiguous()
+    if kps.shape[0] != B:
+        raise ValueError("{2} K_per_sample must be ({0},3,3) or ({0},9), got {1}".format(B, tuple(torch.as_tensor(K_per_sample).shape), who))
+    return kps
+
+
+def _workspace_f64(nbytes, device):
+    """a float64 tensor of at least nbytes (never empty: its pointer is passed as the workspace)"""
+    return torch.empty((max(nbytes, 8) // 8,), dtype=torch.float64, device=device)
+
+
 STATUS_ICP_FEW_POINTS = 32   # DIM_STATUS_ICP_FEW_POINTS: an ICP iteration found < 64 inliers or a singular system (no update)
 
 
 def icp_workspace(B, H, W, device):
-    return torch.empty((max(lib().dim_icp_workspace_bytes(B, H, W), 8) // 8,), dtype=torch.float64, device=device)
+    return _workspace_f64(lib().dim_icp_workspace_bytes(B, H, W), device)
 
 
 def icp_refine(depth_rendered, depth_observed, pose_in, K, iters, max_dist, mask_observed=None, bbox=None, K_per_sample=None,
@@ -225,10 +253,9 @@ def icp_refine(depth_rendered, depth_observed, pose_in, K, iters, max_dist, mask
         workspace = icp_workspace(B, H, W, pose_in.device)
     kps = intrinsics_per_sample(K_per_sample, B, pose_in.device)
     keep, kp = host_f32(K, 9)
-    opt = lambda t, dt=f32: dptr(t, dt) if t is not None else None  # noqa: E731
-    check(lib().dim_icp_refine(dptr(depth_rendered, f32), dptr(depth_observed, f32), opt(mask_observed), opt(bbox, i32), dptr(pose_in, f32),
-                               kp, opt(kps), B, H, W, int(iters), float(max_dist), dptr(workspace, torch.float64), dptr(pose_out, f32),
-                               opt(stats), opt(status, i32), current_stream()))
+    check(lib().dim_icp_refine(dptr(depth_rendered, f32), dptr(depth_observed, f32), _opt(mask_observed), _opt(bbox, i32), dptr(pose_in, f32),
+                               kp, _opt(kps), B, H, W, int(iters), float(max_dist), dptr(workspace, torch.float64), dptr(pose_out, f32),
+                               _opt(stats), _opt(status, i32), current_stream()))
     return pose_out
 
 
@@ -236,7 +263,7 @@ STATUS_FLOW_PNP_FEW_POINTS = 128   # DIM_STATUS_FLOW_PNP_FEW_POINTS: a flow-PnP 
 
 
 def flow_pnp_workspace(B, H, W, device):
-    return torch.empty((max(lib().dim_flow_pnp_workspace_bytes(B, H, W), 8) // 8,), dtype=torch.float64, device=device)
+    return _workspace_f64(lib().dim_flow_pnp_workspace_bytes(B, H, W), device)
 
 
 def flow_pnp(depth_rendered, flow, pose_src, K, iters, warm=2, huber_px=2.0, max_px=8.0, standard_rep=False, valid=None, bbox=None,
@@ -255,10 +282,9 @@ def flow_pnp(depth_rendered, flow, pose_src, K, iters, warm=2, huber_px=2.0, max
         workspace = flow_pnp_workspace(B, H, W, pose_src.device)
     kps = intrinsics_per_sample(K_per_sample, B, pose_src.device)
     keep, kp = host_f32(K, 9)
-    opt = lambda t, dt=f32: dptr(t, dt) if t is not None else None  # noqa: E731
-    check(lib().dim_flow_pnp(dptr(depth_rendered, f32), dptr(flow, f32), opt(valid), opt(bbox, i32), dptr(pose_src, f32), kp, opt(kps), B, H,
+    check(lib().dim_flow_pnp(dptr(depth_rendered, f32), dptr(flow, f32), _opt(valid), _opt(bbox, i32), dptr(pose_src, f32), kp, _opt(kps), B, H,
                              W, int(bool(standard_rep)), int(iters), int(warm), float(huber_px), float(max_px),
-                             dptr(workspace, torch.float64), dptr(pose_out, f32), dptr(se3_q, f32), opt(stats), opt(status, i32),
+                             dptr(workspace, torch.float64), dptr(pose_out, f32), dptr(se3_q, f32), _opt(stats), _opt(status, i32),
                              current_stream()))
     return pose_out, se3_q
 
@@ -288,7 +314,7 @@ def hyp_broadcast(dst, src, N):
 
 
 def pose_score_workspace(B, H, W, device):
-    return torch.empty((max(lib().dim_pose_score_workspace_bytes(B, H, W), 8) // 8,), dtype=torch.float64, device=device)
+    return _workspace_f64(lib().dim_pose_score_workspace_bytes(B, H, W), device)
 
 
 def pose_score(image_observed, image_rendered, depth_rendered, mode="rgb", tau=0.02, depth_observed=None, bbox=None, score=None,
@@ -307,10 +333,9 @@ def pose_score(image_observed, image_rendered, depth_rendered, mode="rgb", tau=0
     score = score if score is not None else _new((B,), depth_rendered)
     if workspace is None:
         workspace = pose_score_workspace(B, H, W, depth_rendered.device)
-    opt = lambda t, dt=f32: dptr(t, dt) if t is not None else None  # noqa: E731
-    check(lib().dim_pose_score(dptr(image_observed, f32), dptr(image_rendered, f32), opt(depth_observed), dptr(depth_rendered, f32),
-                               opt(bbox, i32), B, H, W, HYP_SCORE_ID[mode], float(tau), dptr(workspace, torch.float64), dptr(score, f32),
-                               opt(status, i32), current_stream()))
+    check(lib().dim_pose_score(dptr(image_observed, f32), dptr(image_rendered, f32), _opt(depth_observed), dptr(depth_rendered, f32),
+                               _opt(bbox, i32), B, H, W, HYP_SCORE_ID[mode], float(tau), dptr(workspace, torch.float64), dptr(score, f32),
+                               _opt(status, i32), current_stream()))
     return score
 
 
@@ -328,10 +353,9 @@ def hyp_select(score, N, poses_iter, status_iter=None, pose_icp=None, choice=Non
         status_sel = _new((T, P), status_iter, i32)
     if pose_icp is not None and pose_icp_sel is None:
         pose_icp_sel = _new((P, 3, 4), pose_icp)
-    opt = lambda t, dt=f32: dptr(t, dt) if t is not None else None  # noqa: E731
-    check(lib().dim_hyp_select(dptr(score, f32), P, int(N), T, dptr(poses_iter, f32), opt(status_iter, i32), opt(status_load, i32), opt(pose_icp),
+    check(lib().dim_hyp_select(dptr(score, f32), P, int(N), T, dptr(poses_iter, f32), _opt(status_iter, i32), _opt(status_load, i32), _opt(pose_icp),
                                dptr(choice, i32),
-                               dptr(poses_sel, f32), opt(status_sel, i32), opt(pose_icp_sel), current_stream()))
+                               dptr(poses_sel, f32), _opt(status_sel, i32), _opt(pose_icp_sel), current_stream()))
     return choice, poses_sel, status_sel, pose_icp_sel
 
 
@@ -342,7 +366,7 @@ POSE_ERR_COLUMNS = ("re", "te", "add", "adi", "arp_2d")
 
 
 def pose_errors_workspace(T, B, max_points, device):
-    return torch.empty((max(lib().dim_pose_errors_workspace_bytes(T, B, max_points), 8) // 8,), dtype=torch.float64, device=device)
+    return _workspace_f64(lib().dim_pose_errors_workspace_bytes(T, B, max_points), device)
 
 
 def pose_errors(points, table_off, class_flags, class_index, poses_est, pose_gt, K, errors=None, status=None, workspace=None):
@@ -365,13 +389,11 @@ def pose_errors(points, table_off, class_flags, class_index, poses_est, pose_gt,
     if workspace is None:
         workspace = pose_errors_workspace(T, B, points.shape[0], poses_est.device)
     assert workspace.numel() * workspace.element_size() >= lib().dim_pose_errors_workspace_bytes(T, B, points.shape[0])
-    keep = np.ascontiguousarray(np.asarray(K, dtype=np.float64).reshape(-1))
-    if keep.size != 9:
-        raise ValueError("expected a 3x3 K, got {} numbers".format(keep.size))
+    keep = _host_k9_f64(K)
     is32 = poses_est.dtype == f32
     check(lib().dim_pose_errors(dptr(points, f64), dptr(table_off, i32), dptr(class_flags, i32), n_classes, dptr(class_index, i32),
                                 dptr(poses_est, f32) if is32 else None, None if is32 else dptr(poses_est, f64), dptr(pose_gt, f64),
-                                keep.ctypes.data, T, B, dptr(workspace), dptr(errors, f64), dptr(status, i32) if status is not None else None,
+                                keep.ctypes.data, T, B, dptr(workspace), dptr(errors, f64), _opt(status, i32),
                                 current_stream()))
     return errors
 
@@ -382,7 +404,7 @@ VSD_COUNT_COLUMNS = ("visib_gt", "union", "inter", "drawn_gt")
 
 
 def vsd_workspace(T, B, device):
-    return torch.empty((max(lib().dim_vsd_workspace_bytes(T, B), 8) // 8,), dtype=torch.float64, device=device)
+    return _workspace_f64(lib().dim_vsd_workspace_bytes(T, B), device)
 
 
 def vsd_errors(depth_obs, depth_gt, depth_est, K, delta, taus, cost_type="step", K_per_sample=None, bbox_gt=None, bbox_est=None,
@@ -416,17 +438,10 @@ def vsd_errors(depth_obs, depth_gt, depth_est, K, delta, taus, cost_type="step",
     if workspace is None:
         workspace = vsd_workspace(T, B, dev)
     assert workspace.numel() * workspace.element_size() >= lib().dim_vsd_workspace_bytes(T, B)
-    keep = np.ascontiguousarray(np.asarray(K, dtype=np.float64).reshape(-1))
-    if keep.size != 9:
-        raise ValueError("expected a 3x3 K, got {} numbers".format(keep.size))
-    kps = None
-    if K_per_sample is not None:
-        kps = torch.as_tensor(K_per_sample).to(dev, f64).reshape(-1, 9).contiguous()
-        if kps.shape[0] != B:
-            raise ValueError("vsd K_per_sample must be ({0},3,3) or ({0},9), got {1}".format(B, tuple(torch.as_tensor(K_per_sample).shape)))
-    opt = lambda t, dt: dptr(t, dt) if t is not None else None  # noqa: E731
-    check(lib().dim_vsd_errors(dptr(depth_obs, f32), dptr(depth_gt, f32), dptr(depth_est, f32), keep.ctypes.data, opt(kps, f64),
-                               opt(bbox_gt, i32), opt(bbox_est, i32), T, B, H, W, float(delta), tau.ctypes.data, int(tau.size),
+    keep = _host_k9_f64(K)
+    kps = _kps_f64(K_per_sample, B, dev, "vsd")
+    check(lib().dim_vsd_errors(dptr(depth_obs, f32), dptr(depth_gt, f32), dptr(depth_est, f32), keep.ctypes.data, _opt(kps, f64),
+                               _opt(bbox_gt, i32), _opt(bbox_est, i32), T, B, H, W, float(delta), tau.ctypes.data, int(tau.size),
                                VSD_COST_ID[cost_type], dptr(workspace), dptr(errors, f64), dptr(counts, i32), current_stream()))
     return errors, counts
 
@@ -435,7 +450,7 @@ BOP_ERR_COLUMNS = ("mssd", "mspd")
 
 
 def bop_errors_workspace(T, B, max_sym, device):
-    return torch.empty((max(lib().dim_bop_errors_workspace_bytes(T, B, max_sym), 8) // 8,), dtype=torch.float64, device=device)
+    return _workspace_f64(lib().dim_bop_errors_workspace_bytes(T, B, max_sym), device)
 
 
 def bop_errors(points, table_off, sym, sym_off, class_index, poses_est, pose_gt, K, max_sym, K_per_sample=None, errors=None,
@@ -467,19 +482,13 @@ def bop_errors(points, table_off, sym, sym_off, class_index, poses_est, pose_gt,
     if workspace is None:
         workspace = bop_errors_workspace(T, B, max_sym, dev)
     assert max_sym <= 0 or workspace.numel() * workspace.element_size() >= lib().dim_bop_errors_workspace_bytes(T, B, max_sym)
-    keep = np.ascontiguousarray(np.asarray(K, dtype=np.float64).reshape(-1))
-    if keep.size != 9:
-        raise ValueError("expected a 3x3 K, got {} numbers".format(keep.size))
-    kps = None
-    if K_per_sample is not None:
-        kps = torch.as_tensor(K_per_sample).to(dev, f64).reshape(-1, 9).contiguous()
-        if kps.shape[0] != B:
-            raise ValueError("bop K_per_sample must be ({0},3,3) or ({0},9), got {1}".format(B, tuple(torch.as_tensor(K_per_sample).shape)))
+    keep = _host_k9_f64(K)
+    kps = _kps_f64(K_per_sample, B, dev, "bop")
     is32 = poses_est.dtype == f32
     check(lib().dim_bop_errors(dptr(points, f64), dptr(table_off, i32), dptr(sym, f64), dptr(sym_off, i32), n_classes,
                                dptr(class_index, i32), dptr(poses_est, f32) if is32 else None, None if is32 else dptr(poses_est, f64),
-                               dptr(pose_gt, f64), keep.ctypes.data, dptr(kps, f64) if kps is not None else None, T, B, max_sym,
-                               dptr(workspace), dptr(errors, f64), dptr(best_sym, i32), dptr(status, i32) if status is not None else None,
+                               dptr(pose_gt, f64), keep.ctypes.data, _opt(kps, f64), T, B, max_sym,
+                               dptr(workspace), dptr(errors, f64), dptr(best_sym, i32), _opt(status, i32),
                                current_stream()))
     return errors, best_sym
 
