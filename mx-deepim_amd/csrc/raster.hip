@@ -93,7 +93,16 @@ __device__ __forceinline__ bool k_usable(const float* __restrict__ k) {
   return ok;
 }
 
-// scr[b][i] = (u, v, Zc) for vertex i of the sample's mesh
+// camera-space position of vertex p under pose P (3x4 row-major): shared by the vertex pass and the near-plane paths, bit for bit
+__device__ inline void cam_point(const float* __restrict__ P, const float* __restrict__ p, float c[3]) {
+  c[0] = __fmaf_rn(P[0], p[0], __fmaf_rn(P[1], p[1], __fmaf_rn(P[2], p[2], P[3])));
+  c[1] = __fmaf_rn(P[4], p[0], __fmaf_rn(P[5], p[1], __fmaf_rn(P[6], p[2], P[7])));
+  c[2] = __fmaf_rn(P[8], p[0], __fmaf_rn(P[9], p[1], __fmaf_rn(P[10], p[2], P[11])));
+}
+
+// scr[b][i] = (u, v, Zc) for vertex i of the sample's mesh.  The one pass whose kernels are still wrappers around a body (which is why
+// the body is handed blockDim.x): as one templated kernel like the other passes, the PERK = true instantiation came out with 15 VGPRs
+// for today's 17 ("rasteriser design"), and a pass is folded only when the registers of every instantiation stay what they are.
 template <bool PERK>
 __device__ __forceinline__ void raster_vertex_body(const unsigned bdim, const float* __restrict__ verts, const int* __restrict__ mesh_table,
                                                    const int* __restrict__ class_index, const float* __restrict__ poses, float fx, float fy,
@@ -134,15 +143,12 @@ __device__ __forceinline__ void raster_vertex_body(const unsigned bdim, const fl
   }
   const int* mt = mesh_table + 4 * cls;
   if (i >= mt[1]) return;
-  const float* p = verts + 3 * (long)(mt[0] + i);
-  const float* P = poses + 12 * b;
-  float xc = __fmaf_rn(P[0], p[0], __fmaf_rn(P[1], p[1], __fmaf_rn(P[2], p[2], P[3])));
-  float yc = __fmaf_rn(P[4], p[0], __fmaf_rn(P[5], p[1], __fmaf_rn(P[6], p[2], P[7])));
-  float zc = __fmaf_rn(P[8], p[0], __fmaf_rn(P[9], p[1], __fmaf_rn(P[10], p[2], P[11])));
+  float c[3];
+  cam_point(poses + 12 * b, verts + 3 * (long)(mt[0] + i), c);
   float* s = scr + ((long)b * vmax + i) * 3;
-  s[0] = __fmaf_rn(fx, __fdiv_rn(xc, zc), cx);
-  s[1] = __fmaf_rn(fy, __fdiv_rn(yc, zc), cy);
-  s[2] = zc;
+  s[0] = __fmaf_rn(fx, __fdiv_rn(c[0], c[2]), cx);
+  s[1] = __fmaf_rn(fy, __fdiv_rn(c[1], c[2]), cy);
+  s[2] = c[2];
 }
 
 __global__ __launch_bounds__(256) void raster_vertex_kernel(const float* __restrict__ verts, const int* __restrict__ mesh_table,
@@ -187,13 +193,6 @@ __device__ inline float interp_z(const long long E[3], float inv_area, const flo
 
 constexpr float kZClipMin = 1.0e-4f;
 constexpr float kCoordLim = 1.0e6f;
-
-// camera-space position of vertex p under pose P (3x4 row-major): the vertex pass's arithmetic, bit for bit
-__device__ inline void cam_point(const float* __restrict__ P, const float* __restrict__ p, float c[3]) {
-  c[0] = __fmaf_rn(P[0], p[0], __fmaf_rn(P[1], p[1], __fmaf_rn(P[2], p[2], P[3])));
-  c[1] = __fmaf_rn(P[4], p[0], __fmaf_rn(P[5], p[1], __fmaf_rn(P[6], p[2], P[7])));
-  c[2] = __fmaf_rn(P[8], p[0], __fmaf_rn(P[9], p[1], __fmaf_rn(P[10], p[2], P[11])));
-}
 
 // Sutherland-Hodgman against z >= zc: 0, 3 or 4 vertices in out
 __device__ inline int clip_near(const float cam[3][3], float zc, float out[4][3]) {
@@ -266,14 +265,14 @@ __device__ inline void raster_one(const int X[3], const int Y[3], const float iz
 }
 
 template <bool PERK>
-__device__ __forceinline__ void raster_tri_body(const unsigned bdim, const int* __restrict__ faces, const int* __restrict__ mesh_table,
-                                                const int* __restrict__ class_index, const float* __restrict__ scr,
-                                                const float* __restrict__ verts, const float* __restrict__ poses, float fx, float fy, float cx,
-                                                float cy, const float* __restrict__ K_per_sample, int vmax, int H, int W, float znear,
-                                                float zfar, int n_classes, unsigned long long* __restrict__ zbuf, ResolveHdr* __restrict__ hdr,
-                                                int B) {
+__global__ __launch_bounds__(256) void raster_tri_kernel(const int* __restrict__ faces, const int* __restrict__ mesh_table,
+                                                         const int* __restrict__ class_index, const float* __restrict__ scr,
+                                                         const float* __restrict__ verts, const float* __restrict__ poses, float fx,
+                                                         float fy, float cx, float cy, const float* __restrict__ K_per_sample, int vmax,
+                                                         int H, int W, float znear, float zfar, int n_classes,
+                                                         unsigned long long* __restrict__ zbuf, ResolveHdr* __restrict__ hdr, int B) {
   const int b = blockIdx.y;
-  const int f = blockIdx.x * bdim + threadIdx.x;
+  const int f = blockIdx.x * blockDim.x + threadIdx.x;
   if (b == 0 && f == 0) {   // the z-buffer was clear when this pass started; the resolve passes of this render restore that
     hdr->magic0 = kZbMagic0; hdr->magic1 = kZbMagic1; hdr->B = B; hdr->H = H; hdr->W = W; hdr->vmax = vmax;
   }
@@ -323,26 +322,6 @@ __device__ __forceinline__ void raster_tri_body(const unsigned bdim, const int* 
   raster_one(X, Y, iz, f, H, W, znear, zfar, false, zc, zb);
 }
 
-__global__ __launch_bounds__(256) void raster_tri_kernel(const int* __restrict__ faces, const int* __restrict__ mesh_table,
-                                                         const int* __restrict__ class_index, const float* __restrict__ scr,
-                                                         const float* __restrict__ verts, const float* __restrict__ poses, float fx,
-                                                         float fy, float cx, float cy, int vmax, int H, int W, float znear, float zfar,
-                                                         int n_classes, unsigned long long* __restrict__ zbuf, ResolveHdr* __restrict__ hdr,
-                                                         int B) {
-  raster_tri_body<false>(blockDim.x, faces, mesh_table, class_index, scr, verts, poses, fx, fy, cx, cy, nullptr, vmax, H, W, znear, zfar,
-                         n_classes, zbuf, hdr, B);
-}
-
-__global__ __launch_bounds__(256) void raster_tri_k_kernel(const int* __restrict__ faces, const int* __restrict__ mesh_table,
-                                                           const int* __restrict__ class_index, const float* __restrict__ scr,
-                                                           const float* __restrict__ verts, const float* __restrict__ poses,
-                                                           const float* __restrict__ K_per_sample, int vmax, int H, int W, float znear,
-                                                           float zfar, int n_classes, unsigned long long* __restrict__ zbuf,
-                                                           ResolveHdr* __restrict__ hdr, int B) {
-  raster_tri_body<true>(blockDim.x, faces, mesh_table, class_index, scr, verts, poses, 0.f, 0.f, 0.f, 0.f, K_per_sample, vmax, H, W, znear,
-                        zfar, n_classes, zbuf, hdr, B);
-}
-
 __device__ inline int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 // One thread per pixel.  Outputs (any may be null):
@@ -367,7 +346,7 @@ struct LitArgs {
 // LM (only with LIT): the LINEMOD light rule, render_py_light.py:74 / render_py_light_multi_program.py:76 -- the light colour scales the
 // diffuse term only, colour = texel * ((1 - ratio) + ratio * brightness * intensity); LM = false is the ModelNet rule,
 // colour = texel * ((1 - ratio) + ratio * brightness) * intensity.  Normal, light vector, clamp and quantisation are shared.
-template <bool LIT, bool PERK, bool LM = false>
+template <bool LIT, bool PERK, bool LM>
 __device__ __forceinline__ bool shade_pixel(const LitArgs& lit, const float* __restrict__ K_per_sample, const float* __restrict__ uvs,
                                             const int* __restrict__ faces,
                                             const int* __restrict__ mesh_table, const unsigned char* __restrict__ tex,
@@ -624,21 +603,20 @@ __device__ __forceinline__ void raster_bbox_reduce(const int4* __restrict__ wave
 //   * the first B blocks fold the wave extents of the stream pass into bbox[b] (was a launch of its own);
 //   * EVERY listed key is reset to "clear" by the thread that consumed it, so the z-buffer is clear again when the render ends and the
 //     next one needs no clear pass (ResolveHdr).
-template <bool LIT, bool SHADE, bool PERK, bool LM = false>
-__device__ __forceinline__ void raster_resolve_shade_body(const unsigned bdim, const LitArgs& lit, const float* __restrict__ K_per_sample,
-                                                          const float* __restrict__ uvs, const int* __restrict__ faces,
-                                                          const int* __restrict__ mesh_table, const unsigned char* __restrict__ tex,
-                                                          const int* __restrict__ tex_table, const int* __restrict__ class_index,
-                                                          const float* __restrict__ scr, unsigned long long* __restrict__ zbuf, int vmax,
-                                                          int H, int W, int tex_bilinear, float pm0, float pm1, float pm2,
-                                                          float* __restrict__ image, float* __restrict__ bgr, int* __restrict__ status,
-                                                          const ResolveHdr* __restrict__ hdr, const unsigned* __restrict__ list,
-                                                          const int4* __restrict__ wave_ext, int waves_per_sample, int B,
-                                                          int* __restrict__ bbox) {
+// PERK: only a shading launch reads K_per_sample (near-clipped faces); LM: the LINEMOD light rule (shade_pixel).
+template <bool LIT, bool SHADE, bool PERK, bool LM>
+__global__ __launch_bounds__(256) void raster_resolve_shade_kernel(LitArgs lit, const float* __restrict__ K_per_sample,
+                             const float* __restrict__ uvs, const int* __restrict__ faces, const int* __restrict__ mesh_table,
+                             const unsigned char* __restrict__ tex, const int* __restrict__ tex_table, const int* __restrict__ class_index,
+                             const float* __restrict__ scr, unsigned long long* __restrict__ zbuf, int vmax, int H, int W, int tex_bilinear,
+                             float pm0, float pm1, float pm2, float* __restrict__ image, float* __restrict__ bgr, int* __restrict__ status,
+                             const ResolveHdr* __restrict__ hdr, const unsigned* __restrict__ list, const int4* __restrict__ wave_ext,
+                             int waves_per_sample, int B, int* __restrict__ bbox) {
+  const unsigned nthr = blockDim.x;
   if (bbox && (int)blockIdx.x < B) raster_bbox_reduce(wave_ext, waves_per_sample, H, W, bbox, (int)blockIdx.x);
   const unsigned n = hdr->count;
   const unsigned plane = (unsigned)(H * W);
-  for (unsigned i = blockIdx.x * bdim + threadIdx.x; i < n; i += gridDim.x * bdim) {
+  for (unsigned i = blockIdx.x * nthr + threadIdx.x; i < n; i += gridDim.x * nthr) {
     const unsigned e = list[i];
     const unsigned long long key = zbuf[e];
     zbuf[e] = 0xFFFFFFFFFFFFFFFFull;
@@ -665,60 +643,17 @@ __device__ __forceinline__ void raster_resolve_shade_body(const unsigned bdim, c
   }
 }
 
-template <bool LIT, bool SHADE>
-__global__ __launch_bounds__(256) void raster_resolve_shade_kernel(LitArgs lit, const float* __restrict__ uvs,
-                             const int* __restrict__ faces, const int* __restrict__ mesh_table, const unsigned char* __restrict__ tex,
-                             const int* __restrict__ tex_table, const int* __restrict__ class_index, const float* __restrict__ scr,
-                             unsigned long long* __restrict__ zbuf, int vmax, int H, int W, int tex_bilinear, float pm0, float pm1,
-                             float pm2, float* __restrict__ image, float* __restrict__ bgr, int* __restrict__ status,
-                             const ResolveHdr* __restrict__ hdr, const unsigned* __restrict__ list, const int4* __restrict__ wave_ext,
-                             int waves_per_sample, int B, int* __restrict__ bbox) {
-  raster_resolve_shade_body<LIT, SHADE, false>(blockDim.x, lit, nullptr, uvs, faces, mesh_table, tex, tex_table, class_index, scr, zbuf,
-                                               vmax, H, W, tex_bilinear, pm0, pm1, pm2, image, bgr, status, hdr, list, wave_ext,
-                                               waves_per_sample, B, bbox);
-}
-
-// the same with per-sample intrinsics (only a shading launch reads them: near-clipped faces)
-template <bool LIT>
-__global__ __launch_bounds__(256) void raster_resolve_shade_k_kernel(LitArgs lit, const float* __restrict__ K_per_sample,
-                             const float* __restrict__ uvs, const int* __restrict__ faces, const int* __restrict__ mesh_table,
-                             const unsigned char* __restrict__ tex, const int* __restrict__ tex_table, const int* __restrict__ class_index,
-                             const float* __restrict__ scr, unsigned long long* __restrict__ zbuf, int vmax, int H, int W, int tex_bilinear,
-                             float pm0, float pm1, float pm2, float* __restrict__ image, float* __restrict__ bgr, int* __restrict__ status,
-                             const ResolveHdr* __restrict__ hdr, const unsigned* __restrict__ list, const int4* __restrict__ wave_ext,
-                             int waves_per_sample, int B, int* __restrict__ bbox) {
-  raster_resolve_shade_body<LIT, true, true>(blockDim.x, lit, K_per_sample, uvs, faces, mesh_table, tex, tex_table, class_index, scr, zbuf,
-                                             vmax, H, W, tex_bilinear, pm0, pm1, pm2, image, bgr, status, hdr, list, wave_ext,
-                                             waves_per_sample, B, bbox);
-}
-
-// the LINEMOD light rule (dim_raster_render_lit_lm): kernels of its own, so that the instantiations above stay what they were
-template <bool PERK>
-__global__ __launch_bounds__(256) void raster_resolve_shade_lm_kernel(LitArgs lit, const float* __restrict__ K_per_sample,
-                             const float* __restrict__ uvs, const int* __restrict__ faces, const int* __restrict__ mesh_table,
-                             const unsigned char* __restrict__ tex, const int* __restrict__ tex_table, const int* __restrict__ class_index,
-                             const float* __restrict__ scr, unsigned long long* __restrict__ zbuf, int vmax, int H, int W, int tex_bilinear,
-                             float pm0, float pm1, float pm2, float* __restrict__ image, float* __restrict__ bgr, int* __restrict__ status,
-                             const ResolveHdr* __restrict__ hdr, const unsigned* __restrict__ list, const int4* __restrict__ wave_ext,
-                             int waves_per_sample, int B, int* __restrict__ bbox) {
-  raster_resolve_shade_body<true, true, PERK, true>(blockDim.x, lit, K_per_sample, uvs, faces, mesh_table, tex, tex_table, class_index, scr,
-                                                    zbuf, vmax, H, W, tex_bilinear, pm0, pm1, pm2, image, bgr, status, hdr, list, wave_ext,
-                                                    waves_per_sample, B, bbox);
-}
-
 // One-pass resolve (one thread per pixel): kept for image widths that are not a multiple of 4.
-template <bool LIT, bool PERK, bool LM = false>
-__device__ __forceinline__ void raster_resolve_body(const unsigned bdim, const LitArgs& lit, const float* __restrict__ K_per_sample,
-                                                    const float* __restrict__ uvs, const int* __restrict__ faces,
-                                                    const int* __restrict__ mesh_table, const unsigned char* __restrict__ tex,
-                                                    const int* __restrict__ tex_table, const int* __restrict__ class_index,
-                                                    const float* __restrict__ scr, unsigned long long* __restrict__ zbuf, int vmax, int H,
-                                                    int W, int tex_bilinear, float pm0, float pm1, float pm2, float mask_thr,
-                                                    float* __restrict__ image, float* __restrict__ depth, float* __restrict__ mask,
-                                                    float* __restrict__ bgr, int* __restrict__ bbox, int* __restrict__ status) {
+template <bool LIT, bool PERK, bool LM>
+__global__ __launch_bounds__(256) void raster_resolve_kernel(LitArgs lit, const float* __restrict__ K_per_sample,
+                             const float* __restrict__ uvs, const int* __restrict__ faces, const int* __restrict__ mesh_table,
+                             const unsigned char* __restrict__ tex, const int* __restrict__ tex_table, const int* __restrict__ class_index,
+                             const float* __restrict__ scr, unsigned long long* __restrict__ zbuf, int vmax, int H, int W, int tex_bilinear,
+                             float pm0, float pm1, float pm2, float mask_thr, float* __restrict__ image, float* __restrict__ depth,
+                             float* __restrict__ mask, float* __restrict__ bgr, int* __restrict__ bbox, int* __restrict__ status) {
   const int b = blockIdx.z;
   const int y = blockIdx.y;
-  const int x = blockIdx.x * bdim + threadIdx.x;
+  const int x = blockIdx.x * blockDim.x + threadIdx.x;
   const long plane = (long)H * W;
   float r = 0.f, g = 0.f, bl = 0.f, z = 0.f;
   bool in_img = x < W;
@@ -752,7 +687,7 @@ __device__ __forceinline__ void raster_resolve_body(const unsigned bdim, const L
     if (ball) {
       const int lane = threadIdx.x & 63;
       if (lane == 0) {
-        int wave_x0 = blockIdx.x * bdim + (threadIdx.x & ~63);
+        int wave_x0 = blockIdx.x * blockDim.x + (threadIdx.x & ~63);
         int lo = __ffsll((long long)ball) - 1;
         int hi = 63 - __clzll((long long)ball);
         atomicMin(&bbox[4 * b + 0], wave_x0 + lo);
@@ -762,39 +697,6 @@ __device__ __forceinline__ void raster_resolve_body(const unsigned bdim, const L
       }
     }
   }
-}
-
-template <bool LIT>
-__global__ __launch_bounds__(256) void raster_resolve_kernel(LitArgs lit, const float* __restrict__ uvs, const int* __restrict__ faces,
-                             const int* __restrict__ mesh_table, const unsigned char* __restrict__ tex, const int* __restrict__ tex_table,
-                             const int* __restrict__ class_index, const float* __restrict__ scr, unsigned long long* __restrict__ zbuf,
-                             int vmax, int H, int W, int tex_bilinear, float pm0, float pm1, float pm2, float mask_thr,
-                             float* __restrict__ image, float* __restrict__ depth, float* __restrict__ mask, float* __restrict__ bgr,
-                             int* __restrict__ bbox, int* __restrict__ status) {
-  raster_resolve_body<LIT, false>(blockDim.x, lit, nullptr, uvs, faces, mesh_table, tex, tex_table, class_index, scr, zbuf, vmax, H, W,
-                                  tex_bilinear, pm0, pm1, pm2, mask_thr, image, depth, mask, bgr, bbox, status);
-}
-
-template <bool LIT>
-__global__ __launch_bounds__(256) void raster_resolve_k_kernel(LitArgs lit, const float* __restrict__ K_per_sample,
-                             const float* __restrict__ uvs, const int* __restrict__ faces, const int* __restrict__ mesh_table,
-                             const unsigned char* __restrict__ tex, const int* __restrict__ tex_table, const int* __restrict__ class_index,
-                             const float* __restrict__ scr, unsigned long long* __restrict__ zbuf, int vmax, int H, int W, int tex_bilinear,
-                             float pm0, float pm1, float pm2, float mask_thr, float* __restrict__ image, float* __restrict__ depth,
-                             float* __restrict__ mask, float* __restrict__ bgr, int* __restrict__ bbox, int* __restrict__ status) {
-  raster_resolve_body<LIT, true>(blockDim.x, lit, K_per_sample, uvs, faces, mesh_table, tex, tex_table, class_index, scr, zbuf, vmax, H, W,
-                                 tex_bilinear, pm0, pm1, pm2, mask_thr, image, depth, mask, bgr, bbox, status);
-}
-
-template <bool PERK>
-__global__ __launch_bounds__(256) void raster_resolve_lm_kernel(LitArgs lit, const float* __restrict__ K_per_sample,
-                             const float* __restrict__ uvs, const int* __restrict__ faces, const int* __restrict__ mesh_table,
-                             const unsigned char* __restrict__ tex, const int* __restrict__ tex_table, const int* __restrict__ class_index,
-                             const float* __restrict__ scr, unsigned long long* __restrict__ zbuf, int vmax, int H, int W, int tex_bilinear,
-                             float pm0, float pm1, float pm2, float mask_thr, float* __restrict__ image, float* __restrict__ depth,
-                             float* __restrict__ mask, float* __restrict__ bgr, int* __restrict__ bbox, int* __restrict__ status) {
-  raster_resolve_body<true, PERK, true>(blockDim.x, lit, K_per_sample, uvs, faces, mesh_table, tex, tex_table, class_index, scr, zbuf, vmax,
-                                        H, W, tex_bilinear, pm0, pm1, pm2, mask_thr, image, depth, mask, bgr, bbox, status);
 }
 
 // mask[b] = filled rectangle [y0:y1, x0:x1] (END-EXCLUSIVE: lib/pair_matching/data_pair.py:103-114)
@@ -875,24 +777,26 @@ static int raster_render_impl(const float* verts, const float* normals, const fl
   const bool two_pass = W % 4 == 0 && aligned16(workspace) && aligned16(image) && aligned16(depth) && aligned16(mask) && aligned16(bgr);
   DIM_REQUIRE(!clean_bbox || two_pass, "clean_bbox needs the two-pass resolve: W %% 4 == 0 and 16-byte aligned planes and workspace");
   DIM_REQUIRE((reinterpret_cast<uintptr_t>(K_per_sample) & 3) == 0, "K_per_sample must be 4-byte aligned (B,9) f32");
-  const float* Kps = K_per_sample;   // NULL: every sample uses K9 (the uniform kernels, unchanged)
+  const float* Kps = K_per_sample;   // NULL: every sample uses K9 (the PERK = false instantiations)
   // No clear pass and no init launch (round 4): the z-buffer is clear when a render ends (the pass that consumes a key resets it) and
   // the header in front of it says so; a header that does not match this call makes the vertex pass clear the z-buffer first.  (A
   // clear by hipMemsetAsync was never an option: inside a captured hipGraph the memset node was seen overlapping the resolve pass.)
   const int wide = (int)(aligned16(workspace) && nkeys % 2 == 0);
-  if (Kps) {
+  // Which instantiation of a pass runs: PERK = a K_per_sample was given; LIT = the mesh has normals; LM = the LINEMOD light rule, which
+  // wins whenever colour is asked for (its entry point has checked normals and lights, so LM implies LIT); a two-pass render with no
+  // colour output takes SHADE = false with every other flag off.  Only the combinations below are instantiated.
+  const bool perk = Kps != nullptr, lit_on = normals != nullptr, colour = image || bgr;
+  const float fx = K9[0], fy = K9[4], cx = K9[2], cy = K9[5];
+  if (perk)   // (the vertex pass keeps its two signatures: DESIGN.md, "rasteriser design")
     hipLaunchKernelGGL(raster_vertex_k_kernel, dim3(ceil_div(vmax, 256), B), dim3(256), 0, st, verts, mesh_table, class_index, poses, Kps,
                        vmax, n_classes, status, scr, hdr, zbuf, B, H, W, bbox, wide);
-    hipLaunchKernelGGL(raster_tri_k_kernel, dim3(ceil_div(fmax, 256), B), dim3(256), 0, st, faces, mesh_table, class_index, scr, verts,
-                       poses, Kps, vmax, H, W, znear, zfar, n_classes, zbuf, hdr, B);
-  } else {
-    hipLaunchKernelGGL(raster_vertex_kernel, dim3(ceil_div(vmax, 256), B), dim3(256), 0, st, verts, mesh_table, class_index, poses,
-                       K9[0], K9[4], K9[2], K9[5], vmax, n_classes, status, scr, hdr, zbuf, B, H, W, bbox, wide);
-    hipLaunchKernelGGL(raster_tri_kernel, dim3(ceil_div(fmax, 256), B), dim3(256), 0, st, faces, mesh_table, class_index, scr, verts, poses,
-                       K9[0], K9[4], K9[2], K9[5], vmax, H, W, znear, zfar, n_classes, zbuf, hdr, B);
-  }
+  else
+    hipLaunchKernelGGL(raster_vertex_kernel, dim3(ceil_div(vmax, 256), B), dim3(256), 0, st, verts, mesh_table, class_index, poses, fx, fy,
+                       cx, cy, vmax, n_classes, status, scr, hdr, zbuf, B, H, W, bbox, wide);
+  hipLaunchKernelGGL(perk ? raster_tri_kernel<true> : raster_tri_kernel<false>, dim3(ceil_div(fmax, 256), B), dim3(256), 0, st, faces,
+                     mesh_table, class_index, scr, verts, poses, fx, fy, cx, cy, Kps, vmax, H, W, znear, zfar, n_classes, zbuf, hdr, B);
   float p0 = plane_means3 ? plane_means3[0] : 0.f, p1 = plane_means3 ? plane_means3[1] : 0.f, p2 = plane_means3 ? plane_means3[2] : 0.f;
-  LitArgs lit = {verts, normals, poses, light_pos, light_int, ratio, K9[0], K9[4], K9[2], K9[5], fmaxf(znear, kZClipMin)};
+  LitArgs lit = {verts, normals, poses, light_pos, light_int, ratio, fx, fy, cx, cy, fmaxf(znear, kZClipMin)};
   if (two_pass) {
     // pass 1 streams the z-buffer once and finishes depth / mask / background (only inside the caller's dirty box, if it names one) and
     // lists the covered pixels; pass 2 folds the bbox, colours the listed pixels on full waves and resets their keys
@@ -902,62 +806,21 @@ static int raster_render_impl(const float* verts, const float* normals, const fl
                        mask_thr, image, depth, mask, bgr, wave_ext, wps, hdr, list, clean_bbox);
     int grid = (int)(nkeys / 256 < 2048 ? (nkeys + 255) / 256 : 2048);
     if (grid < B) grid = B;
-    if (lm && (image || bgr)) {   // the LINEMOD light rule (the caller has checked normals and lights)
-      if (Kps)
-        hipLaunchKernelGGL((raster_resolve_shade_lm_kernel<true>), dim3(grid), dim3(256), 0, st, lit, Kps, uvs, faces, mesh_table, textures,
-                           tex_table, class_index, scr, zbuf, vmax, H, W, tex_bilinear, p0, p1, p2, image, bgr, status, hdr, list, wave_ext,
-                           wps, B, bbox);
-      else
-        hipLaunchKernelGGL((raster_resolve_shade_lm_kernel<false>), dim3(grid), dim3(256), 0, st, lit, Kps, uvs, faces, mesh_table, textures,
-                           tex_table, class_index, scr, zbuf, vmax, H, W, tex_bilinear, p0, p1, p2, image, bgr, status, hdr, list, wave_ext,
-                           wps, B, bbox);
-    } else if (!(image || bgr))
-      hipLaunchKernelGGL((raster_resolve_shade_kernel<false, false>), dim3(grid), dim3(256), 0, st, lit, uvs, faces, mesh_table, textures,
-                         tex_table, class_index, scr, zbuf, vmax, H, W, tex_bilinear, p0, p1, p2, image, bgr, status, hdr, list, wave_ext,
-                         wps, B, bbox);
-    else if (Kps && normals)
-      hipLaunchKernelGGL((raster_resolve_shade_k_kernel<true>), dim3(grid), dim3(256), 0, st, lit, Kps, uvs, faces, mesh_table, textures,
-                         tex_table, class_index, scr, zbuf, vmax, H, W, tex_bilinear, p0, p1, p2, image, bgr, status, hdr, list, wave_ext,
-                         wps, B, bbox);
-    else if (Kps)
-      hipLaunchKernelGGL((raster_resolve_shade_k_kernel<false>), dim3(grid), dim3(256), 0, st, lit, Kps, uvs, faces, mesh_table, textures,
-                         tex_table, class_index, scr, zbuf, vmax, H, W, tex_bilinear, p0, p1, p2, image, bgr, status, hdr, list, wave_ext,
-                         wps, B, bbox);
-    else if (normals)
-      hipLaunchKernelGGL((raster_resolve_shade_kernel<true, true>), dim3(grid), dim3(256), 0, st, lit, uvs, faces, mesh_table, textures,
-                         tex_table, class_index, scr, zbuf, vmax, H, W, tex_bilinear, p0, p1, p2, image, bgr, status, hdr, list, wave_ext,
-                         wps, B, bbox);
-    else
-      hipLaunchKernelGGL((raster_resolve_shade_kernel<false, true>), dim3(grid), dim3(256), 0, st, lit, uvs, faces, mesh_table, textures,
-                         tex_table, class_index, scr, zbuf, vmax, H, W, tex_bilinear, p0, p1, p2, image, bgr, status, hdr, list, wave_ext,
-                         wps, B, bbox);
-  } else if (lm) {
-    if (Kps)
-      hipLaunchKernelGGL(raster_resolve_lm_kernel<true>, dim3(ceil_div(W, 256), H, B), dim3(256), 0, st, lit, Kps, uvs, faces, mesh_table,
-                         textures, tex_table, class_index, scr, zbuf, vmax, H, W, tex_bilinear, p0, p1, p2, mask_thr, image, depth, mask, bgr,
-                         bbox, status);
-    else
-      hipLaunchKernelGGL(raster_resolve_lm_kernel<false>, dim3(ceil_div(W, 256), H, B), dim3(256), 0, st, lit, Kps, uvs, faces, mesh_table,
-                         textures, tex_table, class_index, scr, zbuf, vmax, H, W, tex_bilinear, p0, p1, p2, mask_thr, image, depth, mask, bgr,
-                         bbox, status);
-  } else if (Kps) {
-    if (normals)
-      hipLaunchKernelGGL(raster_resolve_k_kernel<true>, dim3(ceil_div(W, 256), H, B), dim3(256), 0, st, lit, Kps, uvs, faces, mesh_table,
-                         textures, tex_table, class_index, scr, zbuf, vmax, H, W, tex_bilinear, p0, p1, p2, mask_thr, image, depth, mask, bgr,
-                         bbox, status);
-    else
-      hipLaunchKernelGGL(raster_resolve_k_kernel<false>, dim3(ceil_div(W, 256), H, B), dim3(256), 0, st, lit, Kps, uvs, faces, mesh_table,
-                         textures, tex_table, class_index, scr, zbuf, vmax, H, W, tex_bilinear, p0, p1, p2, mask_thr, image, depth, mask, bgr,
-                         bbox, status);
+    const auto shade = !colour ? raster_resolve_shade_kernel<false, false, false, false>
+                       : lm    ? (perk ? raster_resolve_shade_kernel<true, true, true, true>
+                                       : raster_resolve_shade_kernel<true, true, false, true>)
+                       : lit_on ? (perk ? raster_resolve_shade_kernel<true, true, true, false>
+                                        : raster_resolve_shade_kernel<true, true, false, false>)
+                                : (perk ? raster_resolve_shade_kernel<false, true, true, false>
+                                        : raster_resolve_shade_kernel<false, true, false, false>);
+    hipLaunchKernelGGL(shade, dim3(grid), dim3(256), 0, st, lit, Kps, uvs, faces, mesh_table, textures, tex_table, class_index, scr, zbuf,
+                       vmax, H, W, tex_bilinear, p0, p1, p2, image, bgr, status, hdr, list, wave_ext, wps, B, bbox);
   } else {
-    if (normals)
-      hipLaunchKernelGGL(raster_resolve_kernel<true>, dim3(ceil_div(W, 256), H, B), dim3(256), 0, st, lit, uvs, faces, mesh_table, textures,
-                         tex_table, class_index, scr, zbuf, vmax, H, W, tex_bilinear, p0, p1, p2, mask_thr, image, depth, mask, bgr, bbox,
-                         status);
-    else
-      hipLaunchKernelGGL(raster_resolve_kernel<false>, dim3(ceil_div(W, 256), H, B), dim3(256), 0, st, lit, uvs, faces, mesh_table,
-                         textures, tex_table, class_index, scr, zbuf, vmax, H, W, tex_bilinear, p0, p1, p2, mask_thr, image, depth, mask,
-                         bgr, bbox, status);
+    const auto resolve = lm      ? (perk ? raster_resolve_kernel<true, true, true> : raster_resolve_kernel<true, false, true>)
+                         : lit_on ? (perk ? raster_resolve_kernel<true, true, false> : raster_resolve_kernel<true, false, false>)
+                                  : (perk ? raster_resolve_kernel<false, true, false> : raster_resolve_kernel<false, false, false>);
+    hipLaunchKernelGGL(resolve, dim3(ceil_div(W, 256), H, B), dim3(256), 0, st, lit, Kps, uvs, faces, mesh_table, textures, tex_table,
+                       class_index, scr, zbuf, vmax, H, W, tex_bilinear, p0, p1, p2, mask_thr, image, depth, mask, bgr, bbox, status);
   }
   return check_launch("raster_render");
 }
@@ -991,12 +854,10 @@ int dim_raster_render_dirty(const float* verts, const float* normals, const floa
                             const float* light_pos, const float* light_int, float brightness_ratio, const float* plane_means3,
                             float mask_thr, void* workspace, float* image, float* depth, float* mask, float* bgr, int* bbox, int* status,
                             const int* clean_bbox, void* stream) {
-  if (B == 0) return DIM_OK;
-  DIM_REQUIRE(!normals || (light_pos && light_int), "lit render: null light pointer");
-  DIM_REQUIRE(!clean_bbox || clean_bbox != bbox, "clean_bbox and bbox must be different arrays (the stream pass reads one while the last pass writes the other)");
-  return raster_render_impl(verts, normals, uvs, faces, mesh_table, n_classes, vmax, fmax, textures, tex_table, class_index, poses, K9, B,
-                            H, W, znear, zfar, tex_bilinear, light_pos, light_int, brightness_ratio, plane_means3, mask_thr, workspace,
-                            image, depth, mask, bgr, bbox, status, clean_bbox, nullptr, stream);
+  // the same checks, the same call: K_per_sample NULL = K9 for every sample
+  return dim_raster_render_k(verts, normals, uvs, faces, mesh_table, n_classes, vmax, fmax, textures, tex_table, class_index, poses, K9, B,
+                             H, W, znear, zfar, tex_bilinear, light_pos, light_int, brightness_ratio, plane_means3, mask_thr, workspace,
+                             image, depth, mask, bgr, bbox, status, clean_bbox, nullptr, stream);
 }
 
 // dim_raster_render_dirty with per-sample intrinsics (the reference's test loop re-renders pair b with its own -K.txt:

@@ -517,38 +517,23 @@ def intrinsics_per_sample(K, B, device):
     return torch.from_numpy(np.ascontiguousarray(a.reshape(B, 9))).to(device)
 
 
-def raster_render_k(rm, class_index, poses, K_per_sample, workspace, light_position=None, light_intensity=None, brightness_ratio=0.0,
-                    plane_means=None, mask_thr=0.2, image=None, depth=None, mask=None, bgr=None, bbox=None, status=None, clean_bbox=None):
-    """dim_raster_render_k: render machine `rm` (lib/render_hip: its mesh table, K, znear / zfar; lit when it has normals) with one
-    camera per sample.  K_per_sample: (B,9) f32 CUDA (intrinsics_per_sample) or None (rm.K for all).  workspace: rm's for this B."""
-    B = poses.shape[0]
-    keep, k9 = host_f32(rm.K, 9)   # (keeps the host array alive through the call)
-    normals = getattr(rm, "normals", None)
+def raster_render(rm, class_index, poses, workspace, K=None, K_per_sample=None, light_position=None, light_intensity=None,
+                  brightness_ratio=0.0, lm=False, plane_means=None, mask_thr=0.2, image=None, depth=None, mask=None, bgr=None, bbox=None,
+                  status=None, clean_bbox=None):
+    """Render machine `rm` (lib/render_hip: its mesh table, K, znear / zfar; lit when it has normals) into whichever outputs are given.
+    K: another uniform camera than rm.K (nine values); K_per_sample: (B,9) f32 CUDA (intrinsics_per_sample), one camera per sample, or
+    None.  lm: dim_raster_render_lit_lm, the LINEMOD light rule (the light colour scales the diffuse term only; rm must have normals and
+    both light tensors (B,3) f32 CUDA are required); otherwise dim_raster_render_k, which with K_per_sample None is
+    dim_raster_render_dirty argument for argument.  workspace: rm's for this B."""
+    keep, k9 = host_f32(rm.K if K is None else K, 9)   # (keeps the host array alive through the call)
     pm = host_f32(plane_means, 3) if plane_means is not None else (None, None)
-    opt = lambda t, dt=f32: dptr(t, dt) if t is not None else None  # noqa: E731
-    check(lib().dim_raster_render_k(
-        dptr(rm.verts), opt(normals), dptr(rm.uvs), dptr(rm.faces), dptr(rm.mesh_table), int(rm.mesh_table.shape[0]), rm.vmax, rm.fmax,
-        dptr(rm.textures), dptr(rm.tex_table), dptr(class_index, i32), dptr(poses, f32), k9, B, rm.height, rm.width, float(rm.zNear),
-        float(rm.zFar), int(rm.tex_bilinear), opt(light_position), opt(light_intensity), float(brightness_ratio), pm[1], float(mask_thr),
-        workspace.data_ptr(), dptr(image), dptr(depth), dptr(mask), dptr(bgr), opt(bbox, i32), opt(status, i32), opt(clean_bbox, i32),
-        opt(K_per_sample), current_stream()))
-
-
-def raster_render_lit_lm(rm, class_index, poses, K_per_sample, workspace, light_position, light_intensity, brightness_ratio,
-                         plane_means=None, mask_thr=0.2, image=None, depth=None, mask=None, bgr=None, bbox=None, status=None,
-                         clean_bbox=None):
-    """dim_raster_render_lit_lm: raster_render_k under the LINEMOD light rule (the light colour scales the diffuse term only); `rm`
-    must have normals, and both light tensors (B,3) f32 CUDA are required."""
-    B = poses.shape[0]
-    keep, k9 = host_f32(rm.K, 9)
-    pm = host_f32(plane_means, 3) if plane_means is not None else (None, None)
-    opt = lambda t, dt=f32: dptr(t, dt) if t is not None else None  # noqa: E731
-    check(lib().dim_raster_render_lit_lm(
-        dptr(rm.verts), dptr(rm.normals), dptr(rm.uvs), dptr(rm.faces), dptr(rm.mesh_table), int(rm.mesh_table.shape[0]), rm.vmax, rm.fmax,
-        dptr(rm.textures), dptr(rm.tex_table), dptr(class_index, i32), dptr(poses, f32), k9, B, rm.height, rm.width, float(rm.zNear),
-        float(rm.zFar), int(rm.tex_bilinear), dptr(light_position, f32), dptr(light_intensity, f32), float(brightness_ratio), pm[1],
-        float(mask_thr), workspace.data_ptr(), dptr(image), dptr(depth), dptr(mask), dptr(bgr), opt(bbox, i32), opt(status, i32),
-        opt(clean_bbox, i32), opt(K_per_sample), current_stream()))
+    render = lib().dim_raster_render_lit_lm if lm else lib().dim_raster_render_k
+    check(render(
+        dptr(rm.verts), _opt(getattr(rm, "normals", None)), dptr(rm.uvs), dptr(rm.faces), dptr(rm.mesh_table), int(rm.mesh_table.shape[0]),
+        rm.vmax, rm.fmax, dptr(rm.textures), dptr(rm.tex_table), dptr(class_index, i32), dptr(poses, f32), k9, poses.shape[0], rm.height,
+        rm.width, float(rm.zNear), float(rm.zFar), int(rm.tex_bilinear), _opt(light_position), _opt(light_intensity), float(brightness_ratio),
+        pm[1], float(mask_thr), workspace.data_ptr(), dptr(image), dptr(depth), dptr(mask), dptr(bgr), _opt(bbox, i32), _opt(status, i32),
+        _opt(clean_bbox, i32), _opt(K_per_sample), current_stream()))
 
 
 STATUS_LAYER_HIDDEN = 256   # DIM_STATUS_LAYER_HIDDEN: dim_scene_compose, a used layer won no pixel

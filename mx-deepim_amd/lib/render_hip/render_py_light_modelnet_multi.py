@@ -10,9 +10,8 @@ All meshes (256 for the ModelNet-unseen configuration) are resident in one HBM t
 import numpy as np
 import torch
 
-from lib.hip import ops
-from lib.hip.capi import check, current_stream, dptr, host_f32, lib
-from lib.render_hip.render_py_multi import Render_Py, quat2mat
+from lib.hip.capi import check, current_stream, dptr, lib
+from lib.render_hip.render_py_multi import Render_Py, pose_1x3x4
 
 LIGHT_DIRS = [[1, 0, 1], [1, 1, 1], [0, 1, 1], [-1, 1, 1], [-1, 0, 1], [0, 0, 1]]  # tester.py:206-218
 
@@ -90,17 +89,12 @@ class Render_Py_Light_ModelNet_Multi(Render_Py):
             tex = np.asarray(Image.open(texture_path).convert("RGB"), dtype=np.uint8)
         if meshes is None:
             meshes = [load_obj_with_normals(p) for p in self.model_path_list]
-        self.width, self.height, self.zNear, self.zFar = width, height, zNear, zFar
-        self.K = np.asarray(K, dtype=np.float32).reshape(3, 3)
+        self._setup(K, width, height, zNear, zFar, device, tex_bilinear)
         self.classes = self.model_path_list
-        self.device = torch.device(device)
-        self.tex_bilinear = bool(tex_bilinear)
         # one shared texture: every class points at the same bytes
         self._upload([(v, t, f, tex) for v, n, t, f in meshes])
         self.normals = torch.from_numpy(np.concatenate([np.ascontiguousarray(n, np.float32) for v, n, t, f in meshes])).to(self.device)
         assert self.normals.shape == self.verts.shape
-        self._ws = None
-        self._ws_B = 0
 
     def light_position(self, poses, idx=2, out=None):
         """tester.py:204-225 on the device: (B,3) light positions for poses (B,3,4)."""
@@ -115,41 +109,17 @@ class Render_Py_Light_ModelNet_Multi(Render_Py):
                      depth=None, mask=None, bgr=None, bbox=None, plane_means=None, mask_thr=0.2, status=None, clean_bbox=None):
         """class_index (B,) int32, poses (B,3,4), light_position / light_intensity (B,3) f32, all cuda.
         light_position None = the loop's rule (idx 2); light_intensity None = white (1,1,1).  K, clean_bbox: as Render_Py.render_batch."""
-        B = poses.shape[0]
-        kps = ops.intrinsics_per_sample(K, B, self.device)   # (a wrong shape raises before the light kernel is launched)
         if light_position is None:
             light_position = self.light_position(poses)
         if light_intensity is None:
-            light_intensity = torch.ones((B, 3), dtype=torch.float32, device=self.device)
-        ws = self._workspace(B)
-        if clean_bbox is not None and not mask_thr < self.zNear:
-            clean_bbox = None
-        if kps is not None:
-            ops.raster_render_k(self, class_index, poses, kps, ws, light_position=light_position, light_intensity=light_intensity,
-                                brightness_ratio=self.brightness_ratios[brightness_k], plane_means=plane_means, mask_thr=mask_thr,
-                                image=image, depth=depth, mask=mask, bgr=bgr, bbox=bbox, status=status, clean_bbox=clean_bbox)
-            return
-        keep, kp = host_f32(self.K if K is None else K, 9)
-        pm = host_f32(plane_means, 3) if plane_means is not None else (None, None)
-        check(lib().dim_raster_render_dirty(
-            dptr(self.verts), dptr(self.normals), dptr(self.uvs), dptr(self.faces), dptr(self.mesh_table), int(self.mesh_table.shape[0]),
-            self.vmax, self.fmax,
-            dptr(self.textures), dptr(self.tex_table), dptr(class_index, torch.int32), dptr(poses, torch.float32), kp, B, self.height,
-            self.width, float(self.zNear), float(self.zFar), int(self.tex_bilinear), dptr(light_position, torch.float32),
-            dptr(light_intensity, torch.float32), float(self.brightness_ratios[brightness_k]), pm[1], float(mask_thr), ws.data_ptr(),
-            dptr(image), dptr(depth), dptr(mask), dptr(bgr), dptr(bbox, torch.int32) if bbox is not None else None,
-            dptr(status, torch.int32) if status is not None else None, dptr(clean_bbox, torch.int32) if clean_bbox is not None else None,
-            current_stream()))
+            light_intensity = torch.ones((poses.shape[0], 3), dtype=torch.float32, device=self.device)
+        self._render(class_index, poses, K, light_position=light_position, light_intensity=light_intensity,
+                     brightness_ratio=self.brightness_ratios[brightness_k], plane_means=plane_means, mask_thr=mask_thr, image=image,
+                     depth=depth, mask=mask, bgr=bgr, bbox=bbox, status=status, clean_bbox=clean_bbox)
 
     def render(self, model_idx, r, t, light_position, light_intensity, brightness_k=0, r_type="quat"):
         """Reference signature (:153-235); returns host numpy (bgr uint8, depth float32) like the glReadPixels path."""
-        if r_type == "quat":
-            R = quat2mat(r)
-        elif r_type == "mat":
-            R = np.asarray(r)
-        pose = np.zeros((1, 3, 4), dtype=np.float32)
-        pose[0, :, :3] = R
-        pose[0, :, 3] = np.asarray(t, dtype=np.float32).squeeze()
+        pose = pose_1x3x4(r, t, r_type)
         d = self.device
         bgr = torch.empty((1, self.height, self.width, 3), dtype=torch.float32, device=d)
         depth = torch.empty((1, 1, self.height, self.width), dtype=torch.float32, device=d)

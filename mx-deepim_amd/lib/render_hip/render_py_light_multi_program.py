@@ -12,9 +12,8 @@ skipped as in the reference (:105-107); `class_index` of `render_batch` counts t
 import numpy as np
 import torch
 
-from lib.hip import ops
 from lib.render_hip.render_py_light_modelnet_multi import load_obj_with_normals, vertex_normals
-from lib.render_hip.render_py_multi import Render_Py, quat2mat
+from lib.render_hip.render_py_multi import Render_Py, pose_1x3x4
 
 
 class Render_Py_Light_MultiProgram(Render_Py):
@@ -22,14 +21,11 @@ class Render_Py_Light_MultiProgram(Render_Py):
                  device="cuda:0", meshes=None, tex_bilinear=False):
         """meshes: optional list, one entry per class that is not "__background__", of (verts, normals, uvs, faces, texture_uint8_HxWx3)
         replacing model_folder_dict[class]/textured.obj and texture_map.png; normals None = area-weighted vertex normals."""
-        self.width, self.height, self.zNear, self.zFar = width, height, zNear, zFar
-        self.K = np.asarray(K, dtype=np.float32).reshape(3, 3)
+        self._setup(K, width, height, zNear, zFar, device, tex_bilinear)
         self.model_folder_dict = model_folder_dict
         self.class_name_list = list(class_name_list)
         self.classes = [c for c in self.class_name_list if c != "__background__"]
         self.brightness_ratios = list(brightness_ratios)
-        self.device = torch.device(device)
-        self.tex_bilinear = bool(tex_bilinear)
         if meshes is None:
             from PIL import Image
 
@@ -44,8 +40,6 @@ class Render_Py_Light_MultiProgram(Render_Py):
         self._upload([(v, t, f, tex) for v, n, t, f, tex in meshes])
         self.normals = torch.from_numpy(np.concatenate([np.ascontiguousarray(n, np.float32) for v, n, t, f, tex in meshes])).to(self.device)
         assert self.normals.shape == self.verts.shape
-        self._ws = None
-        self._ws_B = 0
         self.class_name = self.classes[-1]
         self.brightness_k = 0
 
@@ -53,29 +47,15 @@ class Render_Py_Light_MultiProgram(Render_Py):
                      mask=None, bgr=None, bbox=None, plane_means=None, mask_thr=0.2, status=None, clean_bbox=None):
         """class_index (B,) int32, poses (B,3,4), light_position / light_intensity (B,3) f32, all cuda; one brightness ratio
         (brightness_ratios[brightness_k]) for the batch.  K, outputs, status, clean_bbox: as Render_Py.render_batch."""
-        B = poses.shape[0]
-        kps = ops.intrinsics_per_sample(K, B, self.device)
-        ws = self._workspace(B)
-        if clean_bbox is not None and not mask_thr < self.zNear:
-            clean_bbox = None
-        rm = self
-        if kps is None and K is not None:   # one other camera for the whole batch
-            rm = _WithK(self, K)
-        ops.raster_render_lit_lm(rm, class_index, poses, kps, ws, light_position, light_intensity, self.brightness_ratios[brightness_k],
-                                 plane_means=plane_means, mask_thr=mask_thr, image=image, depth=depth, mask=mask, bgr=bgr, bbox=bbox,
-                                 status=status, clean_bbox=clean_bbox)
+        self._render(class_index, poses, K, light_position=light_position, light_intensity=light_intensity,
+                     brightness_ratio=self.brightness_ratios[brightness_k], lm=True, plane_means=plane_means, mask_thr=mask_thr, image=image,
+                     depth=depth, mask=mask, bgr=bgr, bbox=bbox, status=status, clean_bbox=clean_bbox)
 
     def render(self, r, t, light_position, light_intensity, class_name, brightness_k=0, r_type="quat"):
         """Reference signature (:156-238); returns host numpy (bgr uint8, depth float32) like the glReadPixels path."""
-        if r_type == "quat":
-            R = quat2mat(r)
-        elif r_type == "mat":
-            R = np.asarray(r)
+        pose = pose_1x3x4(r, t, r_type)
         self.class_name = class_name
         self.brightness_k = brightness_k
-        pose = np.zeros((1, 3, 4), dtype=np.float32)
-        pose[0, :, :3] = R
-        pose[0, :, 3] = np.asarray(t, dtype=np.float32).squeeze()
         d = self.device
         bgr = torch.empty((1, self.height, self.width, 3), dtype=torch.float32, device=d)
         depth = torch.empty((1, 1, self.height, self.width), dtype=torch.float32, device=d)
@@ -85,13 +65,3 @@ class Render_Py_Light_MultiProgram(Render_Py):
                           brightness_k=brightness_k, bgr=bgr, depth=depth)
         return bgr[0].cpu().numpy().astype(np.uint8), depth[0, 0].cpu().numpy()
 
-
-class _WithK(object):
-    """a render machine seen with another uniform K (the ops front-end reads rm.K)"""
-
-    def __init__(self, rm, K):
-        self._rm = rm
-        self.K = np.asarray(K, dtype=np.float32).reshape(3, 3)
-
-    def __getattr__(self, name):
-        return getattr(self._rm, name)

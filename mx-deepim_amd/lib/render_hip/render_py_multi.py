@@ -12,8 +12,8 @@ import os
 import numpy as np
 import torch
 
-from lib.hip import capi, ops
-from lib.hip.capi import check, current_stream, dptr, host_f32, lib
+from lib.hip import ops
+from lib.hip.capi import lib
 
 
 def quat2mat(q):
@@ -64,17 +64,28 @@ def load_obj(path):
     return np.asarray(out_v, np.float32), np.asarray(out_t, np.float32), np.asarray(faces, np.int32)
 
 
+def pose_1x3x4(r, t, r_type):
+    """(r, t) of the reference's single-shot render() -> a (1,3,4) float32 host pose; r_type "quat" (w, x, y, z) or "mat" """
+    if r_type == "quat":
+        R = quat2mat(r)
+    elif r_type == "mat":
+        R = np.asarray(r)
+    else:
+        raise Exception("Unknown r_type: {}".format(r_type))
+    pose = np.zeros((1, 3, 4), dtype=np.float32)
+    pose[0, :, :3] = R
+    pose[0, :, 3] = np.asarray(t, dtype=np.float32).squeeze()
+    return pose
+
+
 class Render_Py(object):
     def __init__(self, model_dir, classes, K, width=640, height=480, zNear=0.25, zFar=6.0, device="cuda:0", meshes=None,
                  tex_bilinear=False):
         """meshes: optional list of (verts, uvs, faces, texture_uint8_HxWx3) replacing the textured.obj /
         texture_map.png files under model_dir/<class>/ (render_py_multi.py:66-78)."""
-        self.width, self.height, self.zNear, self.zFar = width, height, zNear, zFar
-        self.K = np.asarray(K, dtype=np.float32).reshape(3, 3)
+        self._setup(K, width, height, zNear, zFar, device, tex_bilinear)
         self.model_dir = model_dir
         self.classes = list(classes)
-        self.device = torch.device(device)
-        self.tex_bilinear = bool(tex_bilinear)
         if meshes is None:
             from PIL import Image
 
@@ -86,8 +97,14 @@ class Render_Py(object):
                 meshes.append((v, t, f, tex))
         assert len(meshes) == len(self.classes)
         self._upload(meshes)
-        self._ws = None
-        self._ws_B = 0
+
+    def _setup(self, K, width, height, zNear, zFar, device, tex_bilinear):
+        """what every render machine holds besides its meshes"""
+        self.width, self.height, self.zNear, self.zFar = width, height, zNear, zFar
+        self.K = np.asarray(K, dtype=np.float32).reshape(3, 3)
+        self.device = torch.device(device)
+        self.tex_bilinear = bool(tex_bilinear)
+        self._ws = {}   # batch size -> workspace
 
     def _upload(self, meshes):
         vo = fo = to = 0
@@ -125,8 +142,6 @@ class Render_Py(object):
         """one workspace per batch size, zero-filled when allocated: its first 256 bytes are the rasteriser's header ("the z-buffer
         behind me is clear"), which must not hold what a previous owner of the memory left there (include/deepim_hip.h); the layout
         behind the header depends on B, so two batch sizes never share one"""
-        if not isinstance(self._ws, dict):
-            self._ws = {}
         if B not in self._ws:
             n = lib().dim_raster_workspace_bytes(B, self.vmax, self.height, self.width)
             self._ws[B] = torch.zeros((n + 7) // 8, dtype=torch.int64, device=self.device)
@@ -144,36 +159,21 @@ class Render_Py(object):
         status: optional (B,) int32 cuda; DIM_STATUS_BAD_CLASS (4) / DIM_STATUS_BAD_FACE (8) / DIM_STATUS_BAD_K (16) are OR-ed in.
         clean_bbox: optional (B,4) int32 cuda, the bbox a PREVIOUS render_batch into the same output tensors returned (another tensor
         than `bbox`): the planes hold background outside it, and pixels out there that this render does not cover are not rewritten."""
+        self._render(class_index, poses, K, plane_means=plane_means, mask_thr=mask_thr, image=image, depth=depth, mask=mask, bgr=bgr,
+                     bbox=bbox, status=status, clean_bbox=clean_bbox)
+
+    def _render(self, class_index, poses, K, mask_thr=0.2, clean_bbox=None, **kw):
+        """what every render_batch ends in.  K as render_batch takes it; kw: the lights and outputs of ops.raster_render"""
         B = poses.shape[0]
-        kps = ops.intrinsics_per_sample(K, B, self.device)
-        ws = self._workspace(B)
+        kps = ops.intrinsics_per_sample(K, B, self.device)   # (a wrong shape raises before the render is launched)
         if clean_bbox is not None and not mask_thr < self.zNear:
             clean_bbox = None   # the mask's box is the box of everything drawn only if every fragment passes the mask threshold
-        if kps is not None:
-            ops.raster_render_k(self, class_index, poses, kps, ws, plane_means=plane_means, mask_thr=mask_thr, image=image, depth=depth,
-                                mask=mask, bgr=bgr, bbox=bbox, status=status, clean_bbox=clean_bbox)
-            return
-        keep, kp = host_f32(self.K if K is None else K, 9)
-        pm = host_f32(plane_means, 3) if plane_means is not None else (None, None)
-        check(lib().dim_raster_render_dirty(
-            dptr(self.verts), None, dptr(self.uvs), dptr(self.faces), dptr(self.mesh_table), int(self.mesh_table.shape[0]), self.vmax, self.fmax,
-            dptr(self.textures), dptr(self.tex_table), dptr(class_index, torch.int32), dptr(poses, torch.float32), kp, B, self.height,
-            self.width, float(self.zNear), float(self.zFar), int(self.tex_bilinear), None, None, 0.0, pm[1], float(mask_thr), ws.data_ptr(),
-            dptr(image), dptr(depth), dptr(mask), dptr(bgr), dptr(bbox, torch.int32) if bbox is not None else None,
-            dptr(status, torch.int32) if status is not None else None, dptr(clean_bbox, torch.int32) if clean_bbox is not None else None,
-            current_stream()))
+        ops.raster_render(self, class_index, poses, self._workspace(B), K=None if kps is not None else K, K_per_sample=kps,
+                          mask_thr=mask_thr, clean_bbox=clean_bbox, **kw)
 
     def render(self, cls_idx, r, t, r_type="quat", K=None):
         """Reference signature (render_py_multi.py:112-147); returns host numpy like glReadPixels did."""
-        if r_type == "quat":
-            R = quat2mat(r)
-        elif r_type == "mat":
-            R = np.asarray(r)
-        else:
-            raise Exception("Unknown r_type: {}".format(r_type))
-        pose = np.zeros((1, 3, 4), dtype=np.float32)
-        pose[0, :, :3] = R
-        pose[0, :, 3] = np.asarray(t, dtype=np.float32).squeeze()
+        pose = pose_1x3x4(r, t, r_type)
         d = self.device
         bgr = torch.empty((1, self.height, self.width, 3), dtype=torch.float32, device=d)
         depth = torch.empty((1, 1, self.height, self.width), dtype=torch.float32, device=d)
