@@ -504,6 +504,8 @@ int dim_conv2d_fwd_winograd(const float* x, const float* w_packed, const float* 
  * the sum of four 3x3 / stride-1 / pad-1 convolutions of the phase images x[2r + py][2q + px] with the sub-kernels
  * w[2u + py][2v + px]; the four F(4x4,3x3)-transformed phase tiles are concatenated along the channels, so 36 GEMMs with K = 4 Cin
  * replace the 25-tap direct form (2.78x fewer multiply-adds) and the output transform is the one of the stride-1 layers.
+ * 23 of the 144 (phase, plane) weight blocks are zero by construction: the forward neither stores their V blocks nor multiplies them
+ * (top of the 5x5 / stride-2 code in csrc/winograd.hip); layouts, sizes and results are unchanged.
  * Weights: MXNet layout (Cout,Cin,5,5).  Output (N, ceil(H/2), ceil(W/2), Cout).  Same f32 accuracy class as F(4x4,3x3). */
 long dim_winograd5x5s2_packed_weight_floats(int Cout, int Cin);
 long dim_winograd5x5s2_workspace_floats(int N, int H, int W, int Cin, int Cout);

@@ -252,6 +252,10 @@ struct WGemmArgs {
   const void* U3;       // the three-term bf16 image of U behind it in the same buffer (wino_gemm_split.hip)
   unsigned u3_bytes;
   int split;            // run wino_gemm_split_kernel (f32 operands as three bf16 terms, six MFMA products)
+  // forward 5x5 / stride-2 layers (winograd.hip): K is four phase blocks of q chunks, and some (plane, phase) blocks of the weights are
+  // zero by construction (wino5_phase_mask).  skip5 = 1: the cursors step over their chunks.  The flat chunk list, and with it every
+  // range boundary, stays the one of the full K: an item is cut where it was cut before, the sums keep their bits.  Plane-major only.
+  int skip5, q;
 };
 // wino_gemm_split.hip.  Every packed Winograd weight buffer is [U f32][U3]: floats -> floats * 5 / 2
 inline long wino_packed_with_split(long u_floats) { return u_floats + (u_floats * 3 + 1) / 2; }
@@ -261,7 +265,7 @@ int wino_get_split();
 bool wino_gemm_split_has(int tile);
 int wino_gemm_split_slots(int tile);
 int wino_gemm_split_run(const WGemmArgs& a, hipStream_t st);
-int wino_gemm_plan(WGemmArgs* plan, const float* V, const float* U, float* M, int T, int K, int Cout, int P, int tile);
+int wino_gemm_plan(WGemmArgs* plan, const float* V, const float* U, float* M, int T, int K, int Cout, int P, int tile, int skip5 = 0);
 // zeroed = the shared tiles have been zeroed already (by the transform kernel that ran before): no separate zero launch
 int wino_gemm_run(const WGemmArgs& plan, bool zeroed, hipStream_t st);
 
@@ -275,8 +279,40 @@ int wino_gemm_run(const WGemmArgs& plan, bool zeroed, hipStream_t st);
 //                     time (2-3 MB of weights), so a plane's weights leave the fabric once per XCD instead of once per item
 struct WCur {
   int ch, p, nt, mt;
+  int m;  // wino5_phase_mask of plane p under skip5, else 0xF: planes without zero blocks pay one comparison per step
 };
-__device__ __forceinline__ WCur wcur_decode(int chunk, const WGemmArgs& a) {
+// phases (bit 2 py + px) of plane p = 6 a + b whose weight block is not zero: a sub-kernel of an odd phase has no third row / column and
+// the last row of G is [0 0 1], so a = 5 keeps py = 0 only and b = 5 keeps px = 0 only
+__host__ __device__ __forceinline__ int wino5_phase_mask(int p) { return (p >= 30 ? 0x3 : 0xF) & (p % 6 == 5 ? 0x5 : 0xF); }
+// first chunk >= ch of a plane with phase mask m whose block is not zero; nch if there is none (chunk 0, phase (0,0), never is)
+__device__ __forceinline__ int wcur_snap(int ch, int m, const WGemmArgs& a) {
+  const int q = a.q;
+  const int ph = (ch >= q) + (ch >= 2 * q) + (ch >= 3 * q);
+  if ((m >> ph) & 1) return ch;
+  const int r = m >> (ph + 1);  // ph + 1 <= 4
+  return r ? (ph + 1 + __builtin_ctz(r)) * q : a.nch;
+}
+// one step in the plane-major order (the only order the split kernel and the skipping plans use)
+__device__ __forceinline__ void wcur_advance_pm(WCur& c, const WGemmArgs& a) {
+  ++c.ch;
+  if (c.m != 0xF) c.ch = wcur_snap(c.ch, c.m, a);
+  if (c.ch >= a.nch) {
+    c.ch = 0;
+    if (++c.nt == a.NTN) {
+      c.nt = 0;
+      if (++c.mt == a.MT) {
+        c.mt = 0;
+        ++c.p;
+        if (a.skip5) c.m = wino5_phase_mask(c.p);
+      }
+    }
+  }
+}
+// is c the last chunk of its item that is multiplied
+__device__ __forceinline__ bool wcur_item_end(const WCur& c, const WGemmArgs& a) {
+  return (c.m != 0xF ? wcur_snap(c.ch + 1, c.m, a) : c.ch + 1) >= a.nch;
+}
+__device__ __forceinline__ WCur wcur_decode_raw(int chunk, const WGemmArgs& a) {
   WCur c;
   const unsigned item = fastdiv((unsigned)chunk, a.d_nch);
   c.ch = chunk - (int)item * a.nch;
@@ -294,6 +330,31 @@ __device__ __forceinline__ WCur wcur_decode(int chunk, const WGemmArgs& a) {
     c.mt = (int)mt;
   }
   return c;
+}
+// the first multiplied chunk at or behind flat position `chunk`
+__device__ __forceinline__ WCur wcur_decode(int chunk, const WGemmArgs& a) {
+  WCur c = wcur_decode_raw(chunk, a);
+  c.m = a.skip5 ? wino5_phase_mask(c.p) : 0xF;
+  if (c.m != 0xF) {
+    c.ch = wcur_snap(c.ch, c.m, a) - 1;
+    wcur_advance_pm(c, a);  // ch + 1, or on to chunk 0 of the next item
+  }
+  return c;
+}
+// multiplied chunks among the flat positions [begin, end)
+__device__ __forceinline__ int wcur_count(int begin, int end, const WGemmArgs& a) {
+  if (!a.skip5) return end - begin;
+  int n = 0;
+  for (int v = begin; v < end;) {
+    const unsigned item = fastdiv((unsigned)v, a.d_nch);
+    const int base = (int)item * a.nch, lo = v - base, hi = min(end - base, a.nch);
+    const int m = wino5_phase_mask((int)fastdiv(fastdiv(item, a.d_NTN), a.d_MT));
+#pragma unroll
+    for (int ph = 0; ph < 4; ++ph)
+      if ((m >> ph) & 1) n += max(0, min(hi, (ph + 1) * a.q) - max(lo, ph * a.q));
+    v = base + a.nch;
+  }
+  return n;
 }
 // workgroups are dealt round-robin to the 8 XCDs (blocks b and b + 8 share one L2): number them so that every XCD owns a CONTIGUOUS
 // run of chunk ranges (bijective for any G: the first G % 8 XCDs own one range more)

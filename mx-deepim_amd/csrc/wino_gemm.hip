@@ -28,6 +28,7 @@ namespace dim {
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 __device__ __forceinline__ void wcur_advance(WCur& c, const WGemmArgs& a) {
+  if (a.plane_major) return wcur_advance_pm(c, a);
   if (++c.ch == a.nch) {
     c.ch = 0;
     if (a.plane_major) {
@@ -80,8 +81,10 @@ __global__ __launch_bounds__(WM * WN * 64) __attribute__((amdgpu_waves_per_eu(BN
   const int khalf = lane >> 5;
 
   const int wg = a.plane_major ? wg_xcd_contiguous(blockIdx.x, a.G) : (int)blockIdx.x;
-  const int c_begin = wg_first_chunk(wg, a);
-  const int c_end = wg_first_chunk(wg + 1, a);
+  // the range in flat positions; the loop below counts the chunks it multiplies (all of them unless a.skip5)
+  const int r_begin = wg_first_chunk(wg, a);
+  const int c_begin = 0, c_end = wcur_count(r_begin, wg_first_chunk(wg + 1, a), a);
+  if (c_end == 0) return;
 
   const int RS = a.P * a.K;  // V row stride (floats)
   const int a_voff0 = (srow * RS + q * 4) * 4;
@@ -92,7 +95,7 @@ __global__ __launch_bounds__(WM * WN * 64) __attribute__((amdgpu_waves_per_eu(BN
   const int wchunk_bytes = a.Cout * BK * 4;
 
   // three cursors into the chunk list: L = next A chunk to load (runs two ahead), Bc = next B fragments (one ahead), C = compute
-  WCur L = wcur_decode(c_begin, a), Bc = L, C = L;
+  WCur L = wcur_decode(r_begin, a), Bc = L, C = L;
 
   float4 ra0, ra1, ra2, ra3, ra4;  // staging registers of the A chunk (named: arrays ended up in scratch); NSTG of them are live
   // rows past T read as zeros through the descriptor's range check (offset 0xFFFFFFFF); so does every load past the range's end.
@@ -165,7 +168,7 @@ __global__ __launch_bounds__(WM * WN * 64) __attribute__((amdgpu_waves_per_eu(BN
   bool whole = C.ch == 0;
 #define W_FLUSH_CHECK(KCUR)                                                                                            \
   {                                                                                                                    \
-    const bool item_end = C.ch == a.nch - 1;                                                                           \
+    const bool item_end = wcur_item_end(C, a);                                                                         \
     if (item_end || (KCUR) == c_end - 1) {                                                                             \
       const int mb = C.mt * BM;                                                                                        \
       const int cb = C.p * a.Cout + C.nt * BN;                                                                         \
@@ -286,7 +289,7 @@ static int wino_gemm_slots() {
 
 // tile: 5 = 128x256 (8 waves, 64x64 per wave), 4 = 128x128 (8 waves), 6 = 160x128 and 7 = 96x128 (4 waves, every wave a 32-column strip
 // of all the rows: the few-row layers), anything else = 64x64 (4 waves)
-int wino_gemm_plan(WGemmArgs* plan, const float* V, const float* U, float* M, int T, int K, int Cout, int P, int tile) {
+int wino_gemm_plan(WGemmArgs* plan, const float* V, const float* U, float* M, int T, int K, int Cout, int P, int tile, int skip5) {
   if (tile == 5 && Cout % 256 != 0) tile = 4;
   if ((tile < 4 || tile > 7) || Cout % 128 != 0) tile = 3;
   const int BM = tile == 3 ? 64 : tile == 6 ? 160 : tile == 7 ? 96 : 128, BN = tile == 5 ? 256 : tile == 3 ? 64 : 128;
@@ -327,7 +330,10 @@ int wino_gemm_plan(WGemmArgs* plan, const float* V, const float* U, float* M, in
   a.split = g_wino_split && wino_gemm_split_has(tile) && (long)P * K * Cout * 6 < (1L << 31);
   a.U3 = U + (long)P * K * Cout;
   a.u3_bytes = (unsigned)((long)P * K * Cout * 6);
-  if (a.split) a.plane_major = 1;
+  DIM_REQUIRE(!skip5 || (P == 36 && a.nch % 4 == 0), "winograd gemm: skipping zero phase blocks needs 36 planes and K = 4 phases of whole chunks");
+  a.skip5 = skip5;
+  a.q = a.nch / 4;
+  if (a.split || skip5) a.plane_major = 1;
   // never more workgroups than items: every range is then at least one item long and an item is shared by at most two workgroups
   const int slots = a.split ? wino_gemm_split_slots(tile) : tile == 5 ? wino_gemm_slots<128, 256, 2, 4>() : tile == 4 ? wino_gemm_slots<128, 128, 2, 4>()
                   : tile == 6 ? wino_gemm_slots<160, 128, 1, 4>() : tile == 7 ? wino_gemm_slots<96, 128, 1, 4>() : wino_gemm_slots<64, 64, 2, 2>();

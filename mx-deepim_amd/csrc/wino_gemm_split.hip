@@ -103,18 +103,7 @@ __device__ unsigned long long g_split_stamps[1024 * 8 * 11];
 #define S_STAMP(K)
 #endif
 
-__device__ __forceinline__ void wscur_advance(WCur& c, const WGemmArgs& a) {
-  if (++c.ch == a.nch) {
-    c.ch = 0;
-    if (++c.nt == a.NTN) {
-      c.nt = 0;
-      if (++c.mt == a.MT) {
-        c.mt = 0;
-        ++c.p;
-      }
-    }
-  }
-}
+__device__ __forceinline__ void wscur_advance(WCur& c, const WGemmArgs& a) { wcur_advance_pm(c, a); }
 
 template <int BM, int WN>
 __global__ __launch_bounds__(WN * 64) __attribute__((amdgpu_waves_per_eu(2, 2))) void wino_gemm_split_kernel(WGemmArgs a) {
@@ -145,8 +134,10 @@ __global__ __launch_bounds__(WN * 64) __attribute__((amdgpu_waves_per_eu(2, 2)))
   const int khalf = lane >> 5;
 
   const int wg = wg_xcd_contiguous(blockIdx.x, a.G);
-  const int c_begin = wg_first_chunk(wg, a);
-  const int c_end = wg_first_chunk(wg + 1, a);
+  // the range in flat positions; the loop below counts the chunks it multiplies (all of them unless a.skip5)
+  const int r_begin = wg_first_chunk(wg, a);
+  const int c_begin = 0, c_end = wcur_count(r_begin, wg_first_chunk(wg + 1, a), a);
+  if (c_end == 0) return;
 
   const int RS = a.P * a.K;
   const int a_voff0 = (srow * RS + q * 4) * 4;
@@ -156,7 +147,7 @@ __global__ __launch_bounds__(WN * 64) __attribute__((amdgpu_waves_per_eu(2, 2)))
   const __amdgpu_buffer_rsrc_t rm = __builtin_amdgcn_make_buffer_rsrc(a.M, 0, a.m_bytes, 0x00020000);
   const int wchunk_bytes = a.Cout * 192;
 
-  WCur L = wcur_decode(c_begin, a), Bc = L, C = L;
+  WCur L = wcur_decode(r_begin, a), Bc = L, C = L;
 
   // staging registers of TWO chunks: a chunk's V loads are issued two iterations before its split (HBM latency under load is of the
   // order of one iteration of this kernel)
@@ -226,7 +217,7 @@ __global__ __launch_bounds__(WN * 64) __attribute__((amdgpu_waves_per_eu(2, 2)))
   bool whole = C.ch == 0;
 #define S_FLUSH_CHECK(KCUR)                                                                                            \
   {                                                                                                                    \
-    const bool item_end = C.ch == a.nch - 1;                                                                           \
+    const bool item_end = wcur_item_end(C, a);                                                                         \
     if (item_end || (KCUR) == c_end - 1) {                                                                             \
       const int mb = C.mt * BM;                                                                                        \
       const int cb = C.p * a.Cout + C.nt * BN;                                                                         \

@@ -162,12 +162,24 @@ struct WinoVec {
     O[5 * S] = D[1] + 1.5f * D[2] - 2.f * D[3] - 1.5f * D[4] + D[5];                    \
   }
 
+// ---- forward 5x5 / stride-2 layers: the zero blocks of the transformed weights are neither stored in V nor multiplied.
+// For an odd phase (py = 1) the third row of the sub-kernel g is zero, and the last row of G is [0 0 1]: every plane (a, b) with a = 5 of
+// U = G g G^T is exactly zero for that phase; likewise px = 1 and b = 5.  That is 6 + 6 + 11 = 23 of the 144 (phase, plane) blocks:
+//   planes (a, b < 5)   phases 0 1 2 3        planes (5, b < 5)   phases (0,0) (0,1)
+//   planes (a < 5, 5)   phases (0,0) (1,0)    plane  (5, 5)       phase  (0,0)
+// (wino5_phase_mask, common.h).  Layouts and sizes of V, U, U3 and M are unchanged: wino4_input_kernel<VEC, 2, true> leaves the 23 blocks
+// of a tile row unwritten (holes), the plane GEMMs step over their chunks (WGemmArgs::skip5) and U keeps the zeros it always held.
+// The GEMM's ranges are still cut in the flat chunk list of the full K, so every item is split between two workgroups exactly where it
+// was when the zeros were multiplied, and adding or leaving out exact zeros does not change a float sum: results keep their bits.
+// The backward paths (weight gradient: all of V; input gradient: zero structure on the GEMM's N side) do not skip.
+
 // V[t][k][c], k = 6a + b: thread = (tile t, VEC channels).
 // S = 1: a 3x3 / stride-1 / pad-1 layer.  S = 2: a 5x5 / stride-2 / pad-2 layer as the sum of four 3x3 / stride-1 / pad-1
 // convolutions of its phase images X^(py,px)[r][q] = x[2r + py][2q + px] (sub-kernels g[u][v] = w[2u + py][2v + px], zero beyond
 // the 5 taps): the four transformed phase tiles are concatenated along the channels, V has 4C of them (phase-major), so that ONE
 // GEMM per Winograd plane contracts over phases and channels and the output transform is that of the stride-1 layer.
-template <int VEC, int S>
+// FWD5 (S = 2, the forward layer): the blocks that meet zero weights are not stored (predicated stores; the loads are unconditional).
+template <int VEC, int S, bool FWD5 = false>
 __global__ __launch_bounds__(256) void wino4_input_kernel(const float* __restrict__ x, float* __restrict__ V, int N, int H, int W, int C,
                                                           int in_cstride, int th, int tw, FastDiv div_cq, FastDiv div_tw, FastDiv div_th,
                                                           unsigned nblk, WGemmArgs plan) {
@@ -222,7 +234,9 @@ __global__ __launch_bounds__(256) void wino4_input_kernel(const float* __restric
     const vf* d = tmp + 6 * a;
     DIM_WINO4_BT(o, d, 1)
 #pragma unroll
-    for (int b = 0; b < 6; ++b) __builtin_nontemporal_store(o[b], reinterpret_cast<vf*>(out + (a * 6 + b) * plane));
+    for (int b = 0; b < 6; ++b)
+      if (!FWD5 || ((a < 5 || py == 0) && (b < 5 || px == 0)))
+        __builtin_nontemporal_store(o[b], reinterpret_cast<vf*>(out + (a * 6 + b) * plane));
   }
 }
 
@@ -543,7 +557,7 @@ static int winograd_slice(const float* x, const float* w_packed, const float* bi
   }
   if (tile == 0) tile = (Cout % 128 == 0 && T >= 1024) ? 4 : 3;
   WGemmArgs plan;
-  int rc = wino_gemm_plan(&plan, V, w_packed, M, (int)T, CT, Cout, nk, tile);
+  int rc = wino_gemm_plan(&plan, V, w_packed, M, (int)T, CT, Cout, nk, tile, S == 2);
   if (rc != DIM_OK) return rc;
   DIM_WINO_EVENT(0)
   const unsigned nblk = (unsigned)ceil_div(T * (CT / kWino4Vec), 256);
@@ -554,7 +568,7 @@ static int winograd_slice(const float* x, const float* w_packed, const float* bi
     hipLaunchKernelGGL((wino4_input_kernel<kWino4Vec, 1>), dim3(nblk + plan.G - 1), dim3(256), 0, st, x, V, N, H, W, Cin, in_cstride, th, tw,
                        make_fastdiv((unsigned)(CT / kWino4Vec)), dtw, dth, nblk, plan);
   else
-    hipLaunchKernelGGL((wino4_input_kernel<kWino4Vec, 2>), dim3(nblk + plan.G - 1), dim3(256), 0, st, x, V, N, H, W, Cin, in_cstride, th, tw,
+    hipLaunchKernelGGL((wino4_input_kernel<kWino4Vec, 2, true>), dim3(nblk + plan.G - 1), dim3(256), 0, st, x, V, N, H, W, Cin, in_cstride, th, tw,
                        make_fastdiv((unsigned)(CT / kWino4Vec)), dtw, dth, nblk, plan);
   rc = check_launch("winograd_input");
   if (rc != DIM_OK) return rc;

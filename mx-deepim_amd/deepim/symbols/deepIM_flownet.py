@@ -362,10 +362,13 @@ class FlowNetHip(object):
         """accounting of one Winograd layer for bench.py: the batched GEMM (planes x [tiles x K] . [K x cout]) and the algorithmic
         bytes of the two transform kernels (read x + write V; read M + write y)"""
         planes, K = planes or (m + 2) ** 2, cin * S * S
+        # sum of the planes' contraction lengths = K columns of V the input transform stores per tile row.  5x5 / stride 2 (S = 2):
+        # 121 of the 144 (plane, phase) blocks of K / 4 -- the weights of the other 23 are zero by construction (csrc/winograd.hip)
+        pk = 121 * (K // 4) if S == 2 else planes * K
         return dict(winograd=True, wino_m=m, wino_tile=tile, wino_planes=planes, wino_rows=tiles, wino_k=K,
-                    wino_flops=2 * planes * tiles * K * cout, wino_gemm_bytes=4 * planes * (tiles * K + K * cout + tiles * cout),
-                    wino_in_bytes=4 * (x_floats + planes * tiles * K), wino_out_bytes=4 * (planes * tiles * cout + y_floats),
-                    wino_in_kernel="dim::wino_input_kernel" if m == 2 else "dim::wino4_input_kernel<2, %d>" % S,
+                    wino_flops=2 * pk * tiles * cout, wino_gemm_bytes=4 * (tiles * pk + pk * cout + planes * tiles * cout),
+                    wino_in_bytes=4 * (x_floats + tiles * pk), wino_out_bytes=4 * (planes * tiles * cout + y_floats),
+                    wino_in_kernel="dim::wino_input_kernel" if m == 2 else "dim::wino4_input_kernel<2, %d, %s>" % (S, "true" if S == 2 else "false"),
                     wino_out_kernel="dim::wino_output_kernel" if m == 2 else "dim::wino4_output_kernel<2>")
 
     # ---- pieces -------------------------------------------------------------------------------
