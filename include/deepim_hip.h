@@ -678,6 +678,25 @@ int dim_pm_l1_grad(const float* p_est, const float* p_obs, const float* weights,
  * scalar = SE3_PM_SL1_SCALAR)   (deepIM_flownet.py:458-499) */
 int dim_pm_loss_grad(const float* p_est, const float* p_obs, const float* weights, float* grad, long n, float norm_term, float grad_scale,
                      int loss_type, float smooth_l1_scalar, float* loss_sum, void* stream);
+/* The point-matching loss against the closest of the symmetric ground truths (train_iter.SE3_PM_SYM).  p_est, points_model, weights:
+ * (B,3,N) float32; tgt_pose (B,3,4) float32; sym (Stot,3,4) float32 and sym_off (n_classes+1) int32: the classes' symmetry sets [Rs | ts],
+ * identity first (lib/utils/symmetry.py symmetry_tables), class c owning entries sym_off[c] .. sym_off[c+1]-1 (an empty range = the
+ * identity alone); class_index (B) int32.  Per pair, with f the element loss of loss_type:
+ *   G_s = [R_g Rs | R_g ts + t_g] (float64), target_s = float32(G_s x), L_s = sum over points and coordinates of w f((p_est - target_s) / norm_term)
+ *   s* = the first s with the least L_s (a later s replaces only with a strictly smaller, finite sum; a NaN L_0 stays)
+ *   grad = grad_scale w f'((p_est - target_s*) / norm_term) / norm_term, bit for bit dim_pm_loss_grad's for (p_est, target_out, weights);
+ *   target_out (B,3,N, may be NULL) = target_s*; best_sym[b] (may be NULL) = s*; *loss_sum (may be NULL) += L_s*, one add per pair.
+ * With the identity alone target_out is bit for bit dim_point_clouds' point_cloud_observed for the same pose and points.
+ * A class index outside [0, n_classes), or a class with more than max_sym entries, gives the pair a zero gradient (and target_out),
+ * best_sym -1, no loss contribution, and ORs DIM_STATUS_BAD_CLASS into status[b] (B int32, may be NULL).
+ * workspace: dim_pm_sym_workspace_bytes(B, n_points, max_sym) bytes, 4-byte aligned, no initialisation needed.  max_sym <= 4096.
+ * Two launches, no allocation or synchronisation (graph-capturable); no atomics in L_s and a summation order that depends on
+ * n_points alone: best_sym and grad repeat bit for bit. */
+long dim_pm_sym_workspace_bytes(int B, int n_points, int max_sym);
+int dim_pm_sym_loss_grad(const float* p_est, const float* points_model, const float* weights, const float* tgt_pose, const float* sym,
+                         const int* sym_off, int n_classes, const int* class_index, int B, int n_points, int max_sym, float norm_term,
+                         float grad_scale, int loss_type, float smooth_l1_scalar, void* workspace, float* grad, float* target_out,
+                         int* best_sym, float* loss_sum, int* status, void* stream);
 /* SE3_DIST_LOSS (deepIM_flownet.py:396-437): rot_loss = 1 - (rot_gt . rot_est_norm)^2 with grad_scale LW_ROT and trans_loss =
  * TRANS_LOSS_TYPE(zoom_trans_est - zoom_trans_gt) with grad_scale LW_TRANS; zoom_trans_est = trans_w fc7 + trans_b is recomputed from
  * fc7 (B,256).  The gradients are ADDED to d_rot_norm (B,4) / d_zoom_trans (B,3), the inputs of dim_pose_head_bwd; loss_sums2 (2

@@ -135,6 +135,188 @@ __global__ __launch_bounds__(256) void pm_loss_grad_kernel(const float* __restri
   }
 }
 
+// ---- symmetry-aware point matching: the loss against the closest of the symmetric ground truths (dim_pm_sym_loss_grad)
+//   G_s = [R_g Rs | R_g ts + t_g]   target_s = G_s x   L_s = sum_{i,k} w f((p_est - target_s) / norm)   s* = the first s with the least L_s
+//   pm_sym_sums_kernel    grid (point tiles, symmetry chunks, B).  A workgroup owns kPmSymTile points of its pair and kPmSymChunk
+//                         symmetries: it composes their G_s once into LDS (float64: a product of two floats is exact there, so with the
+//                         identity G_0 is tgt_pose itself), then every lane loads a point's 9 floats ONCE and walks the chunk with
+//                         one register accumulator per symmetry.  Lanes -> waves -> workgroup in a fixed order; the workgroup's sums
+//                         go to workspace[b][tile][s] with plain stores.
+//   pm_sym_grad_kernel    grid (ceil(N / 256), B).  Every workgroup of a pair adds the tiles in tile order, finds s* (the same bits in
+//                         each of them), composes G_{s*} again and writes target_out / grad for its 256 points with the expressions of
+//                         pm_loss_grad_kernel; workgroup 0 of the pair writes best_sym and adds L_{s*} to loss_sum.
+// Which lane and which workgroup sums a point is a function of n_points alone and nothing in L_s is atomic, so L_s, s* and grad are the
+// same bits on every call.  Nothing allocates or synchronises; the workspace needs no initialisation.
+constexpr int kPmSymThreads = 256;
+constexpr int kPmSymWaves = kPmSymThreads / kWave;
+constexpr int kPmSymPPL = 2;                             // points per lane and workgroup
+constexpr int kPmSymTile = kPmSymThreads * kPmSymPPL;    // points per workgroup
+constexpr int kPmSymChunk = 16;                          // symmetries per workgroup: 16 accumulators, 1.5 KB of matrices
+constexpr int kPmSymMax = 4096;
+
+// class of pair b -> first entry and size of its symmetry set; soff -1 = the identity alone (an empty range).  false: a class index
+// outside the table or a set larger than max_sym (zero gradient, best_sym -1, DIM_STATUS_BAD_CLASS)
+__device__ __forceinline__ bool pm_sym_class(const int* __restrict__ sym_off, int n_classes, int max_sym, int cls, int& soff, int& ns) {
+  soff = -1;
+  ns = 1;
+  if (cls < 0 || cls >= n_classes) return false;
+  const int o = sym_off[cls], n = sym_off[cls + 1] - o;
+  if (n <= 0) return true;
+  if (o < 0 || n > max_sym) return false;
+  soff = o;
+  ns = n;
+  return true;
+}
+
+// entry k = 4 r + col of G = pose . S (S NULL: the identity, G = pose).  Products of two floats are exact in float64, so a listed
+// identity gives the pose's entries back (a -0 entry as +0: the same target unless a whole coordinate sums to zero)
+__device__ __forceinline__ double pm_sym_compose(const float* __restrict__ Pg, const float* __restrict__ S, int k) {
+  if (!S) return (double)Pg[k];
+  const int r = k >> 2, col = k & 3;
+  const float* g = Pg + 4 * r;
+  double v = ((double)g[0] * (double)S[col] + (double)g[1] * (double)S[4 + col]) + (double)g[2] * (double)S[8 + col];
+  if (col == 3) v += (double)g[3];
+  return v;
+}
+
+// one coordinate of G x, rounded to float32 once: ((G0 x + G1 y) + G2 z) + G3, the order of point_clouds_kernel (data.hip) -- with
+// G = a float32 pose every product is exact and the result is that kernel's bit for bit.  The multiply-adds are spelled out so that
+// both passes round alike.
+__device__ __forceinline__ float pm_sym_target(const double* G4, float x, float y, float z) {
+  return (float)(fma(G4[2], (double)z, fma(G4[1], (double)y, G4[0] * (double)x)) + G4[3]);
+}
+
+__global__ __launch_bounds__(kPmSymThreads) void pm_sym_sums_kernel(const float* __restrict__ p_est, const float* __restrict__ pts,
+                                                                    const float* __restrict__ wgt, const float* __restrict__ tgt_pose,
+                                                                    const float* __restrict__ sym, const int* __restrict__ sym_off,
+                                                                    int n_classes, const int* __restrict__ class_index, int N, int max_sym,
+                                                                    float inv_norm, int type, float sl1, float* __restrict__ partial) {
+  __shared__ double G[kPmSymChunk][12];
+  __shared__ float red[kPmSymChunk][kPmSymWaves];
+  const int tile = blockIdx.x, s0 = blockIdx.y * kPmSymChunk, b = blockIdx.z, tid = threadIdx.x;
+  int soff, ns;
+  if (!pm_sym_class(sym_off, n_classes, max_sym, class_index[b], soff, ns) || s0 >= ns) return;   // workgroup-uniform
+  const int m = min(kPmSymChunk, ns - s0);
+  for (int e = tid; e < m * 12; e += kPmSymThreads) {
+    const int s = e / 12, k = e - 12 * s;
+    G[s][k] = pm_sym_compose(tgt_pose + 12L * b, soff < 0 ? nullptr : sym + 12L * (soff + s0 + s), k);
+  }
+  __syncthreads();
+  float acc[kPmSymChunk];
+#pragma unroll
+  for (int s = 0; s < kPmSymChunk; ++s) acc[s] = 0.f;
+  const long base = (long)b * 3 * N;
+#pragma unroll
+  for (int q = 0; q < kPmSymPPL; ++q) {
+    const int j = tile * kPmSymTile + q * kPmSymThreads + tid;
+    if (j < N) {
+      float x[3], pe[3], w[3];
+#pragma unroll
+      for (int r = 0; r < 3; ++r) {
+        const long i = base + (long)r * N + j;
+        x[r] = pts[i]; pe[r] = p_est[i]; w[r] = wgt[i];
+      }
+#pragma unroll
+      for (int s = 0; s < kPmSymChunk; ++s) {
+        if (s < m) {   // wave-uniform
+#pragma unroll
+          for (int r = 0; r < 3; ++r) {
+            float df;
+            const float v = elem_loss(type, (pe[r] - pm_sym_target(G[s] + 4 * r, x[0], x[1], x[2])) * inv_norm, sl1, &df);
+            acc[s] = fmaf(w[r], v, acc[s]);
+          }
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int s = 0; s < kPmSymChunk; ++s) {
+    if (s < m) {
+      float v = acc[s];
+      for (int off = kWave / 2; off > 0; off >>= 1) v += __shfl_down(v, off, kWave);
+      if ((tid & (kWave - 1)) == 0) red[s][tid / kWave] = v;
+    }
+  }
+  __syncthreads();
+  if (tid < m) partial[((long)b * gridDim.x + tile) * max_sym + s0 + tid] = (red[tid][0] + red[tid][1]) + (red[tid][2] + red[tid][3]);
+}
+
+// does candidate a replace b: index INT_MAX = no candidate; the smaller sum, equal sums to the smaller index
+__device__ __forceinline__ bool pm_sym_better(float av, int ai, float bv, int bi) {
+  return ai != INT_MAX && (bi == INT_MAX || av < bv || (av == bv && ai < bi));
+}
+
+__global__ __launch_bounds__(kPmSymThreads) void pm_sym_grad_kernel(const float* __restrict__ p_est, const float* __restrict__ pts,
+                                                                    const float* __restrict__ wgt, const float* __restrict__ tgt_pose,
+                                                                    const float* __restrict__ sym, const int* __restrict__ sym_off,
+                                                                    int n_classes, const int* __restrict__ class_index, int N, int max_sym,
+                                                                    int ntiles, float inv_norm, float gs, int type, float sl1,
+                                                                    const float* __restrict__ partial, float* __restrict__ grad,
+                                                                    float* __restrict__ target_out, int* __restrict__ best_sym,
+                                                                    float* __restrict__ loss_sum, int* __restrict__ status) {
+  __shared__ float red_v[kPmSymWaves];
+  __shared__ int red_i[kPmSymWaves];
+  const int b = blockIdx.y, tid = threadIdx.x, j = blockIdx.x * kPmSymThreads + tid;
+  const long base = (long)b * 3 * N;
+  int soff, ns;
+  if (!pm_sym_class(sym_off, n_classes, max_sym, class_index[b], soff, ns)) {   // workgroup-uniform
+    if (j < N) {
+#pragma unroll
+      for (int r = 0; r < 3; ++r) {
+        grad[base + (long)r * N + j] = 0.f;
+        if (target_out) target_out[base + (long)r * N + j] = 0.f;
+      }
+    }
+    if (blockIdx.x == 0 && tid == 0) {   // one lane per pair touches best_sym[b] and status[b]
+      if (best_sym) best_sym[b] = -1;
+      if (status) status[b] |= DIM_STATUS_BAD_CLASS;
+    }
+    return;
+  }
+  // L_s = the tiles' sums in tile order.  Candidates: s = 0 always, s >= 1 with a finite sum; a lane meets its s in rising order
+  const float* p = partial + (long)b * ntiles * max_sym;
+  float L0 = p[0];
+  for (int t = 1; t < ntiles; ++t) L0 += p[(long)t * max_sym];
+  float bv = L0;
+  int bi = tid == 0 ? 0 : INT_MAX;
+  for (int s = tid == 0 ? kPmSymThreads : tid; s < ns; s += kPmSymThreads) {
+    float v = p[s];
+    for (int t = 1; t < ntiles; ++t) v += p[(long)t * max_sym + s];
+    if (isfinite(v) && pm_sym_better(v, s, bv, bi)) { bv = v; bi = s; }
+  }
+  for (int off = kWave / 2; off > 0; off >>= 1) {
+    const float ov = __shfl_xor(bv, off, kWave);
+    const int oi = __shfl_xor(bi, off, kWave);
+    if (pm_sym_better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
+  }
+  if ((tid & (kWave - 1)) == 0) { red_v[tid / kWave] = bv; red_i[tid / kWave] = bi; }
+  __syncthreads();
+  bv = red_v[0]; bi = red_i[0];
+#pragma unroll
+  for (int w = 1; w < kPmSymWaves; ++w)
+    if (pm_sym_better(red_v[w], red_i[w], bv, bi)) { bv = red_v[w]; bi = red_i[w]; }
+  if (L0 != L0) { bv = L0; bi = 0; }   // a NaN L_0 stays: no comparison with it holds
+  double Gs[12];
+#pragma unroll
+  for (int k = 0; k < 12; ++k) Gs[k] = pm_sym_compose(tgt_pose + 12L * b, soff < 0 ? nullptr : sym + 12L * (soff + bi), k);
+  if (j < N) {
+    const float x = pts[base + j], y = pts[base + N + j], z = pts[base + 2L * N + j];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+      const long i = base + (long)r * N + j;
+      const float t = pm_sym_target(Gs + 4 * r, x, y, z);
+      if (target_out) target_out[i] = t;
+      float df;
+      elem_loss(type, (p_est[i] - t) * inv_norm, sl1, &df);
+      grad[i] = gs * wgt[i] * df * inv_norm;   // pm_loss_grad_kernel's expression: the same bits for the same target
+    }
+  }
+  if (blockIdx.x == 0 && tid == 0) {
+    if (best_sym) best_sym[b] = bi;
+    if (loss_sum) atomicAdd(loss_sum, bv);   // one add per pair
+  }
+}
+
 // SE3_DIST_LOSS (deepIM_flownet.py:396-437), one thread per sample:
 //   rot_loss   = 1 - (rot_gt . rot_est_norm)^2                      d / d rot_est_norm = -2 (rot_gt . rot_est_norm) rot_gt
 //   trans_loss = f(zoom_trans_est - zoom_trans_gt)  (3 values)      zoom_trans_est = the raw output of the `trans` layer, recomputed
@@ -720,6 +902,38 @@ int dim_pm_loss_grad(const float* p_est, const float* p_obs, const float* weight
   hipLaunchKernelGGL(pm_loss_grad_kernel, dim3((unsigned)(pm_wgs < 128 ? pm_wgs : 128)), dim3(256), 0, as_stream(stream), p_est, p_obs, weights, grad, n,
                      1.0f / norm_term, grad_scale, loss_type, smooth_l1_scalar, loss_sum);
   return check_launch("pm_loss_grad");
+}
+
+long dim_pm_sym_workspace_bytes(int B, int n_points, int max_sym) {
+  if (B <= 0 || n_points <= 0 || max_sym <= 0) return 0;
+  return (long)B * ceil_div(n_points, kPmSymTile) * max_sym * (long)sizeof(float);
+}
+
+int dim_pm_sym_loss_grad(const float* p_est, const float* points_model, const float* weights, const float* tgt_pose, const float* sym,
+                         const int* sym_off, int n_classes, const int* class_index, int B, int n_points, int max_sym, float norm_term,
+                         float grad_scale, int loss_type, float smooth_l1_scalar, void* workspace, float* grad, float* target_out,
+                         int* best_sym, float* loss_sum, int* status, void* stream) {
+  DIM_REQUIRE(B >= 1 && B <= 65535, "pm_sym_loss_grad: B = %d (1 .. 65535)", B);
+  DIM_REQUIRE(n_points >= 1, "pm_sym_loss_grad: n_points = %d (>= 1)", n_points);
+  DIM_REQUIRE(max_sym >= 1 && max_sym <= kPmSymMax, "pm_sym_loss_grad: max_sym = %d (1 .. %d)", max_sym, kPmSymMax);
+  DIM_REQUIRE(n_classes >= 1, "pm_sym_loss_grad: n_classes = %d (>= 1)", n_classes);
+  DIM_REQUIRE(loss_type >= 0 && loss_type <= 2 && (loss_type != 2 || smooth_l1_scalar > 0.f),
+              "pm_sym_loss_grad: loss_type 0 L1 | 1 L2 | 2 smooth_L1 (smooth_l1_scalar > 0)");
+  DIM_REQUIRE(norm_term > 0.f, "pm_sym_loss_grad: norm_term must be > 0");
+  DIM_REQUIRE(p_est && points_model && weights && tgt_pose && sym && sym_off && class_index && workspace && grad,
+              "pm_sym_loss_grad: null pointer (p_est, points_model, weights, tgt_pose, sym, sym_off, class_index, workspace, grad)");
+  DIM_REQUIRE(((uintptr_t)workspace % 4) == 0, "pm_sym_loss_grad: workspace must be 4-byte aligned");
+  const int ntiles = ceil_div(n_points, kPmSymTile);
+  const float inv_norm = 1.0f / norm_term;
+  float* partial = (float*)workspace;
+  hipStream_t st = as_stream(stream);
+  hipLaunchKernelGGL(pm_sym_sums_kernel, dim3(ntiles, ceil_div(max_sym, kPmSymChunk), B), dim3(kPmSymThreads), 0, st, p_est, points_model,
+                     weights, tgt_pose, sym, sym_off, n_classes, class_index, n_points, max_sym, inv_norm, loss_type, smooth_l1_scalar,
+                     partial);
+  hipLaunchKernelGGL(pm_sym_grad_kernel, dim3(ceil_div(n_points, kPmSymThreads), B), dim3(kPmSymThreads), 0, st, p_est, points_model, weights,
+                     tgt_pose, sym, sym_off, n_classes, class_index, n_points, max_sym, ntiles, inv_norm, grad_scale, loss_type,
+                     smooth_l1_scalar, (const float*)partial, grad, target_out, best_sym, loss_sum, status);
+  return check_launch("pm_sym_loss_grad");
 }
 
 int dim_se3_dist_loss_grad(const float* rot_est_norm, const float* rot_gt, const float* fc7, const float* trans_w, const float* trans_b,

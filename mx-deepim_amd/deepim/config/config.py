@@ -59,6 +59,9 @@ def _defaults():
         pose_file="./data/ModelNet/render_v1/poses.txt", DEPTH_FACTOR=1000, NORMALIZE_FLOW=1.0, NORMALIZE_3D_POINT=0.1,
         INTRINSIC_MATRIX=np.array([[572.4114, 0, 325.2611], [0, 573.57043, 242.04899], [0, 0, 1]]), ZNEAR=0.25, ZFAR=6.0,
         class_name_file="", class_name=[], trans_means=np.array([0.0, 0.0, 0.0]), trans_stds=np.array([1.0, 1.0, 1.0]),
+        # class name -> its BOP model_info dict (symmetries_discrete / symmetries_continuous, lib/utils/symmetry.py), translations and
+        # offsets in the unit of the model points; read by train_iter.SE3_PM_SYM
+        SYMMETRIES={},
         # synthetic training pairs (lib/dataset/synthetic_pairs.py): occluding objects per pair, the share of the target that may be
         # hidden (toolkit/LM6d_occ_dsm_3_remove_low_visible.py), LINEMOD light model (toolkit/LM6d_occ_dsm_1_gen_observed_light.py)
         SYN_OCC_OBJECTS=0, SYN_OCC_MAX_RATE=0.85, SYN_LIGHT=False)
@@ -90,7 +93,11 @@ def _defaults():
                    BOP_MSPD_THRESH=[5 * k for k in range(1, 11)])
     c.train_iter = edict(SE3_DIST_LOSS=False, LW_ROT=0.0, LW_TRANS=0.0, TRANS_LOSS_TYPE="L2", TRANS_SMOOTH_L1_SCALAR=3.0,
                          SE3_PM_LOSS=False, LW_PM=0.0, SE3_PM_LOSS_TYPE="L1", SE3_PM_SL1_SCALAR=1.0, NUM_3D_SAMPLE=-1, LW_FLOW=0.0,
-                         LW_MASK=0.0)
+                         LW_MASK=0.0,
+                         # the point-matching loss against the closest of the class's symmetric ground truths (dim_pm_sym_loss_grad;
+                         # needs SE3_PM_LOSS) and the discretisation step of continuous symmetries in radians: ceil(pi / 0.1) = 32
+                         # rotations per axis (BOP's evaluation step of 0.01 gives 315)
+                         SE3_PM_SYM=False, SE3_PM_SYM_STEP=0.1)
     return c
 
 

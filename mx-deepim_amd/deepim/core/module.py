@@ -39,14 +39,16 @@ BUCKET_ENDS = ("fc6_weight", "conv5_weight")
 
 
 class MutableModule(object):
-    def __init__(self, config, arg_params, batch_size, device="cuda:0", process_group=None, compute_dtype="f32", overlap_allreduce=True):
+    def __init__(self, config, arg_params, batch_size, device="cuda:0", process_group=None, compute_dtype="f32", overlap_allreduce=True,
+                 symmetries=None):
         """compute_dtype "f32": the reference's precision (deepim/train.py:338-414 trains in fp32).
         "bf16": BASELINE configs[2] -- every convolution / large deconvolution forward, input gradient and weight gradient on the bf16
         matrix pipe with f32 accumulation; master weights, momentum, gradients, losses, SE(3) and every small kernel stay fp32; the
         gradient bucket crosses the ranks as bf16 (115.5 MB instead of 231 MB).  New functionality with a declared tolerance against
         the fp32 path (tests/test_gpu_bf16.py, tests/test_gpu_train_bf16.py).
         overlap_allreduce: hand the gradient to the collective in three buckets while backward is still running (see BACKWARD_ORDER);
-        False = one all-reduce of the whole vector inside update(), the first version.  Same sums either way."""
+        False = one all-reduce of the whole vector inside update(), the first version.  Same sums either way.
+        symmetries: {class name: BOP model_info dict or (S,3,4) set} for train_iter.SE3_PM_SYM, in place of cfg.dataset.SYMMETRIES."""
         cfg = config
         assert compute_dtype in ("f32", "bf16"), compute_dtype
         self.bf16 = compute_dtype == "bf16"
@@ -58,6 +60,9 @@ class MutableModule(object):
         for what, kind in (("SE3_PM_LOSS_TYPE", cfg.train_iter.SE3_PM_LOSS_TYPE), ("TRANS_LOSS_TYPE", cfg.train_iter.TRANS_LOSS_TYPE)):
             if kind not in ops.LOSS_TYPE_ID:   # the reference raises for anything else too (deepIM_flownet.py:427-431, :486-491)
                 raise Exception("Unknown {}: {}".format(what, kind))
+        self.pm_sym = bool(cfg.train_iter.get("SE3_PM_SYM", False))
+        if self.pm_sym and not cfg.train_iter.SE3_PM_LOSS:
+            raise Exception("train_iter.SE3_PM_SYM chooses the target of the point-matching loss: it needs train_iter.SE3_PM_LOSS")
         self.cfg = cfg
         self.B = batch_size
         self.device = torch.device(device)
@@ -119,6 +124,9 @@ class MutableModule(object):
         self._next_bucket = 0
         self._init_forward(cfg, batch_size)
         self._init_backward(batch_size)
+        self.pm_best_sym = None
+        if self.pm_sym:
+            self._init_pm_sym(symmetries, batch_size)
         self.num_update = 0
 
     # ------------------------------------------------------------------------------------------------------------
@@ -141,6 +149,25 @@ class MutableModule(object):
         self.loss_sums = torch.zeros(5, dtype=torch.float32, device=d)  # flow, pm, -, rot, trans (un-scaled sums; metrics only)
         self.T_means = np.asarray(cfg.dataset.trans_means, dtype=np.float32)
         self.T_stds = np.asarray(cfg.dataset.trans_stds, dtype=np.float32)
+
+    def _init_pm_sym(self, symmetries, B):
+        """the classes' symmetry sets as one float32 device table (built once), the kernel's workspace and the chosen indices"""
+        from lib.utils.symmetry import symmetry_tables
+
+        cfg, d = self.cfg, self.device
+        if symmetries is None:
+            symmetries = dict(cfg.dataset.get("SYMMETRIES", {}))
+        classes = list(cfg.dataset.class_name)
+        unknown = sorted(set(symmetries) - set(classes))
+        if unknown:
+            raise Exception("symmetries given for {} which dataset.class_name {} does not list".format(unknown, classes))
+        sym, sym_off, self.pm_max_sym = symmetry_tables(classes, symmetries, float(cfg.train_iter.SE3_PM_SYM_STEP))
+        if self.pm_max_sym > ops.PM_SYM_MAX:
+            raise Exception("a class has {} symmetries, more than {}: raise train_iter.SE3_PM_SYM_STEP".format(self.pm_max_sym, ops.PM_SYM_MAX))
+        self.pm_sym_table = torch.as_tensor(sym.astype(np.float32), device=d)
+        self.pm_sym_off = torch.as_tensor(sym_off, device=d)
+        self.pm_best_sym = torch.zeros((B,), dtype=torch.int32, device=d)
+        self.pm_sym_ws = ops.pm_sym_workspace(B, int(cfg.train_iter.NUM_3D_SAMPLE), self.pm_max_sym, d)
 
     def _init_backward(self, B):
         d, net = self.device, self.net
@@ -343,9 +370,15 @@ class MutableModule(object):
         if ti.SE3_PM_LOSS:   # point matching (:440-499): L1 / L2 / smooth_L1 on (Transform3D(model points) - observed points) / norm
             if self.dpts is None:
                 self.dpts = torch.empty_like(self.pts_est)
-            ops.pm_loss_grad(self.pts_est, batch["point_cloud_observed"], batch["point_cloud_weights"], self.dpts,
-                             cfg.dataset.NORMALIZE_3D_POINT, ti.LW_PM / float(ti.NUM_3D_SAMPLE), ti.SE3_PM_LOSS_TYPE, ti.SE3_PM_SL1_SCALAR,
-                             loss_sum=self.loss_sums[1:2])
+            if self.pm_sym:   # against the closest of the class's symmetric ground truths; point_cloud_observed is not read
+                ops.pm_sym_loss_grad(self.pts_est, batch["point_cloud_model"], batch["point_cloud_weights"], batch["tgt_pose"],
+                                     self.pm_sym_table, self.pm_sym_off, batch["class_index"], self.dpts, cfg.dataset.NORMALIZE_3D_POINT,
+                                     ti.LW_PM / float(ti.NUM_3D_SAMPLE), self.pm_max_sym, ti.SE3_PM_LOSS_TYPE, ti.SE3_PM_SL1_SCALAR,
+                                     loss_sum=self.loss_sums[1:2], best_sym=self.pm_best_sym, workspace=self.pm_sym_ws)
+            else:
+                ops.pm_loss_grad(self.pts_est, batch["point_cloud_observed"], batch["point_cloud_weights"], self.dpts,
+                                 cfg.dataset.NORMALIZE_3D_POINT, ti.LW_PM / float(ti.NUM_3D_SAMPLE), ti.SE3_PM_LOSS_TYPE,
+                                 ti.SE3_PM_SL1_SCALAR, loss_sum=self.loss_sums[1:2])
             d_rn, d_t = ops.transform3d_bwd(self.dpts, batch["point_cloud_model"], self.rot_norm, self.trans_est, batch["src_pose"],
                                             cfg.network.ROT_COORD, self.T_means, self.T_stds)
         else:
@@ -596,6 +629,8 @@ class MutableModule(object):
     def forward_backward(self, batch):
         out = self.forward(batch)
         self.backward(batch)
+        if self.pm_sym:
+            out["pm_best_sym"] = self.pm_best_sym   # (B,) int32: the symmetry of the class's set that the point-matching loss chose
         return out
 
     # ------------------------------------------------------------------------------------------------------------

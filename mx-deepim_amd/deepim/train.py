@@ -87,7 +87,8 @@ def train_net(args):
     # DIM_TRAIN_DTYPE=bf16: convolutions on the bf16 matrix pipe (BASELINE configs[2]); DIM_OVERLAP_ALLREDUCE=0: one flat all-reduce
     # inside update() instead of three buckets overlapped with backward (same sums: tests/test_gpu_entry_points.py)
     mod = MutableModule(config, arg_params, B, device=device, compute_dtype=os.environ.get("DIM_TRAIN_DTYPE", "f32"),
-                        overlap_allreduce=os.environ.get("DIM_OVERLAP_ALLREDUCE", "1") != "0")
+                        overlap_allreduce=os.environ.get("DIM_OVERLAP_ALLREDUCE", "1") != "0",
+                        symmetries=dict(config.dataset.SYMMETRIES))   # read when train_iter.SE3_PM_SYM is on
     states = "%s-%04d.states.npz" % (prefix, begin_epoch)
     if config.TRAIN.RESUME and os.path.exists(states):
         mod.load_optimizer_states(states)

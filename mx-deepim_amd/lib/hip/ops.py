@@ -1198,6 +1198,42 @@ def pm_loss_grad(p_est, p_obs, weights, grad, norm_term, grad_scale, loss_type="
     return grad
 
 
+PM_SYM_MAX = 4096   # dim_pm_sym_loss_grad's largest symmetry set
+
+
+def pm_sym_workspace(B, n_points, max_sym, device):
+    return torch.empty((max(lib().dim_pm_sym_workspace_bytes(B, n_points, max_sym), 4) // 4,), dtype=f32, device=device)
+
+
+def pm_sym_loss_grad(p_est, points_model, weights, tgt_pose, sym, sym_off, class_index, grad, norm_term, grad_scale, max_sym, loss_type="L1",
+                     smooth_l1_scalar=1.0, loss_sum=None, target_out=None, best_sym=None, status=None, workspace=None):
+    """dim_pm_sym_loss_grad: the point-matching loss gradient against the closest of the symmetric ground truths.  p_est,
+    points_model, weights, grad (and target_out when given) (B,3,N) f32, tgt_pose (B,3,4) f32, sym (Stot,3,4) f32 and sym_off
+    (n_classes+1,) int32 as lib.utils.symmetry.symmetry_tables builds them, class_index (B,) int32.  max_sym: at least the largest set
+    of a class that occurs (a larger set gives the pair a zero gradient, best_sym -1 and DIM_STATUS_BAD_CLASS in status (B,) int32);
+    it sizes the workspace.  loss_sum (1,) f32 accumulates the loss of the chosen symmetry, best_sym (B,) int32 receives its index
+    within the class's set.  -> grad"""
+    if loss_type not in LOSS_TYPE_ID:
+        raise ValueError("pm_sym_loss_grad: loss_type must be one of {}, got {!r}".format(sorted(LOSS_TYPE_ID), loss_type))
+    B, three, N = p_est.shape
+    n_classes = sym_off.numel() - 1
+    max_sym = int(max_sym)
+    assert three == 3 and tuple(points_model.shape) == (B, 3, N) and tuple(weights.shape) == (B, 3, N) and tuple(grad.shape) == (B, 3, N)
+    assert tuple(tgt_pose.shape) == (B, 3, 4) and class_index.numel() == B and n_classes >= 1
+    assert sym.dim() == 3 and tuple(sym.shape[1:]) == (3, 4)
+    assert target_out is None or tuple(target_out.shape) == (B, 3, N)
+    assert (best_sym is None or best_sym.numel() == B) and (status is None or status.numel() == B)
+    assert loss_sum is None or loss_sum.numel() == 1
+    if workspace is None:
+        workspace = pm_sym_workspace(B, N, max_sym, p_est.device)
+    assert not 1 <= max_sym <= PM_SYM_MAX or workspace.numel() * workspace.element_size() >= lib().dim_pm_sym_workspace_bytes(B, N, max_sym)
+    check(lib().dim_pm_sym_loss_grad(dptr(p_est, f32), dptr(points_model, f32), dptr(weights, f32), dptr(tgt_pose, f32), dptr(sym, f32),
+                                     dptr(sym_off, i32), n_classes, dptr(class_index, i32), B, N, max_sym, float(norm_term),
+                                     float(grad_scale), LOSS_TYPE_ID[loss_type], float(smooth_l1_scalar), dptr(workspace), dptr(grad, f32),
+                                     _opt(target_out), _opt(best_sym, i32), _opt(loss_sum), _opt(status, i32), current_stream()))
+    return grad
+
+
 def se3_dist_loss_grad(rot_est_norm, rot_gt, fc7, p, zoom_trans_gt, d_rot_norm, d_zoom_trans, lw_rot, lw_trans, trans_loss_type="L2",
                        smooth_l1_scalar=3.0, loss_sums2=None):
     """SE3_DIST_LOSS (deepIM_flownet.py:396-437): adds the rot / trans loss gradients to d_rot_norm (B,4) / d_zoom_trans (B,3)"""

@@ -51,6 +51,23 @@ def get_symmetry_transformations(model_info, max_sym_disc_step=0.01):
     return np.ascontiguousarray(np.stack(out))
 
 
+def symmetry_tables(classes, symmetries, max_sym_disc_step=0.01):
+    """the symmetry sets of `classes` (names, in the order that numbers class_index) concatenated, as dim_pm_sym_loss_grad and
+    dim_bop_errors read them.  symmetries: {class name: a model_info dict or a ready (S,3,4) set}; a class without an entry gets the
+    identity.  -> sym (Stot,3,4) float64, sym_off (n_classes+1,) int32 (class c owns sym[sym_off[c]:sym_off[c+1]], identity first),
+    max_sym = the size of the largest set"""
+    symmetries = symmetries or {}
+    sets = [as_symmetry_set(symmetries.get(c), max_sym_disc_step) for c in classes]
+    if not sets:
+        raise ValueError("symmetry_tables: no classes")
+    for c, s in zip(classes, sets):
+        if not np.array_equal(s[0], np.eye(4)[:3]):
+            raise ValueError("symmetry_tables: the set of class {!r} must start with the identity".format(c))
+    sym_off = np.zeros(len(sets) + 1, dtype=np.int32)
+    sym_off[1:] = np.cumsum([s.shape[0] for s in sets])
+    return np.ascontiguousarray(np.concatenate(sets)), sym_off, int(max(s.shape[0] for s in sets))
+
+
 def as_symmetry_set(entry, max_sym_disc_step=0.01):
     """a model_info dict or a ready (S,3,4) array -> (S,3,4) float64"""
     if entry is None or isinstance(entry, dict):
