@@ -282,6 +282,26 @@ int dim_vsd_errors(const float* depth_obs, const float* depth_gt, const float* d
                    const double* K_per_sample_f64, const int* bbox_gt, const int* bbox_est, int T, int B, int H, int W, float delta,
                    const double* taus, int n_tau, int cost_type, void* workspace, double* errors, int* counts, void* stream);
 
+/* The step cost on BOP's grid: up to DIM_VSD_GRID_MAX_TAU taus per pair, read from the row of the pair's class in a device table
+ * (BOP: ten fractions of the class diameter), scored from one read of the planes.  Planes, cameras, boxes, the visibility rule,
+ * c = |S_gt - S_est| and counts (T,B,4) are those of dim_vsd_errors.
+ *   class_index (B) int32 device; tau_table (n_classes, n_tau) float64 device, metres: the products are made on the host, the device
+ *   only compares.  n_ge (T,B,n_tau) int32 = the pixels of the intersection with c >= tau_table[class_index[b]][k];
+ *   errors (T,B,n_tau) float64 = ((double)n_ge + (double)(|union| - |inter|)) / (double)|union|, one division, and 1 when the union is
+ *   empty: the bits of lib/utils/pose_error.py vsd(..., "step").
+ * A class index outside [0, n_classes) gives its rows NaN errors, zero counts and zero n_ge and touches nothing else.
+ * workspace: dim_vsd_grid_workspace_bytes(T, B) bytes, 8-byte aligned, no initialisation needed.  Every sum is int32 (H W < 2^31):
+ * wave shuffles, LDS across waves, a finish kernel across workgroups that reads only what this call wrote; no atomics and no float
+ * sum, so the result does not depend on how the pixels are dealt out.  2 launches, nothing allocated, no synchronisation.  T or B
+ * outside [1, 65535], H or W <= 0, n_tau outside [1, 16], n_classes < 1, one box without the other, a misaligned workspace or a NULL
+ * required pointer return DIM_ERR_ARG before anything is enqueued. */
+#define DIM_VSD_GRID_MAX_TAU 16
+long dim_vsd_grid_workspace_bytes(int T, int B);
+int dim_vsd_grid_errors(const float* depth_obs, const float* depth_gt, const float* depth_est, const double* K9_f64,
+                        const double* K_per_sample_f64, const int* bbox_gt, const int* bbox_est, const int* class_index,
+                        const double* tau_table, int n_classes, int n_tau, int T, int B, int H, int W, float delta, void* workspace,
+                        double* errors, int* counts, int* n_ge, void* stream);
+
 /* ---------------------------------------------------------------- BOP symmetry-aware pose errors (MSSD, MSPD) on the device
  * lib/utils/pose_error.py mssd / mspd for T pose sets of B pairs: errors (T,B,2) float64 = {mssd, mspd} of poses_est[t][b] against
  * pose_gt[b] (B,3,4) float64 under the symmetry set of the pair's class,

@@ -90,7 +90,13 @@ def _defaults():
                    # max_sym_disc_step), and the thresholds of correctness -- fractions of the class diameter for MSSD, pixels at a
                    # 640-pixel-wide image (scaled by W / 640) for MSPD
                    BOP=False, BOP_SYM_STEP=0.01, BOP_MSSD_THRESH=[round(0.05 * k, 2) for k in range(1, 11)],
-                   BOP_MSPD_THRESH=[5 * k for k in range(1, 11)])
+                   BOP_MSPD_THRESH=[5 * k for k in range(1, 11)],
+                   # pred_eval with BOP: also the step-cost VSD on BOP's grid (dim_vsd_grid_errors) and with it AR_VSD and
+                   # AR = (AR_VSD + AR_MSSD + AR_MSPD) / 3: the visibility tolerance (metres), the misalignment tolerances as
+                   # fractions of the class diameter (up to 16), the errors below which a pose counts as correct, and the least
+                   # visible fraction of the ground truth at which a pose is a target at all
+                   BOP_VSD=False, BOP_VSD_DELTA=0.015, BOP_VSD_TAU=[round(0.05 * k, 2) for k in range(1, 11)],
+                   BOP_VSD_THRESH=[round(0.05 * k, 2) for k in range(1, 11)], BOP_MIN_VISIB_FRACT=0.1)
     c.train_iter = edict(SE3_DIST_LOSS=False, LW_ROT=0.0, LW_TRANS=0.0, TRANS_LOSS_TYPE="L2", TRANS_SMOOTH_L1_SCALAR=3.0,
                          SE3_PM_LOSS=False, LW_PM=0.0, SE3_PM_LOSS_TYPE="L1", SE3_PM_SL1_SCALAR=1.0, NUM_3D_SAMPLE=-1, LW_FLOW=0.0,
                          LW_MASK=0.0,

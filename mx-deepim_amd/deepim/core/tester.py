@@ -23,6 +23,7 @@ HYP_SCORES = ("rgb", "depth")
 ERR_KEYS = ("re", "te", "add", "arp_2d")   # the per-pose error lists lib.dataset.evaluation.PoseEvaluator takes as `errors=`
 VSD_KEYS = ("vsd", "visib_gt", "union", "inter", "drawn_gt")   # per pose: the errors (one per tau) and dim_vsd_errors' four counts
 BOP_KEYS = ("mssd", "mspd", "sym_mssd", "sym_mspd")             # per pose: dim_bop_errors' two errors and the symmetries that attain them
+GRID_KEYS = ("vsd_grid",) + VSD_KEYS[1:]                       # per pose: dim_vsd_grid_errors' errors (one per tau of the class) and counts
 
 
 def hyp_settings(cfg):
@@ -41,6 +42,24 @@ def hyp_settings(cfg):
     if not (np.isfinite(tau) and tau > 0):
         raise ValueError("TEST.HYP_DEPTH_TAU must be a finite distance > 0 (metres), got {!r}".format(T.get("HYP_DEPTH_TAU")))
     return int(n), deg, score, tau
+
+
+def bop_vsd_settings(cfg):
+    """-> (BOP_VSD, BOP_VSD_DELTA, BOP_VSD_TAU as a list of fractions) of cfg.TEST, checked; ValueError names the bad key.  The grid
+    only completes the BOP table (AR needs AR_MSSD and AR_MSPD next to AR_VSD), so it needs TEST.BOP."""
+    T = cfg.TEST
+    if not bool(T.get("BOP_VSD", False)):
+        return False, None, None
+    if not bool(T.get("BOP", False)):
+        raise ValueError("TEST.BOP_VSD needs TEST.BOP (AR averages AR_VSD with the AR_MSSD and AR_MSPD of TEST.BOP)")
+    delta = float(T.BOP_VSD_DELTA)
+    if not np.isfinite(delta):
+        raise ValueError("TEST.BOP_VSD_DELTA must be finite (metres), got {!r}".format(T.BOP_VSD_DELTA))
+    fracs = [float(f) for f in np.asarray(T.BOP_VSD_TAU, dtype=np.float64).reshape(-1)]
+    if not 1 <= len(fracs) <= ops.VSD_GRID_MAX_TAU or not all(np.isfinite(f) and f > 0 for f in fracs):
+        raise ValueError("TEST.BOP_VSD_TAU must hold 1 to {} finite fractions > 0 of the diameter, got {!r}".format(
+            ops.VSD_GRID_MAX_TAU, T.BOP_VSD_TAU))
+    return True, delta, fracs
 
 
 def flow_pnp_settings(cfg):
@@ -483,38 +502,53 @@ class Refiner(object):
 
 
 class VsdScorer(object):
-    """TEST.VSD: the visible surface discrepancy of every pose pred_eval scores, against the batch's observed depth.  Per batch the
-    ground truth is rendered once (depth and box only, float32 pose, the pair's K when one was loaded) with the refiner's render
-    machine; per scored pose set the estimate is rendered into one reused plane and dim_vsd_errors fills that set's row of `errors`
-    (rows, P, n_tau) float64 and `counts` (rows, P, 4) int32.  Nothing leaves the device here."""
+    """TEST.VSD and TEST.BOP_VSD: the visible surface discrepancy of every pose pred_eval scores, against the batch's observed depth.
+    Per batch the ground truth is rendered once (depth and box only, float32 pose, the pair's K when one was loaded) with the refiner's
+    render machine; per scored pose set the estimate is rendered once into one reused plane, and from the same three planes
+    TEST.VSD: dim_vsd_errors fills that set's row of `errors` (rows, P, n_tau) float64 and `counts` (rows, P, 4) int32 (absolute taus);
+    TEST.BOP_VSD: dim_vsd_grid_errors fills its row of `grid_errors` (rows, P, len(BOP_VSD_TAU)) float64 and `grid_counts`
+    (rows, P, 4) int32, at the taus of each pair's class (PoseEvaluator.device_vsd_tau_table).
+    Nothing leaves the device here.  Either half is allocated only when its key is on."""
 
-    def __init__(self, config, refiner, rows):
+    def __init__(self, config, refiner, rows, evaluator=None):
         T = config.TEST
+        self.absolute = bool(T.get("VSD", False))
+        self.grid, self.grid_delta, fracs = bop_vsd_settings(config)
+        who = "TEST.VSD" if self.absolute else "TEST.BOP_VSD"
         if getattr(refiner, "lit", False):
-            raise ValueError("TEST.VSD is not supported with the lit ModelNet renderer")
-        self.taus = [float(t) for t in np.asarray(T.VSD_TAU, dtype=np.float64).reshape(-1)]
-        if not 1 <= len(self.taus) <= ops.VSD_MAX_TAU or not all(np.isfinite(t) and t > 0 for t in self.taus):
-            raise ValueError("TEST.VSD_TAU must hold 1 to {} finite distances > 0 (metres), got {!r}".format(ops.VSD_MAX_TAU, T.VSD_TAU))
-        self.delta, self.cost = float(T.VSD_DELTA), T.VSD_COST
-        if self.cost not in ops.VSD_COST_ID:
-            raise ValueError("TEST.VSD_COST must be 'step' or 'tlinear', got {!r}".format(self.cost))
+            raise ValueError("{} is not supported with the lit ModelNet renderer".format(who))
         self.refiner, self.rm = refiner, refiner.render_machine
         P, H, W, d = refiner.P, self.rm.height, self.rm.width, refiner.net.device
+        if self.absolute:
+            self.taus = [float(t) for t in np.asarray(T.VSD_TAU, dtype=np.float64).reshape(-1)]
+            if not 1 <= len(self.taus) <= ops.VSD_MAX_TAU or not all(np.isfinite(t) and t > 0 for t in self.taus):
+                raise ValueError("TEST.VSD_TAU must hold 1 to {} finite distances > 0 (metres), got {!r}".format(ops.VSD_MAX_TAU, T.VSD_TAU))
+            self.delta, self.cost = float(T.VSD_DELTA), T.VSD_COST
+            if self.cost not in ops.VSD_COST_ID:
+                raise ValueError("TEST.VSD_COST must be 'step' or 'tlinear', got {!r}".format(self.cost))
+            self.errors = torch.zeros((rows, P, len(self.taus)), dtype=torch.float64, device=d)
+            self.counts = torch.zeros((rows, P, 4), dtype=torch.int32, device=d)
+            self.work = ops.vsd_workspace(1, P, d)
+        if self.grid:
+            if evaluator is None:
+                raise ValueError("TEST.BOP_VSD needs the evaluator (its class diameters give the taus)")
+            self.tau_table = evaluator.device_vsd_tau_table(d, fracs)
+            self.grid_errors = torch.zeros((rows, P, len(fracs)), dtype=torch.float64, device=d)
+            self.grid_counts = torch.zeros((rows, P, 4), dtype=torch.int32, device=d)
+            self.grid_n_ge = torch.zeros((rows, P, len(fracs)), dtype=torch.int32, device=d)
+            self.grid_work = ops.vsd_grid_workspace(1, P, d)
         self.K = np.asarray(self.rm.K, dtype=np.float64)   # the camera the planes are rendered with
         self.depth_gt = torch.zeros((P, 1, H, W), dtype=torch.float32, device=d)
         self.depth_est = torch.zeros((P, 1, H, W), dtype=torch.float32, device=d)
         self.depth_obs = None   # allocated only when the refiner keeps no observed depth of its own
         self.bbox_gt = torch.zeros((P, 4), dtype=torch.int32, device=d)
         self.bbox_est = torch.zeros((P, 4), dtype=torch.int32, device=d)
-        self.errors = torch.zeros((rows, P, len(self.taus)), dtype=torch.float64, device=d)
-        self.counts = torch.zeros((rows, P, 4), dtype=torch.int32, device=d)
-        self.work = ops.vsd_workspace(1, P, d)
         self.rm.reserve(P)
 
     @staticmethod
-    def check(batch):
+    def check(batch, who="TEST.VSD"):
         if batch.get("depth_observed") is None:
-            raise KeyError("TEST.VSD needs the blob 'depth_observed' (the test image's depth in metres)")
+            raise KeyError("{} needs the blob 'depth_observed' (the test image's depth in metres)".format(who))
 
     def _observed(self, batch):
         """the pairs' observed depth where the refiner already holds it (ICP, the depth hypothesis score, INPUT_DEPTH), else a copy"""
@@ -529,7 +563,7 @@ class VsdScorer(object):
         return self.depth_obs
 
     def score(self, batch, pose_sets):
-        """pose_sets: list of (P,3,4) float32 device poses, one per row of errors / counts"""
+        """pose_sets: list of (P,3,4) float32 device poses, one per row of errors / counts (and of grid_errors / grid_counts)"""
         r = self.refiner
         cls = r.batch["class_index"] if r.N == 1 else r.pair["class_index"]
         K_pair = (r.K_pair if r.N == 1 else r.pair["K"]) if r.per_pair_K else None
@@ -540,13 +574,22 @@ class VsdScorer(object):
         self.rm.render_batch(cls, gt, depth=self.depth_gt, bbox=self.bbox_gt, mask_thr=0.0, **extra)
         for row, pose in enumerate(pose_sets):
             self.rm.render_batch(cls, pose, depth=self.depth_est, bbox=self.bbox_est, mask_thr=0.0, **extra)
-            ops.vsd_errors(obs, self.depth_gt, self.depth_est, self.K, self.delta, self.taus, self.cost, K_per_sample=K64,
-                           bbox_gt=self.bbox_gt, bbox_est=self.bbox_est, errors=self.errors[row], counts=self.counts[row],
-                           workspace=self.work)
+            if self.absolute:
+                ops.vsd_errors(obs, self.depth_gt, self.depth_est, self.K, self.delta, self.taus, self.cost, K_per_sample=K64,
+                               bbox_gt=self.bbox_gt, bbox_est=self.bbox_est, errors=self.errors[row], counts=self.counts[row],
+                               workspace=self.work)
+            if self.grid:
+                ops.vsd_grid_errors(obs, self.depth_gt, self.depth_est, self.K, self.grid_delta, cls, self.tau_table, K_per_sample=K64,
+                                    bbox_gt=self.bbox_gt, bbox_est=self.bbox_est, errors=self.grid_errors[row],
+                                    counts=self.grid_counts[row], n_ge=self.grid_n_ge[row], workspace=self.grid_work)
 
     def packed(self):
         """(rows, P, n_tau + 4) float64: the errors and, behind them, the counts (exact in float64)"""
         return torch.cat([self.errors, self.counts.to(torch.float64)], dim=2)
+
+    def packed_grid(self):
+        """(rows, P, len(BOP_VSD_TAU) + 4) float64: the grid errors and, behind them, their counts"""
+        return torch.cat([self.grid_errors, self.grid_counts.to(torch.float64)], dim=2)
 
 
 class BopScorer(object):
@@ -675,6 +718,12 @@ def pred_eval(config, refiner, batches, evaluator, result_file=None, logger=None
     "errors", the per-pose lists {mssd, mspd, sym_mssd, sym_mspd}[cls][iter] in the order of all_poses_est; out["icp"]["bop"] the same
     for the ICP row.  A pair that was not refined scores inf for both (symmetry -1).  The numbers travel like the VSD ones.  Every
     other output and the result cache are those of BOP off.
+    With TEST.BOP_VSD (needs TEST.BOP and "depth_observed") every scored pose also gets the step-cost VSD at the fractions
+    TEST.BOP_VSD_TAU of its class's diameter (VsdScorer, dim_vsd_grid_errors on the renders TEST.VSD uses when both are on):
+    out["bop"]["bop19"] = the table of PoseEvaluator.evaluate_pose_bop19 (AR_VSD, AR_MSSD, AR_MSPD, AR per class, over the classes and
+    pooled) plus "errors", the per-pose lists {vsd_grid, visib_gt, union, inter, drawn_gt, mssd, mspd}[cls][iter]; out["icp"]["bop19"]
+    the same for the ICP row.  A pair that was not refined scores 1.0 with zero counts, so it is no target.  Every other output and
+    the result cache are those of BOP_VSD off.
     With TEST.FLOW_PNP_ITER > 0 the refiner's poses from flow (pose_flow_iter, one per loop iteration) are scored next to the head's,
     by the same error code (the host functions, or dim_pose_errors under TEST.DEVICE_EVAL): out["flow_pnp"] = {pose, add: the tables
     of evaluate_pose / evaluate_pose_add; all_rot_err, all_trans_err; inliers, rms: per loop iteration the mean over the refined pairs
@@ -685,6 +734,7 @@ def pred_eval(config, refiner, batches, evaluator, result_file=None, logger=None
 
     from lib.utils.pose_error import calc_rt_dist_m
 
+    bop_vsd = bop_vsd_settings(config)[0]   # before anything is allocated: BOP_VSD without BOP raises here
     n_cls, n_it = len(evaluator.classes), int(config.TEST.test_iter)
     all_rot_err = [[[] for _ in range(n_it)] for _ in range(n_cls)]
     all_trans_err = [[[] for _ in range(n_it)] for _ in range(n_cls)]
@@ -708,13 +758,20 @@ def pred_eval(config, refiner, batches, evaluator, result_file=None, logger=None
         tables = evaluator.device_tables(dev)
         K_eval = np.asarray(config.dataset.INTRINSIC_MATRIX, dtype=np.float64)
         uses_adi = [c in SYM_CLASSES for c in evaluator.classes]
-    # TEST.VSD: vsd_lists[key][cls][iter] (the ICP row: its own one-iteration lists)
-    vsd = vsd_lists = icp_vsd_lists = None
-    if bool(config.TEST.get("VSD", False)):
-        vsd = VsdScorer(config, refiner, n_it + (1 if with_icp else 0))
+    # TEST.VSD: vsd_lists[key][cls][iter] (the ICP row: its own one-iteration lists); TEST.BOP_VSD: grid_lists, the same for the grid.
+    # One scorer renders for both
+    vsd = vsd_lists = icp_vsd_lists = grid_lists = icp_grid_lists = None
+    vsd_who = "TEST.VSD" if bool(config.TEST.get("VSD", False)) else "TEST.BOP_VSD"
+    if bool(config.TEST.get("VSD", False)) or bop_vsd:
+        vsd = VsdScorer(config, refiner, n_it + (1 if with_icp else 0), evaluator)
+    if vsd is not None and vsd.absolute:
         vsd_lists = {k: [[[] for _ in range(n_it)] for _ in range(n_cls)] for k in VSD_KEYS}
         icp_vsd_lists = {k: [[[]] for _ in range(n_cls)] for k in VSD_KEYS} if with_icp else None
         n_tau = len(vsd.taus)
+    if bop_vsd:
+        grid_lists = {k: [[[] for _ in range(n_it)] for _ in range(n_cls)] for k in GRID_KEYS}
+        icp_grid_lists = {k: [[[]] for _ in range(n_cls)] for k in GRID_KEYS} if with_icp else None
+        n_grid = vsd.grid_errors.shape[2]
     # TEST.BOP: bop_lists[key][cls][iter] (the ICP row: its own one-iteration lists)
     bop = bop_lists = icp_bop_lists = None
     if bool(config.TEST.get("BOP", False)):
@@ -732,7 +789,7 @@ def pred_eval(config, refiner, batches, evaluator, result_file=None, logger=None
     for batch in batches:
         extra = {"hyp_poses": batch["hyp_poses"]} if batch.get("hyp_poses") is not None else {}
         if vsd is not None:
-            vsd.check(batch)
+            vsd.check(batch, vsd_who)
         if with_flow and "pose_observed" not in batch:
             raise KeyError("pose from flow (TEST.FLOW_PNP_ITER > 0) needs the blob 'pose_observed' to be scored")
         refiner.load(batch["image_observed"], batch["image_rendered"], batch["mask_observed"], batch["mask_rendered"], batch["src_pose"],
@@ -751,14 +808,18 @@ def pred_eval(config, refiner, batches, evaluator, result_file=None, logger=None
                 rows.append((p_icp, ops.pose_errors(tables[0], tables[1], tables[2], cls_dev, p_icp, gt_dev, K_eval)))
             packed = torch.cat([torch.cat([p.to(torch.float64).reshape(-1, gt_dev.shape[0], 12), e.reshape(-1, gt_dev.shape[0], 5)], dim=2)
                                 for p, e in rows], dim=0)
-            if vsd is not None:
+            if vsd_lists is not None:
                 packed = torch.cat([packed, vsd.packed()], dim=2)
+            if grid_lists is not None:
+                packed = torch.cat([packed, vsd.packed_grid()], dim=2)
             if bop is not None:
                 bop.score(batch, poses_dev, (refiner.pose_icp if n_hyp == 1 else refiner.pose_icp_sel) if with_icp else None)
                 packed = torch.cat([packed, bop.packed()], dim=2)
             packed = packed.cpu().numpy()
-            n_vsd = packed.shape[2] - 17 - (4 if bop is not None else 0)
-            vsd_host, bop_host = packed[:, :, 17:17 + n_vsd], packed[:, :, 17 + n_vsd:]
+            w_grid = n_grid + 4 if grid_lists is not None else 0
+            n_vsd = packed.shape[2] - 17 - w_grid - (4 if bop is not None else 0)
+            vsd_host, grid_host, bop_host = (packed[:, :, 17:17 + n_vsd], packed[:, :, 17 + n_vsd:17 + n_vsd + w_grid],
+                                             packed[:, :, 17 + n_vsd + w_grid:])
             packed = packed[:, :, :17]
             poses, dev_err = packed[:n_it, :, :12].reshape(n_it, -1, 3, 4), packed[:n_it, :, 12:]
             if with_icp:
@@ -766,9 +827,12 @@ def pred_eval(config, refiner, batches, evaluator, result_file=None, logger=None
         else:
             poses_dev = refiner.refine()
             poses = poses_dev.cpu().numpy().astype(np.float64)     # ONE device->host copy per batch: (iter, B, 3, 4)
-            if vsd is not None:   # and one more for the VSD rows
+            if vsd is not None:   # and one more for the VSD rows, one for the grid's
                 vsd.score(batch, list(poses_dev) + ([refiner.pose_icp if n_hyp == 1 else refiner.pose_icp_sel] if with_icp else []))
-                vsd_host = vsd.packed().cpu().numpy()
+                if vsd_lists is not None:
+                    vsd_host = vsd.packed().cpu().numpy()
+                if grid_lists is not None:
+                    grid_host = vsd.packed_grid().cpu().numpy()
             if bop is not None:   # and one for the BOP rows
                 bop.score(batch, poses_dev, (refiner.pose_icp if n_hyp == 1 else refiner.pose_icp_sel) if with_icp else None)
                 bop_host = bop.packed().cpu().numpy()
@@ -820,11 +884,17 @@ def pred_eval(config, refiner, batches, evaluator, result_file=None, logger=None
                 r_dist, t_dist = (1000, 1000) if undetected else calc_rt_dist_m(est, gt[b])
                 for k, v in enumerate((r_dist, t_dist, est, gt[b])):
                     icp_lists[k][cls[b]][0].append(v)
-            if vsd is not None:   # a pair that was not refined: e = 1.0 and no counts, whatever its -1 pose rendered
+            if vsd_lists is not None:   # a pair that was not refined: e = 1.0 and no counts, whatever its -1 pose rendered
                 for lists, rows_b in ((vsd_lists, vsd_host[:n_it, b]), (icp_vsd_lists, vsd_host[n_it:, b])):
                     for it, row in enumerate(rows_b):
                         e, cnt = ([1.0] * n_tau, [0] * 4) if undetected else (row[:n_tau].tolist(), [int(v) for v in row[n_tau:]])
                         for k, v in zip(VSD_KEYS, [e] + cnt):
+                            lists[k][cls[b]][it].append(v)
+            if grid_lists is not None:   # the same rule on the grid
+                for lists, rows_b in ((grid_lists, grid_host[:n_it, b]), (icp_grid_lists, grid_host[n_it:, b])):
+                    for it, row in enumerate(rows_b):
+                        e, cnt = ([1.0] * n_grid, [0] * 4) if undetected else (row[:n_grid].tolist(), [int(v) for v in row[n_grid:]])
+                        for k, v in zip(GRID_KEYS, [e] + cnt):
                             lists[k][cls[b]][it].append(v)
             if bop is not None:   # a pair that was not refined: inf, attained by no symmetry
                 for lists, rows_b in ((bop_lists, bop_host[:n_it, b]), (icp_bop_lists, bop_host[n_it:, b])):
@@ -853,7 +923,8 @@ def pred_eval(config, refiner, batches, evaluator, result_file=None, logger=None
     if merge_ranks and dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
         parts = [None] * dist.get_world_size()
         dist.all_gather_object(parts, (all_rot_err, all_trans_err, all_poses_est, all_poses_gt, icp_lists, hyp_lists, err_lists, icp_err_lists,
-                                       vsd_lists, icp_vsd_lists, bop_lists, icp_bop_lists, flow_lists, flow_err_lists, flow_rows))
+                                       vsd_lists, icp_vsd_lists, bop_lists, icp_bop_lists, flow_lists, flow_err_lists, flow_rows,
+                                       grid_lists, icp_grid_lists))
         for k, mine in enumerate((all_rot_err, all_trans_err, all_poses_est, all_poses_gt)):
             for c in range(n_cls):
                 for it in range(n_it):
@@ -866,7 +937,7 @@ def pred_eval(config, refiner, batches, evaluator, result_file=None, logger=None
             for k, mine in enumerate(hyp_lists):
                 mine[:] = [x for part in parts for x in part[5][k]]
         for slot, lists, iters in ((6, err_lists, n_it), (7, icp_err_lists, 1), (8, vsd_lists, n_it), (9, icp_vsd_lists, 1),
-                                   (10, bop_lists, n_it), (11, icp_bop_lists, 1)):
+                                   (10, bop_lists, n_it), (11, icp_bop_lists, 1), (15, grid_lists, n_it), (16, icp_grid_lists, 1)):
             for k in (lists or {}):
                 for c in range(n_cls):
                     for it in range(iters):
@@ -902,10 +973,13 @@ def pred_eval(config, refiner, batches, evaluator, result_file=None, logger=None
     out["arp_2d"] = evaluator.evaluate_pose_arp_2d(config, all_poses_est, all_poses_gt, output_dir=None, logger=logger, **given)
     if device_eval:
         out["device_eval"] = True
-    if vsd is not None:
+    if vsd_lists is not None:
         out["vsd"] = dict(evaluator.evaluate_pose_vsd(config, vsd_lists, logger), errors=vsd_lists)
     if bop is not None:
         out["bop"] = dict(evaluator.evaluate_pose_bop(config, bop_lists, logger), errors=bop_lists)
+    if grid_lists is not None:   # AR_VSD on the grid, and AR with the two errors above
+        errs = dict(grid_lists, mssd=bop_lists["mssd"], mspd=bop_lists["mspd"])
+        out["bop"]["bop19"] = dict(evaluator.evaluate_pose_bop19(config, errs, logger), errors=errs)
     out["all_rot_err"], out["all_trans_err"] = all_rot_err, all_trans_err
     out["merged_over_ranks"] = merged
     if with_icp:
@@ -923,10 +997,13 @@ def pred_eval(config, refiner, batches, evaluator, result_file=None, logger=None
                       "add": evaluator.evaluate_pose_add(cfg1, icp_est, icp_gt, output_dir=None, logger=logger, **given),
                       "arp_2d": evaluator.evaluate_pose_arp_2d(cfg1, icp_est, icp_gt, output_dir=None, logger=logger, **given),
                       "all_rot_err": icp_rot, "all_trans_err": icp_trans}
-        if vsd is not None:
+        if vsd_lists is not None:
             out["icp"]["vsd"] = dict(evaluator.evaluate_pose_vsd(config, icp_vsd_lists, logger), errors=icp_vsd_lists)
         if bop is not None:
             out["icp"]["bop"] = dict(evaluator.evaluate_pose_bop(config, icp_bop_lists, logger), errors=icp_bop_lists)
+        if grid_lists is not None:
+            errs = dict(icp_grid_lists, mssd=icp_bop_lists["mssd"], mspd=icp_bop_lists["mspd"])
+            out["icp"]["bop19"] = dict(evaluator.evaluate_pose_bop19(config, errs, logger), errors=errs)
     if with_flow:
         flow_rot, flow_trans, flow_est, flow_gt = flow_lists
         line = "evaluate pose from flow ({} iterations, {} unweighted, Huber {} px, gate {} px):".format(

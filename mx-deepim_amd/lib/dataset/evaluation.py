@@ -104,6 +104,25 @@ class PoseEvaluator(object):
             cache[key] = (torch.from_numpy(allp).to(device), torch.from_numpy(off).to(device), torch.from_numpy(flags).to(device))
         return cache[key]
 
+    def vsd_tau_table(self, fracs):
+        """-> (n_classes, n_tau) float64, entry [c][k] = float(fracs[k]) * float(diameter of class c), in class order: the
+        misalignment tolerances of BOP's VSD (fractions of the object diameter) in the unit of the depth planes.  The one rounding of
+        each product is made here; dim_vsd_grid_errors only compares against the table."""
+        fr = [float(f) for f in np.asarray(fracs, dtype=np.float64).reshape(-1)]
+        return np.array([[f * float(self._diameters[c]) for f in fr] for c in self.classes], dtype=np.float64).reshape(len(self.classes), len(fr))
+
+    def device_vsd_tau_table(self, device, fracs):
+        """vsd_tau_table(fracs) resident on `device` as lib.hip.ops.vsd_grid_errors reads it.  Uploaded once per device (and fractions)."""
+        import torch
+
+        from lib.hip import ops
+
+        key = (str(torch.device(device)), tuple(float(f) for f in np.asarray(fracs, dtype=np.float64).reshape(-1)))
+        cache = self.__dict__.setdefault("_device_vsd_tau_tables", {})
+        if key not in cache:
+            cache[key] = ops.vsd_tau_table(self.vsd_tau_table(fracs), device)
+        return cache[key]
+
     def host_pose_errors(self, config, cls_name, RT, pose_gt):
         """the four numbers the three tables below read for one pose: (re, te) of evaluate_pose, ADD or ADD-S, arp_2d"""
         K = np.asarray(config.dataset.INTRINSIC_MATRIX, dtype=np.float64)
@@ -371,3 +390,88 @@ class PoseEvaluator(object):
         return {"recall_mssd": rec_s, "recall_mspd": rec_p, "AR_MSSD": ar_s, "AR_MSPD": ar_p, "overall": overall,
                 "count_all": count_all, "thresh_mssd": th_s.tolist(), "thresh_mspd": th_p.tolist(),
                 "num_valid_class": num_valid_class}
+
+    # ------------------------------------------------------------------------------------------------ BOP: AR_VSD and AR
+    def evaluate_pose_bop19(self, config, errors, logger=None):
+        """The number BOP ranks by, AR = (AR_VSD + AR_MSSD + AR_MSPD) / 3.  errors: {"mssd", "mspd"} as evaluate_pose_bop takes them,
+        "vsd_grid": errors[key][cls][iter] = per pose one list of len(TEST.BOP_VSD_TAU) step-cost VSD errors, at the taus
+        vsd_tau_table(TEST.BOP_VSD_TAU) gives the pose's class (pred_eval with TEST.BOP_VSD fills them from dim_vsd_grid_errors), and
+        "visib_gt" / "drawn_gt": [cls][iter] = per pose the visible and the drawn pixels of the ground-truth render.
+        A pose is a target when drawn_gt > 0 and visib_gt / drawn_gt >= TEST.BOP_MIN_VISIB_FRACT; the others count for none of the
+        three recalls.  Recall = the share of targets with e < threshold.  Per class and iteration: recall_vsd over the grid
+        BOP_VSD_TAU x BOP_VSD_THRESH and its mean AR_VSD, AR_MSSD and AR_MSPD over the thresholds of evaluate_pose_bop, and AR.
+        `overall`: per iteration their means over the classes that have a target, in percent.  `pooled`: per iteration the same four
+        with every recall taken over the targets of all classes at once (BOP's own definition), in percent."""
+        T = config.TEST
+        fracs = np.asarray(T.BOP_VSD_TAU, dtype=np.float64).reshape(-1)
+        th_v = np.asarray(T.BOP_VSD_THRESH, dtype=np.float64).reshape(-1)
+        th_s = np.asarray(T.BOP_MSSD_THRESH, dtype=np.float64).reshape(-1)
+        scales = getattr(config, "SCALES", None)
+        width = float(scales[0][1]) if scales else 640.0
+        th_p = np.asarray(T.BOP_MSPD_THRESH, dtype=np.float64).reshape(-1) * (width / 640.0)
+        min_visib = float(T.BOP_MIN_VISIB_FRACT)
+        num_iter = len(errors["vsd_grid"][0]) if len(errors["vsd_grid"]) else 0
+        n_cls = self.num_classes
+        rec_v = np.zeros((n_cls, num_iter, len(fracs), len(th_v)))
+        rec_s = np.zeros((n_cls, num_iter, len(th_s)))
+        rec_p = np.zeros((n_cls, num_iter, len(th_p)))
+        count_all = np.zeros((n_cls,), dtype=np.float32)
+        count_targets = np.zeros((n_cls, num_iter), dtype=np.int64)
+        # the hits of every class: summed over the classes they give the pooled recalls
+        hit_v = np.zeros((n_cls, num_iter, len(fracs), len(th_v)))
+        hit_s = np.zeros((n_cls, num_iter, len(th_s)))
+        hit_p = np.zeros((n_cls, num_iter, len(th_p)))
+        print_and_log("evaluating pose bop19 (vsd delta {}, tau {} of the diameter, correct below {}; targets: visible fraction >= {})".format(
+            float(T.BOP_VSD_DELTA), fracs.tolist(), th_v.tolist(), min_visib), logger)
+        for cls_idx, cls_name in enumerate(self.classes):
+            if not len(errors["vsd_grid"][cls_idx][0]):
+                continue
+            count_all[cls_idx] = len(errors["vsd_grid"][cls_idx][0])
+            for iter_i in range(num_iter):
+                vis = np.asarray(errors["visib_gt"][cls_idx][iter_i], dtype=np.float64)
+                drawn = np.asarray(errors["drawn_gt"][cls_idx][iter_i], dtype=np.float64)
+                target = np.zeros(drawn.shape, dtype=bool)
+                target[drawn > 0] = vis[drawn > 0] / drawn[drawn > 0] >= min_visib
+                n = int(target.sum())
+                count_targets[cls_idx, iter_i] = n
+                e_v = np.asarray(errors["vsd_grid"][cls_idx][iter_i], dtype=np.float64).reshape(-1, len(fracs))[target]
+                e_s = self._given(errors, "mssd", cls_idx, iter_i, len(target))[target]
+                e_p = self._given(errors, "mspd", cls_idx, iter_i, len(target))[target]
+                hit_v[cls_idx, iter_i] = (e_v[:, :, None] < th_v[None, None, :]).sum(0)
+                hit_s[cls_idx, iter_i] = (e_s[:, None] < th_s[None, :] * self._diameters[cls_name]).sum(0)
+                hit_p[cls_idx, iter_i] = (e_p[:, None] < th_p[None, :]).sum(0)
+                if n:
+                    rec_v[cls_idx, iter_i] = hit_v[cls_idx, iter_i] / n
+                    rec_s[cls_idx, iter_i] = hit_s[cls_idx, iter_i] / n
+                    rec_p[cls_idx, iter_i] = hit_p[cls_idx, iter_i] / n
+                print_and_log("** {}, iter {} **".format(cls_name, iter_i + 1), logger)
+                print_and_log("all poses: {}, targets: {}, AR_VSD: {:.2f}, AR_MSSD: {:.2f}, AR_MSPD: {:.2f}".format(
+                    count_all[cls_idx], n, rec_v[cls_idx, iter_i].mean() * 100, rec_s[cls_idx, iter_i].mean() * 100,
+                    rec_p[cls_idx, iter_i].mean() * 100), logger)
+        ar_v = rec_v.mean((2, 3)) if rec_v.size else np.zeros((n_cls, num_iter))
+        ar_s = rec_s.mean(2) if len(th_s) else np.zeros((n_cls, num_iter))
+        ar_p = rec_p.mean(2) if len(th_p) else np.zeros((n_cls, num_iter))
+        ar = (ar_v + ar_s + ar_p) / 3.0
+        overall, pooled, num_valid_class = [], [], []
+        for iter_i in range(num_iter):
+            valid = int((count_targets[:, iter_i] > 0).sum())
+            num_valid_class.append(valid)
+            n = max(valid, 1)
+            row = {"AR_VSD": np.sum(ar_v[:, iter_i]) / n * 100, "AR_MSSD": np.sum(ar_s[:, iter_i]) / n * 100,
+                   "AR_MSPD": np.sum(ar_p[:, iter_i]) / n * 100, "AR": np.sum(ar[:, iter_i]) / n * 100}
+            overall.append(row)
+            n_all = max(int(count_targets[:, iter_i].sum()), 1)
+            pool = {k: float(h[:, iter_i].sum(0).mean() / n_all * 100) if h[:, iter_i].size else 0.0
+                    for k, h in (("AR_VSD", hit_v), ("AR_MSSD", hit_s), ("AR_MSPD", hit_p))}
+            pool["AR"] = (pool["AR_VSD"] + pool["AR_MSSD"] + pool["AR_MSPD"]) / 3.0
+            pooled.append(pool)
+            print_and_log("---------- bop19 performance over {} classes -----------".format(valid), logger)
+            print_and_log("** iter {} **".format(iter_i + 1), logger)
+            print_and_log("AR_VSD: {:.2f}, AR_MSSD: {:.2f}, AR_MSPD: {:.2f}, AR: {:.2f}".format(
+                row["AR_VSD"], row["AR_MSSD"], row["AR_MSPD"], row["AR"]), logger)
+            print_and_log("pooled over {} targets: AR_VSD: {:.2f}, AR_MSSD: {:.2f}, AR_MSPD: {:.2f}, AR: {:.2f}".format(
+                int(count_targets[:, iter_i].sum()), pool["AR_VSD"], pool["AR_MSSD"], pool["AR_MSPD"], pool["AR"]), logger)
+        return {"recall_vsd": rec_v, "recall_mssd": rec_s, "recall_mspd": rec_p, "AR_VSD": ar_v, "AR_MSSD": ar_s, "AR_MSPD": ar_p,
+                "AR": ar, "overall": overall, "pooled": pooled, "count_all": count_all, "count_targets": count_targets,
+                "tau_fracs": fracs.tolist(), "thresh_vsd": th_v.tolist(), "thresh_mssd": th_s.tolist(), "thresh_mspd": th_p.tolist(),
+                "min_visib_fract": min_visib, "num_valid_class": num_valid_class}

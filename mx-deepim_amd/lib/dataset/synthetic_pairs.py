@@ -55,10 +55,10 @@ class SyntheticPairs(object):
         with_depth = bool(self.config.network.PRED_FLOW and not self.config.TEST.FAST_TEST)
         # the depth ICP after the loop (TEST.ICP_ITER > 0) reads an observed depth: the GT render over a flat wall at ICP_WALL_M, which
         # gives its gate something to reject
-        # (the depth score of several hypotheses per pair and the VSD error of TEST.VSD read it too)
+        # (the depth score of several hypotheses per pair and the VSD errors of TEST.VSD and TEST.BOP_VSD read it too)
         T = self.config.TEST
         icp = int(T.get("ICP_ITER", 0) or 0) > 0 or (int(T.get("HYP_NUM", 1) or 1) > 1 and T.get("HYP_SCORE", "rgb") == "depth")
-        icp = icp or bool(T.get("VSD", False))
+        icp = icp or bool(T.get("VSD", False)) or bool(T.get("BOP_VSD", False))
         for i in self.batch_ids:
             b = syn.build_device_batch(self.render_machine, self.batch_pairs, seed=self.seed + 1000 * (i + 1), n_classes=len(self.classes),
                                        pixel_means=self.config.network.PIXEL_MEANS, device=self.device, with_depth=with_depth or icp)

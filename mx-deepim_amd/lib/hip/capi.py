@@ -53,6 +53,8 @@ SIGNATURES = {
     "dim_pose_errors": (I, [P, P, P, I, P, P, P, P, P, I, I, P, P, P, P]),
     "dim_vsd_workspace_bytes": (L, [I, I]),
     "dim_vsd_errors": (I, [P, P, P, P, P, P, P, I, I, I, I, F, P, I, I, P, P, P, P]),
+    "dim_vsd_grid_workspace_bytes": (L, [I, I]),
+    "dim_vsd_grid_errors": (I, [P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, F, P, P, P, P, P]),
     "dim_bop_errors_workspace_bytes": (L, [I, I, I]),
     "dim_bop_errors": (I, [P, P, P, P, I, P, P, P, P, P, P, I, I, I, P, P, P, P, P]),
     "dim_refiner_create": (I, [P, P, P, P, I, P]),

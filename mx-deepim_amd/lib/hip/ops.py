@@ -446,6 +446,73 @@ def vsd_errors(depth_obs, depth_gt, depth_est, K, delta, taus, cost_type="step",
     return errors, counts
 
 
+VSD_GRID_MAX_TAU = 16   # DIM_VSD_GRID_MAX_TAU
+
+
+def vsd_grid_workspace(T, B, device):
+    return _workspace_f64(lib().dim_vsd_grid_workspace_bytes(T, B), device)
+
+
+def vsd_tau_table(tau_table, device):
+    """the tau table of vsd_grid_errors on `device`: a ready CUDA float64 tensor (n_classes, n_tau) is used where it lies; a host
+    array is checked (finite, > 0, shape (n_classes >= 1, 1..16)) and uploaded"""
+    if isinstance(tau_table, torch.Tensor) and tau_table.is_cuda:
+        if tau_table.dtype != torch.float64 or tau_table.dim() != 2 or not tau_table.is_contiguous():
+            raise ValueError("vsd tau_table on the device must be a contiguous float64 (n_classes, n_tau) tensor, got {} {}".format(
+                tau_table.dtype, tuple(tau_table.shape)))
+        table = tau_table
+    else:
+        a = np.asarray(tau_table, dtype=np.float64)
+        if a.ndim != 2 or not (np.all(np.isfinite(a)) and np.all(a > 0)):
+            raise ValueError("vsd tau_table: (n_classes, n_tau) finite distances > 0, got {!r}".format(tau_table))
+        table = torch.from_numpy(np.ascontiguousarray(a)).to(device)
+    if table.shape[0] < 1 or not 1 <= table.shape[1] <= VSD_GRID_MAX_TAU:
+        raise ValueError("vsd tau_table: at least one class and 1 to {} taus per class, got shape {}".format(
+            VSD_GRID_MAX_TAU, tuple(table.shape)))
+    return table
+
+
+def vsd_grid_errors(depth_obs, depth_gt, depth_est, K, delta, class_index, tau_table, K_per_sample=None, bbox_gt=None, bbox_est=None,
+                    errors=None, counts=None, n_ge=None, workspace=None):
+    """dim_vsd_grid_errors: the step-cost VSD of T pose sets of B pairs at the taus of each pair's class, from one read of the planes
+    (BOP's grid: ten fractions of the class diameter).  Planes, K, K_per_sample and the boxes as vsd_errors takes them.  class_index
+    (B,) int32 CUDA; tau_table (n_classes, n_tau <= 16) metres: a host array (checked and uploaded, see vsd_tau_table) or a ready CUDA
+    float64 tensor (PoseEvaluator.device_vsd_tau_table).  -> errors (T,B,n_tau) f64 with the bits of pose_error.vsd(..., "step"),
+    counts (T,B,4) int32 (VSD_COUNT_COLUMNS), n_ge (T,B,n_tau) int32 = pixels of the intersection with |S_gt - S_est| >= tau; without
+    the T axis for a single set.  A class index outside the table: a NaN row, zero counts and n_ge"""
+    f64 = torch.float64
+    H, W = depth_gt.shape[-2:]
+    B = depth_gt.shape[0]
+    assert depth_gt.numel() == B * H * W and tuple(depth_obs.shape) == tuple(depth_gt.shape)
+    single = depth_est.dim() == depth_gt.dim()
+    T = 1 if single else depth_est.shape[0]
+    assert depth_est.numel() == T * B * H * W and tuple(depth_est.shape[-2:]) == (H, W)
+    dev = depth_gt.device
+    table = vsd_tau_table(tau_table, dev)
+    n_classes, n_tau = table.shape
+    assert class_index.numel() == B
+    lead = (B,) if single else (T, B)
+    if errors is None:
+        errors = torch.empty(lead + (n_tau,), dtype=f64, device=dev)
+    if counts is None:
+        counts = torch.empty(lead + (4,), dtype=i32, device=dev)
+    if n_ge is None:
+        n_ge = torch.empty(lead + (n_tau,), dtype=i32, device=dev)
+    assert errors.numel() == T * B * n_tau and counts.numel() == T * B * 4 and n_ge.numel() == T * B * n_tau
+    assert (bbox_gt is None) == (bbox_est is None), "vsd_grid_errors: both boxes or neither"
+    assert bbox_gt is None or (bbox_gt.numel() == 4 * B and bbox_est.numel() == 4 * T * B)
+    if workspace is None:
+        workspace = vsd_grid_workspace(T, B, dev)
+    assert workspace.numel() * workspace.element_size() >= lib().dim_vsd_grid_workspace_bytes(T, B)
+    keep = _host_k9_f64(K)
+    kps = _kps_f64(K_per_sample, B, dev, "vsd_grid")
+    check(lib().dim_vsd_grid_errors(dptr(depth_obs, f32), dptr(depth_gt, f32), dptr(depth_est, f32), keep.ctypes.data, _opt(kps, f64),
+                                    _opt(bbox_gt, i32), _opt(bbox_est, i32), dptr(class_index, i32), dptr(table, f64), int(n_classes),
+                                    int(n_tau), T, B, H, W, float(delta), dptr(workspace), dptr(errors, f64), dptr(counts, i32),
+                                    dptr(n_ge, i32), current_stream()))
+    return errors, counts, n_ge
+
+
 BOP_ERR_COLUMNS = ("mssd", "mspd")
 
 
