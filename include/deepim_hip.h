@@ -36,7 +36,7 @@ extern "C" {
  * caller that wants both kinds of bits in one word calls dim_zoom_factor BEFORE the render, as the loop does. */
 #define DIM_STATUS_OBS_BOX_EMPTY 1 /* dim_zoom_factor: observed box empty (the reference raises) */
 #define DIM_STATUS_REN_BOX_EMPTY 2 /* dim_zoom_factor: rendered box empty */
-#define DIM_STATUS_BAD_CLASS 4     /* dim_raster_render*: class_index outside [0, n_classes): sample rendered as background; dim_pose_errors, dim_bop_errors: NaN row */
+#define DIM_STATUS_BAD_CLASS 4     /* dim_raster_render*: class_index outside [0, n_classes): sample rendered as background; dim_pose_errors, dim_bop_errors: NaN row; dim_pose_head_fwd_cls: identity delta */
 #define DIM_STATUS_BAD_FACE 8      /* dim_raster_render*: a z-buffer key named a face outside the mesh (pixel left black) */
 #define DIM_STATUS_BAD_K 16        /* dim_raster_render_k: the sample's K has fx <= 0, fy <= 0 or a non-finite entry (rendered as background) */
 #define DIM_STATUS_ICP_FEW_POINTS 32 /* dim_icp_refine: an iteration found fewer than 64 inliers or a singular system (no update) */
@@ -757,6 +757,36 @@ int dim_pose_head_fwd(const float* fc6, const float* fc7_w, const float* fc7_b, 
                       const float* trans_w, const float* trans_b, const float* zoom_factor, float* se3, float* fc7_out, int B,
                       void* stream);
 
+/* ---------------------------------------------------------------- per-class pose regressors (network.REGRESSOR_NUM = K > 1)
+ * One `rot` / `trans` head per object class behind the shared fc6 / fc7: rot_w (4K,256), rot_b (4K), trans_w (3K,256), trans_b (3K),
+ * class c owning rows 4c .. 4c+3 of rot and 3c .. 3c+2 of trans (one FullyConnected(num_hidden = 4K) reshaped to (B,K,4) and picked
+ * by class).  The four entries below are dim_pose_head_fwd, dim_pose_head_bwd, dim_se3_dist_loss_grad and dim_fc_wgrad with
+ * class_index (B int32, device) and n_regressors = K after the weights; sample b uses the rows of class class_index[b].
+ *   - no allocation, no synchronisation (graph-capturable); class_index is read when the kernel runs, so a captured graph replayed
+ *     after new classes are written there uses the new heads
+ *   - n_regressors == 1: class_index may be NULL, and the call IS the un-suffixed entry (same kernel, same bits)
+ *   - any K: sample b's outputs are bit for bit what the un-suffixed entry gives with class c_b's slice of rot / trans (same
+ *     dot-product order, same shuffle tree); class c's rows of dim_fc_wgrad_cls are bit for bit dim_fc_wgrad over the samples of
+ *     class c in their original order.  dim_fc_wgrad_cls writes EVERY element of dW (K*Out,In) and db (K*Out, may be NULL): zeros in
+ *     the rows of a class that the batch does not hold (MXNet's dense FullyConnected gradient); no atomics, sums in ascending b
+ *   - a class index outside [0, K), K > 1: dim_pose_head_fwd_cls writes the identity delta (1,0,0,0,0,0,0) (fc7_out as usual) and ORs
+ *     DIM_STATUS_BAD_CLASS into status[b] (B int32, may be NULL); dim_pose_head_bwd_cls gives the sample zero d_rot / dz7 / dz6
+ *     rows; dim_se3_dist_loss_grad_cls adds nothing to its rows of d_rot_norm / d_zoom_trans and nothing to loss_sums2;
+ *     dim_fc_wgrad_cls skips the sample
+ *   - n_regressors < 1, or class_index == NULL with n_regressors > 1: DIM_ERR_ARG before anything is enqueued */
+int dim_pose_head_fwd_cls(const float* fc6, const float* fc7_w, const float* fc7_b, const float* rot_w, const float* rot_b,
+                          const float* trans_w, const float* trans_b, const int* class_index, int n_regressors,
+                          const float* zoom_factor, float* se3, float* fc7_out, int* status, int B, void* stream);
+int dim_pose_head_bwd_cls(const float* fc6a, const float* fc7, const float* rot_raw, const float* d_rot_norm, const float* d_trans,
+                          const float* fc7_w, const float* rot_w, const float* trans_w, const int* class_index, int n_regressors,
+                          float* d_rot, float* dz7, float* dz6, int B, void* stream);
+int dim_se3_dist_loss_grad_cls(const float* rot_est_norm, const float* rot_gt, const float* fc7, const float* trans_w,
+                               const float* trans_b, const int* class_index, int n_regressors, const float* zoom_trans_gt,
+                               float* d_rot_norm, float* d_zoom_trans, int B, float lw_rot, float lw_trans, int trans_loss_type,
+                               float smooth_l1_scalar, float* loss_sums2, void* stream);
+int dim_fc_wgrad_cls(const float* dz, const float* x, const int* class_index, int n_regressors, float* dW, float* db, int B, int Out,
+                     int In, void* stream);
+
 /* ---------------------------------------------------------------- resident refinement loop (hosts without torch)
  * The inner loop of pred_eval (deepim/core/tester.py:476-598) for a batch of B 480x640 pairs that stays in HBM, FAST_TEST graph,
  * UPDATE_MASK 'box_rendered': per iteration ZoomMask + ZoomImageWithFactor + Concat -> encoder -> fc6/fc7/rot/trans -> RT_transform
@@ -784,6 +814,11 @@ typedef struct {
 } dim_refiner_desc;
 int dim_refiner_create(dim_refiner** out, const dim_refiner_desc* desc, const char* const* param_names, const float* const* param_ptrs,
                        int n_params, void* stream);
+/* dim_refiner_create with per-class pose regressors: n_regressors = 1 (this is dim_refiner_create) or desc->n_classes, the rot /
+ * trans arrays then holding (4 n_classes,256) / (4 n_classes) / (3 n_classes,256) / (3 n_classes) floats (dim_pose_head_fwd_cls);
+ * dim_refiner_run / _run_k pick every pair's head by the class_index they already receive, read when the kernels run. */
+int dim_refiner_create_cls(dim_refiner** out, const dim_refiner_desc* desc, int n_regressors, const char* const* param_names,
+                           const float* const* param_ptrs, int n_params, void* stream);
 int dim_refiner_run(dim_refiner* r, const float* image_observed, const float* image_rendered, const float* mask_observed,
                     const float* mask_rendered, const float* src_pose, const int* class_index, float* poses_iter, float* se3_iter,
                     int* status_iter, void* stream);

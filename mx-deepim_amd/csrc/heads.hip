@@ -164,13 +164,28 @@ __global__ __launch_bounds__(256) void upsample16_x4_kernel(const float* __restr
 
 // Pose head: fc7 + LeakyReLU + rot (4) + trans (3) + inverse ZoomTrans -> se3 (B,7).
 // deepIM_flownet.py:203-208, :956-971; zoom_trans.py:37-41 (b_inv_zoom: dx*wx, dy*wx).
-__global__ __launch_bounds__(1024) void pose_head_kernel(const float* __restrict__ fc6, const float* __restrict__ w7,
-                                                         const float* __restrict__ b7, const float* __restrict__ wr,
-                                                         const float* __restrict__ br, const float* __restrict__ wt,
-                                                         const float* __restrict__ bt, const float* __restrict__ zoom_factor,
-                                                         float* __restrict__ se3, float* __restrict__ fc7_out) {
+// CLS (network.REGRESSOR_NUM = K > 1): wr (4K,256) / br (4K) / wt (3K,256) / bt (3K) hold one head per class and the sample reads the
+// rows of class_index[b] -- a workgroup-uniform offset (one scalar load and an add), everything after it is the shared head's code,
+// so a sample's se3 is bit for bit the shared kernel's with that class's slice.  A class outside [0, K): identity delta + status bit.
+template <bool CLS>
+__device__ __forceinline__ void pose_head_body(const float* __restrict__ fc6, const float* __restrict__ w7, const float* __restrict__ b7,
+                                               const float* __restrict__ wr, const float* __restrict__ br, const float* __restrict__ wt,
+                                               const float* __restrict__ bt, const int* __restrict__ class_index, int n_regressors,
+                                               const float* __restrict__ zoom_factor, float* __restrict__ se3,
+                                               float* __restrict__ fc7_out, int* __restrict__ status) {
   __shared__ float s_h[256];
   const int b = blockIdx.x, t = threadIdx.x;
+  bool bad_class = false;
+  if constexpr (CLS) {
+    const int c = class_index[b];
+    bad_class = (unsigned)c >= (unsigned)n_regressors;
+    if (!bad_class) {
+      wr += (long)c * 4 * 256; br += c * 4;
+      wt += (long)c * 3 * 256; bt += c * 3;
+    } else if (t == 0 && status) {
+      status[b] |= DIM_STATUS_BAD_CLASS;
+    }
+  }
   const int wave = t >> 6, lane = t & 63;
   // fc7 (256 x 256): for each output the 64 lanes of a wave read the weight row as one coalesced 1 KB load (a float4 per lane against
   // the lane's own four fc6 values) and fold their partial dots with a fixed shuffle tree.  (The first version gave every thread one
@@ -216,9 +231,28 @@ __global__ __launch_bounds__(1024) void pose_head_kernel(const float* __restrict
     if (lane == 0) {
       float v = p + ((o < 4) ? br[o] : bt[o - 4]);
       if (o == 4 || o == 5) v = v * zoom_factor[b * 4 + 0];
+      if (CLS && bad_class) v = o == 0 ? 1.f : 0.f;
       se3[b * 7 + o] = v;
     }
   }
+}
+
+__global__ __launch_bounds__(1024) void pose_head_kernel(const float* __restrict__ fc6, const float* __restrict__ w7,
+                                                         const float* __restrict__ b7, const float* __restrict__ wr,
+                                                         const float* __restrict__ br, const float* __restrict__ wt,
+                                                         const float* __restrict__ bt, const float* __restrict__ zoom_factor,
+                                                         float* __restrict__ se3, float* __restrict__ fc7_out) {
+  pose_head_body<false>(fc6, w7, b7, wr, br, wt, bt, nullptr, 1, zoom_factor, se3, fc7_out, nullptr);
+}
+
+__global__ __launch_bounds__(1024) void pose_head_cls_kernel(const float* __restrict__ fc6, const float* __restrict__ w7,
+                                                             const float* __restrict__ b7, const float* __restrict__ wr,
+                                                             const float* __restrict__ br, const float* __restrict__ wt,
+                                                             const float* __restrict__ bt, const int* __restrict__ class_index,
+                                                             int n_regressors, const float* __restrict__ zoom_factor,
+                                                             float* __restrict__ se3, float* __restrict__ fc7_out,
+                                                             int* __restrict__ status) {
+  pose_head_body<true>(fc6, w7, b7, wr, br, wt, bt, class_index, n_regressors, zoom_factor, se3, fc7_out, status);
 }
 
 }  // namespace dim
@@ -280,6 +314,19 @@ int dim_pose_head_fwd(const float* fc6, const float* fc7_w, const float* fc7_b, 
   hipLaunchKernelGGL(pose_head_kernel, dim3(B), dim3(1024), 0, as_stream(stream), fc6, fc7_w, fc7_b, rot_w, rot_b, trans_w,
                      trans_b, zoom_factor, se3, fc7_out);
   return check_launch("pose_head");
+}
+
+int dim_pose_head_fwd_cls(const float* fc6, const float* fc7_w, const float* fc7_b, const float* rot_w, const float* rot_b,
+                          const float* trans_w, const float* trans_b, const int* class_index, int n_regressors,
+                          const float* zoom_factor, float* se3, float* fc7_out, int* status, int B, void* stream) {
+  DIM_REQUIRE(n_regressors >= 1, "n_regressors must be >= 1 (got %d)", n_regressors);
+  if (n_regressors == 1) return dim_pose_head_fwd(fc6, fc7_w, fc7_b, rot_w, rot_b, trans_w, trans_b, zoom_factor, se3, fc7_out, B, stream);
+  DIM_REQUIRE(fc6 && fc7_w && fc7_b && rot_w && rot_b && trans_w && trans_b && zoom_factor && se3, "null pointer");
+  DIM_REQUIRE(class_index, "class_index is required with n_regressors > 1");
+  if (B == 0) return DIM_OK;
+  hipLaunchKernelGGL(pose_head_cls_kernel, dim3(B), dim3(1024), 0, as_stream(stream), fc6, fc7_w, fc7_b, rot_w, rot_b, trans_w, trans_b,
+                     class_index, n_regressors, zoom_factor, se3, fc7_out, status);
+  return check_launch("pose_head_cls");
 }
 
 }  // extern "C"

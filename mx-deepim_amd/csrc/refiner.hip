@@ -41,6 +41,7 @@ using namespace dim;
 
 struct dim_refiner {
   dim_refiner_desc d;
+  int n_regressors;   // 1: one rot / trans head; d.n_classes: one per class (rot (4K,256), trans (3K,256)), picked by class_index
   std::vector<void*> allocs;
   LayerPlan L[10];
   float *fc6_w, *fc6_b, *fc7_w, *fc7_b, *rot_w, *rot_b, *trans_w, *trans_b;
@@ -78,13 +79,21 @@ int dim_refiner_destroy(dim_refiner* r) {
 
 int dim_refiner_create(dim_refiner** out, const dim_refiner_desc* desc, const char* const* param_names, const float* const* param_ptrs,
                        int n_params, void* stream) {
+  return dim_refiner_create_cls(out, desc, 1, param_names, param_ptrs, n_params, stream);
+}
+
+int dim_refiner_create_cls(dim_refiner** out, const dim_refiner_desc* desc, int n_regressors, const char* const* param_names,
+                           const float* const* param_ptrs, int n_params, void* stream) {
   DIM_REQUIRE(out && desc && param_names && param_ptrs, "null pointer");
   const dim_refiner_desc& d = *desc;
+  DIM_REQUIRE(n_regressors == 1 || n_regressors == d.n_classes, "n_regressors must be 1 or the desc's n_classes %d (got %d)", d.n_classes,
+              n_regressors);
   DIM_REQUIRE(d.B > 0 && d.H == 480 && d.W == 640 && d.test_iter >= 1, "B > 0, H x W = 480 x 640, test_iter >= 1 required");
   DIM_REQUIRE(d.verts && d.uvs && d.faces && d.mesh_table && d.textures && d.tex_table && d.n_classes > 0 && d.vmax > 0 && d.fmax > 0,
               "mesh table missing");
   dim_refiner* r = new dim_refiner();
   r->d = d;
+  r->n_regressors = n_regressors;
   for (int c = 0; c < 3; ++c) r->plane_means[c] = d.pixel_means_bgr[2 - c];  // blob plane c holds BGR channel 2 - c
   const int B = d.B;
   int rc = DIM_OK;
@@ -249,7 +258,8 @@ int dim_refiner_run_k(dim_refiner* r, const float* image_observed, const float* 
     }
     TRY(dim_fc_fwd(x, r->fc6_w, r->fc6_b, r->fc6, r->workspace, B, 1024, 8, 10, 256, 0.1f, stream));
     // ---- fc7, rot, trans, inverse ZoomTrans -> se3 (:203-208, :956-971); RT_transform (tester.py:525-532)
-    TRY(dim_pose_head_fwd(r->fc6, r->fc7_w, r->fc7_b, r->rot_w, r->rot_b, r->trans_w, r->trans_b, r->zoom_factor, se3, nullptr, B, stream));
+    TRY(dim_pose_head_fwd_cls(r->fc6, r->fc7_w, r->fc7_b, r->rot_w, r->rot_b, r->trans_w, r->trans_b, class_index, r->n_regressors,
+                              r->zoom_factor, se3, nullptr, status, B, stream));
     TRY(dim_se3_compose(pose, se3, pose_out, nullptr, B, d.rot_coord, d.T_means, d.T_stds, stream));
     if (it < T - 1) {
       // ---- render + update_data_batch (tester.py:563-590, data_pair.py:103-114)

@@ -323,12 +323,23 @@ __global__ __launch_bounds__(kPmSymThreads) void pm_sym_grad_kernel(const float*
 //                                                                    here from fc7 (3 x 256 multiply-adds) so the forward keeps its outputs
 // MakeLoss(grad_scale = LW_ROT / LW_TRANS), no normalisation: the gradients are ADDED to d_rot_norm / d_ztrans (which hold the
 // point-matching gradients, or zeros); loss_sums[0..1] accumulate the un-scaled sums for the Rot_L2Loss / Trans_L2Loss metrics.
-__global__ void se3_dist_loss_grad_kernel(const float* __restrict__ rot_norm, const float* __restrict__ rot_gt, const float* __restrict__ fc7,
-                                          const float* __restrict__ wt, const float* __restrict__ bt, const float* __restrict__ ztrans_gt,
-                                          float* __restrict__ d_rot_norm, float* __restrict__ d_ztrans, int B, float lw_rot, float lw_trans,
-                                          int trans_type, float sl1, float* __restrict__ loss_sums) {
+// CLS (per-class regressors, heads.hip pose_head_body): wt (3K,256) / bt (3K), the sample recomputes with the rows of its class; a class
+// outside [0, K) contributes nothing.
+template <bool CLS>
+__device__ __forceinline__ void se3_dist_loss_grad_body(const float* __restrict__ rot_norm, const float* __restrict__ rot_gt,
+                                                        const float* __restrict__ fc7, const float* __restrict__ wt,
+                                                        const float* __restrict__ bt, const int* __restrict__ class_index,
+                                                        int n_regressors, const float* __restrict__ ztrans_gt,
+                                                        float* __restrict__ d_rot_norm, float* __restrict__ d_ztrans, int B, float lw_rot,
+                                                        float lw_trans, int trans_type, float sl1, float* __restrict__ loss_sums) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= B) return;
+  if constexpr (CLS) {
+    const int c = class_index[b];
+    if ((unsigned)c >= (unsigned)n_regressors) return;
+    wt += (long)c * 3 * 256;
+    bt += c * 3;
+  }
   const float* q = rot_norm + 4 * b;
   const float* g = rot_gt + 4 * b;
   const float dot = g[0] * q[0] + g[1] * q[1] + g[2] * q[2] + g[3] * q[3];
@@ -347,6 +358,23 @@ __global__ void se3_dist_loss_grad_kernel(const float* __restrict__ rot_norm, co
   }
 }
 
+__global__ void se3_dist_loss_grad_kernel(const float* __restrict__ rot_norm, const float* __restrict__ rot_gt, const float* __restrict__ fc7,
+                                          const float* __restrict__ wt, const float* __restrict__ bt, const float* __restrict__ ztrans_gt,
+                                          float* __restrict__ d_rot_norm, float* __restrict__ d_ztrans, int B, float lw_rot, float lw_trans,
+                                          int trans_type, float sl1, float* __restrict__ loss_sums) {
+  se3_dist_loss_grad_body<false>(rot_norm, rot_gt, fc7, wt, bt, nullptr, 1, ztrans_gt, d_rot_norm, d_ztrans, B, lw_rot, lw_trans, trans_type,
+                                 sl1, loss_sums);
+}
+
+__global__ void se3_dist_loss_grad_cls_kernel(const float* __restrict__ rot_norm, const float* __restrict__ rot_gt,
+                                              const float* __restrict__ fc7, const float* __restrict__ wt, const float* __restrict__ bt,
+                                              const int* __restrict__ class_index, int n_regressors, const float* __restrict__ ztrans_gt,
+                                              float* __restrict__ d_rot_norm, float* __restrict__ d_ztrans, int B, float lw_rot,
+                                              float lw_trans, int trans_type, float sl1, float* __restrict__ loss_sums) {
+  se3_dist_loss_grad_body<true>(rot_norm, rot_gt, fc7, wt, bt, class_index, n_regressors, ztrans_gt, d_rot_norm, d_ztrans, B, lw_rot, lw_trans,
+                                trans_type, sl1, loss_sums);
+}
+
 // ---------------------------------------------------------------------------------------------- pose head backward
 // L2Normalization(instance, eps=1e-10) forward: y = x / sqrt(sum x^2 + eps)
 __global__ void quat_normalize_kernel(const float* __restrict__ x, float* __restrict__ y, int B) {
@@ -358,13 +386,28 @@ __global__ void quat_normalize_kernel(const float* __restrict__ x, float* __rest
 }
 
 // one block per sample: d_rot_norm, d_trans -> d_rot (through L2Normalization), d_fc7 -> dz7 (LeakyReLU') -> d_fc6a -> dz6
-__global__ __launch_bounds__(256) void pose_head_bwd_kernel(const float* __restrict__ fc6a, const float* __restrict__ fc7,
-                                                            const float* __restrict__ rot_raw, const float* __restrict__ d_rot_norm,
-                                                            const float* __restrict__ d_trans, const float* __restrict__ w7,
-                                                            const float* __restrict__ wr, const float* __restrict__ wt,
-                                                            float* __restrict__ d_rot, float* __restrict__ dz7, float* __restrict__ dz6) {
+// CLS (per-class regressors): wr (4K,256) / wt (3K,256), the block reads the rows of class_index[b] (a workgroup-uniform offset); a
+// class outside [0, K) gives the sample zero d_rot / dz7 / dz6 rows.
+template <bool CLS>
+__device__ __forceinline__ void pose_head_bwd_body(const float* __restrict__ fc6a, const float* __restrict__ fc7,
+                                                   const float* __restrict__ rot_raw, const float* __restrict__ d_rot_norm,
+                                                   const float* __restrict__ d_trans, const float* __restrict__ w7,
+                                                   const float* __restrict__ wr, const float* __restrict__ wt,
+                                                   const int* __restrict__ class_index, int n_regressors, float* __restrict__ d_rot,
+                                                   float* __restrict__ dz7, float* __restrict__ dz6) {
   const int b = blockIdx.x, t = threadIdx.x;
   __shared__ float s_dr[4], s_dt[3], s_dz7[256];
+  if constexpr (CLS) {
+    const int c = class_index[b];
+    if ((unsigned)c >= (unsigned)n_regressors) {   // the whole block leaves together
+      if (t < 4) d_rot[4 * b + t] = 0.f;
+      dz7[(long)b * 256 + t] = 0.f;
+      dz6[(long)b * 256 + t] = 0.f;
+      return;
+    }
+    wr += (long)c * 4 * 256;
+    wt += (long)c * 3 * 256;
+  }
   if (t == 0) {
     const float* q = rot_raw + 4 * b;
     const float* g = d_rot_norm + 4 * b;
@@ -390,6 +433,24 @@ __global__ __launch_bounds__(256) void pose_head_bwd_kernel(const float* __restr
   dz6[(long)b * 256 + t] = g6;
 }
 
+__global__ __launch_bounds__(256) void pose_head_bwd_kernel(const float* __restrict__ fc6a, const float* __restrict__ fc7,
+                                                            const float* __restrict__ rot_raw, const float* __restrict__ d_rot_norm,
+                                                            const float* __restrict__ d_trans, const float* __restrict__ w7,
+                                                            const float* __restrict__ wr, const float* __restrict__ wt,
+                                                            float* __restrict__ d_rot, float* __restrict__ dz7, float* __restrict__ dz6) {
+  pose_head_bwd_body<false>(fc6a, fc7, rot_raw, d_rot_norm, d_trans, w7, wr, wt, nullptr, 1, d_rot, dz7, dz6);
+}
+
+__global__ __launch_bounds__(256) void pose_head_bwd_cls_kernel(const float* __restrict__ fc6a, const float* __restrict__ fc7,
+                                                                const float* __restrict__ rot_raw, const float* __restrict__ d_rot_norm,
+                                                                const float* __restrict__ d_trans, const float* __restrict__ w7,
+                                                                const float* __restrict__ wr, const float* __restrict__ wt,
+                                                                const int* __restrict__ class_index, int n_regressors,
+                                                                float* __restrict__ d_rot, float* __restrict__ dz7,
+                                                                float* __restrict__ dz6) {
+  pose_head_bwd_body<true>(fc6a, fc7, rot_raw, d_rot_norm, d_trans, w7, wr, wt, class_index, n_regressors, d_rot, dz7, dz6);
+}
+
 // dW[o][i] = sum_b A[b][o] * X[b][i];  db[o] = sum_b A[b][o]      (tiny fully-connected layers)
 __global__ void fc_wgrad_kernel(const float* __restrict__ A, const float* __restrict__ X, float* __restrict__ dW, float* __restrict__ db,
                                 int B, int Out, int In) {
@@ -404,6 +465,27 @@ __global__ void fc_wgrad_kernel(const float* __restrict__ A, const float* __rest
   }
   dW[idx] = s;
   if (i == 0 && db) db[o] = sb;
+}
+
+// the same for K per-class layers stacked along Out (per-class regressors): row r = c Out + o of dW (K Out, In) / db (K Out) sums the
+// samples of class c alone, in ascending b with fc_wgrad_kernel's multiply-adds -- bit for bit fc_wgrad_kernel over that sub-batch.  Every
+// row is written: zeros where the batch holds no sample of the class (a dense gradient, as MXNet's FullyConnected gives); a sample
+// whose class lies outside [0, K) matches no row.
+__global__ void fc_wgrad_cls_kernel(const float* __restrict__ A, const float* __restrict__ X, const int* __restrict__ class_index,
+                                    float* __restrict__ dW, float* __restrict__ db, int B, int K, int Out, int In) {
+  long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= (long)K * Out * In) return;
+  int i = (int)(idx % In), r = (int)(idx / In);
+  int o = r % Out, c = r / Out;
+  float s = 0.f, sb = 0.f;
+  for (int b = 0; b < B; ++b) {
+    if (class_index[b] != c) continue;
+    float a = A[(long)b * Out + o];
+    s = fmaf(a, X[(long)b * In + i], s);
+    sb += a;
+  }
+  dW[idx] = s;
+  if (i == 0 && db) db[r] = sb;
 }
 
 // fc6's weight gradient straight in the MXNet layout: dW[o][c HW + q] = sum_b dz[b][o] x[b][q][c]   (x NHWC: B x HW pixels x C channels;
@@ -948,6 +1030,25 @@ int dim_se3_dist_loss_grad(const float* rot_est_norm, const float* rot_gt, const
   return check_launch("se3_dist_loss_grad");
 }
 
+int dim_se3_dist_loss_grad_cls(const float* rot_est_norm, const float* rot_gt, const float* fc7, const float* trans_w,
+                               const float* trans_b, const int* class_index, int n_regressors, const float* zoom_trans_gt,
+                               float* d_rot_norm, float* d_zoom_trans, int B, float lw_rot, float lw_trans, int trans_loss_type,
+                               float smooth_l1_scalar, float* loss_sums2, void* stream) {
+  DIM_REQUIRE(n_regressors >= 1, "n_regressors must be >= 1 (got %d)", n_regressors);
+  if (n_regressors == 1)
+    return dim_se3_dist_loss_grad(rot_est_norm, rot_gt, fc7, trans_w, trans_b, zoom_trans_gt, d_rot_norm, d_zoom_trans, B, lw_rot, lw_trans,
+                                  trans_loss_type, smooth_l1_scalar, loss_sums2, stream);
+  DIM_REQUIRE(class_index, "class_index is required with n_regressors > 1");
+  if (B == 0) return DIM_OK;
+  DIM_REQUIRE(rot_est_norm && rot_gt && fc7 && trans_w && trans_b && zoom_trans_gt && d_rot_norm && d_zoom_trans, "null pointer");
+  DIM_REQUIRE(trans_loss_type >= 0 && trans_loss_type <= 2 && (trans_loss_type != 2 || smooth_l1_scalar > 0.f),
+              "trans_loss_type 0 L1 | 1 L2 | 2 smooth_L1 (scalar > 0)");
+  hipLaunchKernelGGL(se3_dist_loss_grad_cls_kernel, dim3(ceil_div(B, 64)), dim3(64), 0, as_stream(stream), rot_est_norm, rot_gt, fc7,
+                     trans_w, trans_b, class_index, n_regressors, zoom_trans_gt, d_rot_norm, d_zoom_trans, B, lw_rot, lw_trans,
+                     trans_loss_type, smooth_l1_scalar, loss_sums2);
+  return check_launch("se3_dist_loss_grad_cls");
+}
+
 int dim_quat_normalize(const float* rot, float* rot_norm, int B, void* stream) {
   if (B == 0) return DIM_OK;
   DIM_REQUIRE(rot && rot_norm, "null pointer");
@@ -965,11 +1066,36 @@ int dim_pose_head_bwd(const float* fc6a, const float* fc7, const float* rot_raw,
   return check_launch("pose_head_bwd");
 }
 
+int dim_pose_head_bwd_cls(const float* fc6a, const float* fc7, const float* rot_raw, const float* d_rot_norm, const float* d_trans,
+                          const float* fc7_w, const float* rot_w, const float* trans_w, const int* class_index, int n_regressors,
+                          float* d_rot, float* dz7, float* dz6, int B, void* stream) {
+  DIM_REQUIRE(n_regressors >= 1, "n_regressors must be >= 1 (got %d)", n_regressors);
+  if (n_regressors == 1) return dim_pose_head_bwd(fc6a, fc7, rot_raw, d_rot_norm, d_trans, fc7_w, rot_w, trans_w, d_rot, dz7, dz6, B, stream);
+  DIM_REQUIRE(class_index, "class_index is required with n_regressors > 1");
+  if (B == 0) return DIM_OK;
+  DIM_REQUIRE(fc6a && fc7 && rot_raw && d_rot_norm && d_trans && fc7_w && rot_w && trans_w && d_rot && dz7 && dz6, "null pointer");
+  hipLaunchKernelGGL(pose_head_bwd_cls_kernel, dim3(B), dim3(256), 0, as_stream(stream), fc6a, fc7, rot_raw, d_rot_norm, d_trans, fc7_w,
+                     rot_w, trans_w, class_index, n_regressors, d_rot, dz7, dz6);
+  return check_launch("pose_head_bwd_cls");
+}
+
 int dim_fc_wgrad(const float* dz, const float* x, float* dW, float* db, int B, int Out, int In, void* stream) {
   if (B == 0) return DIM_OK;
   DIM_REQUIRE(dz && x && dW, "null pointer");
   hipLaunchKernelGGL(fc_wgrad_kernel, dim3(ceil_div((long)Out * In, 256)), dim3(256), 0, as_stream(stream), dz, x, dW, db, B, Out, In);
   return check_launch("fc_wgrad");
+}
+
+int dim_fc_wgrad_cls(const float* dz, const float* x, const int* class_index, int n_regressors, float* dW, float* db, int B, int Out,
+                     int In, void* stream) {
+  DIM_REQUIRE(n_regressors >= 1, "n_regressors must be >= 1 (got %d)", n_regressors);
+  if (n_regressors == 1) return dim_fc_wgrad(dz, x, dW, db, B, Out, In, stream);
+  DIM_REQUIRE(class_index, "class_index is required with n_regressors > 1");
+  DIM_REQUIRE(dW && B >= 0 && Out >= 1 && In >= 1 && (B == 0 || (dz && x)), "null pointer or empty layer");
+  // B == 0 is launched too: the rows of every class are zeros then
+  hipLaunchKernelGGL(fc_wgrad_cls_kernel, dim3(ceil_div((long)n_regressors * Out * In, 256)), dim3(256), 0, as_stream(stream), dz, x,
+                     class_index, dW, db, B, n_regressors, Out, In);
+  return check_launch("fc_wgrad_cls");
 }
 
 // dW (Out, C*H*W in MXNet's (c, h, w) order) = dz (B, Out)^T . x (B, H, W, C NHWC), batches of up to 32 (see fc_wgrad_nhwc_kernel)

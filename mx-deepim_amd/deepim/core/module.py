@@ -327,7 +327,7 @@ class MutableModule(object):
             ops.zoom_planes(batch["flow"], net.zoom_factor, scale_mode=1, out=self.zoom_flow_lab)          # ZoomFlow :689-698
             ops.zoom_planes(batch["flow_weights"], net.zoom_factor, post=2, out=self.zoom_flow_w)
         net.encoder()
-        net.head()                                               # se3 = [rot (raw), inverse-zoomed trans]; fc7
+        net.head(class_index=self._cls(batch))                   # se3 = [rot (raw), inverse-zoomed trans]; fc7
         ops.copy_nhwc_channels(self.rot_raw, 0, net.se3, 0, 4)
         ops.quat_normalize(self.rot_raw, out=self.rot_norm)   # L2Normalization :375
         p = self.w
@@ -350,10 +350,18 @@ class MutableModule(object):
             out["mask_logit"] = self.mask_logit
         return out
 
+    def _cls(self, batch):
+        """the batch's class_index as the per-class heads read it (network.REGRESSOR_NUM > 1), None for the shared head"""
+        if self.net.n_regressors == 1:
+            return None
+        cls = batch["class_index"]
+        return cls if cls.dtype == torch.int32 else cls.to(torch.int32)
+
     def backward(self, batch):
         cfg, net, w, g = self.cfg, self.net, self.w, self.g
         ti = cfg.train_iter
         B = self.B
+        K, cls = net.n_regressors, self._cls(batch)
         # collectives of a previous backward() that no update() consumed still read / write flat_g (flat_g16) in place on the
         # communicator's stream: wait for them before this pass rewrites the gradients
         for work, _, _ in self._pending:
@@ -386,17 +394,27 @@ class MutableModule(object):
             d_t = torch.zeros((B, 3), dtype=torch.float32, device=self.device)
         if ti.SE3_DIST_LOSS:   # :396-437; labels "rot" / "trans" = calc_RT_delta(src, gt) as the data layer delivers them (data_pair.py:201-251)
             zt_gt = ops.zoom_trans(net.zoom_factor, batch["trans"].contiguous(), 1)   # ZoomTrans, b_inv_zoom False (:659-665)
-            ops.se3_dist_loss_grad(self.rot_norm, batch["rot"].contiguous(), net.fc7, w, zt_gt, d_rn, d_t, ti.LW_ROT, ti.LW_TRANS,
-                                   ti.TRANS_LOSS_TYPE, ti.TRANS_SMOOTH_L1_SCALAR, loss_sums2=self.loss_sums[3:5])
+            if K > 1:
+                ops.se3_dist_loss_grad_cls(self.rot_norm, batch["rot"].contiguous(), net.fc7, w, cls, K, zt_gt, d_rn, d_t, ti.LW_ROT,
+                                           ti.LW_TRANS, ti.TRANS_LOSS_TYPE, ti.TRANS_SMOOTH_L1_SCALAR, loss_sums2=self.loss_sums[3:5])
+            else:
+                ops.se3_dist_loss_grad(self.rot_norm, batch["rot"].contiguous(), net.fc7, w, zt_gt, d_rn, d_t, ti.LW_ROT, ti.LW_TRANS,
+                                       ti.TRANS_LOSS_TYPE, ti.TRANS_SMOOTH_L1_SCALAR, loss_sums2=self.loss_sums[3:5])
+        self.d_rot_norm, self.d_trans = d_rn, d_t   # the pose head's incoming gradients, kept for inspection
         d10 = self.dacts["conv6_1"]
         if self.has_decoder:
             self._decoder_backward()
         # ---------------- pose head (fc7, rot, trans, fc6)
         fc6a = net.fc6.view(B, 256)
         msk = self.lrelu_mask_from.net if self.lrelu_mask_from is not None else net   # whose activation signs gate the gradients
-        ops.pose_head_bwd(msk.fc6.view(B, 256), msk.fc7, self.rot_raw, d_rn, d_t, w, self.d_rot, self.dz7, self.dz6)
-        ops.fc_wgrad(self.d_rot, net.fc7, g["rot_weight"], g["rot_bias"])
-        ops.fc_wgrad(d_t, net.fc7, g["trans_weight"], g["trans_bias"])
+        if K > 1:   # per-class heads: each sample through its class's rows; dense gradients, zeros for a class the batch does not hold
+            ops.pose_head_bwd_cls(msk.fc6.view(B, 256), msk.fc7, self.rot_raw, d_rn, d_t, w, cls, K, self.d_rot, self.dz7, self.dz6)
+            ops.fc_wgrad_cls(self.d_rot, net.fc7, cls, K, g["rot_weight"], g["rot_bias"])
+            ops.fc_wgrad_cls(d_t, net.fc7, cls, K, g["trans_weight"], g["trans_bias"])
+        else:
+            ops.pose_head_bwd(msk.fc6.view(B, 256), msk.fc7, self.rot_raw, d_rn, d_t, w, self.d_rot, self.dz7, self.dz6)
+            ops.fc_wgrad(self.d_rot, net.fc7, g["rot_weight"], g["rot_bias"])
+            ops.fc_wgrad(d_t, net.fc7, g["trans_weight"], g["trans_bias"])
         ops.fc_wgrad(self.dz7, fc6a, g["fc7_weight"], g["fc7_bias"])
         dz6 = self.dz6.view(B, 1, 1, 256)
         if B <= 32:   # 16 products per element: one 84 MB write in the MXNet layout (f32) instead of the packed "convolution" + conversion

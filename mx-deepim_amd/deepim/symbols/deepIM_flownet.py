@@ -62,6 +62,25 @@ def input_channels(cfg):
     return c
 
 
+def regressor_num(cfg):
+    """network.REGRESSOR_NUM, checked (the one place train and test share): 1 = one class-agnostic rot / trans head; K =
+    len(dataset.class_name) = one head per class behind the shared fc6 / fc7 -- rot_weight (4K,256), rot_bias (4K,), trans_weight
+    (3K,256), trans_bias (3K,), class c owning rows 4c..4c+3 / 3c..3c+2 (one FullyConnected(num_hidden=4K) reshaped to (B,K,4) and picked
+    by class_index)."""
+    k = cfg.network.get("REGRESSOR_NUM", 1)
+    n_cls = len(cfg.dataset.class_name)
+    if isinstance(k, bool) or not float(k).is_integer() or int(k) not in (1, n_cls):
+        raise ValueError("network.REGRESSOR_NUM must be 1 or the number of classes len(dataset.class_name) = {}, got {!r}".format(n_cls, k))
+    k = int(k)
+    if k > 1 and cfg.network.ROT_TYPE != "QUAT":
+        raise ValueError("network.REGRESSOR_NUM = {} needs network.ROT_TYPE 'QUAT' (the only rotation the per-class head kernels "
+                         "produce), got {!r}".format(k, cfg.network.ROT_TYPE))
+    return k
+
+
+HEAD_ROWS = {"rot_weight": 4, "rot_bias": 4, "trans_weight": 3, "trans_bias": 3}   # rows of one class's block
+
+
 class deepIM_flownet(object):
     def __init__(self):
         self.eps = 1e-5
@@ -81,10 +100,11 @@ class deepIM_flownet(object):
         shp["fc6_bias"] = (256,)
         shp["fc7_weight"] = (256, 256)
         shp["fc7_bias"] = (256,)
-        shp["rot_weight"] = (4 if cfg.network.ROT_TYPE == "QUAT" else 3, 256)
+        K = regressor_num(cfg)
+        shp["rot_weight"] = ((4 if cfg.network.ROT_TYPE == "QUAT" else 3) * K, 256)
         shp["rot_bias"] = (shp["rot_weight"][0],)
-        shp["trans_weight"] = (3, 256)
-        shp["trans_bias"] = (3,)
+        shp["trans_weight"] = (3 * K, 256)
+        shp["trans_bias"] = (3 * K,)
         if cfg.network.PRED_FLOW or cfg.network.PRED_MASK:
             shp["Convolution1_weight"] = (2, 1024, 3, 3)
             shp["Convolution1_bias"] = (2,)
@@ -146,6 +166,17 @@ class deepIM_flownet(object):
             for k in ("fc6_bias", "fc6_weight", "fc7_bias", "fc7_weight", "rot_bias", "rot_weight", "trans_bias", "trans_weight",
                       "upsampling_weight", "mask_conv3_bias", "mask_conv3_weight", "mask_upsampling_weight"):
                 arg_params.pop(k, None)
+        # a class-agnostic checkpoint under REGRESSOR_NUM = K > 1: every class starts as the shared head (its block tiled K times);
+        # the other direction has no meaning
+        K = regressor_num(cfg)
+        for k, rows in HEAD_ROWS.items():
+            have, want = np.shape(arg_params[k]) if k in arg_params else None, self.arg_shape_dict[k]
+            if have is None or tuple(have) == tuple(want):
+                continue
+            if K > 1 and tuple(have) == (rows,) + tuple(want[1:]):
+                arg_params[k] = np.tile(np.asarray(arg_params[k], dtype=np.float32), (K,) + (1,) * (len(want) - 1))
+            else:
+                raise ValueError("{}: the checkpoint holds {} but network.REGRESSOR_NUM = {} needs {}".format(k, tuple(have), K, tuple(want)))
         for k, shp in self.arg_shape_dict.items():
             if k in arg_params:
                 continue
@@ -156,7 +187,8 @@ class deepIM_flownet(object):
                 arg_params[k] = self.bilinear_kernel(shp)
             elif k == "rot_weight":
                 w = rng.rand(*shp) * 0.01
-                w[0, :] = rng.rand(shp[1]) + 0.01
+                for r0 in range(0, shp[0], shp[0] // K):   # row 0 of every class's block (K = 1: the draws of the shared head)
+                    w[r0, :] = rng.rand(shp[1]) + 0.01
                 arg_params[k] = w.astype(np.float32)
             elif k == "trans_weight":
                 arg_params[k] = np.zeros(shp, dtype=np.float32)
@@ -198,6 +230,12 @@ class FlowNetHip(object):
         self.B = batch_size
         self.device = torch.device(device)
         self.cin = input_channels(cfg)
+        self.n_regressors = regressor_num(cfg)
+        want = deepIM_flownet().infer_param_shapes(cfg)
+        for k in HEAD_ROWS:
+            if tuple(np.shape(arg_params[k])) != tuple(want[k]):
+                raise ValueError("{} has shape {} but network.REGRESSOR_NUM = {} needs {}".format(
+                    k, tuple(np.shape(arg_params[k])), self.n_regressors, tuple(want[k])))
         # first-layer input arities of get_convs (reference :33-66).  The device tensor X always has 8 NHWC channels:
         #   mode 0  images + masks            (INPUT_MASK and PRED_MASK; the shipped graph)
         #   mode 1  images only, 2 zero lanes (no masks in the Concat: Cin = 6; the weights of the two spare lanes are zero)
@@ -477,9 +515,13 @@ class FlowNetHip(object):
             x = out
         return dict(self.conv_plan)
 
-    def head(self, se3=None):
-        return ops.pose_head_fwd(self.fc6.view(self.B, 256), self.params, self.zoom_factor, se3=self.se3 if se3 is None else se3,
-                                 fc7_out=self.fc7)
+    def head(self, se3=None, class_index=None, status=None):
+        """class_index (B,) int32: which head each sample reads when network.REGRESSOR_NUM > 1 (not read otherwise)"""
+        se3 = self.se3 if se3 is None else se3
+        if self.n_regressors > 1:
+            return ops.pose_head_fwd_cls(self.fc6.view(self.B, 256), self.params, class_index, self.n_regressors, self.zoom_factor, se3=se3,
+                                         fc7_out=self.fc7, status=self.status if status is None else status)
+        return ops.pose_head_fwd(self.fc6.view(self.B, 256), self.params, self.zoom_factor, se3=se3, fc7_out=self.fc7)
 
     def decoder(self):
         """get_convs :213-299: Convolution1, deconv5 (+Crop, LeakyReLU), upsample_flow6to5, Concat2, Convolution2, deconv4,
@@ -525,7 +567,7 @@ class FlowNetHip(object):
         iteration) and receive se3 / status straight in its per-iteration buffers -- no copies between iterations."""
         self.zoom(batch, bbox_ren=bbox_ren, bbox_obs=bbox_obs, src_pose=src_pose, status=status_out)
         self.encoder()
-        se3 = self.head(se3=se3_out)
+        se3 = self.head(se3=se3_out, class_index=batch.get("class_index"), status=status_out)
         out = {"se3_output": se3, "zoom_factor": self.zoom_factor}
         cfg = self.cfg
         if self.has_decoder and not cfg.TEST.FAST_TEST and (cfg.network.PRED_MASK or cfg.network.PRED_FLOW):

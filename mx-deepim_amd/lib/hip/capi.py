@@ -58,6 +58,7 @@ SIGNATURES = {
     "dim_bop_errors_workspace_bytes": (L, [I, I, I]),
     "dim_bop_errors": (I, [P, P, P, P, I, P, P, P, P, P, P, I, I, I, P, P, P, P, P]),
     "dim_refiner_create": (I, [P, P, P, P, I, P]),
+    "dim_refiner_create_cls": (I, [P, P, I, P, P, I, P]),
     "dim_refiner_run": (I, [P, P, P, P, P, P, P, P, P, P, P]),
     "dim_refiner_run_k": (I, [P, P, P, P, P, P, P, P, P, P, P, P]),
     "dim_refiner_destroy": (I, [P]),
@@ -170,6 +171,10 @@ SIGNATURES = {
     "dim_lrelu_bwd_bias_grad": (I, [P, I, I, P, I, I, P, P, I, I, F, I, P]),
     "dim_fc_pack_weight": (I, [P, P, I, I, I, I, P]),
     "dim_pose_head_fwd": (I, [P, P, P, P, P, P, P, P, P, P, I, P]),
+    "dim_pose_head_fwd_cls": (I, [P, P, P, P, P, P, P, P, I, P, P, P, P, I, P]),
+    "dim_pose_head_bwd_cls": (I, [P, P, P, P, P, P, P, P, P, I, P, P, P, I, P]),
+    "dim_se3_dist_loss_grad_cls": (I, [P, P, P, P, P, P, I, P, P, P, I, F, F, I, F, P, P]),
+    "dim_fc_wgrad_cls": (I, [P, P, P, I, P, P, I, I, I, P]),
 }
 
 _lib = None

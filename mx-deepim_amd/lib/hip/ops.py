@@ -1000,6 +1000,29 @@ def pose_head_fwd(fc6, p, zf, se3=None, fc7_out=None):
     return se3
 
 
+def _cls_arg(class_index, B, K):
+    if class_index is None:
+        if K > 1:
+            raise ValueError("{} per-class pose heads need the batch's class_index".format(K))
+        return None
+    assert class_index.numel() == B, (class_index.numel(), B)
+    return dptr(class_index, i32)
+
+
+def pose_head_fwd_cls(fc6, p, class_index, n_regressors, zf, se3=None, fc7_out=None, status=None):
+    """dim_pose_head_fwd_cls: pose_head_fwd with one rot / trans head per class (p: rot (4K,256) / (4K), trans (3K,256) / (3K)); sample
+    b reads the rows of class_index[b] ((B,) int32; None allowed with n_regressors 1).  DIM_STATUS_BAD_CLASS is OR-ed into status (B,)
+    int32 when given, for a class outside [0, K) (identity delta)."""
+    B, K = fc6.shape[0], int(n_regressors)
+    se3 = se3 if se3 is not None else _new((B, 7), fc6)
+    assert status is None or status.numel() == B
+    check(lib().dim_pose_head_fwd_cls(dptr(fc6, f32), dptr(p["fc7_weight"], f32), dptr(p["fc7_bias"], f32), dptr(p["rot_weight"], f32),
+                                      dptr(p["rot_bias"], f32), dptr(p["trans_weight"], f32), dptr(p["trans_bias"], f32),
+                                      _cls_arg(class_index, B, K), K, dptr(zf, f32), dptr(se3, f32), dptr(fc7_out, f32), _opt(status, i32),
+                                      B, current_stream()))
+    return se3
+
+
 # ---------------------------------------------------------------- decoder pieces (deepIM_flownet.py:213-299, :315-340, :502-529)
 def pad32(c):
     return (c + 31) // 32 * 32
@@ -1310,6 +1333,16 @@ def se3_dist_loss_grad(rot_est_norm, rot_gt, fc7, p, zoom_trans_gt, d_rot_norm, 
                                        float(smooth_l1_scalar), dptr(loss_sums2, f32), current_stream()))
 
 
+def se3_dist_loss_grad_cls(rot_est_norm, rot_gt, fc7, p, class_index, n_regressors, zoom_trans_gt, d_rot_norm, d_zoom_trans, lw_rot, lw_trans,
+                           trans_loss_type="L2", smooth_l1_scalar=3.0, loss_sums2=None):
+    """se3_dist_loss_grad with per-class trans heads (3K,256) / (3K): zoom_trans_est of sample b from the rows of class_index[b]"""
+    B, K = rot_est_norm.shape[0], int(n_regressors)
+    check(lib().dim_se3_dist_loss_grad_cls(dptr(rot_est_norm, f32), dptr(rot_gt, f32), dptr(fc7, f32), dptr(p["trans_weight"], f32),
+                                           dptr(p["trans_bias"], f32), _cls_arg(class_index, B, K), K, dptr(zoom_trans_gt, f32),
+                                           dptr(d_rot_norm, f32), dptr(d_zoom_trans, f32), B, float(lw_rot), float(lw_trans),
+                                           LOSS_TYPE_ID[trans_loss_type], float(smooth_l1_scalar), dptr(loss_sums2, f32), current_stream()))
+
+
 def quat_normalize(rot, out=None):
     out = out if out is not None else torch.empty_like(rot)
     check(lib().dim_quat_normalize(dptr(rot, f32), dptr(out, f32), rot.shape[0], current_stream()))
@@ -1324,6 +1357,22 @@ def pose_head_bwd(fc6a, fc7, rot_raw, d_rot_norm, d_trans, p, d_rot, dz7, dz6):
 
 def fc_wgrad(dz, x, dW, db=None):
     check(lib().dim_fc_wgrad(dptr(dz, f32), dptr(x, f32), dptr(dW, f32), dptr(db, f32), dz.shape[0], dz.shape[1], x.shape[1], current_stream()))
+
+
+def pose_head_bwd_cls(fc6a, fc7, rot_raw, d_rot_norm, d_trans, p, class_index, n_regressors, d_rot, dz7, dz6):
+    """pose_head_bwd through the rot (4K,256) / trans (3K,256) rows of each sample's class"""
+    B, K = fc6a.shape[0], int(n_regressors)
+    check(lib().dim_pose_head_bwd_cls(dptr(fc6a, f32), dptr(fc7, f32), dptr(rot_raw, f32), dptr(d_rot_norm, f32), dptr(d_trans, f32),
+                                      dptr(p["fc7_weight"], f32), dptr(p["rot_weight"], f32), dptr(p["trans_weight"], f32),
+                                      _cls_arg(class_index, B, K), K, dptr(d_rot, f32), dptr(dz7, f32), dptr(dz6, f32), B, current_stream()))
+
+
+def fc_wgrad_cls(dz, x, class_index, n_regressors, dW, db=None):
+    """dW (K Out, In) / db (K Out): class c's rows = fc_wgrad over the samples of class c; zeros for a class the batch does not hold"""
+    B, K = dz.shape[0], int(n_regressors)
+    assert tuple(dW.shape) == (K * dz.shape[1], x.shape[1]) and (db is None or db.numel() == K * dz.shape[1])
+    check(lib().dim_fc_wgrad_cls(dptr(dz, f32), dptr(x, f32), _cls_arg(class_index, B, K), K, dptr(dW, f32), dptr(db, f32), B, dz.shape[1],
+                                 x.shape[1], current_stream()))
 
 
 def upsample16_bwd(dout_nchw, w_c1_32_32, df_nhwc, crop=8, scale=1.0):

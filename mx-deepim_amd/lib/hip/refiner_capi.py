@@ -1,4 +1,4 @@
-"""ctypes face of the resident-loop C entry points (include/deepim_hip.h: dim_refiner_create / _run / _run_k / _destroy).
+"""ctypes face of the resident-loop C entry points (include/deepim_hip.h: dim_refiner_create / _create_cls / _run / _run_k / _destroy).
 
 This is what a host WITHOUT torch binds (INTEGRATION.md shows the same struct for C / cgo callers); torch is used here only to own
 the device memory of the arguments, exactly as in the rest of lib/hip."""
@@ -47,7 +47,14 @@ class CRefiner(object):
         cnames = (ctypes.c_char_p * len(names))(*[n.encode() for n in names])
         cptrs = (ctypes.c_void_p * len(names))(*[self.params[n].data_ptr() for n in names])
         self._h = ctypes.c_void_p()
-        check(lib().dim_refiner_create(ctypes.byref(self._h), ctypes.byref(d), cnames, cptrs, len(names), current_stream()))
+        K = int(cfg.network.get("REGRESSOR_NUM", 1))   # the library checks it against the mesh table's class count
+        if tuple(self.params["rot_weight"].shape) != (4 * K, 256) or tuple(self.params["trans_weight"].shape) != (3 * K, 256):
+            raise ValueError("rot_weight {} / trans_weight {}: network.REGRESSOR_NUM = {} needs ({}, 256) / ({}, 256)".format(
+                tuple(self.params["rot_weight"].shape), tuple(self.params["trans_weight"].shape), K, 4 * K, 3 * K))
+        if K > 1:   # one rot / trans head per class: run() picks each pair's by the class_index it receives
+            check(lib().dim_refiner_create_cls(ctypes.byref(self._h), ctypes.byref(d), K, cnames, cptrs, len(names), current_stream()))
+        else:
+            check(lib().dim_refiner_create(ctypes.byref(self._h), ctypes.byref(d), cnames, cptrs, len(names), current_stream()))
         torch.cuda.synchronize(self.device)
         self.poses_iter = torch.zeros((self.T, self.B, 3, 4), dtype=torch.float32, device=self.device)
         self.se3_iter = torch.zeros((self.T, self.B, 7), dtype=torch.float32, device=self.device)
