@@ -500,6 +500,18 @@ int dim_winograd_gemm_tile_planes(int Cout, long tiles, int planes);      /* pla
  * (dim_winograd*_packed_weight_floats counts them).  Takes effect when a layer is next planned (launch or graph capture). */
 int dim_set_winograd_split(int on);
 int dim_get_winograd_split(void);
+/* The plane GEMM of the Winograd layers on its own, planned and run exactly as the layers do (stream-K ranges, shared-tile atomics,
+ * the arithmetic dim_set_winograd_split selects): M[t][p][:] = V[t][p][:] . U_p for P planes.  V [T][P][K], M [T][P][Cout], U_packed =
+ * U in the chunk layout [P][K/32][Cout][32] (element (p, k, co) at ((p * K/32 + k/32) * Cout + co) * 32 + k % 32) with room for its
+ * three-term image behind it: dim_winograd_plane_gemm_weight_floats floats = P*K*Cout + 6 bytes per weight;
+ * dim_winograd_plane_gemm_split_weights writes that image from the first P*K*Cout floats (once per change of U).  tile: 3 .. 7 as
+ * dim_winograd_gemm_tile_planes returns them; *used_split (host) = 1 if the three-term kernel ran (tiles 4, 5, 7 with the switch on).
+ * The tests' entry to the arithmetic of one K chunk.  K % 32 != 0, Cout % 64 != 0, a size < 1, a NULL or a host pointer return
+ * DIM_ERR_ARG before anything is enqueued. */
+long dim_winograd_plane_gemm_weight_floats(int K, int Cout, int P);
+int dim_winograd_plane_gemm_split_weights(float* U_packed, int K, int Cout, int P, void* stream);
+int dim_winograd_plane_gemm(const float* V, const float* U_packed, float* M, int T, int K, int Cout, int P, int tile, int* used_split,
+                            void* stream);
 int dim_conv2d_fwd_ex(const float* x, const float* w_packed, const float* bias, float* y, int N, int H, int W, int Cin, int in_cstride,
                       int Cout, int KH, int KW, int stride, int pad, float slope, int tile, int out_cstride, int out_coff, int OH,
                       int OW, int osy, int osx, int ooy, int oox, int Ho, int Wo, int pad_w, int accumulate, void* stream);

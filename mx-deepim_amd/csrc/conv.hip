@@ -150,6 +150,38 @@ int dim_set_winograd_split(int on) {
 }
 int dim_get_winograd_split(void) { return wino_get_split(); }
 
+// The plane GEMM of the Winograd layers on its own (wino_gemm.hip / wino_gemm_split.hip), as the layers plan and run it: the entry the
+// tests use to pin the arithmetic of one K chunk, which no layer-level bar sees (tests/test_gpu_split_gemm.py).
+static bool plane_gemm_on_device(const void* p) {
+  hipPointerAttribute_t at;
+  const hipError_t e = hipPointerGetAttributes(&at, p);
+  if (e != hipSuccess) (void)hipGetLastError();   // a plain host pointer is reported as an error by some runtimes: not a sticky one
+  return e == hipSuccess && (at.type == hipMemoryTypeDevice || at.type == hipMemoryTypeManaged);
+}
+long dim_winograd_plane_gemm_weight_floats(int K, int Cout, int P) {
+  if (K <= 0 || Cout <= 0 || P <= 0) return 0;
+  return wino_packed_with_split((long)P * K * Cout);
+}
+int dim_winograd_plane_gemm_split_weights(float* U_packed, int K, int Cout, int P, void* stream) {
+  DIM_REQUIRE(K > 0 && K % 32 == 0 && Cout > 0 && Cout % 64 == 0 && P > 0, "winograd plane gemm: K %% 32 == 0 and Cout %% 64 == 0 required");
+  DIM_REQUIRE(U_packed, "null pointer");
+  DIM_REQUIRE(plane_gemm_on_device(U_packed), "winograd plane gemm: U_packed is not a device pointer");
+  return wino_split_weights(U_packed, (long)P * (K / 32), Cout, as_stream(stream));
+}
+int dim_winograd_plane_gemm(const float* V, const float* U_packed, float* M, int T, int K, int Cout, int P, int tile, int* used_split,
+                            void* stream) {
+  DIM_REQUIRE(T > 0 && K > 0 && K % 32 == 0 && Cout > 0 && Cout % 64 == 0 && P > 0,
+              "winograd plane gemm: T, P > 0, K %% 32 == 0 and Cout %% 64 == 0 required");
+  DIM_REQUIRE(V && U_packed && M && used_split, "null pointer");
+  DIM_REQUIRE(plane_gemm_on_device(V) && plane_gemm_on_device(U_packed) && plane_gemm_on_device(M),
+              "winograd plane gemm: V, U_packed and M must be device pointers");
+  WGemmArgs plan;
+  const int rc = wino_gemm_plan(&plan, V, U_packed, M, T, K, Cout, P, tile);
+  if (rc != DIM_OK) return rc;
+  *used_split = plan.split;
+  return wino_gemm_run(plan, /*zeroed=*/false, as_stream(stream));
+}
+
 // workgroup tile of a Winograd layer's plane GEMMs (wino_gemm.hip): 5 = 128 rows x 256 output channels (V is streamed once per 256
 // channels: conv3, conv3_1, conv4_1), 4 = 128 x 128 (conv2: Cout = 128); for the few-row layers (under 1024 tile rows: conv5 .. conv6_1)
 // the tile that wastes the fewest MFMA cycles on padded rows -- 6 = 160 x 128 (conv5, conv5_1: 320 rows at 16 pairs), 7 = 96 x 128

@@ -251,7 +251,8 @@ __global__ __launch_bounds__(512) void conv1_halo_bf16_kernel(ConvArgs a, int ti
 // ---------------------------------------------------------------------------------------------------------------- first layer, three terms
 // flow_conv1 with f32 operands on the bf16 matrix pipe: every weight and every input value is the exact sum of three bf16 terms and a
 // product keeps the six largest term products, accumulated in f32 -- the arithmetic of wino_gemm_split.hip (error <= 3 * 2^-27 per
-// product, below f32's own rounding of the sum).  On the f32 pipe this layer is bound by its 392 MFMAs of 64 cycles per 32 x 64 block
+// product, below f32's own rounding of the sum; pinned by tests/test_gpu_split_conv1.py: one packed chunk of taps at a time, every
+// output against float64 in units of its sum |x w|).  On the f32 pipe this layer is bound by its 392 MFMAs of 64 cycles per 32 x 64 block
 // (conv1_halo_kernel: 0.60 ms at 16 pairs, 102 TFLOP/s); six MFMAs of 32 cycles per tap pair are 2.2x fewer pipe cycles.
 // The three-term weights of all 64 output channels (150 KB) do not fit LDS beside a patch, and streamed per wave from L2 they are the
 // bound (conv1_halo_bf16_kernel's note).  So a PERSISTENT 8-wave workgroup owns HALF the output channels: its 76.8 KB of weights stay in

@@ -4,9 +4,11 @@
 //      x y  ~  h h' + (h m' + m h') + (h l' + m m' + l h')          dropped: m l' + l m' + l l'  <=  3 * 2^-27 |x y|,
 // each exact in the f32 accumulator's input (8 x 8 significant bits), accumulated in f32 by v_mfma_f32_32x32x16_bf16.  Six MFMAs
 // of 32 cycles replace the sixteen 64-cycle v_mfma_f32_32x32x2_f32 of a 32 x 32 x 32 block: 2.67x the f32 matrix rate at an error
-// below f32's own rounding of the sum -- the parity bars of tests/ (2e-5 on a pose step against the f64-accumulating oracle) hold
-// unchanged; every Winograd test of tests/test_gpu_ops.py runs both arithmetics (`wino_split` fixture), tests/test_split_terms.py
-// asserts the bounds on the CPU.  (deepim/symbols/deepIM_flownet.py:95-191 are the layers.)
+// below f32's own rounding of the sum.  What pins it: tests/test_gpu_split_gemm.py calls this GEMM directly (dim_winograd_plane_gemm)
+// at K = 32 and compares every output with float64 in units of its sum |x y|, under a bar that one term product missing from one
+// k-step exceeds (the numpy model and the negative controls: tests/test_split_terms.py, no GPU).  The layer tests of
+// tests/test_gpu_ops.py run both arithmetics (`wino_split` fixture) but their bar, 1e-4 of max|y|, does NOT see such a defect.
+// (deepim/symbols/deepIM_flownet.py:95-191 are the layers.)
 //
 // Operands:
 //   V [T][P][K] f32  as in wino_gemm.hip; split by the staging threads on the way into LDS (11 VALU ops per pair of floats)

@@ -123,6 +123,9 @@ SIGNATURES = {
     "dim_winograd_gemm_tile_planes": (I, [I, L, I]),
     "dim_set_winograd_split": (I, [I]),
     "dim_get_winograd_split": (I, []),
+    "dim_winograd_plane_gemm_weight_floats": (L, [I, I, I]),
+    "dim_winograd_plane_gemm_split_weights": (I, [P, I, I, I, P]),
+    "dim_winograd_plane_gemm": (I, [P, P, P, I, I, I, I, I, P, P]),
     "dim_winograd_packed_weight_floats": (L, [I, I, I]),
     "dim_winograd_workspace_floats": (L, [I, I, I, I, I, I]),
     "dim_winograd_pack_weight": (I, [P, P, I, I, I, P]),

@@ -785,6 +785,23 @@ def get_winograd_split():
     return bool(lib().dim_get_winograd_split())
 
 
+def winograd_plane_gemm(V, U_pkn, T, K, Cout, P, tile, out=None):
+    """the plane GEMM of the Winograd layers on its own (dim_winograd_plane_gemm): M[t][p] = V[t][p] . U_pkn[p] for V (T, P, K) and
+    U_pkn (P, K, Cout), in the arithmetic set_winograd_split selects.  Returns (M (T, P, Cout), used_split); `out`: M to write into."""
+    import ctypes
+
+    assert tuple(V.shape) == (T, P, K) and tuple(U_pkn.shape) == (P, K, Cout) and K % 32 == 0, (V.shape, U_pkn.shape)
+    n = P * K * Cout
+    wp = _new((lib().dim_winograd_plane_gemm_weight_floats(K, Cout, P),), V)
+    wp[:n] = U_pkn.reshape(P, K // 32, 32, Cout).permute(0, 1, 3, 2).reshape(-1)      # -> the chunk layout [P][K/32][Cout][32]
+    check(lib().dim_winograd_plane_gemm_split_weights(dptr(wp, f32), K, Cout, P, current_stream()))
+    out = out if out is not None else _new((T, P, Cout), V)
+    used = ctypes.c_int(-1)
+    check(lib().dim_winograd_plane_gemm(dptr(V, f32), dptr(wp, f32), dptr(out, f32), T, K, Cout, P, int(tile), ctypes.byref(used),
+                                        current_stream()))
+    return out, used.value
+
+
 def winograd_pack_weight(w_oihw, m=2):
     """(Cout,Cin,3,3) -> the (m+2)^2 transformed 1x1 weight sets of the Winograd F(m x m, 3x3) path, m = 2 or 4"""
     Cout, Cin, KH, KW = w_oihw.shape

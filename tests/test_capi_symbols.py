@@ -27,6 +27,19 @@ def test_pure_host_queries(hip_lib):
     # f32 image + the three-term bf16 image behind it (6 bytes per weight): x 5 / 2
     assert hip_lib.dim_winograd_packed_weight_floats(256, 128, 4) == 36 * 256 * 128 * 5 // 2
     assert hip_lib.dim_winograd_packed_weight_floats(256, 128, 2) == 16 * 256 * 128 * 5 // 2
+    # the raw plane GEMM's weight buffer: the same count for the same planes x K x Cout
+    assert hip_lib.dim_winograd_plane_gemm_weight_floats(128, 256, 36) == hip_lib.dim_winograd_packed_weight_floats(256, 128, 4)
+    assert hip_lib.dim_winograd_plane_gemm_weight_floats(32, 64, 81) == 81 * 32 * 64 * 5 // 2
+    assert hip_lib.dim_winograd_plane_gemm_weight_floats(32, 64, 0) == 0
+    # ... and its argument errors that need no device: geometry first, then null pointers
+    import ctypes
+    used = ctypes.c_int(-7)
+    assert hip_lib.dim_winograd_plane_gemm(None, None, None, 8, 48, 64, 16, 3, ctypes.byref(used), None) == -1
+    assert b"K % 32" in hip_lib.dim_last_error()
+    assert hip_lib.dim_winograd_plane_gemm(None, None, None, 8, 32, 96, 16, 3, ctypes.byref(used), None) == -1
+    assert hip_lib.dim_winograd_plane_gemm(None, None, None, 8, 32, 64, 16, 3, ctypes.byref(used), None) == -1
+    assert b"null pointer" in hip_lib.dim_last_error() and used.value == -7
+    assert hip_lib.dim_winograd_plane_gemm_split_weights(None, 32, 64, 16, None) == -1
     assert hip_lib.dim_winograd_workspace_floats(16, 60, 80, 256, 256, 4) == 36 * (16 * 15 * 20) * 512
     assert hip_lib.dim_winograd_workspace_floats(16, 60, 80, 256, 256, 2) == 16 * (16 * 30 * 40) * 512
     assert hip_lib.dim_winograd_workspace_floats(1, 7, 9, 32, 64, 3) == 0  # unsupported tile size
