@@ -36,13 +36,14 @@ extern "C" {
  * caller that wants both kinds of bits in one word calls dim_zoom_factor BEFORE the render, as the loop does. */
 #define DIM_STATUS_OBS_BOX_EMPTY 1 /* dim_zoom_factor: observed box empty (the reference raises) */
 #define DIM_STATUS_REN_BOX_EMPTY 2 /* dim_zoom_factor: rendered box empty */
-#define DIM_STATUS_BAD_CLASS 4     /* dim_raster_render*: class_index outside [0, n_classes): sample rendered as background; dim_pose_errors, dim_bop_errors: NaN row; dim_pose_head_fwd_cls: identity delta */
+#define DIM_STATUS_BAD_CLASS 4     /* dim_raster_render*: class_index outside [0, n_classes): sample rendered as background; dim_pose_errors, dim_bop_errors: NaN row; dim_pose_head_fwd_cls: identity delta; dim_pose_from_box: fallback row */
 #define DIM_STATUS_BAD_FACE 8      /* dim_raster_render*: a z-buffer key named a face outside the mesh (pixel left black) */
 #define DIM_STATUS_BAD_K 16        /* dim_raster_render_k: the sample's K has fx <= 0, fy <= 0 or a non-finite entry (rendered as background) */
 #define DIM_STATUS_ICP_FEW_POINTS 32 /* dim_icp_refine: an iteration found fewer than 64 inliers or a singular system (no update) */
-#define DIM_STATUS_HYP_NO_SCORE 64  /* dim_pose_score: fewer than 64 counted pixels, a constant plane or a non-finite sum (score -inf) */
+#define DIM_STATUS_HYP_NO_SCORE 64  /* dim_pose_score[_indexed]: fewer than 64 counted pixels, a constant plane or a non-finite sum (score -inf); dim_hyp_topk: a slot filled for want of candidates */
 #define DIM_STATUS_FLOW_PNP_FEW_POINTS 128 /* dim_flow_pnp: an iteration had fewer than 64 weighted points or a singular system (no update) */
 #define DIM_STATUS_LAYER_HIDDEN 256 /* dim_scene_compose: a used layer won no pixel (empty or wholly hidden); per layer, (N*S) words */
+#define DIM_STATUS_COARSE_BAD_BOX 512 /* dim_pose_from_box: a bad box, a class without points, a point behind the camera or a non-finite scale (fallback row) */
 
 const char* dim_last_error(void);
 /* library / device probe: fills name (<= n bytes), returns number of compute units or <0 */
@@ -226,6 +227,46 @@ int dim_pose_score(const float* image_observed, const float* image_rendered, con
                    const int* bbox, int B, int H, int W, int mode, float tau, void* workspace, float* score, int* status, void* stream);
 int dim_hyp_select(const float* score, int P, int N, int T, const float* poses_iter, const int* status_iter, const int* status_load,
                    const float* pose_icp, int* choice, float* poses_sel, int* status_sel, float* pose_icp_sel, void* stream);
+
+/* ---------------------------------------------------------------- coarse pose from a 2-D detection box (csrc/coarse.hip)
+ * The front stage of a pipeline that starts from a detector: M candidate rotations per pair, each with the translation at which the
+ * projected model fills the pair's box, all P*M rendered and scored against the pair's one observed frame, the k best of each pair
+ * kept.  Samples are pair-major: sample b = p * M + m.  Restated in float64 by tests/coarse_reference.py.
+ * dim_pose_from_box: pose_out (P*M,3,4) float32 = [R_m | t], rot_table (M,9) float32 device copied into the rotation entries, t fitted
+ *   in float64 (pose_out_f64 (P*M,3,4) float64: the same before the rounding of t; may be NULL).
+ *     points (Ntot,3) float64, table_off (n_classes+1) int32, class_index (P) int32: the tables of dim_pose_errors, one class per pair.
+ *     boxes (P,4) float32 device = {x0, x1, y0, y1}: continuous pixel extents with pixel centres at integers, so the inclusive int box
+ *     {min_x,max_x,min_y,max_y} is {min_x - 0.5, max_x + 0.5, min_y - 0.5, max_y + 0.5}.  K9_f64: HOST pointer, 9 doubles row-major, read
+ *     before the call returns; K_per_sample (P,9) float64 device, one camera per pair, or NULL.
+ *   With fx = K[0], fy = K[4], cx = K[2], cy = K[5], bw = x1 - x0, bh = y1 - y0, cu = (x0 + x1) / 2, cv = (y0 + y1) / 2 the fit starts
+ *   at t = ((cu - cx) z_init / fx, (cv - cy) z_init / fy, z_init) and repeats `iters` times: project every model point of the class
+ *   under [R_m | t] (the transform, then K row by row and two divisions: dim_pose_errors' order) to (u, v); umin, umax, vmin, vmax;
+ *     s = ((umax - umin) / bw + (vmax - vmin) / bh) / 2;  tz' = tz s;  tx' = tx s + (cu - (umin + umax) / 2) tz' / fx;  ty' likewise.
+ *   min / max do not depend on the order of the points: the result equals the numpy restatement bit for bit.
+ *   DIM_STATUS_COARSE_BAD_BOX is OR-ed into status[b] (P*M int32, required) and the row becomes [R_m | (0, 0, z_init)] for: a
+ *   non-finite box, x1 <= x0 or y1 <= y0; a class without points; at any iteration a point whose third projective row is not > 0, or a
+ *   non-finite s.  A class index outside [0, n_classes) gives the same row and DIM_STATUS_BAD_CLASS.  A bad row leaves every other
+ *   row as it would be without it.  One launch (one workgroup per candidate), nothing allocated, no synchronisation.
+ *   P or M outside [1, 65535], iters < 1, z_init <= 0 or non-finite, n_classes <= 0 or a NULL required pointer return DIM_ERR_ARG
+ *   before anything is enqueued.
+ * dim_pose_score_indexed: dim_pose_score with the observed planes indexed: sample b reads row obs_row[b] (B int32 device) of
+ *   image_observed / depth_observed (n_obs rows); image_rendered, depth_rendered and bbox stay per sample.  Terms, summation order,
+ *   status bit and workspace are dim_pose_score's (with obs_row[b] = b it gives the same bits).  An index outside [0, n_obs) gives
+ *   score -inf and DIM_STATUS_HYP_NO_SCORE.  dim_pose_score's argument errors, a NULL obs_row or n_obs < 1 return DIM_ERR_ARG.
+ * dim_hyp_topk: per pair the k largest finite score[p*M+m] in descending order, ties to the smaller m; a candidate with
+ *   status_in[p*M+m] & reject_mask (status_in: P*M int32 or NULL) counts as not finite.  idx_out (P,k) int32 = m, score_out (P,k),
+ *   poses_out (P*k,3,4) gathered from poses_in (P*M,3,4), status_out (P*k) int32 = the candidate's status_in bits.  With fewer than k
+ *   finite scores the remaining slots repeat slot 0 and get DIM_STATUS_HYP_NO_SCORE; with none every slot is candidate 0 with that
+ *   bit.  One workgroup per pair, no atomics: a replay is bit-identical.  One launch.
+ *   P or M outside [1, 65535], k outside [1, min(M, 64)] or a NULL required pointer return DIM_ERR_ARG before anything is enqueued. */
+int dim_pose_from_box(const double* points, const int* table_off, int n_classes, const int* class_index, const float* rot_table,
+                      const float* boxes, const double* K9_f64, const double* K_per_sample, int P, int M, int iters, double z_init,
+                      float* pose_out, double* pose_out_f64, int* status, void* stream);
+int dim_pose_score_indexed(const float* image_observed, const float* image_rendered, const float* depth_observed,
+                           const float* depth_rendered, const int* bbox, const int* obs_row, int n_obs, int B, int H, int W, int mode,
+                           float tau, void* workspace, float* score, int* status, void* stream);
+int dim_hyp_topk(const float* score, const int* status_in, int reject_mask, int P, int M, int k, const float* poses_in, int* idx_out,
+                 float* score_out, float* poses_out, int* status_out, void* stream);
 
 /* ---------------------------------------------------------------- pose errors of the evaluation (lib/utils/pose_error.py) on the device
  * For T pose sets of B pairs: errors (T,B,5) float64 = {re (degrees), te, add, adi, arp_2d} of poses_est[t][b] against pose_gt[b]

@@ -5,7 +5,9 @@
 //   hyp_expand_kernel      pose_out[p*N+h] = [R_h R_p | t_p]; h = 0 is a bit-exact copy of the pair's pose
 //   hyp_broadcast_kernel   the rows of pair p (a plane, a K, a class index) into its N sample rows, float4 where aligned
 //   pose_score_kernel      grid (kScoreBlocks, B) over the render's bbox: float64 per-lane sums of the ZNCC terms and the depth
-//                          counts, float64 across lanes and waves in a fixed order, one partial per workgroup (no atomics)
+//                          counts, float64 across lanes and waves in a fixed order, one partial per workgroup (no atomics).  The
+//                          observed planes are the sample's own row, or the row an index names (dim_pose_score_indexed: the
+//                          candidates of csrc/coarse.hip share the one observed frame of their pair)
 //   pose_score_finish      one lane per sample: the kScoreBlocks partials in order, the score in float64, the status bit
 //   hyp_select_kernel      one lane per pair: argmax of the finite scores (ties: smaller h), then the gathers
 // Nothing allocates or synchronises: every entry is graph-capturable.
@@ -88,7 +90,8 @@ __device__ __forceinline__ void score_pixel(ScoreAcc& a, float o0, float o1, flo
 template <bool VEC>
 __global__ __launch_bounds__(kScoreThreads) void pose_score_kernel(const float* __restrict__ img_o, const float* __restrict__ img_r,
                                                                    const float* __restrict__ dep_o, const float* __restrict__ dep_r,
-                                                                   const int* __restrict__ bbox, int H, int W, int mode, float tau,
+                                                                   const int* __restrict__ bbox, const int* __restrict__ obs_row,
+                                                                   int n_obs, int H, int W, int mode, float tau,
                                                                    double* __restrict__ partial) {
   const int b = blockIdx.y, tid = threadIdx.x;
   const long plane = (long)H * W;
@@ -97,11 +100,20 @@ __global__ __launch_bounds__(kScoreThreads) void pose_score_kernel(const float* 
     x0 = max(bbox[4 * b + 0], 0); x1 = min(bbox[4 * b + 1], W - 1);
     y0 = max(bbox[4 * b + 2], 0); y1 = min(bbox[4 * b + 3], H - 1);
   }
-  const bool empty = x1 < x0 || y1 < y0;
-  const float* o = img_o + (long)b * 3 * plane;
+  // the observed row of the sample: its own, or obs_row[b] of n_obs (an index outside them: nothing is read and nothing counted)
+  long ob = b;
+  bool empty = x1 < x0 || y1 < y0;
+  if (obs_row) {
+    ob = obs_row[b];
+    if (ob < 0 || ob >= n_obs) {
+      ob = 0;
+      empty = true;
+    }
+  }
+  const float* o = img_o + ob * 3 * plane;
   const float* r = img_r + (long)b * 3 * plane;
   const float* dr = dep_r + (long)b * plane;
-  const float* dob = dep_o ? dep_o + (long)b * plane : nullptr;
+  const float* dob = dep_o ? dep_o + ob * plane : nullptr;
   // a per-sample shift (the bbox's first pixel) keeps a large common offset from cancelling in the second moments
   double ref_a = 0.0, ref_r = 0.0;
   if (!empty && mode == DIM_HYP_SCORE_RGB) {
@@ -288,27 +300,44 @@ extern "C" long dim_pose_score_workspace_bytes(int B, int H, int W) {
   return (long)B * kScoreBlocks * kScoreSlot * (long)sizeof(double);
 }
 
-extern "C" int dim_pose_score(const float* image_observed, const float* image_rendered, const float* depth_observed,
-                              const float* depth_rendered, const int* bbox, int B, int H, int W, int mode, float tau, void* workspace,
-                              float* score, int* status, void* stream) {
-  DIM_REQUIRE(B > 0 && H > 0 && W > 0, "pose_score: B = %d, H = %d, W = %d", B, H, W);
-  DIM_REQUIRE(mode == DIM_HYP_SCORE_RGB || mode == DIM_HYP_SCORE_DEPTH, "pose_score: mode = %d", mode);
-  DIM_REQUIRE(image_observed && image_rendered && depth_rendered && workspace && score, "pose_score: null pointer");
-  DIM_REQUIRE(mode != DIM_HYP_SCORE_DEPTH || depth_observed, "pose_score: the depth score needs depth_observed");
-  DIM_REQUIRE(mode != DIM_HYP_SCORE_DEPTH || tau > 0.f, "pose_score: tau must be > 0");
+// dim_pose_score (obs_row NULL: sample b reads observed row b) and dim_pose_score_indexed (row obs_row[b] of n_obs)
+static int launch_pose_score(const char* who, const float* image_observed, const float* image_rendered, const float* depth_observed,
+                             const float* depth_rendered, const int* bbox, const int* obs_row, int n_obs, int B, int H, int W, int mode,
+                             float tau, void* workspace, float* score, int* status, void* stream) {
+  DIM_REQUIRE(B > 0 && H > 0 && W > 0, "%s: B = %d, H = %d, W = %d", who, B, H, W);
+  DIM_REQUIRE(mode == DIM_HYP_SCORE_RGB || mode == DIM_HYP_SCORE_DEPTH, "%s: mode = %d", who, mode);
+  DIM_REQUIRE(image_observed && image_rendered && depth_rendered && workspace && score, "%s: null pointer", who);
+  DIM_REQUIRE(mode != DIM_HYP_SCORE_DEPTH || depth_observed, "%s: the depth score needs depth_observed", who);
+  DIM_REQUIRE(mode != DIM_HYP_SCORE_DEPTH || tau > 0.f, "%s: tau must be > 0", who);
   const float* dob = mode == DIM_HYP_SCORE_DEPTH ? depth_observed : nullptr;
   auto al = [](const void* p) { return ((uintptr_t)p % 16) == 0; };
   const bool vec = W % 4 == 0 && al(image_observed) && al(image_rendered) && al(depth_rendered) && (!dob || al(dob));
   double* partial = (double*)workspace;
   if (vec)
     hipLaunchKernelGGL(pose_score_kernel<true>, dim3(kScoreBlocks, B), dim3(kScoreThreads), 0, as_stream(stream), image_observed,
-                       image_rendered, dob, depth_rendered, bbox, H, W, mode, tau, partial);
+                       image_rendered, dob, depth_rendered, bbox, obs_row, n_obs, H, W, mode, tau, partial);
   else
     hipLaunchKernelGGL(pose_score_kernel<false>, dim3(kScoreBlocks, B), dim3(kScoreThreads), 0, as_stream(stream), image_observed,
-                       image_rendered, dob, depth_rendered, bbox, H, W, mode, tau, partial);
+                       image_rendered, dob, depth_rendered, bbox, obs_row, n_obs, H, W, mode, tau, partial);
   hipLaunchKernelGGL(pose_score_finish, dim3(ceil_div(B, 64)), dim3(64), 0, as_stream(stream), (const double*)partial, B, mode, score,
                      status);
-  return check_launch("pose_score");
+  return check_launch(who);
+}
+
+extern "C" int dim_pose_score(const float* image_observed, const float* image_rendered, const float* depth_observed,
+                              const float* depth_rendered, const int* bbox, int B, int H, int W, int mode, float tau, void* workspace,
+                              float* score, int* status, void* stream) {
+  return launch_pose_score("pose_score", image_observed, image_rendered, depth_observed, depth_rendered, bbox, nullptr, 0, B, H, W, mode,
+                           tau, workspace, score, status, stream);
+}
+
+extern "C" int dim_pose_score_indexed(const float* image_observed, const float* image_rendered, const float* depth_observed,
+                                      const float* depth_rendered, const int* bbox, const int* obs_row, int n_obs, int B, int H, int W,
+                                      int mode, float tau, void* workspace, float* score, int* status, void* stream) {
+  DIM_REQUIRE(obs_row, "pose_score_indexed: null pointer (obs_row)");
+  DIM_REQUIRE(n_obs > 0, "pose_score_indexed: n_obs = %d", n_obs);
+  return launch_pose_score("pose_score_indexed", image_observed, image_rendered, depth_observed, depth_rendered, bbox, obs_row, n_obs, B, H,
+                           W, mode, tau, workspace, score, status, stream);
 }
 
 extern "C" int dim_hyp_select(const float* score, int P, int N, int T, const float* poses_iter, const int* status_iter, const int* status_load,

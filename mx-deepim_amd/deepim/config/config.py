@@ -78,6 +78,12 @@ def _defaults():
                    # several starting poses per pair, scored after the loop (1 = off): rotation of the generated ones (degrees), the
                    # score ("rgb" ZNCC or "depth" inlier fraction) and the depth score's inlier gate (metres)
                    HYP_NUM=1, HYP_ROT_DEG=30.0, HYP_SCORE="rgb", HYP_DEPTH_TAU=0.02,
+                   # starting poses from a detection box per pair (Refiner.load(..., det_boxes=); 0 views = off): a grid of COARSE_VIEWS
+                   # viewpoints x COARSE_INPLANE in-plane turns, the iterations and the starting distance (metres) of the box fit, the
+                   # score of the candidates ("rgb" / "depth" and its gate, as HYP_SCORE) and how many are rendered at a time; the
+                   # HYP_NUM best of every pair start the loop
+                   COARSE_VIEWS=0, COARSE_INPLANE=1, COARSE_BOX_ITER=8, COARSE_Z_INIT=1.0, COARSE_SCORE="rgb", COARSE_DEPTH_TAU=0.02,
+                   COARSE_CHUNK=256,
                    # pred_eval: the pose errors (re, te, ADD, ADD-S, arp_2d) from dim_pose_errors on the device instead of
                    # lib/utils/pose_error.py on the host, one pose at a time
                    DEVICE_EVAL=False,

@@ -17,6 +17,7 @@ import numpy as np
 import torch
 
 from lib.hip import ops
+from deepim.core.coarse import CoarseInit, boxes_from_int, coarse_settings
 from deepim.symbols.deepIM_flownet import FlowNetHip
 
 HYP_SCORES = ("rgb", "depth")
@@ -119,9 +120,12 @@ class Predictor(object):
 class Refiner(object):
     """batch_size = P pairs per loaded batch.  With TEST.HYP_NUM = N > 1 every pair is refined from N starting poses, as the samples
     b = p * N + h of one batch (the Predictor is built for P * N samples); after the loop each sample's last pose is rendered and
-    scored against the observed image (TEST.HYP_SCORE) and the best hypothesis of each pair is selected, all inside the same graph."""
+    scored against the observed image (TEST.HYP_SCORE) and the best hypothesis of each pair is selected, all inside the same graph.
+    With TEST.COARSE_VIEWS > 0 the starting poses come from a detection box per pair: load(..., det_boxes=) runs the coarse stage
+    (deepim.core.coarse.CoarseInit, eagerly, outside the graph) and starts the loop from its HYP_NUM best candidates.  evaluator: the
+    PoseEvaluator whose model points the box fit projects (None: the vertices of the render machine's meshes)."""
 
-    def __init__(self, config, predictor, render_machine, batch_size, capture_graph=False):
+    def __init__(self, config, predictor, render_machine, batch_size, capture_graph=False, evaluator=None):
         cfg = config
         if cfg.network.INPUT_MASK and cfg.network.PRED_MASK and cfg.TEST.UPDATE_MASK not in ("box_rendered", "init"):
             # same restriction as the released loop (tester.py:579-587)
@@ -235,6 +239,14 @@ class Refiner(object):
             if self.icp_iter > 0:
                 self.pose_icp_sel = torch.zeros((P, 3, 4), dtype=torch.float32, device=d)
         render_machine.reserve(B)
+        # starting poses from detection boxes (TEST.COARSE_VIEWS > 0): the coarse stage, its outputs of the latest load, and for one
+        # hypothesis per pair the box and the status of the initial render (several: _expand's bbox_hyp / status_hyp)
+        self.coarse = self.coarse_out = None
+        if coarse_settings(cfg)[0] > 0:
+            self.coarse = CoarseInit(cfg, render_machine, evaluator, batch_size, N)   # (refuses the lit renderer)
+            if N == 1:
+                self.bbox_hyp = torch.zeros((B, 4), dtype=torch.int32, device=d)
+                self.status_hyp = torch.zeros((B,), dtype=torch.int32, device=d)
         # ModelNet: the lit renderer takes a per-render light intensity drawn on the host (tester.py:227-230)
         self.lit = hasattr(render_machine, "normals")
         self.light_int = torch.ones((max(self.test_iter - 1, 1), B, 3), dtype=torch.float32, device=d) if self.lit else None
@@ -244,13 +256,20 @@ class Refiner(object):
 
     # ------------------------------------------------------------------------------------------
     def load(self, image_observed, image_rendered, mask_observed, mask_rendered, src_pose, class_index, depth_observed=None,
-             depth_rendered=None, K=None, hyp_poses=None):
+             depth_rendered=None, K=None, hyp_poses=None, det_boxes=None):
         """copy one batch of blobs (any device) into the resident buffers (the depth planes: INPUT_DEPTH graphs only; depth_observed
         also when TEST.ICP_ITER > 0 or the depth hypothesis score is on).
         K: None (every re-render uses the config K) or the camera of each pair, (B,3,3) or (B,9), any device: the unlit re-renders of
         this batch use it (the lit ModelNet render ignores K, as the reference's render() closure does)
         hyp_poses: TEST.HYP_NUM > 1 only: None (hypothesis 0 = the loaded pair, the others generated from it) or (P,N,3,4) starting
-        poses given by the caller, all of them rendered"""
+        poses given by the caller, all of them rendered
+        det_boxes: TEST.COARSE_VIEWS > 0 only, and required then: (P,4) detection boxes {x0,x1,y0,y1}, continuous pixel extents (the
+        inclusive int box {min_x,max_x,min_y,max_y} is {min_x-0.5, max_x+0.5, min_y-0.5, max_y+0.5}).  The coarse stage finds the
+        starting poses; src_pose, image_rendered and mask_rendered (and depth_rendered) are ignored and may be None"""
+        if self.coarse is not None:
+            return self._load_coarse(image_observed, mask_observed, class_index, depth_observed, K, hyp_poses, det_boxes)
+        if det_boxes is not None:
+            raise ValueError("det_boxes needs TEST.COARSE_VIEWS > 0")
         self._check_hyp_poses(hyp_poses)
         self._load_K(K)
         b = self.batch
@@ -276,6 +295,54 @@ class Refiner(object):
             # same draws, same order as the reference: sample by sample, one np.random.uniform(0.9,1.1,3) per re-render
             li = np.stack([[np.random.uniform(0.9, 1.1, size=(3,)) for _ in range(self.test_iter - 1)] for _ in range(self.B)])
             self.light_int.copy_(torch.from_numpy(li.transpose(1, 0, 2).astype(np.float32)))
+
+    def _load_coarse(self, image_observed, mask_observed, class_index, depth_observed, K, hyp_poses, det_boxes):
+        """load() with TEST.COARSE_VIEWS > 0: the observed blobs, then the coarse stage on them (eagerly, as _expand runs), whose
+        HYP_NUM best candidates per pair become the starting poses, rendered by the render call of _expand.  One hypothesis per
+        pair: the best candidate is pose_init, and mask_observed the box of its render under INIT_MASK 'box_rendered'."""
+        if det_boxes is None:
+            raise ValueError("TEST.COARSE_VIEWS > 0: load() needs det_boxes (P,4), the detection box of every pair")
+        if hyp_poses is not None:
+            raise ValueError("TEST.COARSE_VIEWS > 0: the starting poses come from det_boxes, hyp_poses must be None")
+        self._load_K(K)
+        dst = self._load_targets()
+        if "depth_observed" in dst:
+            if depth_observed is None:
+                raise ValueError("the loop's configuration (INPUT_DEPTH, TEST.ICP_ITER > 0 or TEST.HYP_SCORE 'depth') needs depth_observed")
+            dst["depth_observed"].copy_(torch.as_tensor(depth_observed))
+        dst["image_observed"].copy_(torch.as_tensor(image_observed))
+        dst["class_index"].copy_(torch.as_tensor(class_index).to(torch.int32))
+        box_init = self.cfg.TEST.INIT_MASK == "box_rendered"
+        mask_dst = dst["mask_observed"]
+        if not box_init:
+            if mask_observed is None:
+                raise ValueError("TEST.INIT_MASK {!r}: load() needs mask_observed".format(self.cfg.TEST.INIT_MASK))
+            mask_dst.copy_(torch.as_tensor(mask_observed))
+        K_pair = (self.K_pair if self.N == 1 else self.pair["K"]) if self.per_pair_K else None
+        poses, idx, score, status = self.coarse.run(dst["image_observed"], det_boxes, dst["class_index"],
+                                                    depth_observed=dst.get("depth_observed", depth_observed), K=K_pair)
+        self.coarse_out = {"pose": poses, "idx": idx, "score": score, "status": status}
+        if self.N > 1:
+            ops.copy(self.pair["src_pose"], poses[:, 0].contiguous())
+            self._expand(poses)
+            return
+        ops.copy(self.pose_init, poses.reshape(self.B, 3, 4))
+        self._render_start()
+        if box_init:
+            ops.box_mask(self.bbox_hyp, mask_dst)
+
+    def _render_start(self):
+        """the starting poses (pose_init) rendered as the loop re-renders: init image_rendered / mask_rendered [/ depth_rendered],
+        their boxes in bbox_hyp and the render's status bits in status_hyp"""
+        b, init = self.batch, self.init
+        extra = {}
+        if self.per_pair_K:
+            extra["K"] = self.K_pair
+        if self.input_depth:
+            extra["depth"] = init["depth_rendered"]
+        ops.fill(self.status_hyp, 0)
+        self.render_machine.render_batch(b["class_index"], self.pose_init, image=init["image_rendered"], mask=init["mask_rendered"],
+                                         bbox=self.bbox_hyp, plane_means=self.net.plane_means, mask_thr=0.2, status=self.status_hyp, **extra)
 
     def _load_K(self, K):
         if K is None:
@@ -323,15 +390,9 @@ class Refiner(object):
         ops.hyp_broadcast(b["class_index"], pr["class_index"], N)
         if "depth_observed" in pr:
             ops.hyp_broadcast(b["depth_observed"] if self.input_depth else self.depth_observed, pr["depth_observed"], N)
-        extra = {}
         if self.per_pair_K:
             ops.hyp_broadcast(self.K_pair, pr["K"], N)
-            extra["K"] = self.K_pair
-        if self.input_depth:
-            extra["depth"] = init["depth_rendered"]
-        ops.fill(self.status_hyp, 0)
-        self.render_machine.render_batch(b["class_index"], self.pose_init, image=init["image_rendered"], mask=init["mask_rendered"],
-                                         bbox=self.bbox_hyp, plane_means=self.net.plane_means, mask_thr=0.2, status=self.status_hyp, **extra)
+        self._render_start()
         if self.cfg.TEST.INIT_MASK == "box_rendered":
             ops.box_mask(self.bbox_hyp, init["mask_observed"])
         else:
@@ -344,6 +405,8 @@ class Refiner(object):
     def load_staged(self, loader, staged):
         """take the next batch straight from a deepim.core.loader.TestDataLoader staging set: the raw pixels it uploaded are turned
         into the resident blobs by dim_test_blobs_from_raw / dim_box_mask on the current stream -- no host blobs, no extra copies"""
+        if self.coarse is not None:
+            raise ValueError("TEST.COARSE_VIEWS > 0: the staged batches carry no detection boxes, use load(..., det_boxes=)")
         dst = self._load_targets()
         out = {k: dst[k] for k in ("image_observed", "image_rendered", "mask_rendered", "mask_observed")}
         if self.depth_observed is not None:
@@ -728,7 +791,11 @@ def pred_eval(config, refiner, batches, evaluator, result_file=None, logger=None
     by the same error code (the host functions, or dim_pose_errors under TEST.DEVICE_EVAL): out["flow_pnp"] = {pose, add: the tables
     of evaluate_pose / evaluate_pose_add; all_rot_err, all_trans_err; inliers, rms: per loop iteration the mean over the refined pairs
     of the stage's last weighted point count and pixel rms; flagged: per loop iteration the number of pairs with
-    DIM_STATUS_FLOW_PNP_FEW_POINTS}.  Every other output and the result cache are those of the stage off."""
+    DIM_STATUS_FLOW_PNP_FEW_POINTS}.  Every other output and the result cache are those of the stage off.
+    With TEST.COARSE_VIEWS > 0 (a Refiner with a coarse stage) every pair starts from its detection box: the batch's "det_bbox" (P,4)
+    {x0,x1,y0,y1} continuous pixel extents when it carries one, otherwise the box of its "mask_observed" (dim_mask_bbox, widened by
+    half a pixel to each side).  "src_pose", "image_rendered" and "mask_rendered" are not read (the pair's best coarse pose stands for
+    src_pose).  out["coarse"] = {idx, score, status, pose}: per pair the HYP_NUM kept candidates of the coarse stage, best first."""
     import copy
     import pickle
 
@@ -786,14 +853,32 @@ def pred_eval(config, refiner, batches, evaluator, result_file=None, logger=None
     flow_rows = [] if with_flow else None
     # flow error of the first forward (:500-512): only the full test graph emits the flow head's output
     epe = FlowEPE(config, getattr(refiner, "P", refiner.B), refiner.net.device) if (config.network.PRED_FLOW and not config.TEST.FAST_TEST) else None
+    # starting poses from detection boxes: [idx, score, status, pose] per pair
+    with_coarse = getattr(refiner, "coarse", None) is not None
+    coarse_lists = tuple([] for _ in range(4)) if with_coarse else None
     for batch in batches:
         extra = {"hyp_poses": batch["hyp_poses"]} if batch.get("hyp_poses") is not None else {}
+        if with_coarse:
+            det = batch.get("det_bbox")
+            if det is None:
+                mask = torch.as_tensor(batch["mask_observed"]).to(refiner.net.device, torch.float32).contiguous()
+                det = boxes_from_int(ops.mask_bbox(mask, 0.5))
+            extra["det_boxes"] = det
         if vsd is not None:
             vsd.check(batch, vsd_who)
         if with_flow and "pose_observed" not in batch:
             raise KeyError("pose from flow (TEST.FLOW_PNP_ITER > 0) needs the blob 'pose_observed' to be scored")
-        refiner.load(batch["image_observed"], batch["image_rendered"], batch["mask_observed"], batch["mask_rendered"], batch["src_pose"],
-                     batch["class_index"], depth_observed=batch.get("depth_observed"), K=batch.get("K"), **extra)
+        if with_coarse:
+            refiner.load(batch["image_observed"], None, batch.get("mask_observed"), None, None, batch["class_index"],
+                         depth_observed=batch.get("depth_observed"), K=batch.get("K"), **extra)
+            # one more copy per batch; the best candidate stands for the batch's src_pose
+            co = {k: v.cpu().numpy() for k, v in refiner.coarse_out.items()}
+            for k, key in enumerate(("idx", "score", "status", "pose")):
+                coarse_lists[k].extend(co[key].tolist() if key != "pose" else list(co[key].astype(np.float64)))
+            batch = dict(batch, src_pose=co["pose"][:, 0].copy())
+        else:
+            refiner.load(batch["image_observed"], batch["image_rendered"], batch["mask_observed"], batch["mask_rendered"], batch["src_pose"],
+                         batch["class_index"], depth_observed=batch.get("depth_observed"), K=batch.get("K"), **extra)
         if device_eval:
             # the errors of every pose on the device, packed behind the poses (float32 -> float64 is exact): rows (iter [+ 1 for ICP],
             # B, 12 + 5), ONE device->host copy per batch
@@ -924,7 +1009,7 @@ def pred_eval(config, refiner, batches, evaluator, result_file=None, logger=None
         parts = [None] * dist.get_world_size()
         dist.all_gather_object(parts, (all_rot_err, all_trans_err, all_poses_est, all_poses_gt, icp_lists, hyp_lists, err_lists, icp_err_lists,
                                        vsd_lists, icp_vsd_lists, bop_lists, icp_bop_lists, flow_lists, flow_err_lists, flow_rows,
-                                       grid_lists, icp_grid_lists))
+                                       grid_lists, icp_grid_lists, coarse_lists))
         for k, mine in enumerate((all_rot_err, all_trans_err, all_poses_est, all_poses_gt)):
             for c in range(n_cls):
                 for it in range(n_it):
@@ -936,6 +1021,9 @@ def pred_eval(config, refiner, batches, evaluator, result_file=None, logger=None
         if hyp_lists is not None:
             for k, mine in enumerate(hyp_lists):
                 mine[:] = [x for part in parts for x in part[5][k]]
+        if coarse_lists is not None:
+            for k, mine in enumerate(coarse_lists):
+                mine[:] = [x for part in parts for x in part[17][k]]
         for slot, lists, iters in ((6, err_lists, n_it), (7, icp_err_lists, 1), (8, vsd_lists, n_it), (9, icp_vsd_lists, 1),
                                    (10, bop_lists, n_it), (11, icp_bop_lists, 1), (15, grid_lists, n_it), (16, icp_grid_lists, 1)):
             for k in (lists or {}):
@@ -1034,4 +1122,6 @@ def pred_eval(config, refiner, batches, evaluator, result_file=None, logger=None
         print(line)
         if logger:
             logger.info(line)
+    if coarse_lists is not None:
+        out["coarse"] = dict(zip(("idx", "score", "status", "pose"), coarse_lists))
     return out

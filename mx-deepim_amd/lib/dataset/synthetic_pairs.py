@@ -59,6 +59,7 @@ class SyntheticPairs(object):
         T = self.config.TEST
         icp = int(T.get("ICP_ITER", 0) or 0) > 0 or (int(T.get("HYP_NUM", 1) or 1) > 1 and T.get("HYP_SCORE", "rgb") == "depth")
         icp = icp or bool(T.get("VSD", False)) or bool(T.get("BOP_VSD", False))
+        icp = icp or (int(T.get("COARSE_VIEWS", 0) or 0) > 0 and T.get("COARSE_SCORE", "rgb") == "depth")   # the coarse stage's depth score
         for i in self.batch_ids:
             b = syn.build_device_batch(self.render_machine, self.batch_pairs, seed=self.seed + 1000 * (i + 1), n_classes=len(self.classes),
                                        pixel_means=self.config.network.PIXEL_MEANS, device=self.device, with_depth=with_depth or icp)

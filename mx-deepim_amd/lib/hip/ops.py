@@ -318,21 +318,33 @@ def pose_score_workspace(B, H, W, device):
 
 
 def pose_score(image_observed, image_rendered, depth_rendered, mode="rgb", tau=0.02, depth_observed=None, bbox=None, score=None,
-               status=None, workspace=None):
+               status=None, workspace=None, obs_row=None):
     """dim_pose_score (restated by tests/hyp_reference.py): one score per sample over the drawn pixels of the render inside bbox (B,4)
     int32 (None = whole frame).  mode "rgb": ZNCC of the channel sums of image_observed and image_rendered (B,3,H,W); "depth": the
     fraction of pixels with depth_observed > 0 where |depth_rendered - depth_observed| < tau.  -> score (B,) f32, -inf when it is
-    undefined (and DIM_STATUS_HYP_NO_SCORE is OR-ed into status (B,) int32 when given)"""
+    undefined (and DIM_STATUS_HYP_NO_SCORE is OR-ed into status (B,) int32 when given).
+    obs_row (B,) int32: dim_pose_score_indexed -- image_observed (n_obs,3,H,W) / depth_observed (n_obs,1,H,W) hold n_obs frames and
+    sample b reads frame obs_row[b] (an index outside them: -inf and the status bit)"""
     B, _, H, W = depth_rendered.shape
     if mode not in HYP_SCORE_ID:
         raise ValueError("pose score mode must be 'rgb' or 'depth', got {!r}".format(mode))
     if mode == "depth" and depth_observed is None:
         raise ValueError("the depth pose score needs depth_observed")
-    assert tuple(image_observed.shape) == (B, 3, H, W) and tuple(image_rendered.shape) == (B, 3, H, W)
-    assert depth_observed is None or depth_observed.shape == depth_rendered.shape
+    n_obs = image_observed.shape[0] if obs_row is not None else B
+    assert tuple(image_observed.shape) == (n_obs, 3, H, W) and tuple(image_rendered.shape) == (B, 3, H, W)
+    assert depth_observed is None or tuple(depth_observed.shape) == (n_obs, 1, H, W)
+    assert obs_row is None or obs_row.numel() == B
     score = score if score is not None else _new((B,), depth_rendered)
+    assert score.numel() == B and (status is None or status.numel() == B) and (bbox is None or bbox.numel() == 4 * B)
     if workspace is None:
         workspace = pose_score_workspace(B, H, W, depth_rendered.device)
+    assert workspace.numel() * workspace.element_size() >= lib().dim_pose_score_workspace_bytes(B, H, W)
+    if obs_row is not None:
+        check(lib().dim_pose_score_indexed(dptr(image_observed, f32), dptr(image_rendered, f32), _opt(depth_observed),
+                                           dptr(depth_rendered, f32), _opt(bbox, i32), dptr(obs_row, i32), n_obs, B, H, W,
+                                           HYP_SCORE_ID[mode], float(tau), dptr(workspace, torch.float64), dptr(score, f32),
+                                           _opt(status, i32), current_stream()))
+        return score
     check(lib().dim_pose_score(dptr(image_observed, f32), dptr(image_rendered, f32), _opt(depth_observed), dptr(depth_rendered, f32),
                                _opt(bbox, i32), B, H, W, HYP_SCORE_ID[mode], float(tau), dptr(workspace, torch.float64), dptr(score, f32),
                                _opt(status, i32), current_stream()))
@@ -357,6 +369,50 @@ def hyp_select(score, N, poses_iter, status_iter=None, pose_icp=None, choice=Non
                                dptr(choice, i32),
                                dptr(poses_sel, f32), _opt(status_sel, i32), _opt(pose_icp_sel), current_stream()))
     return choice, poses_sel, status_sel, pose_icp_sel
+
+
+STATUS_COARSE_BAD_BOX = 512   # DIM_STATUS_COARSE_BAD_BOX: dim_pose_from_box gave the candidate its fallback row
+HYP_TOPK_MAX = 64             # dim_hyp_topk: the largest k
+
+
+def pose_from_box(points, table_off, class_index, rot_table, boxes, K, iters=8, z_init=1.0, K_per_sample=None, pose_out=None,
+                  pose_out_f64=None, status=None):
+    """dim_pose_from_box (restated by tests/coarse_reference.py): M candidate poses per pair, sample p*M+m = [R_m | t] with t fitted so
+    that the projected model points of the pair's class fill its box.  points (Ntot,3) f64 and table_off (n_classes+1,) int32 as
+    PoseEvaluator.device_tables returns them, class_index (P,) int32, rot_table (M,3,3) or (M,9) f32, boxes (P,4) f32 {x0,x1,y0,y1}
+    continuous pixel extents, K the host 3x3 unless K_per_sample ((P,3,3) / (P,9)) is given.  -> (pose_out (P*M,3,4) f32, status
+    (P*M,) int32: DIM_STATUS_COARSE_BAD_BOX / DIM_STATUS_BAD_CLASS are OR-ed in, zeroed when allocated here); pose_out_f64 (P*M,3,4)
+    f64 is filled when given"""
+    f64 = torch.float64
+    P, M = class_index.numel(), rot_table.numel() // 9
+    assert rot_table.numel() == 9 * M and tuple(boxes.shape) == (P, 4) and points.dim() == 2 and points.shape[1] == 3
+    dev = boxes.device
+    pose_out = pose_out if pose_out is not None else torch.empty((P * M, 3, 4), dtype=f32, device=dev)
+    status = status if status is not None else torch.zeros((P * M,), dtype=i32, device=dev)
+    assert pose_out.numel() == P * M * 12 and status.numel() == P * M and (pose_out_f64 is None or pose_out_f64.numel() == P * M * 12)
+    kps = _kps_f64(K_per_sample, P, dev, "pose_from_box:")
+    keep = _host_k9_f64(K)
+    check(lib().dim_pose_from_box(dptr(points, f64), dptr(table_off, i32), table_off.numel() - 1, dptr(class_index, i32), dptr(rot_table, f32),
+                                  dptr(boxes, f32), keep.ctypes.data, _opt(kps, f64), P, M, int(iters), float(z_init), dptr(pose_out, f32),
+                                  _opt(pose_out_f64, f64), dptr(status, i32), current_stream()))
+    return pose_out, status
+
+
+def hyp_topk(score, M, k, poses_in, status_in=None, reject_mask=0, idx_out=None, score_out=None, poses_out=None, status_out=None):
+    """dim_hyp_topk: score (P*M,), poses_in (P*M,3,4) -> per pair the k largest finite scores in descending order (ties: the smaller
+    m; a candidate with status_in & reject_mask is skipped): idx_out (P,k) int32, score_out (P,k), poses_out (P,k,3,4), status_out
+    (P,k) int32 = the candidate's status_in bits, DIM_STATUS_HYP_NO_SCORE on the slots that repeat slot 0 for want of candidates"""
+    B = score.numel()
+    assert B % M == 0 and poses_in.numel() == 12 * B and (status_in is None or status_in.numel() == B)
+    P = B // M
+    idx_out = idx_out if idx_out is not None else _new((P, k), score, i32)
+    score_out = score_out if score_out is not None else _new((P, k), score)
+    poses_out = poses_out if poses_out is not None else _new((P, k, 3, 4), score)
+    status_out = status_out if status_out is not None else _new((P, k), score, i32)
+    assert idx_out.numel() == P * k and score_out.numel() == P * k and poses_out.numel() == P * k * 12 and status_out.numel() == P * k
+    check(lib().dim_hyp_topk(dptr(score, f32), _opt(status_in, i32), int(reject_mask), P, int(M), int(k), dptr(poses_in, f32),
+                             dptr(idx_out, i32), dptr(score_out, f32), dptr(poses_out, f32), dptr(status_out, i32), current_stream()))
+    return idx_out, score_out, poses_out, status_out
 
 
 STATUS_BAD_CLASS = 4     # DIM_STATUS_BAD_CLASS: dim_pose_errors gave the pair a NaN row (class index outside the table)
@@ -560,6 +616,7 @@ def bop_errors(points, table_off, sym, sym_off, class_index, poses_est, pose_gt,
     return errors, best_sym
 
 
+STATUS_BAD_FACE = 8   # DIM_STATUS_BAD_FACE: a z-buffer key of dim_raster_render* named a face outside the mesh (pixel left black)
 STATUS_BAD_K = 16   # DIM_STATUS_BAD_K: dim_raster_render_k drew the sample as background (fx <= 0, fy <= 0 or a non-finite entry)
 
 
