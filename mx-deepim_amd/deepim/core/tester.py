@@ -18,6 +18,7 @@ import torch
 
 from lib.hip import ops
 from deepim.core.coarse import CoarseInit, boxes_from_int, coarse_settings
+from deepim.core.score_lists import PairLists, ScoreLists
 from deepim.symbols.deepIM_flownet import FlowNetHip
 
 HYP_SCORES = ("rgb", "depth")
@@ -25,6 +26,11 @@ ERR_KEYS = ("re", "te", "add", "arp_2d")   # the per-pose error lists lib.datase
 VSD_KEYS = ("vsd", "visib_gt", "union", "inter", "drawn_gt")   # per pose: the errors (one per tau) and dim_vsd_errors' four counts
 BOP_KEYS = ("mssd", "mspd", "sym_mssd", "sym_mspd")             # per pose: dim_bop_errors' two errors and the symmetries that attain them
 GRID_KEYS = ("vsd_grid",) + VSD_KEYS[1:]                       # per pose: dim_vsd_grid_errors' errors (one per tau of the class) and counts
+RT_KEYS = ("rot_err", "trans_err", "poses_est", "poses_gt")    # per pose: the four lists of the reference's pred_eval (and of its result cache)
+# the families of per-pose lists pred_eval keeps for a pose set, in the order their columns are packed for the host
+FAMILY_KEYS = {"rt": RT_KEYS, "err": ERR_KEYS, "vsd": VSD_KEYS, "grid": GRID_KEYS, "bop": BOP_KEYS}
+HYP_KEYS = ("score", "choice", "rot_err", "trans_err", "undetected")   # per pair with several hypotheses
+COARSE_KEYS = ("idx", "score", "status", "pose")                       # per pair: the kept candidates of the coarse stage, best first
 
 
 def hyp_settings(cfg):
@@ -564,6 +570,16 @@ class Refiner(object):
         return self.poses_iter if self.N == 1 else self.poses_sel
 
 
+def _pair_view(refiner, cls=True, K=True, icp=False):
+    """-> (class_index, K_pair, pose_icp) of the loaded batch, one row per pair: where a Refiner keeps them depends on its hypotheses
+    (one per pair: the loop's own buffers; several: the pair rows, and the ICP pose of the selected hypothesis).  K_pair is None
+    when no per-pair camera was loaded (the config K holds).  An entry that is not asked for is None and nothing is read for it."""
+    one = int(getattr(refiner, "N", 1)) == 1
+    return ((refiner.batch if one else refiner.pair)["class_index"] if cls else None,
+            (refiner.K_pair if one else refiner.pair["K"]) if K and refiner.per_pair_K else None,
+            (refiner.pose_icp if one else refiner.pose_icp_sel) if icp else None)
+
+
 class VsdScorer(object):
     """TEST.VSD and TEST.BOP_VSD: the visible surface discrepancy of every pose pred_eval scores, against the batch's observed depth.
     Per batch the ground truth is rendered once (depth and box only, float32 pose, the pair's K when one was loaded) with the refiner's
@@ -627,9 +643,7 @@ class VsdScorer(object):
 
     def score(self, batch, pose_sets):
         """pose_sets: list of (P,3,4) float32 device poses, one per row of errors / counts (and of grid_errors / grid_counts)"""
-        r = self.refiner
-        cls = r.batch["class_index"] if r.N == 1 else r.pair["class_index"]
-        K_pair = (r.K_pair if r.N == 1 else r.pair["K"]) if r.per_pair_K else None
+        cls, K_pair, _ = _pair_view(self.refiner)
         extra = {"K": K_pair} if K_pair is not None else {}
         K64 = K_pair.to(torch.float64) if K_pair is not None else None
         obs = self._observed(batch)
@@ -679,14 +693,12 @@ class BopScorer(object):
 
     def score(self, batch, poses, pose_icp=None):
         """poses (rows [- 1], P, 3, 4) float32 on the device, pose_icp (P,3,4) the last row when given"""
-        r = self.refiner
         if pose_icp is not None:   # one call needs the rows in one array
             self.poses[:-1].copy_(poses)
             self.poses[-1].copy_(pose_icp)
             poses = self.poses
         assert poses.shape[0] == self.rows
-        cls = r.batch["class_index"] if r.N == 1 else r.pair["class_index"]
-        K_pair = (r.K_pair if r.N == 1 else r.pair["K"]) if r.per_pair_K else None
+        cls, K_pair, _ = _pair_view(self.refiner)
         gt = torch.as_tensor(batch["pose_observed"]).to(self.errors.device, torch.float64).contiguous()
         ops.bop_errors(self.points, self.table_off, self.sym, self.sym_off, cls, poses.contiguous(), gt, self.K, self.max_sym,
                        K_per_sample=K_pair, errors=self.errors, best_sym=self.best_sym, workspace=self.work)
@@ -796,332 +808,302 @@ def pred_eval(config, refiner, batches, evaluator, result_file=None, logger=None
     {x0,x1,y0,y1} continuous pixel extents when it carries one, otherwise the box of its "mask_observed" (dim_mask_bbox, widened by
     half a pixel to each side).  "src_pose", "image_rendered" and "mask_rendered" are not read (the pair's best coarse pose stands for
     src_pose).  out["coarse"] = {idx, score, status, pose}: per pair the HYP_NUM kept candidates of the coarse stage, best first."""
+    st = _eval_setup(config, refiner, evaluator, logger)
+    for batch in batches:
+        _collect_batch(st, refiner, batch)
+    # several ranks refine disjoint shards (one process per GPU): the metrics are over ALL pairs, so the lists are merged in rank
+    # order on every rank before scoring (the reference scores one list in one process)
+    import torch.distributed as dist
+
+    merged = bool(merge_ranks) and dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
+    if merged:
+        st.store = _merge_over_ranks(st.store)
+        if dist.get_rank() != 0:
+            result_file = None   # one result cache, written by rank 0
+    return _tables(st, result_file, merge_ranks, merged)
+
+
+def _eval_setup(config, refiner, evaluator, logger):
+    """what one pred_eval call holds: the switches, the device scorers and `store`, every list it collects under its name --
+    (pose set, family) -> ScoreLists for the sets "loop", "icp" and "flow_pnp" and the families of FAMILY_KEYS, and the per-pair
+    "hyp", "flow_rows" and "coarse" -> PairLists.  A name is there only when its feature is on."""
+    from types import SimpleNamespace
+
+    bop_vsd = bop_vsd_settings(config)[0]   # before anything is allocated: BOP_VSD without BOP raises here
+    T = config.TEST
+    st = SimpleNamespace(config=config, evaluator=evaluator, logger=logger, n_cls=len(evaluator.classes), n_it=int(T.test_iter),
+                         with_icp=int(T.get("ICP_ITER", 0) or 0) > 0, n_hyp=int(getattr(refiner, "N", 1)),
+                         device_eval=bool(T.get("DEVICE_EVAL", False)), with_flow=int(T.get("FLOW_PNP_ITER", 0) or 0) > 0,
+                         with_coarse=getattr(refiner, "coarse", None) is not None, vsd=None, bop=None,
+                         vsd_who="TEST.VSD" if bool(T.get("VSD", False)) else "TEST.BOP_VSD")
+    if st.device_eval:
+        from lib.dataset.evaluation import SYM_CLASSES
+
+        st.dev = refiner.net.device
+        st.tables = evaluator.device_tables(st.dev)
+        st.K_eval = np.asarray(config.dataset.INTRINSIC_MATRIX, dtype=np.float64)
+        st.uses_adi = [c in SYM_CLASSES for c in evaluator.classes]
+    rows = st.n_it + (1 if st.with_icp else 0)   # the device scorers take the ICP pose as one more row
+    if bool(T.get("VSD", False)) or bop_vsd:     # one scorer renders for TEST.VSD and the grid of TEST.BOP_VSD
+        st.vsd = VsdScorer(config, refiner, rows, evaluator)
+    if bool(T.get("BOP", False)):
+        st.bop = BopScorer(config, refiner, evaluator, rows)
+    on = {"rt": True, "err": st.device_eval, "vsd": st.vsd is not None and st.vsd.absolute, "grid": bop_vsd, "bop": st.bop is not None}
+    families = [f for f in FAMILY_KEYS if on[f]]
+    sets = [("loop", st.n_it, families)]
+    if st.with_icp:    # its own one-row lists, as the reference's PRECOMPUTED_ICP branch scores them
+        sets.append(("icp", 1, families))
+    if st.with_flow:   # pose from flow at every iteration: scored by the error code alone
+        sets.append(("flow_pnp", st.n_it, [f for f in families if f in ("rt", "err")]))
+    st.store = {(name, f): ScoreLists(FAMILY_KEYS[f], st.n_cls, iters) for name, iters, fams in sets for f in fams}
+    st.scored = list(st.store)
+    if st.n_hyp > 1:
+        st.store["hyp"] = PairLists(HYP_KEYS)
+    if st.with_flow:   # per refined pair (iter, 3) = (weighted points, rms, flagged) of the stage's last Gauss-Newton iteration
+        st.store["flow_rows"] = PairLists(("stats",))
+    if st.with_coarse:
+        st.store["coarse"] = PairLists(COARSE_KEYS)
+    # flow error of the first forward (:500-512): only the full test graph emits the flow head's output
+    st.epe = FlowEPE(config, getattr(refiner, "P", refiner.B), refiner.net.device) if (config.network.PRED_FLOW and not T.FAST_TEST) else None
+    return st
+
+
+def _cat(tensors, dim):
+    return tensors[0] if len(tensors) == 1 else torch.cat(tensors, dim=dim)
+
+
+def _to_host(columns):
+    """columns: [(name, width, (rows, P, ...) device tensor)] -> {name: its (rows, P, width) float64 of the ONE device->host copy
+    of the columns side by side, in the order given}"""
+    host = _cat([t.reshape(t.shape[0], -1, w) for _, w, t in columns], 2).cpu().numpy().astype(np.float64, copy=False)
+    out, at = {}, 0
+    for name, w, _ in columns:
+        out[name], at = host[:, :, at:at + w], at + w
+    assert at == host.shape[2]
+    return out
+
+
+def _read_out(st, batch, poses_dev, p_icp, cls_dev, gt_dev):
+    """score the refined batch on the device and bring it to the host -> {column: (rows, P, width) float64}, rows = the loop's
+    iterations and behind them the ICP pose when there is one; "pose" is (rows, P, 3, 4).  TEST.DEVICE_EVAL: the errors of every
+    pose from dim_pose_errors, packed behind the poses (float32 -> float64 is exact) with the scorers' columns: ONE copy per batch.
+    Otherwise one copy per column: the poses, the scorers' in the same order, then the ICP pose."""
+    f64 = torch.float64
+    columns = []
+    if st.vsd is not None:
+        st.vsd.score(batch, list(poses_dev) + ([p_icp] if p_icp is not None else []))
+        if st.vsd.absolute:
+            columns.append(("vsd", len(st.vsd.taus) + 4, st.vsd.packed()))
+        if st.vsd.grid:
+            columns.append(("grid", st.vsd.grid_errors.shape[2] + 4, st.vsd.packed_grid()))
+    if st.bop is not None:
+        st.bop.score(batch, poses_dev, p_icp)
+        columns.append(("bop", 4, st.bop.packed()))
+    if st.device_eval:
+        P, t = gt_dev.shape[0], st.tables
+        sets = [poses_dev] + ([p_icp] if p_icp is not None else [])
+        errs = [ops.pose_errors(t[0], t[1], t[2], cls_dev, p, gt_dev, st.K_eval).reshape(-1, P, 5) for p in sets]
+        host = _to_host([("pose", 12, _cat([p.to(f64).reshape(-1, P, 12) for p in sets], 0)), ("err", 5, _cat(errs, 0))] + columns)
+    else:
+        host = {}
+        for column in [("pose", 12, poses_dev)] + columns + ([("pose_icp", 12, p_icp[None])] if p_icp is not None else []):
+            host.update(_to_host([column]))
+        if p_icp is not None:
+            host["pose"] = np.concatenate([host["pose"], host.pop("pose_icp")])
+    host["pose"] = host["pose"].reshape(len(host["pose"]), -1, 3, 4)
+    return host
+
+
+def _read_out_flow(st, refiner, cls_dev, gt_dev):
+    """one more copy per batch with TEST.FLOW_PNP_ITER > 0: the flow poses [and their device errors], and the stage's last stats
+    and flag -> {pose (iter, P, 3, 4), [err (iter, P, 5)], stats (iter, P, 3)}"""
+    f64, n_it, t = torch.float64, st.n_it, st.tables if st.device_eval else None
+    columns = [("pose", 12, refiner.pose_flow_iter.to(f64))]
+    if st.device_eval:
+        columns.append(("err", 5, ops.pose_errors(t[0], t[1], t[2], cls_dev, refiner.pose_flow_iter, gt_dev, st.K_eval)))
+    columns += [("stats", 2, refiner.flow_pnp_stats[:, :, -1].to(f64)),
+                ("flagged", 1, (refiner.status_flow & ops.STATUS_FLOW_PNP_FEW_POINTS).ne(0).to(f64))]
+    host = _to_host(columns)
+    host["pose"] = host["pose"].reshape(n_it, -1, 3, 4)
+    host["stats"] = np.concatenate([host["stats"], host.pop("flagged")], axis=2)
+    return host
+
+
+def _pair_values(st, family, rows, b, undetected, src, gt, cls_b):
+    """What pair b adds to the lists of one family for one pose set: one tuple of FAMILY_KEYS[family] values per row of `rows`
+    (iterations, ...), the pair's rows of the family's column.  This is the one place of the rule for a pair that was not refined,
+    "NO POINT VALID IN INIT POSE" (:419-445): an undetected object comes with pose_rendered = -1 everywhere (sum -12) and is scored
+    with its initial pose and 1000 deg / 1000 m at every iteration instead of its rows; under TEST.DEVICE_EVAL by the host error
+    functions on that pose; its VSD is 1.0 with no counts, whatever its -1 pose rendered; its BOP errors are inf, attained by no
+    symmetry."""
+    from lib.utils.pose_error import calc_rt_dist_m
+
+    if family == "err" and undetected:
+        host = tuple(float(v) for v in st.evaluator.host_pose_errors(st.config, st.evaluator.classes[cls_b], src[b], gt[b]))
+    for row in rows:
+        if family == "rt":
+            est = src[b] if undetected else row
+            yield ((1000, 1000) if undetected else tuple(calc_rt_dist_m(est, gt[b]))) + (est, gt[b])
+        elif family == "err":   # {re, te, add, adi, arp_2d} -> ERR_KEYS: a symmetric class is scored by ADD-S
+            yield host if undetected else tuple(float(v) for v in (row[0], row[1], row[3] if st.uses_adi[cls_b] else row[2], row[4]))
+        elif family in ("vsd", "grid"):   # the errors, one per tau, and the four counts behind them
+            n = len(row) - 4
+            yield ([1.0] * n, 0, 0, 0, 0) if undetected else (row[:n].tolist(),) + tuple(int(v) for v in row[n:])
+        else:
+            yield (float("inf"), float("inf"), -1, -1) if undetected else (float(row[0]), float(row[1]), int(row[2]), int(row[3]))
+
+
+def _collect_batch(st, refiner, batch):
+    """load, refine and score one batch; its pairs go behind what `st.store` holds"""
+    n_it, n_hyp, store = st.n_it, st.n_hyp, st.store
+    extra = {"hyp_poses": batch["hyp_poses"]} if batch.get("hyp_poses") is not None else {}
+    if st.with_coarse:
+        det = batch.get("det_bbox")
+        if det is None:
+            mask = torch.as_tensor(batch["mask_observed"]).to(refiner.net.device, torch.float32).contiguous()
+            det = boxes_from_int(ops.mask_bbox(mask, 0.5))
+        extra["det_boxes"] = det
+    if st.vsd is not None:
+        st.vsd.check(batch, st.vsd_who)
+    if st.with_flow and "pose_observed" not in batch:
+        raise KeyError("pose from flow (TEST.FLOW_PNP_ITER > 0) needs the blob 'pose_observed' to be scored")
+    if st.with_coarse:
+        refiner.load(batch["image_observed"], None, batch.get("mask_observed"), None, None, batch["class_index"],
+                     depth_observed=batch.get("depth_observed"), K=batch.get("K"), **extra)
+        # one more copy per batch; the best candidate stands for the batch's src_pose
+        co = {k: v.cpu().numpy() for k, v in refiner.coarse_out.items()}
+        pose64 = co["pose"].astype(np.float64)
+        for p in range(len(pose64)):
+            store["coarse"].append([pose64[p] if k == "pose" else co[k][p].tolist() for k in COARSE_KEYS])
+        batch = dict(batch, src_pose=co["pose"][:, 0].copy())
+    else:
+        refiner.load(batch["image_observed"], batch["image_rendered"], batch["mask_observed"], batch["mask_rendered"], batch["src_pose"],
+                     batch["class_index"], depth_observed=batch.get("depth_observed"), K=batch.get("K"), **extra)
+    poses_dev = refiner.refine()
+    cls_dev, _, p_icp = _pair_view(refiner, cls=st.device_eval, K=False, icp=st.with_icp)
+    gt_dev = torch.as_tensor(batch["pose_observed"]).to(st.dev, torch.float64).contiguous() if st.device_eval else None
+    host = _read_out(st, batch, poses_dev, p_icp, cls_dev, gt_dev)
+    by_set = {"loop": {k: v[:n_it] for k, v in host.items()}, "icp": {k: v[n_it:] for k, v in host.items()}}
+    if st.with_flow:
+        by_set["flow_pnp"] = _read_out_flow(st, refiner, cls_dev, gt_dev)
+    cls = torch.as_tensor(batch["class_index"]).cpu().numpy().astype(int)
+    gt = torch.as_tensor(batch["pose_observed"]).cpu().numpy().astype(np.float64)
+    src = torch.as_tensor(batch["src_pose"]).cpu().numpy().astype(np.float64)
+    undetected = [bool(np.sum(src[b]) == -12) for b in range(len(src))]
+    if st.epe is not None:   # defined on hypothesis 0, the loaded render
+        flow0 = refiner.flow_est_iter[0] if n_hyp == 1 else refiner.flow_est_iter[0][::n_hyp].contiguous()
+        st.epe.add(batch, flow0, skip=np.sum(src.reshape(src.shape[0], -1), axis=1) == -12)
+    if n_hyp > 1:   # per pair the N scores, the choice and the last-iteration errors of every hypothesis
+        scores = refiner.hyp_score.cpu().numpy().reshape(-1, n_hyp).astype(np.float64)
+        choice = refiner.hyp_choice.cpu().numpy().astype(int)
+        last = refiner.poses_iter[-1].cpu().numpy().astype(np.float64).reshape(-1, n_hyp, 3, 4)
+    for b in range(host["pose"].shape[1]):
+        if n_hyp > 1:
+            errs = list(_pair_values(st, "rt", last[b], b, undetected[b], src, gt, cls[b]))
+            store["hyp"].append((scores[b].tolist(), int(choice[b]), [e[0] for e in errs], [e[1] for e in errs], undetected[b]))
+        for name, family in st.scored:
+            rows = by_set[name]["pose" if family == "rt" else family][:, b]
+            for it, values in enumerate(_pair_values(st, family, rows, b, undetected[b], src, gt, cls[b])):
+                store[name, family].append(cls[b], it, values)
+        if st.with_flow and not undetected[b]:   # the stage's statistics count refined pairs only
+            store["flow_rows"].append((by_set["flow_pnp"]["stats"][:, b].tolist(),))
+
+
+def _merge_over_ranks(store):
+    """-> what every rank collected, rank after rank under every name: one all_gather_object of the whole store"""
+    import torch.distributed as dist
+
+    parts = [None] * dist.get_world_size()
+    dist.all_gather_object(parts, store)
+    for part in parts[1:]:
+        for name, lists in parts[0].items():
+            lists.extend(part[name])
+    return parts[0]
+
+
+def _say(logger, line):
+    print(line)
+    if logger:
+        logger.info(line)
+
+
+def _pose_tables(st, config, name, arp_2d=True):
+    """-> {pose, add [, arp_2d], all_rot_err, all_trans_err} of one pose set: the evaluator's tables on its lists (with
+    TEST.DEVICE_EVAL on the device's errors; flag off: the evaluator is called as before)"""
+    ev, rt = st.evaluator, st.store[name, "rt"]
+    est, gt = rt["poses_est"], rt["poses_gt"]
+    given = {"errors": st.store[name, "err"].lists} if st.device_eval else {}
+    out = {"pose": ev.evaluate_pose(config, est, gt, st.logger, **given),
+           "add": ev.evaluate_pose_add(config, est, gt, output_dir=None, logger=st.logger, **given)}
+    if arp_2d:
+        out["arp_2d"] = ev.evaluate_pose_arp_2d(config, est, gt, output_dir=None, logger=st.logger, **given)
+    return dict(out, all_rot_err=rt["rot_err"], all_trans_err=rt["trans_err"])
+
+
+def _scorer_tables(st, name):
+    """-> {[vsd], [bop], [bop19]} of one pose set: each scorer's table plus "errors", its per-pose lists"""
+    ev, config, store, out = st.evaluator, st.config, st.store, {}
+    if (name, "vsd") in store:
+        out["vsd"] = dict(ev.evaluate_pose_vsd(config, store[name, "vsd"].lists, st.logger), errors=store[name, "vsd"].lists)
+    if (name, "bop") in store:
+        bop = store[name, "bop"]
+        out["bop"] = dict(ev.evaluate_pose_bop(config, bop.lists, st.logger), errors=bop.lists)
+        if (name, "grid") in store:   # AR_VSD on the grid, and AR with the two errors above
+            errs = dict(store[name, "grid"].lists, mssd=bop["mssd"], mspd=bop["mspd"])
+            out["bop19"] = dict(ev.evaluate_pose_bop19(config, errs, st.logger), errors=errs)
+    return out
+
+
+def _tables(st, result_file, merge_ranks, merged):
+    """the result cache, then every table of `out`, printed and logged in the order of the keys"""
     import copy
     import pickle
 
-    from lib.utils.pose_error import calc_rt_dist_m
-
-    bop_vsd = bop_vsd_settings(config)[0]   # before anything is allocated: BOP_VSD without BOP raises here
-    n_cls, n_it = len(evaluator.classes), int(config.TEST.test_iter)
-    all_rot_err = [[[] for _ in range(n_it)] for _ in range(n_cls)]
-    all_trans_err = [[[] for _ in range(n_it)] for _ in range(n_cls)]
-    all_poses_est = [[[] for _ in range(n_it)] for _ in range(n_cls)]
-    all_poses_gt = [[[] for _ in range(n_it)] for _ in range(n_cls)]
-    # depth ICP after the loop: its own one-row lists [rot_err, trans_err, poses_est, poses_gt][cls][0]
-    with_icp = int(config.TEST.get("ICP_ITER", 0) or 0) > 0
-    icp_lists = tuple([[[]] for _ in range(n_cls)] for _ in range(4)) if with_icp else None
-    # several hypotheses per pair: [score, choice, rot_err, trans_err, undetected] per pair
-    n_hyp = int(getattr(refiner, "N", 1))
-    hyp_lists = tuple([] for _ in range(5)) if n_hyp > 1 else None
-    # TEST.DEVICE_EVAL: the per-pose errors the evaluator reads, err_lists[key][cls][iter] (the ICP row: its own one-iteration lists)
-    device_eval = bool(config.TEST.get("DEVICE_EVAL", False))
-    err_lists = icp_err_lists = None
-    if device_eval:
-        from lib.dataset.evaluation import SYM_CLASSES
-
-        err_lists = {k: [[[] for _ in range(n_it)] for _ in range(n_cls)] for k in ERR_KEYS}
-        icp_err_lists = {k: [[[]] for _ in range(n_cls)] for k in ERR_KEYS} if with_icp else None
-        dev = refiner.net.device
-        tables = evaluator.device_tables(dev)
-        K_eval = np.asarray(config.dataset.INTRINSIC_MATRIX, dtype=np.float64)
-        uses_adi = [c in SYM_CLASSES for c in evaluator.classes]
-    # TEST.VSD: vsd_lists[key][cls][iter] (the ICP row: its own one-iteration lists); TEST.BOP_VSD: grid_lists, the same for the grid.
-    # One scorer renders for both
-    vsd = vsd_lists = icp_vsd_lists = grid_lists = icp_grid_lists = None
-    vsd_who = "TEST.VSD" if bool(config.TEST.get("VSD", False)) else "TEST.BOP_VSD"
-    if bool(config.TEST.get("VSD", False)) or bop_vsd:
-        vsd = VsdScorer(config, refiner, n_it + (1 if with_icp else 0), evaluator)
-    if vsd is not None and vsd.absolute:
-        vsd_lists = {k: [[[] for _ in range(n_it)] for _ in range(n_cls)] for k in VSD_KEYS}
-        icp_vsd_lists = {k: [[[]] for _ in range(n_cls)] for k in VSD_KEYS} if with_icp else None
-        n_tau = len(vsd.taus)
-    if bop_vsd:
-        grid_lists = {k: [[[] for _ in range(n_it)] for _ in range(n_cls)] for k in GRID_KEYS}
-        icp_grid_lists = {k: [[[]] for _ in range(n_cls)] for k in GRID_KEYS} if with_icp else None
-        n_grid = vsd.grid_errors.shape[2]
-    # TEST.BOP: bop_lists[key][cls][iter] (the ICP row: its own one-iteration lists)
-    bop = bop_lists = icp_bop_lists = None
-    if bool(config.TEST.get("BOP", False)):
-        bop = BopScorer(config, refiner, evaluator, n_it + (1 if with_icp else 0))
-        bop_lists = {k: [[[] for _ in range(n_it)] for _ in range(n_cls)] for k in BOP_KEYS}
-        icp_bop_lists = {k: [[[]] for _ in range(n_cls)] for k in BOP_KEYS} if with_icp else None
-    # pose from flow at every iteration: [rot_err, trans_err, poses_est, poses_gt][cls][iter], and per refined pair (iter, 3) =
-    # (weighted points, rms, flagged) of the stage's last Gauss-Newton iteration
-    with_flow = int(config.TEST.get("FLOW_PNP_ITER", 0) or 0) > 0
-    flow_lists = tuple([[[] for _ in range(n_it)] for _ in range(n_cls)] for _ in range(4)) if with_flow else None
-    flow_err_lists = {k: [[[] for _ in range(n_it)] for _ in range(n_cls)] for k in ERR_KEYS} if (with_flow and device_eval) else None
-    flow_rows = [] if with_flow else None
-    # flow error of the first forward (:500-512): only the full test graph emits the flow head's output
-    epe = FlowEPE(config, getattr(refiner, "P", refiner.B), refiner.net.device) if (config.network.PRED_FLOW and not config.TEST.FAST_TEST) else None
-    # starting poses from detection boxes: [idx, score, status, pose] per pair
-    with_coarse = getattr(refiner, "coarse", None) is not None
-    coarse_lists = tuple([] for _ in range(4)) if with_coarse else None
-    for batch in batches:
-        extra = {"hyp_poses": batch["hyp_poses"]} if batch.get("hyp_poses") is not None else {}
-        if with_coarse:
-            det = batch.get("det_bbox")
-            if det is None:
-                mask = torch.as_tensor(batch["mask_observed"]).to(refiner.net.device, torch.float32).contiguous()
-                det = boxes_from_int(ops.mask_bbox(mask, 0.5))
-            extra["det_boxes"] = det
-        if vsd is not None:
-            vsd.check(batch, vsd_who)
-        if with_flow and "pose_observed" not in batch:
-            raise KeyError("pose from flow (TEST.FLOW_PNP_ITER > 0) needs the blob 'pose_observed' to be scored")
-        if with_coarse:
-            refiner.load(batch["image_observed"], None, batch.get("mask_observed"), None, None, batch["class_index"],
-                         depth_observed=batch.get("depth_observed"), K=batch.get("K"), **extra)
-            # one more copy per batch; the best candidate stands for the batch's src_pose
-            co = {k: v.cpu().numpy() for k, v in refiner.coarse_out.items()}
-            for k, key in enumerate(("idx", "score", "status", "pose")):
-                coarse_lists[k].extend(co[key].tolist() if key != "pose" else list(co[key].astype(np.float64)))
-            batch = dict(batch, src_pose=co["pose"][:, 0].copy())
-        else:
-            refiner.load(batch["image_observed"], batch["image_rendered"], batch["mask_observed"], batch["mask_rendered"], batch["src_pose"],
-                         batch["class_index"], depth_observed=batch.get("depth_observed"), K=batch.get("K"), **extra)
-        if device_eval:
-            # the errors of every pose on the device, packed behind the poses (float32 -> float64 is exact): rows (iter [+ 1 for ICP],
-            # B, 12 + 5), ONE device->host copy per batch
-            poses_dev = refiner.refine()
-            if vsd is not None:
-                vsd.score(batch, list(poses_dev) + ([refiner.pose_icp if n_hyp == 1 else refiner.pose_icp_sel] if with_icp else []))
-            gt_dev = torch.as_tensor(batch["pose_observed"]).to(dev, torch.float64).contiguous()
-            cls_dev = refiner.batch["class_index"] if n_hyp == 1 else refiner.pair["class_index"]
-            rows = [(poses_dev, ops.pose_errors(tables[0], tables[1], tables[2], cls_dev, poses_dev, gt_dev, K_eval))]
-            if with_icp:
-                p_icp = refiner.pose_icp if n_hyp == 1 else refiner.pose_icp_sel
-                rows.append((p_icp, ops.pose_errors(tables[0], tables[1], tables[2], cls_dev, p_icp, gt_dev, K_eval)))
-            packed = torch.cat([torch.cat([p.to(torch.float64).reshape(-1, gt_dev.shape[0], 12), e.reshape(-1, gt_dev.shape[0], 5)], dim=2)
-                                for p, e in rows], dim=0)
-            if vsd_lists is not None:
-                packed = torch.cat([packed, vsd.packed()], dim=2)
-            if grid_lists is not None:
-                packed = torch.cat([packed, vsd.packed_grid()], dim=2)
-            if bop is not None:
-                bop.score(batch, poses_dev, (refiner.pose_icp if n_hyp == 1 else refiner.pose_icp_sel) if with_icp else None)
-                packed = torch.cat([packed, bop.packed()], dim=2)
-            packed = packed.cpu().numpy()
-            w_grid = n_grid + 4 if grid_lists is not None else 0
-            n_vsd = packed.shape[2] - 17 - w_grid - (4 if bop is not None else 0)
-            vsd_host, grid_host, bop_host = (packed[:, :, 17:17 + n_vsd], packed[:, :, 17 + n_vsd:17 + n_vsd + w_grid],
-                                             packed[:, :, 17 + n_vsd + w_grid:])
-            packed = packed[:, :, :17]
-            poses, dev_err = packed[:n_it, :, :12].reshape(n_it, -1, 3, 4), packed[:n_it, :, 12:]
-            if with_icp:
-                poses_icp, dev_err_icp = packed[n_it, :, :12].reshape(-1, 3, 4), packed[n_it, :, 12:]
-        else:
-            poses_dev = refiner.refine()
-            poses = poses_dev.cpu().numpy().astype(np.float64)     # ONE device->host copy per batch: (iter, B, 3, 4)
-            if vsd is not None:   # and one more for the VSD rows, one for the grid's
-                vsd.score(batch, list(poses_dev) + ([refiner.pose_icp if n_hyp == 1 else refiner.pose_icp_sel] if with_icp else []))
-                if vsd_lists is not None:
-                    vsd_host = vsd.packed().cpu().numpy()
-                if grid_lists is not None:
-                    grid_host = vsd.packed_grid().cpu().numpy()
-            if bop is not None:   # and one for the BOP rows
-                bop.score(batch, poses_dev, (refiner.pose_icp if n_hyp == 1 else refiner.pose_icp_sel) if with_icp else None)
-                bop_host = bop.packed().cpu().numpy()
-            if with_icp:
-                poses_icp = (refiner.pose_icp if n_hyp == 1 else refiner.pose_icp_sel).cpu().numpy().astype(np.float64)
-        if with_flow:   # one more copy per batch: the flow poses [and their device errors], and the stage's last stats / status
-            pf = refiner.pose_flow_iter.to(torch.float64).reshape(n_it, -1, 12)
-            if device_eval:
-                pf = torch.cat([pf, ops.pose_errors(tables[0], tables[1], tables[2], cls_dev, refiner.pose_flow_iter, gt_dev, K_eval)], dim=2)
-            pf = torch.cat([pf, refiner.flow_pnp_stats[:, :, -1].to(torch.float64),
-                            (refiner.status_flow & ops.STATUS_FLOW_PNP_FEW_POINTS).ne(0).to(torch.float64)[:, :, None]], dim=2).cpu().numpy()
-            poses_flow, flow_dev_err, flow_stat = pf[:, :, :12].reshape(n_it, -1, 3, 4), pf[:, :, 12:-3], pf[:, :, -3:]
-        cls = torch.as_tensor(batch["class_index"]).cpu().numpy().astype(int)
-        gt = torch.as_tensor(batch["pose_observed"]).cpu().numpy().astype(np.float64)
-        src = torch.as_tensor(batch["src_pose"]).cpu().numpy().astype(np.float64)
-        if epe is not None:   # defined on hypothesis 0, the loaded render
-            flow0 = refiner.flow_est_iter[0] if n_hyp == 1 else refiner.flow_est_iter[0][::n_hyp].contiguous()
-            epe.add(batch, flow0, skip=np.sum(src.reshape(src.shape[0], -1), axis=1) == -12)
-        if n_hyp > 1:
-            scores = refiner.hyp_score.cpu().numpy().reshape(-1, n_hyp).astype(np.float64)
-            choice = refiner.hyp_choice.cpu().numpy().astype(int)
-            last = refiner.poses_iter[-1].cpu().numpy().astype(np.float64).reshape(-1, n_hyp, 3, 4)
-            for b in range(poses.shape[1]):
-                undetected = bool(np.sum(src[b]) == -12)
-                errs = [(1000, 1000) if undetected else calc_rt_dist_m(last[b, h], gt[b]) for h in range(n_hyp)]
-                for k, v in enumerate((scores[b].tolist(), int(choice[b]), [e[0] for e in errs], [e[1] for e in errs], undetected)):
-                    hyp_lists[k].append(v)
-        for b in range(poses.shape[1]):
-            # "NO POINT VALID IN INIT POSE" (:419-445): an undetected object comes with pose_rendered = -1 everywhere (sum -12); it is
-            # scored with its initial pose and 1000 deg / 1000 m at every iteration instead of being refined
-            undetected = np.sum(src[b]) == -12
-            for it in range(n_it):
-                est = src[b] if undetected else poses[it, b]
-                r_dist, t_dist = (1000, 1000) if undetected else calc_rt_dist_m(est, gt[b])
-                all_poses_est[cls[b]][it].append(est)
-                all_poses_gt[cls[b]][it].append(gt[b])
-                all_rot_err[cls[b]][it].append(r_dist)
-                all_trans_err[cls[b]][it].append(t_dist)
-            if with_flow:   # scored as the loop's poses are; the stage's statistics count refined pairs only
-                for it in range(n_it):
-                    est = src[b] if undetected else poses_flow[it, b]
-                    r_dist, t_dist = (1000, 1000) if undetected else calc_rt_dist_m(est, gt[b])
-                    for k, v in enumerate((r_dist, t_dist, est, gt[b])):
-                        flow_lists[k][cls[b]][it].append(v)
-                if not undetected:
-                    flow_rows.append(flow_stat[:, b].tolist())
-            if with_icp:   # an undetected object is scored as the loop scores it
-                est = src[b] if undetected else poses_icp[b]
-                r_dist, t_dist = (1000, 1000) if undetected else calc_rt_dist_m(est, gt[b])
-                for k, v in enumerate((r_dist, t_dist, est, gt[b])):
-                    icp_lists[k][cls[b]][0].append(v)
-            if vsd_lists is not None:   # a pair that was not refined: e = 1.0 and no counts, whatever its -1 pose rendered
-                for lists, rows_b in ((vsd_lists, vsd_host[:n_it, b]), (icp_vsd_lists, vsd_host[n_it:, b])):
-                    for it, row in enumerate(rows_b):
-                        e, cnt = ([1.0] * n_tau, [0] * 4) if undetected else (row[:n_tau].tolist(), [int(v) for v in row[n_tau:]])
-                        for k, v in zip(VSD_KEYS, [e] + cnt):
-                            lists[k][cls[b]][it].append(v)
-            if grid_lists is not None:   # the same rule on the grid
-                for lists, rows_b in ((grid_lists, grid_host[:n_it, b]), (icp_grid_lists, grid_host[n_it:, b])):
-                    for it, row in enumerate(rows_b):
-                        e, cnt = ([1.0] * n_grid, [0] * 4) if undetected else (row[:n_grid].tolist(), [int(v) for v in row[n_grid:]])
-                        for k, v in zip(GRID_KEYS, [e] + cnt):
-                            lists[k][cls[b]][it].append(v)
-            if bop is not None:   # a pair that was not refined: inf, attained by no symmetry
-                for lists, rows_b in ((bop_lists, bop_host[:n_it, b]), (icp_bop_lists, bop_host[n_it:, b])):
-                    for it, row in enumerate(rows_b):
-                        vals = (float("inf"), float("inf"), -1, -1) if undetected else (float(row[0]), float(row[1]), int(row[2]), int(row[3]))
-                        for k, v in zip(BOP_KEYS, vals):
-                            lists[k][cls[b]][it].append(v)
-            if device_eval:   # {re, te, add, adi, arp_2d} -> the four lists; a pair that was not refined: the host functions on its row
-                host = evaluator.host_pose_errors(config, evaluator.classes[cls[b]], src[b], gt[b]) if undetected else None
-                pick = lambda e: (e[0], e[1], e[3] if uses_adi[cls[b]] else e[2], e[4])  # noqa: E731
-                for it in range(n_it):
-                    for k, v in zip(ERR_KEYS, host or pick(dev_err[it, b])):
-                        err_lists[k][cls[b]][it].append(float(v))
-                if with_icp:
-                    for k, v in zip(ERR_KEYS, host or pick(dev_err_icp[b])):
-                        icp_err_lists[k][cls[b]][0].append(float(v))
-                if with_flow:
-                    for it in range(n_it):
-                        for k, v in zip(ERR_KEYS, host or pick(flow_dev_err[it, b])):
-                            flow_err_lists[k][cls[b]][it].append(float(v))
-    # several ranks refine disjoint shards (one process per GPU): the metrics are over ALL pairs, so the per-class lists are merged in
-    # rank order on every rank before scoring (the reference scores one list in one process)
-    import torch.distributed as dist
-
-    merged = False
-    if merge_ranks and dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
-        parts = [None] * dist.get_world_size()
-        dist.all_gather_object(parts, (all_rot_err, all_trans_err, all_poses_est, all_poses_gt, icp_lists, hyp_lists, err_lists, icp_err_lists,
-                                       vsd_lists, icp_vsd_lists, bop_lists, icp_bop_lists, flow_lists, flow_err_lists, flow_rows,
-                                       grid_lists, icp_grid_lists, coarse_lists))
-        for k, mine in enumerate((all_rot_err, all_trans_err, all_poses_est, all_poses_gt)):
-            for c in range(n_cls):
-                for it in range(n_it):
-                    mine[c][it] = [x for part in parts for x in part[k][c][it]]
-        if with_icp:
-            for k, mine in enumerate(icp_lists):
-                for c in range(n_cls):
-                    mine[c][0] = [x for part in parts for x in part[4][k][c][0]]
-        if hyp_lists is not None:
-            for k, mine in enumerate(hyp_lists):
-                mine[:] = [x for part in parts for x in part[5][k]]
-        if coarse_lists is not None:
-            for k, mine in enumerate(coarse_lists):
-                mine[:] = [x for part in parts for x in part[17][k]]
-        for slot, lists, iters in ((6, err_lists, n_it), (7, icp_err_lists, 1), (8, vsd_lists, n_it), (9, icp_vsd_lists, 1),
-                                   (10, bop_lists, n_it), (11, icp_bop_lists, 1), (15, grid_lists, n_it), (16, icp_grid_lists, 1)):
-            for k in (lists or {}):
-                for c in range(n_cls):
-                    for it in range(iters):
-                        lists[k][c][it] = [x for part in parts for x in part[slot][k][c][it]]
-        if with_flow:
-            for k, mine in enumerate(flow_lists):
-                for c in range(n_cls):
-                    for it in range(n_it):
-                        mine[c][it] = [x for part in parts for x in part[12][k][c][it]]
-            for k in (flow_err_lists or {}):
-                for c in range(n_cls):
-                    for it in range(n_it):
-                        flow_err_lists[k][c][it] = [x for part in parts for x in part[13][k][c][it]]
-            flow_rows[:] = [x for part in parts for x in part[14]]
-        merged = True
-        if dist.get_rank() != 0:
-            result_file = None   # one result cache, written by rank 0
+    config, store, logger, n_it = st.config, st.store, st.logger, st.n_it
+    rt = store["loop", "rt"]
     if result_file:
         with open(result_file, "wb") as f:
-            pickle.dump([np.array(all_rot_err, dtype=object), np.array(all_trans_err, dtype=object), all_poses_est, all_poses_gt], f,
+            pickle.dump([np.array(rt["rot_err"], dtype=object), np.array(rt["trans_err"], dtype=object), rt["poses_est"], rt["poses_gt"]], f,
                         protocol=2)
     out = {}
-    if epe is not None:   # :656-660, before the pose tables like the reference
-        out["epe"] = epe.result(merge_ranks=merge_ranks)
+    if st.epe is not None:   # :656-660, before the pose tables like the reference
+        out["epe"] = st.epe.result(merge_ranks=merge_ranks)
         for line in ("evaluate flow:", "EPE all: {}".format(out["epe"]["epe_all"]), "EPE ignore unvisible: {}".format(out["epe"]["epe_vizbg"]),
                      "EPE visible: {}".format(out["epe"]["epe_viz"])):
-            print(line)
-            if logger:
-                logger.info(line)
-    given = {"errors": err_lists} if device_eval else {}   # flag off: the evaluator is called as before
-    out["pose"] = evaluator.evaluate_pose(config, all_poses_est, all_poses_gt, logger, **given)
-    out["add"] = evaluator.evaluate_pose_add(config, all_poses_est, all_poses_gt, output_dir=None, logger=logger, **given)
-    out["arp_2d"] = evaluator.evaluate_pose_arp_2d(config, all_poses_est, all_poses_gt, output_dir=None, logger=logger, **given)
-    if device_eval:
+            _say(logger, line)
+    tables = _pose_tables(st, config, "loop")
+    out.update((k, tables[k]) for k in ("pose", "add", "arp_2d"))
+    if st.device_eval:
         out["device_eval"] = True
-    if vsd_lists is not None:
-        out["vsd"] = dict(evaluator.evaluate_pose_vsd(config, vsd_lists, logger), errors=vsd_lists)
-    if bop is not None:
-        out["bop"] = dict(evaluator.evaluate_pose_bop(config, bop_lists, logger), errors=bop_lists)
-    if grid_lists is not None:   # AR_VSD on the grid, and AR with the two errors above
-        errs = dict(grid_lists, mssd=bop_lists["mssd"], mspd=bop_lists["mspd"])
-        out["bop"]["bop19"] = dict(evaluator.evaluate_pose_bop19(config, errs, logger), errors=errs)
-    out["all_rot_err"], out["all_trans_err"] = all_rot_err, all_trans_err
+    out.update(_scorer_tables(st, "loop"))
+    if "bop19" in out:   # the loop's completes its BOP table; the ICP row's stays next to it
+        out["bop"]["bop19"] = out.pop("bop19")
+    out["all_rot_err"], out["all_trans_err"] = tables["all_rot_err"], tables["all_trans_err"]
     out["merged_over_ranks"] = merged
-    if with_icp:
+    if st.with_icp:
         # one row, as the reference's PRECOMPUTED_ICP branch scores it (tester.py:253-330) -- on a copy of the config, since that
         # branch sets the global config.TEST.test_iter = 1
         cfg1 = copy.deepcopy(config)
         cfg1.TEST.test_iter = 1
-        icp_rot, icp_trans, icp_est, icp_gt = icp_lists
-        line = "evaluate ICP ({} iterations, gate {} m):".format(int(config.TEST.ICP_ITER), float(config.TEST.ICP_MAX_DIST))
-        print(line)
-        if logger:
-            logger.info(line)
-        given = {"errors": icp_err_lists} if device_eval else {}
-        out["icp"] = {"pose": evaluator.evaluate_pose(cfg1, icp_est, icp_gt, logger, **given),
-                      "add": evaluator.evaluate_pose_add(cfg1, icp_est, icp_gt, output_dir=None, logger=logger, **given),
-                      "arp_2d": evaluator.evaluate_pose_arp_2d(cfg1, icp_est, icp_gt, output_dir=None, logger=logger, **given),
-                      "all_rot_err": icp_rot, "all_trans_err": icp_trans}
-        if vsd_lists is not None:
-            out["icp"]["vsd"] = dict(evaluator.evaluate_pose_vsd(config, icp_vsd_lists, logger), errors=icp_vsd_lists)
-        if bop is not None:
-            out["icp"]["bop"] = dict(evaluator.evaluate_pose_bop(config, icp_bop_lists, logger), errors=icp_bop_lists)
-        if grid_lists is not None:
-            errs = dict(icp_grid_lists, mssd=icp_bop_lists["mssd"], mspd=icp_bop_lists["mspd"])
-            out["icp"]["bop19"] = dict(evaluator.evaluate_pose_bop19(config, errs, logger), errors=errs)
-    if with_flow:
-        flow_rot, flow_trans, flow_est, flow_gt = flow_lists
-        line = "evaluate pose from flow ({} iterations, {} unweighted, Huber {} px, gate {} px):".format(
-            int(config.TEST.FLOW_PNP_ITER), int(config.TEST.FLOW_PNP_WARM), float(config.TEST.FLOW_PNP_HUBER_PX), float(config.TEST.FLOW_PNP_MAX_PX))
-        print(line)
-        if logger:
-            logger.info(line)
-        given = {"errors": flow_err_lists} if device_eval else {}
-        rows = np.asarray(flow_rows, dtype=np.float64).reshape(-1, n_it, 3)
+        _say(logger, "evaluate ICP ({} iterations, gate {} m):".format(int(config.TEST.ICP_ITER), float(config.TEST.ICP_MAX_DIST)))
+        out["icp"] = dict(_pose_tables(st, cfg1, "icp"), **_scorer_tables(st, "icp"))
+    if st.with_flow:
+        _say(logger, "evaluate pose from flow ({} iterations, {} unweighted, Huber {} px, gate {} px):".format(
+            int(config.TEST.FLOW_PNP_ITER), int(config.TEST.FLOW_PNP_WARM), float(config.TEST.FLOW_PNP_HUBER_PX), float(config.TEST.FLOW_PNP_MAX_PX)))
+        rows = np.asarray(store["flow_rows"]["stats"], dtype=np.float64).reshape(-1, n_it, 3)
         mean = rows.mean(axis=0) if len(rows) else np.full((n_it, 3), np.nan)
-        out["flow_pnp"] = {"pose": evaluator.evaluate_pose(config, flow_est, flow_gt, logger, **given),
-                           "add": evaluator.evaluate_pose_add(config, flow_est, flow_gt, output_dir=None, logger=logger, **given),
-                           "all_rot_err": flow_rot, "all_trans_err": flow_trans, "inliers": mean[:, 0].tolist(), "rms": mean[:, 1].tolist(),
-                           "flagged": [int(v) for v in rows[:, :, 2].sum(axis=0)]}
+        out["flow_pnp"] = dict(_pose_tables(st, config, "flow_pnp", arp_2d=False), inliers=mean[:, 0].tolist(), rms=mean[:, 1].tolist(),
+                               flagged=[int(v) for v in rows[:, :, 2].sum(axis=0)])
         for it in range(n_it):
-            line = "iter {}: {:.1f} weighted points, rms {:.3f} px, {} of {} pairs flagged".format(
-                it + 1, mean[it, 0], mean[it, 1], out["flow_pnp"]["flagged"][it], len(rows))
-            print(line)
-            if logger:
-                logger.info(line)
-    if hyp_lists is not None:
-        score, choice, rot, trans, undet = hyp_lists
-        best = [c == int(np.argmin(r)) for c, r, u in zip(choice, rot, undet) if not u]
-        out["hyp"] = {"num": n_hyp, "score": score, "choice": choice, "rot_err": rot, "trans_err": trans, "undetected": undet,
-                      "chosen_is_least_rot_err": float(np.mean(best)) if best else float("nan")}
-        line = "hypotheses: {} per pair, the chosen one has the least rotation error in {:.1f} % of {} pairs".format(
-            n_hyp, 100.0 * out["hyp"]["chosen_is_least_rot_err"], len(best))
-        print(line)
-        if logger:
-            logger.info(line)
-    if coarse_lists is not None:
-        out["coarse"] = dict(zip(("idx", "score", "status", "pose"), coarse_lists))
+            _say(logger, "iter {}: {:.1f} weighted points, rms {:.3f} px, {} of {} pairs flagged".format(
+                it + 1, mean[it, 0], mean[it, 1], out["flow_pnp"]["flagged"][it], len(rows)))
+    if st.n_hyp > 1:
+        hyp = store["hyp"]
+        best = [c == int(np.argmin(r)) for c, r, u in zip(hyp["choice"], hyp["rot_err"], hyp["undetected"]) if not u]
+        out["hyp"] = dict({"num": st.n_hyp}, **hyp.lists)
+        out["hyp"]["chosen_is_least_rot_err"] = float(np.mean(best)) if best else float("nan")
+        _say(logger, "hypotheses: {} per pair, the chosen one has the least rotation error in {:.1f} % of {} pairs".format(
+            st.n_hyp, 100.0 * out["hyp"]["chosen_is_least_rot_err"], len(best)))
+    if st.with_coarse:
+        out["coarse"] = dict(store["coarse"].lists)
     return out
