@@ -14,6 +14,7 @@ Master parameters keep the MXNet layouts and names (one flat fp32 vector, 57.75 
 """
 from __future__ import print_function, division
 
+import collections
 import os
 
 import numpy as np
@@ -21,8 +22,11 @@ import torch
 
 from lib.hip import ops
 from lib.utils.dist_utils import allreduce_sum_
-from deepim.symbols.deepIM_flownet import bf16_tile, BF16_PATCH, ENCODER, FlowNetHip, deepIM_flownet
+from deepim.symbols.deepIM_flownet import bf16_tile, BF16_PATCH, ENCODER, FlowNetHip, deepIM_flownet, encoder_geometry
 
+# Switches.  These two and BF16_PATCH / BF16_BIG_TILE (deepIM_flownet.py) are read at import; DIM_BF16_HALO, DIM_BF16_DGRAD_SPLITK,
+# DIM_BF16_SMALL_TILE and DIM_WINO_WGRAD when an executor is constructed (read_switches): the backward plan is built from them once,
+# and a change of the environment after that does not reach an existing executor.
 FUSED_UNPACK = os.environ.get("DIM_WGRAD_FUSED_UNPACK", "1") != "0"   # encoder weight gradients through dim_conv2d_wgrad_oihw
 FOLD_LRELU = os.environ.get("DIM_BF16_FOLD_LRELU", "1") != "0"         # bf16: LeakyReLU' + bias gradient inside the input-gradient epilogue
 FROZEN = ("upsampling_weight", "mask_upsampling_weight")  # attr lr_mult 0.0 (deepIM_flownet.py:334, :520)
@@ -36,6 +40,126 @@ FROZEN = ("upsampling_weight", "mask_upsampling_weight")  # attr lr_mult 0.0 (de
 BACKWARD_ORDER = ["Convolution3", "mask_conv3", "upsample_flow5to4", "deconv4", "Convolution2", "upsample_flow6to5", "deconv5", "Convolution1",
                   "rot", "trans", "fc7", "fc6"] + [l[0] for l in reversed(ENCODER)]
 BUCKET_ENDS = ("fc6_weight", "conv5_weight")
+
+Switches = collections.namedtuple("Switches", "fused_unpack fold_lrelu patch halo dgrad_splitk small_tile wino_wgrad")
+# One encoder layer of backward(): its geometry record, how its weight gradient runs -- kind "wino" (S, pixel splits), "lanes"
+# (flow_conv1 with 6 or 10 input channels), "fused" (dim_conv2d_wgrad_oihw) or "packed" (FUSED_UNPACK off), each with its split count --,
+# how the gradient reaches the layer below -- kind None (first layer), "wino" (m, GEMM tile), "wino5", "fold" (conv2d_dgrad_lrelu, which
+# also delivers the dz and bias gradient of the layer below) or "gemm" (tile, split-K count) --, the concat-gradient buffer whose skip
+# term it adds (or None), and whether it computes its own dz (False: the fold of the layer above has)
+WGrad = collections.namedtuple("WGrad", "kind splits S")
+DGrad = collections.namedtuple("DGrad", "kind tile splits m")
+LayerBackward = collections.namedtuple("LayerBackward", "geom wgrad dgrad skip own_dz")
+# layers: top down.  deconv: {name: (pixel splits of the weight gradient, tile of the input gradient)}.  The rest: buffer sizes in floats (0: no buffer)
+BackwardPlan = collections.namedtuple("BackwardPlan", "layers deconv ws gpack bias_ws fold_ws wino_ws wino_wgrad_ws")
+
+
+def read_switches(env=None):
+    env = os.environ if env is None else env
+    on = lambda key: env.get(key, "1") != "0"  # noqa: E731
+    return Switches(FUSED_UNPACK, FOLD_LRELU, BF16_PATCH, on("DIM_BF16_HALO"), on("DIM_BF16_DGRAD_SPLITK"), on("DIM_BF16_SMALL_TILE"), on("DIM_WINO_WGRAD"))
+
+
+def bf16_gemm_tile(rows, cols, small_tile=True):
+    """workgroup tile of a bf16 input-gradient GEMM with `rows` output pixels (per launch: a stride-2 gradient runs one launch per
+    input phase, each with as many rows as dY has pixels) x `cols` channels: the wide tile only when it fills the chip -- conv6_1's
+    gradient is 10 x 8 tiles of 128 x 128 with K = 9216, 80 workgroups on 256 CUs (149 us); 64 x 64 tiles give 320.
+    small_tile False (DIM_BF16_SMALL_TILE=0): the wide tile wherever the channel count allows."""
+    t = bf16_tile(cols)
+    return 3 if (t != 3 and small_tile and -(-rows // 128) * (cols // 128) < 200) else t
+
+
+def dgrad_splits(tile, rows, cols, cout, n_cu, splitk=True):
+    """split-K count of a bf16 input gradient on the gathered-tap kernel: the small maps (conv5 .. conv6_1: 1280-4800 rows per
+    launch) make 144-600 tiles of 64 x 64 for the 1280 workgroups that fit the chip (5 per CU), and each walks K = 4608-9216 alone.
+    The K range is cut so that the grid fills the slots; every phase of a strided gradient must keep >= splits chunks of 32 dy
+    channels (its 1-tap phase has cout / 32).  splitk False (DIM_BF16_DGRAD_SPLITK=0): off."""
+    tiles = -(-rows // 64) * (cols // 64)
+    return next((sp for sp in (8, 4, 2) if tile == 3 and splitk and sp * tiles <= 5 * n_cu and (cout // 32) % sp == 0), 1)
+
+
+def plan_backward(B, bf16, has_decoder, n_cu, wino, wino5, wino_m, lanes, sw):
+    """Everything backward() decides and every scratch size _init_backward allocates, from what is static once an executor exists;
+    needs no device (the library's size / split queries are host arithmetic).  wino / wino5 / wino_m: the forward executor's Winograd
+    layers; lanes: 8-lane input groups of flow_conv1 beyond the plain 8-channel case (0, 1 or 2); sw: Switches.  -> BackwardPlan"""
+    lib, P = ops.lib(), ops.pad64
+    ws = gpack = fold_ws = wino_ws = wino_wgrad_ws = 4
+    bias_ws = lib.dim_bias_grad_workspace_floats(B * 240 * 320, 64) + 1024 * 64
+    layers, folded = [], set()
+    for geom in reversed(encoder_geometry()):
+        name, prev, c, cout, k, s, p, h, w, ho, wo = geom
+        rows, wide = B * ho * wo, (cout // 128 if cout % 128 == 0 else cout // 64)
+        # ---- weight gradient.  Direct kernel: split the pixel range until the grid has ~4096 workgroups (measured at B = 16: 1024 ->
+        # 15.6 ms per backward, 2048 -> 14.7, 4096 -> 14.3, 8192 -> 14.1; short workgroups hide the gather latency better and balance the CUs)
+        nchunks = -(-k * k // 4) if c == 8 else k * k * (c // 32)
+        sp = max(1, min(-(-4096 // (nchunks * wide)), max(1, (-(-rows // 32)) // 4)))
+        if bf16:
+            # the WHOLE grid must be resident at once (2-4 workgroups per CU by kernel form): a grid one workgroup over that runs a
+            # second, nearly empty round in which nothing overlaps the phases of a step.  tools/wgrad_sweep.py at B = 16,
+            # workgroups: us -- conv3_1 756: 155, 1044: 187, 1512: 168; conv2 767: 252, 1027: 318 (the round-2 rule aimed at ~1024
+            # with a ceiling division and overshot the 768 slots on every layer).  One plan function for every caller:
+            sp = lib.dim_conv2d_wgrad_bf16_splits(B, h, w, c, cout, k, k, s, p, n_cu)
+        wgrad = WGrad("lanes" if (prev is None and lanes) else "fused" if sw.fused_unpack else "packed", sp, 0)
+        ws = max(ws, lib.dim_conv2d_wgrad_workspace_floats(cout, c, k, k, sp + 1))   # + 1: dim_conv2d_wgrad_oihw
+        gpack = max(gpack, lib.dim_conv2d_packed_weight_floats(cout, c, k, k))
+        # Winograd weight gradients (3x3 / stride-1 and 5x5 / stride-2 layers whose maps are large enough: at 8x10 the 36 plane
+        # products are 3 pixel steps long and their 151 MB of dM cost more than the direct kernel saves)
+        S, tiles = (1 if name in wino else 2 if name in wino5 else 0), B * (-(-ho // 4)) * (-(-wo // 4))
+        if sw.wino_wgrad and not bf16 and S and tiles >= 256 and (c * S * S) % 64 == 0:
+            wgrad = WGrad("wino", max(1, min(-(-2048 // (36 * (c * S * S // 64) * wide)), max(1, (tiles // 32) // 4))), S)
+            wino_wgrad_ws = max(wino_wgrad_ws, lib.dim_conv2d_wgrad_winograd_workspace_floats(B, h, w, c, cout, S, wgrad.splits))
+        # ---- input gradient
+        if prev is None:
+            dgrad = DGrad(None, 0, 1, 0)
+        elif name in wino:
+            # dX of a 3x3 / stride-1 / pad-1 convolution = the same kind of convolution of dZ with the flipped, transposed
+            # kernel: Winograd like the forward (no bias, no activation)
+            m = wino_m[name]
+            dgrad = DGrad("wino", 4 if (c % 128 == 0 and B * (-(-ho // m)) * (-(-wo // m)) >= 1024) else 3, 1, m)
+            wino_ws = max(wino_ws, lib.dim_winograd_workspace_floats(B, h, w, cout, c, m))
+        elif name in wino5:
+            dgrad = DGrad("wino5", 0, 1, 0)
+            wino_ws = max(wino_ws, lib.dim_winograd5x5s2_workspace_floats(B, h, w, c, cout))
+        else:
+            # bf16: operand-traffic bound, so the widest tile the channel count allows (dX channels are the GEMM's N)
+            tile = bf16_gemm_tile(rows, P(c), sw.small_tile) if bf16 else 3
+            if tile != 3 and s == 1 and k == 3 and ho * wo >= 1200 and sw.halo:
+                tile = 7   # stride-1 input gradient of a large map: LDS-halo kernel
+            if bf16 and sw.patch and k in (3, 5) and ho * wo >= 1200:
+                tile = 9   # stride-1 patch kernel: the gradient itself (stride 1) or its four phase convolutions (stride 2)
+            ksp = dgrad_splits(tile, rows, P(c), cout, n_cu, sw.dgrad_splitk) if bf16 else 1
+            # fold: every phase runs on the patch kernel and this is the only gradient that reaches the layer below, so its LeakyReLU'
+            # and bias gradient ride in the epilogue instead of a 12-bytes-per-element pass of their own (flow_conv1, conv2, conv3,
+            # conv4: 80 % of the encoder's activation elements).  The decoder clause cannot fire on this encoder -- the layers above
+            # conv4_1 and conv5_1 are 3x3 / stride-2, which the fold does not take -- and stays: it is what keeps the rule safe (the
+            # skip term is a second gradient into those layers) if a layer changes
+            fold = (sw.fold_lrelu and tile == 9 and ksp == 1 and (k, s) in ((5, 2), (3, 1)) and c % 64 == 0
+                    and not (has_decoder and prev in ("conv4_1", "conv5_1")))
+            dgrad = DGrad("fold" if fold else "gemm", tile, ksp, 0)
+            if fold:
+                folded.add(prev)
+        if bf16 and c != 8:
+            # split-K slabs of this layer's input gradient (copies of dX): an upper bound -- sized for the gathered-tap kernel's
+            # split count whether or not the layer ends on tile 7 or 9 (no split-K) or on Winograd
+            ub = dgrad_splits(bf16_gemm_tile(rows, P(c), sw.small_tile), rows, P(c), cout, n_cu, sw.dgrad_splitk)
+            ws = max(ws, lib.dim_conv2d_dgrad_splitk_workspace_floats(B, h, w, P(c), ub))
+        if bf16 and sw.fold_lrelu and c % 64 == 0:   # partial column sums of the folded input gradients: every layer that could fold
+            fold_ws = max(fold_ws, lib.dim_conv2d_dgrad_lrelu_workspace_floats(B, h, w, c, s))
+        bias_ws = max(bias_ws, lib.dim_lrelu_bwd_bias_grad_workspace_floats(rows, cout))   # partial column sums of the fused LeakyReLU' + bias-gradient pass
+        skip = {"conv5_1": "dconcat2", "conv4_1": "dconcat3"}.get(name) if has_decoder else None
+        layers.append(LayerBackward(geom, wgrad, dgrad, skip, name not in folded))
+    gpack = max(gpack, 256 * 81920, 4 * 4 * 512 * 1024, 4 * 4 * 256 * P(1026))
+    ws = max(ws, lib.dim_conv2d_wgrad_workspace_floats(P(1026), 256, 4, 4, 3),   # deconv4's split gradient (_deconv_bwd)
+             lib.dim_conv_small_cout_bwd_workspace_floats(B, 30, 40, 770, 2, 3, 3),
+             lib.dim_conv_small_cout_bwd_workspace_floats(B, 15, 20, 1026, 2, 3, 3),
+             lib.dim_conv_small_cout_bwd_workspace_floats(B, 8, 10, 1024, 2, 3, 3))
+
+    def deconv(rows, cpad):
+        # bf16: deconv4's weight-gradient view is 544 workgroups of the 64-row kernel: three pixel splits fill the resident slots, 183 -> 151 us
+        return (3 if (bf16 and rows >= 4096 and cpad % 128 != 0) else 1, bf16_gemm_tile(rows, cpad, sw.small_tile) if bf16 else 3)
+    return BackwardPlan(tuple(layers), {"deconv4": deconv(B * 15 * 20, P(1026)), "deconv5": deconv(B * 8 * 10, 1024)}, ws, gpack, bias_ws,
+                        fold_ws if (bf16 and sw.fold_lrelu) else 0, wino_ws if (wino or wino5) else 0,
+                        wino_wgrad_ws if (sw.wino_wgrad and not bf16) else 0)
 
 
 class MutableModule(object):
@@ -177,6 +301,8 @@ class MutableModule(object):
         nl = 0 if net.cin == 8 else (2 if net.input_mode == 3 else 1)
         self.w1_lanes = [z(64, 8, 7, 7) for _ in range(nl)]
         self.g1_lanes = [z(64, 8, 7, 7) for _ in range(nl)]
+        # (input tensor, first channel, channels) of each group: one weight gradient per group, copied into its channel window
+        self.lane_groups = [(net.X, 0, min(net.cin, 8)), (net.X2, 8, 2)][:nl]
         self.dconcat3 = z(B, 30, 40, ops.pad64(770))
         self.dconcat2 = z(B, 15, 20, ops.pad64(1026))
         self.dflow4, self.dmask4 = z(B, 30, 40, 2), z(B, 30, 40, 1)
@@ -184,84 +310,14 @@ class MutableModule(object):
         self.dflow_full, self.dlogit = z(B, 2, 480, 640), z(B, 1, 480, 640)
         self.d_rot_norm, self.d_rot, self.d_trans = z(B, 4), z(B, 4), z(B, 3)
         self.dz7, self.dz6 = z(B, 256), z(B, 256)
-        self.pts_est = None
-        self.dpts = None
-        # wgrad plan: split the pixel range until the grid has ~4096 workgroups (measured at B = 16: 1024 -> 15.6 ms per backward,
-        # 2048 -> 14.7, 4096 -> 14.3, 8192 -> 14.1; short workgroups hide the gather latency better and balance the CUs);
-        # scratch = biggest slab set / packed gradient
-        self.wgrad_splits, max_ws, max_pack = {}, 4, 4
-        h, w, c = 480, 640, 8
-        for name, cout, k, s, p in ENCODER:
-            ho, wo = ops.conv_out_hw(h, w, k, k, s, p)
-            nchunks = -(-k * k // 4) if c == 8 else k * k * (c // 32)
-            blocks = nchunks * (cout // 128 if cout % 128 == 0 else cout // 64)
-            nsteps = -(-B * ho * wo // 32)
-            sp = max(1, min(-(-4096 // blocks), max(1, nsteps // 4)))
-            if self.bf16:
-                # the WHOLE grid must be resident at once (2-4 workgroups per CU by kernel form): a grid one workgroup over that runs a
-                # second, nearly empty round in which nothing overlaps the phases of a step.  tools/wgrad_sweep.py at B = 16,
-                # workgroups: us -- conv3_1 756: 155, 1044: 187, 1512: 168; conv2 767: 252, 1027: 318 (the round-2 rule aimed at ~1024
-                # with a ceiling division and overshot the 768 slots on every layer).  One plan function for every caller:
-                sp = ops.lib().dim_conv2d_wgrad_bf16_splits(B, h, w, c, cout, k, k, s, p, self.n_cu)
-            self.wgrad_splits[name] = sp
-            max_ws = max(max_ws, ops.lib().dim_conv2d_wgrad_workspace_floats(cout, c, k, k, sp + 1))   # + 1: dim_conv2d_wgrad_oihw
-            if self.bf16 and c != 8:   # split-K slabs of this layer's input gradient (copies of dX), see _dgrad_splits
-                ksp = self._dgrad_splits(self._bf16_gemm_tile(B * ho * wo, ops.pad64(c)), B * ho * wo, ops.pad64(c), cout)
-                max_ws = max(max_ws, ops.lib().dim_conv2d_dgrad_splitk_workspace_floats(B, h, w, ops.pad64(c), ksp))
-            max_pack = max(max_pack, ops.lib().dim_conv2d_packed_weight_floats(cout, c, k, k))
-            h, w, c = ho, wo, cout
-        max_pack = max(max_pack, 256 * 81920, 4 * 4 * 512 * 1024, 4 * 4 * 256 * ops.pad64(1026))
-        max_ws = max(max_ws, ops.lib().dim_conv2d_wgrad_workspace_floats(ops.pad64(1026), 256, 4, 4, 3),   # deconv4's split gradient (_deconv_bwd)
-                     ops.lib().dim_conv_small_cout_bwd_workspace_floats(B, 30, 40, 770, 2, 3, 3),
-                     ops.lib().dim_conv_small_cout_bwd_workspace_floats(B, 15, 20, 1026, 2, 3, 3),
-                     ops.lib().dim_conv_small_cout_bwd_workspace_floats(B, 8, 10, 1024, 2, 3, 3))
-        self.ws = torch.empty(max_ws, dtype=torch.float32, device=d)
-        self.gpack = torch.empty(max_pack, dtype=torch.float32, device=d)
-        need_b, h, w = ops.lib().dim_bias_grad_workspace_floats(B * 240 * 320, 64) + 1024 * 64, 480, 640
-        for name, cout, k, s, p in ENCODER:   # partial column sums of the fused LeakyReLU' + bias-gradient pass
-            h, w = ops.conv_out_hw(h, w, k, k, s, p)
-            need_b = max(need_b, ops.lib().dim_lrelu_bwd_bias_grad_workspace_floats(B * h * w, cout))
-        self.bias_ws = torch.empty(need_b, dtype=torch.float32, device=d)
-        self.fold_ws = None
-        if self.bf16 and FOLD_LRELU:   # partial column sums of the folded input gradients (backward)
-            need_f, h, w, c = 4, 480, 640, 8
-            for name, cout, k, s, p in ENCODER:
-                if c % 64 == 0:
-                    need_f = max(need_f, ops.lib().dim_conv2d_dgrad_lrelu_workspace_floats(B, h, w, c, s))
-                h, w = ops.conv_out_hw(h, w, k, k, s, p)
-                c = cout
-            self.fold_ws = torch.empty(need_f, dtype=torch.float32, device=d)
+        self.pts_est = self.dpts = None
+        # every per-layer choice of backward() and every scratch size: decided here, once (the switches are read here and nowhere else)
+        self.plan = plan_backward(B, self.bf16, self.has_decoder, self.n_cu, set(net.wino), set(net.wino5), dict(net.wino_m), nl, read_switches())
+        buf = lambda n: torch.empty(n, dtype=torch.float32, device=d) if n else None  # noqa: E731
+        self.ws, self.gpack, self.bias_ws, self.fold_ws = buf(self.plan.ws), buf(self.plan.gpack), buf(self.plan.bias_ws), buf(self.plan.fold_ws)
+        self.wino_ws, self.wino_wgrad_ws = buf(self.plan.wino_ws), buf(self.plan.wino_wgrad_ws)
         # dgrad-layout weights (refreshed by repack())
-        self.dgrad_packed = {}
-        self.wino_dgrad = {}
-        self.wino5_dgrad = {}
-        self.wino_ws = None
-        if net.wino or net.wino5:
-            need, h, w, c = 4, 480, 640, 8
-            for name, cout, k, s, p in ENCODER:
-                if name in net.wino:
-                    need = max(need, ops.lib().dim_winograd_workspace_floats(B, h, w, cout, c, net.wino_m[name]))
-                if name in net.wino5:
-                    need = max(need, ops.lib().dim_winograd5x5s2_workspace_floats(B, h, w, c, cout))
-                h, w = ops.conv_out_hw(h, w, k, k, s, p)
-                c = cout
-            self.wino_ws = torch.empty(need, dtype=torch.float32, device=d)
-        # Winograd weight gradients (3x3 / stride-1 and 5x5 / stride-2 layers whose maps are large enough: at 8x10 the 36 plane
-        # products are 3 pixel steps long and their 151 MB of dM cost more than the direct kernel saves): {layer: (S, pixel splits)}
-        self.wino_wgrad = {}
-        if os.environ.get("DIM_WINO_WGRAD", "1") != "0" and not self.bf16:
-            need, h, w, c = 4, 480, 640, 8
-            for name, cout, k, s, p in ENCODER:
-                ho, wo = ops.conv_out_hw(h, w, k, k, s, p)
-                S = 1 if name in net.wino else 2 if name in net.wino5 else 0
-                tiles = B * (-(-ho // 4)) * (-(-wo // 4))
-                if S and tiles >= 256 and (c * S * S) % 64 == 0:
-                    blocks = 36 * (c * S * S // 64) * (cout // 128 if cout % 128 == 0 else cout // 64)
-                    sp = max(1, min(-(-2048 // blocks), max(1, (tiles // 32) // 4)))
-                    self.wino_wgrad[name] = (S, sp)
-                    need = max(need, ops.lib().dim_conv2d_wgrad_winograd_workspace_floats(B, h, w, c, cout, S, sp))
-                h, w, c = ho, wo, cout
-            self.wino_wgrad_ws = torch.empty(need, dtype=torch.float32, device=d)
+        self.dgrad_packed, self.wino_dgrad, self.wino5_dgrad = {}, {}, {}
         self.repack(forward=False)
 
     # ------------------------------------------------------------------------------------------------------------
@@ -428,71 +484,38 @@ class MutableModule(object):
         ops.conv2d_fwd_ex(dz6, 0, 256, self.dgrad_packed["fc6"], None, d10.view(B, 1, 1, 81920), 0, 81920, 1, 1, 1, 0,
                           accumulate=self.has_decoder)  # M = B rows: tile 3; without a decoder this is d10's only term
         # ---------------- encoder, top down
-        prev = {ENCODER[i][0]: (ENCODER[i - 1][0] if i else None) for i in range(len(ENCODER))}
-        cin = {}
-        c = 8
-        for name, cout, k, s, p in ENCODER:
-            cin[name] = c
-            c = cout
-        dz_done = set()
-        for name, cout, k, s, p in reversed(ENCODER):
-            dy = self.dacts[name]
-            if name == "conv5_1" and self.has_decoder:
-                ops.copy_nhwc_channels(dy, 0, self.dconcat2, 0, 512, add=True)   # skip connection into Concat2
-            if name == "conv4_1" and self.has_decoder:
-                ops.copy_nhwc_channels(dy, 0, self.dconcat3, 0, 512, add=True)   # skip connection into Concat3
-            if name not in dz_done:   # else: the layer above already delivered dz and the bias gradient (folded input gradient, below)
+        for (name, prev, cin, cout, k, s, p, *_), wg, dg, skip, own_dz in self.plan.layers:   # see plan_backward: one dispatch per record
+            dy, gw = self.dacts[name], g[name + "_weight"]
+            if skip:   # skip connection into Concat2 (conv5_1) / Concat3 (conv4_1)
+                ops.copy_nhwc_channels(dy, 0, getattr(self, skip), 0, 512, add=True)
+            if own_dz:   # else: the layer above already delivered dz and the bias gradient (folded input gradient, below)
                 ops.lrelu_bwd_bias_grad(msk.acts[name], dy, cout, g[name + "_bias"], workspace=self.bias_ws)   # dz in place + bias gradient
-            x = net.acts[prev[name]] if prev[name] else net.X
-            if name in self.wino_wgrad:
-                S, sp = self.wino_wgrad[name]
-                ops.conv2d_wgrad_winograd(x, cin[name], dy, cout, g[name + "_weight"], S=S, splits=sp, workspace=self.wino_wgrad_ws)
-            elif name == "flow_conv1" and net.cin != 8:
-                # one weight gradient per 8-lane input group, each copied into its channel window of the (64, cin, 7, 7) gradient
-                for lane, xin, c0, nch in ((0, net.X, 0, min(net.cin, 8)),) + (((1, net.X2, 8, 2),) if net.input_mode == 3 else ()):
-                    ops.conv2d_wgrad(xin, 8, dy, cout, k, k, s, p, self.gpack, splits=self.wgrad_splits[name], workspace=self.ws,
-                                     bf16_mfma=self.bf16)
-                    ops.conv2d_unpack_weight(self.gpack, self.g1_lanes[lane])
-                    ops.copy_channels(g[name + "_weight"], c0, self.g1_lanes[lane], 0, nch)
-            elif FUSED_UNPACK:
+            x = net.acts[prev] if prev else net.X
+            if wg.kind == "wino":
+                ops.conv2d_wgrad_winograd(x, cin, dy, cout, gw, S=wg.S, splits=wg.splits, workspace=self.wino_wgrad_ws)
+            elif wg.kind == "lanes":
+                for (xin, c0, nch), g1 in zip(self.lane_groups, self.g1_lanes):
+                    ops.conv2d_wgrad(xin, 8, dy, cout, k, k, s, p, self.gpack, splits=wg.splits, workspace=self.ws, bf16_mfma=self.bf16)
+                    ops.conv2d_unpack_weight(self.gpack, g1)
+                    ops.copy_channels(gw, c0, g1, 0, nch)
+            elif wg.kind == "fused":
                 # slabs summed inside the layout converter: no packed intermediate, no reduce launch (10 launches and ~0.3 GB less per backward)
-                ops.conv2d_wgrad_oihw(x, cin[name], dy, cout, k, k, s, p, g[name + "_weight"], splits=self.wgrad_splits[name], workspace=self.ws,
-                                      bf16_mfma=self.bf16)
+                ops.conv2d_wgrad_oihw(x, cin, dy, cout, k, k, s, p, gw, splits=wg.splits, workspace=self.ws, bf16_mfma=self.bf16)
             else:
-                ops.conv2d_wgrad(x, cin[name], dy, cout, k, k, s, p, self.gpack, splits=self.wgrad_splits[name], workspace=self.ws,
-                                 bf16_mfma=self.bf16)
-                ops.conv2d_unpack_weight(self.gpack, g[name + "_weight"])
+                ops.conv2d_wgrad(x, cin, dy, cout, k, k, s, p, self.gpack, splits=wg.splits, workspace=self.ws, bf16_mfma=self.bf16)
+                ops.conv2d_unpack_weight(self.gpack, gw)
             self._bucket_ready(name + "_weight")
-            if prev[name]:
-                if name in self.wino_dgrad:
-                    # dX of a 3x3 / stride-1 / pad-1 convolution = the same kind of convolution of dZ with the flipped, transposed
-                    # kernel: Winograd like the forward (no bias, no activation)
-                    wm = self.net.wino_m[name]
-                    wtiles = dy.shape[0] * (-(-dy.shape[1] // wm)) * (-(-dy.shape[2] // wm))
-                    ops.conv2d_fwd_winograd(dy, cout, self.wino_dgrad[name], None, cin[name], slope=1.0,
-                                            tile=4 if (cin[name] % 128 == 0 and wtiles >= 1024) else 3,
-                                            out=self.dacts[prev[name]], workspace=self.wino_ws, m=wm)
-                elif name in self.wino5_dgrad:
-                    ops.conv2d_dgrad_winograd5x5s2(dy, cout, self.wino5_dgrad[name], self.dacts[prev[name]], cin[name], workspace=self.wino_ws)
-                else:
-                    # bf16: operand-traffic bound, so the widest tile the channel count allows (dX channels are the GEMM's N)
-                    dg_tile = self._bf16_gemm_tile(dy.shape[0] * dy.shape[1] * dy.shape[2], ops.pad64(cin[name])) if self.bf16 else 3
-                    if (dg_tile != 3 and s == 1 and k == 3 and dy.shape[1] * dy.shape[2] >= 1200 and os.environ.get("DIM_BF16_HALO", "1") != "0"):
-                        dg_tile = 7   # stride-1 input gradient of a large map: LDS-halo kernel
-                    if self.bf16 and BF16_PATCH and k in (3, 5) and dy.shape[1] * dy.shape[2] >= 1200:
-                        dg_tile = 9   # stride-1 patch kernel: the gradient itself (stride 1) or its four phase convolutions (stride 2)
-                    ksp = self._dgrad_splits(dg_tile, dy.shape[0] * dy.shape[1] * dy.shape[2], ops.pad64(cin[name]), cout) if self.bf16 else 1
-                    if FOLD_LRELU and dg_tile == 9 and ksp == 1 and ((k == 5 and s == 2) or (k == 3 and s == 1)) and cin[name] % 64 == 0 and not (
-                            self.has_decoder and prev[name] in ("conv4_1", "conv5_1")):
-                        # every phase runs on the patch kernel and this is the only gradient that reaches the layer below: its
-                        # LeakyReLU' and bias gradient ride in the epilogue instead of a 12-bytes-per-element pass of their own
-                        # (flow_conv1, conv2, conv3, conv4: 80 % of the encoder's activation elements)
-                        ops.conv2d_dgrad_lrelu(dy, cout, self.dgrad_packed[name], self.dacts[prev[name]], msk.acts[prev[name]], cin[name], k, k, s, p,
-                                               g[prev[name] + "_bias"], workspace=self.fold_ws)
-                        dz_done.add(prev[name])
-                        continue
-                    ops.conv2d_dgrad(dy, cout, self.dgrad_packed[name], self.dacts[prev[name]], cin[name], k, k, s, p, accumulate=False,
-                                     tile=dg_tile, splits=ksp, workspace=self.ws if ksp > 1 else None)
+            if dg.kind == "wino":
+                ops.conv2d_fwd_winograd(dy, cout, self.wino_dgrad[name], None, cin, slope=1.0, tile=dg.tile, out=self.dacts[prev],
+                                        workspace=self.wino_ws, m=dg.m)
+            elif dg.kind == "wino5":
+                ops.conv2d_dgrad_winograd5x5s2(dy, cout, self.wino5_dgrad[name], self.dacts[prev], cin, workspace=self.wino_ws)
+            elif dg.kind == "fold":
+                ops.conv2d_dgrad_lrelu(dy, cout, self.dgrad_packed[name], self.dacts[prev], msk.acts[prev], cin, k, k, s, p,
+                                       g[prev + "_bias"], workspace=self.fold_ws)
+            elif dg.kind == "gemm":
+                ops.conv2d_dgrad(dy, cout, self.dgrad_packed[name], self.dacts[prev], cin, k, k, s, p, accumulate=False,
+                                 tile=dg.tile, splits=dg.splits, workspace=self.ws if dg.splits > 1 else None)
         self._bucket_ready(None)
         return g
 
@@ -608,41 +631,13 @@ class MutableModule(object):
         """Deconvolution(k4,s2)+Crop(1,1) backward.  x: deconv input (N,h,w,stride>=x_cpad), dz: gradient w.r.t. the pre-activation
         output = channels [dz_coff, dz_coff+cout) of a concat-gradient buffer over the crop window (N,oh,ow,stride)."""
         g, w = self.g, self.w
-        N, h, wd, _ = x.shape
+        (_, h, wd, _), (sp, tile) = x.shape, self.plan.deconv[name]
         # weight gradient through the convolution view: conv'(input = dz, k4, s2, pad 1) with "output gradient" = x
-        # (bf16: deconv4's view is 544 workgroups of the 64-row kernel: three pixel splits fill the resident slots, 183 -> 151 us)
-        sp = 3 if (self.bf16 and N * h * wd >= 4096 and x_cpad % 128 != 0) else 1
-        ops.conv2d_wgrad_ex(dz, dz_coff, cout, x, 0, x_cpad, 4, 4, 2, 1, self.gpack, splits=sp, workspace=self.ws if sp > 1 else None,
-                            bf16_mfma=self.bf16)
+        ops.conv2d_wgrad_ex(dz, dz_coff, cout, x, 0, x_cpad, 4, 4, 2, 1, self.gpack, splits=sp, workspace=self.ws if sp > 1 else None, bf16_mfma=self.bf16)
         ops.conv2d_unpack_weight(self.gpack, g[name + "_weight"], CoutPad=x_cpad)
         ops.bias_grad(dz, cout, g[name + "_bias"], dz_coff=dz_coff, workspace=self.bias_ws)
         # data gradient: the same convolution applied to dz
-        ops.conv2d_fwd_ex(dz, dz_coff, cout, self.dgrad_packed[name], None, dx, 0, x_cpad, 4, 4, 2, 1, Ho=h, Wo=wd, accumulate=False,
-                          tile=self._bf16_gemm_tile(N * h * wd, x_cpad) if self.bf16 else 3)
-
-    def _dgrad_splits(self, tile, rows, cols, cout):
-        """split-K count of a bf16 input gradient on the gathered-tap kernel: the small maps (conv5 .. conv6_1: 1280-4800 rows per
-        launch) make 144-600 tiles of 64 x 64 for the 1280 workgroups that fit the chip (5 per CU), and each walks K = 4608-9216 alone.
-        The K range is cut so that the grid fills the slots; every phase of a strided gradient must keep >= splits chunks of 32 dy
-        channels (its 1-tap phase has cout / 32).  DIM_BF16_DGRAD_SPLITK=0: off."""
-        if tile != 3 or os.environ.get("DIM_BF16_DGRAD_SPLITK", "1") == "0":
-            return 1
-        tiles = -(-rows // 64) * (cols // 64)
-        for sp in (8, 4, 2):
-            if sp * tiles <= 5 * self.n_cu and (cout // 32) % sp == 0:
-                return sp
-        return 1
-
-    @staticmethod
-    def _bf16_gemm_tile(rows, cols):
-        """workgroup tile of a bf16 input-gradient GEMM with `rows` output pixels (per launch: a stride-2 gradient runs one launch per
-        input phase, each with as many rows as dY has pixels) x `cols` channels: the wide tile only when it fills the chip -- conv6_1's
-        gradient is 10 x 8 tiles of 128 x 128 with K = 9216, 80 workgroups on 256 CUs (149 us); 64 x 64 tiles give 320.
-        DIM_BF16_SMALL_TILE=0: the wide tile wherever the channel count allows."""
-        t = bf16_tile(cols)
-        if t != 3 and os.environ.get("DIM_BF16_SMALL_TILE", "1") != "0" and -(-rows // 128) * (cols // 128) < 200:
-            return 3
-        return t
+        ops.conv2d_fwd_ex(dz, dz_coff, cout, self.dgrad_packed[name], None, dx, 0, x_cpad, 4, 4, 2, 1, Ho=h, Wo=wd, accumulate=False, tile=tile)
 
     def forward_backward(self, batch):
         out = self.forward(batch)

@@ -10,6 +10,7 @@ f32 MFMA, NHWC) -> pose head -> se3.  Weights are packed once into the kernels' 
   init_weights         :998-1124 -> deepIM_flownet.init_weights() (random init; the FlowNet
                                     checkpoint is an external download and is not available offline)
 """
+import collections
 import os
 
 import numpy as np
@@ -30,6 +31,19 @@ ENCODER = [
     ("conv6", 1024, 3, 2, 1),
     ("conv6_1", 1024, 3, 1, 1),
 ]
+
+LayerGeometry = collections.namedtuple("LayerGeometry", "name prev cin cout k s p h w ho wo")
+
+
+def encoder_geometry(H=480, W=640, lanes=8):
+    """ENCODER with everything its consumers derive from it, one immutable record per layer: the layer below (`prev`, None for
+    flow_conv1), the input channels as the device holds them (`cin`: `lanes` for the first layer), input map h x w, output map ho x wo"""
+    out, prev, h, w, c = [], None, H, W, lanes
+    for name, cout, k, s, p in ENCODER:
+        ho, wo = ops.conv_out_hw(h, w, k, k, s, p)
+        out.append(LayerGeometry(name, prev, c, cout, k, s, p, h, w, ho, wo))
+        prev, h, w, c = name, ho, wo, cout
+    return tuple(out)
 
 
 # Winograd output tile edge per 3x3 / stride-1 layer (4 where not listed; measured at B = 16: F(4x4) wins on all four, also on the
@@ -258,103 +272,73 @@ class FlowNetHip(object):
             self.packed["flow_conv1_masks"] = self.pack_conv(
                 torch.cat([w1[:, 8:], torch.zeros((w1.shape[0], 6) + tuple(w1.shape[2:]), device=d)], dim=1).contiguous())
             self.params["flow_conv1_weight"] = w1[:, :8].contiguous()
-        for name, cout, k, s, p in ENCODER:
-            self.packed[name] = self.pack_conv(self.params[name + "_weight"])
         self.packed["fc6"] = ops.fc_pack_weight(self.params["fc6_weight"], 1024, 8, 10)
-        self.wino, self.wino_m, self.wino5, self.wino3s2 = {}, {}, {}, {}
-        if winograd:
-            hh, ww, cc = self.H, self.W, 8
-            for name, cout, k, s, p in ENCODER:
-                # conv4, conv5: phase images + minimal filtering (81 plane GEMMs); the rule lives in C (dim_winograd3x3s2_use), shared with
-                # dim_refiner_create.  Inference only: the training executor keeps its forward on the direct kernel (wino_s2=False).
-                if wino_s2 and k == 3 and s == 2 and p == 1 and ops.lib().dim_winograd3x3s2_use(hh, ww, cc, cout):
-                    self.wino3s2[name] = ops.winograd3x3s2_pack_weight(self.params[name + "_weight"])
-                hh, ww = ops.conv_out_hw(hh, ww, k, k, s, p)
-                cc = cout
-            for name, cout, k, s, p in ENCODER:
-                if k == 5 and s == 2 and p == 2:  # conv2, conv3: four phase images through F(4x4,3x3), 36 GEMMs with K = 4 Cin
-                    self.wino5[name] = ops.winograd5x5s2_pack_weight(self.params[name + "_weight"])
-                if k == 3 and s == 1 and p == 1:
-                    # output tile edge: F(4x4,3x3) (4x fewer multiply-adds) by default
-                    self.wino_m[name] = int((wino_m or {}).get(name, WINO_M_DEFAULT.get(name, 4)))
-                    self.wino[name] = ops.winograd_pack_weight(self.params[name + "_weight"], m=self.wino_m[name])
         self.K = np.asarray(cfg.dataset.INTRINSIC_MATRIX, dtype=np.float32).reshape(3, 3)
         self.plane_means = np.asarray(cfg.network.PIXEL_MEANS, dtype=np.float32).reshape(3)[::-1].copy()
-        # tile / split-K plan per layer: (tile, splits); 0 = library heuristic
-        self.conv_plan = {"fc6": (3, 40)}
-        if self.bf16:
-            # operand-traffic bound: 128 x 128 tiles (8 waves) wherever Cout allows, no split-K except on the 8 x 10 / 15 x 20 maps
-            c = 8
-            h, w = self.H, self.W
-            for name, cout, k, s, p in ENCODER:
-                h, w = ops.conv_out_hw(h, w, k, k, s, p)
-                tiles = -(-batch_size * h * w // 128) * (cout // 128) if cout % 128 == 0 else 0
-                # split-K on the small maps: the 8-wave 128 x 128 kernel keeps 2 workgroups per CU = 512 resident slots, and a grid just
-                # over that pays a second, nearly empty round (the round-2 rule, ceil(512 / tiles) capped at 4, gave conv5 / conv5_1
-                # 608 workgroups).  tools/fwd_bf16_sweep.py at B = 16, splits: us incl. the slab sum -- conv5 3: 54, 4: 62; conv5_1 3: 52,
-                # 4: 59; conv6 3: 32, 4: 39, 6: 36; conv6_1 3: 50, 4: 61, 6: 49
-                self.conv_plan[name] = (bf16_tile(cout) if c != 8 else 3, 1 if (tiles == 0 or tiles >= 256) else max(1, min(3, 512 // tiles)))
-                # 3x3 / stride-1 layers on large maps: the LDS-halo kernel (conv_bf16_tiles.hip conv_bf16_halo_kernel, tile 7).  Measured at B = 16
-                # against the gathered-tap kernel: conv3_1 0.150 vs 0.161 ms, conv4_1 0.175 vs 0.177; the stride-2 layers lose (conv2
-                # 0.366 vs 0.256, conv3 0.286 vs 0.247, conv4 0.143 vs 0.102: their 45-53 KB patches + 41 KB of weight buffers leave
-                # one 4-wave workgroup per CU), so they stay where they were.  DIM_BF16_HALO=0: gathered-tap kernel everywhere; =2: every
-                # eligible layer on tile 7 (the A/B above)
-                halo = os.environ.get("DIM_BF16_HALO", "1")
-                if c % 32 == 0 and cout % 128 == 0 and h * w >= 1200 and ((halo == "1" and k == 3 and s == 1) or (halo == "2" and k in (3, 5))):
-                    self.conv_plan[name] = (7, 1)
-                if BF16_PATCH and c % 32 == 0 and cout % 128 == 0 and h * w >= 1200 and (
-                        (k == 3 and s == 1) or (s == 2 and k in BF16_PATCH_S2_KERNELS)):
-                    self.conv_plan[name] = (9, 1)   # patch kernel (conv_bf16_tiles.hip conv_bf16_patch_kernel): 3x3 / stride 1, 3x3 and 5x5 / stride 2
-                c = cout
-        if conv_plan:
-            self.conv_plan.update(conv_plan)
         B, H, W = batch_size, self.H, self.W
         self.X = torch.empty((B, H, W, 8), dtype=torch.float32, device=d)
         self.X2 = torch.empty((B, H, W, 8), dtype=torch.float32, device=d) if self.input_mode == 3 else None   # the mask lanes of the 10-channel input
+        self.geometry = encoder_geometry(H, W)
+        assert self.geometry[-1][-2:] == (8, 10) and self.geometry[-1].cout == 1024
+        # tile / split-K plan per layer: (tile, splits); 0 = library heuristic.  An entry of the `conv_plan` argument wins over every rule below
+        self.conv_plan = {"fc6": (3, 40)}
+        self.conv_plan.update(conv_plan or {})
+        self.wino, self.wino_m, self.wino5, self.wino3s2 = {}, {}, {}, {}
         self.acts = {}
-        h, w, c = H, W, 8
-        max_ws = 0
         self.layer_info = {}  # name -> dict(M, K, N, flops, tile, splits) for profiling / roofline accounting
-        for name, cout, k, s, p in ENCODER:
-            ho, wo = ops.conv_out_hw(h, w, k, k, s, p)
+        halo = os.environ.get("DIM_BF16_HALO", "1")
+        lib, max_ws = ops.lib(), 0
+        # the one pass over the layers: packed weights, Winograd kinds, launch plan, activations, accounting, workspace
+        for name, _, c, cout, k, s, p, h, w, ho, wo in self.geometry:
+            wgt = self.params[name + "_weight"]
+            self.packed[name] = self.pack_conv(wgt)
+            if winograd and (k, s, p) == (5, 2, 2):  # conv2, conv3: four phase images through F(4x4,3x3), 36 GEMMs with K = 4 Cin
+                self.wino5[name] = ops.winograd5x5s2_pack_weight(wgt)
+            if winograd and (k, s, p) == (3, 1, 1):
+                # output tile edge: F(4x4,3x3) (4x fewer multiply-adds) by default
+                self.wino_m[name] = int((wino_m or {}).get(name, WINO_M_DEFAULT.get(name, 4)))
+                self.wino[name] = ops.winograd_pack_weight(wgt, m=self.wino_m[name])
+            # conv4, conv5: phase images + minimal filtering (81 plane GEMMs); the rule lives in C (dim_winograd3x3s2_use), shared with
+            # dim_refiner_create.  Inference only: the training executor keeps its forward on the direct kernel (wino_s2=False).
+            if winograd and wino_s2 and (k, s, p) == (3, 2, 1) and lib.dim_winograd3x3s2_use(h, w, c, cout):
+                self.wino3s2[name] = ops.winograd3x3s2_pack_weight(wgt)
             self.acts[name] = torch.empty((B, ho, wo, cout), dtype=torch.float32, device=d)
-            nchunks = -(-k * k // 4) if c == 8 else k * k * (c // 32)
-            tile, splits = self.conv_plan.get(name, ops.conv_auto_plan(B * ho * wo, cout, nchunks, cin=c))
-            if name == "flow_conv1" and name not in (conv_plan or {}) and os.environ.get("DIM_CONV1_HALO", "1") != "0":
+            if name in self.conv_plan:
+                tile, splits = self.conv_plan[name]
+            elif name == "flow_conv1" and os.environ.get("DIM_CONV1_HALO", "1") != "0":
                 # LDS-halo first-layer kernel (conv_first.hip conv1_halo_kernel, on the bf16 pipe conv1_halo_bf16_kernel: 0.26 -> ~0.12 ms at
                 # B = 16, the layer's HBM bytes once); DIM_CONV1_HALO=0: the gathered-tap kernel
                 tile, splits = 6, 1
+            elif self.bf16:
+                tile, splits = self._bf16_plan(B, c, cout, k, s, ho, wo, halo)
+            else:
+                tile, splits = ops.conv_auto_plan(B * ho * wo, cout, -(-k * k // 4) if c == 8 else k * k * (c // 32), cin=c)
             self.conv_plan[name] = (tile, splits)
             self.layer_info[name] = dict(M=B * ho * wo, K=c * k * k, N=cout, flops=2 * B * ho * wo * cout * c * k * k, tile=tile,
                                          splits=splits, cin=c, min_bytes=4 * (B * h * w * c + cout * c * k * k + B * ho * wo * cout))
             if splits != 1:
-                max_ws = max(max_ws, ops.lib().dim_conv2d_workspace_floats(B, h, w, c, cout, k, k, s, p, splits))
+                max_ws = max(max_ws, lib.dim_conv2d_workspace_floats(B, h, w, c, cout, k, k, s, p, splits))
+            # Winograd: GEMM rows = tiles; 128x128 workgroup tiles once there are enough of them, 64x64 for the small maps
+            tiles, xy = B * (-(-ho // 4)) * (-(-wo // 4)), (B * h * w * c, B * ho * wo * cout)
             if name in self.wino:
-                # GEMM rows = tiles; 128x128 workgroup tiles once there are enough of them, 64x64 for the small maps
                 m = self.wino_m[name]
                 tiles = B * (-(-h // m)) * (-(-w // m))
                 wt = (wino_tile or {}).get(name, self._wino_tile(cout, tiles))
-                self.layer_info[name].update(self._wino_info(m, 1, wt, tiles, c, cout, B * h * w * c, B * ho * wo * cout))
-                max_ws = max(max_ws, ops.lib().dim_winograd_workspace_floats(B, h, w, c, cout, m))
+                self.layer_info[name].update(self._wino_info(m, 1, wt, tiles, c, cout, *xy))
+                max_ws = max(max_ws, lib.dim_winograd_workspace_floats(B, h, w, c, cout, m))
             if name in self.wino5:
-                tiles = B * (-(-ho // 4)) * (-(-wo // 4))
                 wt = (wino_tile or {}).get(name, self._wino_tile(cout, tiles))
-                self.layer_info[name].update(self._wino_info(4, 2, wt, tiles, c, cout, B * h * w * c, B * ho * wo * cout))
-                max_ws = max(max_ws, ops.lib().dim_winograd5x5s2_workspace_floats(B, h, w, c, cout))
+                self.layer_info[name].update(self._wino_info(4, 2, wt, tiles, c, cout, *xy))
+                max_ws = max(max_ws, lib.dim_winograd5x5s2_workspace_floats(B, h, w, c, cout))
             if name in self.wino3s2:
-                tiles = B * (-(-ho // 4)) * (-(-wo // 4))
                 wt = (wino_tile or {}).get(name, self._wino_tile(cout, tiles, 81))
-                info = self._wino_info(4, 1, wt, tiles, c, cout, B * h * w * c, B * ho * wo * cout, planes=81)
-                info.update(wino_in_kernel="dim::wino_s2_input_kernel", wino_out_kernel="dim::wino_s2_output_kernel")
-                self.layer_info[name].update(info)
-                max_ws = max(max_ws, ops.lib().dim_winograd3x3s2_workspace_floats(B, h, w, c, cout))
-            h, w, c = ho, wo, cout
-        assert (h, w, c) == (8, 10, 1024)
+                self.layer_info[name].update(self._wino_info(4, 1, wt, tiles, c, cout, *xy, planes=81),
+                                             wino_in_kernel="dim::wino_s2_input_kernel", wino_out_kernel="dim::wino_s2_output_kernel")
+                max_ws = max(max_ws, lib.dim_winograd3x3s2_workspace_floats(B, h, w, c, cout))
         tile, splits = self.conv_plan["fc6"]
         self.layer_info["fc6"] = dict(M=B, K=81920, N=256, flops=2 * B * 81920 * 256, tile=tile, splits=splits, cin=1024,
                                       min_bytes=4 * (B * 81920 + 256 * 81920 + B * 256))
-        max_ws = max(max_ws, ops.lib().dim_conv2d_workspace_floats(B, 8, 10, 1024, 256, 8, 10, 1, 0, splits),
-                     ops.lib().dim_fc_fwd_workspace_floats(1024, 8, 10, 256))
+        max_ws = max(max_ws, lib.dim_conv2d_workspace_floats(B, 8, 10, 1024, 256, 8, 10, 1, 0, splits), lib.dim_fc_fwd_workspace_floats(1024, 8, 10, 256))
         self.workspace = torch.empty((max(max_ws, 4),), dtype=torch.float32, device=d)
         # ---- decoder + flow / mask heads (only in the graph when not FAST_TEST, reference :840-954)
         self.has_decoder = "deconv5_weight" in self.params
@@ -382,6 +366,28 @@ class FlowNetHip(object):
         self.bbox_ren = torch.empty((B, 4), dtype=torch.int32, device=d)
         self.status = torch.zeros((B,), dtype=torch.int32, device=d)
         torch.cuda.synchronize(d)
+
+    @staticmethod
+    def _bf16_plan(B, c, cout, k, s, ho, wo, halo):
+        """(tile, splits) of a bf16 layer with c input channels and an ho x wo output map.  Operand-traffic bound: 128 x 128 tiles (8 waves)
+        wherever Cout allows, no split-K except on the 8 x 10 / 15 x 20 maps.  `halo`: DIM_BF16_HALO"""
+        tiles = -(-B * ho * wo // 128) * (cout // 128) if cout % 128 == 0 else 0
+        # split-K on the small maps: the 8-wave 128 x 128 kernel keeps 2 workgroups per CU = 512 resident slots, and a grid just
+        # over that pays a second, nearly empty round (the round-2 rule, ceil(512 / tiles) capped at 4, gave conv5 / conv5_1
+        # 608 workgroups).  tools/fwd_bf16_sweep.py at B = 16, splits: us incl. the slab sum -- conv5 3: 54, 4: 62; conv5_1 3: 52,
+        # 4: 59; conv6 3: 32, 4: 39, 6: 36; conv6_1 3: 50, 4: 61, 6: 49
+        plan = (bf16_tile(cout) if c != 8 else 3, 1 if (tiles == 0 or tiles >= 256) else max(1, min(3, 512 // tiles)))
+        big = c % 32 == 0 and cout % 128 == 0 and ho * wo >= 1200
+        # 3x3 / stride-1 layers on large maps: the LDS-halo kernel (conv_bf16_tiles.hip conv_bf16_halo_kernel, tile 7).  Measured at B = 16
+        # against the gathered-tap kernel: conv3_1 0.150 vs 0.161 ms, conv4_1 0.175 vs 0.177; the stride-2 layers lose (conv2
+        # 0.366 vs 0.256, conv3 0.286 vs 0.247, conv4 0.143 vs 0.102: their 45-53 KB patches + 41 KB of weight buffers leave
+        # one 4-wave workgroup per CU), so they stay where they were.  DIM_BF16_HALO=0: gathered-tap kernel everywhere; =2: every
+        # eligible layer on tile 7 (the A/B above)
+        if big and ((halo == "1" and k == 3 and s == 1) or (halo == "2" and k in (3, 5))):
+            plan = (7, 1)
+        if BF16_PATCH and big and ((k == 3 and s == 1) or (s == 2 and k in BF16_PATCH_S2_KERNELS)):
+            plan = (9, 1)   # patch kernel (conv_bf16_tiles.hip conv_bf16_patch_kernel): 3x3 / stride 1, 3x3 and 5x5 / stride 2
+        return plan
 
     def pack_conv(self, w_oihw):
         """MXNet (Cout,Cin,kh,kw) -> the forward kernel's packed array (bf16 copy in bf16 mode)"""
@@ -443,24 +449,26 @@ class FlowNetHip(object):
                                       self.zoom_factor, self.plane_means, 3, X=self.X2)
         return self.X
 
+    def _run_winograd(self, name, cout, x, events=None, s2=True):
+        """the layer's Winograd forward into self.acts[name] if it has one (s2=False: the 3x3 / stride-2 form does not count), else None"""
+        if name in self.wino:
+            fn, wp, kw = ops.conv2d_fwd_winograd, self.wino[name], {"m": self.wino_m[name]}
+        elif name in self.wino5:
+            fn, wp, kw = ops.conv2d_fwd_winograd5x5s2, self.wino5[name], {}
+        elif s2 and name in self.wino3s2:
+            fn, wp, kw = ops.conv2d_fwd_winograd3x3s2, self.wino3s2[name], {}
+        else:
+            return None
+        return fn(x, x.shape[-1], wp, self.params[name + "_bias"], cout, slope=0.1, tile=self.layer_info[name]["wino_tile"], out=self.acts[name],
+                  workspace=self.workspace, events=None if events is None else events.setdefault(name, []), **kw)
+
     def encoder(self, X=None, events=None):
         """events: optional dict layer-name -> list of (tag, start, end) HIP-event triples (see ops.conv2d_fwd)."""
         x = self.X if X is None else X
-        for name, cout, k, s, p in ENCODER:
-            if name in self.wino:
-                x = ops.conv2d_fwd_winograd(x, x.shape[-1], self.wino[name], self.params[name + "_bias"], cout, slope=0.1,
-                                            tile=self.layer_info[name]["wino_tile"], out=self.acts[name], workspace=self.workspace,
-                                            events=None if events is None else events.setdefault(name, []), m=self.wino_m[name])
-                continue
-            if name in self.wino5:
-                x = ops.conv2d_fwd_winograd5x5s2(x, x.shape[-1], self.wino5[name], self.params[name + "_bias"], cout, slope=0.1,
-                                                 tile=self.layer_info[name]["wino_tile"], out=self.acts[name], workspace=self.workspace,
-                                                 events=None if events is None else events.setdefault(name, []))
-                continue
-            if name in self.wino3s2:
-                x = ops.conv2d_fwd_winograd3x3s2(x, x.shape[-1], self.wino3s2[name], self.params[name + "_bias"], cout, slope=0.1,
-                                                 tile=self.layer_info[name]["wino_tile"], out=self.acts[name], workspace=self.workspace,
-                                                 events=None if events is None else events.setdefault(name, []))
+        for name, _, _, cout, k, s, p, *_ in self.geometry:
+            y = self._run_winograd(name, cout, x, events)
+            if y is not None:
+                x = y
                 continue
             tile, splits = self.conv_plan[name]
             first10 = name == "flow_conv1" and self.input_mode == 3
@@ -479,16 +487,13 @@ class FlowNetHip(object):
         """Pick (tile, splits) per layer by timing the candidates on this GPU (HIP events on the launch stream).
         Only speed changes: split-K alters the f32 summation order (|delta| ~1e-6 relative), nothing else."""
         x = self.X
-        layers = [(n, co, k, k, s, p, self.params[n + "_bias"], self.acts[n]) for n, co, k, s, p in ENCODER]
-        for name, cout, kh, kw, s, p, bias, out in layers:
-            N, H, W, C = x.shape
-            if name in self.wino:  # Winograd layers have no (tile, splits) plan of the direct kernel: just produce their output
-                x = ops.conv2d_fwd_winograd(x, C, self.wino[name], bias, cout, slope=0.1, tile=self.layer_info[name]["wino_tile"], out=out,
-                                            workspace=self.workspace, m=self.wino_m[name])
-                continue
-            if name in self.wino5:
-                x = ops.conv2d_fwd_winograd5x5s2(x, C, self.wino5[name], bias, cout, slope=0.1, tile=self.layer_info[name]["wino_tile"],
-                                                 out=out, workspace=self.workspace)
+        for name, _, C, cout, kh, s, p, H, W, *_ in self.geometry:
+            N, kw, bias, out = x.shape[0], kh, self.params[name + "_bias"], self.acts[name]
+            # Winograd layers have no (tile, splits) plan of the direct kernel: just produce their output.  The 3x3 / stride-2 form is
+            # not asked for: such a layer (wino_s2: conv4, conv5) is timed and left on the direct kernel here, as it always was
+            y = self._run_winograd(name, cout, x, s2=False)
+            if y is not None:
+                x = y
                 continue
             cands = [(t, sp) for t in tiles for sp in split_choices if not (t in (1, 4) and (cout % 128 or C == 8))]
             best = None
@@ -577,12 +582,7 @@ class FlowNetHip(object):
 
     def flops_per_forward(self):
         """algorithmic MACs*2 of encoder + head for this batch (SURVEY.md 8a layer table)."""
-        h, w, c, total = self.H, self.W, 8, 0
-        for name, cout, k, s, p in ENCODER:
-            h, w = ops.conv_out_hw(h, w, k, k, s, p)
-            total += h * w * cout * c * k * k
-            c = cout
-        total += 81920 * 256 + 256 * 256 + 256 * 7
+        total = sum(g.ho * g.wo * g.cout * g.cin * g.k * g.k for g in self.geometry) + 81920 * 256 + 256 * 256 + 256 * 7
         if self.has_decoder and not self.cfg.TEST.FAST_TEST and (self.cfg.network.PRED_MASK or self.cfg.network.PRED_FLOW):
             total += 1967511120   # decoder + flow / mask heads (SURVEY.md 8a layer table: 3.94 GFLOP per pair and forward)
         return 2 * total * self.B
