@@ -9,7 +9,8 @@
 //   conv_bf16_tiles.hip  bf16 LDS-halo kernel (tile 7) and bf16 patch kernel (tile 9)
 //   conv_pack.hip        every weight packer of the direct / dgrad / deconvolution / small-Cout / fc layers, f32 <-> bf16 converters
 //   heads.hip            small-Cout convolution, tiny deconvolution, 16x upsampling, pose head (own arguments, no ConvArgs, no tile)
-//   winograd.hip         Winograd transforms, weight packers and entry points (uses common.h only; GEMMs in wino_gemm*.hip)
+//   winograd.hip         Winograd transforms, weight packers and entry points (GEMMs in wino_gemm*.hip); wino_s2.hip: 3x3 / stride 2
+//   wino_driver.h        their shared host side: slice geometry (workspace sizes, the 2^32 rule) and the loop over the slices of a batch
 #pragma once
 #include <cstdlib>
 #include <type_traits>

@@ -16,7 +16,7 @@
 // tools/wino_s2_proto.py is the same algorithm in numpy: exact in f64, 1.4e-6 of max|y| in f32 on a conv4-shaped layer (direct f32: 3e-7).
 #include <cstdlib>
 
-#include "common.h"
+#include "wino_driver.h"
 
 namespace dim {
 
@@ -221,12 +221,6 @@ __global__ void wino_s2_pack_weight_kernel(const float* __restrict__ w, float* _
 
 using namespace dim;
 
-// one slice of the batch: T * 81 * max(Cin, Cout) floats must stay below 2^32 bytes (32-bit buffer offsets in the GEMM)
-static long s2_slice_images(long tiles_per_image, long K, long Cout) {
-  const long per_image = tiles_per_image * kPlanes * (K > Cout ? K : Cout) * 4;
-  return per_image < (1L << 32) ? ((1L << 32) - 1) / per_image : 0;
-}
-
 extern "C" {
 
 long dim_winograd3x3s2_packed_weight_floats(int Cout, int Cin) { return wino_packed_with_split((long)kPlanes * Cout * Cin); }
@@ -244,11 +238,7 @@ int dim_winograd3x3s2_use(int H, int W, int Cin, int Cout) {
 }
 
 long dim_winograd3x3s2_workspace_floats(int N, int H, int W, int Cin, int Cout) {
-  const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
-  const long per = (long)((Ho + 3) / 4) * ((Wo + 3) / 4);
-  const long ns = s2_slice_images(per, Cin, Cout);
-  const long n = ns <= 0 ? N : (ns < N ? ns : N);
-  return kPlanes * n * per * ((long)Cin + Cout);
+  return wino_geom(N, (H - 1) / 2 + 1, (W - 1) / 2 + 1, kPlanes, 4, Cin, Cout).workspace_floats();
 }
 
 int dim_winograd3x3s2_pack_weight(const float* w_oihw, float* w_packed, int Cout, int Cin, void* stream) {
@@ -276,52 +266,24 @@ int dim_conv2d_fwd_winograd3x3s2(const float* x, const float* w_packed, const fl
               "channel strides / offsets must be even and cover the channels");
   DIM_REQUIRE((reinterpret_cast<uintptr_t>(x) & 7) == 0 && (reinterpret_cast<uintptr_t>(y) & 7) == 0, "x and y must be 8-byte aligned");
   const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
-  const int th = (Ho + 3) / 4, tw = (Wo + 3) / 4;
-  const long ns = s2_slice_images((long)th * tw, Cin, Cout);
-  DIM_REQUIRE(ns > 0, "one image alone exceeds the 32-bit offsets of the plane GEMMs");
-  int n_slice = ns < N ? (int)ns : N;
-  if (const char* e = getenv("DIM_WINO_MAX_SLICE")) {  // test hook: force the slicing path at sizes a unit test can check
-    const int cap = atoi(e);
-    if (cap > 0 && cap < n_slice) n_slice = cap;
-  }
+  const WinoGeom g = wino_geom(N, Ho, Wo, kPlanes, 4, Cin, Cout);
+  const int th = g.th, tw = g.tw;
   hipStream_t st = as_stream(stream);
   const FastDiv dtw = make_fastdiv((unsigned)tw), dth = make_fastdiv((unsigned)th);
-  for (int n0 = 0; n0 < N; n0 += n_slice) {
-    const int n = N - n0 < n_slice ? N - n0 : n_slice;
-    const long T = (long)n * th * tw;
-    float* V = workspace;
-    float* M = workspace + kPlanes * T * Cin;
-    const float* xs = x + (long)n0 * H * W * in_cstride;
-    float* ys = y + (long)n0 * Ho * Wo * out_cstride;
-    void** ev = n0 == 0 ? events4 : nullptr;
-#define DIM_S2_EVENT(I)                                                                    \
-  if (ev && ev[I]) {                                                                       \
-    hipError_t e = hipEventRecord(reinterpret_cast<hipEvent_t>(ev[I]), st);                \
-    if (e != hipSuccess) return set_err(DIM_ERR_LAUNCH, "hipEventRecord: %s", hipGetErrorString(e)); \
-  }
-    int gt = tile;
-    if (gt == 0) gt = dim_winograd_gemm_tile_planes(Cout, T, kPlanes);
-    WGemmArgs plan;
-    int rc = wino_gemm_plan(&plan, V, w_packed, M, (int)T, Cin, Cout, kPlanes, gt);
-    if (rc != DIM_OK) return rc;
-    DIM_S2_EVENT(0)
+  auto gemm_tile = [&](long T) { return tile ? tile : dim_winograd_gemm_tile_planes(Cout, T, kPlanes); };
+  auto input = [&](int n0, int n, long T, const WGemmArgs& plan, float* V) {
     const unsigned nblk = (unsigned)((T * (Cin / kVec) + 255) / 256);
-    hipLaunchKernelGGL(wino_s2_input_kernel, dim3(nblk + plan.G - 1), dim3(256), 0, st, xs, V, n, H, W, Cin, in_cstride, th, tw,
-                       make_fastdiv((unsigned)(Cin / kVec)), dtw, dth, nblk, plan);
-    rc = check_launch("winograd3x3s2_input");
-    if (rc != DIM_OK) return rc;
-    DIM_S2_EVENT(1)
-    rc = wino_gemm_run(plan, true, st);
-    if (rc != DIM_OK) return rc;
-    DIM_S2_EVENT(2)
-    hipLaunchKernelGGL(wino_s2_output_kernel, dim3((unsigned)((T * (Cout / kVec) + 255) / 256)), dim3(256), 0, st, M, bias, ys, n, Ho, Wo, Cout,
-                       out_cstride, out_coff, th, tw, slope, make_fastdiv((unsigned)(Cout / kVec)), dtw, dth);
-    rc = check_launch("winograd3x3s2_output");
-    if (rc != DIM_OK) return rc;
-    DIM_S2_EVENT(3)
-#undef DIM_S2_EVENT
-  }
-  return DIM_OK;
+    hipLaunchKernelGGL(wino_s2_input_kernel, dim3(nblk + plan.G - 1), dim3(256), 0, st, x + (long)n0 * H * W * in_cstride, V, n, H, W, Cin,
+                       in_cstride, th, tw, make_fastdiv((unsigned)(Cin / kVec)), dtw, dth, nblk, plan);
+    return check_launch("winograd3x3s2_input");
+  };
+  auto output = [&](int n0, int n, long T, const float* M) {
+    hipLaunchKernelGGL(wino_s2_output_kernel, dim3((unsigned)((T * (Cout / kVec) + 255) / 256)), dim3(256), 0, st, M, bias,
+                       y + (long)n0 * Ho * Wo * out_cstride, n, Ho, Wo, Cout, out_cstride, out_coff, th, tw, slope,
+                       make_fastdiv((unsigned)(Cout / kVec)), dtw, dth);
+    return check_launch("winograd3x3s2_output");
+  };
+  return wino_run_slices(g, w_packed, workspace, gemm_tile, /*skip5=*/0, /*zeroed=*/true, events4, st, input, output);
 }
 
 }  // extern "C"

@@ -3,9 +3,7 @@
 //   V = B^T d B  (input tiles 4x4, stride 2)  ->  16 independent GEMMs  M_k = V_k (T x Cin) * U_k (Cin x Cout)  ->  Y = A^T M A
 // 2.25x fewer multiply-adds than the direct form; the GEMMs run as ONE persistent stream-K launch (wino_gemm.hip).  Transforms are exact in the sense of using only +,- on the data (B, A have entries
 // 0, +-1); the weight transform G (entries 1, 1/2) is applied once at pack time.  f32 throughout.
-#include <cstdlib>
-
-#include "common.h"
+#include "wino_driver.h"
 
 namespace dim {
 
@@ -495,18 +493,8 @@ extern "C" {
 
 long dim_winograd_packed_weight_floats(int Cout, int Cin, int m) { return wino_packed_with_split((long)(m + 2) * (m + 2) * Cout * Cin); }
 
-// images per slice: tiles * planes * max(K, Cout) floats of one slice stay below 2^32 bytes (32-bit buffer offsets in the plane GEMMs)
-static long wino_slice_images(long tiles_per_image, int planes, long K, long Cout) {
-  const long per_image = tiles_per_image * planes * (K > Cout ? K : Cout) * 4;
-  return per_image < (1L << 32) ? ((1L << 32) - 1) / per_image : 0;
-}
-
 long dim_winograd_workspace_floats(int N, int H, int W, int Cin, int Cout, int m) {
-  if (m != 2 && m != 4) return 0;
-  const long per = (long)((H + m - 1) / m) * ((W + m - 1) / m);
-  const long ns = wino_slice_images(per, (m + 2) * (m + 2), Cin, Cout);
-  long T = (N < ns || ns == 0 ? (long)N : ns) * per;
-  return (long)(m + 2) * (m + 2) * T * ((long)Cin + Cout);
+  return m == 2 || m == 4 ? wino_geom(N, H, W, (m + 2) * (m + 2), m, Cin, Cout).workspace_floats() : 0;
 }
 
 int dim_winograd_pack_weight(const float* w_oihw, float* w_packed, int Cout, int Cin, int m, void* stream) {
@@ -537,62 +525,10 @@ int dim_winograd_dgrad_pack_weight(const float* w_oihw, float* w_packed, int Cou
   return rc != DIM_OK ? rc : wino_split_weights(w_packed, (long)(m + 2) * (m + 2) * (Cout / 32), Cin, as_stream(stream));
 }
 
-// one slice of the batch: T * planes * max(K, Cout) floats must stay below 2^32 bytes (32-bit buffer offsets in the GEMM)
-static int winograd_slice(const float* x, const float* w_packed, const float* bias, float* y, float* workspace, int N, int H, int W, int Cin,
-                          int in_cstride, int Cout, int out_cstride, int out_coff, float slope, int tile, int m, int S, void** events4,
-                          void* stream) {
-  const int Ho = S == 1 ? H : (H + 1) / 2, Wo = S == 1 ? W : (W + 1) / 2;  // 5x5 / s2 / p2: floor((H - 1) / 2) + 1
-  const int CT = Cin * S * S;                                                  // contraction length of the GEMMs
-  const int th = (Ho + m - 1) / m, tw = (Wo + m - 1) / m;
-  const int nk = (m + 2) * (m + 2);
-  const long T = (long)N * th * tw;
-  float* V = workspace;
-  float* M = workspace + nk * T * CT;
-  hipStream_t st = as_stream(stream);
-  const FastDiv dtw = make_fastdiv((unsigned)tw), dth = make_fastdiv((unsigned)th);
-#define DIM_WINO_EVENT(I)                                                                  \
-  if (events4 && events4[I]) {                                                             \
-    hipError_t e = hipEventRecord(reinterpret_cast<hipEvent_t>(events4[I]), st);           \
-    if (e != hipSuccess) return set_err(DIM_ERR_LAUNCH, "hipEventRecord: %s", hipGetErrorString(e)); \
-  }
-  if (tile == 0) tile = (Cout % 128 == 0 && T >= 1024) ? 4 : 3;
-  WGemmArgs plan;
-  int rc = wino_gemm_plan(&plan, V, w_packed, M, (int)T, CT, Cout, nk, tile, S == 2);
-  if (rc != DIM_OK) return rc;
-  DIM_WINO_EVENT(0)
-  const unsigned nblk = (unsigned)ceil_div(T * (CT / kWino4Vec), 256);
-  if (m == 2)
-    hipLaunchKernelGGL(wino_input_kernel, dim3(ceil_div(T * (Cin / 4), 256)), dim3(256), 0, st, x, V, N, H, W, Cin, in_cstride, th, tw,
-                       make_fastdiv((unsigned)(Cin / 4)), dtw, dth);
-  else if (S == 1)  // + G - 1 spare blocks that zero the M tiles shared by two GEMM workgroups
-    hipLaunchKernelGGL((wino4_input_kernel<kWino4Vec, 1>), dim3(nblk + plan.G - 1), dim3(256), 0, st, x, V, N, H, W, Cin, in_cstride, th, tw,
-                       make_fastdiv((unsigned)(CT / kWino4Vec)), dtw, dth, nblk, plan);
-  else
-    hipLaunchKernelGGL((wino4_input_kernel<kWino4Vec, 2, true>), dim3(nblk + plan.G - 1), dim3(256), 0, st, x, V, N, H, W, Cin, in_cstride, th, tw,
-                       make_fastdiv((unsigned)(CT / kWino4Vec)), dtw, dth, nblk, plan);
-  rc = check_launch("winograd_input");
-  if (rc != DIM_OK) return rc;
-  DIM_WINO_EVENT(1)
-  rc = wino_gemm_run(plan, m == 4, st);
-  if (rc != DIM_OK) return rc;
-  DIM_WINO_EVENT(2)
-  if (m == 2)
-    hipLaunchKernelGGL(wino_output_kernel, dim3(ceil_div(T * (Cout / 4), 256)), dim3(256), 0, st, M, bias, y, N, Ho, Wo, Cout, out_cstride,
-                       out_coff, th, tw, slope, make_fastdiv((unsigned)(Cout / 4)), dtw, dth);
-  else
-    hipLaunchKernelGGL((wino4_output_kernel<kWino4Vec, 1>), dim3(ceil_div(T * (Cout / kWino4Vec), 256)), dim3(256), 0, st, M, bias, y, N, Ho, Wo,
-                       Cout, out_cstride, out_coff, th, tw, slope, make_fastdiv((unsigned)(Cout / kWino4Vec)), dtw, dth);
-  rc = check_launch("winograd_output");
-  DIM_WINO_EVENT(3)
-#undef DIM_WINO_EVENT
-  return rc;
-}
-
 // S = 1: 3x3 / stride 1 / pad 1 with output tile m; S = 2: 5x5 / stride 2 / pad 2 through its four phase images (m = 4).
-// Large batches run as several slices of whole images through the same workspace (stream order keeps them apart).
-static int winograd_impl(const float* x, const float* w_packed, const float* bias, float* y, float* workspace, int N, int H, int W, int Cin,
-                         int in_cstride, int Cout, int out_cstride, int out_coff, float slope, int tile, int m, int S, void** events4,
-                         void* stream) {
+static int winograd_fwd(const float* x, const float* w_packed, const float* bias, float* y, float* workspace, int N, int H, int W, int Cin,
+                        int in_cstride, int Cout, int out_cstride, int out_coff, float slope, int tile, int m, int S, void** events4,
+                        void* stream) {
   if (N == 0) return DIM_OK;
   DIM_REQUIRE(x && w_packed && y && workspace, "null pointer");
   DIM_REQUIRE(m == 2 || m == 4, "output tile m must be 2 or 4");
@@ -601,37 +537,50 @@ static int winograd_impl(const float* x, const float* w_packed, const float* bia
   if (out_cstride == 0) out_cstride = Cout;
   DIM_REQUIRE(in_cstride >= Cin && in_cstride % 4 == 0 && out_cstride >= out_coff + Cout && out_cstride % 4 == 0 && out_coff % 4 == 0,
               "channel strides / offsets must be multiples of 4 and cover the channels");
-  const int Ho = S == 1 ? H : (H + 1) / 2, Wo = S == 1 ? W : (W + 1) / 2;
-  const long ns = wino_slice_images((long)((Ho + m - 1) / m) * ((Wo + m - 1) / m), (m + 2) * (m + 2), (long)Cin * S * S, Cout);
-  DIM_REQUIRE(ns > 0, "one image alone exceeds the 32-bit offsets of the plane GEMMs");
-  int n_slice = ns < N ? (int)ns : N;
-  if (const char* e = getenv("DIM_WINO_MAX_SLICE")) {  // test hook: force the slicing path at sizes a unit test can check
-    const int cap = atoi(e);
-    if (cap > 0 && cap < n_slice) n_slice = cap;
-  }
-  for (int n0 = 0; n0 < N; n0 += n_slice) {
-    const int n = N - n0 < n_slice ? N - n0 : n_slice;
-    int rc = winograd_slice(x + (long)n0 * H * W * in_cstride, w_packed, bias, y + (long)n0 * Ho * Wo * out_cstride, workspace, n, H, W, Cin,
-                            in_cstride, Cout, out_cstride, out_coff, slope, tile, m, S, n0 == 0 ? events4 : nullptr, stream);
-    if (rc != DIM_OK) return rc;
-  }
-  return DIM_OK;
+  const int Ho = S == 1 ? H : (H + 1) / 2, Wo = S == 1 ? W : (W + 1) / 2;  // 5x5 / s2 / p2: floor((H - 1) / 2) + 1
+  const WinoGeom g = wino_geom(N, Ho, Wo, (m + 2) * (m + 2), m, Cin * S * S, Cout);
+  const int th = g.th, tw = g.tw, CT = g.K;
+  hipStream_t st = as_stream(stream);
+  const FastDiv dtw = make_fastdiv((unsigned)tw), dth = make_fastdiv((unsigned)th);
+  auto gemm_tile = [&](long T) { return tile ? tile : (Cout % 128 == 0 && T >= 1024) ? 4 : 3; };
+  auto input = [&](int n0, int n, long T, const WGemmArgs& plan, float* V) {
+    const float* xs = x + (long)n0 * H * W * in_cstride;
+    const unsigned nblk = (unsigned)ceil_div(T * (CT / kWino4Vec), 256);
+    if (m == 2)
+      hipLaunchKernelGGL(wino_input_kernel, dim3(ceil_div(T * (Cin / 4), 256)), dim3(256), 0, st, xs, V, n, H, W, Cin, in_cstride, th, tw,
+                         make_fastdiv((unsigned)(Cin / 4)), dtw, dth);
+    else if (S == 1)  // + G - 1 spare blocks that zero the M tiles shared by two GEMM workgroups
+      hipLaunchKernelGGL((wino4_input_kernel<kWino4Vec, 1>), dim3(nblk + plan.G - 1), dim3(256), 0, st, xs, V, n, H, W, Cin, in_cstride, th,
+                         tw, make_fastdiv((unsigned)(CT / kWino4Vec)), dtw, dth, nblk, plan);
+    else
+      hipLaunchKernelGGL((wino4_input_kernel<kWino4Vec, 2, true>), dim3(nblk + plan.G - 1), dim3(256), 0, st, xs, V, n, H, W, Cin, in_cstride,
+                         th, tw, make_fastdiv((unsigned)(CT / kWino4Vec)), dtw, dth, nblk, plan);
+    return check_launch("winograd_input");
+  };
+  auto output = [&](int n0, int n, long T, const float* M) {
+    float* ys = y + (long)n0 * Ho * Wo * out_cstride;
+    if (m == 2)
+      hipLaunchKernelGGL(wino_output_kernel, dim3(ceil_div(T * (Cout / 4), 256)), dim3(256), 0, st, M, bias, ys, n, Ho, Wo, Cout, out_cstride,
+                         out_coff, th, tw, slope, make_fastdiv((unsigned)(Cout / 4)), dtw, dth);
+    else
+      hipLaunchKernelGGL((wino4_output_kernel<kWino4Vec, 1>), dim3(ceil_div(T * (Cout / kWino4Vec), 256)), dim3(256), 0, st, M, bias, ys, n, Ho,
+                         Wo, Cout, out_cstride, out_coff, th, tw, slope, make_fastdiv((unsigned)(Cout / kWino4Vec)), dtw, dth);
+    return check_launch("winograd_output");
+  };
+  return wino_run_slices(g, w_packed, workspace, gemm_tile, /*skip5=*/S == 2, /*zeroed=*/m == 4, events4, st, input, output);
 }
 
 int dim_conv2d_fwd_winograd(const float* x, const float* w_packed, const float* bias, float* y, float* workspace, int N, int H, int W,
                             int Cin, int in_cstride, int Cout, int out_cstride, int out_coff, float slope, int tile, int m,
                             void** events4, void* stream) {
-  return winograd_impl(x, w_packed, bias, y, workspace, N, H, W, Cin, in_cstride, Cout, out_cstride, out_coff, slope, tile, m, 1, events4,
+  return winograd_fwd(x, w_packed, bias, y, workspace, N, H, W, Cin, in_cstride, Cout, out_cstride, out_coff, slope, tile, m, 1, events4,
                        stream);
 }
 
 long dim_winograd5x5s2_packed_weight_floats(int Cout, int Cin) { return wino_packed_with_split(36L * Cout * 4 * Cin); }
 
 long dim_winograd5x5s2_workspace_floats(int N, int H, int W, int Cin, int Cout) {
-  const long per = (long)(((H + 1) / 2 + 3) / 4) * (((W + 1) / 2 + 3) / 4);
-  const long ns = wino_slice_images(per, 36, 4L * Cin, Cout);
-  long T = (N < ns || ns == 0 ? (long)N : ns) * per;
-  return 36 * T * (4L * Cin + Cout);
+  return wino_geom(N, (H + 1) / 2, (W + 1) / 2, 36, 4, 4 * Cin, Cout).workspace_floats();
 }
 
 int dim_winograd5x5s2_pack_weight(const float* w_oihw, float* w_packed, int Cout, int Cin, void* stream) {
@@ -663,34 +612,24 @@ int dim_conv2d_dgrad_winograd5x5s2(const float* dy, const float* w_packed, float
   if (dy_cstride == 0) dy_cstride = Cout;
   DIM_REQUIRE(dx_cstride >= Cin && dx_cstride % 2 == 0 && dy_cstride >= Cout && dy_cstride % 2 == 0, "channel strides must cover the channels");
   const int Ho = (H + 1) / 2, Wo = (W + 1) / 2;
-  const int th = (Ho + 3) / 4, tw = (Wo + 3) / 4;
-  const int CT = 4 * Cin;
-  const long ns = wino_slice_images((long)th * tw, 36, Cout, CT);
-  DIM_REQUIRE(ns > 0, "one image alone exceeds the 32-bit offsets of the plane GEMMs");
+  const WinoGeom g = wino_geom(N, Ho, Wo, 36, 4, Cout, 4 * Cin);  // the forward's workspace: K and the output width change places
+  const int th = g.th, tw = g.tw, CT = g.Nout;
   hipStream_t st = as_stream(stream);
   const FastDiv dtw = make_fastdiv((unsigned)tw), dth = make_fastdiv((unsigned)th);
-  for (int n0 = 0; n0 < N; n0 += (int)ns) {
-    const int n = N - n0 < ns ? N - n0 : (int)ns;
-    const long T = (long)n * th * tw;
-    float* V = workspace;
-    float* M = workspace + 36 * T * Cout;
-    WGemmArgs plan;
-    int rc = wino_gemm_plan(&plan, V, w_packed, M, (int)T, Cout, CT, 36, tile == 0 ? ((CT % 128 == 0 && T >= 1024) ? 4 : 3) : tile);
-    if (rc != DIM_OK) return rc;
+  auto gemm_tile = [&](long T) { return tile ? tile : (CT % 128 == 0 && T >= 1024) ? 4 : 3; };
+  auto input = [&](int n0, int n, long T, const WGemmArgs& plan, float* V) {
     const unsigned nblk = (unsigned)ceil_div(T * (Cout / kWino4Vec), 256);
     hipLaunchKernelGGL((wino4_input_kernel<kWino4Vec, 1>), dim3(nblk + plan.G - 1), dim3(256), 0, st, dy + (long)n0 * Ho * Wo * dy_cstride, V, n,
                        Ho, Wo, Cout, dy_cstride, th, tw, make_fastdiv((unsigned)(Cout / kWino4Vec)), dtw, dth, nblk, plan);
-    rc = check_launch("winograd_dgrad_input");
-    if (rc != DIM_OK) return rc;
-    rc = wino_gemm_run(plan, true, st);
-    if (rc != DIM_OK) return rc;
+    return check_launch("winograd_dgrad_input");
+  };
+  auto output = [&](int n0, int n, long T, const float* M) {
     hipLaunchKernelGGL((wino4_output_kernel<kWino4Vec, 2>), dim3(ceil_div(T * (CT / kWino4Vec), 256)), dim3(256), 0, st, M, nullptr,
                        dx + (long)n0 * H * W * dx_cstride, n, H, W, Cin, dx_cstride, 0, th, tw, 1.0f, make_fastdiv((unsigned)(CT / kWino4Vec)),
                        dtw, dth);
-    rc = check_launch("winograd_dgrad_output");
-    if (rc != DIM_OK) return rc;
-  }
-  return DIM_OK;
+    return check_launch("winograd_dgrad_output");
+  };
+  return wino_run_slices(g, w_packed, workspace, gemm_tile, /*skip5=*/0, /*zeroed=*/true, nullptr, st, input, output);
 }
 
 // Weight gradient through Winograd.  S = 1: 3x3 / stride 1 / pad 1; S = 2: 5x5 / stride 2 / pad 2 (phase images of x).
@@ -749,7 +688,7 @@ int dim_conv2d_wgrad_winograd(const float* x, const float* dy, float* dw_oihw, f
 int dim_conv2d_fwd_winograd5x5s2(const float* x, const float* w_packed, const float* bias, float* y, float* workspace, int N, int H, int W,
                                  int Cin, int in_cstride, int Cout, int out_cstride, int out_coff, float slope, int tile, void** events4,
                                  void* stream) {
-  return winograd_impl(x, w_packed, bias, y, workspace, N, H, W, Cin, in_cstride, Cout, out_cstride, out_coff, slope, tile, 4, 2, events4,
+  return winograd_fwd(x, w_packed, bias, y, workspace, N, H, W, Cin, in_cstride, Cout, out_cstride, out_coff, slope, tile, 4, 2, events4,
                        stream);
 }
 

@@ -878,29 +878,41 @@ def winograd_dgrad_pack_weight(w_oihw, m=2):
     return out
 
 
-def conv2d_fwd_winograd(x_nhwc, Cin, w_packed, bias, Cout, slope=0.1, tile=0, out=None, out_coff=0, workspace=None, events=None, m=2):
-    """3x3 / stride 1 / pad 1 convolution through Winograd F(m x m, 3x3) (m = 2 or 4, the m the weights were packed with);
-    x may carry padded channels (in_cstride = x.shape[-1]).
-    events: optional list; ("wino_in" | "conv" | "wino_out", start, end) HIP-event triples of the three launches are appended."""
+def _wino_events(events):
     import ctypes
 
-    ev_arr, evs = None, None
-    if events is not None:
-        evs = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
-        for e in evs:
-            e.record()  # materialises the hipEvent_t behind the torch object
-        ev_arr = (ctypes.c_void_p * 4)(*[e.cuda_event for e in evs])
+    if events is None:
+        return None, None
+    evs = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+    for e in evs:
+        e.record()  # materialises the hipEvent_t behind the torch object
+    return (ctypes.c_void_p * 4)(*[e.cuda_event for e in evs]), evs
+
+
+def _winograd_fwd(entry, workspace_floats, out_hw, x_nhwc, Cin, w_packed, bias, Cout, slope, tile, out, out_coff, workspace, events, *tail):
+    """the three forward Winograd wrappers: `entry` into `out` ((N,) + out_hw + (Cout,) when not given) through `workspace` (a new one
+    when none or a smaller one than workspace_floats(...) is given).  tail: what entry takes between tile and events4, and
+    workspace_floats after Cout (the m of the stride-1 path)"""
     N, H, W, in_cs = x_nhwc.shape
-    out = out if out is not None else _new((N, H, W, Cout), x_nhwc)
-    need = lib().dim_winograd_workspace_floats(N, H, W, Cin, Cout, m)
+    out = out if out is not None else _new((N,) + out_hw + (Cout,), x_nhwc)
+    need = workspace_floats(N, H, W, Cin, Cout, *tail)
     if workspace is None or workspace.numel() < need:
         workspace = _new((need,), x_nhwc)
-    check(lib().dim_conv2d_fwd_winograd(dptr(x_nhwc, f32), dptr(w_packed, f32), dptr(bias, f32), dptr(out, f32), dptr(workspace, f32), N, H, W,
-                                        Cin, in_cs, Cout, out.shape[-1], out_coff, float(slope), tile, m, ev_arr, current_stream()))
+    ev_arr, evs = _wino_events(events)
+    check(entry(dptr(x_nhwc, f32), dptr(w_packed, f32), dptr(bias, f32), dptr(out, f32), dptr(workspace, f32), N, H, W, Cin, in_cs, Cout,
+                out.shape[-1], out_coff, float(slope), tile, *tail, ev_arr, current_stream()))
     if events is not None:
         events.extend([("wino_in", evs[0], evs[1]), ("conv", evs[1], evs[2]), ("wino_out", evs[2], evs[3])])
     return out
 
+
+def conv2d_fwd_winograd(x_nhwc, Cin, w_packed, bias, Cout, slope=0.1, tile=0, out=None, out_coff=0, workspace=None, events=None, m=2):
+    """3x3 / stride 1 / pad 1 convolution through Winograd F(m x m, 3x3) (m = 2 or 4, the m the weights were packed with);
+    x may carry padded channels (in_cstride = x.shape[-1]).
+    events: optional list; ("wino_in" | "conv" | "wino_out", start, end) HIP-event triples of the three launches are appended."""
+    H, W = x_nhwc.shape[1:3]
+    return _winograd_fwd(lib().dim_conv2d_fwd_winograd, lib().dim_winograd_workspace_floats, (H, W), x_nhwc, Cin, w_packed, bias, Cout, slope,
+                         tile, out, out_coff, workspace, events, m)
 
 
 def winograd3x3s2_pack_weight(w_oihw):
@@ -915,17 +927,9 @@ def winograd3x3s2_pack_weight(w_oihw):
 def conv2d_fwd_winograd3x3s2(x_nhwc, Cin, w_packed, bias, Cout, slope=0.1, tile=0, out=None, out_coff=0, workspace=None, events=None):
     """y = LeakyReLU(conv 3x3 / stride 2 / pad 1 + bias) through the phase-image Winograd path (81 plane GEMMs); x (N,H,W,>=Cin) NHWC.
     events: as conv2d_fwd_winograd."""
-    N, H, W, in_cs = x_nhwc.shape
-    out = out if out is not None else _new((N, (H - 1) // 2 + 1, (W - 1) // 2 + 1, Cout), x_nhwc)
-    need = lib().dim_winograd3x3s2_workspace_floats(N, H, W, Cin, Cout)
-    if workspace is None or workspace.numel() < need:
-        workspace = _new((need,), x_nhwc)
-    ev_arr, evs = _wino_events(events)
-    check(lib().dim_conv2d_fwd_winograd3x3s2(dptr(x_nhwc, f32), dptr(w_packed, f32), dptr(bias, f32), dptr(out, f32), dptr(workspace, f32),
-                                             N, H, W, Cin, in_cs, Cout, out.shape[-1], out_coff, float(slope), tile, ev_arr, current_stream()))
-    if events is not None:
-        events.extend([("wino_in", evs[0], evs[1]), ("conv", evs[1], evs[2]), ("wino_out", evs[2], evs[3])])
-    return out
+    H, W = x_nhwc.shape[1:3]
+    return _winograd_fwd(lib().dim_conv2d_fwd_winograd3x3s2, lib().dim_winograd3x3s2_workspace_floats, ((H - 1) // 2 + 1, (W - 1) // 2 + 1),
+                         x_nhwc, Cin, w_packed, bias, Cout, slope, tile, out, out_coff, workspace, events)
 
 
 def winograd5x5s2_pack_weight(w_oihw):
@@ -992,30 +996,12 @@ def fc_fwd(x_nhwc, w_packed, bias, Out, slope=0.1, out=None, workspace=None, eve
     return out
 
 
-def _wino_events(events):
-    import ctypes
-
-    if events is None:
-        return None, None
-    evs = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
-    for e in evs:
-        e.record()  # materialises the hipEvent_t behind the torch object
-    return (ctypes.c_void_p * 4)(*[e.cuda_event for e in evs]), evs
-
-
 def conv2d_fwd_winograd5x5s2(x_nhwc, Cin, w_packed, bias, Cout, slope=0.1, tile=0, out=None, out_coff=0, workspace=None, events=None):
     """5x5 / stride 2 / pad 2 convolution as four phase images through Winograd F(4x4,3x3) (see include/deepim_hip.h)."""
-    ev_arr, evs = _wino_events(events)
-    N, H, W, in_cs = x_nhwc.shape
-    out = out if out is not None else _new((N, (H + 1) // 2, (W + 1) // 2, Cout), x_nhwc)
-    need = lib().dim_winograd5x5s2_workspace_floats(N, H, W, Cin, Cout)
-    if workspace is None or workspace.numel() < need:
-        workspace = _new((need,), x_nhwc)
-    check(lib().dim_conv2d_fwd_winograd5x5s2(dptr(x_nhwc, f32), dptr(w_packed, f32), dptr(bias, f32), dptr(out, f32), dptr(workspace, f32),
-                                             N, H, W, Cin, in_cs, Cout, out.shape[-1], out_coff, float(slope), tile, ev_arr, current_stream()))
-    if events is not None:
-        events.extend([("wino_in", evs[0], evs[1]), ("conv", evs[1], evs[2]), ("wino_out", evs[2], evs[3])])
-    return out
+    H, W = x_nhwc.shape[1:3]
+    return _winograd_fwd(lib().dim_conv2d_fwd_winograd5x5s2, lib().dim_winograd5x5s2_workspace_floats, ((H + 1) // 2, (W + 1) // 2), x_nhwc,
+                         Cin, w_packed, bias, Cout, slope, tile, out, out_coff, workspace, events)
+
 
 def conv2d_fwd(x_nhwc, w_packed, bias, Cout, KH, KW, stride, pad, slope=0.1, splits=1, tile=0, out=None, workspace=None,
                events=None):

@@ -49,7 +49,22 @@ def test_pure_host_queries(hip_lib):
     big = hip_lib.dim_winograd5x5s2_workspace_floats(512, 240, 320, 64, 128)
     assert big == hip_lib.dim_winograd5x5s2_workspace_floats(1024, 240, 320, 64, 128)
     assert big * 4 * 256 // (256 + 128) < (1 << 32)  # V of one slice stays below 4 GiB
-    assert hip_lib.dim_conv2d_wgrad_winograd_workspace_floats(16, 60, 80, 256, 256, 1, 4) == 36 * 4800 * 512 + 36 * 256 * 256 * 5
+    # the three size functions as literal numbers (recorded from the library before they were moved onto one geometry record): a
+    # network shape, a batch that the slice cap binds (388, 218, 97 and 323 images per slice), one image alone too big for a slice (sized
+    # for the whole batch; the run refuses), an empty batch, m = 3
+    w, w5, w3 = hip_lib.dim_winograd_workspace_floats, hip_lib.dim_winograd5x5s2_workspace_floats, hip_lib.dim_winograd3x3s2_workspace_floats
+    assert [w(16, 60, 80, 256, 256, m) for m in (4, 2, 3)] == [88473600, 157286400, 0]
+    assert [w(n, 60, 80, 256, 256, 4) for n in (388, 389, 512, 1024)] == [2145484800] * 4
+    assert [w(n, 60, 80, 256, 256, 2) for n in (218, 512, 1024)] == [2143027200] * 3
+    assert [w(512, 60, 80, 256, 256, 3), w(5, 22, 30, 64, 128, 3), w(2, 2048, 2048, 256, 256, 3)] == [0, 0, 0]
+    assert [w(5, 22, 30, 64, 128, m) for m in (4, 2)] == [1658880, 2534400]
+    assert [w(2, 2048, 2048, 256, 256, m) for m in (4, 2)] == [9663676416, 17179869184]
+    assert [w(0, 60, 80, 256, 256, m) for m in (4, 2)] == [0, 0]
+    assert [w5(16, 240, 320, 64, 128), w5(16, 120, 160, 128, 256), w5(5, 22, 30, 64, 128)] == [265420800, 132710400, 829440]
+    assert [w5(n, 240, 320, 64, 128) for n in (97, 512, 1024)] == [1609113600] * 3 and w5(2, 4096, 4096, 64, 128) == 7247757312
+    assert [w3(16, 60, 80, 256, 512), w3(16, 30, 40, 512, 512), w3(5, 29, 37, 32, 64)] == [79626240, 26542080, 777600]
+    assert [w3(n, 60, 80, 256, 512) for n in (323, 512, 1024)] == [1607454720] * 3 and w3(2, 4096, 4096, 256, 512) == 32614907904
+    assert hip_lib.dim_conv2d_wgrad_winograd_workspace_floats(16, 60, 80, 256, 256, 1, 4) ==36 * 4800 * 512 + 36 * 256 * 256 * 5
     assert hip_lib.dim_fc_fwd_workspace_floats(1024, 8, 10, 256) == 256 * 32 * 256
 
 

@@ -737,6 +737,44 @@ def test_winograd_batch_slices(hip_lib, monkeypatch):
     np.testing.assert_array_equal(ops.conv2d_fwd_winograd5x5s2(x, 64, wp5, b, 128, workspace=ws).cpu().numpy(), s5.cpu().numpy())
 
 
+def test_winograd_dgrad_batch_slices(hip_lib, monkeypatch, wino_split):
+    """the input gradient of the 5x5 / stride-2 layer runs its batch through the same slice loop as the forward layers: 5 images of
+    22 x 30 (an odd tile count in H) whole and as 2 + 2 + 1 (DIM_WINO_MAX_SLICE), both vs torch-CPU float64 autograd, padded channel
+    strides on both sides, one workspace of exactly the documented size that is NaN before every call"""
+    import torch.nn.functional as F
+    from lib.hip import ops
+
+    N, H, W, Cin, Cout = 5, 22, 30, 64, 128
+    g = torch.Generator().manual_seed(78)
+    w = torch.randn((Cout, Cin, 5, 5), generator=g) * (1.0 / np.sqrt(25 * Cout))
+    Ho, Wo = (H + 1) // 2, (W + 1) // 2
+    dy = torch.randn((N, Cout, Ho, Wo), generator=g)
+    x = torch.zeros((N, Cin, H, W), dtype=torch.float64, requires_grad=True)
+    F.conv2d(x, w.double(), None, stride=2, padding=2).backward(dy.double())
+    ref = x.grad.permute(0, 2, 3, 1).numpy()
+    tol = 1e-4 * np.abs(ref).max() + 2e-5
+    dyd = torch.zeros((N, Ho, Wo, Cout + 32), device="cuda:0")
+    dyd[..., :Cout] = dy.permute(0, 2, 3, 1).to("cuda:0")
+    wp = ops.winograd5x5s2_dgrad_pack_weight(w.to("cuda:0"))
+    ws = torch.empty((ops.lib().dim_winograd5x5s2_workspace_floats(N, H, W, Cin, Cout),), device="cuda:0")
+
+    def run():
+        ws.fill_(float("nan"))
+        dx = torch.full((N, H, W, Cin + 8), 7.0, device="cuda:0")
+        ops.conv2d_dgrad_winograd5x5s2(dyd, Cout, wp, dx, Cin, workspace=ws)
+        return dx.cpu().numpy()
+
+    whole = run()
+    monkeypatch.setenv("DIM_WINO_MAX_SLICE", "2")
+    sliced = run()
+    for name, got in (("whole", whole), ("sliced", sliced)):
+        err = np.abs(got[..., :Cin] - ref).max()
+        print("dgrad slices, {}: max error {:.3g}, bound {:.3g}".format(name, err, tol))
+        assert err <= tol, name
+        assert np.all(got[..., Cin:] == 7.0), name
+    np.testing.assert_array_equal(run(), sliced)
+
+
 @pytest.mark.parametrize("shape,tile", [((16, 60, 80, 64, 256, 3, 1, 1), 4), ((9, 120, 160, 32, 128, 3, 2, 1), 4), ((6, 96, 128, 32, 64, 3, 1, 1), 3)])
 def test_conv_auto_split_tail_vs_f64(hip_lib, shape, tile):
     """splits = 0: whole tiles per CU in one launch + split-K tail (dim_conv2d_tail_plan confirms the two-launch path) vs float64"""
