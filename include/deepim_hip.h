@@ -97,6 +97,20 @@ int dim_zoom_net_input(const float* image_observed, const float* image_rendered,
 int dim_zoom_net_input_ex(const float* image_observed, const float* image_rendered, const float* extra_observed, const float* extra_rendered,
                           const float* zoom_factor, float* X_nhwc8, int B, int H, int W, const float* means3, int mode, void* stream);
 
+/* The same samplers from planes of a SOURCE size Hs x Ws into the NETWORK size Hn x Wn (MXNet's GridGenerator(target_shape = (Hn, Wn))
+ * + BilinearSampler on Hs x Ws data): target coordinates x_t = -1 + j 2/(Wn-1), j < Wn; the affine step unchanged; x_real =
+ * (x_s + 1)(Ws-1)/2; corner validity, clamps and plane stride of the Hs x Ws planes.  The zoom factor is the window in the source's
+ * normalised coordinates (dim_zoom_factor with H = Hs, W = Ws).  With Hs, Ws == Hn, Wn every bit equals the entry points above.  All
+ * four sizes must be >= 2.
+ * dim_zoom_planes_src: the forward direction of dim_zoom_planes (no inverse, no scale_mode): x (B,C,Hs,Ws) -> y (B,C,Hn,Wn).
+ * dim_zoom_net_input_src: dim_zoom_net_input_ex (modes 0-3) with X (B,Hn,Wn,8), plus the four optional (Hn,Wn) NCHW outputs of
+ * dim_zoom_net_input (all or none; mode 0 only). */
+int dim_zoom_planes_src(const float* x, const float* zoom_factor, float* y, int B, int C, int Hs, int Ws, int Hn, int Wn, int pre, int post,
+                        const float* add3, void* stream);
+int dim_zoom_net_input_src(const float* image_observed, const float* image_rendered, const float* extra_observed, const float* extra_rendered,
+                           const float* zoom_factor, float* X_nhwc8, int B, int Hs, int Ws, int Hn, int Wn, const float* means3, int mode,
+                           float* z_image_observed, float* z_image_rendered, float* z_mask_observed, float* z_mask_rendered, void* stream);
+
 /* ZoomTrans (zoom_trans.py:22-76): mode 0 copy, 1 (dx,dy)/wx, 2 (dx,dy)*wx */
 int dim_zoom_trans(const float* zoom_factor, const float* in, float* out, int B, int mode, void* stream);
 
@@ -841,7 +855,8 @@ int dim_fc_wgrad_cls(const float* dz, const float* x, const int* class_index, in
                      int In, void* stream);
 
 /* ---------------------------------------------------------------- resident refinement loop (hosts without torch)
- * The inner loop of pred_eval (deepim/core/tester.py:476-598) for a batch of B 480x640 pairs that stays in HBM, FAST_TEST graph,
+ * The inner loop of pred_eval (deepim/core/tester.py:476-598) for a batch of B 480x640 pairs (dim_refiner_create_src: pairs of another
+ * 4:3 size) that stays in HBM, FAST_TEST graph,
  * UPDATE_MASK 'box_rendered': per iteration ZoomMask + ZoomImageWithFactor + Concat -> encoder -> fc6/fc7/rot/trans -> RT_transform
  * -> render -> box mask.  dim_refiner_create packs the weights (MXNet-layout device arrays given by name: <layer>_weight / _bias of
  * the ten encoder layers, fc6, fc7, rot, trans; the bias / fc7 / rot / trans arrays are read in place and must outlive the object),
@@ -871,6 +886,12 @@ int dim_refiner_create(dim_refiner** out, const dim_refiner_desc* desc, const ch
  * trans arrays then holding (4 n_classes,256) / (4 n_classes) / (3 n_classes,256) / (3 n_classes) floats (dim_pose_head_fwd_cls);
  * dim_refiner_run / _run_k pick every pair's head by the class_index they already receive, read when the kernels run. */
 int dim_refiner_create_cls(dim_refiner** out, const dim_refiner_desc* desc, int n_regressors, const char* const* param_names,
+                           const float* const* param_ptrs, int n_params, void* stream);
+/* dim_refiner_create_cls for a camera image of another size: desc->H x desc->W is the SOURCE size of the six blobs (4:3, H * 640 ==
+ * W * 480, both >= 2) and desc->K9 the camera of that image; the network input stays 480 x 640.  The rendered planes, the box masks,
+ * the boxes and the zoom window live at the source size, X and the encoder at the network size (dim_zoom_net_input_src between them).
+ * dim_refiner_run / _run_k take the object as they take the others; their blobs are then (B,.,H,W) of the desc. */
+int dim_refiner_create_src(dim_refiner** out, const dim_refiner_desc* desc, int n_regressors, const char* const* param_names,
                            const float* const* param_ptrs, int n_params, void* stream);
 int dim_refiner_run(dim_refiner* r, const float* image_observed, const float* image_rendered, const float* mask_observed,
                     const float* mask_rendered, const float* src_pose, const int* class_index, float* poses_iter, float* se3_iter,

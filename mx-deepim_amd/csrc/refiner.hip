@@ -4,6 +4,7 @@
 // Replaces the inner loop of pred_eval (/root/reference/deepim/core/tester.py:476-598) for a batch of B pairs that stays in HBM:
 //   ZoomMask + ZoomImageWithFactor + Concat -> FlowNetS encoder (Winograd / direct MFMA layers) -> fc6 -> fc7 / rot / trans ->
 //   RT_transform -> render -> box_rendered mask -> next iteration
+// (dim_refiner_create_src: the blobs, the renders and the boxes at the size of the camera image, X and the encoder at 480 x 640)
 // for the shipped FAST_TEST test graph (8-channel input, UPDATE_MASK 'box_rendered').  create() packs the weights and allocates every
 // buffer; run() only enqueues kernels on the caller's stream (no allocation, no synchronisation: it can be captured into a hipGraph);
 // the layer plans (tile, split-K, Winograd tile) are the ones the Python executor uses, so both drive the same launches and produce
@@ -39,8 +40,11 @@ struct LayerPlan {
 
 using namespace dim;
 
+enum { kNetH = 480, kNetW = 640 };   // the network input (the encoder's first map); a refiner's blobs may have another (source) size
+
 struct dim_refiner {
-  dim_refiner_desc d;
+  dim_refiner_desc d;   // d.H x d.W: the size of the blobs, the renders, the masks and the boxes
+  bool src;             // created by dim_refiner_create_src: the zoom samples d.H x d.W planes into the kNetH x kNetW input
   int n_regressors;   // 1: one rot / trans head; d.n_classes: one per class (rot (4K,256), trans (3K,256)), picked by class_index
   std::vector<void*> allocs;
   LayerPlan L[10];
@@ -82,17 +86,36 @@ int dim_refiner_create(dim_refiner** out, const dim_refiner_desc* desc, const ch
   return dim_refiner_create_cls(out, desc, 1, param_names, param_ptrs, n_params, stream);
 }
 
+static int refiner_create(dim_refiner** out, const dim_refiner_desc* desc, int n_regressors, const char* const* param_names,
+                          const float* const* param_ptrs, int n_params, void* stream, bool src);
+
 int dim_refiner_create_cls(dim_refiner** out, const dim_refiner_desc* desc, int n_regressors, const char* const* param_names,
                            const float* const* param_ptrs, int n_params, void* stream) {
   DIM_REQUIRE(out && desc && param_names && param_ptrs, "null pointer");
+  DIM_REQUIRE(desc->B > 0 && desc->H == kNetH && desc->W == kNetW && desc->test_iter >= 1, "B > 0, H x W = 480 x 640, test_iter >= 1 required");
+  return refiner_create(out, desc, n_regressors, param_names, param_ptrs, n_params, stream, false);
+}
+
+int dim_refiner_create_src(dim_refiner** out, const dim_refiner_desc* desc, int n_regressors, const char* const* param_names,
+                           const float* const* param_ptrs, int n_params, void* stream) {
+  DIM_REQUIRE(out && desc && param_names && param_ptrs, "null pointer");
+  DIM_REQUIRE(desc->B > 0 && desc->test_iter >= 1, "B > 0, test_iter >= 1 required");
+  DIM_REQUIRE(desc->H >= 2 && desc->W >= 2 && (long)desc->H * kNetW == (long)desc->W * kNetH,
+              "source size %d x %d must be 4:3 (H * 640 == W * 480) and >= 2", desc->H, desc->W);
+  DIM_REQUIRE(desc->W % 4 == 0, "source width must be a multiple of 4 (got %d)", desc->W);
+  return refiner_create(out, desc, n_regressors, param_names, param_ptrs, n_params, stream, true);
+}
+
+static int refiner_create(dim_refiner** out, const dim_refiner_desc* desc, int n_regressors, const char* const* param_names,
+                          const float* const* param_ptrs, int n_params, void* stream, bool src) {
   const dim_refiner_desc& d = *desc;
   DIM_REQUIRE(n_regressors == 1 || n_regressors == d.n_classes, "n_regressors must be 1 or the desc's n_classes %d (got %d)", d.n_classes,
               n_regressors);
-  DIM_REQUIRE(d.B > 0 && d.H == 480 && d.W == 640 && d.test_iter >= 1, "B > 0, H x W = 480 x 640, test_iter >= 1 required");
   DIM_REQUIRE(d.verts && d.uvs && d.faces && d.mesh_table && d.textures && d.tex_table && d.n_classes > 0 && d.vmax > 0 && d.fmax > 0,
               "mesh table missing");
   dim_refiner* r = new dim_refiner();
   r->d = d;
+  r->src = src;
   r->n_regressors = n_regressors;
   for (int c = 0; c < 3; ++c) r->plane_means[c] = d.pixel_means_bgr[2 - c];  // blob plane c holds BGR channel 2 - c
   const int B = d.B;
@@ -105,7 +128,7 @@ int dim_refiner_create_cls(dim_refiner** out, const dim_refiner_desc* desc, int 
   auto need = [&](const std::string& n) -> const float* { return find_param(param_names, param_ptrs, n_params, n); };
   // ---- encoder: plans, packed weights, activations
   long max_ws = 4;
-  int h = d.H, w = d.W, c = 8;
+  int h = kNetH, w = kNetW, c = 8;
   for (int i = 0; i < 10; ++i) {
     const Layer& ly = kEncoder[i];
     LayerPlan& P = r->L[i];
@@ -172,7 +195,7 @@ int dim_refiner_create_cls(dim_refiner** out, const dim_refiner_desc* desc, int 
   max_ws = std::max(max_ws, dim_fc_fwd_workspace_floats(1024, 8, 10, 256));
   // ---- buffers
   const size_t plane = (size_t)d.H * d.W * 4;
-  TRY(dev_alloc(r, (void**)&r->X, (size_t)B * plane * 8));
+  TRY(dev_alloc(r, (void**)&r->X, (size_t)B * kNetH * kNetW * 4 * 8));
   TRY(dev_alloc(r, (void**)&r->workspace, (size_t)max_ws * 4));
   TRY(dev_alloc(r, (void**)&r->fc6, (size_t)B * 256 * 4));
   TRY(dev_alloc(r, (void**)&r->zoom_factor, (size_t)B * 4 * 4));
@@ -234,8 +257,13 @@ int dim_refiner_run_k(dim_refiner* r, const float* image_observed, const float* 
       bb_ren = r->bbox_ren;
     }
     TRY(dim_zoom_factor(bb_obs, bb_ren, pose, d.K9, B, H, W, r->zoom_factor, status, stream));
-    TRY(dim_zoom_net_input(image_observed, img_ren, m_obs, m_ren, r->zoom_factor, r->X, B, H, W, r->plane_means, nullptr, nullptr, nullptr,
-                           nullptr, stream));
+    if (r->src) {
+      TRY(dim_zoom_net_input_src(image_observed, img_ren, m_obs, m_ren, r->zoom_factor, r->X, B, H, W, kNetH, kNetW, r->plane_means, 0, nullptr,
+                                 nullptr, nullptr, nullptr, stream));
+    } else {
+      TRY(dim_zoom_net_input(image_observed, img_ren, m_obs, m_ren, r->zoom_factor, r->X, B, H, W, r->plane_means, nullptr, nullptr, nullptr,
+                             nullptr, stream));
+    }
     // ---- encoder (:67-198)
     const float* x = r->X;
     for (int i = 0; i < 10; ++i) {

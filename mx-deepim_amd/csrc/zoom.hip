@@ -8,6 +8,8 @@
 //   ZoomMaskWithFactor  deepim/operator_py/zoom_mask_with_factor.py:29-68
 //   ZoomFlow            deepim/operator_py/zoom_flow.py:28-77
 //   ZoomDepth           deepim/operator_py/zoom_depth.py:24-50
+// The planes that are read may have another size (the camera image's, config.SCALES) than the planes that are written (the network
+// input): dim_zoom_planes_src / dim_zoom_net_input_src, the same kernel bodies with two sizes.
 // The sampling grid is never materialised.  HBM-bound: every input plane is read once
 // (neighbouring output pixels share source texels through L1/L2), every output written once.
 #include "common.h"
@@ -173,8 +175,11 @@ struct Tap {
 // Every operation is individually rounded (__f*_rn: no FMA contraction) so coordinates and weights are
 // bit-identical to a plain float32 evaluation: with 8-bit image data a 1-ulp coordinate change at x~600
 // already moves a sample by ~1e-2, which would otherwise dominate the parity budget.
-__device__ inline Tap make_tap(const Affine& a, int y, int x, int H, int W) {
-  const float sx = (float)(2.0 / (double)(W - 1)), sy = (float)(2.0 / (double)(H - 1));
+// Two sizes (GridGenerator(target_shape = (Hn, Wn)) + BilinearSampler on an H x W plane): the target coordinates x_t run over the
+// Hn x Wn grid the thread indices (y, x) belong to; x_real, the corner validity, the clamps and the offsets belong to the H x W plane
+// that is read.  The same-size entry points pass Hn = H, Wn = W and compile to what they were.
+__device__ inline Tap make_tap(const Affine& a, int y, int x, int H, int W, int Hn, int Wn) {
+  const float sx = (float)(2.0 / (double)(Wn - 1)), sy = (float)(2.0 / (double)(Hn - 1));
   float xt = __fadd_rn(-1.f, __fmul_rn((float)x, sx));
   float yt = __fadd_rn(-1.f, __fmul_rn((float)y, sy));
   float xs = __fadd_rn(__fmul_rn(a.wx, xt), a.tx);
@@ -231,17 +236,17 @@ __device__ inline float sample(const float* plane, const Tap& t, float add) {
 
 // Generic NCHW plane sampler: y[b,c] = post( sample(pre(x[b,c] + add[c])) - add[c] ) * scale(b)
 // scale_mode: 0 none, 1 divide by zoom_factor[b,0], 2 multiply by zoom_factor[b,0]   (ZoomFlow)
+// x planes are H x W, y planes Hn x Wn; one thread per pixel of y.  (The inverse factor is defined between planes of one size only.)
 template <int PRE, int POST>
-__global__ __launch_bounds__(256) void zoom_planes_kernel(const float* __restrict__ x, const float* __restrict__ zoom_factor,
-                                                          float* __restrict__ y, int C, int H, int W, int inverse,
-                                                          float add0, float add1, float add2, int scale_mode) {
+__device__ inline void zoom_planes_body(const float* __restrict__ x, const float* __restrict__ zoom_factor, float* __restrict__ y, int C,
+                                        int H, int W, int Hn, int Wn, int inverse, float add0, float add1, float add2, int scale_mode) {
   const int b = blockIdx.z;
   const int px = blockIdx.x * blockDim.x + threadIdx.x;
   const int py = blockIdx.y;
-  if (px >= W) return;
+  if (px >= Wn) return;
   const Affine a = load_affine(zoom_factor + 4 * b, inverse != 0, H, W);
-  const Tap t = make_tap(a, py, px, H, W);
-  const long plane = (long)H * W;
+  const Tap t = make_tap(a, py, px, H, W, Hn, Wn);
+  const long plane = (long)H * W, plane_n = (long)Hn * Wn;
   const float zwx = zoom_factor[4 * b];
   for (int c = 0; c < C; ++c) {
     float add = c == 0 ? add0 : (c == 1 ? add1 : add2);
@@ -252,8 +257,23 @@ __global__ __launch_bounds__(256) void zoom_planes_kernel(const float* __restric
     if (POST == POST_ROUND_M045) v = mx_round(__fsub_rn(v, 0.45f));
     if (scale_mode == 1) v = __fdiv_rn(v, zwx);
     if (scale_mode == 2) v = __fmul_rn(v, zwx);
-    y[((long)b * C + c) * plane + (long)py * W + px] = v;
+    y[((long)b * C + c) * plane_n + (long)py * Wn + px] = v;
   }
+}
+
+template <int PRE, int POST>
+__global__ __launch_bounds__(256) void zoom_planes_kernel(const float* __restrict__ x, const float* __restrict__ zoom_factor,
+                                                          float* __restrict__ y, int C, int H, int W, int inverse,
+                                                          float add0, float add1, float add2, int scale_mode) {
+  zoom_planes_body<PRE, POST>(x, zoom_factor, y, C, H, W, H, W, inverse, add0, add1, add2, scale_mode);
+}
+
+// forward only, from Hs x Ws planes into Hn x Wn planes
+template <int PRE, int POST>
+__global__ __launch_bounds__(256) void zoom_planes_src_kernel(const float* __restrict__ x, const float* __restrict__ zoom_factor,
+                                                              float* __restrict__ y, int C, int Hs, int Ws, int Hn, int Wn,
+                                                              float add0, float add1, float add2) {
+  zoom_planes_body<PRE, POST>(x, zoom_factor, y, C, Hs, Ws, Hn, Wn, 0, add0, add1, add2, 0);
 }
 
 // Fused network input (the test/train graph's Concat, deepIM_flownet.py:53-60):
@@ -263,24 +283,24 @@ __global__ __launch_bounds__(256) void zoom_planes_kernel(const float* __restric
 // MODE 0: the two masks (shipped graph); MODE 1: no masks (INPUT_MASK off: channels 6, 7 = 0, the first layer's weights for them are
 // zero too); MODE 2: no masks, depth_observed / depth_rendered in their place: plain bilinear samples (ZoomDepth, zoom_depth.py:24-50)
 // divided by 255 like the images (deepIM_flownet.py:33-51)
+// The input planes are H x W (the source size), X and the NCHW copies Hn x Wn (the network size); one thread per pixel of X.
 template <int MODE>
-__global__ __launch_bounds__(256) void zoom_net_input_kernel(const float* __restrict__ img_obs, const float* __restrict__ img_ren,
-                                                             const float* __restrict__ mask_obs, const float* __restrict__ mask_ren,
-                                                             const float* __restrict__ zoom_factor, float* __restrict__ X,
-                                                             int H, int W, float m0, float m1, float m2,
-                                                             float* __restrict__ z_img_obs, float* __restrict__ z_img_ren,
-                                                             float* __restrict__ z_mask_obs, float* __restrict__ z_mask_ren) {
+__device__ inline void zoom_net_input_body(const float* __restrict__ img_obs, const float* __restrict__ img_ren,
+                                           const float* __restrict__ mask_obs, const float* __restrict__ mask_ren,
+                                           const float* __restrict__ zoom_factor, float* __restrict__ X, int H, int W, int Hn, int Wn,
+                                           float m0, float m1, float m2, float* __restrict__ z_img_obs, float* __restrict__ z_img_ren,
+                                           float* __restrict__ z_mask_obs, float* __restrict__ z_mask_ren) {
   const int b = blockIdx.z;
   const int px = blockIdx.x * blockDim.x + threadIdx.x;
   const int py = blockIdx.y;
-  if (px >= W) return;
+  if (px >= Wn) return;
   const Affine a = load_affine(zoom_factor + 4 * b, false, H, W);
-  const Tap t = make_tap(a, py, px, H, W);
-  const long plane = (long)H * W;
+  const Tap t = make_tap(a, py, px, H, W, Hn, Wn);
+  const long plane = (long)H * W, plane_n = (long)Hn * Wn;
   if (MODE == 3) {   // the two mask lanes alone (second 8-lane group of the 10-channel first layer): [mask_obs, mask_ren, 0 x 6]
     const float mo = mx_round(sample<PRE_NONE>(mask_obs + (long)b * plane, t, 0.f));
     const float mr = mx_round(sample<PRE_BIN02>(mask_ren + (long)b * plane, t, 0.f));
-    float4* dst = reinterpret_cast<float4*>(X + ((long)b * plane + (long)py * W + px) * 8);
+    float4* dst = reinterpret_cast<float4*>(X + ((long)b * plane_n + (long)py * Wn + px) * 8);
     dst[0] = make_float4(mo, mr, 0.f, 0.f);
     dst[1] = make_float4(0.f, 0.f, 0.f, 0.f);
     return;
@@ -303,20 +323,43 @@ __global__ __launch_bounds__(256) void zoom_net_input_kernel(const float* __rest
   } else {
     v[6] = v[7] = 0.f;
   }
-  const long o = (long)py * W + px;
+  const long o = (long)py * Wn + px;
   if (MODE == 0 && z_img_obs) {
     for (int c = 0; c < 3; ++c) {
-      z_img_obs[((long)b * 3 + c) * plane + o] = v[c];
-      z_img_ren[((long)b * 3 + c) * plane + o] = v[3 + c];
+      z_img_obs[((long)b * 3 + c) * plane_n + o] = v[c];
+      z_img_ren[((long)b * 3 + c) * plane_n + o] = v[3 + c];
     }
-    z_mask_obs[(long)b * plane + o] = v[6];
-    z_mask_ren[(long)b * plane + o] = v[7];
+    z_mask_obs[(long)b * plane_n + o] = v[6];
+    z_mask_ren[(long)b * plane_n + o] = v[7];
   }
   float4 lo = make_float4(__fdiv_rn(v[0], 255.f), __fdiv_rn(v[1], 255.f), __fdiv_rn(v[2], 255.f), __fdiv_rn(v[3], 255.f));
   float4 hi = make_float4(__fdiv_rn(v[4], 255.f), __fdiv_rn(v[5], 255.f), v[6], v[7]);
-  float4* dst = reinterpret_cast<float4*>(X + ((long)b * plane + o) * 8);
+  float4* dst = reinterpret_cast<float4*>(X + ((long)b * plane_n + o) * 8);
   dst[0] = lo;
   dst[1] = hi;
+}
+
+template <int MODE>
+__global__ __launch_bounds__(256) void zoom_net_input_kernel(const float* __restrict__ img_obs, const float* __restrict__ img_ren,
+                                                             const float* __restrict__ mask_obs, const float* __restrict__ mask_ren,
+                                                             const float* __restrict__ zoom_factor, float* __restrict__ X,
+                                                             int H, int W, float m0, float m1, float m2,
+                                                             float* __restrict__ z_img_obs, float* __restrict__ z_img_ren,
+                                                             float* __restrict__ z_mask_obs, float* __restrict__ z_mask_ren) {
+  zoom_net_input_body<MODE>(img_obs, img_ren, mask_obs, mask_ren, zoom_factor, X, H, W, H, W, m0, m1, m2, z_img_obs, z_img_ren, z_mask_obs,
+                            z_mask_ren);
+}
+
+// the blobs at the source size Hs x Ws, X at the network size Hn x Wn
+template <int MODE>
+__global__ __launch_bounds__(256) void zoom_net_input_src_kernel(const float* __restrict__ img_obs, const float* __restrict__ img_ren,
+                                                                 const float* __restrict__ mask_obs, const float* __restrict__ mask_ren,
+                                                                 const float* __restrict__ zoom_factor, float* __restrict__ X,
+                                                                 int Hs, int Ws, int Hn, int Wn, float m0, float m1, float m2,
+                                                                 float* __restrict__ z_img_obs, float* __restrict__ z_img_ren,
+                                                                 float* __restrict__ z_mask_obs, float* __restrict__ z_mask_ren) {
+  zoom_net_input_body<MODE>(img_obs, img_ren, mask_obs, mask_ren, zoom_factor, X, Hs, Ws, Hn, Wn, m0, m1, m2, z_img_obs, z_img_ren,
+                            z_mask_obs, z_mask_ren);
 }
 
 }  // namespace dim
@@ -409,6 +452,57 @@ int dim_zoom_net_input_ex(const float* image_observed, const float* image_render
   else DIM_ZNI(3);
 #undef DIM_ZNI
   return check_launch("zoom_net_input_ex");
+}
+
+int dim_zoom_planes_src(const float* x, const float* zoom_factor, float* y, int B, int C, int Hs, int Ws, int Hn, int Wn, int pre, int post,
+                        const float* add3, void* stream) {
+  if (B == 0) return DIM_OK;  // empty batch: nothing to do, pointers may be NULL
+  DIM_REQUIRE(x && zoom_factor && y, "null pointer");
+  DIM_REQUIRE(Hs >= 2 && Ws >= 2 && Hn >= 2 && Wn >= 2, "source %d x %d and network %d x %d sizes must be >= 2", Hs, Ws, Hn, Wn);
+  DIM_REQUIRE(C >= 1, "C must be >= 1 (got %d)", C);
+  DIM_REQUIRE(pre == PRE_NONE || pre == PRE_BIN02, "pre must be 0 or 1");
+  DIM_REQUIRE(post >= 0 && post <= 2, "post must be 0..2");
+  DIM_REQUIRE(!add3 || C <= 3, "per-plane add constants only for C <= 3");
+  float a0 = add3 ? add3[0] : 0.f, a1 = add3 && C > 1 ? add3[1] : 0.f, a2 = add3 && C > 2 ? add3[2] : 0.f;
+  dim3 grid(ceil_div(Wn, 256), Hn, B), block(256);
+  hipStream_t st = as_stream(stream);
+#define DIM_ZP(PRE, POST) \
+  hipLaunchKernelGGL((zoom_planes_src_kernel<PRE, POST>), grid, block, 0, st, x, zoom_factor, y, C, Hs, Ws, Hn, Wn, a0, a1, a2)
+  if (pre == 0 && post == 0) DIM_ZP(0, 0);
+  else if (pre == 0 && post == 1) DIM_ZP(0, 1);
+  else if (pre == 0 && post == 2) DIM_ZP(0, 2);
+  else if (pre == 1 && post == 0) DIM_ZP(1, 0);
+  else if (pre == 1 && post == 1) DIM_ZP(1, 1);
+  else DIM_ZP(1, 2);
+#undef DIM_ZP
+  return check_launch("zoom_planes_src");
+}
+
+int dim_zoom_net_input_src(const float* image_observed, const float* image_rendered, const float* extra_observed, const float* extra_rendered,
+                           const float* zoom_factor, float* X_nhwc8, int B, int Hs, int Ws, int Hn, int Wn, const float* means3, int mode,
+                           float* z_image_observed, float* z_image_rendered, float* z_mask_observed, float* z_mask_rendered, void* stream) {
+  if (B == 0) return DIM_OK;
+  DIM_REQUIRE(image_observed && image_rendered && zoom_factor && X_nhwc8 && means3, "null pointer");
+  DIM_REQUIRE(Hs >= 2 && Ws >= 2 && Hn >= 2 && Wn >= 2, "source %d x %d and network %d x %d sizes must be >= 2", Hs, Ws, Hn, Wn);
+  DIM_REQUIRE(mode >= 0 && mode <= 3, "mode 0 (masks), 1 (images only), 2 (depth planes) or 3 (mask lanes alone)");
+  DIM_REQUIRE(mode == 1 || (extra_observed && extra_rendered), "modes 0, 2 and 3 need the two extra planes");
+  bool any = z_image_observed || z_image_rendered || z_mask_observed || z_mask_rendered;
+  bool all = z_image_observed && z_image_rendered && z_mask_observed && z_mask_rendered;
+  DIM_REQUIRE(!any || all, "pass all four NCHW outputs or none");
+  DIM_REQUIRE(!any || mode == 0, "the four NCHW outputs exist in mode 0 only");
+  const int bx = (Wn % 256 != 0 && Wn % 128 == 0) ? 128 : 256;
+  dim3 grid(ceil_div(Wn, bx), Hn, B), block(bx);
+  hipStream_t st = as_stream(stream);
+#define DIM_ZNI(M)                                                                                                                        \
+  hipLaunchKernelGGL(zoom_net_input_src_kernel<M>, grid, block, 0, st, image_observed, image_rendered, extra_observed, extra_rendered, \
+                     zoom_factor, X_nhwc8, Hs, Ws, Hn, Wn, means3[0], means3[1], means3[2], z_image_observed, z_image_rendered,        \
+                     z_mask_observed, z_mask_rendered)
+  if (mode == 0) DIM_ZNI(0);
+  else if (mode == 1) DIM_ZNI(1);
+  else if (mode == 2) DIM_ZNI(2);
+  else DIM_ZNI(3);
+#undef DIM_ZNI
+  return check_launch("zoom_net_input_src");
 }
 
 }  // extern "C"

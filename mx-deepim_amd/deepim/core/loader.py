@@ -20,7 +20,8 @@ Randomness (training) is drawn by the single staging thread in pair order with t
 mask_dilate's draws; np.random.shuffle for the point sample), so a seeded run is reproducible as long as nothing else draws from
 the global generators while an epoch is being staged -- the reference itself is not reproducible (its draws happen in pool processes).
 
-Not built (raise): img_flipped (the reference raises too), TRAIN.MASK_SYN, network.MASK_INPUTS, SCALES other than the image size.
+Not built (raise): img_flipped (the reference raises too), TRAIN.MASK_SYN, network.MASK_INPUTS, SCALES other than the image size
+(test loader: any 4:3 size, staged as it is; train loader: the network size only).
 `RawPairSource` is the seam for pixels that do not come from files (bench.py's synthetic `fresh_batch` line).
 """
 from __future__ import print_function, division
@@ -317,10 +318,19 @@ def _DeviceLoader_reset(self):
     self._prefetch()
 
 
-def _check_common(cfg, H, W):
+def _check_common(cfg, H, W, test=False):
+    """the files are staged as they are (there is no resize): SCALES must name their size.  The test loader takes any 4:3 size
+    (deepim.symbols.deepIM_flownet.source_size: the refinement loop zooms from it into the network input); training is built at the
+    network size only."""
     scales = [tuple(int(v) for v in s) for s in cfg.SCALES]
-    if any(s != (min(H, W), max(H, W)) for s in scales):
-        raise NotImplementedError("device loader: SCALES must be [[{}, {}]] (resize is the identity), got {}".format(min(H, W), max(H, W), cfg.SCALES))
+    if test:
+        from deepim.symbols.deepIM_flownet import source_size
+
+        if source_size(cfg) != (H, W):
+            raise ValueError("device loader: the files are staged at {}x{} but SCALES is {} (there is no resize)".format(H, W, cfg.SCALES))
+    elif any(s != (min(H, W), max(H, W)) for s in scales):
+        raise NotImplementedError("device loader: SCALES must be [[{}, {}]] (resize is the identity; training at another image size is out "
+                                  "of scope, only the test path zooms from it), got {}".format(min(H, W), max(H, W), cfg.SCALES))
     if cfg.network.get("MASK_INPUTS", False):
         raise NotImplementedError("device loader: network.MASK_INPUTS")
 
@@ -348,10 +358,15 @@ class TestDataLoader(_DeviceLoader):
     depth_observed is staged for INPUT_DEPTH, for the depth ICP after the loop (TEST.ICP_ITER > 0) and for the depth score of several
     hypotheses per pair (TEST.HYP_NUM > 1, TEST.HYP_SCORE 'depth')."""
 
-    def __init__(self, pairdb, config, batch_size=1, shuffle=False, device="cuda:0", workers=8, source=None, height=480, width=640,
+    def __init__(self, pairdb, config, batch_size=1, shuffle=False, device="cuda:0", workers=8, source=None, height=None, width=None,
                  cache=None):
+        """height, width: the size of the files, None = config.SCALES[0] (any 4:3 size; the blobs are staged at it)"""
         cfg = config
-        _check_common(cfg, height, width)
+        if height is None or width is None:
+            from deepim.symbols.deepIM_flownet import source_size
+
+            height, width = source_size(cfg)
+        _check_common(cfg, height, width, test=True)
         self.input_mask, self.input_depth = bool(cfg.network.INPUT_MASK), bool(cfg.network.INPUT_DEPTH)
         self.init_mask = cfg.TEST.INIT_MASK
         self.dilate = bool(cfg.TEST.get("MASK_DILATE", False))

@@ -9,7 +9,8 @@ pairs stays in HBM for all iterations:
     forward (zoom -> encoder -> heads)  ->  se3_compose  ->  rasterise (image_rendered, mask_rendered,
     bbox)  ->  box mask (mask_observed, UPDATE_MASK == "box_rendered")  ->  forward ...
 
-and the whole loop can be captured into one hipGraph (`Refiner(capture_graph=True)`).
+and the whole loop can be captured into one hipGraph (`Refiner(capture_graph=True)`).  The blobs, the renders and the masks have the
+size of the camera image, config.SCALES[0] (any 4:3 size, K the camera of that image); the network input stays 480x640.
 """
 from __future__ import print_function, division
 
@@ -19,7 +20,7 @@ import torch
 from lib.hip import ops
 from deepim.core.coarse import CoarseInit, boxes_from_int, coarse_settings
 from deepim.core.score_lists import PairLists, ScoreLists
-from deepim.symbols.deepIM_flownet import FlowNetHip
+from deepim.symbols.deepIM_flownet import FlowNetHip, source_size
 
 HYP_SCORES = ("rgb", "depth")
 ERR_KEYS = ("re", "te", "add", "arp_2d")   # the per-pose error lists lib.dataset.evaluation.PoseEvaluator takes as `errors=`
@@ -110,11 +111,30 @@ def hypothesis_rotations(N, rot_deg):
     return R
 
 
+def refuse_at_source_size(cfg, size, lit=False):
+    """the stages that exist at the network size only: with SCALES of another size every one that is switched on raises a ValueError
+    naming its key and SCALES (none may run at the wrong size).  What runs at any 4:3 size: the FAST_TEST loop (UPDATE_MASK
+    'box_rendered' / 'init', per-pair K, graph capture, the INPUT_DEPTH graphs), TEST.DEVICE_EVAL and TEST.BOP without BOP_VSD."""
+    if tuple(size) == (FlowNetHip.H, FlowNetHip.W):
+        return
+    T = cfg.TEST
+    on = [("TEST.ICP_ITER", int(T.get("ICP_ITER", 0) or 0) > 0), ("TEST.HYP_NUM", int(T.get("HYP_NUM", 1) or 1) > 1),
+          ("TEST.COARSE_VIEWS", int(T.get("COARSE_VIEWS", 0) or 0) > 0), ("TEST.VSD", bool(T.get("VSD", False))),
+          ("TEST.BOP_VSD", bool(T.get("BOP_VSD", False))), ("TEST.FLOW_PNP_ITER", int(T.get("FLOW_PNP_ITER", 0) or 0) > 0),
+          ("network.PRED_FLOW without TEST.FAST_TEST (the test-time flow error)", bool(cfg.network.PRED_FLOW and not T.FAST_TEST)),
+          ("the lit ModelNet renderer", bool(lit))]
+    for key, active in on:
+        if active:
+            raise ValueError("{} is built for SCALES [[{}, {}]] only, got SCALES {}x{}: switch it off or shrink the images to the network "
+                             "size".format(key, FlowNetHip.H, FlowNetHip.W, size[0], size[1]))
+
+
 class Predictor(object):
     """Reference: binds a MutableModule and calls forward (tester.py:27-56).  Here: owns a FlowNetHip."""
 
     def __init__(self, config, arg_params, batch_size, device="cuda:0", conv_plan=None, winograd=True):
-        self.net = FlowNetHip(config, arg_params, batch_size, device=device, conv_plan=conv_plan, winograd=winograd)
+        self.net = FlowNetHip(config, arg_params, batch_size, device=device, conv_plan=conv_plan, winograd=winograd,
+                              source_size=source_size(config))
         self.data_names = ["image_observed", "image_rendered", "src_pose", "class_index", "mask_observed", "mask_rendered"]
 
     def predict(self, data_batch):
@@ -136,6 +156,9 @@ class Refiner(object):
         if cfg.network.INPUT_MASK and cfg.network.PRED_MASK and cfg.TEST.UPDATE_MASK not in ("box_rendered", "init"):
             # same restriction as the released loop (tester.py:579-587)
             raise Exception("Unknown UPDATE_MASK type: {}".format(cfg.TEST.UPDATE_MASK))
+        # (Hs, Ws): the size of every image-like buffer here -- the camera image, the renders, the masks; the network input stays 480x640
+        H, W = source_size(cfg)
+        refuse_at_source_size(cfg, (H, W), lit=hasattr(render_machine, "normals"))
         self.hyp_num, self.hyp_rot_deg, self.hyp_score_mode, self.hyp_tau = hyp_settings(cfg)
         self.flow_pnp_iter, self.flow_pnp_warm, self.flow_pnp_huber, self.flow_pnp_gate = flow_pnp_settings(cfg)
         N = self.hyp_num
@@ -144,6 +167,12 @@ class Refiner(object):
                 batch_size, N, batch_size * N, predictor.net.B))
         if N > 1 and hasattr(render_machine, "normals"):
             raise ValueError("TEST.HYP_NUM > 1 is not supported with the lit ModelNet renderer")
+        if (predictor.net.Hs, predictor.net.Ws) != (H, W):
+            raise ValueError("Refiner: SCALES is {}x{} but the Predictor's network was built for a {}x{} source".format(
+                H, W, predictor.net.Hs, predictor.net.Ws))
+        if (int(render_machine.height), int(render_machine.width)) != (H, W):
+            raise ValueError("Refiner: SCALES is {}x{} but the render machine draws {}x{}".format(H, W, render_machine.height,
+                                                                                                   render_machine.width))
         self.cfg = cfg
         self.predictor = predictor
         self.net = predictor.net
@@ -152,7 +181,7 @@ class Refiner(object):
         self.B = batch_size * N   # samples
         self.test_iter = int(cfg.TEST.test_iter)
         d = self.net.device
-        B, H, W = self.B, 480, 640
+        B = self.B
         self.batch = {
             "image_observed": torch.zeros((B, 3, H, W), dtype=torch.float32, device=d),
             "image_rendered": torch.zeros((B, 3, H, W), dtype=torch.float32, device=d),
@@ -720,7 +749,9 @@ class FlowEPE(object):
         K = np.asarray(config.dataset.INTRINSIC_MATRIX, dtype=np.float64).reshape(3, 3)
         self.K = K
         self.Kinv64 = np.linalg.inv(K)
-        B, H, W = batch_size, 480, 640
+        H, W = source_size(config)
+        refuse_at_source_size(config, (H, W))   # the flow head's output exists at the network size only
+        B = batch_size
         self.flow = torch.empty((B, 2, H, W), dtype=torch.float32, device=device)
         self.weights = torch.empty((B, 2, H, W), dtype=torch.float32, device=device)
         self.sums = torch.zeros((B, 5), dtype=torch.float64, device=device)

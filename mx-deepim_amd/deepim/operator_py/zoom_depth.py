@@ -1,5 +1,5 @@
 """ZoomDepth custom op on the HIP kernels (reference: deepim/operator_py/zoom_depth.py:18-84)."""
-from lib.hip import ops
+from .zoom_common import zoom_to, zoomed_shape
 from .custom_op import CustomOp, CustomOpProp, register
 
 
@@ -13,8 +13,8 @@ class ZoomDepthOperator(CustomOp):
         zoom_factor, depth_real, depth_rendered = in_data
         for wx, wy, tx, ty in zoom_factor.cpu().tolist():
             print("wx: {}, wy: {}, tx: {}, ty: {}".format(wx, wy, tx, ty))  # the reference prints per sample (:32)
-        self.assign(out_data[0], req[0], ops.zoom_planes(depth_real, zoom_factor))
-        self.assign(out_data[1], req[1], ops.zoom_planes(depth_rendered, zoom_factor))
+        self.assign(out_data[0], req[0], zoom_to(depth_real, zoom_factor, self.height, self.width))
+        self.assign(out_data[1], req[1], zoom_to(depth_rendered, zoom_factor, self.height, self.width))
 
     def backward(self, req, out_grad, in_data, out_data, in_grad, aux):
         for i in range(3):
@@ -35,7 +35,7 @@ class ZoomDepthProp(CustomOpProp):
         return ["zoom_depth_observed", "zoom_depth_rendered"]
 
     def infer_shape(self, in_shape):
-        return in_shape, [in_shape[1], in_shape[2]], []
+        return in_shape, [zoomed_shape(in_shape[1], self.height, self.width), zoomed_shape(in_shape[2], self.height, self.width)], []
 
     def infer_type(self, in_type):
         dtype = in_type[0]

@@ -3,6 +3,7 @@ Output arity changes with b_inv_zoom exactly like the reference Prop (:93-105)."
 import torch
 
 from lib.hip import ops
+from .zoom_common import require_same_size
 from .custom_op import CustomOp, CustomOpProp, register
 
 
@@ -15,6 +16,8 @@ class ZoomFlowOperator(CustomOp):
 
     def forward(self, is_train, req, in_data, out_data, aux):
         zoom_factor, flow = in_data[0], in_data[1]
+        for x in in_data[1:]:   # the inverse factor and the scaling of the flow values by wx hold between planes of one size
+            require_same_size("ZoomFlow", x, self.height, self.width, "the inverse zoom and the flow scaling")
         zf_host = zoom_factor[:, :2].cpu()
         assert torch.equal(zf_host[:, 0], zf_host[:, 1]), "wx and wy should be equal"  # (:62)
         # inverse zoom multiplies the values by wx, forward zoom divides (:59-66)

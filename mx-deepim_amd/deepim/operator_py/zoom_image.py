@@ -4,6 +4,7 @@ import numpy as np
 import torch
 
 from lib.hip import ops
+from .zoom_common import zoom_to, zoomed_shape
 from .custom_op import CustomOp, CustomOpProp, parse_array, register
 
 
@@ -20,14 +21,15 @@ class ZoomImageOperator(CustomOp):
         bo = ops.mask_bbox(image_real, 0.01, mode=1, means3=self.pixel_means)
         br = ops.mask_bbox(image_rendered, 0.01, mode=1, means3=self.pixel_means)
         status = torch.zeros(src_pose.shape[0], dtype=torch.int32, device=src_pose.device)
-        zf = ops.zoom_factor(bo, br, src_pose, self.K, self.height, self.width, status=status)
+        # the window in the INPUT's normalised coordinates (K is the camera of that image); the samples land in (height, width)
+        zf = ops.zoom_factor(bo, br, src_pose, self.K, image_real.shape[2], image_real.shape[3], status=status)
         st = status.cpu().numpy()
         if (st & 1).any():
             raise ValueError("zero-size array to reduction operation minimum which has no identity (empty observed image)")
         for b in np.nonzero(st & 2)[0]:
             print("NO POINT VALID IN rendered")
-        self.assign(out_data[0], req[0], ops.zoom_planes(image_real, zf, add3=self.pixel_means))
-        self.assign(out_data[1], req[1], ops.zoom_planes(image_rendered, zf, add3=self.pixel_means))
+        self.assign(out_data[0], req[0], zoom_to(image_real, zf, self.height, self.width, add3=self.pixel_means))
+        self.assign(out_data[1], req[1], zoom_to(image_rendered, zf, self.height, self.width, add3=self.pixel_means))
         self.assign(out_data[2], req[2], zf)
 
     def backward(self, req, out_grad, in_data, out_data, in_grad, aux):
@@ -52,7 +54,7 @@ class ZoomImageProp(CustomOpProp):
 
     def infer_shape(self, in_shape):
         batch_size = in_shape[0][0]
-        return in_shape, [in_shape[0], in_shape[1], [batch_size, 4]], []
+        return in_shape, [zoomed_shape(in_shape[0], self.height, self.width), zoomed_shape(in_shape[1], self.height, self.width), [batch_size, 4]], []
 
     def infer_type(self, in_type):
         dtype = in_type[0]

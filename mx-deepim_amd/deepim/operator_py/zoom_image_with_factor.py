@@ -5,7 +5,7 @@ config's PIXEL_MEANS and is reversed like the reference Prop does (:94); the opt
 import numpy as np
 import torch
 
-from lib.hip import ops
+from .zoom_common import zoom_to, zoomed_shape
 from .custom_op import CustomOp, CustomOpProp, parse_array, register
 
 
@@ -21,8 +21,8 @@ class ZoomImageWithFactorOperator(CustomOp):
 
     def forward(self, is_train, req, in_data, out_data, aux):
         zoom_factor, image_real, image_rendered = in_data
-        zoom_real = ops.zoom_planes(image_real, zoom_factor, add3=self.pixel_means)
-        zoom_rendered = ops.zoom_planes(image_rendered, zoom_factor, add3=self.pixel_means)
+        zoom_real = zoom_to(image_real, zoom_factor, self.height, self.width, add3=self.pixel_means)
+        zoom_rendered = zoom_to(image_rendered, zoom_factor, self.height, self.width, add3=self.pixel_means)
         if self.high_light_center:
             if self.center_map is None:
                 B = image_real.shape[0]
@@ -57,7 +57,7 @@ class ZoomImageWithFactorProp(CustomOpProp):
         return ["zoom_image_observed", "zoom_image_rendered"]
 
     def infer_shape(self, in_shape):
-        return in_shape, [in_shape[1], in_shape[2]], []
+        return in_shape, [zoomed_shape(in_shape[1], self.height, self.width), zoomed_shape(in_shape[2], self.height, self.width)], []
 
     def infer_type(self, in_type):
         dtype = in_type[0]

@@ -6,6 +6,7 @@ import numpy as np
 import torch
 
 from lib.hip import ops
+from .zoom_common import zoom_to, zoomed_shape
 from .custom_op import CustomOp, CustomOpProp, parse_array, register
 
 
@@ -21,15 +22,16 @@ class ZoomMaskOperator(CustomOp):
         bo = ops.mask_bbox(mask_real_gt, 0.3)          # valid_real = sum(mask_gt, axis=1) > 0.3      (:35-37)
         br = ops.mask_bbox(mask_rendered, 0.2)         # rendered binarised at 0.2, then > 0.3        (:39-47)
         status = torch.zeros(src_pose.shape[0], dtype=torch.int32, device=src_pose.device)
-        zf = ops.zoom_factor(bo, br, src_pose, self.K, self.height, self.width, status=status)
+        # the window in the INPUT's normalised coordinates (K is the camera of that image); the samples land in (height, width)
+        zf = ops.zoom_factor(bo, br, src_pose, self.K, mask_real_gt.shape[2], mask_real_gt.shape[3], status=status)
         st = status.cpu().numpy()
         if (st & 1).any():
             # reference: np.min(nz_x) of an empty array (:58)
             raise ValueError("zero-size array to reduction operation minimum which has no identity (empty observed mask)")
         for b in np.nonzero(st & 2)[0]:
             print("NO POINT VALID IN MASK rendered")    # (:75)
-        outs = [ops.zoom_planes(mask_real_est, zf, post=1), ops.zoom_planes(mask_real_gt, zf, post=1),
-                ops.zoom_planes(mask_rendered, zf, pre=1, post=1), zf]
+        hw = (self.height, self.width)
+        outs = [zoom_to(mask_real_est, zf, *hw, post=1), zoom_to(mask_real_gt, zf, *hw, post=1), zoom_to(mask_rendered, zf, *hw, pre=1, post=1), zf]
         for i in range(4):
             self.assign(out_data[i], req[i], outs[i])
 
@@ -54,7 +56,7 @@ class ZoomMaskProp(CustomOpProp):
 
     def infer_shape(self, in_shape):
         batch_size = in_shape[0][0]
-        out_shape = in_shape[:-1]
+        out_shape = [zoomed_shape(s, self.height, self.width) for s in in_shape[:-1]]
         out_shape.append([batch_size, 4])
         return in_shape, out_shape, []
 

@@ -1,5 +1,6 @@
 """ZoomMaskWithFactor custom op on the HIP kernels (reference: deepim/operator_py/zoom_mask_with_factor.py:22-110)."""
 from lib.hip import ops
+from .zoom_common import require_same_size, zoom_to, zoomed_shape
 from .custom_op import CustomOp, CustomOpProp, register
 
 
@@ -12,8 +13,13 @@ class ZoomMaskWithFactorOperator(CustomOp):
 
     def forward(self, is_train, req, in_data, out_data, aux):
         zoom_factor, mask = in_data
+        if self.b_inv_zoom:
+            require_same_size("ZoomMaskWithFactor", mask, self.height, self.width, "the inverse zoom (b_inv_zoom)")
+            out = ops.zoom_planes(mask, zoom_factor, inverse=True, pre=1, post=1)
+        else:
+            out = zoom_to(mask, zoom_factor, self.height, self.width, pre=1, post=1)
         # binarise at 0.2 (:35-38), sample forward / inverse (:41-63), mx.nd.round (:66)
-        self.assign(out_data[0], req[0], ops.zoom_planes(mask, zoom_factor, inverse=self.b_inv_zoom, pre=1, post=1))
+        self.assign(out_data[0], req[0], out)
 
     def backward(self, req, out_grad, in_data, out_data, in_grad, aux):
         self.assign(in_grad[0], req[0], 0)
@@ -35,7 +41,7 @@ class ZoomMaskWithFactorProp(CustomOpProp):
         return ["zoom_mask"]
 
     def infer_shape(self, in_shape):
-        return in_shape, [in_shape[1]], []
+        return in_shape, [zoomed_shape(in_shape[1], self.height, self.width)], []
 
     def infer_type(self, in_type):
         dtype = in_type[0]

@@ -220,14 +220,30 @@ class deepIM_flownet(object):
         return arg_params
 
 
+def source_size(cfg, net=(480, 640)):
+    """(Hs, Ws) = config.SCALES[0], the size of every image-like blob (the camera image, the renders, the masks), checked: ONE entry
+    of the network input's 4:3 aspect (the zoom window rule's 0.75 assumes it), both sides >= 2.  ValueError names SCALES."""
+    scales = [tuple(int(v) for v in s) for s in cfg.SCALES]
+    if len(scales) != 1 or len(scales[0]) != 2:
+        raise ValueError("SCALES must hold exactly one [height, width] entry (multi-scale testing is not supported), got {}".format(cfg.SCALES))
+    Hs, Ws = scales[0]
+    if Hs < 2 or Ws < 2 or Hs * net[1] != Ws * net[0]:
+        raise ValueError("SCALES {} is not a 4:3 [height, width] with both sides >= 2: the zoom window assumes the aspect of the {}x{} "
+                         "network input -- crop the images to 4:3".format(cfg.SCALES, net[0], net[1]))
+    return Hs, Ws
+
+
 class FlowNetHip(object):
     """Device executor of the test graph for a fixed per-GPU batch size B (all buffers pre-allocated)."""
 
-    H, W = 480, 640
+    H, W = 480, 640   # the network size: X, the encoder, the heads
 
     def __init__(self, cfg, arg_params, batch_size, device="cuda:0", conv_plan=None, winograd=True, wino_m=None, wino_tile=None,
-                 bf16=False, wino_s2=True):
-        """winograd: run the 3x3 / stride-1 layers (conv3_1, conv4_1, conv5_1, conv6_1) through Winograd F(4x4,3x3) / F(2x2,3x3)
+                 bf16=False, wino_s2=True, source_size=None):
+        """source_size: (Hs, Ws) of the blobs forward_test / zoom / net_input read (4:3), None = the network size.  The zoom window is
+        found at that size (with cfg.dataset.INTRINSIC_MATRIX the camera of that image) and the blobs are sampled into the 480x640
+        input; the FAST_TEST graph only (the inverse zoom of the flow / mask heads is defined between planes of one size).
+        winograd: run the 3x3 / stride-1 layers (conv3_1, conv4_1, conv5_1, conv6_1) through Winograd F(4x4,3x3) / F(2x2,3x3)
         (same f32 result within 1e-4 relative, 4x / 2.25x fewer multiply-adds) and the 5x5 / stride-2 layers (conv2, conv3) through
         their four phase images and F(4x4,3x3) (2.78x fewer).  False = direct kernel for every layer.
         wino_s2: with winograd, also the 3x3 / stride-2 layers whose output map has >= 300 pixels (conv4, conv5) through their phase
@@ -242,6 +258,9 @@ class FlowNetHip(object):
             winograd = False
         self.cfg = cfg
         self.B = batch_size
+        self.Hs, self.Ws = (self.H, self.W) if source_size is None else (int(source_size[0]), int(source_size[1]))
+        if self.Hs < 2 or self.Ws < 2 or self.Hs * self.W != self.Ws * self.H:
+            raise ValueError("source size {}x{} (SCALES) must be 4:3 with both sides >= 2".format(self.Hs, self.Ws))
         self.device = torch.device(device)
         self.cin = input_channels(cfg)
         self.n_regressors = regressor_num(cfg)
@@ -342,6 +361,10 @@ class FlowNetHip(object):
         self.workspace = torch.empty((max(max_ws, 4),), dtype=torch.float32, device=d)
         # ---- decoder + flow / mask heads (only in the graph when not FAST_TEST, reference :840-954)
         self.has_decoder = "deconv5_weight" in self.params
+        if (self.has_decoder and not cfg.TEST.FAST_TEST and (cfg.network.PRED_MASK or cfg.network.PRED_FLOW)
+                and (self.Hs, self.Ws) != (self.H, self.W)):
+            raise ValueError("the full graph (decoder, mask and flow heads; TEST.FAST_TEST off) runs at SCALES [[{}, {}]] only, got {}x{}: "
+                             "set TEST.FAST_TEST or SCALES to the network size".format(self.H, self.W, self.Hs, self.Ws))
         if self.has_decoder:
             self.packed["deconv5"] = self.pack_deconv(self.params["deconv5_weight"])
             self.packed["deconv4"] = self.pack_deconv(self.params["deconv4_weight"])
@@ -429,13 +452,15 @@ class FlowNetHip(object):
             # ZoomImage (zoom_image.py:31-37): the validity "mask" of an image is sum_c(image + mean) > 0.01
             bbox_obs = ops.mask_bbox(batch["image_observed"], 0.01, mode=1, means3=self.plane_means, out=self.bbox_obs)
             bbox_ren = ops.mask_bbox(batch["image_rendered"], 0.01, mode=1, means3=self.plane_means, out=self.bbox_ren)
-        ops.zoom_factor(bbox_obs, bbox_ren, batch["src_pose"] if src_pose is None else src_pose, self.K, self.H, self.W,
+        ops.zoom_factor(bbox_obs, bbox_ren, batch["src_pose"] if src_pose is None else src_pose, self.K, self.Hs, self.Ws,
                         out=self.zoom_factor, status=self.status if status is None else status)
         return self.net_input(batch, nchw_out=nchw_out)
 
     def net_input(self, batch, nchw_out=None):
         """the first layer's input from the blobs and self.zoom_factor: ZoomImageWithFactor (+ ZoomDepth) (+ the zoomed masks) in the
         Concat order of get_convs (reference :33-66), as one or two 8-lane NHWC tensors (see input_mode)"""
+        if (self.Hs, self.Ws) != (self.H, self.W):
+            return self._net_input_src(batch, nchw_out)
         if self.input_mode == 0:
             ops.zoom_net_input(batch["image_observed"], batch["image_rendered"], batch["mask_observed"], batch["mask_rendered"],
                                self.zoom_factor, self.plane_means, X=self.X, nchw_out=nchw_out)
@@ -447,6 +472,20 @@ class FlowNetHip(object):
             if self.input_mode == 3:
                 ops.zoom_net_input_ex(batch["image_observed"], batch["image_rendered"], batch["mask_observed"], batch["mask_rendered"],
                                       self.zoom_factor, self.plane_means, 3, X=self.X2)
+        return self.X
+
+    def _net_input_src(self, batch, nchw_out=None):
+        """net_input from blobs of another (source) size: the same lanes through dim_zoom_net_input_src"""
+        img = (batch["image_observed"], batch["image_rendered"])
+        masks, depths = (batch.get("mask_observed"), batch.get("mask_rendered")), (batch.get("depth_observed"), batch.get("depth_rendered"))
+        if self.input_mode == 0:
+            ops.zoom_net_input_src(*img, *masks, self.zoom_factor, self.plane_means, 0, X=self.X, nchw_out=nchw_out)
+        elif self.input_mode == 1:
+            ops.zoom_net_input_src(*img, None, None, self.zoom_factor, self.plane_means, 1, X=self.X)
+        else:
+            ops.zoom_net_input_src(*img, *depths, self.zoom_factor, self.plane_means, 2, X=self.X)
+            if self.input_mode == 3:
+                ops.zoom_net_input_src(*img, *masks, self.zoom_factor, self.plane_means, 3, X=self.X2)
         return self.X
 
     def _run_winograd(self, name, cout, x, events=None, s2=True):

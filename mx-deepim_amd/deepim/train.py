@@ -82,6 +82,9 @@ def train_net(args):
         print("no checkpoint found ({}-{:04d}.params): seeded initialisation".format(config.network.pretrained, config.network.pretrained_epoch))
     arg_params = sym_instance.init_weights(config, arg_params, {}, seed=0)
 
+    if [tuple(int(v) for v in sc) for sc in config.SCALES] != [(480, 640)]:
+        raise NotImplementedError("training runs at SCALES [[480, 640]] only, got {}: another image size is built for the test path "
+                                  "(deepim/test.py) alone, training at it is out of scope".format(config.SCALES))
     B = int(config.TRAIN.BATCH_PAIRS)
     data = SyntheticPairs(config, args.num_pairs, B, device=device, rank=rank, world=world, equal_shards=True)
     # DIM_TRAIN_DTYPE=bf16: convolutions on the bf16 matrix pipe (BASELINE configs[2]); DIM_OVERLAP_ALLREDUCE=0: one flat all-reduce

@@ -21,8 +21,11 @@ class SyntheticPairs(object):
         self.classes = list(config.dataset.class_name)
         self.models = syn.make_models(seed=seed, n_models=len(self.classes), subdiv=subdiv)
         self.K = np.asarray(config.dataset.INTRINSIC_MATRIX, dtype=np.float32).reshape(3, 3)
-        self.render_machine = Render_Py(None, self.classes, self.K, zNear=config.dataset.ZNEAR, zFar=config.dataset.ZFAR, device=device,
-                                        meshes=self.models)
+        from deepim.symbols.deepIM_flownet import source_size
+
+        self.height, self.width = source_size(config)   # config.SCALES: the size of the pairs, K the camera of that image
+        self.render_machine = Render_Py(None, self.classes, self.K, width=self.width, height=self.height, zNear=config.dataset.ZNEAR,
+                                        zFar=config.dataset.ZFAR, device=device, meshes=self.models)
         self.batch_pairs, self.device, self.seed = int(batch_pairs), device, seed
         # occluded / lit training scenes (dataset.SYN_OCC_OBJECTS, SYN_OCC_MAX_RATE, SYN_LIGHT); all off = the batches of before
         self.occluders = int(config.dataset.get("SYN_OCC_OBJECTS", 0) or 0)
@@ -32,7 +35,8 @@ class SyntheticPairs(object):
         if self.lit:
             from lib.render_hip.render_py_light_multi_program import Render_Py_Light_MultiProgram
 
-            self.light_machine = Render_Py_Light_MultiProgram(self.classes, None, self.K, zNear=config.dataset.ZNEAR, zFar=config.dataset.ZFAR,
+            self.light_machine = Render_Py_Light_MultiProgram(self.classes, None, self.K, width=self.width, height=self.height,
+                                                              zNear=config.dataset.ZNEAR, zFar=config.dataset.ZFAR,
                                                               brightness_ratios=syn.LM_BRIGHTNESS_RATIOS, device=device,
                                                               meshes=[(v, None, t, f, tex) for v, t, f, tex in self.models])
         n_batches = int(num_pairs) // self.batch_pairs  # whole batches only

@@ -28,6 +28,8 @@ SIGNATURES = {
     "dim_zoom_planes": (I, [P, P, P, I, I, I, I, I, I, I, P, I, P]),
     "dim_zoom_net_input": (I, [P, P, P, P, P, P, I, I, I, P, P, P, P, P, P]),
     "dim_zoom_net_input_ex": (I, [P, P, P, P, P, P, I, I, I, P, I, P]),
+    "dim_zoom_planes_src": (I, [P, P, P, I, I, I, I, I, I, I, I, P, P]),
+    "dim_zoom_net_input_src": (I, [P, P, P, P, P, P, I, I, I, I, I, P, I, P, P, P, P, P]),
     "dim_zoom_trans": (I, [P, P, P, I, I, P]),
     "dim_se3_compose": (I, [P, P, P, P, I, I, P, P, P]),
     "dim_se3_delta": (I, [P, P, P, P, I, I, P, P, P]),
@@ -62,6 +64,7 @@ SIGNATURES = {
     "dim_bop_errors": (I, [P, P, P, P, I, P, P, P, P, P, P, I, I, I, P, P, P, P, P]),
     "dim_refiner_create": (I, [P, P, P, P, I, P]),
     "dim_refiner_create_cls": (I, [P, P, I, P, P, I, P]),
+    "dim_refiner_create_src": (I, [P, P, I, P, P, I, P]),
     "dim_refiner_run": (I, [P, P, P, P, P, P, P, P, P, P, P]),
     "dim_refiner_run_k": (I, [P, P, P, P, P, P, P, P, P, P, P, P]),
     "dim_refiner_destroy": (I, [P]),

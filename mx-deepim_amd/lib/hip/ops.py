@@ -92,6 +92,55 @@ def zoom_net_input_ex(img_obs, img_ren, extra_obs, extra_ren, zf, plane_means3, 
     return X
 
 
+def _net_size(out, net_size, what):
+    """the network size (Hn, Wn) of a `_src` sampler: the explicit argument, else the output tensor's (`what` = its rows, cols axes)"""
+    if net_size is None:
+        if out is None:
+            raise ValueError("pass the output tensor or net_size=(Hn, Wn)")
+        return int(out.shape[what[0]]), int(out.shape[what[1]])
+    return int(net_size[0]), int(net_size[1])
+
+
+def _same_shape(t, shape, name):
+    if t is not None and tuple(t.shape) != tuple(shape):
+        raise ValueError("{} must have shape {}, got {}".format(name, tuple(shape), tuple(t.shape)))
+
+
+def zoom_planes_src(x, zf, pre=0, post=0, add3=None, out=None, net_size=None):
+    """dim_zoom_planes_src: x (B,C,Hs,Ws) sampled into out (B,C,Hn,Wn), forward direction only.  The source size is x's; the network
+    size out's, or net_size=(Hn, Wn) when out is allocated here."""
+    B, C, Hs, Ws = x.shape
+    Hn, Wn = _net_size(out, net_size, (2, 3))
+    out = out if out is not None else _new((B, C, Hn, Wn), x)
+    _same_shape(out, (B, C, Hn, Wn), "out")
+    _same_shape(zf, (B, 4), "zoom_factor")
+    keep, ap = host_f32(add3, 3) if add3 is not None else (None, None)
+    check(lib().dim_zoom_planes_src(dptr(x, f32), dptr(zf, f32), dptr(out, f32), B, C, Hs, Ws, Hn, Wn, pre, post, ap, current_stream()))
+    return out
+
+
+def zoom_net_input_src(img_obs, img_ren, extra_obs, extra_ren, zf, plane_means3, mode=0, X=None, nchw_out=None, net_size=None):
+    """dim_zoom_net_input_src: the blobs (B,.,Hs,Ws) sampled into X (B,Hn,Wn,8), modes as zoom_net_input_ex.  The source size is the
+    blobs'; the network size X's, or net_size=(Hn, Wn) when X is allocated here.  nchw_out (mode 0): the four (B,.,Hn,Wn) op outputs."""
+    B, _, Hs, Ws = img_obs.shape
+    Hn, Wn = _net_size(X, net_size, (1, 2))
+    X = X if X is not None else _new((B, Hn, Wn, 8), img_obs)
+    _same_shape(X, (B, Hn, Wn, 8), "X")
+    _same_shape(zf, (B, 4), "zoom_factor")
+    _same_shape(img_obs, (B, 3, Hs, Ws), "image_observed")
+    _same_shape(img_ren, (B, 3, Hs, Ws), "image_rendered")
+    _same_shape(extra_obs, (B, 1, Hs, Ws), "the observed extra plane")
+    _same_shape(extra_ren, (B, 1, Hs, Ws), "the rendered extra plane")
+    z = nchw_out if nchw_out is not None else (None, None, None, None)
+    for t, c in zip(z, (3, 3, 1, 1)):
+        _same_shape(t, (B, c, Hn, Wn), "an NCHW output")
+    keep, mp = host_f32(plane_means3, 3)
+    check(lib().dim_zoom_net_input_src(dptr(img_obs, f32), dptr(img_ren, f32), dptr(extra_obs, f32), dptr(extra_ren, f32), dptr(zf, f32),
+                                       dptr(X, f32), B, Hs, Ws, Hn, Wn, mp, int(mode), dptr(z[0], f32), dptr(z[1], f32), dptr(z[2], f32),
+                                       dptr(z[3], f32), current_stream()))
+    return X
+
+
 def zoom_trans(zf, t, mode, out=None):
     B = t.shape[0]
     out = out if out is not None else torch.empty_like(t)

@@ -1,4 +1,4 @@
-"""ctypes face of the resident-loop C entry points (include/deepim_hip.h: dim_refiner_create / _create_cls / _run / _run_k / _destroy).
+"""ctypes face of the resident-loop C entry points (include/deepim_hip.h: dim_refiner_create / _create_cls / _create_src / _run / _run_k / _destroy).
 
 This is what a host WITHOUT torch binds (INTEGRATION.md shows the same struct for C / cgo callers); torch is used here only to own
 the device memory of the arguments, exactly as in the rest of lib/hip."""
@@ -54,7 +54,9 @@ class CRefiner(object):
         if tuple(self.params["rot_weight"].shape) != (4 * K, 256) or tuple(self.params["trans_weight"].shape) != (3 * K, 256):
             raise ValueError("rot_weight {} / trans_weight {}: network.REGRESSOR_NUM = {} needs ({}, 256) / ({}, 256)".format(
                 tuple(self.params["rot_weight"].shape), tuple(self.params["trans_weight"].shape), K, 4 * K, 3 * K))
-        if K > 1:   # one rot / trans head per class: run() picks each pair's by the class_index it receives
+        if (d.H, d.W) != (480, 640):   # a camera image of another (4:3) size: the blobs and the renders at it, the network input at 480x640
+            check(lib().dim_refiner_create_src(ctypes.byref(self._h), ctypes.byref(d), K, cnames, cptrs, len(names), current_stream()))
+        elif K > 1:   # one rot / trans head per class: run() picks each pair's by the class_index it receives
             check(lib().dim_refiner_create_cls(ctypes.byref(self._h), ctypes.byref(d), K, cnames, cptrs, len(names), current_stream()))
         else:
             check(lib().dim_refiner_create(ctypes.byref(self._h), ctypes.byref(d), cnames, cptrs, len(names), current_stream()))

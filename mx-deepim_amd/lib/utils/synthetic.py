@@ -114,12 +114,15 @@ def perturb_pose(rng, pose, angle_std=15.0, angle_max=45.0, xy_std=0.01, z_std=0
     return out.astype(np.float32)
 
 
-def sample_pairs(seed, B, n_classes=1, **noise):
+def sample_pairs(seed, B, n_classes=1, frame=None, **noise):
     """-> class_index (B,) int32, pose_gt (B,3,4), pose_init (B,3,4), background seeds.
+    frame: None (the 640x480 LINEMOD camera) or (K, W, H) of another image size (config.SCALES): the same draws place the object in
+    that frame, the margin scaled with its width.
     noise: keyword arguments of perturb_pose (angle_std, angle_max, xy_std, z_std) for pairs with another initial error."""
     rng = np.random.default_rng(seed)
     cls = rng.integers(0, n_classes, size=B).astype(np.int32)
-    gt = np.stack([sample_gt_pose(rng) for _ in range(B)])
+    where = {} if frame is None else dict(K=np.asarray(frame[0], np.float64).reshape(3, 3), W=frame[1], H=frame[2], margin=120.0 * frame[1] / 640.0)
+    gt = np.stack([sample_gt_pose(rng, **where) for _ in range(B)])
     init = np.stack([perturb_pose(rng, gt[i], **noise) for i in range(B)])
     return cls, gt, init
 
@@ -167,8 +170,9 @@ def build_device_batch(render_machine, B, seed, n_classes=1, pixel_means=PIXEL_M
     from lib.hip import ops
 
     d = torch.device(device)
-    cls, gt, init = sample_pairs(seed, B, n_classes, **(noise or {}))
     H, W = render_machine.height, render_machine.width
+    frame = None if (H, W) == (480, 640) else (render_machine.K, W, H)   # another image size (config.SCALES): its own camera
+    cls, gt, init = sample_pairs(seed, B, n_classes, frame=frame, **(noise or {}))
     pm = plane_means(pixel_means)
     cls_t = torch.from_numpy(cls).to(d)
     img = torch.empty((B, 3, H, W), device=d)
