@@ -111,6 +111,24 @@ int dim_zoom_net_input_src(const float* image_observed, const float* image_rende
                            const float* zoom_factor, float* X_nhwc8, int B, int Hs, int Ws, int Hn, int Wn, const float* means3, int mode,
                            float* z_image_observed, float* z_image_rendered, float* z_mask_observed, float* z_mask_rendered, void* stream);
 
+/* The `_src` samplers with an area filter for windows that shrink the source.  Per pair and per axis, with the
+ * window's size w = |wx| or |wy| of zoom_factor[b]:
+ *   step = w * f32((S-1)/(N-1))                       source pixels per network pixel (S, N: source and network extent of the axis)
+ *   n    = min(max(floor(step + 0.5), 1), max_taps)   sub-samples (a NaN step gives 1, an infinite one max_taps)
+ *   o_k  = f32((k + 0.5)/n - 0.5), k < n              their offsets in network pixels (0 for n = 1)
+ * Every output is the mean of the n_y x n_x bilinear samples at the target coordinates -1 + (j + o_k) 2/(N-1): summed with ky outer and
+ * kx inner, one float32 addition each, then one division by n_x n_y; `- add`, the rounding and / 255 follow the mean.  Sub-samples
+ * outside the source plane are zeros (no clamp).  Where n_x = n_y = 1 every bit equals the `_src` entry point.  The argument lists and
+ * checks are the `_src` ones plus max_taps in 1..8.
+ * dim_zoom_area_taps writes the (n_x, n_y) the two samplers use into taps_xy, device (B,2) int32. */
+int dim_zoom_planes_area(const float* x, const float* zoom_factor, float* y, int B, int C, int Hs, int Ws, int Hn, int Wn, int pre, int post,
+                         const float* add3, int max_taps, void* stream);
+int dim_zoom_net_input_area(const float* image_observed, const float* image_rendered, const float* extra_observed, const float* extra_rendered,
+                            const float* zoom_factor, float* X_nhwc8, int B, int Hs, int Ws, int Hn, int Wn, const float* means3, int mode,
+                            float* z_image_observed, float* z_image_rendered, float* z_mask_observed, float* z_mask_rendered, int max_taps,
+                            void* stream);
+int dim_zoom_area_taps(const float* zoom_factor, int B, int Hs, int Ws, int Hn, int Wn, int max_taps, int* taps_xy, void* stream);
+
 /* ZoomTrans (zoom_trans.py:22-76): mode 0 copy, 1 (dx,dy)/wx, 2 (dx,dy)*wx */
 int dim_zoom_trans(const float* zoom_factor, const float* in, float* out, int B, int mode, void* stream);
 
@@ -893,6 +911,10 @@ int dim_refiner_create_cls(dim_refiner** out, const dim_refiner_desc* desc, int 
  * dim_refiner_run / _run_k take the object as they take the others; their blobs are then (B,.,H,W) of the desc. */
 int dim_refiner_create_src(dim_refiner** out, const dim_refiner_desc* desc, int n_regressors, const char* const* param_names,
                            const float* const* param_ptrs, int n_params, void* stream);
+/* The zoom filter of a refiner made by any of the create functions: max_taps 0 or 1 = one bilinear sample per network pixel (the
+ * default), 2..8 = the area filter (dim_zoom_net_input_area with that max_taps, also for 480 x 640 blobs, whose windows may be larger
+ * than the frame).  Call it before the first dim_refiner_run / _run_k (and so before a graph capture of one): later it is refused. */
+int dim_refiner_set_zoom_filter(dim_refiner* r, int max_taps);
 int dim_refiner_run(dim_refiner* r, const float* image_observed, const float* image_rendered, const float* mask_observed,
                     const float* mask_rendered, const float* src_pose, const int* class_index, float* poses_iter, float* se3_iter,
                     int* status_iter, void* stream);

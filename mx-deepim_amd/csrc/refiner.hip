@@ -45,6 +45,8 @@ enum { kNetH = 480, kNetW = 640 };   // the network input (the encoder's first m
 struct dim_refiner {
   dim_refiner_desc d;   // d.H x d.W: the size of the blobs, the renders, the masks and the boxes
   bool src;             // created by dim_refiner_create_src: the zoom samples d.H x d.W planes into the kNetH x kNetW input
+  int zoom_max_taps;    // dim_refiner_set_zoom_filter: 0 = one bilinear sample, 2..8 = the area filter
+  bool ran;             // a run has enqueued the loop (possibly into a graph): the zoom filter stays what it is
   int n_regressors;   // 1: one rot / trans head; d.n_classes: one per class (rot (4K,256), trans (3K,256)), picked by class_index
   std::vector<void*> allocs;
   LayerPlan L[10];
@@ -78,6 +80,14 @@ int dim_refiner_destroy(dim_refiner* r) {
   if (!r) return DIM_OK;
   for (void* p : r->allocs) (void)hipFree(p);
   delete r;
+  return DIM_OK;
+}
+
+int dim_refiner_set_zoom_filter(dim_refiner* r, int max_taps) {
+  DIM_REQUIRE(r, "null pointer");
+  DIM_REQUIRE(max_taps >= 0 && max_taps <= 8, "max_taps must be 0..8 (0, 1: bilinear; 2..8: area filter), got %d", max_taps);
+  DIM_REQUIRE(!r->ran, "dim_refiner_set_zoom_filter must be called before the first dim_refiner_run");
+  r->zoom_max_taps = max_taps >= 2 ? max_taps : 0;
   return DIM_OK;
 }
 
@@ -116,6 +126,8 @@ static int refiner_create(dim_refiner** out, const dim_refiner_desc* desc, int n
   dim_refiner* r = new dim_refiner();
   r->d = d;
   r->src = src;
+  r->zoom_max_taps = 0;
+  r->ran = false;
   r->n_regressors = n_regressors;
   for (int c = 0; c < 3; ++c) r->plane_means[c] = d.pixel_means_bgr[2 - c];  // blob plane c holds BGR channel 2 - c
   const int B = d.B;
@@ -234,6 +246,7 @@ int dim_refiner_run_k(dim_refiner* r, const float* image_observed, const float* 
               "null pointer");
   const dim_refiner_desc& d = r->d;
   const int B = d.B, H = d.H, W = d.W, T = d.test_iter;
+  r->ran = true;
   int rc;
 #define TRY(x) \
   if ((rc = (x)) != DIM_OK) return rc;
@@ -257,7 +270,10 @@ int dim_refiner_run_k(dim_refiner* r, const float* image_observed, const float* 
       bb_ren = r->bbox_ren;
     }
     TRY(dim_zoom_factor(bb_obs, bb_ren, pose, d.K9, B, H, W, r->zoom_factor, status, stream));
-    if (r->src) {
+    if (r->zoom_max_taps >= 2) {
+      TRY(dim_zoom_net_input_area(image_observed, img_ren, m_obs, m_ren, r->zoom_factor, r->X, B, H, W, kNetH, kNetW, r->plane_means, 0,
+                                  nullptr, nullptr, nullptr, nullptr, r->zoom_max_taps, stream));
+    } else if (r->src) {
       TRY(dim_zoom_net_input_src(image_observed, img_ren, m_obs, m_ren, r->zoom_factor, r->X, B, H, W, kNetH, kNetW, r->plane_means, 0, nullptr,
                                  nullptr, nullptr, nullptr, stream));
     } else {

@@ -10,6 +10,8 @@
 //   ZoomDepth           deepim/operator_py/zoom_depth.py:24-50
 // The planes that are read may have another size (the camera image's, config.SCALES) than the planes that are written (the network
 // input): dim_zoom_planes_src / dim_zoom_net_input_src, the same kernel bodies with two sizes.
+// Where the zoom window shrinks the source, dim_zoom_planes_area / dim_zoom_net_input_area average several bilinear samples per output
+// pixel (the same bodies with the template flag AREA).
 // The sampling grid is never materialised.  HBM-bound: every input plane is read once
 // (neighbouring output pixels share source texels through L1/L2), every output written once.
 #include "common.h"
@@ -178,7 +180,9 @@ struct Tap {
 // Two sizes (GridGenerator(target_shape = (Hn, Wn)) + BilinearSampler on an H x W plane): the target coordinates x_t run over the
 // Hn x Wn grid the thread indices (y, x) belong to; x_real, the corner validity, the clamps and the offsets belong to the H x W plane
 // that is read.  The same-size entry points pass Hn = H, Wn = W and compile to what they were.
-__device__ inline Tap make_tap(const Affine& a, int y, int x, int H, int W, int Hn, int Wn) {
+// (y, x): the position on the Hn x Wn grid, a pixel index (int) or, for the area filter, a pixel index plus a sub-sample offset (float).
+template <class G>
+__device__ inline Tap make_tap(const Affine& a, G y, G x, int H, int W, int Hn, int Wn) {
   const float sx = (float)(2.0 / (double)(Wn - 1)), sy = (float)(2.0 / (double)(Hn - 1));
   float xt = __fadd_rn(-1.f, __fmul_rn((float)x, sx));
   float yt = __fadd_rn(-1.f, __fmul_rn((float)y, sy));
@@ -200,6 +204,63 @@ __device__ inline Tap make_tap(const Affine& a, int y, int x, int H, int W, int 
   t.o00 = yc0 * W + xc0; t.o01 = yc0 * W + xc1; t.o10 = yc1 * W + xc0; t.o11 = yc1 * W + xc1;
   t.v00 = vy0 && vx0; t.v01 = vy0 && vx1; t.v10 = vy1 && vx0; t.v11 = vy1 && vx1;
   return t;
+}
+
+// ------------------------------------------------------------------ area filter
+// A window that shrinks the source (more than one source pixel per network pixel) is sampled n_y x n_x times per network pixel, at
+// sub-pixel offsets of the network grid, and the bilinear samples are averaged.  Per axis:
+//   step = |w| * f32((S - 1) / (N - 1))     source pixels per network pixel (the quotient in double, rounded once: area_ratio)
+//   n    = min(max(floor(step + 0.5), 1), max_taps)     (fmaxf first: a NaN step gives 1, an infinite one max_taps)
+//   o_k  = f32((k + 0.5) / n - 0.5), k < n            (in double, rounded once; exactly 0 for n = 1)
+enum { kAreaMaxTaps = 8 };
+
+struct AreaOffsets {
+  float o[kAreaMaxTaps + 1][kAreaMaxTaps];
+};
+
+constexpr AreaOffsets make_area_offsets() {
+  AreaOffsets t{};
+  for (int n = 1; n <= kAreaMaxTaps; ++n)
+    for (int k = 0; k < n; ++k) t.o[n][k] = (float)(((double)k + 0.5) / (double)n - 0.5);
+  return t;
+}
+
+__constant__ const AreaOffsets kAreaOffsets = make_area_offsets();
+
+static inline float area_ratio(int S, int N) { return (float)((double)(S - 1) / (double)(N - 1)); }
+
+struct AreaTaps {
+  int nx, ny;
+};
+
+__device__ inline int area_taps_axis(float w, float ratio, int max_taps) {
+  const float step = __fmul_rn(fabsf(w), ratio);
+  return (int)fminf(fmaxf(floorf(__fadd_rn(step, 0.5f)), 1.f), (float)max_taps);
+}
+
+// zf = zoom_factor + 4 b.  The one copy of the rule: the sampling kernels and dim_zoom_area_taps call it.
+__device__ inline AreaTaps area_taps(const float* zf, float ratio_x, float ratio_y, int max_taps) {
+  AreaTaps n;
+  n.nx = area_taps_axis(zf[0], ratio_x, max_taps);
+  n.ny = area_taps_axis(zf[1], ratio_y, max_taps);
+  return n;
+}
+
+// the same for a workgroup of a sampling kernel, whose b = blockIdx.z is uniform: trip counts in scalar registers
+__device__ inline AreaTaps area_taps_uniform(const float* zf, float ratio_x, float ratio_y, int max_taps) {
+  AreaTaps n = area_taps(zf, ratio_x, ratio_y, max_taps);
+  n.nx = __builtin_amdgcn_readfirstlane(n.nx);
+  n.ny = __builtin_amdgcn_readfirstlane(n.ny);
+  return n;
+}
+
+__global__ void zoom_area_taps_kernel(const float* __restrict__ zoom_factor, int B, float ratio_x, float ratio_y, int max_taps,
+                                      int* __restrict__ taps_xy) {
+  int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  const AreaTaps n = area_taps(zoom_factor + 4 * b, ratio_x, ratio_y, max_taps);
+  taps_xy[2 * b + 0] = n.nx;
+  taps_xy[2 * b + 1] = n.ny;
 }
 
 enum { PRE_NONE = 0, PRE_BIN02 = 1 };                        // mask > 0.2 -> {0,1} before sampling
@@ -237,9 +298,26 @@ __device__ inline float sample(const float* plane, const Tap& t, float add) {
 // Generic NCHW plane sampler: y[b,c] = post( sample(pre(x[b,c] + add[c])) - add[c] ) * scale(b)
 // scale_mode: 0 none, 1 divide by zoom_factor[b,0], 2 multiply by zoom_factor[b,0]   (ZoomFlow)
 // x planes are H x W, y planes Hn x Wn; one thread per pixel of y.  (The inverse factor is defined between planes of one size only.)
-template <int PRE, int POST>
+// The mean of the n.ny x n.nx sub-samples of one plane at network pixel (py, px): ky outer, kx inner; the first sample initialises the
+// sum (a -0 survives n = 1), every later one is one addition, then one division.
+template <int PRE>
+__device__ inline float sample_area(const float* plane, const Affine& a, int py, int px, int H, int W, int Hn, int Wn, const AreaTaps& n,
+                                    float add) {
+  float acc = 0.f;
+  for (int ky = 0; ky < n.ny; ++ky)
+    for (int kx = 0; kx < n.nx; ++kx) {
+      const Tap t = make_tap(a, __fadd_rn((float)py, kAreaOffsets.o[n.ny][ky]), __fadd_rn((float)px, kAreaOffsets.o[n.nx][kx]), H, W, Hn, Wn);
+      const float r = sample<PRE>(plane, t, add);
+      acc = (ky | kx) == 0 ? r : __fadd_rn(acc, r);
+    }
+  return __fdiv_rn(acc, (float)(n.nx * n.ny));
+}
+
+// AREA: forward only (inverse, scale_mode = 0); max_taps and the two size ratios (area_ratio) select the sub-samples per pair
+template <int PRE, int POST, bool AREA = false>
 __device__ inline void zoom_planes_body(const float* __restrict__ x, const float* __restrict__ zoom_factor, float* __restrict__ y, int C,
-                                        int H, int W, int Hn, int Wn, int inverse, float add0, float add1, float add2, int scale_mode) {
+                                        int H, int W, int Hn, int Wn, int inverse, float add0, float add1, float add2, int scale_mode,
+                                        int max_taps = 1, float ratio_x = 1.f, float ratio_y = 1.f) {
   const int b = blockIdx.z;
   const int px = blockIdx.x * blockDim.x + threadIdx.x;
   const int py = blockIdx.y;
@@ -248,10 +326,13 @@ __device__ inline void zoom_planes_body(const float* __restrict__ x, const float
   const Tap t = make_tap(a, py, px, H, W, Hn, Wn);
   const long plane = (long)H * W, plane_n = (long)Hn * Wn;
   const float zwx = zoom_factor[4 * b];
+  AreaTaps n = {1, 1};
+  if (AREA) n = area_taps_uniform(zoom_factor + 4 * b, ratio_x, ratio_y, max_taps);
   for (int c = 0; c < C; ++c) {
     float add = c == 0 ? add0 : (c == 1 ? add1 : add2);
     if (C > 3) add = 0.f;
-    float v = sample<PRE>(x + ((long)b * C + c) * plane, t, add);
+    float v = AREA ? sample_area<PRE>(x + ((long)b * C + c) * plane, a, py, px, H, W, Hn, Wn, n, add)
+                   : sample<PRE>(x + ((long)b * C + c) * plane, t, add);
     v = __fsub_rn(v, add);
     if (POST == POST_ROUND) v = mx_round(v);
     if (POST == POST_ROUND_M045) v = mx_round(__fsub_rn(v, 0.45f));
@@ -276,6 +357,15 @@ __global__ __launch_bounds__(256) void zoom_planes_src_kernel(const float* __res
   zoom_planes_body<PRE, POST>(x, zoom_factor, y, C, Hs, Ws, Hn, Wn, 0, add0, add1, add2, 0);
 }
 
+// zoom_planes_src_kernel with the area filter
+template <int PRE, int POST>
+__global__ __launch_bounds__(256) void zoom_planes_area_kernel(const float* __restrict__ x, const float* __restrict__ zoom_factor,
+                                                               float* __restrict__ y, int C, int Hs, int Ws, int Hn, int Wn,
+                                                               float add0, float add1, float add2, int max_taps, float ratio_x,
+                                                               float ratio_y) {
+  zoom_planes_body<PRE, POST, true>(x, zoom_factor, y, C, Hs, Ws, Hn, Wn, 0, add0, add1, add2, 0, max_taps, ratio_x, ratio_y);
+}
+
 // Fused network input (the test/train graph's Concat, deepIM_flownet.py:53-60):
 //   X[b, y, x, 0:3] = zoom(image_observed)/255, [3:6] = zoom(image_rendered)/255,
 //   X[.., 6] = round(zoom(mask_observed)), X[.., 7] = round(zoom(bin02(mask_rendered)))   (NHWC, 8 ch)
@@ -284,12 +374,60 @@ __global__ __launch_bounds__(256) void zoom_planes_src_kernel(const float* __res
 // zero too); MODE 2: no masks, depth_observed / depth_rendered in their place: plain bilinear samples (ZoomDepth, zoom_depth.py:24-50)
 // divided by 255 like the images (deepIM_flownet.py:33-51)
 // The input planes are H x W (the source size), X and the NCHW copies Hn x Wn (the network size); one thread per pixel of X.
+// The area filter's lanes: ra[i] = the mean over the n_y x n_x sub-samples of lane i's sample(pre(x) + mean), before `- mean` and the
+// lane's rounding or / 255 (sample_area's order and arithmetic).  ra[0:3] image_observed, ra[3:6] image_rendered (not MODE 3), ra[6],
+// ra[7] the two extra planes (not MODE 1; the rendered mask binarised in MODEs 0 and 3).  The samples of all lanes at one sub-sample
+// share its tap, and their loads (sample's are unconditional) are all issued before the first is used.
 template <int MODE>
+__device__ inline void net_input_area_lanes(const float* io, const float* ir, const float* eo, const float* er, long plane, const Affine& a,
+                                            int py, int px, int H, int W, int Hn, int Wn, const AreaTaps& n, float m0, float m1, float m2,
+                                            float* ra) {
+  // the lanes' samples at one tap (a lane the MODE does not read stays 0)
+  auto lanes = [&](const Tap& t, float* s) {
+    if (MODE != 3) {
+      s[0] = sample<PRE_NONE>(io, t, m0);
+      s[1] = sample<PRE_NONE>(io + plane, t, m1);
+      s[2] = sample<PRE_NONE>(io + 2 * plane, t, m2);
+      s[3] = sample<PRE_NONE>(ir, t, m0);
+      s[4] = sample<PRE_NONE>(ir + plane, t, m1);
+      s[5] = sample<PRE_NONE>(ir + 2 * plane, t, m2);
+    }
+    if (MODE != 1) {
+      s[6] = sample<PRE_NONE>(eo, t, 0.f);
+      s[7] = MODE == 2 ? sample<PRE_NONE>(er, t, 0.f) : sample<PRE_BIN02>(er, t, 0.f);
+    }
+  };
+  if (n.nx * n.ny == 1) {
+    // A pair whose window magnifies (a uniform branch: n is per pair).  The general path below gives these bits too -- offset 0, a
+    // sum of one, a division by 1 -- but as a loop it keeps fewer loads in flight: measured 94.5 against 66.8 us per launch for
+    // the one-sample kernel at 960x1280.  Straight-line code with all loads issued together, as in the bilinear kernels.
+    lanes(make_tap(a, py, px, H, W, Hn, Wn), ra);
+    return;
+  }
+  for (int ky = 0; ky < n.ny; ++ky)
+    for (int kx = 0; kx < n.nx; ++kx) {
+      const Tap t = make_tap(a, __fadd_rn((float)py, kAreaOffsets.o[n.ny][ky]), __fadd_rn((float)px, kAreaOffsets.o[n.nx][kx]), H, W, Hn, Wn);
+      float s[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+      lanes(t, s);
+      const bool first = (ky | kx) == 0;
+#pragma unroll
+      for (int i = 0; i < 8; ++i) ra[i] = first ? s[i] : __fadd_rn(ra[i], s[i]);
+    }
+  const float count = (float)(n.nx * n.ny);
+#pragma unroll
+  for (int i = 0; i < 8; ++i) ra[i] = __fdiv_rn(ra[i], count);
+}
+
+// AREA: every lane's one sample is replaced by net_input_area_lanes' mean; what follows the sample (- mean, rounding, / 255, the lane
+// order, the NCHW copies) is this one body.  (Without AREA the statements are in the order they had before the flag existed, so that
+// the bilinear kernels compile to what they were.)
+template <int MODE, bool AREA = false>
 __device__ inline void zoom_net_input_body(const float* __restrict__ img_obs, const float* __restrict__ img_ren,
                                            const float* __restrict__ mask_obs, const float* __restrict__ mask_ren,
                                            const float* __restrict__ zoom_factor, float* __restrict__ X, int H, int W, int Hn, int Wn,
                                            float m0, float m1, float m2, float* __restrict__ z_img_obs, float* __restrict__ z_img_ren,
-                                           float* __restrict__ z_mask_obs, float* __restrict__ z_mask_ren) {
+                                           float* __restrict__ z_mask_obs, float* __restrict__ z_mask_ren, int max_taps = 1,
+                                           float ratio_x = 1.f, float ratio_y = 1.f) {
   const int b = blockIdx.z;
   const int px = blockIdx.x * blockDim.x + threadIdx.x;
   const int py = blockIdx.y;
@@ -297,9 +435,14 @@ __device__ inline void zoom_net_input_body(const float* __restrict__ img_obs, co
   const Affine a = load_affine(zoom_factor + 4 * b, false, H, W);
   const Tap t = make_tap(a, py, px, H, W, Hn, Wn);
   const long plane = (long)H * W, plane_n = (long)Hn * Wn;
+  float ra[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  if (AREA)
+    net_input_area_lanes<MODE>(img_obs + (long)b * 3 * plane, img_ren + (long)b * 3 * plane, mask_obs + (long)b * plane,
+                               mask_ren + (long)b * plane, plane, a, py, px, H, W, Hn, Wn,
+                               area_taps_uniform(zoom_factor + 4 * b, ratio_x, ratio_y, max_taps), m0, m1, m2, ra);
   if (MODE == 3) {   // the two mask lanes alone (second 8-lane group of the 10-channel first layer): [mask_obs, mask_ren, 0 x 6]
-    const float mo = mx_round(sample<PRE_NONE>(mask_obs + (long)b * plane, t, 0.f));
-    const float mr = mx_round(sample<PRE_BIN02>(mask_ren + (long)b * plane, t, 0.f));
+    const float mo = mx_round(AREA ? ra[6] : sample<PRE_NONE>(mask_obs + (long)b * plane, t, 0.f));
+    const float mr = mx_round(AREA ? ra[7] : sample<PRE_BIN02>(mask_ren + (long)b * plane, t, 0.f));
     float4* dst = reinterpret_cast<float4*>(X + ((long)b * plane_n + (long)py * Wn + px) * 8);
     dst[0] = make_float4(mo, mr, 0.f, 0.f);
     dst[1] = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -308,18 +451,18 @@ __device__ inline void zoom_net_input_body(const float* __restrict__ img_obs, co
   const float* io = img_obs + (long)b * 3 * plane;
   const float* ir = img_ren + (long)b * 3 * plane;
   float v[8];
-  v[0] = __fsub_rn(sample<PRE_NONE>(io, t, m0), m0);
-  v[1] = __fsub_rn(sample<PRE_NONE>(io + plane, t, m1), m1);
-  v[2] = __fsub_rn(sample<PRE_NONE>(io + 2 * plane, t, m2), m2);
-  v[3] = __fsub_rn(sample<PRE_NONE>(ir, t, m0), m0);
-  v[4] = __fsub_rn(sample<PRE_NONE>(ir + plane, t, m1), m1);
-  v[5] = __fsub_rn(sample<PRE_NONE>(ir + 2 * plane, t, m2), m2);
+  v[0] = __fsub_rn(AREA ? ra[0] : sample<PRE_NONE>(io, t, m0), m0);
+  v[1] = __fsub_rn(AREA ? ra[1] : sample<PRE_NONE>(io + plane, t, m1), m1);
+  v[2] = __fsub_rn(AREA ? ra[2] : sample<PRE_NONE>(io + 2 * plane, t, m2), m2);
+  v[3] = __fsub_rn(AREA ? ra[3] : sample<PRE_NONE>(ir, t, m0), m0);
+  v[4] = __fsub_rn(AREA ? ra[4] : sample<PRE_NONE>(ir + plane, t, m1), m1);
+  v[5] = __fsub_rn(AREA ? ra[5] : sample<PRE_NONE>(ir + 2 * plane, t, m2), m2);
   if (MODE == 0) {
-    v[6] = mx_round(sample<PRE_NONE>(mask_obs + (long)b * plane, t, 0.f));
-    v[7] = mx_round(sample<PRE_BIN02>(mask_ren + (long)b * plane, t, 0.f));
+    v[6] = mx_round(AREA ? ra[6] : sample<PRE_NONE>(mask_obs + (long)b * plane, t, 0.f));
+    v[7] = mx_round(AREA ? ra[7] : sample<PRE_BIN02>(mask_ren + (long)b * plane, t, 0.f));
   } else if (MODE == 2) {
-    v[6] = __fdiv_rn(sample<PRE_NONE>(mask_obs + (long)b * plane, t, 0.f), 255.f);
-    v[7] = __fdiv_rn(sample<PRE_NONE>(mask_ren + (long)b * plane, t, 0.f), 255.f);
+    v[6] = __fdiv_rn(AREA ? ra[6] : sample<PRE_NONE>(mask_obs + (long)b * plane, t, 0.f), 255.f);
+    v[7] = __fdiv_rn(AREA ? ra[7] : sample<PRE_NONE>(mask_ren + (long)b * plane, t, 0.f), 255.f);
   } else {
     v[6] = v[7] = 0.f;
   }
@@ -360,6 +503,19 @@ __global__ __launch_bounds__(256) void zoom_net_input_src_kernel(const float* __
                                                                  float* __restrict__ z_mask_obs, float* __restrict__ z_mask_ren) {
   zoom_net_input_body<MODE>(img_obs, img_ren, mask_obs, mask_ren, zoom_factor, X, Hs, Ws, Hn, Wn, m0, m1, m2, z_img_obs, z_img_ren,
                             z_mask_obs, z_mask_ren);
+}
+
+// zoom_net_input_src_kernel with the area filter
+template <int MODE>
+__global__ __launch_bounds__(256) void zoom_net_input_area_kernel(const float* __restrict__ img_obs, const float* __restrict__ img_ren,
+                                                                  const float* __restrict__ mask_obs, const float* __restrict__ mask_ren,
+                                                                  const float* __restrict__ zoom_factor, float* __restrict__ X,
+                                                                  int Hs, int Ws, int Hn, int Wn, float m0, float m1, float m2,
+                                                                  float* __restrict__ z_img_obs, float* __restrict__ z_img_ren,
+                                                                  float* __restrict__ z_mask_obs, float* __restrict__ z_mask_ren,
+                                                                  int max_taps, float ratio_x, float ratio_y) {
+  zoom_net_input_body<MODE, true>(img_obs, img_ren, mask_obs, mask_ren, zoom_factor, X, Hs, Ws, Hn, Wn, m0, m1, m2, z_img_obs, z_img_ren,
+                                  z_mask_obs, z_mask_ren, max_taps, ratio_x, ratio_y);
 }
 
 }  // namespace dim
@@ -454,8 +610,9 @@ int dim_zoom_net_input_ex(const float* image_observed, const float* image_render
   return check_launch("zoom_net_input_ex");
 }
 
-int dim_zoom_planes_src(const float* x, const float* zoom_factor, float* y, int B, int C, int Hs, int Ws, int Hn, int Wn, int pre, int post,
-                        const float* add3, void* stream) {
+// dim_zoom_planes_src (max_taps 0: one bilinear sample) and dim_zoom_planes_area (max_taps 1..8): one set of checks, one grid
+static int zoom_planes_src_launch(const char* what, const float* x, const float* zoom_factor, float* y, int B, int C, int Hs, int Ws, int Hn,
+                                  int Wn, int pre, int post, const float* add3, int max_taps, void* stream) {
   if (B == 0) return DIM_OK;  // empty batch: nothing to do, pointers may be NULL
   DIM_REQUIRE(x && zoom_factor && y, "null pointer");
   DIM_REQUIRE(Hs >= 2 && Ws >= 2 && Hn >= 2 && Wn >= 2, "source %d x %d and network %d x %d sizes must be >= 2", Hs, Ws, Hn, Wn);
@@ -466,8 +623,15 @@ int dim_zoom_planes_src(const float* x, const float* zoom_factor, float* y, int 
   float a0 = add3 ? add3[0] : 0.f, a1 = add3 && C > 1 ? add3[1] : 0.f, a2 = add3 && C > 2 ? add3[2] : 0.f;
   dim3 grid(ceil_div(Wn, 256), Hn, B), block(256);
   hipStream_t st = as_stream(stream);
-#define DIM_ZP(PRE, POST) \
-  hipLaunchKernelGGL((zoom_planes_src_kernel<PRE, POST>), grid, block, 0, st, x, zoom_factor, y, C, Hs, Ws, Hn, Wn, a0, a1, a2)
+  const float rx = area_ratio(Ws, Wn), ry = area_ratio(Hs, Hn);
+#define DIM_ZP(PRE, POST)                                                                                                              \
+  do {                                                                                                                                 \
+    if (max_taps == 0)                                                                                                                 \
+      hipLaunchKernelGGL((zoom_planes_src_kernel<PRE, POST>), grid, block, 0, st, x, zoom_factor, y, C, Hs, Ws, Hn, Wn, a0, a1, a2);   \
+    else                                                                                                                               \
+      hipLaunchKernelGGL((zoom_planes_area_kernel<PRE, POST>), grid, block, 0, st, x, zoom_factor, y, C, Hs, Ws, Hn, Wn, a0, a1, a2,   \
+                         max_taps, rx, ry);                                                                                            \
+  } while (0)
   if (pre == 0 && post == 0) DIM_ZP(0, 0);
   else if (pre == 0 && post == 1) DIM_ZP(0, 1);
   else if (pre == 0 && post == 2) DIM_ZP(0, 2);
@@ -475,12 +639,13 @@ int dim_zoom_planes_src(const float* x, const float* zoom_factor, float* y, int 
   else if (pre == 1 && post == 1) DIM_ZP(1, 1);
   else DIM_ZP(1, 2);
 #undef DIM_ZP
-  return check_launch("zoom_planes_src");
+  return check_launch(what);
 }
 
-int dim_zoom_net_input_src(const float* image_observed, const float* image_rendered, const float* extra_observed, const float* extra_rendered,
-                           const float* zoom_factor, float* X_nhwc8, int B, int Hs, int Ws, int Hn, int Wn, const float* means3, int mode,
-                           float* z_image_observed, float* z_image_rendered, float* z_mask_observed, float* z_mask_rendered, void* stream) {
+static int zoom_net_input_src_launch(const char* what, const float* image_observed, const float* image_rendered, const float* extra_observed,
+                                     const float* extra_rendered, const float* zoom_factor, float* X_nhwc8, int B, int Hs, int Ws, int Hn,
+                                     int Wn, const float* means3, int mode, float* z_image_observed, float* z_image_rendered,
+                                     float* z_mask_observed, float* z_mask_rendered, int max_taps, void* stream) {
   if (B == 0) return DIM_OK;
   DIM_REQUIRE(image_observed && image_rendered && zoom_factor && X_nhwc8 && means3, "null pointer");
   DIM_REQUIRE(Hs >= 2 && Ws >= 2 && Hn >= 2 && Wn >= 2, "source %d x %d and network %d x %d sizes must be >= 2", Hs, Ws, Hn, Wn);
@@ -493,16 +658,67 @@ int dim_zoom_net_input_src(const float* image_observed, const float* image_rende
   const int bx = (Wn % 256 != 0 && Wn % 128 == 0) ? 128 : 256;
   dim3 grid(ceil_div(Wn, bx), Hn, B), block(bx);
   hipStream_t st = as_stream(stream);
-#define DIM_ZNI(M)                                                                                                                        \
-  hipLaunchKernelGGL(zoom_net_input_src_kernel<M>, grid, block, 0, st, image_observed, image_rendered, extra_observed, extra_rendered, \
-                     zoom_factor, X_nhwc8, Hs, Ws, Hn, Wn, means3[0], means3[1], means3[2], z_image_observed, z_image_rendered,        \
-                     z_mask_observed, z_mask_rendered)
+  const float rx = area_ratio(Ws, Wn), ry = area_ratio(Hs, Hn);
+#define DIM_ZNI(M)                                                                                                                         \
+  do {                                                                                                                                     \
+    if (max_taps == 0)                                                                                                                     \
+      hipLaunchKernelGGL(zoom_net_input_src_kernel<M>, grid, block, 0, st, image_observed, image_rendered, extra_observed, extra_rendered, \
+                         zoom_factor, X_nhwc8, Hs, Ws, Hn, Wn, means3[0], means3[1], means3[2], z_image_observed, z_image_rendered,        \
+                         z_mask_observed, z_mask_rendered);                                                                                \
+    else                                                                                                                                   \
+      hipLaunchKernelGGL(zoom_net_input_area_kernel<M>, grid, block, 0, st, image_observed, image_rendered, extra_observed,                \
+                         extra_rendered, zoom_factor, X_nhwc8, Hs, Ws, Hn, Wn, means3[0], means3[1], means3[2], z_image_observed,          \
+                         z_image_rendered, z_mask_observed, z_mask_rendered, max_taps, rx, ry);                                            \
+  } while (0)
   if (mode == 0) DIM_ZNI(0);
   else if (mode == 1) DIM_ZNI(1);
   else if (mode == 2) DIM_ZNI(2);
   else DIM_ZNI(3);
 #undef DIM_ZNI
-  return check_launch("zoom_net_input_src");
+  return check_launch(what);
 }
+
+int dim_zoom_planes_src(const float* x, const float* zoom_factor, float* y, int B, int C, int Hs, int Ws, int Hn, int Wn, int pre, int post,
+                        const float* add3, void* stream) {
+  return zoom_planes_src_launch("zoom_planes_src", x, zoom_factor, y, B, C, Hs, Ws, Hn, Wn, pre, post, add3, 0, stream);
+}
+
+int dim_zoom_net_input_src(const float* image_observed, const float* image_rendered, const float* extra_observed, const float* extra_rendered,
+                           const float* zoom_factor, float* X_nhwc8, int B, int Hs, int Ws, int Hn, int Wn, const float* means3, int mode,
+                           float* z_image_observed, float* z_image_rendered, float* z_mask_observed, float* z_mask_rendered, void* stream) {
+  return zoom_net_input_src_launch("zoom_net_input_src", image_observed, image_rendered, extra_observed, extra_rendered, zoom_factor, X_nhwc8,
+                                   B, Hs, Ws, Hn, Wn, means3, mode, z_image_observed, z_image_rendered, z_mask_observed, z_mask_rendered, 0,
+                                   stream);
+}
+
+#define DIM_REQUIRE_MAX_TAPS(max_taps) \
+  DIM_REQUIRE((max_taps) >= 1 && (max_taps) <= kAreaMaxTaps, "max_taps must be 1..%d (got %d)", (int)kAreaMaxTaps, (max_taps))
+
+int dim_zoom_planes_area(const float* x, const float* zoom_factor, float* y, int B, int C, int Hs, int Ws, int Hn, int Wn, int pre, int post,
+                         const float* add3, int max_taps, void* stream) {
+  DIM_REQUIRE_MAX_TAPS(max_taps);
+  return zoom_planes_src_launch("zoom_planes_area", x, zoom_factor, y, B, C, Hs, Ws, Hn, Wn, pre, post, add3, max_taps, stream);
+}
+
+int dim_zoom_net_input_area(const float* image_observed, const float* image_rendered, const float* extra_observed, const float* extra_rendered,
+                            const float* zoom_factor, float* X_nhwc8, int B, int Hs, int Ws, int Hn, int Wn, const float* means3, int mode,
+                            float* z_image_observed, float* z_image_rendered, float* z_mask_observed, float* z_mask_rendered, int max_taps,
+                            void* stream) {
+  DIM_REQUIRE_MAX_TAPS(max_taps);
+  return zoom_net_input_src_launch("zoom_net_input_area", image_observed, image_rendered, extra_observed, extra_rendered, zoom_factor, X_nhwc8,
+                                   B, Hs, Ws, Hn, Wn, means3, mode, z_image_observed, z_image_rendered, z_mask_observed, z_mask_rendered,
+                                   max_taps, stream);
+}
+
+int dim_zoom_area_taps(const float* zoom_factor, int B, int Hs, int Ws, int Hn, int Wn, int max_taps, int* taps_xy, void* stream) {
+  DIM_REQUIRE_MAX_TAPS(max_taps);
+  if (B == 0) return DIM_OK;
+  DIM_REQUIRE(zoom_factor && taps_xy, "null pointer");
+  DIM_REQUIRE(Hs >= 2 && Ws >= 2 && Hn >= 2 && Wn >= 2, "source %d x %d and network %d x %d sizes must be >= 2", Hs, Ws, Hn, Wn);
+  hipLaunchKernelGGL(zoom_area_taps_kernel, dim3(ceil_div(B, 64)), dim3(64), 0, as_stream(stream), zoom_factor, B, area_ratio(Ws, Wn),
+                     area_ratio(Hs, Hn), max_taps, taps_xy);
+  return check_launch("zoom_area_taps");
+}
+#undef DIM_REQUIRE_MAX_TAPS
 
 }  // extern "C"

@@ -71,6 +71,9 @@ def _defaults():
         TENSORBOARD_LOG=False, INIT_MASK="box_gt", UPDATE_MASK="box_gt", MASK_DILATE=False, REPLACE_OBSERVED_BG_RATIO=0.0)
     c.TEST = edict(BATCH_PAIRS=1, test_epoch=0, VISUALIZE=False, test_iter=1, INIT_MASK="box_rendered", UPDATE_MASK="box_rendered",
                    FAST_TEST=False, PRECOMPUTED_ICP=False, BEFORE_ICP=False,
+                   # how the zoom window is sampled into the network input (FAST_TEST loop): "bilinear" = one sample per network pixel,
+                   # "area" = where the window shrinks the image, the mean of up to ZOOM_AREA_MAX_TAPS (1..8) sub-samples per axis
+                   ZOOM_FILTER="bilinear", ZOOM_AREA_MAX_TAPS=4,
                    ICP_ITER=0, ICP_MAX_DIST=0.02,   # depth ICP after the loop: iterations (0 = off), gate in metres
                    # pose from the flow head's output at every loop iteration (dim_flow_pnp; needs PRED_FLOW and the full graph):
                    # Gauss-Newton iterations (0 = off), how many of them are unweighted, the Huber knee and the hard gate (pixels)

@@ -318,6 +318,15 @@ def _DeviceLoader_reset(self):
     self._prefetch()
 
 
+def refuse_zoom_filter_in_training(cfg):
+    """the training graph zooms with the bilinear sampler (its zoomed labels and the backward pass are defined for it alone): a
+    TEST.ZOOM_FILTER other than 'bilinear' in a training run raises, naming the key"""
+    name = cfg.TEST.get("ZOOM_FILTER", "bilinear")
+    if name != "bilinear":
+        raise ValueError("TEST.ZOOM_FILTER {!r} is built for the test path (deepim/test.py, the FAST_TEST loop) alone: training zooms "
+                         "bilinearly -- set TEST.ZOOM_FILTER 'bilinear'".format(name))
+
+
 def _check_common(cfg, H, W, test=False):
     """the files are staged as they are (there is no resize): SCALES must name their size.  The test loader takes any 4:3 size
     (deepim.symbols.deepIM_flownet.source_size: the refinement loop zooms from it into the network input); training is built at the
@@ -331,6 +340,8 @@ def _check_common(cfg, H, W, test=False):
     elif any(s != (min(H, W), max(H, W)) for s in scales):
         raise NotImplementedError("device loader: SCALES must be [[{}, {}]] (resize is the identity; training at another image size is out "
                                   "of scope, only the test path zooms from it), got {}".format(min(H, W), max(H, W), cfg.SCALES))
+    if not test:
+        refuse_zoom_filter_in_training(cfg)
     if cfg.network.get("MASK_INPUTS", False):
         raise NotImplementedError("device loader: network.MASK_INPUTS")
 

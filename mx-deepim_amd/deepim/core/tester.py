@@ -20,7 +20,7 @@ import torch
 from lib.hip import ops
 from deepim.core.coarse import CoarseInit, boxes_from_int, coarse_settings
 from deepim.core.score_lists import PairLists, ScoreLists
-from deepim.symbols.deepIM_flownet import FlowNetHip, source_size
+from deepim.symbols.deepIM_flownet import FlowNetHip, source_size, zoom_filter
 
 HYP_SCORES = ("rgb", "depth")
 ERR_KEYS = ("re", "te", "add", "arp_2d")   # the per-pose error lists lib.dataset.evaluation.PoseEvaluator takes as `errors=`
@@ -133,8 +133,9 @@ class Predictor(object):
     """Reference: binds a MutableModule and calls forward (tester.py:27-56).  Here: owns a FlowNetHip."""
 
     def __init__(self, config, arg_params, batch_size, device="cuda:0", conv_plan=None, winograd=True):
+        name, max_taps = zoom_filter(config)
         self.net = FlowNetHip(config, arg_params, batch_size, device=device, conv_plan=conv_plan, winograd=winograd,
-                              source_size=source_size(config))
+                              source_size=source_size(config), zoom_filter=name, zoom_area_max_taps=max_taps)
         self.data_names = ["image_observed", "image_rendered", "src_pose", "class_index", "mask_observed", "mask_rendered"]
 
     def predict(self, data_batch):
@@ -158,6 +159,7 @@ class Refiner(object):
             raise Exception("Unknown UPDATE_MASK type: {}".format(cfg.TEST.UPDATE_MASK))
         # (Hs, Ws): the size of every image-like buffer here -- the camera image, the renders, the masks; the network input stays 480x640
         H, W = source_size(cfg)
+        filter_cfg = zoom_filter(cfg)   # (refuses 'area' in the full graph)
         refuse_at_source_size(cfg, (H, W), lit=hasattr(render_machine, "normals"))
         self.hyp_num, self.hyp_rot_deg, self.hyp_score_mode, self.hyp_tau = hyp_settings(cfg)
         self.flow_pnp_iter, self.flow_pnp_warm, self.flow_pnp_huber, self.flow_pnp_gate = flow_pnp_settings(cfg)
@@ -170,6 +172,9 @@ class Refiner(object):
         if (predictor.net.Hs, predictor.net.Ws) != (H, W):
             raise ValueError("Refiner: SCALES is {}x{} but the Predictor's network was built for a {}x{} source".format(
                 H, W, predictor.net.Hs, predictor.net.Ws))
+        if filter_cfg != (predictor.net.zoom_filter, predictor.net.zoom_area_max_taps):
+            raise ValueError("Refiner: TEST.ZOOM_FILTER / TEST.ZOOM_AREA_MAX_TAPS are {} but the Predictor's network was built for {}".format(
+                filter_cfg, (predictor.net.zoom_filter, predictor.net.zoom_area_max_taps)))
         if (int(render_machine.height), int(render_machine.width)) != (H, W):
             raise ValueError("Refiner: SCALES is {}x{} but the render machine draws {}x{}".format(H, W, render_machine.height,
                                                                                                    render_machine.width))
@@ -204,6 +209,8 @@ class Refiner(object):
         self.bbox2 = torch.zeros((B, 4), dtype=torch.int32, device=d)   # consecutive renders alternate: one box is the next render's dirty-box hint
         self.bbox_obs = torch.zeros((B, 4), dtype=torch.int32, device=d)
         self.status_iter = torch.zeros((self.test_iter, B), dtype=torch.int32, device=d)
+        # TEST.ZOOM_FILTER 'area', for diagnostics: the sub-samples (n_x, n_y) every iteration's zoom took per pair (dim_zoom_area_taps)
+        self.taps_iter = torch.ones((self.test_iter, B, 2), dtype=torch.int32, device=d) if self.net.zoom_filter == "area" else None
         # the camera of each pair's re-render (reference tester.py:165, :560-562: a pair's own -K.txt replaces the config K there, and
         # only there -- ZoomMask and the flow error keep the config K).  Resident so that a captured graph reads whatever load() put in
         # it; `per_pair_K` False (no K loaded) keeps the uniform render with the config K, the launches of a loop without the feature.
@@ -495,6 +502,8 @@ class Refiner(object):
             # se3 and status land directly in their per-iteration rows; the pose of the previous iteration is read where it lies
             out = net.forward_test(cur, bbox_ren=bbox_ren, bbox_obs=bbox_obs, src_pose=pose, se3_out=self.se3_iter[it],
                                    status_out=self.status_iter[it])
+            if self.taps_iter is not None:
+                net.zoom_area_taps(out=self.taps_iter[it])
             if self.mask_pred_iter is not None:
                 ops.copy(self.mask_pred_iter[it], out["mask_observed_pred_output"])
             if self.flow_est_iter is not None:

@@ -11,6 +11,7 @@ f32 MFMA, NHWC) -> pose head -> se3.  Weights are packed once into the kernels' 
                                     checkpoint is an external download and is not available offline)
 """
 import collections
+import functools
 import os
 
 import numpy as np
@@ -233,14 +234,39 @@ def source_size(cfg, net=(480, 640)):
     return Hs, Ws
 
 
+ZOOM_FILTERS = ("bilinear", "area")
+
+
+def check_zoom_filter(name, max_taps):
+    """-> (name, max_taps) of TEST.ZOOM_FILTER / TEST.ZOOM_AREA_MAX_TAPS, checked: ValueError names the key"""
+    if name not in ZOOM_FILTERS:
+        raise ValueError("TEST.ZOOM_FILTER must be one of {}, got {!r}".format(ZOOM_FILTERS, name))
+    if isinstance(max_taps, bool) or not isinstance(max_taps, (int, np.integer)) or not 1 <= int(max_taps) <= 8:
+        raise ValueError("TEST.ZOOM_AREA_MAX_TAPS must be an integer in 1..8, got {!r}".format(max_taps))
+    return name, int(max_taps)
+
+
+def zoom_filter(cfg):
+    """(name, max_taps) from the config, checked.  "area" exists in the FAST_TEST loop only: the full graph (decoder, mask and flow
+    heads, whose inverse zoom and operator_py zoom ops sample bilinearly) refuses it with a ValueError naming TEST.ZOOM_FILTER."""
+    name, max_taps = check_zoom_filter(cfg.TEST.get("ZOOM_FILTER", "bilinear"), cfg.TEST.get("ZOOM_AREA_MAX_TAPS", 4))
+    if name == "area" and not cfg.TEST.FAST_TEST:
+        raise ValueError("TEST.ZOOM_FILTER 'area' is built for the FAST_TEST loop only: the full graph (TEST.FAST_TEST off: decoder, "
+                         "network.PRED_FLOW / PRED_MASK heads) zooms back with the bilinear inverse zoom, and the operator_py zoom ops "
+                         "sample bilinearly -- set TEST.FAST_TEST or TEST.ZOOM_FILTER 'bilinear'")
+    return name, max_taps
+
+
 class FlowNetHip(object):
     """Device executor of the test graph for a fixed per-GPU batch size B (all buffers pre-allocated)."""
 
     H, W = 480, 640   # the network size: X, the encoder, the heads
 
     def __init__(self, cfg, arg_params, batch_size, device="cuda:0", conv_plan=None, winograd=True, wino_m=None, wino_tile=None,
-                 bf16=False, wino_s2=True, source_size=None):
-        """source_size: (Hs, Ws) of the blobs forward_test / zoom / net_input read (4:3), None = the network size.  The zoom window is
+                 bf16=False, wino_s2=True, source_size=None, zoom_filter="bilinear", zoom_area_max_taps=4):
+        """zoom_filter, zoom_area_max_taps: how net_input samples the zoom window (TEST.ZOOM_FILTER / TEST.ZOOM_AREA_MAX_TAPS): "bilinear"
+        = one sample per network pixel; "area" = dim_zoom_net_input_area at every source size, the FAST_TEST graph only.
+        source_size: (Hs, Ws) of the blobs forward_test / zoom / net_input read (4:3), None = the network size.  The zoom window is
         found at that size (with cfg.dataset.INTRINSIC_MATRIX the camera of that image) and the blobs are sampled into the 480x640
         input; the FAST_TEST graph only (the inverse zoom of the flow / mask heads is defined between planes of one size).
         winograd: run the 3x3 / stride-1 layers (conv3_1, conv4_1, conv5_1, conv6_1) through Winograd F(4x4,3x3) / F(2x2,3x3)
@@ -261,6 +287,7 @@ class FlowNetHip(object):
         self.Hs, self.Ws = (self.H, self.W) if source_size is None else (int(source_size[0]), int(source_size[1]))
         if self.Hs < 2 or self.Ws < 2 or self.Hs * self.W != self.Ws * self.H:
             raise ValueError("source size {}x{} (SCALES) must be 4:3 with both sides >= 2".format(self.Hs, self.Ws))
+        self.zoom_filter, self.zoom_area_max_taps = check_zoom_filter(zoom_filter, zoom_area_max_taps)
         self.device = torch.device(device)
         self.cin = input_channels(cfg)
         self.n_regressors = regressor_num(cfg)
@@ -365,6 +392,8 @@ class FlowNetHip(object):
                 and (self.Hs, self.Ws) != (self.H, self.W)):
             raise ValueError("the full graph (decoder, mask and flow heads; TEST.FAST_TEST off) runs at SCALES [[{}, {}]] only, got {}x{}: "
                              "set TEST.FAST_TEST or SCALES to the network size".format(self.H, self.W, self.Hs, self.Ws))
+        if self.zoom_filter == "area" and not cfg.TEST.FAST_TEST:
+            raise ValueError("TEST.ZOOM_FILTER 'area' needs TEST.FAST_TEST: the full graph (decoder, mask and flow heads) samples bilinearly")
         if self.has_decoder:
             self.packed["deconv5"] = self.pack_deconv(self.params["deconv5_weight"])
             self.packed["deconv4"] = self.pack_deconv(self.params["deconv4_weight"])
@@ -459,7 +488,7 @@ class FlowNetHip(object):
     def net_input(self, batch, nchw_out=None):
         """the first layer's input from the blobs and self.zoom_factor: ZoomImageWithFactor (+ ZoomDepth) (+ the zoomed masks) in the
         Concat order of get_convs (reference :33-66), as one or two 8-lane NHWC tensors (see input_mode)"""
-        if (self.Hs, self.Ws) != (self.H, self.W):
+        if (self.Hs, self.Ws) != (self.H, self.W) or self.zoom_filter == "area":
             return self._net_input_src(batch, nchw_out)
         if self.input_mode == 0:
             ops.zoom_net_input(batch["image_observed"], batch["image_rendered"], batch["mask_observed"], batch["mask_rendered"],
@@ -475,18 +504,27 @@ class FlowNetHip(object):
         return self.X
 
     def _net_input_src(self, batch, nchw_out=None):
-        """net_input from blobs of another (source) size: the same lanes through dim_zoom_net_input_src"""
+        """net_input from blobs of another (source) size: the same lanes through dim_zoom_net_input_src; with the area filter (at every
+        source size, the network's included) through dim_zoom_net_input_area"""
+        zoom = ops.zoom_net_input_src
+        if self.zoom_filter == "area":
+            zoom = functools.partial(ops.zoom_net_input_area, max_taps=self.zoom_area_max_taps)
         img = (batch["image_observed"], batch["image_rendered"])
         masks, depths = (batch.get("mask_observed"), batch.get("mask_rendered")), (batch.get("depth_observed"), batch.get("depth_rendered"))
         if self.input_mode == 0:
-            ops.zoom_net_input_src(*img, *masks, self.zoom_factor, self.plane_means, 0, X=self.X, nchw_out=nchw_out)
+            zoom(*img, *masks, self.zoom_factor, self.plane_means, 0, X=self.X, nchw_out=nchw_out)
         elif self.input_mode == 1:
-            ops.zoom_net_input_src(*img, None, None, self.zoom_factor, self.plane_means, 1, X=self.X)
+            zoom(*img, None, None, self.zoom_factor, self.plane_means, 1, X=self.X)
         else:
-            ops.zoom_net_input_src(*img, *depths, self.zoom_factor, self.plane_means, 2, X=self.X)
+            zoom(*img, *depths, self.zoom_factor, self.plane_means, 2, X=self.X)
             if self.input_mode == 3:
-                ops.zoom_net_input_src(*img, *masks, self.zoom_factor, self.plane_means, 3, X=self.X2)
+                zoom(*img, *masks, self.zoom_factor, self.plane_means, 3, X=self.X2)
         return self.X
+
+    def zoom_area_taps(self, out=None):
+        """(B,2) int32 (n_x, n_y): the sub-samples per axis the area filter takes for the windows now in self.zoom_factor (all 1 where
+        a window magnifies, and what "bilinear" amounts to)"""
+        return ops.zoom_area_taps(self.zoom_factor, (self.Hs, self.Ws), (self.H, self.W), self.zoom_area_max_taps, out=out)
 
     def _run_winograd(self, name, cout, x, events=None, s2=True):
         """the layer's Winograd forward into self.acts[name] if it has one (s2=False: the 3x3 / stride-2 form does not count), else None"""

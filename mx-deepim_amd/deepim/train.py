@@ -39,6 +39,7 @@ def train_net(args):
     import torch
 
     from deepim.core import callback, metric
+    from deepim.core.loader import refuse_zoom_filter_in_training
     from deepim.core.module import MutableModule, fit_batch
     from deepim.symbols import deepIM_flownet as symbols
     from lib.dataset.synthetic_pairs import SyntheticPairs
@@ -85,6 +86,7 @@ def train_net(args):
     if [tuple(int(v) for v in sc) for sc in config.SCALES] != [(480, 640)]:
         raise NotImplementedError("training runs at SCALES [[480, 640]] only, got {}: another image size is built for the test path "
                                   "(deepim/test.py) alone, training at it is out of scope".format(config.SCALES))
+    refuse_zoom_filter_in_training(config)
     B = int(config.TRAIN.BATCH_PAIRS)
     data = SyntheticPairs(config, args.num_pairs, B, device=device, rank=rank, world=world, equal_shards=True)
     # DIM_TRAIN_DTYPE=bf16: convolutions on the bf16 matrix pipe (BASELINE configs[2]); DIM_OVERLAP_ALLREDUCE=0: one flat all-reduce

@@ -30,6 +30,9 @@ SIGNATURES = {
     "dim_zoom_net_input_ex": (I, [P, P, P, P, P, P, I, I, I, P, I, P]),
     "dim_zoom_planes_src": (I, [P, P, P, I, I, I, I, I, I, I, I, P, P]),
     "dim_zoom_net_input_src": (I, [P, P, P, P, P, P, I, I, I, I, I, P, I, P, P, P, P, P]),
+    "dim_zoom_planes_area": (I, [P, P, P, I, I, I, I, I, I, I, I, P, I, P]),
+    "dim_zoom_net_input_area": (I, [P, P, P, P, P, P, I, I, I, I, I, P, I, P, P, P, P, I, P]),
+    "dim_zoom_area_taps": (I, [P, I, I, I, I, I, I, P, P]),
     "dim_zoom_trans": (I, [P, P, P, I, I, P]),
     "dim_se3_compose": (I, [P, P, P, P, I, I, P, P, P]),
     "dim_se3_delta": (I, [P, P, P, P, I, I, P, P, P]),
@@ -65,6 +68,7 @@ SIGNATURES = {
     "dim_refiner_create": (I, [P, P, P, P, I, P]),
     "dim_refiner_create_cls": (I, [P, P, I, P, P, I, P]),
     "dim_refiner_create_src": (I, [P, P, I, P, P, I, P]),
+    "dim_refiner_set_zoom_filter": (I, [P, I]),
     "dim_refiner_run": (I, [P, P, P, P, P, P, P, P, P, P, P]),
     "dim_refiner_run_k": (I, [P, P, P, P, P, P, P, P, P, P, P, P]),
     "dim_refiner_destroy": (I, [P]),

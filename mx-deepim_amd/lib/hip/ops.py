@@ -106,22 +106,18 @@ def _same_shape(t, shape, name):
         raise ValueError("{} must have shape {}, got {}".format(name, tuple(shape), tuple(t.shape)))
 
 
-def zoom_planes_src(x, zf, pre=0, post=0, add3=None, out=None, net_size=None):
-    """dim_zoom_planes_src: x (B,C,Hs,Ws) sampled into out (B,C,Hn,Wn), forward direction only.  The source size is x's; the network
-    size out's, or net_size=(Hn, Wn) when out is allocated here."""
+def _zoom_planes_two_sizes(entry, tail, x, zf, pre, post, add3, out, net_size):
     B, C, Hs, Ws = x.shape
     Hn, Wn = _net_size(out, net_size, (2, 3))
     out = out if out is not None else _new((B, C, Hn, Wn), x)
     _same_shape(out, (B, C, Hn, Wn), "out")
     _same_shape(zf, (B, 4), "zoom_factor")
     keep, ap = host_f32(add3, 3) if add3 is not None else (None, None)
-    check(lib().dim_zoom_planes_src(dptr(x, f32), dptr(zf, f32), dptr(out, f32), B, C, Hs, Ws, Hn, Wn, pre, post, ap, current_stream()))
+    check(entry(dptr(x, f32), dptr(zf, f32), dptr(out, f32), B, C, Hs, Ws, Hn, Wn, pre, post, ap, *tail, current_stream()))
     return out
 
 
-def zoom_net_input_src(img_obs, img_ren, extra_obs, extra_ren, zf, plane_means3, mode=0, X=None, nchw_out=None, net_size=None):
-    """dim_zoom_net_input_src: the blobs (B,.,Hs,Ws) sampled into X (B,Hn,Wn,8), modes as zoom_net_input_ex.  The source size is the
-    blobs'; the network size X's, or net_size=(Hn, Wn) when X is allocated here.  nchw_out (mode 0): the four (B,.,Hn,Wn) op outputs."""
+def _zoom_net_input_two_sizes(entry, tail, img_obs, img_ren, extra_obs, extra_ren, zf, plane_means3, mode, X, nchw_out, net_size):
     B, _, Hs, Ws = img_obs.shape
     Hn, Wn = _net_size(X, net_size, (1, 2))
     X = X if X is not None else _new((B, Hn, Wn, 8), img_obs)
@@ -135,10 +131,46 @@ def zoom_net_input_src(img_obs, img_ren, extra_obs, extra_ren, zf, plane_means3,
     for t, c in zip(z, (3, 3, 1, 1)):
         _same_shape(t, (B, c, Hn, Wn), "an NCHW output")
     keep, mp = host_f32(plane_means3, 3)
-    check(lib().dim_zoom_net_input_src(dptr(img_obs, f32), dptr(img_ren, f32), dptr(extra_obs, f32), dptr(extra_ren, f32), dptr(zf, f32),
-                                       dptr(X, f32), B, Hs, Ws, Hn, Wn, mp, int(mode), dptr(z[0], f32), dptr(z[1], f32), dptr(z[2], f32),
-                                       dptr(z[3], f32), current_stream()))
+    check(entry(dptr(img_obs, f32), dptr(img_ren, f32), dptr(extra_obs, f32), dptr(extra_ren, f32), dptr(zf, f32), dptr(X, f32), B, Hs, Ws,
+                Hn, Wn, mp, int(mode), dptr(z[0], f32), dptr(z[1], f32), dptr(z[2], f32), dptr(z[3], f32), *tail, current_stream()))
     return X
+
+
+def zoom_planes_src(x, zf, pre=0, post=0, add3=None, out=None, net_size=None):
+    """dim_zoom_planes_src: x (B,C,Hs,Ws) sampled into out (B,C,Hn,Wn), forward direction only.  The source size is x's; the network
+    size out's, or net_size=(Hn, Wn) when out is allocated here."""
+    return _zoom_planes_two_sizes(lib().dim_zoom_planes_src, (), x, zf, pre, post, add3, out, net_size)
+
+
+def zoom_net_input_src(img_obs, img_ren, extra_obs, extra_ren, zf, plane_means3, mode=0, X=None, nchw_out=None, net_size=None):
+    """dim_zoom_net_input_src: the blobs (B,.,Hs,Ws) sampled into X (B,Hn,Wn,8), modes as zoom_net_input_ex.  The source size is the
+    blobs'; the network size X's, or net_size=(Hn, Wn) when X is allocated here.  nchw_out (mode 0): the four (B,.,Hn,Wn) op outputs."""
+    return _zoom_net_input_two_sizes(lib().dim_zoom_net_input_src, (), img_obs, img_ren, extra_obs, extra_ren, zf, plane_means3, mode, X,
+                                     nchw_out, net_size)
+
+
+def zoom_planes_area(x, zf, pre=0, post=0, add3=None, out=None, net_size=None, max_taps=4):
+    """dim_zoom_planes_area: zoom_planes_src with the area filter -- every output the mean of its n_y x n_x bilinear sub-samples, the
+    counts per pair and axis from the window's size (zoom_area_taps), at most max_taps (1..8) per axis"""
+    return _zoom_planes_two_sizes(lib().dim_zoom_planes_area, (int(max_taps),), x, zf, pre, post, add3, out, net_size)
+
+
+def zoom_net_input_area(img_obs, img_ren, extra_obs, extra_ren, zf, plane_means3, mode=0, X=None, nchw_out=None, net_size=None,
+                        max_taps=4):
+    """dim_zoom_net_input_area: zoom_net_input_src (same arguments, same lanes) with the area filter of zoom_planes_area"""
+    return _zoom_net_input_two_sizes(lib().dim_zoom_net_input_area, (int(max_taps),), img_obs, img_ren, extra_obs, extra_ren, zf,
+                                     plane_means3, mode, X, nchw_out, net_size)
+
+
+def zoom_area_taps(zf, src_size, net_size, max_taps=4, out=None):
+    """dim_zoom_area_taps: (B,2) int32 (n_x, n_y), the sub-samples per axis the area samplers take for every pair's window"""
+    B = zf.shape[0]
+    _same_shape(zf, (B, 4), "zoom_factor")
+    out = out if out is not None else _new((B, 2), zf, i32)
+    _same_shape(out, (B, 2), "out")
+    check(lib().dim_zoom_area_taps(dptr(zf, f32), B, int(src_size[0]), int(src_size[1]), int(net_size[0]), int(net_size[1]), int(max_taps),
+                                   dptr(out, i32), current_stream()))
+    return out
 
 
 def zoom_trans(zf, t, mode, out=None):

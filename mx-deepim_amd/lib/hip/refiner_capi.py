@@ -1,4 +1,5 @@
-"""ctypes face of the resident-loop C entry points (include/deepim_hip.h: dim_refiner_create / _create_cls / _create_src / _run / _run_k / _destroy).
+"""ctypes face of the resident-loop C entry points (include/deepim_hip.h: dim_refiner_create / _create_cls / _create_src /
+_set_zoom_filter / _run / _run_k / _destroy).
 
 This is what a host WITHOUT torch binds (INTEGRATION.md shows the same struct for C / cgo callers); torch is used here only to own
 the device memory of the arguments, exactly as in the rest of lib/hip."""
@@ -60,6 +61,12 @@ class CRefiner(object):
             check(lib().dim_refiner_create_cls(ctypes.byref(self._h), ctypes.byref(d), K, cnames, cptrs, len(names), current_stream()))
         else:
             check(lib().dim_refiner_create(ctypes.byref(self._h), ctypes.byref(d), cnames, cptrs, len(names), current_stream()))
+        # TEST.ZOOM_FILTER 'area': the loop's zoom through dim_zoom_net_input_area (any create function; before the first run)
+        from deepim.symbols.deepIM_flownet import zoom_filter
+
+        name, max_taps = zoom_filter(cfg)
+        if name == "area":
+            check(lib().dim_refiner_set_zoom_filter(self._h, max_taps))
         torch.cuda.synchronize(self.device)
         self.poses_iter = torch.zeros((self.T, self.B, 3, 4), dtype=torch.float32, device=self.device)
         self.se3_iter = torch.zeros((self.T, self.B, 7), dtype=torch.float32, device=self.device)
