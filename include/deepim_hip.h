@@ -44,6 +44,7 @@ extern "C" {
 #define DIM_STATUS_FLOW_PNP_FEW_POINTS 128 /* dim_flow_pnp: an iteration had fewer than 64 weighted points or a singular system (no update) */
 #define DIM_STATUS_LAYER_HIDDEN 256 /* dim_scene_compose: a used layer won no pixel (empty or wholly hidden); per layer, (N*S) words */
 #define DIM_STATUS_COARSE_BAD_BOX 512 /* dim_pose_from_box: a bad box, a class without points, a point behind the camera or a non-finite scale (fallback row) */
+#define DIM_STATUS_PHOTO_FEW_POINTS 1024 /* dim_photo_refine: an iteration had fewer than 64 weighted points or a singular system, or the pair has no usable template (no update) */
 
 const char* dim_last_error(void);
 /* library / device probe: fills name (<= n bytes), returns number of compute units or <0 */
@@ -227,6 +228,49 @@ long dim_flow_pnp_workspace_bytes(int B, int H, int W);
 int dim_flow_pnp(const float* depth_rendered, const float* flow, const float* valid, const int* bbox, const float* pose_src, const float* K9,
                  const float* K_per_sample, int B, int H, int W, int standard_rep, int iters, int warm, float huber_px, float max_px,
                  void* workspace, float* pose_out, float* se3_q, float* stats, int* status, void* stream);
+
+/* ---------------------------------------------------------------- photometric pose polish after the refinement loop (RGB test time)
+ * Dense direct image alignment between the render at a pose and the observed image: coarse to fine over `levels` pyramid levels,
+ * `iters` fixed Gauss-Newton iterations per level (no early exit: graph-capturable), restated by tests/photo_reference.py.  A polish
+ * for a pose that is already within a few degrees and millimetres, not a tracker.  Per pair b:
+ *   image_observed, image_rendered (B,3,H,W) f32 mean-subtracted blobs give the gray planes g = (c0 + c1) + c2 (float32, no division:
+ *   huber and gate are in units of the channel sum); depth_rendered (B,1,H,W) metres, 0 = background; pose_in (B,3,4) = T0, the pose
+ *   the render was drawn at; bbox[b] (B,4 int32 {min_x,max_x,min_y,max_y} inclusive, clipped to the frame, as dim_raster_render*
+ *   returns it; NULL = whole frame).
+ *   Pyramids: level 0 is the frame, level l the 2x2 mean ((a + b) + (c + d)) * 0.25f of level l-1 (a, b the upper row), size
+ *   floor(H/2) x floor(W/2) of it (a leftover row or column is dropped) -- of the observed gray, the rendered gray, the rendered depth
+ *   and a template-valid flag: level 0 = depth > 0 inside the box, level l = all four children valid.
+ *   Gain and bias: over the level-0 valid pixels float64 n, sum Ir, sum Ir^2, sum Io, sum Io^2 (Io at the same pixel);
+ *   a = sqrt(var_o / var_r), b = mean_o - a mean_r (gain == 0: a = 1, b = 0); the template value is t = a Ir_l + b.  n < 64 or a
+ *   variance that is not a finite number > 0: the pair takes no step in any iteration.
+ *   Levels levels-1 .. 0; T_delta starts at the identity and carries over.  At level l, s = 2^l, a valid pixel (X, Y) has the level-0
+ *   centre (xc, yc) = (X s + (s-1)/2, Y s + (s-1)/2) and the point p0 = d_l ((xc-cx)/fx, (yc-cy)/fy, 1).  Each iteration:
+ *   p = R p0 + t (p_z <= 0: dropped), (u, v) its projection, (U, V) = ((u - (s-1)/2)/s, (v - (s-1)/2)/s), cell x0 = floor(U),
+ *   y0 = floor(V) (dropped unless 0 <= x0 < W_l - 1 and 0 <= y0 < H_l - 1), I the bilinear value of the observed level there and
+ *   (gx, gy) the gradient of that interpolant divided by s; r = I - t, e = |r|, w = 1 for e <= huber, huber / e above, 0 for
+ *   e > gate; gp = gx du/dp + gy dv/dp, J = (p x gp, gp) in the left twist xi = (omega, v);
+ *   (A + 1e-9 tr(A)/6 I) xi = -sum w J r by float64 Cholesky, T_delta <- [Rodrigues(omega) | v] T_delta.  Fewer than 64 points with
+ *   w > 0 or a non-positive-definite A: no update, DIM_STATUS_PHOTO_FEW_POINTS is OR-ed into status[b] (B int32, may be NULL), and
+ *   the later iterations and levels still run.
+ * pose_out (B,3,4) f32 = T_delta T0; a pair that never updated gets pose_in bit for bit.  stats (B, levels*iters, 2) f32 or NULL =
+ * (points with w > 0, sqrt(sum of w r^2 over them / their count)) of every iteration before its update, coarsest level first.
+ * Camera as dim_icp_refine: K_per_sample (B,9) device f32 or NULL = K9 (host, 9 floats) for every pair; a non-positive or non-finite
+ * focal length gives the pair no points.
+ * workspace: dim_photo_workspace_bytes(B, H, W, levels) bytes (0 for a refused shape), no initialisation needed; 16-byte aligned for
+ * the 16-byte loads (8 suffices otherwise).  It holds the Gauss-Newton state and partials, per pair 8 doubles {n, sum Ir, sum Ir^2,
+ * sum Io, sum Io^2, a, b, may step} and the planes; dim_photo_workspace_offset(B, H, W, levels, plane, level) is the byte offset of
+ * plane 0 .. 3 = {observed gray, rendered gray, depth, valid flag as 0.f / 1.f} at `level` ((B, H_l, W_l) f32), and with plane = 4 of
+ * the (B, 8) doubles (-1 for a bad index) -- for tests and diagnostics.
+ * Arithmetic: planes in float32; per point, per lane, across lanes, waves and workgroups float64 in a fixed order (no atomics, no
+ * memcpy / memset): a replay is bit-identical.  16-byte loads in the pyramid pass when W % 4 == 0 and the arrays are 16-byte aligned.
+ * levels + 2 + 2 levels iters launches; iters == 0 copies pose_in to pose_out.  B <= 0, levels outside 1 .. 5, iters < 0, huber <= 0,
+ * gate < huber, a coarsest level smaller than 3 x 3 or a NULL required pointer (the three images, pose_in, K9, workspace, pose_out)
+ * return DIM_ERR_ARG before anything is enqueued. */
+long dim_photo_workspace_bytes(int B, int H, int W, int levels);
+long dim_photo_workspace_offset(int B, int H, int W, int levels, int plane, int level);
+int dim_photo_refine(const float* image_observed, const float* image_rendered, const float* depth_rendered, const int* bbox,
+                     const float* pose_in, const float* K9, const float* K_per_sample, int B, int H, int W, int levels, int iters,
+                     float huber, float gate, int gain, void* workspace, float* pose_out, float* stats, int* status, void* stream);
 
 /* ---------------------------------------------------------------- multi-hypothesis refinement (several starting poses per pair)
  * Samples are pair-major: sample b = p * N + h of P pairs with N hypotheses each.  Restated in float64 by tests/hyp_reference.py.

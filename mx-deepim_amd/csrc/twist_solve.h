@@ -1,6 +1,6 @@
-// Float64 device helpers shared by the Gauss-Newton pose stages (icp.hip, flow_pnp.hip) and the pose algebra (se3.hip): the 6x6
+// Float64 device helpers shared by the Gauss-Newton pose stages (icp.hip, flow_pnp.hip, photo.hip) and the pose algebra (se3.hip): the 6x6
 // Cholesky solve of the normal equations, the Rodrigues rotation of a twist's omega, and rotation matrix -> quaternion; and what
-// the two Gauss-Newton stages have in common: the workspace layout, the camera and box of a pair, and the solve kernel.
+// the Gauss-Newton stages have in common: the workspace layout, the camera and box of a pair, and the solve kernel.
 #pragma once
 #include "common.h"
 
@@ -10,6 +10,8 @@ namespace dim {
 // and gn_solve_kernel, one workgroup per pair, adds them in order.  Workspace: [state B x kGnState][partial B x kGnBlocks x kGnSlot]
 constexpr int kGnBlocks = 16;      // workgroups per pair: 4096 lanes over the bbox (a LINEMOD object covers 5k-80k pixels)
 constexpr int kGnTerms = 29;       // 21 upper-triangle entries of sum J J^T, 6 of sum J r, point count, sum of squared residuals
+                                   // (terms 27 and 28 only feed stats and the point test: icp.hip and flow_pnp.hip put the unweighted
+                                   // sum of r^2 over the counted points into 28, photo.hip the weighted one, sum of w r^2)
 constexpr int kGnSlot = 32;        // doubles per partial (padded)
 constexpr int kGnState = 16;       // doubles per pair: R (9), t (3), updated (1), pad
 constexpr int kGnMinPoints = 64;   // fewer points: no update, the stage's status bit
@@ -105,7 +107,8 @@ __device__ inline void mat2quat_d(const double M[9], double q[4]) {
 }
 
 // One Gauss-Newton step of pair b = blockIdx.x (64 lanes): sums the kGnBlocks partials in order, solves the damped normal equations
-// by Cholesky, T <- [Rodrigues(omega) | v] T, writes stats (B, iters, 2) = (points, rms residual) when given, and ORs FAIL_BIT into
+// by Cholesky, T <- [Rodrigues(omega) | v] T, writes stats (B, iters, 2) = (term 27, sqrt(term 28 / term 27)) = (points, rms residual
+// as the stage defines term 28) when given, and ORs FAIL_BIT into
 // status[b] when the step was skipped (fewer than kGnMinPoints points or a singular system).  After the last iteration
 // pose_out = T pose_in and, when se3_q is given, se3_q = [quat(R), t]; a pair that never updated gets pose_in bit for bit and the
 // identity.

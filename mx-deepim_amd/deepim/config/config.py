@@ -75,6 +75,10 @@ def _defaults():
                    # "area" = where the window shrinks the image, the mean of up to ZOOM_AREA_MAX_TAPS (1..8) sub-samples per axis
                    ZOOM_FILTER="bilinear", ZOOM_AREA_MAX_TAPS=4,
                    ICP_ITER=0, ICP_MAX_DIST=0.02,   # depth ICP after the loop: iterations (0 = off), gate in metres
+                   # photometric polish after the loop (dim_photo_refine; a polish of a pose within a few degrees, not a tracker):
+                   # Gauss-Newton iterations per pyramid level (0 = off), pyramid levels (1..5), the Huber knee and the hard gate in
+                   # units of the channel sum (three times a gray level), one gain and bias per pair
+                   PHOTO_ITER=0, PHOTO_LEVELS=3, PHOTO_HUBER=30.0, PHOTO_MAX=180.0, PHOTO_GAIN=True,
                    # pose from the flow head's output at every loop iteration (dim_flow_pnp; needs PRED_FLOW and the full graph):
                    # Gauss-Newton iterations (0 = off), how many of them are unweighted, the Huber knee and the hard gate (pixels)
                    FLOW_PNP_ITER=0, FLOW_PNP_WARM=2, FLOW_PNP_HUBER_PX=2.0, FLOW_PNP_MAX_PX=8.0,

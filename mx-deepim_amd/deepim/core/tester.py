@@ -96,6 +96,33 @@ def flow_pnp_settings(cfg):
     return int(n), int(warm), huber, gate
 
 
+def photo_settings(cfg):
+    """-> (PHOTO_ITER, PHOTO_LEVELS, PHOTO_HUBER, PHOTO_MAX, PHOTO_GAIN) of cfg.TEST, checked; ValueError names the bad key(s).
+    PHOTO_ITER counts Gauss-Newton iterations per pyramid level (0 = off); the two thresholds are in units of the channel sum.
+    Selecting among polished hypotheses is not defined, so the stage is refused together with HYP_NUM > 1 and COARSE_VIEWS > 0."""
+    T = cfg.TEST
+    n = T.get("PHOTO_ITER", 0) or 0
+    if isinstance(n, bool) or not float(n).is_integer() or int(n) < 0:
+        raise ValueError("TEST.PHOTO_ITER must be an integer >= 0 (iterations per level, 0 = off), got {!r}".format(n))
+    levels = T.get("PHOTO_LEVELS", 3)
+    if isinstance(levels, bool) or not float(levels).is_integer() or not 1 <= int(levels) <= 5:
+        raise ValueError("TEST.PHOTO_LEVELS must be an integer in 1..5, got {!r}".format(levels))
+    huber, gate = float(T.get("PHOTO_HUBER", 30.0)), float(T.get("PHOTO_MAX", 180.0))
+    if not (np.isfinite(huber) and huber > 0):
+        raise ValueError("TEST.PHOTO_HUBER must be a finite number > 0 (units of the channel sum), got {!r}".format(T.get("PHOTO_HUBER")))
+    if not (np.isfinite(gate) and gate >= huber):
+        raise ValueError("TEST.PHOTO_MAX must be finite and >= TEST.PHOTO_HUBER, got {!r}".format(T.get("PHOTO_MAX")))
+    gain = T.get("PHOTO_GAIN", True)
+    if not isinstance(gain, (bool, np.bool_)):
+        raise ValueError("TEST.PHOTO_GAIN must be True or False, got {!r}".format(gain))
+    if int(n) > 0:
+        if int(T.get("HYP_NUM", 1) or 1) > 1:
+            raise ValueError("TEST.PHOTO_ITER > 0 cannot be combined with TEST.HYP_NUM > 1")
+        if int(T.get("COARSE_VIEWS", 0) or 0) > 0:
+            raise ValueError("TEST.PHOTO_ITER > 0 cannot be combined with TEST.COARSE_VIEWS > 0")
+    return int(n), int(levels), huber, gate, bool(gain)
+
+
 def hypothesis_rotations(N, rot_deg):
     """(N,3,3) float64: R_0 = I; R_h (h >= 1) = the Rodrigues rotation by rot_deg about axis h-1 of a Fibonacci sphere of N-1 points,
     z = 1 - (2k+1)/(N-1), r = sqrt(1-z^2), phi = k pi (3 - sqrt 5), axis = (r cos phi, r sin phi, z).  Hypothesis h starts the
@@ -121,6 +148,7 @@ def refuse_at_source_size(cfg, size, lit=False):
     on = [("TEST.ICP_ITER", int(T.get("ICP_ITER", 0) or 0) > 0), ("TEST.HYP_NUM", int(T.get("HYP_NUM", 1) or 1) > 1),
           ("TEST.COARSE_VIEWS", int(T.get("COARSE_VIEWS", 0) or 0) > 0), ("TEST.VSD", bool(T.get("VSD", False))),
           ("TEST.BOP_VSD", bool(T.get("BOP_VSD", False))), ("TEST.FLOW_PNP_ITER", int(T.get("FLOW_PNP_ITER", 0) or 0) > 0),
+          ("TEST.PHOTO_ITER", int(T.get("PHOTO_ITER", 0) or 0) > 0),
           ("network.PRED_FLOW without TEST.FAST_TEST (the test-time flow error)", bool(cfg.network.PRED_FLOW and not T.FAST_TEST)),
           ("the lit ModelNet renderer", bool(lit))]
     for key, active in on:
@@ -163,6 +191,9 @@ class Refiner(object):
         refuse_at_source_size(cfg, (H, W), lit=hasattr(render_machine, "normals"))
         self.hyp_num, self.hyp_rot_deg, self.hyp_score_mode, self.hyp_tau = hyp_settings(cfg)
         self.flow_pnp_iter, self.flow_pnp_warm, self.flow_pnp_huber, self.flow_pnp_gate = flow_pnp_settings(cfg)
+        self.photo_iter, self.photo_levels, self.photo_huber, self.photo_gate, self.photo_gain = photo_settings(cfg)
+        if self.photo_iter > 0 and hasattr(render_machine, "normals"):
+            raise ValueError("TEST.PHOTO_ITER > 0 is not supported with the lit ModelNet renderer")
         N = self.hyp_num
         if N > 1 and predictor.net.B != batch_size * N:
             raise ValueError("Refiner: {} pairs x TEST.HYP_NUM {} = {} samples, but the Predictor was built for {} samples".format(
@@ -239,6 +270,17 @@ class Refiner(object):
             self.icp_stats = torch.zeros((B, self.icp_iter, 2), dtype=torch.float32, device=d)
             self.status_icp = torch.zeros((B,), dtype=torch.int32, device=d)
             self.icp_work = ops.icp_workspace(B, H, W, d)
+        # photometric polish after the loop (TEST.PHOTO_ITER > 0): the render at the last pose (image, depth, box) and the polished
+        # pose per pair; nothing is allocated when the stage is off
+        self.pose_photo = self.photo_stats = self.status_photo = None
+        if self.photo_iter > 0:
+            self.image_photo = torch.zeros((B, 3, H, W), dtype=torch.float32, device=d)
+            self.depth_photo = torch.zeros((B, 1, H, W), dtype=torch.float32, device=d)
+            self.bbox_photo = torch.zeros((B, 4), dtype=torch.int32, device=d)
+            self.pose_photo = torch.zeros((B, 3, 4), dtype=torch.float32, device=d)
+            self.photo_stats = torch.zeros((B, self.photo_levels * self.photo_iter, 2), dtype=torch.float32, device=d)
+            self.status_photo = torch.zeros((B,), dtype=torch.int32, device=d)
+            self.photo_work = ops.photo_workspace(B, H, W, self.photo_levels, d)
         # pose from the flow head's output at every iteration (TEST.FLOW_PNP_ITER > 0): the depth of the render each forward looked
         # at (INPUT_DEPTH graphs hold it already), the box of the initial render, and the per-iteration outputs
         self.pose_flow_iter = self.se3_flow_iter = self.flow_pnp_stats = self.status_flow = None
@@ -548,6 +590,8 @@ class Refiner(object):
         ops.copy(b["src_pose"], pose)  # the blob ends up as the reference leaves it: the pose the last forward used
         if self.icp_iter > 0:
             self._icp(self.poses_iter[self.test_iter - 1])
+        if self.photo_iter > 0:   # independent of the ICP: both start from the loop's last pose
+            self._photo(self.poses_iter[self.test_iter - 1])
         if self.N > 1:
             self._select(self.poses_iter[self.test_iter - 1])
 
@@ -579,9 +623,24 @@ class Refiner(object):
         ops.icp_refine(self.depth_icp, self.depth_observed, pose, self.render_machine.K, self.icp_iter, self.icp_max_dist, bbox=self.bbox_icp,
                        K_per_sample=K_pair, pose_out=self.pose_icp, stats=self.icp_stats, status=self.status_icp, workspace=self.icp_work)
 
+    def _photo(self, pose):
+        """photometric polish from the loop's last pose: render its image, depth and box (the pair's K when loaded), then
+        dim_photo_refine against image_observed -> pose_photo, photo_stats (B,PHOTO_LEVELS*PHOTO_ITER,2), status_photo (render bits
+        and DIM_STATUS_PHOTO_FEW_POINTS)"""
+        b = self.batch
+        ops.fill(self.status_photo, 0)
+        K_pair = self.K_pair if self.per_pair_K else None
+        extra = {"K": K_pair} if K_pair is not None else {}
+        self.render_machine.render_batch(b["class_index"], pose, image=self.image_photo, depth=self.depth_photo, bbox=self.bbox_photo,
+                                         plane_means=self.net.plane_means, mask_thr=0.0, status=self.status_photo, **extra)
+        ops.photo_refine(b["image_observed"], self.image_photo, self.depth_photo, pose, self.render_machine.K, self.photo_levels,
+                         self.photo_iter, self.photo_huber, self.photo_gate, gain=self.photo_gain, bbox=self.bbox_photo, K_per_sample=K_pair,
+                         pose_out=self.pose_photo, stats=self.photo_stats, status=self.status_photo, workspace=self.photo_work)
+
     def refine(self):
         """run test_iter iterations on the loaded batch; returns poses_iter (test_iter,B,3,4) (device).  With TEST.ICP_ITER > 0 the
-        ICP stage runs after them (inside the same graph) and leaves its pose in pose_icp (B,3,4).  With TEST.FLOW_PNP_ITER > 0 every
+        ICP stage runs after them (inside the same graph) and leaves its pose in pose_icp (B,3,4); with TEST.PHOTO_ITER > 0 the
+        photometric polish does the same from the same last pose and leaves pose_photo (B,3,4).  With TEST.FLOW_PNP_ITER > 0 every
         iteration also solves the pose from its flow head's output (dim_flow_pnp, inside the same graph): pose_flow_iter
         (test_iter,B,3,4), se3_flow_iter (test_iter,B,7), flow_pnp_stats (test_iter,B,FLOW_PNP_ITER,2), status_flow (test_iter,B);
         the loop itself never reads them.  With TEST.HYP_NUM > 1 it returns
@@ -817,6 +876,10 @@ def pred_eval(config, refiner, batches, evaluator, result_file=None, logger=None
     evaluator: lib.dataset.evaluation.PoseEvaluator.  Returns the three result dicts.
     With TEST.ICP_ITER > 0 the refiner's ICP poses are scored too, as the one-row table of the reference's PRECOMPUTED_ICP branch
     (tester.py:253-330), under out["icp"] = {pose, add, arp_2d}; every other output and the result cache are those of ICP off.
+    With TEST.PHOTO_ITER > 0 the refiner's photometrically polished poses (pose_photo) are scored the same way, as a one-row table
+    under out["photo"] = {pose, add, arp_2d} (the host error functions, or dim_pose_errors under TEST.DEVICE_EVAL; one more copy per
+    batch); every other output and the result cache are those of the stage off.  Scoring that row by TEST.VSD / TEST.BOP is left out:
+    the combination raises a ValueError.
     With TEST.HYP_NUM = N > 1 every table, the result cache and out["icp"] score the selected hypothesis of each pair, and out["hyp"]
     holds per pair the N scores, the choice and the last-iteration rotation / translation error of every hypothesis, plus the rate
     at which the chosen hypothesis is also the one with the least rotation error.  A batch may carry "hyp_poses" (P,N,3,4).
@@ -865,7 +928,7 @@ def pred_eval(config, refiner, batches, evaluator, result_file=None, logger=None
 
 def _eval_setup(config, refiner, evaluator, logger):
     """what one pred_eval call holds: the switches, the device scorers and `store`, every list it collects under its name --
-    (pose set, family) -> ScoreLists for the sets "loop", "icp" and "flow_pnp" and the families of FAMILY_KEYS, and the per-pair
+    (pose set, family) -> ScoreLists for the sets "loop", "icp", "flow_pnp" and "photo" and the families of FAMILY_KEYS, and the per-pair
     "hyp", "flow_rows" and "coarse" -> PairLists.  A name is there only when its feature is on."""
     from types import SimpleNamespace
 
@@ -875,7 +938,10 @@ def _eval_setup(config, refiner, evaluator, logger):
                          with_icp=int(T.get("ICP_ITER", 0) or 0) > 0, n_hyp=int(getattr(refiner, "N", 1)),
                          device_eval=bool(T.get("DEVICE_EVAL", False)), with_flow=int(T.get("FLOW_PNP_ITER", 0) or 0) > 0,
                          with_coarse=getattr(refiner, "coarse", None) is not None, vsd=None, bop=None,
+                         with_photo=int(T.get("PHOTO_ITER", 0) or 0) > 0,
                          vsd_who="TEST.VSD" if bool(T.get("VSD", False)) else "TEST.BOP_VSD")
+    if st.with_photo and (bool(T.get("VSD", False)) or bool(T.get("BOP", False))):
+        raise ValueError("TEST.PHOTO_ITER > 0 cannot be combined with TEST.VSD or TEST.BOP (the photometric row is not scored there)")
     if st.device_eval:
         from lib.dataset.evaluation import SYM_CLASSES
 
@@ -895,6 +961,8 @@ def _eval_setup(config, refiner, evaluator, logger):
         sets.append(("icp", 1, families))
     if st.with_flow:   # pose from flow at every iteration: scored by the error code alone
         sets.append(("flow_pnp", st.n_it, [f for f in families if f in ("rt", "err")]))
+    if st.with_photo:  # one row, as the ICP pose; by the error code alone
+        sets.append(("photo", 1, [f for f in families if f in ("rt", "err")]))
     st.store = {(name, f): ScoreLists(FAMILY_KEYS[f], st.n_cls, iters) for name, iters, fams in sets for f in fams}
     st.scored = list(st.store)
     if st.n_hyp > 1:
@@ -969,6 +1037,19 @@ def _read_out_flow(st, refiner, cls_dev, gt_dev):
     return host
 
 
+def _read_out_photo(st, refiner, cls_dev, gt_dev):
+    """one more copy per batch with TEST.PHOTO_ITER > 0: the polished poses [and their device errors] -> {pose (1, P, 3, 4),
+    [err (1, P, 5)]}"""
+    pose = refiner.pose_photo
+    columns = [("pose", 12, pose.to(torch.float64)[None])]
+    if st.device_eval:
+        t = st.tables
+        columns.append(("err", 5, ops.pose_errors(t[0], t[1], t[2], cls_dev, pose, gt_dev, st.K_eval).reshape(1, -1, 5)))
+    host = _to_host(columns)
+    host["pose"] = host["pose"].reshape(1, -1, 3, 4)
+    return host
+
+
 def _pair_values(st, family, rows, b, undetected, src, gt, cls_b):
     """What pair b adds to the lists of one family for one pose set: one tuple of FAMILY_KEYS[family] values per row of `rows`
     (iterations, ...), the pair's rows of the family's column.  This is the one place of the rule for a pair that was not refined,
@@ -1026,6 +1107,8 @@ def _collect_batch(st, refiner, batch):
     by_set = {"loop": {k: v[:n_it] for k, v in host.items()}, "icp": {k: v[n_it:] for k, v in host.items()}}
     if st.with_flow:
         by_set["flow_pnp"] = _read_out_flow(st, refiner, cls_dev, gt_dev)
+    if st.with_photo:
+        by_set["photo"] = _read_out_photo(st, refiner, cls_dev, gt_dev)
     cls = torch.as_tensor(batch["class_index"]).cpu().numpy().astype(int)
     gt = torch.as_tensor(batch["pose_observed"]).cpu().numpy().astype(np.float64)
     src = torch.as_tensor(batch["src_pose"]).cpu().numpy().astype(np.float64)
@@ -1127,6 +1210,13 @@ def _tables(st, result_file, merge_ranks, merged):
         cfg1.TEST.test_iter = 1
         _say(logger, "evaluate ICP ({} iterations, gate {} m):".format(int(config.TEST.ICP_ITER), float(config.TEST.ICP_MAX_DIST)))
         out["icp"] = dict(_pose_tables(st, cfg1, "icp"), **_scorer_tables(st, "icp"))
+    if st.with_photo:   # one row, scored as the ICP row is
+        cfg1 = copy.deepcopy(config)
+        cfg1.TEST.test_iter = 1
+        _say(logger, "evaluate photometric polish ({} levels x {} iterations, Huber {}, gate {}):".format(
+            int(config.TEST.get("PHOTO_LEVELS", 3)), int(config.TEST.PHOTO_ITER), float(config.TEST.get("PHOTO_HUBER", 30.0)),
+            float(config.TEST.get("PHOTO_MAX", 180.0))))
+        out["photo"] = _pose_tables(st, cfg1, "photo")
     if st.with_flow:
         _say(logger, "evaluate pose from flow ({} iterations, {} unweighted, Huber {} px, gate {} px):".format(
             int(config.TEST.FLOW_PNP_ITER), int(config.TEST.FLOW_PNP_WARM), float(config.TEST.FLOW_PNP_HUBER_PX), float(config.TEST.FLOW_PNP_MAX_PX)))

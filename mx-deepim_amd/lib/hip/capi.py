@@ -49,6 +49,9 @@ SIGNATURES = {
     "dim_icp_refine": (I, [P, P, P, P, P, P, P, I, I, I, I, F, P, P, P, P, P]),
     "dim_flow_pnp_workspace_bytes": (L, [I, I, I]),
     "dim_flow_pnp": (I, [P, P, P, P, P, P, P, I, I, I, I, I, I, F, F, P, P, P, P, P, P]),
+    "dim_photo_workspace_bytes": (L, [I, I, I, I]),
+    "dim_photo_workspace_offset": (L, [I, I, I, I, I, I]),
+    "dim_photo_refine": (I, [P, P, P, P, P, P, P, I, I, I, I, I, F, F, I, P, P, P, P, P]),
     "dim_hyp_expand": (I, [P, P, I, I, P, P]),
     "dim_hyp_broadcast": (I, [P, P, I, I, L, P]),
     "dim_pose_score_workspace_bytes": (L, [I, I, I]),

@@ -370,7 +370,59 @@ def flow_pnp(depth_rendered, flow, pose_src, K, iters, warm=2, huber_px=2.0, max
     return pose_out, se3_q
 
 
-STATUS_HYP_NO_SCORE = 64   # DIM_STATUS_HYP_NO_SCORE: dim_pose_score had < 64 counted pixels, a constant plane or a non-finite sum
+STATUS_PHOTO_FEW_POINTS = 1024   # DIM_STATUS_PHOTO_FEW_POINTS: a photometric iteration had < 64 weighted points, a singular system or no template
+PHOTO_PLANES = ("obs", "ren", "depth", "valid")   # the plane kinds of dim_photo_workspace_offset, in its order
+
+
+def photo_workspace(B, H, W, levels, device):
+    nbytes = lib().dim_photo_workspace_bytes(B, H, W, int(levels))
+    if nbytes <= 0:
+        raise ValueError("photo_workspace: B = {}, a {}x{} frame and {} levels are refused (levels 1..5, coarsest level >= 3x3)".format(
+            B, H, W, levels))
+    return _workspace_f64(nbytes, device)
+
+
+def photo_workspace_views(workspace, B, H, W, levels):
+    """what dim_photo_refine left in its workspace, for tests and diagnostics (views, no copy) -> ({kind: [(B,H_l,W_l) f32 per level]}
+    for the kinds of PHOTO_PLANES, (B,8) f64 = {n, sum Ir, sum Ir^2, sum Io, sum Io^2, a, b, may step})"""
+    off = lambda plane, level: lib().dim_photo_workspace_offset(B, H, W, int(levels), plane, level)  # noqa: E731
+    as_f32 = workspace.view(f32)
+    planes, h, w = {k: [] for k in PHOTO_PLANES}, H, W
+    for lv in range(levels):
+        for p, kind in enumerate(PHOTO_PLANES):
+            at = off(p, lv) // 4
+            planes[kind].append(as_f32[at:at + B * h * w].view(B, h, w))
+        h, w = h // 2, w // 2
+    at = off(len(PHOTO_PLANES), 0) // 8
+    return planes, workspace[at:at + 8 * B].view(B, 8)
+
+
+def photo_refine(image_observed, image_rendered, depth_rendered, pose_in, K, levels, iters, huber, gate, gain=True, bbox=None,
+                 K_per_sample=None, pose_out=None, stats=None, status=None, workspace=None):
+    """photometric pose polish of dim_photo_refine (restated by tests/photo_reference.py): image_observed / image_rendered (B,3,H,W)
+    mean-subtracted blobs, depth_rendered (B,1,H,W) rendered at pose_in (B,3,4); `levels` pyramid levels, `iters` Gauss-Newton
+    iterations per level, huber and gate in units of the channel sum, one gain and bias per pair unless gain is False; K / K_per_sample
+    / bbox as icp_refine.  -> pose_out (B,3,4); stats (B,levels*iters,2) = (weighted points, rms residual) per iteration, coarsest
+    level first; status (B,) int32: DIM_STATUS_PHOTO_FEW_POINTS is OR-ed in."""
+    B, _, H, W = depth_rendered.shape
+    assert tuple(image_observed.shape) == (B, 3, H, W) and tuple(image_rendered.shape) == (B, 3, H, W)
+    assert tuple(depth_rendered.shape) == (B, 1, H, W) and tuple(pose_in.shape) == (B, 3, 4)
+    assert stats is None or stats.numel() >= 2 * B * int(levels) * int(iters)
+    assert (status is None or status.numel() == B) and (bbox is None or bbox.numel() == 4 * B)
+    pose_out = pose_out if pose_out is not None else _new((B, 3, 4), pose_in)
+    if workspace is None:
+        workspace = photo_workspace(B, H, W, levels, pose_in.device)
+    assert workspace.numel() * workspace.element_size() >= lib().dim_photo_workspace_bytes(B, H, W, int(levels))
+    kps = intrinsics_per_sample(K_per_sample, B, pose_in.device)
+    keep, kp = host_f32(K, 9)
+    check(lib().dim_photo_refine(dptr(image_observed, f32), dptr(image_rendered, f32), dptr(depth_rendered, f32), _opt(bbox, i32),
+                                 dptr(pose_in, f32), kp, _opt(kps), B, H, W, int(levels), int(iters), float(huber), float(gate),
+                                 int(bool(gain)), dptr(workspace, torch.float64), dptr(pose_out, f32), _opt(stats), _opt(status, i32),
+                                 current_stream()))
+    return pose_out
+
+
+STATUS_HYP_NO_SCORE = 64  # DIM_STATUS_HYP_NO_SCORE: dim_pose_score had < 64 counted pixels, a constant plane or a non-finite sum
 HYP_SCORE_ID = {"rgb": 0, "depth": 1}   # DIM_HYP_SCORE_RGB / DIM_HYP_SCORE_DEPTH
 
 
