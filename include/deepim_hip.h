@@ -45,6 +45,7 @@ extern "C" {
 #define DIM_STATUS_LAYER_HIDDEN 256 /* dim_scene_compose: a used layer won no pixel (empty or wholly hidden); per layer, (N*S) words */
 #define DIM_STATUS_COARSE_BAD_BOX 512 /* dim_pose_from_box: a bad box, a class without points, a point behind the camera or a non-finite scale (fallback row) */
 #define DIM_STATUS_PHOTO_FEW_POINTS 1024 /* dim_photo_refine: an iteration had fewer than 64 weighted points or a singular system, or the pair has no usable template (no update) */
+#define DIM_STATUS_SIL_FEW_POINTS 2048 /* dim_sil_refine: an iteration had fewer than 64 weighted contour points or a singular system (no update) */
 
 const char* dim_last_error(void);
 /* library / device probe: fills name (<= n bytes), returns number of compute units or <0 */
@@ -271,6 +272,49 @@ long dim_photo_workspace_offset(int B, int H, int W, int levels, int plane, int 
 int dim_photo_refine(const float* image_observed, const float* image_rendered, const float* depth_rendered, const int* bbox,
                      const float* pose_in, const float* K9, const float* K_per_sample, int B, int H, int W, int levels, int iters,
                      float huber, float gate, int gain, void* workspace, float* pose_out, float* stats, int* status, void* stream);
+
+/* ---------------------------------------------------------------- silhouette pose polish after the refinement loop (RGB test time)
+ * Contour alignment for textureless objects: the outline of the render at a pose is pulled onto the edge of a segmentation mask
+ * (a detector's, or the network's own mask head).  Restated by tests/sil_reference.py.  A polish for a pose that is already within a
+ * few degrees and pixels; a silhouette constrains depth, and rotation about the axes of near-symmetric outlines, only weakly.
+ *
+ * dim_sil_edge_field: mask (B,1,H,W) f32 -> field (B,H,W) int32, the exact nearest edge pixel of every pixel within `radius`.
+ *   A pixel is foreground when m >= 0.5 (a NaN is background).  An edge pixel is a foreground pixel with at least one 4-neighbour
+ *   inside the frame that is background; neighbours outside the frame count as foreground, so an object cut by the image border grows
+ *   no edge along the border.  field[b,y,x] = (ey << 16) | ex of the edge pixel of pair b that minimises the key (dx^2 + dy^2, ex, ey)
+ *   lexicographically among the edge pixels with dx^2 + dy^2 <= radius^2, or -1 when there is none.  Integer arithmetic throughout:
+ *   the result is exact and has no ties.  Two launches (columns, then rows; the column pass leaves its nearest edge row per pixel in
+ *   `field` itself and the row pass rewrites each row in place, so no scratch is needed), no atomics: a replay is bit-identical.
+ *   1 <= radius <= 64, H and W in 3 .. 32767, B in 1 .. 65535; otherwise, or with a NULL pointer, DIM_ERR_ARG before anything is
+ *   enqueued.
+ *
+ * dim_sil_refine: `iters` fixed Gauss-Newton iterations (no early exit: graph-capturable) per pair b.
+ *   depth_rendered (B,1,H,W) metres, 0 = background, rendered at pose_in (B,3,4) = T0; field (B,H,W) from dim_sil_edge_field; bbox,
+ *   K9 / K_per_sample, stats, status and the workspace as dim_flow_pnp: bbox[b] (B,4 int32 {min_x,max_x,min_y,max_y} inclusive,
+ *   clipped to the frame; NULL = whole frame), K_per_sample (B,9) device f32 or NULL = K9 (host, 9 floats) for every pair, a
+ *   non-positive or non-finite focal length gives the pair no points.
+ *   Contour points: a pixel (x, y) inside the clipped box with depth > 0 and at least one 4-neighbour inside the frame (not
+ *   necessarily inside the box) whose depth is not > 0; the frame-border rule is that of the field.  p0 = d ((x-cx)/fx, (y-cy)/fy, 1).
+ *   T = [R | t] starts at the identity.  Each iteration: m = R p0 + t (m_z <= 0: dropped), (u, v) = (fx m_x/m_z + cx, fy m_y/m_z + cy),
+ *   xi = floor(u + 0.5), yi = floor(v + 0.5) (outside the frame: dropped), f = field[b, yi, xi] (f < 0: dropped), (ex, ey) its edge
+ *   pixel, r = (u - ex, v - ey), e = |r|, w = 0 for e > max_px, 1 for e <= huber_px, huber_px / e between.  Jacobian rows in the left
+ *   twist (omega, v) with dm = omega x m + v, (A + 1e-9 tr(A)/6 I) xi = -sum w J r by float64 Cholesky, T <- [Rodrigues(omega) | v] T
+ *   -- the arithmetic of dim_flow_pnp.  Fewer than 64 points with w > 0 or a non-positive-definite A: no update,
+ *   DIM_STATUS_SIL_FEW_POINTS is OR-ed into status[b] (B int32, may be NULL), and the later iterations still run.
+ *   Matching is one-directional, render to mask: an occluded mask only loses points to the gate.
+ * pose_out (B,3,4) f32 = T T0; a pair that never updated gets pose_in bit for bit.  stats (B, iters, 2) f32 or NULL = (points with
+ * w > 0, rms of e over them in pixels) of every iteration before its update.
+ * workspace: dim_sil_workspace_bytes(B, H, W) bytes = B (16 + 16 x 32) doubles (0 for B <= 0), 8-byte aligned, no initialisation needed.
+ * Arithmetic: float64 per point, per lane, across lanes, waves and workgroups in a fixed order; the box is scanned in every
+ * iteration and its contour pixels are compacted by position (no atomics): a replay is bit-identical.  Two launches per iteration;
+ * iters == 0 copies pose_in to pose_out.  B outside 1 .. 65535, iters < 0, huber_px <= 0, max_px < huber_px, H or W outside
+ * 3 .. 32767 (a field word holds 16 bits per coordinate) or a NULL required pointer (depth_rendered, field, pose_in, K9, workspace,
+ * pose_out) return DIM_ERR_ARG before anything is enqueued. */
+int dim_sil_edge_field(const float* mask, int B, int H, int W, int radius, int* field, void* stream);
+long dim_sil_workspace_bytes(int B, int H, int W);
+int dim_sil_refine(const float* depth_rendered, const int* field, const int* bbox, const float* pose_in, const float* K9,
+                   const float* K_per_sample, int B, int H, int W, int iters, float huber_px, float max_px, void* workspace,
+                   float* pose_out, float* stats, int* status, void* stream);
 
 /* ---------------------------------------------------------------- multi-hypothesis refinement (several starting poses per pair)
  * Samples are pair-major: sample b = p * N + h of P pairs with N hypotheses each.  Restated in float64 by tests/hyp_reference.py.

@@ -1,5 +1,5 @@
 // Float64 sums across lanes in an order that never changes, so that a replay is bit-identical: the workgroup sum of the accumulate
-// kernels (icp.hip, flow_pnp.hip, photo.hip, vsd.hip) and the 64-lane butterflies (hyp.hip, metrics.hip).
+// kernels (icp.hip, flow_pnp.hip, photo.hip, sil.hip, vsd.hip) and the 64-lane butterflies (hyp.hip, metrics.hip).
 #pragma once
 #include "common.h"
 

@@ -1,4 +1,4 @@
-// Float64 device helpers shared by the Gauss-Newton pose stages (icp.hip, flow_pnp.hip, photo.hip) and the pose algebra (se3.hip): the 6x6
+// Float64 device helpers shared by the Gauss-Newton pose stages (icp.hip, flow_pnp.hip, photo.hip, sil.hip) and the pose algebra (se3.hip): the 6x6
 // Cholesky solve of the normal equations, the Rodrigues rotation of a twist's omega, and rotation matrix -> quaternion; and what
 // the Gauss-Newton stages have in common: the workspace layout, the camera and box of a pair, and the solve kernel.
 #pragma once
@@ -10,7 +10,7 @@ namespace dim {
 // and gn_solve_kernel, one workgroup per pair, adds them in order.  Workspace: [state B x kGnState][partial B x kGnBlocks x kGnSlot]
 constexpr int kGnBlocks = 16;      // workgroups per pair: 4096 lanes over the bbox (a LINEMOD object covers 5k-80k pixels)
 constexpr int kGnTerms = 29;       // 21 upper-triangle entries of sum J J^T, 6 of sum J r, point count, sum of squared residuals
-                                   // (terms 27 and 28 only feed stats and the point test: icp.hip and flow_pnp.hip put the unweighted
+                                   // (terms 27 and 28 only feed stats and the point test: icp.hip, flow_pnp.hip and sil.hip put the unweighted
                                    // sum of r^2 over the counted points into 28, photo.hip the weighted one, sum of w r^2)
 constexpr int kGnSlot = 32;        // doubles per partial (padded)
 constexpr int kGnState = 16;       // doubles per pair: R (9), t (3), updated (1), pad

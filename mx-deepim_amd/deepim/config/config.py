@@ -79,6 +79,11 @@ def _defaults():
                    # Gauss-Newton iterations per pyramid level (0 = off), pyramid levels (1..5), the Huber knee and the hard gate in
                    # units of the channel sum (three times a gray level), one gain and bias per pair
                    PHOTO_ITER=0, PHOTO_LEVELS=3, PHOTO_HUBER=30.0, PHOTO_MAX=180.0, PHOTO_GAIN=True,
+                   # silhouette polish after the loop (dim_sil_refine; for textureless objects, a polish of a pose within a few degrees and
+                   # pixels): Gauss-Newton iterations per round (0 = off), rounds (1..8; each renders the contour again at its pose), the
+                   # Huber knee and the hard gate in pixels (the edge field reaches ceil(SIL_MAX_PX) <= 64 pixels), and the mask whose
+                   # edge the contour is pulled onto: "observed" = the mask_observed handed to load(), "pred" = the mask head's last output
+                   SIL_ITER=0, SIL_ROUNDS=2, SIL_HUBER_PX=2.0, SIL_MAX_PX=12.0, SIL_MASK="observed",
                    # pose from the flow head's output at every loop iteration (dim_flow_pnp; needs PRED_FLOW and the full graph):
                    # Gauss-Newton iterations (0 = off), how many of them are unweighted, the Huber knee and the hard gate (pixels)
                    FLOW_PNP_ITER=0, FLOW_PNP_WARM=2, FLOW_PNP_HUBER_PX=2.0, FLOW_PNP_MAX_PX=8.0,

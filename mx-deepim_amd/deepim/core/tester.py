@@ -123,6 +123,37 @@ def photo_settings(cfg):
     return int(n), int(levels), huber, gate, bool(gain)
 
 
+def sil_settings(cfg):
+    """-> (SIL_ITER, SIL_ROUNDS, SIL_HUBER_PX, SIL_MAX_PX, SIL_MASK) of cfg.TEST, checked; ValueError names the bad key(s).
+    SIL_ITER counts Gauss-Newton iterations per round (0 = off); the two thresholds are in pixels, and the edge field reaches
+    ceil(SIL_MAX_PX) <= 64 pixels.  Selecting among polished hypotheses is not defined, so the stage is refused together with
+    HYP_NUM > 1 and COARSE_VIEWS > 0; SIL_MASK 'pred' needs the mask head's output, which only the full graph computes."""
+    T = cfg.TEST
+    n = T.get("SIL_ITER", 0) or 0
+    if isinstance(n, bool) or not float(n).is_integer() or int(n) < 0:
+        raise ValueError("TEST.SIL_ITER must be an integer >= 0 (iterations per round, 0 = off), got {!r}".format(n))
+    rounds = T.get("SIL_ROUNDS", 2)
+    if isinstance(rounds, bool) or not float(rounds).is_integer() or not 1 <= int(rounds) <= 8:
+        raise ValueError("TEST.SIL_ROUNDS must be an integer in 1..8, got {!r}".format(rounds))
+    huber, gate = float(T.get("SIL_HUBER_PX", 2.0)), float(T.get("SIL_MAX_PX", 12.0))
+    if not (np.isfinite(huber) and huber > 0):
+        raise ValueError("TEST.SIL_HUBER_PX must be a finite number > 0 (pixels), got {!r}".format(T.get("SIL_HUBER_PX")))
+    if not (np.isfinite(gate) and huber <= gate <= 64):
+        raise ValueError("TEST.SIL_MAX_PX must be finite, >= TEST.SIL_HUBER_PX and <= 64 (pixels), got {!r}".format(T.get("SIL_MAX_PX")))
+    which = T.get("SIL_MASK", "observed")
+    if which not in ("observed", "pred"):
+        raise ValueError("TEST.SIL_MASK must be 'observed' or 'pred', got {!r}".format(which))
+    if int(n) > 0:
+        if int(T.get("HYP_NUM", 1) or 1) > 1:
+            raise ValueError("TEST.SIL_ITER > 0 cannot be combined with TEST.HYP_NUM > 1")
+        if int(T.get("COARSE_VIEWS", 0) or 0) > 0:
+            raise ValueError("TEST.SIL_ITER > 0 cannot be combined with TEST.COARSE_VIEWS > 0")
+        if which == "pred" and not (cfg.network.PRED_MASK and not T.FAST_TEST):
+            raise ValueError("TEST.SIL_ITER > 0 with TEST.SIL_MASK 'pred' needs the mask head of the full graph "
+                             "(network.PRED_MASK, TEST.FAST_TEST off)")
+    return int(n), int(rounds), huber, gate, str(which)
+
+
 def hypothesis_rotations(N, rot_deg):
     """(N,3,3) float64: R_0 = I; R_h (h >= 1) = the Rodrigues rotation by rot_deg about axis h-1 of a Fibonacci sphere of N-1 points,
     z = 1 - (2k+1)/(N-1), r = sqrt(1-z^2), phi = k pi (3 - sqrt 5), axis = (r cos phi, r sin phi, z).  Hypothesis h starts the
@@ -148,7 +179,7 @@ def refuse_at_source_size(cfg, size, lit=False):
     on = [("TEST.ICP_ITER", int(T.get("ICP_ITER", 0) or 0) > 0), ("TEST.HYP_NUM", int(T.get("HYP_NUM", 1) or 1) > 1),
           ("TEST.COARSE_VIEWS", int(T.get("COARSE_VIEWS", 0) or 0) > 0), ("TEST.VSD", bool(T.get("VSD", False))),
           ("TEST.BOP_VSD", bool(T.get("BOP_VSD", False))), ("TEST.FLOW_PNP_ITER", int(T.get("FLOW_PNP_ITER", 0) or 0) > 0),
-          ("TEST.PHOTO_ITER", int(T.get("PHOTO_ITER", 0) or 0) > 0),
+          ("TEST.PHOTO_ITER", int(T.get("PHOTO_ITER", 0) or 0) > 0), ("TEST.SIL_ITER", int(T.get("SIL_ITER", 0) or 0) > 0),
           ("network.PRED_FLOW without TEST.FAST_TEST (the test-time flow error)", bool(cfg.network.PRED_FLOW and not T.FAST_TEST)),
           ("the lit ModelNet renderer", bool(lit))]
     for key, active in on:
@@ -194,6 +225,9 @@ class Refiner(object):
         self.photo_iter, self.photo_levels, self.photo_huber, self.photo_gate, self.photo_gain = photo_settings(cfg)
         if self.photo_iter > 0 and hasattr(render_machine, "normals"):
             raise ValueError("TEST.PHOTO_ITER > 0 is not supported with the lit ModelNet renderer")
+        self.sil_iter, self.sil_rounds, self.sil_huber, self.sil_gate, self.sil_mask = sil_settings(cfg)
+        if self.sil_iter > 0 and hasattr(render_machine, "normals"):
+            raise ValueError("TEST.SIL_ITER > 0 is not supported with the lit ModelNet renderer")
         N = self.hyp_num
         if N > 1 and predictor.net.B != batch_size * N:
             raise ValueError("Refiner: {} pairs x TEST.HYP_NUM {} = {} samples, but the Predictor was built for {} samples".format(
@@ -281,6 +315,25 @@ class Refiner(object):
             self.photo_stats = torch.zeros((B, self.photo_levels * self.photo_iter, 2), dtype=torch.float32, device=d)
             self.status_photo = torch.zeros((B,), dtype=torch.int32, device=d)
             self.photo_work = ops.photo_workspace(B, H, W, self.photo_levels, d)
+        # silhouette polish after the loop (TEST.SIL_ITER > 0): the edge field of the stage's mask, the depth and box rendered at every
+        # round's pose, the pose after every round (the last one is pose_sil); nothing is allocated when the stage is off
+        self.pose_sil = self.sil_stats = self.status_sil = None
+        if self.sil_iter > 0:
+            if self.sil_mask == "pred" and self.mask_pred_iter is None:
+                raise ValueError("TEST.SIL_ITER > 0 with TEST.SIL_MASK 'pred': the network has no mask head (network.PRED_MASK with a "
+                                 "decoder, TEST.FAST_TEST off)")
+            if self.sil_mask == "observed":   # a private copy: the loop rewrites its own mask_observed (UPDATE_MASK 'box_rendered')
+                self.mask_sil = torch.zeros((B, 1, H, W), dtype=torch.float32, device=d)
+            self.sil_radius = int(np.ceil(self.sil_gate))
+            self.field_sil = torch.zeros((B, H, W), dtype=torch.int32, device=d)
+            self.depth_sil = torch.zeros((B, 1, H, W), dtype=torch.float32, device=d)
+            self.bbox_sil = torch.zeros((B, 4), dtype=torch.int32, device=d)
+            self.pose_sil_round = torch.zeros((self.sil_rounds, B, 3, 4), dtype=torch.float32, device=d)
+            self.pose_sil = self.pose_sil_round[self.sil_rounds - 1]
+            self.sil_stats_round = torch.zeros((B, self.sil_iter, 2), dtype=torch.float32, device=d)
+            self.sil_stats = torch.zeros((B, self.sil_rounds * self.sil_iter, 2), dtype=torch.float32, device=d)
+            self.status_sil = torch.zeros((B,), dtype=torch.int32, device=d)
+            self.sil_work = ops.sil_workspace(B, H, W, d)
         # pose from the flow head's output at every iteration (TEST.FLOW_PNP_ITER > 0): the depth of the render each forward looked
         # at (INPUT_DEPTH graphs hold it already), the box of the initial render, and the per-iteration outputs
         self.pose_flow_iter = self.se3_flow_iter = self.flow_pnp_stats = self.status_flow = None
@@ -355,6 +408,12 @@ class Refiner(object):
         if det_boxes is not None:
             raise ValueError("det_boxes needs TEST.COARSE_VIEWS > 0")
         self._check_hyp_poses(hyp_poses)
+        if self.sil_iter > 0 and self.sil_mask == "observed":
+            # taken from the caller's segmentation itself, before any INIT_MASK kind replaces the loop's mask by a box
+            if mask_observed is None:
+                raise ValueError("TEST.SIL_ITER > 0 with TEST.SIL_MASK 'observed': load() needs mask_observed, the segmentation whose "
+                                 "edge the contour is pulled onto")
+            self.mask_sil.copy_(torch.as_tensor(mask_observed).reshape(self.mask_sil.shape))
         self._load_K(K)
         b = self.batch
         dst = self._load_targets()
@@ -491,6 +550,9 @@ class Refiner(object):
         into the resident blobs by dim_test_blobs_from_raw / dim_box_mask on the current stream -- no host blobs, no extra copies"""
         if self.coarse is not None:
             raise ValueError("TEST.COARSE_VIEWS > 0: the staged batches carry no detection boxes, use load(..., det_boxes=)")
+        if self.sil_iter > 0 and self.sil_mask == "observed":
+            raise ValueError("TEST.SIL_ITER > 0 with TEST.SIL_MASK 'observed': a staged batch carries the TEST.INIT_MASK mask of the loop, "
+                             "not a segmentation; use load(..., mask_observed=)")
         dst = self._load_targets()
         out = {k: dst[k] for k in ("image_observed", "image_rendered", "mask_rendered", "mask_observed")}
         if self.depth_observed is not None:
@@ -592,6 +654,8 @@ class Refiner(object):
             self._icp(self.poses_iter[self.test_iter - 1])
         if self.photo_iter > 0:   # independent of the ICP: both start from the loop's last pose
             self._photo(self.poses_iter[self.test_iter - 1])
+        if self.sil_iter > 0:     # likewise independent of the other two
+            self._sil(self.poses_iter[self.test_iter - 1])
         if self.N > 1:
             self._select(self.poses_iter[self.test_iter - 1])
 
@@ -637,10 +701,32 @@ class Refiner(object):
                          self.photo_iter, self.photo_huber, self.photo_gate, gain=self.photo_gain, bbox=self.bbox_photo, K_per_sample=K_pair,
                          pose_out=self.pose_photo, stats=self.photo_stats, status=self.status_photo, workspace=self.photo_work)
 
+    def _sil(self, pose):
+        """silhouette polish from the loop's last pose: the edge field of the stage's mask once (radius ceil(SIL_MAX_PX)), then
+        SIL_ROUNDS rounds, each rendering depth and box at the current pose (the pair's K when loaded) and running dim_sil_refine
+        from it -> pose_sil, sil_stats (B,SIL_ROUNDS*SIL_ITER,2), status_sil (render bits and DIM_STATUS_SIL_FEW_POINTS)"""
+        b = self.batch
+        ops.fill(self.status_sil, 0)
+        K_pair = self.K_pair if self.per_pair_K else None
+        extra = {"K": K_pair} if K_pair is not None else {}
+        mask = self.mask_sil if self.sil_mask == "observed" else self.mask_pred_iter[self.test_iter - 1]
+        ops.sil_edge_field(mask, self.sil_radius, field=self.field_sil)
+        n = 2 * self.sil_iter   # floats per pair and round
+        flat = self.sil_stats.view(-1)
+        for r in range(self.sil_rounds):
+            self.render_machine.render_batch(b["class_index"], pose, depth=self.depth_sil, bbox=self.bbox_sil, mask_thr=0.0,
+                                             status=self.status_sil, **extra)
+            ops.sil_refine(self.depth_sil, self.field_sil, pose, self.render_machine.K, self.sil_iter, self.sil_huber, self.sil_gate,
+                           bbox=self.bbox_sil, K_per_sample=K_pair, pose_out=self.pose_sil_round[r], stats=self.sil_stats_round,
+                           status=self.status_sil, workspace=self.sil_work)
+            ops.copy_rows(flat[r * n:], self.sil_rounds * n, self.sil_stats_round, n, self.B, n)
+            pose = self.pose_sil_round[r]
+
     def refine(self):
         """run test_iter iterations on the loaded batch; returns poses_iter (test_iter,B,3,4) (device).  With TEST.ICP_ITER > 0 the
         ICP stage runs after them (inside the same graph) and leaves its pose in pose_icp (B,3,4); with TEST.PHOTO_ITER > 0 the
-        photometric polish does the same from the same last pose and leaves pose_photo (B,3,4).  With TEST.FLOW_PNP_ITER > 0 every
+        photometric polish does the same from the same last pose and leaves pose_photo (B,3,4), and with TEST.SIL_ITER > 0 the
+        silhouette polish leaves pose_sil (B,3,4).  With TEST.FLOW_PNP_ITER > 0 every
         iteration also solves the pose from its flow head's output (dim_flow_pnp, inside the same graph): pose_flow_iter
         (test_iter,B,3,4), se3_flow_iter (test_iter,B,7), flow_pnp_stats (test_iter,B,FLOW_PNP_ITER,2), status_flow (test_iter,B);
         the loop itself never reads them.  With TEST.HYP_NUM > 1 it returns
@@ -880,6 +966,7 @@ def pred_eval(config, refiner, batches, evaluator, result_file=None, logger=None
     under out["photo"] = {pose, add, arp_2d} (the host error functions, or dim_pose_errors under TEST.DEVICE_EVAL; one more copy per
     batch); every other output and the result cache are those of the stage off.  Scoring that row by TEST.VSD / TEST.BOP is left out:
     the combination raises a ValueError.
+    With TEST.SIL_ITER > 0 the silhouette-polished poses (pose_sil) are scored exactly so under out["sil"], with the same refusals.
     With TEST.HYP_NUM = N > 1 every table, the result cache and out["icp"] score the selected hypothesis of each pair, and out["hyp"]
     holds per pair the N scores, the choice and the last-iteration rotation / translation error of every hypothesis, plus the rate
     at which the chosen hypothesis is also the one with the least rotation error.  A batch may carry "hyp_poses" (P,N,3,4).
@@ -928,7 +1015,7 @@ def pred_eval(config, refiner, batches, evaluator, result_file=None, logger=None
 
 def _eval_setup(config, refiner, evaluator, logger):
     """what one pred_eval call holds: the switches, the device scorers and `store`, every list it collects under its name --
-    (pose set, family) -> ScoreLists for the sets "loop", "icp", "flow_pnp" and "photo" and the families of FAMILY_KEYS, and the per-pair
+    (pose set, family) -> ScoreLists for the sets "loop", "icp", "flow_pnp", "photo" and "sil" and the families of FAMILY_KEYS, and the per-pair
     "hyp", "flow_rows" and "coarse" -> PairLists.  A name is there only when its feature is on."""
     from types import SimpleNamespace
 
@@ -938,10 +1025,12 @@ def _eval_setup(config, refiner, evaluator, logger):
                          with_icp=int(T.get("ICP_ITER", 0) or 0) > 0, n_hyp=int(getattr(refiner, "N", 1)),
                          device_eval=bool(T.get("DEVICE_EVAL", False)), with_flow=int(T.get("FLOW_PNP_ITER", 0) or 0) > 0,
                          with_coarse=getattr(refiner, "coarse", None) is not None, vsd=None, bop=None,
-                         with_photo=int(T.get("PHOTO_ITER", 0) or 0) > 0,
+                         with_photo=int(T.get("PHOTO_ITER", 0) or 0) > 0, with_sil=int(T.get("SIL_ITER", 0) or 0) > 0,
                          vsd_who="TEST.VSD" if bool(T.get("VSD", False)) else "TEST.BOP_VSD")
     if st.with_photo and (bool(T.get("VSD", False)) or bool(T.get("BOP", False))):
         raise ValueError("TEST.PHOTO_ITER > 0 cannot be combined with TEST.VSD or TEST.BOP (the photometric row is not scored there)")
+    if st.with_sil and (bool(T.get("VSD", False)) or bool(T.get("BOP", False))):
+        raise ValueError("TEST.SIL_ITER > 0 cannot be combined with TEST.VSD or TEST.BOP (the silhouette row is not scored there)")
     if st.device_eval:
         from lib.dataset.evaluation import SYM_CLASSES
 
@@ -963,6 +1052,8 @@ def _eval_setup(config, refiner, evaluator, logger):
         sets.append(("flow_pnp", st.n_it, [f for f in families if f in ("rt", "err")]))
     if st.with_photo:  # one row, as the ICP pose; by the error code alone
         sets.append(("photo", 1, [f for f in families if f in ("rt", "err")]))
+    if st.with_sil:    # likewise
+        sets.append(("sil", 1, [f for f in families if f in ("rt", "err")]))
     st.store = {(name, f): ScoreLists(FAMILY_KEYS[f], st.n_cls, iters) for name, iters, fams in sets for f in fams}
     st.scored = list(st.store)
     if st.n_hyp > 1:
@@ -1037,10 +1128,10 @@ def _read_out_flow(st, refiner, cls_dev, gt_dev):
     return host
 
 
-def _read_out_photo(st, refiner, cls_dev, gt_dev):
-    """one more copy per batch with TEST.PHOTO_ITER > 0: the polished poses [and their device errors] -> {pose (1, P, 3, 4),
-    [err (1, P, 5)]}"""
-    pose = refiner.pose_photo
+def _read_out_photo(st, refiner, cls_dev, gt_dev, pose=None):
+    """one more copy per batch with TEST.PHOTO_ITER > 0 (and one with TEST.SIL_ITER > 0, `pose` = pose_sil): the polished poses [and
+    their device errors] -> {pose (1, P, 3, 4), [err (1, P, 5)]}"""
+    pose = refiner.pose_photo if pose is None else pose
     columns = [("pose", 12, pose.to(torch.float64)[None])]
     if st.device_eval:
         t = st.tables
@@ -1109,6 +1200,8 @@ def _collect_batch(st, refiner, batch):
         by_set["flow_pnp"] = _read_out_flow(st, refiner, cls_dev, gt_dev)
     if st.with_photo:
         by_set["photo"] = _read_out_photo(st, refiner, cls_dev, gt_dev)
+    if st.with_sil:
+        by_set["sil"] = _read_out_photo(st, refiner, cls_dev, gt_dev, pose=refiner.pose_sil)
     cls = torch.as_tensor(batch["class_index"]).cpu().numpy().astype(int)
     gt = torch.as_tensor(batch["pose_observed"]).cpu().numpy().astype(np.float64)
     src = torch.as_tensor(batch["src_pose"]).cpu().numpy().astype(np.float64)
@@ -1217,6 +1310,13 @@ def _tables(st, result_file, merge_ranks, merged):
             int(config.TEST.get("PHOTO_LEVELS", 3)), int(config.TEST.PHOTO_ITER), float(config.TEST.get("PHOTO_HUBER", 30.0)),
             float(config.TEST.get("PHOTO_MAX", 180.0))))
         out["photo"] = _pose_tables(st, cfg1, "photo")
+    if st.with_sil:     # one row, scored as the ICP row is
+        cfg1 = copy.deepcopy(config)
+        cfg1.TEST.test_iter = 1
+        _say(logger, "evaluate silhouette polish ({} rounds x {} iterations, Huber {} px, gate {} px, mask {}):".format(
+            int(config.TEST.get("SIL_ROUNDS", 2)), int(config.TEST.SIL_ITER), float(config.TEST.get("SIL_HUBER_PX", 2.0)),
+            float(config.TEST.get("SIL_MAX_PX", 12.0)), config.TEST.get("SIL_MASK", "observed")))
+        out["sil"] = _pose_tables(st, cfg1, "sil")
     if st.with_flow:
         _say(logger, "evaluate pose from flow ({} iterations, {} unweighted, Huber {} px, gate {} px):".format(
             int(config.TEST.FLOW_PNP_ITER), int(config.TEST.FLOW_PNP_WARM), float(config.TEST.FLOW_PNP_HUBER_PX), float(config.TEST.FLOW_PNP_MAX_PX)))

@@ -52,6 +52,9 @@ SIGNATURES = {
     "dim_photo_workspace_bytes": (L, [I, I, I, I]),
     "dim_photo_workspace_offset": (L, [I, I, I, I, I, I]),
     "dim_photo_refine": (I, [P, P, P, P, P, P, P, I, I, I, I, I, F, F, I, P, P, P, P, P]),
+    "dim_sil_edge_field": (I, [P, I, I, I, I, P, P]),
+    "dim_sil_workspace_bytes": (L, [I, I, I]),
+    "dim_sil_refine": (I, [P, P, P, P, P, P, I, I, I, I, F, F, P, P, P, P, P]),
     "dim_hyp_expand": (I, [P, P, I, I, P, P]),
     "dim_hyp_broadcast": (I, [P, P, I, I, L, P]),
     "dim_pose_score_workspace_bytes": (L, [I, I, I]),

@@ -422,6 +422,46 @@ def photo_refine(image_observed, image_rendered, depth_rendered, pose_in, K, lev
     return pose_out
 
 
+STATUS_SIL_FEW_POINTS = 2048   # DIM_STATUS_SIL_FEW_POINTS: a silhouette iteration had < 64 weighted contour points or a singular system
+
+
+def sil_edge_field(mask, radius, field=None):
+    """nearest-edge field of dim_sil_edge_field (restated by tests/sil_reference.py): mask (B,1,H,W) f32, foreground where >= 0.5
+    -> field (B,H,W) int32 = (ey << 16) | ex of the nearest edge pixel within `radius` (1..64) pixels, -1 where there is none"""
+    B, C, H, W = mask.shape
+    assert C == 1
+    field = field if field is not None else _new((B, H, W), mask, i32)
+    assert tuple(field.shape) == (B, H, W)
+    check(lib().dim_sil_edge_field(dptr(mask, f32), B, H, W, int(radius), dptr(field, i32), current_stream()))
+    return field
+
+
+def sil_workspace(B, H, W, device):
+    return _workspace_f64(lib().dim_sil_workspace_bytes(B, H, W), device)
+
+
+def sil_refine(depth_rendered, field, pose_in, K, iters, huber_px, max_px, bbox=None, K_per_sample=None, pose_out=None, stats=None,
+               status=None, workspace=None):
+    """silhouette pose polish of dim_sil_refine (restated by tests/sil_reference.py): the contour pixels of depth_rendered (B,1,H,W),
+    rendered at pose_in (B,3,4), are pulled onto the edge pixels of field (B,H,W) int32 (sil_edge_field) by `iters` Gauss-Newton
+    iterations, Huber knee and hard gate in pixels; K / K_per_sample / bbox as flow_pnp.  -> pose_out (B,3,4); stats (B,iters,2) =
+    (weighted points, rms pixel distance) per iteration; status (B,) int32: DIM_STATUS_SIL_FEW_POINTS is OR-ed in."""
+    B, _, H, W = depth_rendered.shape
+    assert tuple(depth_rendered.shape) == (B, 1, H, W) and tuple(field.shape) == (B, H, W) and tuple(pose_in.shape) == (B, 3, 4)
+    assert stats is None or stats.numel() >= 2 * B * int(iters)
+    assert (status is None or status.numel() == B) and (bbox is None or bbox.numel() == 4 * B)
+    pose_out = pose_out if pose_out is not None else _new((B, 3, 4), pose_in)
+    if workspace is None:
+        workspace = sil_workspace(B, H, W, pose_in.device)
+    assert workspace.numel() * workspace.element_size() >= lib().dim_sil_workspace_bytes(B, H, W)
+    kps = intrinsics_per_sample(K_per_sample, B, pose_in.device)
+    keep, kp = host_f32(K, 9)
+    check(lib().dim_sil_refine(dptr(depth_rendered, f32), dptr(field, i32), _opt(bbox, i32), dptr(pose_in, f32), kp, _opt(kps), B, H, W,
+                               int(iters), float(huber_px), float(max_px), dptr(workspace, torch.float64), dptr(pose_out, f32),
+                               _opt(stats), _opt(status, i32), current_stream()))
+    return pose_out
+
+
 STATUS_HYP_NO_SCORE = 64  # DIM_STATUS_HYP_NO_SCORE: dim_pose_score had < 64 counted pixels, a constant plane or a non-finite sum
 HYP_SCORE_ID = {"rgb": 0, "depth": 1}   # DIM_HYP_SCORE_RGB / DIM_HYP_SCORE_DEPTH
 
