@@ -706,6 +706,28 @@ int dim_winograd5x5s2_pack_weight(const float* w_oihw, float* w_packed, int Cout
 int dim_conv2d_fwd_winograd5x5s2(const float* x, const float* w_packed, const float* bias, float* y, float* workspace, int N, int H, int W,
                                  int Cin, int in_cstride, int Cout, int out_cstride, int out_coff, float slope, int tile, void** events4,
                                  void* stream);
+/* Equal live work per workgroup for the plane GEMMs of these layers (csrc/wino_balance.hip).  With the zero blocks skipped, a
+ * workgroup's range of the flat chunk list holds a full, a half or a quarter of its length in live chunks, by the planes it lies in.
+ * An item map is a permutation of the list's item slots that evens the live work out: ranges and cuts stay where they are, every slot
+ * with a cut inside stays in place, whole items change workgroups.  The output keeps its bits.
+ *   dim_wino_item_map_create   plans the layer (N, H, W, Cin, Cout, tile as dim_conv2d_fwd_winograd5x5s2 takes them), builds the table on
+ *                              the host and uploads it (hipMalloc + a blocking copy: call it where layers are planned, never while a
+ *                              stream is being captured).  *map is never NULL on DIM_OK; a map that gains nothing holds the identity.
+ *   dim_wino_item_map_query    header (12 ints: T, K, Cout, tile, G, per, rem, largest live work of a range before / after, slots that
+ *                              hold another item, items, chunks per item) and, when table != NULL, the items of all slots
+ *                              (capacity >= items ints) into host memory.
+ *   dim_wino_item_map_plan     the same answer for a GEMM shape without a map object: T rows, K = 4 Cin, tile, G workgroups (host
+ *                              arithmetic only, no device needed; G <= 0: the G a launch on the current device would take),
+ *                              skip5 = 0: the plan of a layer that multiplies every block (identity).
+ *   dim_conv2d_fwd_winograd5x5s2_map   the forward with a map (NULL: identity).  The map is used when the plan of the run is the one it
+ *                              was built for; any other run (another batch, a sliced run, the f32 matrix pipe) is the plain forward. */
+int dim_wino_item_map_create(void** map, int N, int H, int W, int Cin, int Cout, int tile);
+void dim_wino_item_map_destroy(void* map);
+int dim_wino_item_map_query(const void* map, int* header12, int* table, long capacity);
+int dim_wino_item_map_plan(int T, int K, int Cout, int tile, int G, int skip5, int* header12, int* table, long capacity);
+int dim_conv2d_fwd_winograd5x5s2_map(const float* x, const float* w_packed, const float* bias, float* y, float* workspace, int N, int H,
+                                     int W, int Cin, int in_cstride, int Cout, int out_cstride, int out_coff, float slope, int tile,
+                                     const void* item_map, void** events4, void* stream);
 /* Input gradient of the same 5x5 / stride-2 layers (training): dx (N,H,W,dx_cstride) = conv_transpose(dy (N,ceil(H/2),ceil(W/2),
  * dy_cstride), w) as ONE F(4x4,3x3) transform of dy, 36 GEMMs with K = Cout and N = 4 Cin (the four phase images of dx), and a
  * phase-scattering output transform; dx is overwritten.  Weights: dim_winograd5x5s2_dgrad_pack_weight from the same (Cout,Cin,5,5)

@@ -256,6 +256,10 @@ struct WGemmArgs {
   // zero by construction (wino5_phase_mask).  skip5 = 1: the cursors step over their chunks.  The flat chunk list, and with it every
   // range boundary, stays the one of the full K: an item is cut where it was cut before, the sums keep their bits.  Plane-major only.
   int skip5, q;
+  // item-slot table of the balanced 5x5 / stride-2 plans (wino_balance.hip), device memory: slot s of the flat list holds item sigma[s].
+  // NULL = identity.  Only wino_gemm_split_kernel reads it; a slot with a range boundary inside is a fixed point, so wino_gemm_zero_tile
+  // and the f32 kernel (which always gets NULL) decode slots as items.
+  const int* sigma;
 };
 // wino_gemm_split.hip.  Every packed Winograd weight buffer is [U f32][U3]: floats -> floats * 5 / 2
 inline long wino_packed_with_split(long u_floats) { return u_floats + (u_floats * 3 + 1) / 2; }
@@ -266,6 +270,23 @@ bool wino_gemm_split_has(int tile);
 int wino_gemm_split_slots(int tile);
 int wino_gemm_split_run(const WGemmArgs& a, hipStream_t st);
 int wino_gemm_plan(WGemmArgs* plan, const float* V, const float* U, float* M, int T, int K, int Cout, int P, int tile, int skip5 = 0);
+// the tile id wino_gemm_plan settles on for (tile, Cout) and its shape
+void wino_tile_shape(int* tile, int Cout, int* BM, int* BN);
+// wino_balance.hip: the item-slot permutation of a skipping plan (see there).  Header words as dim_wino_item_map_query returns them.
+enum { kMapT, kMapK, kMapCout, kMapTile, kMapG, kMapPer, kMapRem, kMapLiveBefore, kMapLiveAfter, kMapMoved, kMapItems, kMapNch, kMapWords };
+struct WinoItemMap {
+  int hdr[kMapWords];
+  int* host;  // hdr[kMapItems] entries
+  int* dev;   // the same in device memory; NULL when the table is the identity
+};
+int wino_item_map_build(int T, int K, int Cout, int tile, int G, int skip5, int* hdr, int** table);
+// the table for this plan, or NULL (no map, the f32 kernel, or a plan other than the one the map was built for: identity, correct, slower)
+inline const int* wino_item_map_for(const WinoItemMap* m, const WGemmArgs& a) {
+  if (!m || !m->dev || !a.split || !a.skip5) return nullptr;
+  const int* h = m->hdr;
+  return (h[kMapT] == a.T && h[kMapK] == a.K && h[kMapCout] == a.Cout && h[kMapTile] == a.tile && h[kMapG] == a.G && h[kMapPer] == a.per &&
+          h[kMapRem] == a.rem) ? m->dev : nullptr;
+}
 // zeroed = the shared tiles have been zeroed already (by the transform kernel that ran before): no separate zero launch
 int wino_gemm_run(const WGemmArgs& plan, bool zeroed, hipStream_t st);
 
@@ -280,6 +301,15 @@ int wino_gemm_run(const WGemmArgs& plan, bool zeroed, hipStream_t st);
 struct WCur {
   int ch, p, nt, mt;
   int m;  // wino5_phase_mask of plane p under skip5, else 0xF: planes without zero blocks pay one comparison per step
+  int s;  // slots behind the workgroup's first one (only kept under a WTab)
+};
+// a workgroup's window of WGemmArgs::sigma, loaded once before the chunk loop: lane i holds the item of slot s0 + i, and a cursor that
+// wraps to slot s0 + j reads it with v_readlane (no memory operation inside the loop: a scalar load there would share lgkmcnt with the
+// scheduled LDS traffic).  on = false: slots are items.  The builder keeps a range within 64 slots; the cursors that run ahead of the
+// range's end may read lanes past the window (readlane wraps), whose items only ever address rejected loads.
+struct WTab {
+  int v, s0;
+  bool on;
 };
 // phases (bit 2 py + px) of plane p = 6 a + b whose weight block is not zero: a sub-kernel of an odd phase has no third row / column and
 // the last row of G is [0 0 1], so a = 5 keeps py = 0 only and b = 5 keeps px = 0 only
@@ -292,13 +322,34 @@ __device__ __forceinline__ int wcur_snap(int ch, int m, const WGemmArgs& a) {
   const int r = m >> (ph + 1);  // ph + 1 <= 4
   return r ? (ph + 1 + __builtin_ctz(r)) * q : a.nch;
 }
+__device__ __forceinline__ WTab wtab_load(int r_begin, const WGemmArgs& a) {
+  WTab t;
+  t.on = true;
+  t.s0 = (int)fastdiv((unsigned)r_begin, a.d_nch);
+  const int s = t.s0 + (int)(threadIdx.x & 63);
+  t.v = s < a.P * a.MT * a.NTN ? a.sigma[s] : 0;
+  return t;
+}
+__device__ __forceinline__ int wtab_item(const WTab& t, int j) { return __builtin_amdgcn_readlane(t.v, j & 63); }
+// (p, mt, nt) and the phase mask of a plane-major item
+__device__ __forceinline__ void wcur_set_item(WCur& c, unsigned item, const WGemmArgs& a) {
+  const unsigned u = fastdiv(item, a.d_NTN);
+  c.nt = (int)(item - u * a.NTN);
+  const unsigned p = fastdiv(u, a.d_MT);
+  c.mt = (int)(u - p * a.MT);
+  c.p = (int)p;
+  c.m = a.skip5 ? wino5_phase_mask(c.p) : 0xF;
+}
 // one step in the plane-major order (the only order the split kernel and the skipping plans use)
-__device__ __forceinline__ void wcur_advance_pm(WCur& c, const WGemmArgs& a) {
+__device__ __forceinline__ void wcur_advance_pm(WCur& c, const WGemmArgs& a, const WTab& t = WTab{0, 0, false}) {
   ++c.ch;
   if (c.m != 0xF) c.ch = wcur_snap(c.ch, c.m, a);
   if (c.ch >= a.nch) {
     c.ch = 0;
-    if (++c.nt == a.NTN) {
+    if (t.on) {
+      ++c.s;
+      wcur_set_item(c, (unsigned)wtab_item(t, c.s), a);
+    } else if (++c.nt == a.NTN) {
       c.nt = 0;
       if (++c.mt == a.MT) {
         c.mt = 0;
@@ -332,22 +383,25 @@ __device__ __forceinline__ WCur wcur_decode_raw(int chunk, const WGemmArgs& a) {
   return c;
 }
 // the first multiplied chunk at or behind flat position `chunk`
-__device__ __forceinline__ WCur wcur_decode(int chunk, const WGemmArgs& a) {
+__device__ __forceinline__ WCur wcur_decode(int chunk, const WGemmArgs& a, const WTab& t = WTab{0, 0, false}) {
   WCur c = wcur_decode_raw(chunk, a);
+  c.s = 0;
   c.m = a.skip5 ? wino5_phase_mask(c.p) : 0xF;
+  if (t.on) wcur_set_item(c, (unsigned)wtab_item(t, 0), a);
   if (c.m != 0xF) {
     c.ch = wcur_snap(c.ch, c.m, a) - 1;
-    wcur_advance_pm(c, a);  // ch + 1, or on to chunk 0 of the next item
+    wcur_advance_pm(c, a, t);  // ch + 1, or on to chunk 0 of the next item
   }
   return c;
 }
 // multiplied chunks among the flat positions [begin, end)
-__device__ __forceinline__ int wcur_count(int begin, int end, const WGemmArgs& a) {
+__device__ __forceinline__ int wcur_count(int begin, int end, const WGemmArgs& a, const WTab& t = WTab{0, 0, false}) {
   if (!a.skip5) return end - begin;
   int n = 0;
   for (int v = begin; v < end;) {
-    const unsigned item = fastdiv((unsigned)v, a.d_nch);
-    const int base = (int)item * a.nch, lo = v - base, hi = min(end - base, a.nch);
+    const unsigned slot = fastdiv((unsigned)v, a.d_nch);
+    const int base = (int)slot * a.nch, lo = v - base, hi = min(end - base, a.nch);
+    const unsigned item = t.on ? (unsigned)wtab_item(t, (int)slot - t.s0) : slot;
     const int m = wino5_phase_mask((int)fastdiv(fastdiv(item, a.d_NTN), a.d_MT));
 #pragma unroll
     for (int ph = 0; ph < 4; ++ph)

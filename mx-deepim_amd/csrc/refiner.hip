@@ -34,6 +34,7 @@ struct LayerPlan {
   float* w_packed;
   float* bias;
   float* out;
+  void* item_map;  // kind 2: the item-slot table of the layer's plane GEMMs (dim_wino_item_map_create), made with the plan
 };
 
 }  // namespace dim
@@ -79,6 +80,7 @@ extern "C" {
 int dim_refiner_destroy(dim_refiner* r) {
   if (!r) return DIM_OK;
   for (void* p : r->allocs) (void)hipFree(p);
+  for (LayerPlan& P : r->L) dim_wino_item_map_destroy(P.item_map);
   delete r;
   return DIM_OK;
 }
@@ -169,6 +171,7 @@ static int refiner_create(dim_refiner** out, const dim_refiner_desc* desc, int n
       P.splits = 1;
       TRY(dev_alloc(r, (void**)&P.w_packed, (size_t)dim_winograd5x5s2_packed_weight_floats(ly.cout, c) * 4));
       TRY(dim_winograd5x5s2_pack_weight(wsrc, P.w_packed, ly.cout, c, stream));
+      TRY(dim_wino_item_map_create(&P.item_map, B, h, w, c, ly.cout, P.tile));
       max_ws = std::max(max_ws, dim_winograd5x5s2_workspace_floats(B, h, w, c, ly.cout));
     } else if (ly.k == 3 && ly.s == 2 && ly.p == 1 && dim_winograd3x3s2_use(h, w, c, ly.cout)) {
       P.kind = 3;
@@ -289,8 +292,8 @@ int dim_refiner_run_k(dim_refiner* r, const float* image_observed, const float* 
         TRY(dim_conv2d_fwd_winograd(x, P.w_packed, P.bias, P.out, r->workspace, B, P.h, P.w, P.cin, P.cin, ly.cout, ly.cout, 0, 0.1f, P.tile, 4,
                                     nullptr, stream));
       } else if (P.kind == 2) {
-        TRY(dim_conv2d_fwd_winograd5x5s2(x, P.w_packed, P.bias, P.out, r->workspace, B, P.h, P.w, P.cin, P.cin, ly.cout, ly.cout, 0, 0.1f,
-                                         P.tile, nullptr, stream));
+        TRY(dim_conv2d_fwd_winograd5x5s2_map(x, P.w_packed, P.bias, P.out, r->workspace, B, P.h, P.w, P.cin, P.cin, ly.cout, ly.cout, 0,
+                                             0.1f, P.tile, P.item_map, nullptr, stream));
       } else if (P.kind == 3) {
         TRY(dim_conv2d_fwd_winograd3x3s2(x, P.w_packed, P.bias, P.out, r->workspace, B, P.h, P.w, P.cin, P.cin, ly.cout, ly.cout, 0, 0.1f,
                                          P.tile, nullptr, stream));

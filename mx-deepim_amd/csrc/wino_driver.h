@@ -41,9 +41,10 @@ inline int wino_record_event(void** events4, int i, hipStream_t st) {
 //                                  tiles that two stream-K workgroups share
 //   launch_out(n0, n, T, M)        output transform of M into the slice's images
 // both return their check_launch.  events4: optional 4 hipEvent_t recorded around the three steps of the first slice.
+// map: optional item-slot table of the layer (wino_balance.hip); a slice whose plan is not the one it was built for runs without it.
 template <class Tile, class In, class Out>
 int wino_run_slices(const WinoGeom& g, const float* w_packed, float* workspace, Tile&& gemm_tile, int skip5, bool zeroed, void** events4,
-                    hipStream_t st, In&& launch_in, Out&& launch_out) {
+                    hipStream_t st, In&& launch_in, Out&& launch_out, const WinoItemMap* map = nullptr) {
   DIM_REQUIRE(g.n_slice > 0, "one image alone exceeds the 32-bit offsets of the plane GEMMs");
   int n_slice = g.n_slice;
   if (const char* e = getenv("DIM_WINO_MAX_SLICE")) {  // test hook: force the slicing path at sizes a unit test can check
@@ -58,6 +59,7 @@ int wino_run_slices(const WinoGeom& g, const float* w_packed, float* workspace, 
     void** ev = n0 == 0 ? events4 : nullptr;
     WGemmArgs plan;
     int rc = wino_gemm_plan(&plan, V, w_packed, M, (int)T, g.K, g.Nout, g.planes, gemm_tile(T), skip5);
+    if (rc == DIM_OK) plan.sigma = wino_item_map_for(map, plan);
     if (rc == DIM_OK) rc = wino_record_event(ev, 0, st);
     if (rc == DIM_OK) rc = launch_in(n0, n, T, plan, V);
     if (rc == DIM_OK) rc = wino_record_event(ev, 1, st);

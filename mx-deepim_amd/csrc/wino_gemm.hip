@@ -289,10 +289,16 @@ static int wino_gemm_slots() {
 
 // tile: 5 = 128x256 (8 waves, 64x64 per wave), 4 = 128x128 (8 waves), 6 = 160x128 and 7 = 96x128 (4 waves, every wave a 32-column strip
 // of all the rows: the few-row layers), anything else = 64x64 (4 waves)
+void wino_tile_shape(int* tile, int Cout, int* BM, int* BN) {
+  if (*tile == 5 && Cout % 256 != 0) *tile = 4;
+  if ((*tile < 4 || *tile > 7) || Cout % 128 != 0) *tile = 3;
+  *BM = *tile == 3 ? 64 : *tile == 6 ? 160 : *tile == 7 ? 96 : 128;
+  *BN = *tile == 5 ? 256 : *tile == 3 ? 64 : 128;
+}
+
 int wino_gemm_plan(WGemmArgs* plan, const float* V, const float* U, float* M, int T, int K, int Cout, int P, int tile, int skip5) {
-  if (tile == 5 && Cout % 256 != 0) tile = 4;
-  if ((tile < 4 || tile > 7) || Cout % 128 != 0) tile = 3;
-  const int BM = tile == 3 ? 64 : tile == 6 ? 160 : tile == 7 ? 96 : 128, BN = tile == 5 ? 256 : tile == 3 ? 64 : 128;
+  int BM, BN;
+  wino_tile_shape(&tile, Cout, &BM, &BN);
   DIM_REQUIRE(K % 32 == 0 && Cout % BN == 0 && T > 0, "winograd gemm: K %% 32 == 0 and Cout %% 64 == 0 required");
   const long MT = (T + BM - 1) / BM;
   const long items = MT * (Cout / BN) * P;
@@ -348,6 +354,10 @@ int wino_gemm_plan(WGemmArgs* plan, const float* V, const float* U, float* M, in
     if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&g_wino_cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) g_wino_cus = 0;
   }
   if (g_round && g_wino_cus > 0 && a.G > g_wino_cus && a.G < slots) a.G = a.G / g_wino_cus * g_wino_cus;
+  if (const char* e = getenv("DIM_WINO_MAX_G")) {  // test hook: ranges several items long at sizes a unit test can check
+    const int cap = atoi(e);
+    if (cap > 0 && cap < a.G) a.G = cap;
+  }
   const long total = items * a.nch;
   a.per = (int)(total / a.G);
   a.rem = (int)(total % a.G);

@@ -105,10 +105,12 @@ __device__ unsigned long long g_split_stamps[1024 * 8 * 11];
 #define S_STAMP(K)
 #endif
 
-__device__ __forceinline__ void wscur_advance(WCur& c, const WGemmArgs& a) { wcur_advance_pm(c, a); }
+__device__ __forceinline__ void wscur_advance(WCur& c, const WGemmArgs& a, const WTab& t) { wcur_advance_pm(c, a, t); }
 
-template <int BM, int WN>
-__global__ __launch_bounds__(WN * 64) __attribute__((amdgpu_waves_per_eu(2, 2))) void wino_gemm_split_kernel(WGemmArgs a) {
+// TAB: the launch has an item-slot table (WGemmArgs::sigma; wino_gemm_split_map_kernel).  Without one the cursors are the ones they
+// always were, at compile time (wino_gemm_split_kernel).
+template <int BM, int WN, bool TAB>
+__device__ __forceinline__ void wino_gemm_split_body(const WGemmArgs& a) {
   constexpr int BK = 32;
   constexpr int NT = WN * 64;
   constexpr int BN = 32 * WN;
@@ -138,7 +140,9 @@ __global__ __launch_bounds__(WN * 64) __attribute__((amdgpu_waves_per_eu(2, 2)))
   const int wg = wg_xcd_contiguous(blockIdx.x, a.G);
   // the range in flat positions; the loop below counts the chunks it multiplies (all of them unless a.skip5)
   const int r_begin = wg_first_chunk(wg, a);
-  const int c_begin = 0, c_end = wcur_count(r_begin, wg_first_chunk(wg + 1, a), a);
+  // the items of the range's slots (balanced 5x5 / stride-2 plans: wino_balance.hip), across the lanes of one register
+  const WTab tab = TAB ? wtab_load(r_begin, a) : WTab{0, 0, false};
+  const int c_begin = 0, c_end = wcur_count(r_begin, wg_first_chunk(wg + 1, a), a, tab);
   if (c_end == 0) return;
 
   const int RS = a.P * a.K;
@@ -149,7 +153,7 @@ __global__ __launch_bounds__(WN * 64) __attribute__((amdgpu_waves_per_eu(2, 2)))
   const __amdgpu_buffer_rsrc_t rm = __builtin_amdgcn_make_buffer_rsrc(a.M, 0, a.m_bytes, 0x00020000);
   const int wchunk_bytes = a.Cout * 192;
 
-  WCur L = wcur_decode(r_begin, a), Bc = L, C = L;
+  WCur L = wcur_decode(r_begin, a, tab), Bc = L, C = L;
 
   // staging registers of TWO chunks: a chunk's V loads are issued two iterations before its split (HBM latency under load is of the
   // order of one iteration of this kernel)
@@ -159,7 +163,7 @@ __global__ __launch_bounds__(WN * 64) __attribute__((amdgpu_waves_per_eu(2, 2)))
   const bool l_pf = (PF_OK);                                                           \
   const int l_mb = L.mt * BM;                                                          \
   const int l_soff = (int)((unsigned)(l_mb * RS + L.p * a.K + L.ch * BK) * 4u);        \
-  wscur_advance(L, a);
+  wscur_advance(L, a, tab);
 #define S_LOAD_ISSUE(RSET)                                                             \
   _Pragma("unroll") for (int ps = 0; ps < NSTG; ++ps)                                   \
     rav[RSET][ps] = buf_load16_nt(rv, (l_pf && l_mb + srow + ps * RP < a.T) ? a_voff0 + ps * a_vstep : -1, l_soff);
@@ -197,7 +201,7 @@ __global__ __launch_bounds__(WN * 64) __attribute__((amdgpu_waves_per_eu(2, 2)))
   const int bf_voff = wave * 6144 + frow * 32 + khalf * 16;
 #define S_BFRAG_PREP(VALID)                                                                                            \
   const int b_soff = (VALID) ? (Bc.p * a.nch + Bc.ch) * wchunk_bytes + Bc.nt * BN * 192 : 0;                            \
-  wscur_advance(Bc, a);
+  wscur_advance(Bc, a, tab);
 #define S_BFRAG_ISSUE(SET)                                                                                             \
   _Pragma("unroll") for (int t = 0; t < 3; ++t) _Pragma("unroll") for (int s = 0; s < 2; ++s) {                         \
     const float4 v = buf_load16(ru, bf_voff + (t * 2 + s) * 1024, b_soff);                                             \
@@ -269,7 +273,7 @@ __global__ __launch_bounds__(WN * 64) __attribute__((amdgpu_waves_per_eu(2, 2)))
       _Pragma("unroll") for (int i = 0; i < TM; ++i) _Pragma("unroll") for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;    \
       whole = true;                                                                                                    \
     }                                                                                                                  \
-    wscur_advance(C, a);                                                                                               \
+    wscur_advance(C, a, tab);                                                                                               \
   }
 
   // ---- one iteration per chunk of 32 = two k-steps of six MFMA terms, between two workgroup barriers, as ONE scheduling region:
@@ -363,7 +367,7 @@ __global__ __launch_bounds__(WN * 64) __attribute__((amdgpu_waves_per_eu(2, 2)))
       __builtin_amdgcn_sched_barrier(0);                                               \
     });                                                                                \
     S_STAMP(0)                                                                         \
-    if constexpr (!(DIM_SPLIT_EXP & 64)) S_FLUSH_CHECK(KCUR) else wscur_advance(C, a); \
+    if constexpr (!(DIM_SPLIT_EXP & 64)) S_FLUSH_CHECK(KCUR) else wscur_advance(C, a, tab); \
     S_STAMP(1)                                                                         \
     if constexpr (!(DIM_SPLIT_EXP & 32)) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); \
     S_STAMP(2)                                                                         \
@@ -403,6 +407,16 @@ __global__ __launch_bounds__(WN * 64) __attribute__((amdgpu_waves_per_eu(2, 2)))
 }
 
 template <int BM, int WN>
+__global__ __launch_bounds__(WN * 64) __attribute__((amdgpu_waves_per_eu(2, 2))) void wino_gemm_split_kernel(WGemmArgs a) {
+  wino_gemm_split_body<BM, WN, false>(a);
+}
+// the same launch with the item-slot table of a balanced 5x5 / stride-2 plan (wino_balance.hip)
+template <int BM, int WN>
+__global__ __launch_bounds__(WN * 64) __attribute__((amdgpu_waves_per_eu(2, 2))) void wino_gemm_split_map_kernel(WGemmArgs a) {
+  wino_gemm_split_body<BM, WN, true>(a);
+}
+
+template <int BM, int WN>
 static constexpr size_t split_lds_bytes() {
   return 2 * 3 * BM * 64 + WN * 16 * 32 * sizeof(float);
 }
@@ -434,7 +448,10 @@ template <int BM, int WN>
 static int wino_gemm_split_launch(const WGemmArgs& a, hipStream_t st) {
   constexpr size_t lds = split_lds_bytes<BM, WN>();
   static_assert(lds <= 65536, "a workgroup's dynamic LDS stays within 64 KB (see wino_gemm.hip)");
-  hipLaunchKernelGGL((wino_gemm_split_kernel<BM, WN>), dim3(a.G), dim3(WN * 64), lds, st, a);
+  if (a.sigma)
+    hipLaunchKernelGGL((wino_gemm_split_map_kernel<BM, WN>), dim3(a.G), dim3(WN * 64), lds, st, a);
+  else
+    hipLaunchKernelGGL((wino_gemm_split_kernel<BM, WN>), dim3(a.G), dim3(WN * 64), lds, st, a);
   return check_launch("winograd_gemm_split");
 }
 

@@ -528,7 +528,7 @@ int dim_winograd_dgrad_pack_weight(const float* w_oihw, float* w_packed, int Cou
 // S = 1: 3x3 / stride 1 / pad 1 with output tile m; S = 2: 5x5 / stride 2 / pad 2 through its four phase images (m = 4).
 static int winograd_fwd(const float* x, const float* w_packed, const float* bias, float* y, float* workspace, int N, int H, int W, int Cin,
                         int in_cstride, int Cout, int out_cstride, int out_coff, float slope, int tile, int m, int S, void** events4,
-                        void* stream) {
+                        void* stream, const WinoItemMap* map = nullptr) {
   if (N == 0) return DIM_OK;
   DIM_REQUIRE(x && w_packed && y && workspace, "null pointer");
   DIM_REQUIRE(m == 2 || m == 4, "output tile m must be 2 or 4");
@@ -567,7 +567,7 @@ static int winograd_fwd(const float* x, const float* w_packed, const float* bias
                          Wo, Cout, out_cstride, out_coff, th, tw, slope, make_fastdiv((unsigned)(Cout / kWino4Vec)), dtw, dth);
     return check_launch("winograd_output");
   };
-  return wino_run_slices(g, w_packed, workspace, gemm_tile, /*skip5=*/S == 2, /*zeroed=*/m == 4, events4, st, input, output);
+  return wino_run_slices(g, w_packed, workspace, gemm_tile, /*skip5=*/S == 2, /*zeroed=*/m == 4, events4, st, input, output, map);
 }
 
 int dim_conv2d_fwd_winograd(const float* x, const float* w_packed, const float* bias, float* y, float* workspace, int N, int H, int W,
@@ -690,6 +690,13 @@ int dim_conv2d_fwd_winograd5x5s2(const float* x, const float* w_packed, const fl
                                  void* stream) {
   return winograd_fwd(x, w_packed, bias, y, workspace, N, H, W, Cin, in_cstride, Cout, out_cstride, out_coff, slope, tile, 4, 2, events4,
                        stream);
+}
+
+int dim_conv2d_fwd_winograd5x5s2_map(const float* x, const float* w_packed, const float* bias, float* y, float* workspace, int N, int H,
+                                     int W, int Cin, int in_cstride, int Cout, int out_cstride, int out_coff, float slope, int tile,
+                                     const void* item_map, void** events4, void* stream) {
+  return winograd_fwd(x, w_packed, bias, y, workspace, N, H, W, Cin, in_cstride, Cout, out_cstride, out_coff, slope, tile, 4, 2, events4,
+                       stream, static_cast<const WinoItemMap*>(item_map));
 }
 
 }  // extern "C"

@@ -332,7 +332,9 @@ class MutableModule(object):
                 if name in net.wino:   # 3x3 / stride-1 layers run their forward through Winograd: re-transform the weights
                     net.wino[name] = ops.winograd_pack_weight(w[name + "_weight"], m=net.wino_m[name])
                 elif name in net.wino5:  # 5x5 / stride-2 layers: phase-image Winograd forward (backward: wino5_dgrad below)
+                    item_map = getattr(net.wino5[name], "item_map", None)   # the layer's plan, not the weights': it stays
                     net.wino5[name] = ops.winograd5x5s2_pack_weight(w[name + "_weight"])
+                    net.wino5[name].item_map = item_map
                 elif name == "flow_conv1" and net.cin != 8:
                     # 6 input channels (no masks in the Concat) or 10 (depth planes and masks): the kernels take 8-lane groups
                     ops.copy_channels(self.w1_lanes[0], 0, w[name + "_weight"], 0, min(net.cin, 8))

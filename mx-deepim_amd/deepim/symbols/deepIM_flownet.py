@@ -375,6 +375,9 @@ class FlowNetHip(object):
             if name in self.wino5:
                 wt = (wino_tile or {}).get(name, self._wino_tile(cout, tiles))
                 self.layer_info[name].update(self._wino_info(4, 2, wt, tiles, c, cout, *xy))
+                # equal live work per workgroup of the plane GEMMs (csrc/wino_balance.hip): the layer's item map is made here, at plan
+                # time, and rides on the packed weights, where ops.conv2d_fwd_winograd5x5s2 finds it (also under graph capture)
+                self.wino5[name].item_map = ops.wino_item_map_create(B, h, w, c, cout, wt)
                 max_ws = max(max_ws, lib.dim_winograd5x5s2_workspace_floats(B, h, w, c, cout))
             if name in self.wino3s2:
                 wt = (wino_tile or {}).get(name, self._wino_tile(cout, tiles, 81))

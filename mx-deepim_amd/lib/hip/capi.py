@@ -155,6 +155,11 @@ SIGNATURES = {
     "dim_winograd5x5s2_workspace_floats": (L, [I, I, I, I, I]),
     "dim_winograd5x5s2_pack_weight": (I, [P, P, I, I, P]),
     "dim_conv2d_fwd_winograd5x5s2": (I, [P, P, P, P, P, I, I, I, I, I, I, I, I, F, I, P, P]),
+    "dim_wino_item_map_create": (I, [P, I, I, I, I, I, I]),
+    "dim_wino_item_map_destroy": (None, [P]),
+    "dim_wino_item_map_query": (I, [P, P, P, L]),
+    "dim_wino_item_map_plan": (I, [I, I, I, I, I, I, P, P, L]),
+    "dim_conv2d_fwd_winograd5x5s2_map": (I, [P, P, P, P, P, I, I, I, I, I, I, I, I, F, I, P, P, P]),
     "dim_winograd5x5s2_dgrad_pack_weight": (I, [P, P, I, I, P]),
     "dim_conv2d_dgrad_winograd5x5s2": (I, [P, P, P, P, I, I, I, I, I, I, I, I, P]),
     "dim_conv2d_wgrad_winograd_workspace_floats": (L, [I, I, I, I, I, I, I]),

@@ -1169,11 +1169,61 @@ def fc_fwd(x_nhwc, w_packed, bias, Out, slope=0.1, out=None, workspace=None, eve
     return out
 
 
-def conv2d_fwd_winograd5x5s2(x_nhwc, Cin, w_packed, bias, Cout, slope=0.1, tile=0, out=None, out_coff=0, workspace=None, events=None):
-    """5x5 / stride 2 / pad 2 convolution as four phase images through Winograd F(4x4,3x3) (see include/deepim_hip.h)."""
+WINO_ITEM_MAP_HEADER = ("T", "K", "Cout", "tile", "G", "per", "rem", "live_max_before", "live_max_after", "moved", "items", "nch")
+
+
+def _wino_item_map_read(query):
+    """header dict and table (items,) int32 of an item map; query(header_ptr, table_ptr, capacity) is one of the two C queries"""
+    hdr = np.zeros(len(WINO_ITEM_MAP_HEADER), dtype=np.int32)
+    check(query(hdr.ctypes.data, None, 0))
+    table = np.zeros(int(hdr[WINO_ITEM_MAP_HEADER.index("items")]), dtype=np.int32)
+    check(query(hdr.ctypes.data, table.ctypes.data, table.size))
+    return dict(zip(WINO_ITEM_MAP_HEADER, (int(v) for v in hdr))), table
+
+
+def wino_item_map_plan(T, K, Cout, tile, G=0, skip5=True):
+    """the item-slot table dim_wino_item_map_create would build for the plane GEMMs [T x K] . [K x Cout] x 36 on `tile` cut into G ranges
+    (0: the G of a launch on this device), without a device: (header dict, table).  Host arithmetic only when G is given."""
+    return _wino_item_map_read(lambda h, t, n: lib().dim_wino_item_map_plan(int(T), int(K), int(Cout), int(tile), int(G), int(skip5), h, t, n))
+
+
+class WinoItemMap(object):
+    """a 5x5 / stride-2 layer's item-slot table in device memory (dim_wino_item_map_create); lives as long as this object"""
+
+    def __init__(self, N, H, W, Cin, Cout, tile=0):
+        import ctypes
+
+        self._destroy, handle = lib().dim_wino_item_map_destroy, ctypes.c_void_p()
+        check(lib().dim_wino_item_map_create(ctypes.byref(handle), int(N), int(H), int(W), int(Cin), int(Cout), int(tile)))
+        self.handle = handle.value
+
+    def query(self):
+        return _wino_item_map_read(lambda h, t, n: lib().dim_wino_item_map_query(self.handle, h, t, n))
+
+    def __del__(self):
+        if getattr(self, "handle", None):
+            self._destroy(self.handle)
+            self.handle = None
+
+
+def wino_item_map_create(N, H, W, Cin, Cout, tile=0):
+    """plan step of a 5x5 / stride-2 layer with input (N,H,W,Cin): its WinoItemMap.  Allocates and copies: never under graph capture."""
+    return WinoItemMap(N, H, W, Cin, Cout, tile)
+
+
+def conv2d_fwd_winograd5x5s2(x_nhwc, Cin, w_packed, bias, Cout, slope=0.1, tile=0, out=None, out_coff=0, workspace=None, events=None,
+                             item_map=None):
+    """5x5 / stride 2 / pad 2 convolution as four phase images through Winograd F(4x4,3x3) (see include/deepim_hip.h).
+    item_map: the layer's WinoItemMap; when not given, the one its planner left on the packed weights (`w_packed.item_map`), else
+    none.  A map built for another plan is ignored by the library: same bits either way."""
     H, W = x_nhwc.shape[1:3]
-    return _winograd_fwd(lib().dim_conv2d_fwd_winograd5x5s2, lib().dim_winograd5x5s2_workspace_floats, ((H + 1) // 2, (W + 1) // 2), x_nhwc,
-                         Cin, w_packed, bias, Cout, slope, tile, out, out_coff, workspace, events)
+    item_map = item_map if item_map is not None else getattr(w_packed, "item_map", None)
+    if item_map is None:
+        return _winograd_fwd(lib().dim_conv2d_fwd_winograd5x5s2, lib().dim_winograd5x5s2_workspace_floats, ((H + 1) // 2, (W + 1) // 2),
+                             x_nhwc, Cin, w_packed, bias, Cout, slope, tile, out, out_coff, workspace, events)
+    return _winograd_fwd(lib().dim_conv2d_fwd_winograd5x5s2_map, lambda *a: lib().dim_winograd5x5s2_workspace_floats(*a[:5]),
+                         ((H + 1) // 2, (W + 1) // 2), x_nhwc, Cin, w_packed, bias, Cout, slope, tile, out, out_coff, workspace, events,
+                         item_map.handle)
 
 
 def conv2d_fwd(x_nhwc, w_packed, bias, Cout, KH, KW, stride, pad, slope=0.1, splits=1, tile=0, out=None, workspace=None,
