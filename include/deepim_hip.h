@@ -169,7 +169,8 @@ int dim_depth_to_flow(const float* depth_src, const float* depth_tgt, const floa
  * tester.py:485-487 stores it; flow_gt (B,2,H,W) / visible (B,1,H,W) = calc_flow's outputs (dim_calc_flow_labels, weight_type 1);
  * bg = visible == 0 and depth_rendered == 0.  sums (B,5) float64 (device) = {epe_all, epe_viz, epe_vizbg, num_viz, num_vizbg} per
  * sample (num_all = H W), overwritten or -- accumulate != 0 -- added to.  Float64 arithmetic like numpy's (calc_flow returns
- * float64); deterministic two-stage sum.  workspace: dim_flow_epe_workspace_bytes(B). */
+ * float64); deterministic two-stage sum.  workspace: dim_flow_epe_workspace_bytes(B) bytes (doubles), 8-byte aligned, no
+ * initialisation needed: every partial sum is written before it is read. */
 long dim_flow_epe_workspace_bytes(int B);
 int dim_flow_epe_sums(const float* flow_pred, const float* flow_gt, const float* visible, const float* depth_rendered, int B, int H,
                       int W, void* workspace, double* sums, int accumulate, void* stream);
@@ -629,7 +630,43 @@ int dim_scene_compose(const float* layer_bgr, const float* layer_depth, const in
  * splits > 1 = split-K through `workspace` (dim_conv2d_workspace_floats), deterministic reduce.
  * tile: 0 auto | 1 128x128 (4 waves) | 2 128x64 | 3 64x64 | 4 128x128 (8 waves) (GEMM rows x output channels per workgroup of the
  *       gathered-tap kernel) | 6 the LDS-halo first-layer kernel (Cin 8, 7x7 / stride 2, Cout 64, dense f32 output).
- * Outputs are stored through a buffer descriptor with 32-bit byte offsets: N*OH*OW*out_cstride*4 must stay below 2^31. */
+ * Outputs are stored through a buffer descriptor with 32-bit byte offsets: N*OH*OW*out_cstride*4 must stay below 2^31.
+ *
+ * Caller-owned buffers of the convolution stack (every entry point from here to the optimizer steps; pinned on guarded buffers by
+ * tests/test_gpu_conv_workspace_contract.py):
+ *   workspace   Its size is what the entry's dim_*_workspace_floats function returns for the same arguments, in floats; a call
+ *               neither reads nor writes a byte beyond that.  The tests place it 256-byte aligned; dim_conv2d_dgrad_bf16_splitk
+ *               requires 16 bytes, no entry requires more.  Its contents before the call do not matter: zero words, NaN words, +inf
+ *               words and what a call of the same entry on another shape left behind give the same output bit for bit, so one buffer
+ *               of the largest size may serve every layer in turn without being cleared (deepim/core/module.py does that).
+ *                 dim_conv2d_fwd / _partial + dim_splitk_reduce   dim_conv2d_workspace_floats(..., splits); 0 floats for splits == 1;
+ *                                                                 splits == 0 ("auto"): the bound of the split tail
+ *                 dim_conv2d_fwd_winograd (forward, and the 3x3 input gradient run through it)   dim_winograd_workspace_floats
+ *                 dim_conv2d_fwd_winograd3x3s2                    dim_winograd3x3s2_workspace_floats
+ *                 dim_conv2d_fwd_winograd5x5s2[_map], dim_conv2d_dgrad_winograd5x5s2   dim_winograd5x5s2_workspace_floats
+ *                   (the four above: V and M of one slice of the batch; a later slice overwrites the earlier one's, and the M tiles
+ *                   two stream-K workgroups share are zeroed inside the call)
+ *                 dim_conv2d_wgrad_winograd                       dim_conv2d_wgrad_winograd_workspace_floats
+ *                 dim_conv2d_wgrad[_bf16]                         dim_conv2d_wgrad_workspace_floats(..., splits); 0 for splits == 1
+ *                 dim_conv2d_wgrad_oihw                           dim_conv2d_wgrad_workspace_floats(..., splits + 1), also for splits == 1
+ *                   (a split count larger than the pixel steps / 8 x 8 blocks can fill is clamped: fewer slabs are used, never more)
+ *                 dim_conv2d_dgrad_bf16_splitk                    dim_conv2d_dgrad_splitk_workspace_floats
+ *                 dim_conv2d_dgrad_bf16_lrelu                     dim_conv2d_dgrad_lrelu_workspace_floats
+ *                 dim_bias_grad, dim_lrelu_bwd_bias_grad          dim_bias_grad_workspace_floats, dim_lrelu_bwd_bias_grad_workspace_floats
+ *                 dim_fc_fwd                                      dim_fc_fwd_workspace_floats
+ *                 dim_conv_small_cout_bwd                         dim_conv_small_cout_bwd_workspace_floats
+ *   outputs     An entry with out_cstride / out_coff (dx_cstride, dy_coff, dz_coff: the same for a gradient) writes channels
+ *               [coff, coff + C) of every row and no other byte of the buffer; a dense output is written in full, whatever it held
+ *               (accumulate / accumulate_dx: added to).  The refusals the tests provoke -- a 128-wide tile on 64 filters, dim_fc_fwd
+ *               with Out % 256 != 0, dim_conv2d_wgrad[_bf16] with accumulate and more than one split -- return DIM_ERR_ARG before
+ *               anything is enqueued and leave workspace and outputs untouched.
+ *   packers     Each writes all N elements of its output, N = the packer's dim_*_packed_weight_floats (dim_fc_pack_weight,
+ *               dim_fc_dgrad_pack_weight[_bf16]: Out*C*H*W; dim_conv_small_cout_pack_weight: Cout*KH*KW*CinPad; the _padded packer:
+ *               KH*KW*Cin*CoutPad), pad rows, pad columns and the three-term image behind the f32 weights (first layer, Winograd
+ *               layers) included, whatever the buffer held: no kernel reads a word of a packed buffer that its packer did not write.
+ *               One exception: dim_conv2d_pack_weight_bf16 for the 8-channel 7x7 first layer writes the ceil(KH*KW/4)*32*CoutPad
+ *               weights and leaves the rest of a buffer of dim_conv2d_packed_weight_floats elements alone -- the f32 buffer's
+ *               three-term image has no bf16 counterpart, and the bf16 kernels read the weights only. */
 long dim_conv2d_packed_weight_floats(int Cout, int Cin, int KH, int KW);
 int dim_conv2d_pack_weight(const float* w_oihw, float* w_packed, int Cout, int Cin, int KH, int KW, void* stream);
 long dim_conv2d_workspace_floats(int N, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int splits);
@@ -832,8 +869,9 @@ int dim_conv2d_dgrad_bf16_lrelu(const float* dy, const void* w_dgrad_packed_bf16
                                 int KH, int KW, int stride, int pad, int accumulate_db, void* stream);
 int dim_f32_to_bf16(const float* src, void* dst_bf16, long n, void* stream);
 int dim_bf16_to_f32(const void* src_bf16, float* dst, long n, void* stream);
-/* The packers with the rounding folded in: each writes exactly dim_f32_to_bf16 of its f32 twin's output (same element count, same
- * order) in one pass over the MXNet-layout weights -- the training executor re-packs every layer after every update.
+/* The packers with the rounding folded in: each writes exactly dim_f32_to_bf16 of the weights its f32 twin writes (same element
+ * count, same order; for the 8-channel first layer that is the 13 x 32 x CoutPad weights, not the three-term image the f32 buffer
+ * carries behind them) in one pass over the MXNet-layout weights -- the training executor re-packs every layer after every update.
  * dim_conv2d_pack_weight_bf16 covers both dim_conv2d_pack_weight (CoutPad == Cout) and dim_conv2d_pack_weight_padded. */
 int dim_conv2d_pack_weight_bf16(const float* w_oihw, void* w_packed_bf16, int Cout, int CoutPad, int Cin, int KH, int KW, void* stream);
 int dim_conv2d_dgrad_pack_weight_bf16(const float* w_oihw, void* w_packed_bf16, int Cout, int Cin, int KH, int KW, int stride, int pad,

@@ -801,6 +801,8 @@ int wgrad_launch(WgradArgs& a, float* dw_packed, float* workspace, int splits, i
   a.steps_per_split = ceil_div(a.nsteps, splits);
   splits = ceil_div(a.nsteps, a.steps_per_split);
   DIM_REQUIRE((splits == 1 && !keep_slabs) || workspace, "split wgrad needs a workspace (dim_conv2d_wgrad_workspace_floats)");
+  // refused before anything is enqueued: the slabs would be summed over dw, not onto it (reduce first, then accumulate with splits == 1)
+  DIM_REQUIRE(!(accumulate && splits > 1), "accumulate with splits > 1 is not supported (reduce first, then accumulate with splits == 1)");
   a.dw = (splits > 1 || keep_slabs) ? workspace : dw_packed;
   a.accumulate = accumulate;
   static const int xcd_env = [] { const char* e = getenv("DIM_WGRAD_XCD"); return e ? atoi(e) : 1; }();
@@ -845,10 +847,7 @@ int wgrad_launch(WgradArgs& a, float* dw_packed, float* workspace, int splits, i
     int rcb = check_launch("conv_wgrad_bf16");
     if (rcb != DIM_OK) return rcb;
     if (keep_slabs) { *keep_slabs = splits; return DIM_OK; }
-    if (splits > 1) {
-      DIM_REQUIRE(!accumulate, "accumulate with splits > 1 is not supported");
-      return dim_splitk_reduce(workspace, nullptr, dw_packed, (long)a.nchunks * Cout * 32 / 4, 4, splits, 1.0f, stream);
-    }
+    if (splits > 1) return dim_splitk_reduce(workspace, nullptr, dw_packed, (long)a.nchunks * Cout * 32 / 4, 4, splits, 1.0f, stream);
     return DIM_OK;
   }
   const bool two = a.nchunks >= 2;  // two K chunks (64 packed columns) per workgroup share one dZ tile
@@ -867,10 +866,6 @@ int wgrad_launch(WgradArgs& a, float* dw_packed, float* workspace, int splits, i
   if (keep_slabs) { *keep_slabs = splits; return DIM_OK; }
   if (splits > 1) {
     long n = (long)a.nchunks * Cout * 32;
-    if (accumulate) {
-      // slabs + existing value: treat dw itself as one more addend by summing into a temp is avoided -- reduce then add
-      return set_err(DIM_ERR_ARG, "accumulate with splits > 1 is not supported (reduce first, then accumulate with splits == 1)");
-    }
     return dim_splitk_reduce(workspace, nullptr, dw_packed, n / 4, 4, splits, 1.0f, stream);
   }
   return DIM_OK;

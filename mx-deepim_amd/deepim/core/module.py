@@ -84,6 +84,11 @@ def plan_backward(B, bf16, has_decoder, n_cu, wino, wino5, wino_m, lanes, sw):
     layers; lanes: 8-lane input groups of flow_conv1 beyond the plain 8-channel case (0, 1 or 2); sw: Switches.  -> BackwardPlan"""
     lib, P = ops.lib(), ops.pad64
     ws = gpack = fold_ws = wino_ws = wino_wgrad_ws = 4
+    # bias_ws: the first layer's dim_bias_grad size + 64 Ki floats, raised below to the largest fused LeakyReLU' + bias-gradient pass.
+    # No call needs the 64 Ki: each fits what its own size function reports and the kernels stay inside that
+    # (tests/test_train_plan_host.py::test_bias_workspace_covers_every_call_through_it,
+    # tests/test_gpu_conv_workspace_contract.py::test_column_sums).  They stay because the launch-trace goldens record the shape of
+    # every workspace tensor, this one included.
     bias_ws = lib.dim_bias_grad_workspace_floats(B * 240 * 320, 64) + 1024 * 64
     layers, folded = [], set()
     for geom in reversed(encoder_geometry()):

@@ -15,6 +15,7 @@ import torch
 pytestmark = pytest.mark.gpu
 
 import bop_reference as ref  # noqa: E402
+import guard_arena  # noqa: E402
 from loop_parity import moving_head  # noqa: E402
 from scene import make_test_config  # noqa: E402
 
@@ -274,10 +275,13 @@ def test_dirty_workspace_and_graph_replay_give_the_same_bits(hip_lib):
     tb = tables()["dev"]
     o = ops()
     first_e, first_s = _run(tb, c["draw"], c["est"], c["gt"])
-    work = o.bop_errors_workspace(2, 7, MAX_SYM, DEV)
+    # exactly dim_bop_errors_workspace_bytes between guards, at the documented minimum alignment (8 mod 16)
+    arena = guard_arena.workspace(o.lib().dim_bop_errors_workspace_bytes(2, 7, MAX_SYM), 8, DEV)
+    work = arena.view()
     for fill in (float("nan"), -1.0e300, 1.0e300):
         work.fill_(fill)
         e, s = _run(tb, c["draw"], c["est"], c["gt"], workspace=work)
+        arena.check("dim_bop_errors workspace, {} before the call".format(fill))
         assert np.array_equal(e.cpu().numpy().view(np.uint64), first_e.cpu().numpy().view(np.uint64)), fill
         assert np.array_equal(s.cpu().numpy(), first_s.cpu().numpy())
     # captured and replayed

@@ -9,6 +9,7 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
+import guard_arena  # noqa: E402
 from oracle import evaluation as oev  # noqa: E402
 from scene import make_test_config, make_train_scene  # noqa: E402
 
@@ -23,7 +24,10 @@ def test_flow_epe_sums_vs_reference_outputs(hip_lib, golden_dir):
     t = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.float32)).to(DEV)
     pred, flow = t(e["pred"].transpose(0, 3, 1, 2)), t(g["flow"].transpose(0, 3, 1, 2))
     vis, d0 = t(g["visible"][:, None]), t(g["depth_src"][:, None])
-    sums = ops.flow_epe_sums(pred, flow, vis, d0)
+    # the workspace: exactly dim_flow_epe_workspace_bytes between guards, at the documented minimum alignment (8 mod 16), NaN bits
+    work = guard_arena.workspace(ops.lib().dim_flow_epe_workspace_bytes(pred.shape[0]), 8, DEV)
+    sums = ops.flow_epe_sums(pred, flow, vis, d0, workspace=work.view())
+    work.check("dim_flow_epe_sums workspace")
     got = sums.cpu().numpy()
     want = e["out"]
     # float32 storage of calc_flow's float64 flow: <= 6e-8 relative per element; the sums themselves are float64 on both sides

@@ -8,6 +8,7 @@ import torch
 pytestmark = pytest.mark.gpu
 
 import flow_pnp_reference as fr  # noqa: E402
+import guard_arena  # noqa: E402
 from scene import make_scene, make_test_config  # noqa: E402
 from test_flow_pnp_host import GATE, HUBER, ITERS, WARM, gpu_batches  # noqa: E402
 
@@ -131,7 +132,10 @@ def test_eager_and_graph_replays_are_bit_identical(batches):
     args = (_dev(depth), _dev(flow), _dev(pose), Ks[0].reshape(3, 3), ITERS, WARM, HUBER, GATE)
     o = ops()
     bufs = dict(pose_out=torch.zeros((B, 3, 4), device=DEV), se3_q=torch.zeros((B, 7), device=DEV), stats=torch.zeros((B, ITERS, 2), device=DEV),
-                status=torch.zeros((B,), dtype=torch.int32, device=DEV), workspace=o.flow_pnp_workspace(B, H, W, DEV))
+                status=torch.zeros((B,), dtype=torch.int32, device=DEV))
+    # the workspace: exactly dim_flow_pnp_workspace_bytes between guards, at the documented minimum alignment (8 mod 16), NaN bits
+    work = guard_arena.workspace(o.lib().dim_flow_pnp_workspace_bytes(B, H, W), 8, DEV)
+    bufs["workspace"] = work.view()
     kw = dict(standard_rep=rep, valid=_dev(valid), bbox=_dev(bbox, torch.int32), K_per_sample=_dev(Ks), **bufs)
 
     def snapshot():
@@ -139,6 +143,7 @@ def test_eager_and_graph_replays_are_bit_identical(batches):
         out = [bufs[k].cpu().numpy().copy() for k in ("pose_out", "se3_q", "stats")]
         for k in ("pose_out", "se3_q", "stats"):
             bufs[k].fill_(-7.0)
+        work.check("dim_flow_pnp workspace")
         bufs["workspace"].fill_(float("nan"))   # the workspace needs no initialisation
         torch.cuda.synchronize()
         return out

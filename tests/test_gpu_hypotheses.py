@@ -7,6 +7,7 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
+import guard_arena  # noqa: E402
 import hyp_reference as hr  # noqa: E402
 from loop_parity import moving_head  # noqa: E402
 from scene import make_scene, make_test_config  # noqa: E402
@@ -116,7 +117,11 @@ def test_pose_score_matches_restatement(score_planes, mode):
     img_r, dep_r, bbox, img_o, dep_o = _hostile(score_planes)
     B = img_r.shape[0]
     status = torch.zeros((B,), dtype=torch.int32, device=DEV)
-    s = ops().pose_score(img_o, img_r, dep_r, mode, 0.02, depth_observed=dep_o if mode == "depth" else None, bbox=bbox, status=status)
+    # the workspace: exactly dim_pose_score_workspace_bytes between guards, at the documented minimum alignment (8 mod 16), NaN bits
+    work = guard_arena.workspace(ops().lib().dim_pose_score_workspace_bytes(B, H, W), 8, DEV)
+    s = ops().pose_score(img_o, img_r, dep_r, mode, 0.02, depth_observed=dep_o if mode == "depth" else None, bbox=bbox, status=status,
+                         workspace=work.view())
+    work.check("dim_pose_score workspace, mode " + mode)
     got = s.cpu().numpy().astype(np.float64)
     want = hr.scores(mode, img_o.cpu().numpy(), img_r.cpu().numpy(), dep_r.cpu().numpy(), bbox.cpu().numpy(), dep_o.cpu().numpy(), 0.02)
     st = status.cpu().numpy()

@@ -7,6 +7,7 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
+import guard_arena  # noqa: E402
 import icp_reference as ir  # noqa: E402
 from loop_parity import moving_head  # noqa: E402
 from scene import make_scene, make_test_config  # noqa: E402
@@ -51,8 +52,11 @@ def _icp(rm, dr, do, pose_in, iters, K=None, bbox=None, max_dist=MAX_DIST):
     B = pose_in.shape[0]
     stats = torch.zeros((B, max(iters, 1), 2), dtype=torch.float32, device=DEV)
     status = torch.zeros((B,), dtype=torch.int32, device=DEV)
+    # the workspace: exactly dim_icp_workspace_bytes between guards, at the documented minimum alignment (8 mod 16), full of NaN bits
+    work = guard_arena.workspace(ops().lib().dim_icp_workspace_bytes(B, H, W), 8, DEV)
     out = ops().icp_refine(dr, do, torch.as_tensor(pose_in).to(DEV), rm.K, iters, max_dist, bbox=bbox, K_per_sample=K, stats=stats,
-                           status=status)
+                           status=status, workspace=work.view())
+    work.check("dim_icp_refine workspace, B = {}".format(B))
     torch.cuda.synchronize()
     return out.cpu().numpy(), stats.cpu().numpy(), status.cpu().numpy()
 

@@ -8,6 +8,7 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
+import guard_arena  # noqa: E402
 import occ_scene_reference as ref  # noqa: E402
 from lib.utils import synthetic as syn  # noqa: E402
 from oracle import native  # noqa: E402
@@ -103,7 +104,10 @@ def test_compose_bit_equal_to_restatement(hip_lib, S, H, W):
     t = [torch.from_numpy(x).to(DEV) for x in (bgr, depth, label)]
     status = torch.zeros(N * S, dtype=torch.int32, device=DEV)
     out = garbage_outputs(S, H, W)
-    ops.scene_compose(t[0], t[1], t[2], S, status=status, workspace=garbage_workspace(S, H, W), **out)
+    # the workspace: exactly dim_scene_compose_workspace_bytes between guards, at the documented minimum alignment (4 mod 8), NaN bits
+    work = guard_arena.workspace(ops.lib().dim_scene_compose_workspace_bytes(N, S, H, W), 4, DEV)
+    ops.scene_compose(t[0], t[1], t[2], S, status=status, workspace=work.view(), **out)
+    work.check("dim_scene_compose workspace, S = {}, {} x {}".format(S, H, W))
     for k in OUTS:
         assert_bits(out[k], want[k], k)
     hidden = (label > 0) & (want["counts"][:, 1] == 0)

@@ -11,6 +11,7 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
+import guard_arena  # noqa: E402
 import photo_reference as pr  # noqa: E402
 import test_photo_host as host  # noqa: E402
 from loop_parity import moving_head  # noqa: E402
@@ -37,9 +38,13 @@ def _photo(obs, ren, dep, pose_in, K, levels, iters, bbox=None, Kps=None, huber=
     B, _, h, w = dep.shape
     stats = torch.zeros((B, max(levels * iters, 1), 2), dtype=torch.float32, device=DEV)
     status = torch.zeros((B,), dtype=torch.int32, device=DEV)
-    work = ops().photo_workspace(B, h, w, levels, DEV)
+    # the workspace: exactly dim_photo_workspace_bytes between guards, at the alignment the fast path documents and no better (16 mod
+    # 32), full of NaN bits
+    arena = guard_arena.workspace(ops().lib().dim_photo_workspace_bytes(B, h, w, levels), 16, DEV)
+    work = arena.view()
     out = ops().photo_refine(obs, ren, dep, pose_in, K, levels, iters, huber, gate, gain=gain, bbox=bbox, K_per_sample=Kps, stats=stats,
                              status=status, workspace=work)
+    arena.check("dim_photo_refine workspace, B = {}, {} x {}, {} levels".format(B, h, w, levels))
     torch.cuda.synchronize()
     res = (out.cpu().numpy(), stats.cpu().numpy(), status.cpu().numpy())
     if views:

@@ -11,6 +11,7 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
+import guard_arena  # noqa: E402
 from conftest import GOLDEN  # noqa: E402
 from loop_parity import moving_head  # noqa: E402
 from scene import make_test_config  # noqa: E402
@@ -216,11 +217,14 @@ def test_second_call_with_a_dirty_workspace_is_bit_identical(hip_lib):
     draw = (4, 0, 2, 3, 1, 7, 6)
     gt = np.stack([_gt_pose(rng) for _ in draw])
     est = _est_f32(rng, gt, T=3)
-    work = ops().pose_errors_workspace(3, 7, max(SIZES), DEV)
-    work.fill_(float("nan"))
+    # exactly dim_pose_errors_workspace_bytes between guards, at the documented minimum alignment (8 mod 16), full of NaN bits
+    arena = guard_arena.workspace(ops().lib().dim_pose_errors_workspace_bytes(3, 7, max(SIZES)), 8, DEV)
+    work = arena.view()
     a = _run(tables, draw, est, gt, workspace=work).cpu().numpy().copy()
+    arena.check("dim_pose_errors workspace, NaN before the call")
     work.copy_(torch.randn(work.shape, dtype=torch.float64, device=DEV) * 1e6)
     b = _run(tables, draw, est, gt, workspace=work).cpu().numpy()
+    arena.check("dim_pose_errors workspace, noise before the call")
     assert np.array_equal(a.view(np.uint64), b.view(np.uint64))
     c = _run(tables, draw, est.astype(np.float64), gt).cpu().numpy()   # the float64 entry on the same (float32-valued) poses
     assert np.array_equal(a.view(np.uint64), c.view(np.uint64))

@@ -8,6 +8,8 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
+import guard_arena  # noqa: E402
+
 DEV = "cuda:0"
 
 
@@ -35,8 +37,18 @@ def _same(a, b):
 def test_recycled_workspace_and_other_batch_size(hip_lib):
     B = 3
     rm, cls, gt, init, pm = _setup(B)
+    # the renderer's workspace for this batch size: dim_raster_workspace_bytes (in whole 8-byte words, as Render_Py allocates it) between
+    # guards, at the alignment of the fast path and no better (16 mod 32); the header rule of include/deepim_hip.h -- the first 256 bytes
+    # zero -- and NaN bits behind it
+    from lib.hip import ops
+
+    n = ops.lib().dim_raster_workspace_bytes(B, rm.vmax, rm.height, rm.width)
+    arena = guard_arena.GuardArena((n + 7) // 8, dtype=torch.int64, device=DEV, fill=guard_arena.NAN_WORD, align=32, phase=16)
+    arena.view()[:32].zero_()
+    rm._ws[B] = arena.view()
     ref_gt, ref_init = _planes(B), _planes(B)
     rm.render_batch(cls, gt, plane_means=pm, **ref_gt)
+    arena.check("dim_raster_render workspace, first render")
     rm.render_batch(cls, init, plane_means=pm, **ref_init)          # second render on the same workspace: no clear pass ran
     assert not _same(ref_gt, ref_init) and ref_init["mask"].sum() > 1000
     ws = rm._workspace(B)
@@ -63,6 +75,7 @@ def test_recycled_workspace_and_other_batch_size(hip_lib):
     two = _planes(2)
     rm.render_batch(cls[:2], init[:2], plane_means=pm, **two)
     assert all(torch.equal(two[k], ref_init[k][:2]) for k in two)
+    arena.check("dim_raster_render workspace, after every render above")
 
 
 def test_renders_without_colour_output_leave_the_zbuffer_clear(hip_lib):

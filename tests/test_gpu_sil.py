@@ -14,6 +14,7 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
+import guard_arena  # noqa: E402
 import sil_reference as sr  # noqa: E402
 import test_sil_host as host  # noqa: E402
 from loop_parity import moving_head  # noqa: E402
@@ -41,7 +42,12 @@ def _refine(depth, field, pose_in, K, iters, bbox=None, Kps=None, huber=HUBER, g
     B = depth.shape[0]
     stats = torch.zeros((B, max(iters, 1), 2), dtype=torch.float32, device=DEV)
     status = torch.zeros((B,), dtype=torch.int32, device=DEV)
-    out = ops().sil_refine(depth, field, pose_in, K, iters, huber, gate, bbox=bbox, K_per_sample=Kps, stats=stats, status=status)
+    # the workspace: exactly dim_sil_workspace_bytes between guards, at the documented minimum alignment (8 mod 16), full of NaN bits
+    _, _, h, w = depth.shape
+    work = guard_arena.workspace(ops().lib().dim_sil_workspace_bytes(B, h, w), 8, DEV)
+    out = ops().sil_refine(depth, field, pose_in, K, iters, huber, gate, bbox=bbox, K_per_sample=Kps, stats=stats, status=status,
+                           workspace=work.view())
+    work.check("dim_sil_refine workspace, B = {}".format(B))
     torch.cuda.synchronize()
     return out.cpu().numpy(), stats.cpu().numpy(), status.cpu().numpy()
 

@@ -8,6 +8,7 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
+import guard_arena  # noqa: E402
 import sym_pm_reference as S  # noqa: E402
 
 DEV = "cuda:0"
@@ -55,8 +56,13 @@ def run(ops, inp, loss_type="L1", s=1.0, optional=True, max_sym=None, status0=0,
     if optional:
         out = dict(target_out=torch.full_like(d["p_est"], SENTINEL), best_sym=torch.full((B,), 99, dtype=torch.int32, device=DEV),
                    loss_sum=torch.full((1,), PRIOR, device=DEV), status=torch.full((B,), status0, dtype=torch.int32, device=DEV))
+    # the workspace: exactly dim_pm_sym_workspace_bytes (one word where a refused max_sym makes that 0) between guards, at the
+    # documented minimum alignment (4 mod 8), full of NaN bits
+    msym = inp["max_sym"] if max_sym is None else max_sym
+    work = guard_arena.workspace(max(ops.lib().dim_pm_sym_workspace_bytes(B, inp["p_est"].shape[2], msym), 4), 4, DEV)
     ops.pm_sym_loss_grad(d["p_est"], d["points_model"], d["weights"], d["tgt_pose"], d["sym"], off, cls, grad, args["norm_term"],
-                         args["grad_scale"], inp["max_sym"] if max_sym is None else max_sym, loss_type=loss_type, smooth_l1_scalar=s, **out)
+                         args["grad_scale"], msym, loss_type=loss_type, smooth_l1_scalar=s, workspace=work.view(), **out)
+    work.check("dim_pm_sym_loss_grad workspace, max_sym = {}".format(msym))
     res = {k: host(v) for k, v in out.items()}
     res["grad"] = host(grad)
     return res

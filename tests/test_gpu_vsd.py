@@ -11,6 +11,7 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
+import guard_arena  # noqa: E402
 from conftest import GOLDEN  # noqa: E402
 from loop_parity import moving_head  # noqa: E402
 from scene import make_test_config  # noqa: E402
@@ -122,12 +123,16 @@ def test_kernel_equals_the_host_on_the_golden_planes(hip_lib, name, per_pair):
 @pytest.mark.parametrize("name", ["a", "b"], ids=["48x64", "50x63"])
 def test_several_taus_in_one_call_equal_single_calls_and_a_dirty_workspace_changes_nothing(hip_lib, name):
     L = layout(name)
-    work = ops().vsd_workspace(T_SETS, ROWS, DEV)
+    # exactly dim_vsd_workspace_bytes between guards, at the documented minimum alignment (8 mod 16)
+    arena = guard_arena.workspace(ops().lib().dim_vsd_workspace_bytes(T_SETS, ROWS), 8, DEV)
+    work = arena.view()
     for cost in COSTS:
         work.fill_(float("nan"))
         all8, n8 = run_layout(L, (0, 1, 2), cost, L["taus"], True, True, workspace=work)
+        arena.check("dim_vsd_errors workspace, NaN before the call, " + cost)
         work.copy_(torch.randn(work.shape, dtype=torch.float64, device=DEV) * 1e6)
         again, n_again = run_layout(L, (0, 1, 2), cost, L["taus"], True, True, workspace=work)
+        arena.check("dim_vsd_errors workspace, noise before the call, " + cost)
         assert np.array_equal(all8.view(np.uint64), again.view(np.uint64)) and np.array_equal(n8, n_again)
         single = [run_layout(L, (0, 1, 2), cost, [tau], True, True)[0][:, :, 0] for tau in L["taus"]]
         for k in range(8):

@@ -9,6 +9,7 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
+import guard_arena  # noqa: E402
 from loop_parity import moving_head  # noqa: E402
 from scene import make_test_config  # noqa: E402
 from test_gpu_vsd import ROWS, T_SETS, _box, _dev, _same, layout  # noqa: E402  (the golden planes as that file arranges them)
@@ -259,13 +260,17 @@ def test_a_dirty_workspace_and_a_replayed_graph_change_nothing(hip_lib):
     tab = table(10)
     obs, gt, est, cams, classes = permuted(L, (0, 1, 2))
     want = run(obs, gt, est, L["K"], classes, tab, cams=cams, boxes=True)
-    work = ops().vsd_grid_workspace(T_SETS, ROWS, DEV)
+    # exactly dim_vsd_grid_workspace_bytes between guards, at the documented minimum alignment (8 mod 16)
+    arena = guard_arena.workspace(ops().lib().dim_vsd_grid_workspace_bytes(T_SETS, ROWS), 8, DEV)
+    work = arena.view()
+    assert work.dtype == torch.float64
     for fill in ("nan", "noise"):
         if fill == "nan":
             work.fill_(float("nan"))
         else:
             work.copy_(torch.randn(work.shape, dtype=torch.float64, device=DEV) * 1e6)
         equal(run(obs, gt, est, L["K"], classes, tab, cams=cams, boxes=True, workspace=work), want, fill)
+        arena.check("dim_vsd_grid_errors workspace, {} before the call".format(fill))
     # captured once, replayed twice: everything the call reads is resident, nothing is allocated inside
     d_obs, d_gt, d_est = _dev(np.stack(obs)), _dev(np.stack(gt)), _dev(np.stack([np.stack(row) for row in est]))
     d_cls, d_tab, d_K = _dev(np.asarray(classes, np.int32)), _dev(tab), _dev(np.stack(cams).reshape(ROWS, 9))

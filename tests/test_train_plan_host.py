@@ -61,6 +61,29 @@ def test_plan_equals_what_the_executor_decided(hip_lib, B, dtype):
     assert {layer.geom.name: layer.skip for layer in pl.layers if layer.skip} == {"conv5_1": "dconcat2", "conv4_1": "dconcat3"}
 
 
+@pytest.mark.parametrize("B,dtype", CASES)
+def test_bias_workspace_covers_every_call_through_it(hip_lib, B, dtype):
+    """every dim_bias_grad / dim_lrelu_bwd_bias_grad call of the recorded step needs, by its own size function, no more than the plan
+    without the 64 Ki floats it carries on top of the first layer's size (kept because the goldens record the workspace's shape; the
+    kernels stay inside the reported size: tests/test_gpu_conv_workspace_contract.py::test_column_sums)"""
+    with open(os.path.join(GOLDEN, "launch_trace", "train_B{}_{}.json".format(B, dtype))) as f:
+        want = json.load(f)
+    pl = plan(B, dtype, n_cu=want["n_cu"])
+    size_fn = {"bias_grad": hip_lib.dim_bias_grad_workspace_floats, "lrelu_bwd_bias_grad": hip_lib.dim_lrelu_bwd_bias_grad_workspace_floats}
+    needs = []
+    for fn, args, kw in want["trace"]:
+        if fn not in size_fn:
+            continue
+        shape = args[0 if fn == "bias_grad" else 1][1]                 # dz / dy: (N, H, W, row width)
+        rows, C = shape[0] * shape[1] * shape[2], args[1 if fn == "bias_grad" else 2]
+        needs.append(size_fn[fn](rows, C))
+        assert 0 < needs[-1] <= pl.bias_ws == kw["workspace"][1][0], (fn, rows, C, needs[-1])
+    assert len(needs) >= 8
+    without = max(hip_lib.dim_bias_grad_workspace_floats(B * 240 * 320, 64), max(n for n in needs))
+    print("B {} {}: largest need {} floats, allocated {}".format(B, dtype, max(needs), pl.bias_ws))
+    assert max(needs) <= without <= pl.bias_ws
+
+
 # layer: f32 B=2, f32 B=16, bf16 B=2, bf16 B=16   (256 CUs, decoder present; "gemm t,k" = workgroup tile t, split-K k)
 TABLE = {
     "flow_conv1": ("fused 316 / -", "fused 316 / -", "fused 256 / -", "fused 256 / -"),
