@@ -521,6 +521,30 @@ int dim_pair_blobs_from_raw(const unsigned char* obs_bgr, const unsigned char* b
 /* mask_dilate (lib/utils/mask_dilate.py:10-55) with the random draws made by the caller: thickness4 (B,4) = {down, up, right, left}
  * displacement of the boundary copies, 0 = side skipped.  mask_out != mask_in. */
 int dim_mask_dilate(const float* mask_in, const int* thickness4, float* mask_out, int B, int H, int W, void* stream);
+/* Photometric augmentation of observed training images (csrc/augment.hip), one pass over the blob, the draws made by the caller
+ * (lib/utils/augment.py) as for mask_dilate.  in, out: image_observed blobs (B,3,H,W) float32, mean-subtracted, plane c = BGR channel
+ * 2 - c (plane 0 is red); pixel_means_bgr3 (host) = network.PIXEL_MEANS.  The kernel works on grey levels v = in + mean of the plane, all
+ * in float32 with every product and every sum rounded (no fused multiply-add), for pair b in this order:
+ *   on[b] == 0     out is a copy of in, bit for bit; nothing below applies
+ *   blur           radius r = radius_host[b] in 0..7 (HOST array) and taps[b] (device, B x 15, the first 2 r + 1 used, normalised by the
+ *                  caller): separable, rows first, then columns of the row-blurred values; coordinates clamped to the image
+ *                  (replicate border); each 1-D sum starts at 0 and is accumulated in ascending tap order, acc = acc + w * v;
+ *                  r = 0 skips both passes (no multiplication by 1)
+ *   saturation s   gray = 0.299 R + 0.587 G + 0.114 B (float32 constants, summed left to right), v_c = gray + s * (v_c - gray)
+ *   contrast k, brightness d (grey levels)   v_c = (v_c - 128) * k + 128 + d, left to right
+ *   gain g_c       v_c = v_c * g_c, c the blob plane (white balance)
+ *   noise sigma    v_c = v_c + sigma * n(seed[b], (c * H + y) * W + x); sigma == 0 skips the addition.  With uint32 arithmetic
+ *                  mix(x): x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16
+ *                  h0 = mix(seed + counter * 0x9E3779B9), h1 = mix(h0 ^ 0x85EBCA6B),
+ *                  n = (float)((h0 & 0xFFFF) + (h0 >> 16) + (h1 & 0xFFFF) + (h1 >> 16) - 131070) * 2.6428997e-05f  (unit variance,
+ *                  within +-3.4642)
+ *   clamp to [0, 255]; with quantize != 0 rintf (half to even); out = v_c - mean
+ * chain[b] (device, B x 7) = {s, k, d, g_0, g_1, g_2, sigma}; on (B) int32 and seed (B) uint32 are device arrays.
+ * No workspace.  in and out must not overlap (the halo of one tile is another tile's output) and are 16-byte aligned; W % 4 == 0.
+ * A NULL pointer, B, H or W <= 0, W % 4 != 0, overlapping or misaligned blobs or a radius outside 0..7 return DIM_ERR_ARG with a
+ * message before anything is enqueued. */
+int dim_augment_observed(const float* in, float* out, int B, int H, int W, const float* pixel_means_bgr3, const int* on,
+                         const int* radius_host, const float* taps, const float* chain, const unsigned* seed, int quantize, void* stream);
 /* First-iteration flow labels = calc_flow (lib/pair_matching/flow.py:12-81; float64 per pixel like numpy) + the weights of
  * get_pair_flow (image.py:531-545).  depth_src = rendered depth, depth_tgt = observed depth (B,1,H,W) metres; P12 (B,3,4) float64 (device) =
  * K se3_mul(pose_tgt, se3_inverse(pose_src)) as the reference forms it on the host; Kinv9_f64 = inv(K) in float64 (host pointer).

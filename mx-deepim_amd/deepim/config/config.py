@@ -68,7 +68,14 @@ def _defaults():
     c.TRAIN = edict(
         optimizer="sgd", warmup=False, warmup_lr=0, warmup_step=0, begin_epoch=0, end_epoch=0, lr=0.0001, lr_step="4, 6",
         momentum=0.975, wd=0.0005, model_prefix="deepim", RESUME=False, SHUFFLE=True, BATCH_PAIRS=1, FLOW_WEIGHT_TYPE="all",
-        TENSORBOARD_LOG=False, INIT_MASK="box_gt", UPDATE_MASK="box_gt", MASK_DILATE=False, REPLACE_OBSERVED_BG_RATIO=0.0)
+        TENSORBOARD_LOG=False, INIT_MASK="box_gt", UPDATE_MASK="box_gt", MASK_DILATE=False, REPLACE_OBSERVED_BG_RATIO=0.0,
+        # photometric augmentation of image_observed on the device (dim_augment_observed, lib/utils/augment.py; off = the batches of
+        # before): the seed of its own generator (with the epoch and the pair's key), the share of pairs that are touched at all and
+        # of those that are blurred, and [lo, hi] ranges ([a, a] pins): Gaussian blur sigma in pixels (radius ceil(3 sigma) <= 7),
+        # saturation and contrast factors, brightness shift in grey levels, gain per colour plane (white balance), sensor noise sigma
+        # in grey levels; AUG_QUANTIZE rounds the result to whole grey levels, as a camera delivers them
+        AUG_OBSERVED=False, AUG_SEED=0, AUG_PROB=0.8, AUG_BLUR_PROB=0.4, AUG_BLUR_SIGMA=[0.5, 2.0], AUG_SATURATION=[0.6, 1.4],
+        AUG_CONTRAST=[0.7, 1.3], AUG_BRIGHTNESS=[-30.0, 30.0], AUG_GAIN=[0.9, 1.1], AUG_NOISE_SIGMA=[0.0, 8.0], AUG_QUANTIZE=True)
     c.TEST = edict(BATCH_PAIRS=1, test_epoch=0, VISUALIZE=False, test_iter=1, INIT_MASK="box_rendered", UPDATE_MASK="box_rendered",
                    FAST_TEST=False, PRECOMPUTED_ICP=False, BEFORE_ICP=False,
                    # how the zoom window is sampled into the network input (FAST_TEST loop): "bilinear" = one sample per network pixel,

@@ -19,6 +19,9 @@ Randomness (training) is drawn by the single staging thread in pair order with t
 (get_data_pair_train_batch([rec]): np.random.randint(18); random.randrange(len(SCALES)); [np.random.rand()]; [random.randint bg];
 mask_dilate's draws; np.random.shuffle for the point sample), so a seeded run is reproducible as long as nothing else draws from
 the global generators while an epoch is being staged -- the reference itself is not reproducible (its draws happen in pool processes).
+TRAIN.AUG_OBSERVED (photometric augmentation of image_observed, lib/utils/augment.py + csrc/augment.hip; not in the reference) draws
+from a generator of its own seeded by (TRAIN.AUG_SEED, the loader's epoch count, the pair's index in the pairdb): the global draws, and
+with them every other blob of a seeded run, are the same with it on or off.
 
 Not built (raise): img_flipped (the reference raises too), TRAIN.MASK_SYN, network.MASK_INPUTS, SCALES other than the image size
 (test loader: any 4:3 size, staged as it is; train loader: the network size only).
@@ -151,7 +154,7 @@ _FIELD_SHAPES = {"obs": (3, torch.uint8), "ren": (3, torch.uint8), "bg": (3, tor
 class _Staging(object):
     """one pinned host set + its device mirror + the events that order it against the copy and the compute stream"""
 
-    def __init__(self, B, H, W, device, fields, n_points=0):
+    def __init__(self, B, H, W, device, fields, n_points=0, augment=False):
         pin = lambda shape, dt: torch.empty(shape, dtype=dt).pin_memory()  # noqa: E731
         self.h, self.d = {}, {}
         for f in fields:
@@ -163,6 +166,9 @@ class _Staging(object):
                 "P12": ((B, 3, 4), torch.float64), "tab_off": ((B,), torch.int32), "K": ((B, 9), torch.float32)}
         if n_points:
             meta["pt_idx"] = ((B, n_points), torch.int32)
+        if augment:   # the draws of lib/utils/augment.py (TRAIN.AUG_OBSERVED); the radius is read on the host (its pinned copy)
+            meta.update(aug_on=((B,), torch.int32), aug_radius=((B,), torch.int32), aug_taps=((B, 15), torch.float32),
+                        aug_chain=((B, 7), torch.float32), aug_seed=((B,), torch.int32))
         self.mh = {k: pin(s, dt) for k, (s, dt) in meta.items()}
         self.md = {k: torch.empty_like(v, device=device) for k, v in self.mh.items()}
         self.ready = torch.cuda.Event()
@@ -184,7 +190,7 @@ class _Staging(object):
 class _DeviceLoader(object):
     """shared machinery: index / shuffle, the decode pool, the copy stream, two staging sets, the cache"""
 
-    def _setup(self, size, batch_size, shuffle, device, workers, height, width, fields, n_points=0, cache=None):
+    def _setup(self, size, batch_size, shuffle, device, workers, height, width, fields, n_points=0, cache=None, augment=False):
         self.size, self.batch_size, self.shuffle = int(size), int(batch_size), shuffle
         self.index = np.arange(self.size)
         self.device = torch.device(device)
@@ -192,7 +198,7 @@ class _DeviceLoader(object):
         self.pool = ThreadPoolExecutor(max_workers=max(1, int(workers)))
         self.copy_stream = torch.cuda.Stream(device=self.device)
         self.fields = tuple(fields)
-        self.sets = [_Staging(self.batch_size, self.H, self.W, self.device, self.fields, n_points) for _ in range(2)]
+        self.sets = [_Staging(self.batch_size, self.H, self.W, self.device, self.fields, n_points, augment) for _ in range(2)]
         self.cache = cache
         # ONE background thread stages batch k+1 (draws, cache look-ups, decode fan-out over the pool, copy-stream traffic) while the
         # caller's thread is already enqueueing the work on batch k: with staging in the caller's thread the GPU sat idle for the
@@ -313,6 +319,7 @@ class _DeviceLoader(object):
 
 def _DeviceLoader_reset(self):
     self._rewind()
+    self.epoch = getattr(self, "epoch", -1) + 1   # epochs of this loader, from 0: part of the seed of the augmentation's draws
     if self.shuffle:
         np.random.shuffle(self.index)
     self._prefetch()
@@ -550,7 +557,14 @@ class TrainDataLoader(_DeviceLoader):
         self.n_points = int(cfg.train_iter.NUM_3D_SAMPLE) if self.pm_loss else 0
         self.may_paste = any("data_syn" in rec for rec in pairdb)
         fields = ["obs", "ren", "depth", "depth_gt", "label"] + (["depth_obs"] if self.input_depth else []) + (["bg"] if self.may_paste else [])
-        self._setup(len(pairdb), batch_size, shuffle, device, workers, height, width, fields, n_points=self.n_points, cache=cache)
+        # TRAIN.AUG_OBSERVED: photometric augmentation of image_observed (lib/utils/augment.py draws, csrc/augment.hip applies)
+        self.augmenter = None
+        if cfg.TRAIN.get("AUG_OBSERVED", False):
+            from lib.utils.augment import ObservedAugmenter
+
+            self.augmenter = ObservedAugmenter(cfg)
+        self._setup(len(pairdb), batch_size, shuffle, device, workers, height, width, fields, n_points=self.n_points, cache=cache,
+                    augment=self.augmenter is not None)
         self.data_name = ["image_observed", "image_rendered", "depth_gt_observed", "class_index", "src_pose", "tgt_pose"]
         if self.input_depth:
             self.data_name += ["depth_observed", "depth_rendered"]
@@ -586,6 +600,8 @@ class TrainDataLoader(_DeviceLoader):
                      class_index=torch.empty((B,), dtype=torch.int32, device=d),
                      _mask_tmp=plane(1), _bbox=torch.empty((B, 4), dtype=torch.int32, device=d),
                      _bbox_label=torch.empty((B, 4), dtype=torch.int32, device=d))
+            if self.augmenter is not None:
+                b["_obs_plain"] = plane(3)   # the observed image as decoded; the augmentation kernel writes image_observed from it
             return b
 
         # TWO blob sets and a build stream: the blobs of batch k+1 are built (by the staging thread, on its own stream) while the
@@ -687,6 +703,10 @@ class TrainDataLoader(_DeviceLoader):
             # float32 se3 helpers when K is float32); shipped as float64, which holds either precision exactly
             mh["P12"][j] = np.matmul(self.K, se3_mul(tgt, se3_inverse(src)))
         st.any_bg = bool(mh["use_bg"].any())
+        if self.augmenter is not None:   # from its own generator (seed, epoch, pair index): the global draws above are not disturbed
+            p = self.augmenter.draw([int(i) for i in ids], self.epoch)
+            mh["aug_on"][...], mh["aug_radius"][...], mh["aug_taps"][...] = p.on, p.radius, p.taps
+            mh["aug_chain"][...], mh["aug_seed"][...] = p.chain, p.seed.view(np.int32)
         self._fill_files(st, jobs)
         st.n, st.has_gt = len(ids), True
         self._upload_meta(st, tuple(st.mh.keys()))
@@ -712,10 +732,14 @@ class TrainDataLoader(_DeviceLoader):
         ops.pair_blobs_from_raw(self.batch_size, self.H, self.W, self.depth_factor, self.pixel_means_bgr, obs_bgr=st.d["obs"],
                                 bg_bgr=st.d["bg"] if (self.may_paste and st.any_bg) else None, use_bg=st.md["use_bg"], ren_bgr=st.d["ren"],
                                 depth_ren=st.d["depth"], depth_a=st.d["depth_gt"], depth_b=st.d.get("depth_obs"), label=st.d["label"],
-                                mask_idx=st.md["mask_idx"], image_observed=out["image_observed"], image_rendered=out["image_rendered"],
+                                mask_idx=st.md["mask_idx"], image_observed=out["_obs_plain" if self.augmenter is not None else "image_observed"],
+                                image_rendered=out["image_rendered"],
                                 mask_rendered=out["mask_rendered"], depth_rendered=out["depth_rendered"], depth_a_out=out["depth_gt_observed"],
                                 depth_b_out=out.get("depth_observed") if self.input_depth else None, mask_label=out["mask_gt_observed"],
                                 label_raw=first if raw_label else None, bbox_ren=bbox, bbox_label=bbox_label)
+        if self.augmenter is not None:
+            ops.augment_observed(out["_obs_plain"], st.md["aug_on"], st.mh["aug_radius"].numpy(), st.md["aug_taps"], st.md["aug_chain"],
+                                 st.md["aug_seed"], self.pixel_means_bgr, quantize=self.augmenter.quantize, out=out["image_observed"])
         if need_mask:
             if self.init_mask == "box_gt":
                 ops.box_mask(bbox_label, first)

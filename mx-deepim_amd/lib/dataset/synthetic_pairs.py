@@ -39,6 +39,12 @@ class SyntheticPairs(object):
                                                               zNear=config.dataset.ZNEAR, zFar=config.dataset.ZFAR,
                                                               brightness_ratios=syn.LM_BRIGHTNESS_RATIOS, device=device,
                                                               meshes=[(v, None, t, f, tex) for v, t, f, tex in self.models])
+        # photometric augmentation of the observed training image (TRAIN.AUG_OBSERVED, lib/utils/augment.py); never at test time
+        self.augmenter = None
+        if config.TRAIN.get("AUG_OBSERVED", False):
+            from lib.utils.augment import ObservedAugmenter
+
+            self.augmenter = ObservedAugmenter(config)
         n_batches = int(num_pairs) // self.batch_pairs  # whole batches only
         lo, hi = (even_shard_range if equal_shards else shard_range)(n_batches, rank, world)
         if equal_shards and hi == lo:
@@ -79,8 +85,14 @@ class SyntheticPairs(object):
         order = np.random.RandomState(self.seed + epoch).permutation(len(self.batch_ids)) if self.config.TRAIN.SHUFFLE else np.arange(len(self.batch_ids))
         for j in order:
             i = self.batch_ids[int(j)]
-            yield syn.build_device_train_batch(self.render_machine, self.batch_pairs, seed=self.seed + 1000 * (i + 1), models=self.models,
-                                               n_classes=len(self.classes), pixel_means=self.config.network.PIXEL_MEANS,
-                                               npts=int(self.config.train_iter.NUM_3D_SAMPLE), device=self.device,
-                                               occluders=self.occluders, lit=self.lit, occ_max_rate=self.occ_max_rate,
-                                               light_machine=self.light_machine)
+            b = syn.build_device_train_batch(self.render_machine, self.batch_pairs, seed=self.seed + 1000 * (i + 1), models=self.models,
+                                             n_classes=len(self.classes), pixel_means=self.config.network.PIXEL_MEANS,
+                                             npts=int(self.config.train_iter.NUM_3D_SAMPLE), device=self.device,
+                                             occluders=self.occluders, lit=self.lit, occ_max_rate=self.occ_max_rate,
+                                             light_machine=self.light_machine)
+            if self.augmenter is not None:
+                # the pair's key: batch_id * batch_pairs + slot.  image_observed is the only observed colour image of a batch (the
+                # occluded-scene path merges its occluded and unoccluded renders into it), so it is the only blob that changes
+                params = self.augmenter.draw([i * self.batch_pairs + s for s in range(self.batch_pairs)], epoch)
+                b["image_observed"] = self.augmenter.apply(b["image_observed"], params, self.config.network.PIXEL_MEANS)
+            yield b

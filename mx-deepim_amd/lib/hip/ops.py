@@ -901,6 +901,25 @@ def mask_dilate(mask_in, thickness4, out=None):
     return out
 
 
+def augment_observed(image, on, radius, taps, chain, seed, pixel_means_bgr, quantize=True, out=None):
+    """photometric augmentation of an image_observed blob (B,3,H,W) with the caller's draws (csrc/augment.hip; include/deepim_hip.h lists
+    the rules; lib/utils/augment.py draws them).  Device tensors: on (B,) int32, taps (B,15) f32, chain (B,7) f32 = {saturation,
+    contrast, brightness, gain of plane 0, 1, 2, noise sigma}, seed (B,) int32 holding the uint32 bits.  radius: HOST int array (B,),
+    0..7 (checked before the launch).  out must not be image."""
+    B, C, H, W = image.shape
+    if C != 3:
+        raise ValueError("augment_observed: expected a (B,3,H,W) blob, got {}".format(tuple(image.shape)))
+    out = out if out is not None else torch.empty_like(image)
+    rad = np.ascontiguousarray(np.asarray(radius, dtype=np.int32).reshape(-1))
+    if rad.size != B or tuple(on.shape) != (B,) or tuple(taps.shape) != (B, 15) or tuple(chain.shape) != (B, 7) or tuple(seed.shape) != (B,) \
+            or tuple(out.shape) != tuple(image.shape):
+        raise ValueError("augment_observed: parameters of {} pairs expected: on (B,), radius (B,), taps (B,15), chain (B,7), seed (B,)".format(B))
+    keep, mp = host_f32(pixel_means_bgr, 3)
+    check(lib().dim_augment_observed(dptr(image, f32), dptr(out, f32), B, H, W, mp, dptr(on, i32), rad.ctypes.data, dptr(taps, f32),
+                                     dptr(chain, f32), dptr(seed, i32), int(bool(quantize)), current_stream()))
+    return out
+
+
 FLOW_WEIGHT_ID = {"all": 0, "viz": 1, "valid": 2}
 
 
