@@ -16,7 +16,6 @@
 // Two launches per iteration; nothing allocates or synchronises, so the stage is graph-capturable.
 // Float64 per point, not float32: the stage is bound by its 2 x iters dependent launches, not by arithmetic (a pair has 5k-80k
 // points), and the gate decision e > max_px then agrees with the restatement's, so the inlier counts are equal, not close.
-#include "block_sum.h"
 #include "common.h"
 #include "twist_solve.h"
 
@@ -34,14 +33,8 @@ __global__ __launch_bounds__(256) void flow_pnp_accumulate_kernel(const float* _
   const int b = blockIdx.y, tid = threadIdx.x;
   const PinholeCam c = cam_pick(K_per_sample, k9, b);
   const double fx = c.fx, fy = c.fy, cx = c.cx, cy = c.cy;
-  double R[9] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0}, t[3] = {0.0, 0.0, 0.0};
-  if (it > 0) {
-    const double* s = state + (long)b * kGnState;
-#pragma unroll
-    for (int k = 0; k < 9; ++k) R[k] = s[k];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) t[k] = s[9 + k];
-  }
+  double R[9], t[3];
+  gn_load_pose(state, b, it, R, t);
   const PixelBox box = clamp_bbox(bbox, b, H, W);
   const int x0 = box.x0, x1 = box.x1, y0 = box.y0, y1 = box.y1;
   const int xq0 = x0 & ~3;                       // the quads are aligned to 4 pixels in the row
@@ -105,24 +98,10 @@ __global__ __launch_bounds__(256) void flow_pnp_accumulate_kernel(const float* _
         if (e > gate) continue;   // w = 0
         if (!(e <= hub)) w = hub / e;
       }
-      // d(pixel)/dm = [ax 0 bx; 0 ay by], dm = omega x m + v
-      const double ax = fx / mz, bx = -fx * mx / (mz * mz), ay = fy / mz, by = -fy * my / (mz * mz);
-      const double Jx[6] = {bx * my, ax * mz - bx * mx, -ax * my, ax, 0.0, bx};
-      const double Jy[6] = {by * my - ay * mz, -by * mx, ay * mx, 0.0, ay, by};
-      int q = 0;
-#pragma unroll
-      for (int a = 0; a < 6; ++a) {
-#pragma unroll
-        for (int e = a; e < 6; ++e) acc[q++] += w * (Jx[a] * Jx[e] + Jy[a] * Jy[e]);
-      }
-#pragma unroll
-      for (int a = 0; a < 6; ++a) acc[21 + a] += w * (Jx[a] * rx + Jy[a] * ry);
-      acc[27] += 1.0;
-      acc[28] += e2;
+      gn_add_pixel(acc, fx, fy, mx, my, mz, rx, ry, w, e2);
     }
   }
-  const double total = block_sum(acc);
-  if (tid < kGnTerms) partial[((long)b * kGnBlocks + blockIdx.x) * kGnSlot + tid] = total;
+  gn_store_partial(acc, partial, b);
 }
 
 // iters == 0: se3_q of a pair that never updated
@@ -157,17 +136,14 @@ extern "C" int dim_flow_pnp(const float* depth_rendered, const float* flow, cons
     return dim_copy_words(pose_out, pose_src, 12L * B, stream);
   }
   const PinholeCam k9 = cam_of_k9(K9);
-  double* state = (double*)workspace;
-  double* partial = state + (long)B * kGnState;
+  const GnWorkspace ws(workspace, B);
   auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
   const bool vec = W % 4 == 0 && al16(depth_rendered) && al16(flow) && (!valid || al16(valid));
   const int comp_x = standard_rep ? 0 : 1;   // (dy, dx) unless standard_rep
-  for (int it = 0; it < iters; ++it) {
+  gn_iterate<DIM_STATUS_FLOW_PNP_FEW_POINTS>(ws, B, iters, pose_src, pose_out, se3_q, stats, status, as_stream(stream), [&](int it) {
     hipLaunchKernelGGL(vec ? flow_pnp_accumulate_kernel<true> : flow_pnp_accumulate_kernel<false>, dim3(kGnBlocks, B), dim3(256), 0,
                        as_stream(stream), depth_rendered, flow, valid, bbox, k9, K_per_sample, H, W, comp_x, it, warm, huber_px, max_px,
-                       (const double*)state, partial);
-    hipLaunchKernelGGL(gn_solve_kernel<DIM_STATUS_FLOW_PNP_FEW_POINTS>, dim3(B), dim3(64), 0, as_stream(stream), (const double*)partial,
-                       state, it, iters, pose_src, pose_out, se3_q, stats, status);
-  }
+                       (const double*)ws.state, ws.partial);
+  });
   return check_launch("flow_pnp");
 }

@@ -9,7 +9,6 @@
 //   gn_solve_kernel        (twist_solve.h) one workgroup per pair: sums the partials, Cholesky in float64,
 //                          T_delta <- [Rodrigues(omega) | v] T_delta, stats / status, and after the last iteration pose_out = T_delta T0
 // Two launches per iteration; nothing allocates or synchronises, so the stage is graph-capturable.
-#include "block_sum.h"
 #include "common.h"
 #include "twist_solve.h"
 
@@ -22,14 +21,8 @@ __global__ __launch_bounds__(256) void icp_accumulate_kernel(const float* __rest
                                                              double* __restrict__ partial) {
   const int b = blockIdx.y, tid = threadIdx.x;
   const PinholeCam c = cam_pick(K_per_sample, k9, b);
-  float R[9] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f}, t[3] = {0.f, 0.f, 0.f};
-  if (it > 0) {
-    const double* s = state + (long)b * kGnState;
-#pragma unroll
-    for (int k = 0; k < 9; ++k) R[k] = (float)s[k];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) t[k] = (float)s[9 + k];
-  }
+  float R[9], t[3];
+  gn_load_pose(state, b, it, R, t);
   const PixelBox box = clamp_bbox(bbox, b, H, W);
   const int x0 = box.x0, x1 = box.x1, y0 = box.y0, y1 = box.y1;
   const int bw = x1 - x0 + 1;
@@ -83,23 +76,11 @@ __global__ __launch_bounds__(256) void icp_accumulate_kernel(const float* __rest
     if (ex * ex + ey * ey + ez * ez > md2) continue;
     const float r = nx * ex + ny * ey + nz * ez;
     const float J[6] = {py * nz - pz * ny, pz * nx - px * nz, px * ny - py * nx, nx, ny, nz};
-    int k = 0;
-#pragma unroll
-    for (int a = 0; a < 6; ++a) {
-#pragma unroll
-      for (int e = a; e < 6; ++e) acc[k++] += J[a] * J[e];
-    }
-#pragma unroll
-    for (int a = 0; a < 6; ++a) acc[21 + a] += J[a] * r;
+    gn_add_row(acc, J, r);
     acc[27] += 1.f;
     acc[28] += r * r;
   }
-  // float64 from here on, in a fixed order
-  double acc64[kGnTerms];
-#pragma unroll
-  for (int k = 0; k < kGnTerms; ++k) acc64[k] = (double)acc[k];
-  const double total = block_sum(acc64);
-  if (tid < kGnTerms) partial[((long)b * kGnBlocks + blockIdx.x) * kGnSlot + tid] = total;
+  gn_store_partial(acc, partial, b);   // float64 from here on, in a fixed order
 }
 
 }  // namespace dim
@@ -122,13 +103,10 @@ extern "C" int dim_icp_refine(const float* depth_rendered, const float* depth_ob
   DIM_REQUIRE(depth_rendered && depth_observed && pose_in && K9 && workspace && pose_out, "icp_refine: null pointer");
   if (iters == 0) return dim_copy_words(pose_out, pose_in, 12L * B, stream);
   const PinholeCam k9 = cam_of_k9(K9);
-  double* state = (double*)workspace;
-  double* partial = state + (long)B * kGnState;
-  for (int it = 0; it < iters; ++it) {
+  const GnWorkspace ws(workspace, B);
+  gn_iterate<DIM_STATUS_ICP_FEW_POINTS>(ws, B, iters, pose_in, pose_out, nullptr, stats, status, as_stream(stream), [&](int it) {
     hipLaunchKernelGGL(icp_accumulate_kernel, dim3(kGnBlocks, B), dim3(256), 0, as_stream(stream), depth_rendered, depth_observed,
-                       mask_observed, bbox, k9, K_per_sample, H, W, max_dist, it, (const double*)state, partial);
-    hipLaunchKernelGGL(gn_solve_kernel<DIM_STATUS_ICP_FEW_POINTS>, dim3(B), dim3(64), 0, as_stream(stream), (const double*)partial, state,
-                       it, iters, pose_in, pose_out, (float*)nullptr, stats, status);
-  }
+                       mask_observed, bbox, k9, K_per_sample, H, W, max_dist, it, (const double*)ws.state, ws.partial);
+  });
   return check_launch("icp_refine");
 }

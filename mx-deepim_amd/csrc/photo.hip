@@ -15,7 +15,6 @@
 //   gn_solve_kernel          (twist_solve.h) one workgroup per pair, driven with one iteration index over levels * iters
 // No atomics, no memcpy / memset: a replay is bit-identical and the stage is graph-capturable.  Float64 per point, as flow_pnp.hip: the
 // stage is bound by its dependent launches, and the gate and cell decisions then agree with the restatement's, so the counts are equal.
-#include "block_sum.h"
 #include "common.h"
 #include "twist_solve.h"
 
@@ -212,14 +211,8 @@ __global__ __launch_bounds__(256) void photo_accumulate_kernel(const float* __re
   const int b = blockIdx.y, tid = threadIdx.x;
   const PinholeCam c = cam_pick(K_per_sample, k9, b);
   const double fx = c.fx, fy = c.fy, cx = c.cx, cy = c.cy;
-  double R[9] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0}, t[3] = {0.0, 0.0, 0.0};
-  if (it > 0) {
-    const double* s = state + (long)b * kGnState;
-#pragma unroll
-    for (int k = 0; k < 9; ++k) R[k] = s[k];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) t[k] = s[9 + k];
-  }
+  double R[9], t[3];
+  gn_load_pose(state, b, it, R, t);
   const double* g = gain + (long)b * kPhotoGain;
   const double ga = g[5], gb = g[6];
   const bool may_step = g[7] > 0.5 && cam_ok(c);
@@ -262,19 +255,11 @@ __global__ __launch_bounds__(256) void photo_accumulate_kernel(const float* __re
     // gp = gx du/dp + gy dv/dp, J = (p x gp, gp)
     const double gpx = gx * (fx / pz), gpy = gy * (fy / pz), gpz = -(gx * fx * px + gy * fy * py) / (pz * pz);
     const double J[6] = {py * gpz - pz * gpy, pz * gpx - px * gpz, px * gpy - py * gpx, gpx, gpy, gpz};
-    int k = 0;
-#pragma unroll
-    for (int a = 0; a < 6; ++a) {
-      const double wa = w * J[a];
-#pragma unroll
-      for (int f = a; f < 6; ++f) acc[k++] += wa * J[f];
-      acc[21 + a] += wa * r;
-    }
+    gn_add_row(acc, J, r, w);
     acc[27] += 1.0;
     acc[28] += w * r * r;
   }
-  const double total = block_sum(acc);
-  if (tid < kGnTerms) partial[((long)b * kGnBlocks + blockIdx.x) * kGnSlot + tid] = total;
+  gn_store_partial(acc, partial, b);
 }
 
 }  // namespace dim
@@ -314,8 +299,7 @@ extern "C" int dim_photo_refine(const float* image_observed, const float* image_
   const PinholeCam k9 = cam_of_k9(K9);
   const PhotoLayout L = photo_layout(B, H, W, levels);
   char* ws = (char*)workspace;
-  double* state = (double*)ws;
-  double* partial = state + (long)B * kGnState;
+  const GnWorkspace gn(workspace, B);
   double* gains = (double*)(ws + L.gain);
   PhotoPlanes lv[kPhotoMaxLevels];
   for (int l = 0; l < levels; ++l)
@@ -332,17 +316,14 @@ extern "C" int dim_photo_refine(const float* image_observed, const float* image_
                        L.W[l - 1], L.H[l], L.W[l]);
   }
   hipLaunchKernelGGL(photo_stats_kernel, dim3(kGnBlocks, B), dim3(256), 0, st, (const float*)lv[0].p[0], (const float*)lv[0].p[1],
-                     (const float*)lv[0].p[3], bbox, H, W, partial);
-  hipLaunchKernelGGL(photo_gain_kernel, dim3(B), dim3(64), 0, st, (const double*)partial, gain, gains);
-  const int total = levels * iters;
-  int it = 0;
-  for (int l = levels - 1; l >= 0; --l)
-    for (int k = 0; k < iters; ++k, ++it) {
-      hipLaunchKernelGGL(photo_accumulate_kernel, dim3(kGnBlocks, B), dim3(256), 0, st, (const float*)lv[l].p[0], (const float*)lv[l].p[1],
-                         (const float*)lv[l].p[2], (const float*)lv[l].p[3], bbox, k9, K_per_sample, H, W, L.H[l], L.W[l], l, huber, gate,
-                         (const double*)gains, it, (const double*)state, partial);
-      hipLaunchKernelGGL(gn_solve_kernel<DIM_STATUS_PHOTO_FEW_POINTS>, dim3(B), dim3(64), 0, st, (const double*)partial, state, it, total,
-                         pose_in, pose_out, (float*)nullptr, stats, status);
-    }
+                     (const float*)lv[0].p[3], bbox, H, W, gn.partial);
+  hipLaunchKernelGGL(photo_gain_kernel, dim3(B), dim3(64), 0, st, (const double*)gn.partial, gain, gains);
+  // one iteration index over levels * iters, from the coarsest level down
+  gn_iterate<DIM_STATUS_PHOTO_FEW_POINTS>(gn, B, levels * iters, pose_in, pose_out, nullptr, stats, status, st, [&](int it) {
+    const int l = levels - 1 - it / iters;
+    hipLaunchKernelGGL(photo_accumulate_kernel, dim3(kGnBlocks, B), dim3(256), 0, st, (const float*)lv[l].p[0], (const float*)lv[l].p[1],
+                       (const float*)lv[l].p[2], (const float*)lv[l].p[3], bbox, k9, K_per_sample, H, W, L.H[l], L.W[l], l, huber, gate,
+                       (const double*)gains, it, (const double*)gn.state, gn.partial);
+  });
   return check_launch("photo_refine");
 }

@@ -18,7 +18,6 @@
 //                          is positional, a replay is bit-identical
 //   gn_solve_kernel        (twist_solve.h) as the other Gauss-Newton stages
 // Two launches per iteration; nothing allocates or synchronises, so the stage is graph-capturable.
-#include "block_sum.h"
 #include "common.h"
 #include "twist_solve.h"
 
@@ -107,14 +106,8 @@ __global__ __launch_bounds__(256) void sil_accumulate_kernel(const float* __rest
   const int b = blockIdx.y, tid = threadIdx.x, wave = tid >> 6;
   const PinholeCam c = cam_pick(K_per_sample, k9, b);
   const double fx = c.fx, fy = c.fy, cx = c.cx, cy = c.cy;
-  double R[9] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0}, t[3] = {0.0, 0.0, 0.0};
-  if (it > 0) {
-    const double* s = state + (long)b * kGnState;
-#pragma unroll
-    for (int k = 0; k < 9; ++k) R[k] = s[k];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) t[k] = s[9 + k];
-  }
+  double R[9], t[3];
+  gn_load_pose(state, b, it, R, t);
   const PixelBox box = clamp_bbox(bbox, b, H, W);
   const int bw = box.x1 - box.x0 + 1, bh = box.y1 - box.y0 + 1;
   const long n = (cam_ok(c) && bw > 0 && bh > 0) ? (long)bw * bh : 0;
@@ -145,20 +138,7 @@ __global__ __launch_bounds__(256) void sil_accumulate_kernel(const float* __rest
     if (!(e <= gate)) return;   // w = 0
     double w = 1.0;
     if (!(e <= hub)) w = hub / e;
-    // d(pixel)/dm = [ax 0 bx; 0 ay by], dm = omega x m + v
-    const double ax = fx / mz, bx = -fx * mx / (mz * mz), ay = fy / mz, by = -fy * my / (mz * mz);
-    const double Jx[6] = {bx * my, ax * mz - bx * mx, -ax * my, ax, 0.0, bx};
-    const double Jy[6] = {by * my - ay * mz, -by * mx, ay * mx, 0.0, ay, by};
-    int q = 0;
-#pragma unroll
-    for (int a = 0; a < 6; ++a) {
-#pragma unroll
-      for (int k = a; k < 6; ++k) acc[q++] += w * (Jx[a] * Jx[k] + Jy[a] * Jy[k]);
-    }
-#pragma unroll
-    for (int a = 0; a < 6; ++a) acc[21 + a] += w * (Jx[a] * rx + Jy[a] * ry);
-    acc[27] += 1.0;
-    acc[28] += e2;
+    gn_add_pixel(acc, fx, fy, mx, my, mz, rx, ry, w, e2);
   };
 
   int count = 0;   // queue length: the same in every lane
@@ -197,8 +177,7 @@ __global__ __launch_bounds__(256) void sil_accumulate_kernel(const float* __rest
     }
   }
   if (tid < count) point(queue[tid]);
-  const double total = block_sum(acc);
-  if (tid < kGnTerms) partial[((long)b * kGnBlocks + blockIdx.x) * kGnSlot + tid] = total;
+  gn_store_partial(acc, partial, b);
 }
 
 }  // namespace dim
@@ -234,13 +213,10 @@ extern "C" int dim_sil_refine(const float* depth_rendered, const int* field, con
   DIM_REQUIRE(depth_rendered && field && pose_in && K9 && workspace && pose_out, "sil_refine: null pointer");
   if (iters == 0) return dim_copy_words(pose_out, pose_in, 12L * B, stream);
   const PinholeCam k9 = cam_of_k9(K9);
-  double* state = (double*)workspace;
-  double* partial = state + (long)B * kGnState;
-  for (int it = 0; it < iters; ++it) {
+  const GnWorkspace ws(workspace, B);
+  gn_iterate<DIM_STATUS_SIL_FEW_POINTS>(ws, B, iters, pose_in, pose_out, nullptr, stats, status, as_stream(stream), [&](int it) {
     hipLaunchKernelGGL(sil_accumulate_kernel, dim3(kGnBlocks, B), dim3(256), 0, as_stream(stream), depth_rendered, field, bbox, k9,
-                       K_per_sample, H, W, it, huber_px, max_px, (const double*)state, partial);
-    hipLaunchKernelGGL(gn_solve_kernel<DIM_STATUS_SIL_FEW_POINTS>, dim3(B), dim3(64), 0, as_stream(stream), (const double*)partial, state,
-                       it, iters, pose_in, pose_out, (float*)nullptr, stats, status);
-  }
+                       K_per_sample, H, W, it, huber_px, max_px, (const double*)ws.state, ws.partial);
+  });
   return check_launch("sil_refine");
 }

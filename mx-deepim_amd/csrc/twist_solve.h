@@ -1,7 +1,9 @@
 // Float64 device helpers shared by the Gauss-Newton pose stages (icp.hip, flow_pnp.hip, photo.hip, sil.hip) and the pose algebra (se3.hip): the 6x6
 // Cholesky solve of the normal equations, the Rodrigues rotation of a twist's omega, and rotation matrix -> quaternion; and what
-// the Gauss-Newton stages have in common: the workspace layout, the camera and box of a pair, and the solve kernel.
+// the Gauss-Newton stages have in common: the workspace layout, the camera and box of a pair, the solve kernel, the pieces of an
+// accumulate kernel (pose load, normal-equation terms, partial store) and the host loop over the two launches of an iteration.
 #pragma once
+#include "block_sum.h"
 #include "common.h"
 
 namespace dim {
@@ -187,6 +189,99 @@ __global__ __launch_bounds__(64) void gn_solve_kernel(const double* __restrict__
     mat2quat_d(R, q);
     for (int k = 0; k < 4; ++k) sq[k] = (float)q[k];
     for (int k = 0; k < 3; ++k) sq[4 + k] = (float)t[k];
+  }
+}
+
+// ---- what the accumulate kernels share.  All of it is inlined: the kGnTerms accumulators of a lane are registers of the kernel.
+
+// the correction T_delta = [R | t] an iteration linearises at: the identity at it == 0, else the state row of pair b as T
+template <class T>
+__device__ __forceinline__ void gn_load_pose(const double* __restrict__ state, int b, int it, T (&R)[9], T (&t)[3]) {
+#pragma unroll
+  for (int k = 0; k < 9; ++k) R[k] = k % 4 == 0 ? (T)1 : (T)0;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) t[k] = (T)0;
+  if (it > 0) {
+    const double* s = state + (long)b * kGnState;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) R[k] = (T)s[k];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) t[k] = (T)s[9 + k];
+  }
+}
+
+// one scalar residual r with Jacobian J: terms 0..20 += J J^T (upper triangle), terms 21..26 += J r.  Terms 27 and 28 are the caller's.
+template <class T>
+__device__ __forceinline__ void gn_add_row(T (&acc)[kGnTerms], const T (&J)[6], T r) {
+  int k = 0;
+#pragma unroll
+  for (int a = 0; a < 6; ++a) {
+#pragma unroll
+    for (int e = a; e < 6; ++e) acc[k++] += J[a] * J[e];
+  }
+#pragma unroll
+  for (int a = 0; a < 6; ++a) acc[21 + a] += J[a] * r;
+}
+// the same under the weight w: += (w J[a]) J[e] and (w J[a]) r
+template <class T>
+__device__ __forceinline__ void gn_add_row(T (&acc)[kGnTerms], const T (&J)[6], T r, T w) {
+  int k = 0;
+#pragma unroll
+  for (int a = 0; a < 6; ++a) {
+    const T wa = w * J[a];
+#pragma unroll
+    for (int e = a; e < 6; ++e) acc[k++] += wa * J[e];
+    acc[21 + a] += wa * r;
+  }
+}
+
+// one reprojected point m = (mx, my, mz), mz > 0, with pixel residual (rx, ry), e2 = rx^2 + ry^2, under the weight w: both rows of
+// d(pixel)/dm = [ax 0 bx; 0 ay by], dm = omega x m + v, into terms 0..26, the point into 27 and e2 (unweighted) into 28
+__device__ __forceinline__ void gn_add_pixel(double (&acc)[kGnTerms], double fx, double fy, double mx, double my, double mz, double rx,
+                                             double ry, double w, double e2) {
+  const double ax = fx / mz, bx = -fx * mx / (mz * mz), ay = fy / mz, by = -fy * my / (mz * mz);
+  const double Jx[6] = {bx * my, ax * mz - bx * mx, -ax * my, ax, 0.0, bx};
+  const double Jy[6] = {by * my - ay * mz, -by * mx, ay * mx, 0.0, ay, by};
+  int q = 0;
+#pragma unroll
+  for (int a = 0; a < 6; ++a) {
+#pragma unroll
+    for (int e = a; e < 6; ++e) acc[q++] += w * (Jx[a] * Jx[e] + Jy[a] * Jy[e]);
+  }
+#pragma unroll
+  for (int a = 0; a < 6; ++a) acc[21 + a] += w * (Jx[a] * rx + Jy[a] * ry);
+  acc[27] += 1.0;
+  acc[28] += e2;
+}
+
+// the workgroup's sums (block_sum.h: every lane must call) into its slot of pair b = partial[b][blockIdx.x]
+__device__ __forceinline__ void gn_store_partial(const double (&acc)[kGnTerms], double* __restrict__ partial, int b) {
+  const double total = block_sum(acc);
+  if (threadIdx.x < kGnTerms) partial[((long)b * kGnBlocks + blockIdx.x) * kGnSlot + threadIdx.x] = total;
+}
+// per-lane float32 sums: float64 from here on, in a fixed order
+__device__ __forceinline__ void gn_store_partial(const float (&acc)[kGnTerms], double* __restrict__ partial, int b) {
+  double acc64[kGnTerms];
+#pragma unroll
+  for (int k = 0; k < kGnTerms; ++k) acc64[k] = (double)acc[k];
+  gn_store_partial(acc64, partial, b);
+}
+
+// ---- host side of a stage's driver
+struct GnWorkspace {
+  double* state;
+  double* partial;
+  GnWorkspace(void* workspace, int B) : state((double*)workspace), partial(state + (long)B * kGnState) {}
+};
+
+// the two launches of each of `total` iterations: accumulate(it), the stage's own launch into ws.partial, then the solve
+template <int FAIL_BIT, class Accumulate>
+inline void gn_iterate(const GnWorkspace& ws, int B, int total, const float* pose_in, float* pose_out, float* se3_q, float* stats,
+                       int* status, hipStream_t st, Accumulate accumulate) {
+  for (int it = 0; it < total; ++it) {
+    accumulate(it);
+    hipLaunchKernelGGL(gn_solve_kernel<FAIL_BIT>, dim3(B), dim3(64), 0, st, (const double*)ws.partial, ws.state, it, total, pose_in,
+                       pose_out, se3_q, stats, status);
   }
 }
 

@@ -13,12 +13,15 @@ and the whole loop can be captured into one hipGraph (`Refiner(capture_graph=Tru
 size of the camera image, config.SCALES[0] (any 4:3 size, K the camera of that image); the network input stays 480x640.
 """
 from __future__ import print_function, division
+from collections import namedtuple
 
 import numpy as np
 import torch
 
 from lib.hip import ops
 from deepim.core.coarse import CoarseInit, boxes_from_int, coarse_settings
+from deepim.core.pose_stages import (POST_LOOP, STAGE_KEY, STAGES, flow_pnp_settings, icp_settings, int_setting, photo_settings,  # noqa: F401
+                                     sil_settings, stage_settings, stages_on)
 from deepim.core.score_lists import PairLists, ScoreLists
 from deepim.symbols.deepIM_flownet import FlowNetHip, source_size, zoom_filter
 
@@ -32,14 +35,21 @@ RT_KEYS = ("rot_err", "trans_err", "poses_est", "poses_gt")    # per pose: the f
 FAMILY_KEYS = {"rt": RT_KEYS, "err": ERR_KEYS, "vsd": VSD_KEYS, "grid": GRID_KEYS, "bop": BOP_KEYS}
 HYP_KEYS = ("score", "choice", "rot_err", "trans_err", "undetected")   # per pair with several hypotheses
 COARSE_KEYS = ("idx", "score", "status", "pose")                       # per pair: the kept candidates of the coarse stage, best first
+# the one-row pose sets of pred_eval, in the order of their tables.  pose: its attribute on the refiner; full: every family scores it, from
+# _read_out's rows -- else the error code alone, from a copy of its own, and TEST.VSD / TEST.BOP refuse its `word` row; keys: (key, default)
+OneRowSet = namedtuple("OneRowSet", "name pose full word headline keys")
+ONE_ROW_SETS = (
+    OneRowSet("icp", "pose_icp", True, None, "evaluate ICP ({} iterations, gate {} m):", (("ICP_ITER", 0), ("ICP_MAX_DIST", 0.02))),
+    OneRowSet("photo", "pose_photo", False, "photometric", "evaluate photometric polish ({} levels x {} iterations, Huber {}, gate {}):",
+     (("PHOTO_LEVELS", 3), ("PHOTO_ITER", 0), ("PHOTO_HUBER", 30.0), ("PHOTO_MAX", 180.0))),
+    OneRowSet("sil", "pose_sil", False, "silhouette", "evaluate silhouette polish ({} rounds x {} iterations, Huber {} px, gate {} px, mask {}):",
+     (("SIL_ROUNDS", 2), ("SIL_ITER", 0), ("SIL_HUBER_PX", 2.0), ("SIL_MAX_PX", 12.0), ("SIL_MASK", "observed"))))
 
 
 def hyp_settings(cfg):
     """-> (HYP_NUM, HYP_ROT_DEG, HYP_SCORE, HYP_DEPTH_TAU) of cfg.TEST, checked; ValueError names the bad key"""
     T = cfg.TEST
-    n = T.get("HYP_NUM", 1)
-    if isinstance(n, bool) or not float(n).is_integer() or int(n) < 1:
-        raise ValueError("TEST.HYP_NUM must be an integer >= 1 (1 = one hypothesis per pair, off), got {!r}".format(n))
+    n = int_setting("HYP_NUM", T.get("HYP_NUM", 1), 1, None, "an integer >= 1 (1 = one hypothesis per pair, off)")
     deg = float(T.get("HYP_ROT_DEG", 30.0))
     if not np.isfinite(deg):
         raise ValueError("TEST.HYP_ROT_DEG must be finite, got {!r}".format(T.get("HYP_ROT_DEG")))
@@ -49,7 +59,7 @@ def hyp_settings(cfg):
     tau = float(T.get("HYP_DEPTH_TAU", 0.02))
     if not (np.isfinite(tau) and tau > 0):
         raise ValueError("TEST.HYP_DEPTH_TAU must be a finite distance > 0 (metres), got {!r}".format(T.get("HYP_DEPTH_TAU")))
-    return int(n), deg, score, tau
+    return n, deg, score, tau
 
 
 def bop_vsd_settings(cfg):
@@ -68,90 +78,6 @@ def bop_vsd_settings(cfg):
         raise ValueError("TEST.BOP_VSD_TAU must hold 1 to {} finite fractions > 0 of the diameter, got {!r}".format(
             ops.VSD_GRID_MAX_TAU, T.BOP_VSD_TAU))
     return True, delta, fracs
-
-
-def flow_pnp_settings(cfg):
-    """-> (FLOW_PNP_ITER, FLOW_PNP_WARM, FLOW_PNP_HUBER_PX, FLOW_PNP_MAX_PX) of cfg.TEST, checked; ValueError names the bad key(s).
-    The stage reads the flow head's output of every loop iteration, so it needs PRED_FLOW and the full (not FAST_TEST) graph; choosing
-    among per-hypothesis flow poses is not defined, so it is refused together with HYP_NUM > 1."""
-    T = cfg.TEST
-    n = T.get("FLOW_PNP_ITER", 0) or 0
-    if isinstance(n, bool) or not float(n).is_integer() or int(n) < 0:
-        raise ValueError("TEST.FLOW_PNP_ITER must be an integer >= 0 (0 = off), got {!r}".format(n))
-    warm = T.get("FLOW_PNP_WARM", 2)
-    if isinstance(warm, bool) or not float(warm).is_integer() or int(warm) < 0:
-        raise ValueError("TEST.FLOW_PNP_WARM must be an integer >= 0, got {!r}".format(warm))
-    huber, gate = float(T.get("FLOW_PNP_HUBER_PX", 2.0)), float(T.get("FLOW_PNP_MAX_PX", 8.0))
-    if not (np.isfinite(huber) and huber > 0):
-        raise ValueError("TEST.FLOW_PNP_HUBER_PX must be a finite number of pixels > 0, got {!r}".format(T.get("FLOW_PNP_HUBER_PX")))
-    if not (np.isfinite(gate) and gate >= huber):
-        raise ValueError("TEST.FLOW_PNP_MAX_PX must be finite and >= TEST.FLOW_PNP_HUBER_PX, got {!r}".format(T.get("FLOW_PNP_MAX_PX")))
-    if int(n) > 0:
-        if not cfg.network.PRED_FLOW:
-            raise ValueError("TEST.FLOW_PNP_ITER > 0 needs network.PRED_FLOW (the stage reads the flow head's output)")
-        if T.FAST_TEST:
-            raise ValueError("TEST.FLOW_PNP_ITER > 0 needs TEST.FAST_TEST off (the fast graph has no flow head)")
-        if int(T.get("HYP_NUM", 1)) > 1:
-            raise ValueError("TEST.FLOW_PNP_ITER > 0 cannot be combined with TEST.HYP_NUM > 1")
-    return int(n), int(warm), huber, gate
-
-
-def photo_settings(cfg):
-    """-> (PHOTO_ITER, PHOTO_LEVELS, PHOTO_HUBER, PHOTO_MAX, PHOTO_GAIN) of cfg.TEST, checked; ValueError names the bad key(s).
-    PHOTO_ITER counts Gauss-Newton iterations per pyramid level (0 = off); the two thresholds are in units of the channel sum.
-    Selecting among polished hypotheses is not defined, so the stage is refused together with HYP_NUM > 1 and COARSE_VIEWS > 0."""
-    T = cfg.TEST
-    n = T.get("PHOTO_ITER", 0) or 0
-    if isinstance(n, bool) or not float(n).is_integer() or int(n) < 0:
-        raise ValueError("TEST.PHOTO_ITER must be an integer >= 0 (iterations per level, 0 = off), got {!r}".format(n))
-    levels = T.get("PHOTO_LEVELS", 3)
-    if isinstance(levels, bool) or not float(levels).is_integer() or not 1 <= int(levels) <= 5:
-        raise ValueError("TEST.PHOTO_LEVELS must be an integer in 1..5, got {!r}".format(levels))
-    huber, gate = float(T.get("PHOTO_HUBER", 30.0)), float(T.get("PHOTO_MAX", 180.0))
-    if not (np.isfinite(huber) and huber > 0):
-        raise ValueError("TEST.PHOTO_HUBER must be a finite number > 0 (units of the channel sum), got {!r}".format(T.get("PHOTO_HUBER")))
-    if not (np.isfinite(gate) and gate >= huber):
-        raise ValueError("TEST.PHOTO_MAX must be finite and >= TEST.PHOTO_HUBER, got {!r}".format(T.get("PHOTO_MAX")))
-    gain = T.get("PHOTO_GAIN", True)
-    if not isinstance(gain, (bool, np.bool_)):
-        raise ValueError("TEST.PHOTO_GAIN must be True or False, got {!r}".format(gain))
-    if int(n) > 0:
-        if int(T.get("HYP_NUM", 1) or 1) > 1:
-            raise ValueError("TEST.PHOTO_ITER > 0 cannot be combined with TEST.HYP_NUM > 1")
-        if int(T.get("COARSE_VIEWS", 0) or 0) > 0:
-            raise ValueError("TEST.PHOTO_ITER > 0 cannot be combined with TEST.COARSE_VIEWS > 0")
-    return int(n), int(levels), huber, gate, bool(gain)
-
-
-def sil_settings(cfg):
-    """-> (SIL_ITER, SIL_ROUNDS, SIL_HUBER_PX, SIL_MAX_PX, SIL_MASK) of cfg.TEST, checked; ValueError names the bad key(s).
-    SIL_ITER counts Gauss-Newton iterations per round (0 = off); the two thresholds are in pixels, and the edge field reaches
-    ceil(SIL_MAX_PX) <= 64 pixels.  Selecting among polished hypotheses is not defined, so the stage is refused together with
-    HYP_NUM > 1 and COARSE_VIEWS > 0; SIL_MASK 'pred' needs the mask head's output, which only the full graph computes."""
-    T = cfg.TEST
-    n = T.get("SIL_ITER", 0) or 0
-    if isinstance(n, bool) or not float(n).is_integer() or int(n) < 0:
-        raise ValueError("TEST.SIL_ITER must be an integer >= 0 (iterations per round, 0 = off), got {!r}".format(n))
-    rounds = T.get("SIL_ROUNDS", 2)
-    if isinstance(rounds, bool) or not float(rounds).is_integer() or not 1 <= int(rounds) <= 8:
-        raise ValueError("TEST.SIL_ROUNDS must be an integer in 1..8, got {!r}".format(rounds))
-    huber, gate = float(T.get("SIL_HUBER_PX", 2.0)), float(T.get("SIL_MAX_PX", 12.0))
-    if not (np.isfinite(huber) and huber > 0):
-        raise ValueError("TEST.SIL_HUBER_PX must be a finite number > 0 (pixels), got {!r}".format(T.get("SIL_HUBER_PX")))
-    if not (np.isfinite(gate) and huber <= gate <= 64):
-        raise ValueError("TEST.SIL_MAX_PX must be finite, >= TEST.SIL_HUBER_PX and <= 64 (pixels), got {!r}".format(T.get("SIL_MAX_PX")))
-    which = T.get("SIL_MASK", "observed")
-    if which not in ("observed", "pred"):
-        raise ValueError("TEST.SIL_MASK must be 'observed' or 'pred', got {!r}".format(which))
-    if int(n) > 0:
-        if int(T.get("HYP_NUM", 1) or 1) > 1:
-            raise ValueError("TEST.SIL_ITER > 0 cannot be combined with TEST.HYP_NUM > 1")
-        if int(T.get("COARSE_VIEWS", 0) or 0) > 0:
-            raise ValueError("TEST.SIL_ITER > 0 cannot be combined with TEST.COARSE_VIEWS > 0")
-        if which == "pred" and not (cfg.network.PRED_MASK and not T.FAST_TEST):
-            raise ValueError("TEST.SIL_ITER > 0 with TEST.SIL_MASK 'pred' needs the mask head of the full graph "
-                             "(network.PRED_MASK, TEST.FAST_TEST off)")
-    return int(n), int(rounds), huber, gate, str(which)
 
 
 def hypothesis_rotations(N, rot_deg):
@@ -175,11 +101,11 @@ def refuse_at_source_size(cfg, size, lit=False):
     'box_rendered' / 'init', per-pair K, graph capture, the INPUT_DEPTH graphs), TEST.DEVICE_EVAL and TEST.BOP without BOP_VSD."""
     if tuple(size) == (FlowNetHip.H, FlowNetHip.W):
         return
-    T = cfg.TEST
-    on = [("TEST.ICP_ITER", int(T.get("ICP_ITER", 0) or 0) > 0), ("TEST.HYP_NUM", int(T.get("HYP_NUM", 1) or 1) > 1),
+    T, stages = cfg.TEST, stages_on(cfg)
+    on = [("TEST.ICP_ITER", "icp" in stages), ("TEST.HYP_NUM", int(T.get("HYP_NUM", 1) or 1) > 1),
           ("TEST.COARSE_VIEWS", int(T.get("COARSE_VIEWS", 0) or 0) > 0), ("TEST.VSD", bool(T.get("VSD", False))),
-          ("TEST.BOP_VSD", bool(T.get("BOP_VSD", False))), ("TEST.FLOW_PNP_ITER", int(T.get("FLOW_PNP_ITER", 0) or 0) > 0),
-          ("TEST.PHOTO_ITER", int(T.get("PHOTO_ITER", 0) or 0) > 0), ("TEST.SIL_ITER", int(T.get("SIL_ITER", 0) or 0) > 0),
+          ("TEST.BOP_VSD", bool(T.get("BOP_VSD", False))), ("TEST.FLOW_PNP_ITER", "flow_pnp" in stages),
+          ("TEST.PHOTO_ITER", "photo" in stages), ("TEST.SIL_ITER", "sil" in stages),
           ("network.PRED_FLOW without TEST.FAST_TEST (the test-time flow error)", bool(cfg.network.PRED_FLOW and not T.FAST_TEST)),
           ("the lit ModelNet renderer", bool(lit))]
     for key, active in on:
@@ -221,13 +147,8 @@ class Refiner(object):
         filter_cfg = zoom_filter(cfg)   # (refuses 'area' in the full graph)
         refuse_at_source_size(cfg, (H, W), lit=hasattr(render_machine, "normals"))
         self.hyp_num, self.hyp_rot_deg, self.hyp_score_mode, self.hyp_tau = hyp_settings(cfg)
-        self.flow_pnp_iter, self.flow_pnp_warm, self.flow_pnp_huber, self.flow_pnp_gate = flow_pnp_settings(cfg)
-        self.photo_iter, self.photo_levels, self.photo_huber, self.photo_gate, self.photo_gain = photo_settings(cfg)
-        if self.photo_iter > 0 and hasattr(render_machine, "normals"):
-            raise ValueError("TEST.PHOTO_ITER > 0 is not supported with the lit ModelNet renderer")
-        self.sil_iter, self.sil_rounds, self.sil_huber, self.sil_gate, self.sil_mask = sil_settings(cfg)
-        if self.sil_iter > 0 and hasattr(render_machine, "normals"):
-            raise ValueError("TEST.SIL_ITER > 0 is not supported with the lit ModelNet renderer")
+        settings = stage_settings(cfg, lit=hasattr(render_machine, "normals"))   # every key checked, whether its stage is on or not
+        self.icp_iter, self.photo_iter, self.sil_iter, self.flow_pnp_iter = (settings[k][0] for k in ("icp", "photo", "sil", "flow_pnp"))
         N = self.hyp_num
         if N > 1 and predictor.net.B != batch_size * N:
             raise ValueError("Refiner: {} pairs x TEST.HYP_NUM {} = {} samples, but the Predictor was built for {} samples".format(
@@ -290,64 +211,19 @@ class Refiner(object):
             self.flow_est_iter = torch.zeros((self.test_iter, B, 2, H, W), dtype=torch.float32, device=d)
         self.T_means = np.asarray(cfg.dataset.trans_means, dtype=np.float32)
         self.T_stds = np.asarray(cfg.dataset.trans_stds, dtype=np.float32)
-        # depth ICP after the loop (TEST.ICP_ITER > 0): the depth rendered at the last pose, its box, and the polished pose per pair
-        self.icp_iter = int(cfg.TEST.get("ICP_ITER", 0) or 0)
-        self.icp_max_dist = float(cfg.TEST.get("ICP_MAX_DIST", 0.02))
-        self.depth_observed = self.pose_icp = self.icp_stats = self.status_icp = None
-        hyp_depth = N > 1 and self.hyp_score_mode == "depth"
-        if self.icp_iter > 0 or hyp_depth:
+        self.depth_observed = None   # read by the ICP stage and the depth hypothesis score (an INPUT_DEPTH graph holds it as a blob)
+        if self.icp_iter > 0 or (N > 1 and self.hyp_score_mode == "depth"):
             self.depth_observed = self.batch["depth_observed"] if self.input_depth else torch.zeros((B, 1, H, W), dtype=torch.float32, device=d)
-        if self.icp_iter > 0:
-            self.depth_icp = torch.zeros((B, 1, H, W), dtype=torch.float32, device=d)
-            self.bbox_icp = torch.zeros((B, 4), dtype=torch.int32, device=d)
-            self.pose_icp = torch.zeros((B, 3, 4), dtype=torch.float32, device=d)
-            self.icp_stats = torch.zeros((B, self.icp_iter, 2), dtype=torch.float32, device=d)
-            self.status_icp = torch.zeros((B,), dtype=torch.int32, device=d)
-            self.icp_work = ops.icp_workspace(B, H, W, d)
-        # photometric polish after the loop (TEST.PHOTO_ITER > 0): the render at the last pose (image, depth, box) and the polished
-        # pose per pair; nothing is allocated when the stage is off
-        self.pose_photo = self.photo_stats = self.status_photo = None
-        if self.photo_iter > 0:
-            self.image_photo = torch.zeros((B, 3, H, W), dtype=torch.float32, device=d)
-            self.depth_photo = torch.zeros((B, 1, H, W), dtype=torch.float32, device=d)
-            self.bbox_photo = torch.zeros((B, 4), dtype=torch.int32, device=d)
-            self.pose_photo = torch.zeros((B, 3, 4), dtype=torch.float32, device=d)
-            self.photo_stats = torch.zeros((B, self.photo_levels * self.photo_iter, 2), dtype=torch.float32, device=d)
-            self.status_photo = torch.zeros((B,), dtype=torch.int32, device=d)
-            self.photo_work = ops.photo_workspace(B, H, W, self.photo_levels, d)
-        # silhouette polish after the loop (TEST.SIL_ITER > 0): the edge field of the stage's mask, the depth and box rendered at every
-        # round's pose, the pose after every round (the last one is pose_sil); nothing is allocated when the stage is off
-        self.pose_sil = self.sil_stats = self.status_sil = None
-        if self.sil_iter > 0:
-            if self.sil_mask == "pred" and self.mask_pred_iter is None:
-                raise ValueError("TEST.SIL_ITER > 0 with TEST.SIL_MASK 'pred': the network has no mask head (network.PRED_MASK with a "
-                                 "decoder, TEST.FAST_TEST off)")
-            if self.sil_mask == "observed":   # a private copy: the loop rewrites its own mask_observed (UPDATE_MASK 'box_rendered')
-                self.mask_sil = torch.zeros((B, 1, H, W), dtype=torch.float32, device=d)
-            self.sil_radius = int(np.ceil(self.sil_gate))
-            self.field_sil = torch.zeros((B, H, W), dtype=torch.int32, device=d)
-            self.depth_sil = torch.zeros((B, 1, H, W), dtype=torch.float32, device=d)
-            self.bbox_sil = torch.zeros((B, 4), dtype=torch.int32, device=d)
-            self.pose_sil_round = torch.zeros((self.sil_rounds, B, 3, 4), dtype=torch.float32, device=d)
-            self.pose_sil = self.pose_sil_round[self.sil_rounds - 1]
-            self.sil_stats_round = torch.zeros((B, self.sil_iter, 2), dtype=torch.float32, device=d)
-            self.sil_stats = torch.zeros((B, self.sil_rounds * self.sil_iter, 2), dtype=torch.float32, device=d)
-            self.status_sil = torch.zeros((B,), dtype=torch.int32, device=d)
-            self.sil_work = ops.sil_workspace(B, H, W, d)
-        # pose from the flow head's output at every iteration (TEST.FLOW_PNP_ITER > 0): the depth of the render each forward looked
-        # at (INPUT_DEPTH graphs hold it already), the box of the initial render, and the per-iteration outputs
-        self.pose_flow_iter = self.se3_flow_iter = self.flow_pnp_stats = self.status_flow = None
-        if self.flow_pnp_iter > 0:
-            if self.flow_est_iter is None:
-                raise ValueError("TEST.FLOW_PNP_ITER > 0: the network has no flow head (network.PRED_FLOW with a decoder)")
-            if not self.input_depth:
-                self.depth_flow = torch.zeros((B, 1, H, W), dtype=torch.float32, device=d)
-                self.bbox_flow = torch.zeros((B, 4), dtype=torch.int32, device=d)
-            self.pose_flow_iter = torch.zeros((self.test_iter, B, 3, 4), dtype=torch.float32, device=d)
-            self.se3_flow_iter = torch.zeros((self.test_iter, B, 7), dtype=torch.float32, device=d)
-            self.flow_pnp_stats = torch.zeros((self.test_iter, B, self.flow_pnp_iter, 2), dtype=torch.float32, device=d)
-            self.status_flow = torch.zeros((self.test_iter, B), dtype=torch.int32, device=d)
-            self.flow_work = ops.flow_pnp_workspace(B, H, W, d)
+        # the pose stages that are on, each with its own buffers, and their outputs under the Refiner's public names: None when off
+        self.stages = {name: cls(self, H, W, settings[name]) for name, cls in STAGES if settings[name][0] > 0}
+        icp, photo, sil, flow = (self.stages.get(k) for k in ("icp", "photo", "sil", "flow_pnp"))
+        self.pose_icp, self.icp_stats, self.status_icp = (icp.pose, icp.stats, icp.status) if icp else (None, None, None)
+        self.pose_photo, self.photo_stats, self.status_photo = (photo.pose, photo.stats, photo.status) if photo else (None, None, None)
+        self.pose_sil, self.sil_stats, self.status_sil = (sil.pose, sil.stats, sil.status) if sil else (None, None, None)
+        self.pose_flow_iter, self.se3_flow_iter, self.flow_pnp_stats, self.status_flow = (
+            flow.pose_iter, flow.se3_iter, flow.stats, flow.status) if flow else (None, None, None, None)
+        if sil and sil.mask is not None:   # SIL_MASK 'observed': load() fills it
+            self.mask_sil = sil.mask
         # several hypotheses per pair (TEST.HYP_NUM > 1): the loaded pairs land in `pair` (P rows) and are expanded into the B = P*N
         # sample rows by load(); after the loop: the render at the last pose, the scores, the choice and the selected outputs
         self.pair = self.hyp_score = self.hyp_choice = self.poses_sel = self.status_sel = self.pose_icp_sel = None
@@ -408,7 +284,7 @@ class Refiner(object):
         if det_boxes is not None:
             raise ValueError("det_boxes needs TEST.COARSE_VIEWS > 0")
         self._check_hyp_poses(hyp_poses)
-        if self.sil_iter > 0 and self.sil_mask == "observed":
+        if "sil" in self.stages and self.stages["sil"].which == "observed":
             # taken from the caller's segmentation itself, before any INIT_MASK kind replaces the loop's mask by a box
             if mask_observed is None:
                 raise ValueError("TEST.SIL_ITER > 0 with TEST.SIL_MASK 'observed': load() needs mask_observed, the segmentation whose "
@@ -550,7 +426,7 @@ class Refiner(object):
         into the resident blobs by dim_test_blobs_from_raw / dim_box_mask on the current stream -- no host blobs, no extra copies"""
         if self.coarse is not None:
             raise ValueError("TEST.COARSE_VIEWS > 0: the staged batches carry no detection boxes, use load(..., det_boxes=)")
-        if self.sil_iter > 0 and self.sil_mask == "observed":
+        if "sil" in self.stages and self.stages["sil"].which == "observed":
             raise ValueError("TEST.SIL_ITER > 0 with TEST.SIL_MASK 'observed': a staged batch carries the TEST.INIT_MASK mask of the loop, "
                              "not a segmentation; use load(..., mask_observed=)")
         dst = self._load_targets()
@@ -590,18 +466,9 @@ class Refiner(object):
                 cur[k] = b[k]
         bbox_ren = bbox_obs = None
         pose = self.pose_init
-        flow_on = self.flow_pnp_iter > 0
-        if flow_on:
-            # the first forward looks at the loaded render, whose depth is not among the blobs: render pose_init once more, depth and
-            # box only (an INPUT_DEPTH graph has the plane; its box is not known, so the first stage scans the whole frame)
-            K_flow = self.K_pair if (self.per_pair_K and not self.lit) else None
-            ops.fill(self.status_flow, 0)
-            if not self.input_depth:
-                extra = {"light_intensity": self.light_int[0]} if self.lit else {}
-                if K_flow is not None:
-                    extra["K"] = K_flow
-                self.render_machine.render_batch(b["class_index"], pose, depth=self.depth_flow, bbox=self.bbox_flow, mask_thr=0.0,
-                                                 status=self.status_flow[0], **extra)
+        flow = self.stages.get("flow_pnp")
+        if flow is not None:
+            flow.start(self, pose)
         for it in range(self.test_iter):
             # se3 and status land directly in their per-iteration rows; the pose of the previous iteration is read where it lies
             out = net.forward_test(cur, bbox_ren=bbox_ren, bbox_obs=bbox_obs, src_pose=pose, se3_out=self.se3_iter[it],
@@ -612,15 +479,8 @@ class Refiner(object):
                 ops.copy(self.mask_pred_iter[it], out["mask_observed_pred_output"])
             if self.flow_est_iter is not None:
                 ops.copy(self.flow_est_iter[it], out["flow_est_crop_output"])
-            if flow_on:
-                # flow2se3 on what this forward saw: the render's depth and box, the flow it predicted, mask_observed as it read it.
-                # The result is recorded only: the next iteration starts from the head's pose
-                ops.flow_pnp(cur["depth_rendered"] if self.input_depth else self.depth_flow, self.flow_est_iter[it], pose,
-                             self.render_machine.K, self.flow_pnp_iter, self.flow_pnp_warm, self.flow_pnp_huber, self.flow_pnp_gate,
-                             standard_rep=bool(cfg.network.STANDARD_FLOW_REP), valid=cur["mask_observed"],
-                             bbox=bbox_ren if it > 0 else (None if self.input_depth else self.bbox_flow), K_per_sample=K_flow,
-                             pose_out=self.pose_flow_iter[it], se3_q=self.se3_flow_iter[it], stats=self.flow_pnp_stats[it],
-                             status=self.status_flow[it], workspace=self.flow_work)
+            if flow is not None:   # the result is recorded only: the next iteration starts from the head's pose
+                flow.step(self, it, cur, pose, bbox_ren)
             # pose_rendered_update = RT_transform(pose_rendered, se3[:-3], se3[-3:], ...)   (:525-532)
             ops.se3_compose(pose, self.se3_iter[it], cfg.network.ROT_COORD, self.T_means, self.T_stds, out=self.poses_iter[it])
             if it < self.test_iter - 1:
@@ -632,8 +492,8 @@ class Refiner(object):
                 # and the depth plane is not materialised -- 1.2 MB per pair and render less to write)
                 if self.input_depth:
                     extra["depth"] = b["depth_rendered"]   # INPUT_DEPTH: the rendered depth is a network input (tester.py:573-574)
-                elif flow_on:
-                    extra["depth"] = self.depth_flow       # the next iteration's flow stage back-projects it
+                elif flow is not None:
+                    extra["depth"] = flow.depth            # the next iteration's flow stage back-projects it
                 # from the second render on the planes hold the previous render: background outside ITS box, which is not written again
                 bb_new, bb_prev = (self.bbox, self.bbox2) if it % 2 == 0 else (self.bbox2, self.bbox)
                 self.render_machine.render_batch(b["class_index"], self.poses_iter[it], image=b["image_rendered"],
@@ -650,12 +510,8 @@ class Refiner(object):
                 pose = self.poses_iter[it]
                 bbox_ren = bb_new
         ops.copy(b["src_pose"], pose)  # the blob ends up as the reference leaves it: the pose the last forward used
-        if self.icp_iter > 0:
-            self._icp(self.poses_iter[self.test_iter - 1])
-        if self.photo_iter > 0:   # independent of the ICP: both start from the loop's last pose
-            self._photo(self.poses_iter[self.test_iter - 1])
-        if self.sil_iter > 0:     # likewise independent of the other two
-            self._sil(self.poses_iter[self.test_iter - 1])
+        for name in [n for n in POST_LOOP if n in self.stages]:   # independent of each other, all from the loop's last pose
+            self.stages[name].run(self, self.poses_iter[self.test_iter - 1])
         if self.N > 1:
             self._select(self.poses_iter[self.test_iter - 1])
 
@@ -673,65 +529,19 @@ class Refiner(object):
         ops.hyp_select(self.hyp_score, self.N, self.poses_iter, status_iter=self.status_iter, status_load=self.status_hyp, pose_icp=self.pose_icp,
                        choice=self.hyp_choice, poses_sel=self.poses_sel, status_sel=self.status_sel, pose_icp_sel=self.pose_icp_sel)
 
-    def _icp(self, pose):
-        """depth ICP from the loop's last pose: render its depth and box (the pair's K when loaded), then dim_icp_refine against
-        depth_observed -> pose_icp, icp_stats (B,ICP_ITER,2), status_icp (render bits and DIM_STATUS_ICP_FEW_POINTS)"""
-        b = self.batch
-        ops.fill(self.status_icp, 0)
-        extra = {"light_intensity": self.light_int[0]} if self.lit else {}
-        K_pair = self.K_pair if (self.per_pair_K and not self.lit) else None
-        if K_pair is not None:
-            extra["K"] = K_pair
-        self.render_machine.render_batch(b["class_index"], pose, depth=self.depth_icp, bbox=self.bbox_icp, mask_thr=0.0,
-                                         status=self.status_icp, **extra)
-        ops.icp_refine(self.depth_icp, self.depth_observed, pose, self.render_machine.K, self.icp_iter, self.icp_max_dist, bbox=self.bbox_icp,
-                       K_per_sample=K_pair, pose_out=self.pose_icp, stats=self.icp_stats, status=self.status_icp, workspace=self.icp_work)
-
-    def _photo(self, pose):
-        """photometric polish from the loop's last pose: render its image, depth and box (the pair's K when loaded), then
-        dim_photo_refine against image_observed -> pose_photo, photo_stats (B,PHOTO_LEVELS*PHOTO_ITER,2), status_photo (render bits
-        and DIM_STATUS_PHOTO_FEW_POINTS)"""
-        b = self.batch
-        ops.fill(self.status_photo, 0)
-        K_pair = self.K_pair if self.per_pair_K else None
-        extra = {"K": K_pair} if K_pair is not None else {}
-        self.render_machine.render_batch(b["class_index"], pose, image=self.image_photo, depth=self.depth_photo, bbox=self.bbox_photo,
-                                         plane_means=self.net.plane_means, mask_thr=0.0, status=self.status_photo, **extra)
-        ops.photo_refine(b["image_observed"], self.image_photo, self.depth_photo, pose, self.render_machine.K, self.photo_levels,
-                         self.photo_iter, self.photo_huber, self.photo_gate, gain=self.photo_gain, bbox=self.bbox_photo, K_per_sample=K_pair,
-                         pose_out=self.pose_photo, stats=self.photo_stats, status=self.status_photo, workspace=self.photo_work)
-
-    def _sil(self, pose):
-        """silhouette polish from the loop's last pose: the edge field of the stage's mask once (radius ceil(SIL_MAX_PX)), then
-        SIL_ROUNDS rounds, each rendering depth and box at the current pose (the pair's K when loaded) and running dim_sil_refine
-        from it -> pose_sil, sil_stats (B,SIL_ROUNDS*SIL_ITER,2), status_sil (render bits and DIM_STATUS_SIL_FEW_POINTS)"""
-        b = self.batch
-        ops.fill(self.status_sil, 0)
-        K_pair = self.K_pair if self.per_pair_K else None
-        extra = {"K": K_pair} if K_pair is not None else {}
-        mask = self.mask_sil if self.sil_mask == "observed" else self.mask_pred_iter[self.test_iter - 1]
-        ops.sil_edge_field(mask, self.sil_radius, field=self.field_sil)
-        n = 2 * self.sil_iter   # floats per pair and round
-        flat = self.sil_stats.view(-1)
-        for r in range(self.sil_rounds):
-            self.render_machine.render_batch(b["class_index"], pose, depth=self.depth_sil, bbox=self.bbox_sil, mask_thr=0.0,
-                                             status=self.status_sil, **extra)
-            ops.sil_refine(self.depth_sil, self.field_sil, pose, self.render_machine.K, self.sil_iter, self.sil_huber, self.sil_gate,
-                           bbox=self.bbox_sil, K_per_sample=K_pair, pose_out=self.pose_sil_round[r], stats=self.sil_stats_round,
-                           status=self.status_sil, workspace=self.sil_work)
-            ops.copy_rows(flat[r * n:], self.sil_rounds * n, self.sil_stats_round, n, self.B, n)
-            pose = self.pose_sil_round[r]
+    def _render_at(self, pose, status, **targets):
+        """a stage's render of `pose` into `targets` (image / depth / bbox ..., every drawn pixel) -> the per-pair K it used, or None"""
+        extra = {"light_intensity": self.light_int[0]} if self.lit else ({"K": self.K_pair} if self.per_pair_K else {})
+        self.render_machine.render_batch(self.batch["class_index"], pose, mask_thr=0.0, status=status, **dict(targets, **extra))
+        return extra.get("K")
 
     def refine(self):
-        """run test_iter iterations on the loaded batch; returns poses_iter (test_iter,B,3,4) (device).  With TEST.ICP_ITER > 0 the
-        ICP stage runs after them (inside the same graph) and leaves its pose in pose_icp (B,3,4); with TEST.PHOTO_ITER > 0 the
-        photometric polish does the same from the same last pose and leaves pose_photo (B,3,4), and with TEST.SIL_ITER > 0 the
-        silhouette polish leaves pose_sil (B,3,4).  With TEST.FLOW_PNP_ITER > 0 every
-        iteration also solves the pose from its flow head's output (dim_flow_pnp, inside the same graph): pose_flow_iter
-        (test_iter,B,3,4), se3_flow_iter (test_iter,B,7), flow_pnp_stats (test_iter,B,FLOW_PNP_ITER,2), status_flow (test_iter,B);
-        the loop itself never reads them.  With TEST.HYP_NUM > 1 it returns
-        the selected hypothesis of each pair, poses_sel (test_iter,P,3,4); poses_iter (all P*N samples), hyp_score (P*N,),
-        hyp_choice (P,), status_sel (test_iter,P) and pose_icp_sel (P,3,4) stay readable on the Refiner."""
+        """run test_iter iterations on the loaded batch; returns poses_iter (test_iter,B,3,4) (device).  The stages of
+        deepim.core.pose_stages that are on run inside the same graph: ICP, photometric and silhouette polish after the iterations, each
+        from the same last pose, leave pose_icp / pose_photo / pose_sil (B,3,4); pose from flow at every iteration (dim_flow_pnp) leaves
+        pose_flow_iter (test_iter,B,3,4), se3_flow_iter (test_iter,B,7), flow_pnp_stats (test_iter,B,FLOW_PNP_ITER,2) and status_flow
+        (test_iter,B), which the loop itself never reads.  With TEST.HYP_NUM > 1 it returns the selected hypothesis of each pair, poses_sel
+        (test_iter,P,3,4); poses_iter (P*N samples), hyp_score (P*N,), hyp_choice (P,), status_sel and pose_icp_sel stay readable."""
         if self.graph is not None and self._graph_per_pair_K != self.per_pair_K:
             self.graph = None   # captured with the other render (uniform / per-pair K): capture this one
         if self._want_graph and self.graph is None:
@@ -1022,15 +832,14 @@ def _eval_setup(config, refiner, evaluator, logger):
     bop_vsd = bop_vsd_settings(config)[0]   # before anything is allocated: BOP_VSD without BOP raises here
     T = config.TEST
     st = SimpleNamespace(config=config, evaluator=evaluator, logger=logger, n_cls=len(evaluator.classes), n_it=int(T.test_iter),
-                         with_icp=int(T.get("ICP_ITER", 0) or 0) > 0, n_hyp=int(getattr(refiner, "N", 1)),
-                         device_eval=bool(T.get("DEVICE_EVAL", False)), with_flow=int(T.get("FLOW_PNP_ITER", 0) or 0) > 0,
+                         on=stages_on(config), n_hyp=int(getattr(refiner, "N", 1)), device_eval=bool(T.get("DEVICE_EVAL", False)),
                          with_coarse=getattr(refiner, "coarse", None) is not None, vsd=None, bop=None,
-                         with_photo=int(T.get("PHOTO_ITER", 0) or 0) > 0, with_sil=int(T.get("SIL_ITER", 0) or 0) > 0,
                          vsd_who="TEST.VSD" if bool(T.get("VSD", False)) else "TEST.BOP_VSD")
-    if st.with_photo and (bool(T.get("VSD", False)) or bool(T.get("BOP", False))):
-        raise ValueError("TEST.PHOTO_ITER > 0 cannot be combined with TEST.VSD or TEST.BOP (the photometric row is not scored there)")
-    if st.with_sil and (bool(T.get("VSD", False)) or bool(T.get("BOP", False))):
-        raise ValueError("TEST.SIL_ITER > 0 cannot be combined with TEST.VSD or TEST.BOP (the silhouette row is not scored there)")
+    st.with_icp, st.with_flow = "icp" in st.on, "flow_pnp" in st.on
+    for s in ONE_ROW_SETS:
+        if s.name in st.on and not s.full and (bool(T.get("VSD", False)) or bool(T.get("BOP", False))):
+            raise ValueError("TEST.{} > 0 cannot be combined with TEST.VSD or TEST.BOP (the {} row is not scored there)".format(
+                STAGE_KEY[s.name], s.word))
     if st.device_eval:
         from lib.dataset.evaluation import SYM_CLASSES
 
@@ -1045,15 +854,11 @@ def _eval_setup(config, refiner, evaluator, logger):
         st.bop = BopScorer(config, refiner, evaluator, rows)
     on = {"rt": True, "err": st.device_eval, "vsd": st.vsd is not None and st.vsd.absolute, "grid": bop_vsd, "bop": st.bop is not None}
     families = [f for f in FAMILY_KEYS if on[f]]
+    error_code = [f for f in families if f in ("rt", "err")]
     sets = [("loop", st.n_it, families)]
-    if st.with_icp:    # its own one-row lists, as the reference's PRECOMPUTED_ICP branch scores them
-        sets.append(("icp", 1, families))
+    sets += [(s.name, 1, families if s.full else error_code) for s in ONE_ROW_SETS if s.name in st.on]
     if st.with_flow:   # pose from flow at every iteration: scored by the error code alone
-        sets.append(("flow_pnp", st.n_it, [f for f in families if f in ("rt", "err")]))
-    if st.with_photo:  # one row, as the ICP pose; by the error code alone
-        sets.append(("photo", 1, [f for f in families if f in ("rt", "err")]))
-    if st.with_sil:    # likewise
-        sets.append(("sil", 1, [f for f in families if f in ("rt", "err")]))
+        sets.append(("flow_pnp", st.n_it, error_code))
     st.store = {(name, f): ScoreLists(FAMILY_KEYS[f], st.n_cls, iters) for name, iters, fams in sets for f in fams}
     st.scored = list(st.store)
     if st.n_hyp > 1:
@@ -1128,14 +933,11 @@ def _read_out_flow(st, refiner, cls_dev, gt_dev):
     return host
 
 
-def _read_out_photo(st, refiner, cls_dev, gt_dev, pose=None):
-    """one more copy per batch with TEST.PHOTO_ITER > 0 (and one with TEST.SIL_ITER > 0, `pose` = pose_sil): the polished poses [and
-    their device errors] -> {pose (1, P, 3, 4), [err (1, P, 5)]}"""
-    pose = refiner.pose_photo if pose is None else pose
+def _read_out_pose(st, pose, cls_dev, gt_dev):
+    """one more copy per batch for a one-row pose set outside _read_out's rows: (P,3,4) [and its device errors] -> {pose (1,P,3,4), [err (1,P,5)]}"""
     columns = [("pose", 12, pose.to(torch.float64)[None])]
     if st.device_eval:
-        t = st.tables
-        columns.append(("err", 5, ops.pose_errors(t[0], t[1], t[2], cls_dev, pose, gt_dev, st.K_eval).reshape(1, -1, 5)))
+        columns.append(("err", 5, ops.pose_errors(*st.tables[:3], cls_dev, pose, gt_dev, st.K_eval).reshape(1, -1, 5)))
     host = _to_host(columns)
     host["pose"] = host["pose"].reshape(1, -1, 3, 4)
     return host
@@ -1198,10 +1000,9 @@ def _collect_batch(st, refiner, batch):
     by_set = {"loop": {k: v[:n_it] for k, v in host.items()}, "icp": {k: v[n_it:] for k, v in host.items()}}
     if st.with_flow:
         by_set["flow_pnp"] = _read_out_flow(st, refiner, cls_dev, gt_dev)
-    if st.with_photo:
-        by_set["photo"] = _read_out_photo(st, refiner, cls_dev, gt_dev)
-    if st.with_sil:
-        by_set["sil"] = _read_out_photo(st, refiner, cls_dev, gt_dev, pose=refiner.pose_sil)
+    for s in ONE_ROW_SETS:
+        if s.name in st.on and not s.full:
+            by_set[s.name] = _read_out_pose(st, getattr(refiner, s.pose), cls_dev, gt_dev)
     cls = torch.as_tensor(batch["class_index"]).cpu().numpy().astype(int)
     gt = torch.as_tensor(batch["pose_observed"]).cpu().numpy().astype(np.float64)
     src = torch.as_tensor(batch["src_pose"]).cpu().numpy().astype(np.float64)
@@ -1296,27 +1097,12 @@ def _tables(st, result_file, merge_ranks, merged):
         out["bop"]["bop19"] = out.pop("bop19")
     out["all_rot_err"], out["all_trans_err"] = tables["all_rot_err"], tables["all_trans_err"]
     out["merged_over_ranks"] = merged
-    if st.with_icp:
-        # one row, as the reference's PRECOMPUTED_ICP branch scores it (tester.py:253-330) -- on a copy of the config, since that
-        # branch sets the global config.TEST.test_iter = 1
+    for s in [s for s in ONE_ROW_SETS if s.name in st.on]:
+        # one row, as the reference's PRECOMPUTED_ICP branch scores it (tester.py:253-330), which sets config.TEST.test_iter = 1: a copy
         cfg1 = copy.deepcopy(config)
         cfg1.TEST.test_iter = 1
-        _say(logger, "evaluate ICP ({} iterations, gate {} m):".format(int(config.TEST.ICP_ITER), float(config.TEST.ICP_MAX_DIST)))
-        out["icp"] = dict(_pose_tables(st, cfg1, "icp"), **_scorer_tables(st, "icp"))
-    if st.with_photo:   # one row, scored as the ICP row is
-        cfg1 = copy.deepcopy(config)
-        cfg1.TEST.test_iter = 1
-        _say(logger, "evaluate photometric polish ({} levels x {} iterations, Huber {}, gate {}):".format(
-            int(config.TEST.get("PHOTO_LEVELS", 3)), int(config.TEST.PHOTO_ITER), float(config.TEST.get("PHOTO_HUBER", 30.0)),
-            float(config.TEST.get("PHOTO_MAX", 180.0))))
-        out["photo"] = _pose_tables(st, cfg1, "photo")
-    if st.with_sil:     # one row, scored as the ICP row is
-        cfg1 = copy.deepcopy(config)
-        cfg1.TEST.test_iter = 1
-        _say(logger, "evaluate silhouette polish ({} rounds x {} iterations, Huber {} px, gate {} px, mask {}):".format(
-            int(config.TEST.get("SIL_ROUNDS", 2)), int(config.TEST.SIL_ITER), float(config.TEST.get("SIL_HUBER_PX", 2.0)),
-            float(config.TEST.get("SIL_MAX_PX", 12.0)), config.TEST.get("SIL_MASK", "observed")))
-        out["sil"] = _pose_tables(st, cfg1, "sil")
+        _say(logger, s.headline.format(*[type(default)(config.TEST.get(key, default)) for key, default in s.keys]))
+        out[s.name] = dict(_pose_tables(st, cfg1, s.name), **_scorer_tables(st, s.name))
     if st.with_flow:
         _say(logger, "evaluate pose from flow ({} iterations, {} unweighted, Huber {} px, gate {} px):".format(
             int(config.TEST.FLOW_PNP_ITER), int(config.TEST.FLOW_PNP_WARM), float(config.TEST.FLOW_PNP_HUBER_PX), float(config.TEST.FLOW_PNP_MAX_PX)))

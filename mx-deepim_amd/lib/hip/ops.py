@@ -313,6 +313,20 @@ def _workspace_f64(nbytes, device):
     return torch.empty((max(nbytes, 8) // 8,), dtype=torch.float64, device=device)
 
 
+def _gn_tail(pose_in, K, K_per_sample, bbox, pose_out, stats, status, workspace, nbytes):
+    """what the wrappers of the four Gauss-Newton stages share -> (pose_out, keep, ptr): pose_out and a workspace of the stage's nbytes
+    made when not given; keep: what has to outlive the call; ptr: the shared C arguments by name (None = a null pointer)"""
+    B = pose_in.shape[0]
+    pose_out = pose_out if pose_out is not None else _new((B, 3, 4), pose_in)
+    workspace = workspace if workspace is not None else _workspace_f64(nbytes, pose_in.device)
+    assert workspace.numel() * workspace.element_size() >= nbytes
+    kps = intrinsics_per_sample(K_per_sample, B, pose_in.device)
+    keep, kp = host_f32(K, 9)
+    return pose_out, (keep, kps, workspace), dict(pose_in=dptr(pose_in, f32), K9=kp, kps=_opt(kps), bbox=_opt(bbox, i32),
+                                                  workspace=dptr(workspace, torch.float64), pose_out=dptr(pose_out, f32),
+                                                  stats=_opt(stats), status=_opt(status, i32))
+
+
 STATUS_ICP_FEW_POINTS = 32   # DIM_STATUS_ICP_FEW_POINTS: an ICP iteration found < 64 inliers or a singular system (no update)
 
 
@@ -329,14 +343,10 @@ def icp_refine(depth_rendered, depth_observed, pose_in, K, iters, max_dist, mask
     B, _, H, W = depth_rendered.shape
     assert depth_observed.shape == depth_rendered.shape and tuple(pose_in.shape) == (B, 3, 4)
     assert mask_observed is None or mask_observed.shape == depth_rendered.shape
-    pose_out = pose_out if pose_out is not None else _new((B, 3, 4), pose_in)
-    if workspace is None:
-        workspace = icp_workspace(B, H, W, pose_in.device)
-    kps = intrinsics_per_sample(K_per_sample, B, pose_in.device)
-    keep, kp = host_f32(K, 9)
-    check(lib().dim_icp_refine(dptr(depth_rendered, f32), dptr(depth_observed, f32), _opt(mask_observed), _opt(bbox, i32), dptr(pose_in, f32),
-                               kp, _opt(kps), B, H, W, int(iters), float(max_dist), dptr(workspace, torch.float64), dptr(pose_out, f32),
-                               _opt(stats), _opt(status, i32), current_stream()))
+    pose_out, keep, p = _gn_tail(pose_in, K, K_per_sample, bbox, pose_out, stats, status, workspace, lib().dim_icp_workspace_bytes(B, H, W))
+    check(lib().dim_icp_refine(dptr(depth_rendered, f32), dptr(depth_observed, f32), _opt(mask_observed), p["bbox"], p["pose_in"], p["K9"],
+                               p["kps"], B, H, W, int(iters), float(max_dist), p["workspace"], p["pose_out"], p["stats"], p["status"],
+                               current_stream()))
     return pose_out
 
 
@@ -357,16 +367,11 @@ def flow_pnp(depth_rendered, flow, pose_src, K, iters, warm=2, huber_px=2.0, max
     B, _, H, W = depth_rendered.shape
     assert tuple(flow.shape) == (B, 2, H, W) and tuple(pose_src.shape) == (B, 3, 4)
     assert valid is None or valid.shape == depth_rendered.shape
-    pose_out = pose_out if pose_out is not None else _new((B, 3, 4), pose_src)
     se3_q = se3_q if se3_q is not None else _new((B, 7), pose_src)
-    if workspace is None:
-        workspace = flow_pnp_workspace(B, H, W, pose_src.device)
-    kps = intrinsics_per_sample(K_per_sample, B, pose_src.device)
-    keep, kp = host_f32(K, 9)
-    check(lib().dim_flow_pnp(dptr(depth_rendered, f32), dptr(flow, f32), _opt(valid), _opt(bbox, i32), dptr(pose_src, f32), kp, _opt(kps), B, H,
-                             W, int(bool(standard_rep)), int(iters), int(warm), float(huber_px), float(max_px),
-                             dptr(workspace, torch.float64), dptr(pose_out, f32), dptr(se3_q, f32), _opt(stats), _opt(status, i32),
-                             current_stream()))
+    pose_out, keep, p = _gn_tail(pose_src, K, K_per_sample, bbox, pose_out, stats, status, workspace, lib().dim_flow_pnp_workspace_bytes(B, H, W))
+    check(lib().dim_flow_pnp(dptr(depth_rendered, f32), dptr(flow, f32), _opt(valid), p["bbox"], p["pose_in"], p["K9"], p["kps"], B, H, W,
+                             int(bool(standard_rep)), int(iters), int(warm), float(huber_px), float(max_px), p["workspace"], p["pose_out"],
+                             dptr(se3_q, f32), p["stats"], p["status"], current_stream()))
     return pose_out, se3_q
 
 
@@ -409,16 +414,12 @@ def photo_refine(image_observed, image_rendered, depth_rendered, pose_in, K, lev
     assert tuple(depth_rendered.shape) == (B, 1, H, W) and tuple(pose_in.shape) == (B, 3, 4)
     assert stats is None or stats.numel() >= 2 * B * int(levels) * int(iters)
     assert (status is None or status.numel() == B) and (bbox is None or bbox.numel() == 4 * B)
-    pose_out = pose_out if pose_out is not None else _new((B, 3, 4), pose_in)
-    if workspace is None:
+    if workspace is None:   # (refuses a shape the pyramid cannot hold)
         workspace = photo_workspace(B, H, W, levels, pose_in.device)
-    assert workspace.numel() * workspace.element_size() >= lib().dim_photo_workspace_bytes(B, H, W, int(levels))
-    kps = intrinsics_per_sample(K_per_sample, B, pose_in.device)
-    keep, kp = host_f32(K, 9)
-    check(lib().dim_photo_refine(dptr(image_observed, f32), dptr(image_rendered, f32), dptr(depth_rendered, f32), _opt(bbox, i32),
-                                 dptr(pose_in, f32), kp, _opt(kps), B, H, W, int(levels), int(iters), float(huber), float(gate),
-                                 int(bool(gain)), dptr(workspace, torch.float64), dptr(pose_out, f32), _opt(stats), _opt(status, i32),
-                                 current_stream()))
+    pose_out, keep, p = _gn_tail(pose_in, K, K_per_sample, bbox, pose_out, stats, status, workspace, lib().dim_photo_workspace_bytes(B, H, W, int(levels)))
+    check(lib().dim_photo_refine(dptr(image_observed, f32), dptr(image_rendered, f32), dptr(depth_rendered, f32), p["bbox"], p["pose_in"],
+                                 p["K9"], p["kps"], B, H, W, int(levels), int(iters), float(huber), float(gate), int(bool(gain)),
+                                 p["workspace"], p["pose_out"], p["stats"], p["status"], current_stream()))
     return pose_out
 
 
@@ -450,15 +451,9 @@ def sil_refine(depth_rendered, field, pose_in, K, iters, huber_px, max_px, bbox=
     assert tuple(depth_rendered.shape) == (B, 1, H, W) and tuple(field.shape) == (B, H, W) and tuple(pose_in.shape) == (B, 3, 4)
     assert stats is None or stats.numel() >= 2 * B * int(iters)
     assert (status is None or status.numel() == B) and (bbox is None or bbox.numel() == 4 * B)
-    pose_out = pose_out if pose_out is not None else _new((B, 3, 4), pose_in)
-    if workspace is None:
-        workspace = sil_workspace(B, H, W, pose_in.device)
-    assert workspace.numel() * workspace.element_size() >= lib().dim_sil_workspace_bytes(B, H, W)
-    kps = intrinsics_per_sample(K_per_sample, B, pose_in.device)
-    keep, kp = host_f32(K, 9)
-    check(lib().dim_sil_refine(dptr(depth_rendered, f32), dptr(field, i32), _opt(bbox, i32), dptr(pose_in, f32), kp, _opt(kps), B, H, W,
-                               int(iters), float(huber_px), float(max_px), dptr(workspace, torch.float64), dptr(pose_out, f32),
-                               _opt(stats), _opt(status, i32), current_stream()))
+    pose_out, keep, p = _gn_tail(pose_in, K, K_per_sample, bbox, pose_out, stats, status, workspace, lib().dim_sil_workspace_bytes(B, H, W))
+    check(lib().dim_sil_refine(dptr(depth_rendered, f32), dptr(field, i32), p["bbox"], p["pose_in"], p["K9"], p["kps"], B, H, W, int(iters),
+                               float(huber_px), float(max_px), p["workspace"], p["pose_out"], p["stats"], p["status"], current_stream()))
     return pose_out
 
 

@@ -263,7 +263,8 @@ def _flow_out(ref):
 @pytest.mark.parametrize("graph", [False, True])
 def test_refiner_flow_pnp_leaves_the_loop_alone(loop_setup, graph):
     off = _refiner(loop_setup, 0, graph)
-    assert off.pose_flow_iter is None and not hasattr(off, "depth_flow")
+    assert "flow_pnp" not in off.stages
+    assert off.pose_flow_iter is None and off.se3_flow_iter is None and off.flow_pnp_stats is None and off.status_flow is None
     _load(off, loop_setup)
     off.refine()
     want = _loop_out(off)

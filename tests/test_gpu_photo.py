@@ -300,7 +300,7 @@ def _photo_out(ref):
 @pytest.mark.parametrize("graph", [False, True])
 def test_refiner_photo_leaves_the_loop_alone(loop_setup, graph):
     off = _refiner(loop_setup, 0, graph)
-    assert off.pose_photo is None and off.photo_stats is None and off.status_photo is None and not hasattr(off, "image_photo")
+    assert "photo" not in off.stages and off.pose_photo is None and off.photo_stats is None and off.status_photo is None
     _load(off, loop_setup)
     off.refine()
     want = _loop_out(off)

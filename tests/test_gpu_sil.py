@@ -360,7 +360,7 @@ def _standalone(cfg, rm, mask, last, Kd, rounds=SIL_ROUNDS, iters=SIL_ITER):
 @pytest.mark.parametrize("graph", [False, True])
 def test_refiner_sil_leaves_the_loop_alone(loop_setup, graph):
     off = _refiner(loop_setup, 0, graph)
-    assert off.pose_sil is None and off.sil_stats is None and off.status_sil is None
+    assert "sil" not in off.stages and off.pose_sil is None and off.sil_stats is None and off.status_sil is None
     assert not hasattr(off, "mask_sil") and not hasattr(off, "field_sil") and not hasattr(off, "depth_sil")
     _load(off, loop_setup)
     off.refine()

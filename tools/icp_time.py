@@ -1,4 +1,4 @@
-"""Time of the depth ICP stage after the refinement loop (Refiner._icp): 16 pairs, TEST.ICP_ITER = 10, the depth + bbox render at the
+"""Time of the depth ICP stage after the refinement loop (IcpStage.run): 16 pairs, TEST.ICP_ITER = 10, the depth + bbox render at the
 loop's last pose followed by dim_icp_refine, with device events -- eagerly and replayed from a captured hipGraph -- and the ICP launches
 alone.  Bytes moved are counted from the actual boxes (render: the depth plane written; each iteration: the box of the rendered depth
 read + 5 gathered observed depths per source pixel) against the HBM roof (6.29 TB/s measured copy rate, MI355X_MICROARCH.md).

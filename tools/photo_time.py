@@ -1,4 +1,4 @@
-"""Time of the photometric polish after the refinement loop (Refiner._photo): 16 pairs, the shipped ape test config (FAST_TEST, 4 loop
+"""Time of the photometric polish after the refinement loop (PhotoStage.run): 16 pairs, the shipped ape test config (FAST_TEST, 4 loop
 iterations) and the defaults of the stage (3 levels x 4 iterations, Huber 30, gate 180), with device events, in alternating rounds:
   step_off / step_on   the whole refinement step replayed from its captured hipGraph, without and with the stage (the difference is
                        what the stage costs a step; step_off is the step as it is without this feature, measured in the same run)
@@ -49,16 +49,16 @@ for r in (off, on):
 torch.cuda.synchronize()
 assert torch.equal(off.poses_iter, on.poses_iter)
 pose = on.poses_iter[-1].clone()
+st = on.stages["photo"]
 
 
 def photo():
-    ops.photo_refine(on.batch["image_observed"], on.image_photo, on.depth_photo, pose, rm.K, LEVELS, ITERS, on.photo_huber, on.photo_gate,
-                     gain=on.photo_gain, bbox=on.bbox_photo, pose_out=on.pose_photo, stats=on.photo_stats, status=on.status_photo,
-                     workspace=on.photo_work)
+    ops.photo_refine(on.batch["image_observed"], st.image, st.depth, pose, rm.K, LEVELS, ITERS, st.huber, st.gate, gain=st.gain,
+                     bbox=st.bbox, pose_out=st.pose, stats=st.stats, status=st.status, workspace=st.work)
 
 
 def stage():
-    on._photo(pose)
+    st.run(on, pose)
 
 
 def timed(fn):
@@ -88,9 +88,9 @@ for r in range(ROUNDS):
     for tag, fn in (order if r % 2 == 0 else order[::-1]):
         times[tag].append(timed(fn))
 torch.cuda.synchronize()
-bb = on.bbox_photo.cpu().numpy()
+bb = st.bbox.cpu().numpy()
 box_px = int(sum(max(b[1] - b[0] + 1, 0) * max(b[3] - b[2] + 1, 0) for b in bb))
-tmpl_px = int((on.depth_photo > 0).sum())
+tmpl_px = int((st.depth > 0).sum())
 frame = B * H * W * 4
 bytes_render = 4 * frame
 bytes_pyramid = 7 * frame + 4 * frame + sum(4 * frame // 4 ** (l - 1) + 4 * frame // 4 ** l for l in range(1, LEVELS))
@@ -105,7 +105,7 @@ print(json.dumps({
     "stage_share_of_step": round((med["step_on"] - med["step_off"]) / med["step_off"], 4),
     "stage_eager_us": round(med["stage_eager"], 1), "stage_graph_us": round(med["stage_graph"], 1),
     "photo_only_eager_us": round(med["photo_only"], 1), "photo_launches": LEVELS + 2 + 2 * LEVELS * ITERS,
-    "workspace_bytes": int(on.photo_work.numel() * 8),
+    "workspace_bytes": int(st.work.numel() * 8),
     "bytes_render": bytes_render, "bytes_pyramid": bytes_pyramid, "bytes_stats": bytes_stats, "bytes_iterations": bytes_iters,
     "hbm_roof_us": round((bytes_render + bytes_pyramid + bytes_stats + bytes_iters) / HBM_BPS * 1e6, 2),
     "rounds_us": {k: [round(x, 1) for x in v] for k, v in times.items()}}))

@@ -1,4 +1,4 @@
-"""Time of the silhouette polish after the refinement loop (Refiner._sil): 16 pairs, the shipped ape test config (FAST_TEST, 4 loop
+"""Time of the silhouette polish after the refinement loop (SilStage.run): 16 pairs, the shipped ape test config (FAST_TEST, 4 loop
 iterations) and the stage as cfgs/deepim_hip_LM_ape_test_sil.yaml sets it (2 rounds x 6 iterations, Huber 2 px, gate 12 px), the
 segmentation being the render at the ground-truth pose.  Device events, in alternating rounds:
   step_off / step_on   the whole refinement step replayed from its captured hipGraph, without and with the stage, in the same
@@ -50,19 +50,20 @@ for r in (off, on):
 torch.cuda.synchronize()
 assert torch.equal(off.poses_iter, on.poses_iter)
 pose = on.poses_iter[-1].clone()
+st = on.stages["sil"]
 
 
 def field():
-    ops.sil_edge_field(on.mask_sil, on.sil_radius, field=on.field_sil)
+    ops.sil_edge_field(st.mask, st.radius, field=st.field)
 
 
 def refine():
-    ops.sil_refine(on.depth_sil, on.field_sil, pose, rm.K, ITERS, on.sil_huber, on.sil_gate, bbox=on.bbox_sil, pose_out=on.pose_sil_round[0],
-                   stats=on.sil_stats_round, status=on.status_sil, workspace=on.sil_work)
+    ops.sil_refine(st.depth, st.field, pose, rm.K, ITERS, st.huber, st.gate, bbox=st.bbox, pose_out=st.pose_round[0], stats=st.stats_round,
+                   status=st.status, workspace=st.work)
 
 
 def stage():
-    on._sil(pose)
+    st.run(on, pose)
 
 
 def timed(fn):
@@ -94,11 +95,11 @@ for r in range(ROUNDS):
         times[tag].append(timed(fn))
 on.graph.replay()
 torch.cuda.synchronize()
-bb = on.bbox_sil.cpu().numpy()
+bb = st.bbox.cpu().numpy()
 box_px = int(sum(max(b[1] - b[0] + 1, 0) * max(b[3] - b[2] + 1, 0) for b in bb))
 med = {k: float(np.median(v)) for k, v in times.items()}
 print(json.dumps({
-    "B": B, "rounds_of_the_stage": SIL_ROUNDS, "iters_per_round": ITERS, "radius": on.sil_radius, "steps_per_round": N, "rounds": ROUNDS,
+    "B": B, "rounds_of_the_stage": SIL_ROUNDS, "iters_per_round": ITERS, "radius": st.radius, "steps_per_round": N, "rounds": ROUNDS,
     "status": on.status_sil.cpu().tolist(), "points_first_iter": on.sil_stats[:, 0, 0].cpu().numpy().astype(int).tolist(),
     "points_last_iter": on.sil_stats[:, -1, 0].cpu().numpy().astype(int).tolist(),
     "rms_first_iter": [round(float(x), 3) for x in on.sil_stats[:, 0, 1].cpu()],
@@ -108,5 +109,5 @@ print(json.dumps({
     "stage_share_of_step": round((med["step_on"] - med["step_off"]) / med["step_off"], 4),
     "stage_eager_us": round(med["stage_eager"], 1), "stage_graph_us": round(med["stage_graph"], 1),
     "field_only_eager_us": round(med["field_only"], 1), "refine_only_eager_us": round(med["refine_only"], 1),
-    "launches": 3 + SIL_ROUNDS * (2 * ITERS + 1), "renders": SIL_ROUNDS, "workspace_bytes": int(on.sil_work.numel() * 8),
+    "launches": 3 + SIL_ROUNDS * (2 * ITERS + 1), "renders": SIL_ROUNDS, "workspace_bytes": int(st.work.numel() * 8),
     "rounds_us": {k: [round(x, 1) for x in v] for k, v in times.items()}}))
