@@ -545,6 +545,27 @@ int dim_mask_dilate(const float* mask_in, const int* thickness4, float* mask_out
  * message before anything is enqueued. */
 int dim_augment_observed(const float* in, float* out, int B, int H, int W, const float* pixel_means_bgr3, const int* on,
                          const int* radius_host, const float* taps, const float* chain, const unsigned* seed, int quantize, void* stream);
+/* Contour overlays for test --vis (csrc/vis.hip): the outlines of L layers blended over an observed frame, one pass, a finished 8-bit
+ * frame out.  image: an image_observed blob (B,3,H,W) float32, mean-subtracted, plane c = BGR channel 2 - c, as dim_augment_observed
+ * takes it; pixel_means_bgr3 (host).  layers (L,B,H,W) float32: a pixel is INSIDE layer l where its value is > 0 (a NaN is not inside):
+ * rendered depth and a 0/1 mask both qualify.  style (host, L x 5 ints) = {B, G, R, edge_alpha, fill_alpha} per layer, colours 0..255,
+ * alphas 0..256; it travels as kernel arguments.  out_bgr (B,H,W,3) uint8 in B,G,R order, as an image file holds it.  The rules:
+ *   base colour   per channel v = image + mean (one float32 add), rintf (half to even), clamp to [0, 255]; a NaN gives 0
+ *   edge pixel    of layer l: the pixel is inside, and at least one of its 4-neighbours that lies inside the frame is not inside.
+ *                 Neighbours outside the frame are ignored: an object cut by the frame has no outline along the frame border and a
+ *                 1 x 1 frame has no edge (the contour-point rule of dim_sil_refine)
+ *   marked pixel  of layer l: some edge pixel of l lies in the (2 radius + 1)^2 square centred on the pixel, clipped to the frame
+ *   painting      the layers in the order l = 0 .. L-1, each over the result of the one before it: a marked pixel blends the layer's
+ *                 colour with edge_alpha; a pixel that is inside, not marked and has fill_alpha > 0 blends it with fill_alpha; any
+ *                 other pixel is unchanged
+ *   blend         per channel in integers: c' = (c (256 - a) + colour a + 128) >> 8  (a = 0 returns c, a = 256 the colour)
+ * counts (B,L,2) int32 or NULL: per pair and layer {marked pixels, inside pixels}; what it held before the call does not matter (it is
+ * zeroed on the stream first; integer atomics, exact in any order).  No workspace.  Any W; with W % 4 == 0 and 16-byte aligned image and
+ * layers the kernel moves whole words of four pixels.
+ * L outside 1..8, radius outside 0..3, B outside 1..65535, H or W outside 1..32767, a colour outside 0..255 or an alpha outside 0..256,
+ * a NULL required pointer, or out_bgr overlapping image or layers return DIM_ERR_ARG with a message before anything is enqueued. */
+int dim_vis_overlay(const float* image, const float* pixel_means_bgr3, const float* layers, int L, const int* style, int radius, int B,
+                    int H, int W, unsigned char* out_bgr, int* counts, void* stream);
 /* First-iteration flow labels = calc_flow (lib/pair_matching/flow.py:12-81; float64 per pixel like numpy) + the weights of
  * get_pair_flow (image.py:531-545).  depth_src = rendered depth, depth_tgt = observed depth (B,1,H,W) metres; P12 (B,3,4) float64 (device) =
  * K se3_mul(pose_tgt, se3_inverse(pose_src)) as the reference forms it on the host; Kinv9_f64 = inv(K) in float64 (host pointer).

@@ -121,7 +121,14 @@ def _defaults():
                    # fractions of the class diameter (up to 16), the errors below which a pose counts as correct, and the least
                    # visible fraction of the ground truth at which a pose is a target at all
                    BOP_VSD=False, BOP_VSD_DELTA=0.015, BOP_VSD_TAU=[round(0.05 * k, 2) for k in range(1, 11)],
-                   BOP_VSD_THRESH=[round(0.05 * k, 2) for k in range(1, 11)], BOP_MIN_VISIB_FRACT=0.1)
+                   BOP_VSD_THRESH=[round(0.05 * k, 2) for k in range(1, 11)], BOP_MIN_VISIB_FRACT=0.1,
+                   # with VISUALIZE (test.py --vis): contour overlays of the ground truth, the initial and the refined pose of every
+                   # iteration (deepim/core/visualize.py, dim_vis_overlay): the directory ("" = <output path>/vis), how many of the
+                   # first pairs are drawn (0 = all), the outline's radius (0..3: 2 radius + 1 pixels wide), its alpha (0..256), the
+                   # alpha of a fill under the refined outline (0 = none), and whether the frames zoomed to the object are written too
+                   # (VIS_ZOOM), and whether each pair's frames / zoomed frames are also assembled into a GIF (--vis_video[_zoom])
+                   VIS_DIR="", VIS_MAX_PAIRS=64, VIS_RADIUS=1, VIS_EDGE_ALPHA=256, VIS_FILL_ALPHA=0, VIS_ZOOM=True, VIS_VIDEO=False,
+                   VIS_VIDEO_ZOOM=False)
     c.train_iter = edict(SE3_DIST_LOSS=False, LW_ROT=0.0, LW_TRANS=0.0, TRANS_LOSS_TYPE="L2", TRANS_SMOOTH_L1_SCALAR=3.0,
                          SE3_PM_LOSS=False, LW_PM=0.0, SE3_PM_LOSS_TYPE="L1", SE3_PM_SL1_SCALAR=1.0, NUM_3D_SAMPLE=-1, LW_FLOW=0.0,
                          LW_MASK=0.0,

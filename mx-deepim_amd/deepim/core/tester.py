@@ -807,7 +807,9 @@ def pred_eval(config, refiner, batches, evaluator, result_file=None, logger=None
     With TEST.COARSE_VIEWS > 0 (a Refiner with a coarse stage) every pair starts from its detection box: the batch's "det_bbox" (P,4)
     {x0,x1,y0,y1} continuous pixel extents when it carries one, otherwise the box of its "mask_observed" (dim_mask_bbox, widened by
     half a pixel to each side).  "src_pose", "image_rendered" and "mask_rendered" are not read (the pair's best coarse pose stands for
-    src_pose).  out["coarse"] = {idx, score, status, pose}: per pair the HYP_NUM kept candidates of the coarse stage, best first."""
+    src_pose).  out["coarse"] = {idx, score, status, pose}: per pair the HYP_NUM kept candidates of the coarse stage, best first.
+    With TEST.VISUALIZE every refined batch is also drawn (deepim.core.visualize.PoseVisualizer: contour overlays of the ground truth,
+    the initial and the refined poses under TEST.VIS_DIR); every output is that of the switch off."""
     st = _eval_setup(config, refiner, evaluator, logger)
     for batch in batches:
         _collect_batch(st, refiner, batch)
@@ -869,6 +871,11 @@ def _eval_setup(config, refiner, evaluator, logger):
         st.store["coarse"] = PairLists(COARSE_KEYS)
     # flow error of the first forward (:500-512): only the full test graph emits the flow head's output
     st.epe = FlowEPE(config, getattr(refiner, "P", refiner.B), refiner.net.device) if (config.network.PRED_FLOW and not T.FAST_TEST) else None
+    st.vis = None   # TEST.VISUALIZE: the overlays of every refined batch (deepim/core/visualize.py); off: nothing is imported or allocated
+    if bool(T.get("VISUALIZE", False)):
+        from deepim.core.visualize import PoseVisualizer
+
+        st.vis = PoseVisualizer(config, refiner, evaluator)
     return st
 
 
@@ -994,6 +1001,8 @@ def _collect_batch(st, refiner, batch):
         refiner.load(batch["image_observed"], batch["image_rendered"], batch["mask_observed"], batch["mask_rendered"], batch["src_pose"],
                      batch["class_index"], depth_observed=batch.get("depth_observed"), K=batch.get("K"), **extra)
     poses_dev = refiner.refine()
+    if st.vis is not None:
+        st.vis.draw(batch)
     cls_dev, _, p_icp = _pair_view(refiner, cls=st.device_eval, K=False, icp=st.with_icp)
     gt_dev = torch.as_tensor(batch["pose_observed"]).to(st.dev, torch.float64).contiguous() if st.device_eval else None
     host = _read_out(st, batch, poses_dev, p_icp, cls_dev, gt_dev)

@@ -1,5 +1,5 @@
 """Test entry point with the reference's command line (deepim/test.py:14-44):
-    python deepim/test.py --cfg experiments/deepim/cfgs/<name>.yaml --gpus 0 [--ignore_cache] [--skip_flow]
+    python deepim/test.py --cfg experiments/deepim/cfgs/<name>.yaml --gpus 0 [--ignore_cache] [--skip_flow] [--vis [--vis_video] [--vis_video_zoom]]
 Flow of test_deepim (:58-215): update_config -> logger -> symbol -> load_param(prefix, test_epoch, process=True) -> Predictor ->
 pred_eval (4-iteration refinement, result cache, evaluate_pose / _add / _arp_2d).
 Differences, all forced by the environment: the LINEMOD / ModelNet dataset classes are out of scope and no data is present, so the
@@ -43,8 +43,11 @@ def test_deepim(args):
     from lib.utils.create_logger import create_logger
     from lib.utils.load_model import load_param
 
-    if args.vis or args.vis_video or args.vis_video_zoom:
-        raise NotImplementedError("visualisation is outside the refinement path built here (SURVEY.md 8: out of scope)")
+    vis = bool(args.vis or args.vis_video or args.vis_video_zoom)
+    if vis:   # the overlays of deepim/core/visualize.py; a video is assembled from the frames, so either video flag switches them on
+        config.TEST.VISUALIZE = True
+        config.TEST.VIS_VIDEO = bool(args.vis_video)
+        config.TEST.VIS_VIDEO_ZOOM = bool(args.vis_video_zoom)
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
     gpu_ids = [int(i) for i in args.gpus.split(",")]
     dev_id = gpu_ids[int(os.environ.get("LOCAL_RANK", "0")) % len(gpu_ids)] if world > 1 else gpu_ids[0]
@@ -80,13 +83,21 @@ def test_deepim(args):
     arg_params = sym_instance.init_weights(config, arg_params, {}, seed=0)
 
     B = int(config.TEST.BATCH_PAIRS)
+    if vis and 0 < args.num_pairs < B:
+        B = args.num_pairs   # a handful of pictures: one batch of that many pairs (only whole batches are refined)
     data = SyntheticPairs(config, args.num_pairs, B, device=device, rank=rank, world=world)
     # TEST.HYP_NUM hypotheses per pair are refined side by side: the network runs B pairs x HYP_NUM samples
     predictor = Predictor(config, arg_params, B * int(config.TEST.get("HYP_NUM", 1) or 1), device=device)
     refiner = Refiner(config, predictor, data.render_machine, B, capture_graph=True)
     result_file = os.path.join(final_output_path, "{}_results.pkl".format(image_set))
+    if vis:   # as the reference (tester.py:86, :650): a visualising run neither reads nor writes the result cache
+        result_file = None
+        if not config.TEST.get("VIS_DIR", ""):
+            config.TEST.VIS_DIR = os.path.join(final_output_path, "vis")
     out = pred_eval(config, refiner, data.test_batches(), data.evaluator(), result_file=result_file, logger=logger)
     print("refined {} pairs x {} iterations on {}; result cache: {}".format(data.num_pairs, config.TEST.test_iter, device, result_file))
+    if vis:
+        print("overlays: {}".format(config.TEST.VIS_DIR))
     print(args.cfg, config.TEST.test_epoch)
     if world > 1:
         torch.distributed.destroy_process_group()

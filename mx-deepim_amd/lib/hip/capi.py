@@ -82,6 +82,7 @@ SIGNATURES = {
     "dim_pair_blobs_from_raw": (I, [P, P, P, P, P, P, P, P, P, I, I, I, F, P, F, P, P, P, P, P, P, P, P, P, P, P]),
     "dim_mask_dilate": (I, [P, P, P, I, I, I, P]),
     "dim_augment_observed": (I, [P, P, I, I, I, P, P, P, P, P, P, I, P]),
+    "dim_vis_overlay": (I, [P, P, P, I, P, I, I, I, I, P, P, P]),
     "dim_calc_flow_labels": (I, [P, P, P, P, I, I, I, D, I, I, P, P, P]),
     "dim_point_clouds": (I, [P, P, P, P, I, I, P, P, P, P]),
     "dim_raster_workspace_bytes": (L, [I, I, I, I]),

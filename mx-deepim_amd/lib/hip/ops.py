@@ -915,6 +915,29 @@ def augment_observed(image, on, radius, taps, chain, seed, pixel_means_bgr, quan
     return out
 
 
+VIS_MAX_LAYERS = 8   # dim_vis_overlay: the most layers of one call
+VIS_MAX_RADIUS = 3   # ... and the widest outline (2 radius + 1 pixels)
+
+
+def vis_overlay(image, layers, style, radius, pixel_means_bgr, out=None, counts=None):
+    """dim_vis_overlay (csrc/vis.hip; include/deepim_hip.h lists the rules): the outlines of layers (L,B,H,W) f32 (inside where > 0)
+    painted in order over the image_observed blob image (B,3,H,W) -> out (B,H,W,3) uint8 B,G,R.  style: HOST ints (L,5) = {B, G, R,
+    edge_alpha, fill_alpha}, checked before the launch like radius (0..3).  counts: optional (B,L,2) int32 = {marked, inside} pixels."""
+    B, C, H, W = image.shape
+    sty = np.ascontiguousarray(np.asarray(style, dtype=np.int32))
+    if C != 3 or layers.dim() != 4 or tuple(layers.shape[1:]) != (B, H, W) or sty.shape != (layers.shape[0], 5):
+        raise ValueError("vis_overlay: image (B,3,H,W), layers (L,B,H,W) and style (L,5) expected, got {} {} {}".format(
+            tuple(image.shape), tuple(layers.shape), sty.shape))
+    L = int(layers.shape[0])
+    out = out if out is not None else torch.empty((B, H, W, 3), dtype=torch.uint8, device=image.device)
+    _same_shape(out, (B, H, W, 3), "out")
+    _same_shape(counts, (B, L, 2), "counts")
+    keep, mp = host_f32(pixel_means_bgr, 3)
+    check(lib().dim_vis_overlay(dptr(image, f32), mp, dptr(layers, f32), L, sty.ctypes.data, int(radius), B, H, W, dptr(out, torch.uint8),
+                                dptr(counts, i32), current_stream()))
+    return out
+
+
 FLOW_WEIGHT_ID = {"all": 0, "viz": 1, "valid": 2}
 
 
