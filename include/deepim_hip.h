@@ -902,7 +902,20 @@ int dim_conv2d_wgrad_oihw(const float* x, const float* dz, float* dw_oihw, float
  * bf16-only tiles: 7 = LDS-halo kernel (8 x 16 pixels x 128 channels; 3x3 / 5x5, stride 1 / 2, dense output); 8 = 128 x 256 gathered taps;
  * 9 = stride-1 patch kernel (16 x 16 pixels x 128 or 64 channels, KH, KW <= 3 with 2 .. 9 taps, Cin % 32 == 0, Cout % 64 == 0, dense or
  * scattered output, batched phases); dim_conv2d_dgrad_bf16 with tile 9 applies it to every phase of a strided gradient that has >= 2
- * taps and runs the single-tap phase on the gathered-tap kernel. */
+ * taps and runs the single-tap phase on the gathered-tap kernel.  Tile 9 also has a stride-2 form (8 x 16 pixels x 128 channels, 3x3 or
+ * 5x5, dense output): Cout % 128 == 0 there, so a 64-filter stride-2 request is refused.
+ * What the direct entries refuse (DIM_ERR_ARG before anything is enqueued; outputs and workspace untouched; pinned by
+ * tests/test_gpu_direct_conv_exact.py):
+ *   forward    tiles 1 / 4 with Cout % 128 != 0; tile 4 on the 8-channel layer; tile 6 on anything but the 8-channel 7x7 / stride-2 /
+ *              64-filter layer; tiles 7, 8, 9 on f32 weights; tile 7 with Cout % 128 != 0 or on a 5x5 / stride-1 layer; tile 8 with
+ *              Cout % 256 != 0; tile 9 at stride 1 with KH or KW > 3; a map smaller than the kernel (H + 2 pad < KH or W + 2 pad < KW:
+ *              an empty output)
+ *   dgrad      tile 7 on f32 weights (tile 9 there runs every phase on the gathered-tap kernel); tiles 4 / 7 unless Cin rounded up to 64
+ *              is a multiple of 128; tile 7 at stride 2 (its output is dense); the folded form (dim_conv2d_dgrad_bf16_lrelu) on a layer
+ *              with a single-tap phase (3x3 / stride 2)
+ *   wgrad      accumulate with more than one split (after clamping); accumulate in the bf16 patch form (3x3 / stride 1 / pad 1,
+ *              Cout % 128 == 0, Ho Wo >= 1200)
+ *   deconv     tile 9 on f32 weights */
 /* The input gradient of a layer whose INPUT is another layer's LeakyReLU output, with that LeakyReLU' and the lower layer's bias
  * gradient folded into the epilogue (tile 9, the bf16 patch kernel: 3x3 / stride 1 and 5x5 / stride 2 layers on maps of >= 1200 pixels):
  * dz (N,H,W,Cin) = dX * (y_act > 0 ? 1 : slope), db[Cin] (+)= column sums of dz.  y_act (N,H,W,Cin) is the stored activation; Cin % 64 == 0.

@@ -280,6 +280,10 @@ static int conv2d_fwd_impl(const float* x, const float* w_packed, const float* b
   a.N = N; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.KH = KH; a.KW = KW; a.stride = stride;
   a.pad_h = pad;
   a.pad_w = (ex && ex->pad_w >= 0) ? ex->pad_w : pad;
+  // a map smaller than the kernel has no output: C division rounds (H + 2 pad - KH) / stride towards zero, which would turn -1 / 2 into
+  // one output row that lies outside the caller's (empty) buffer
+  DIM_REQUIRE((ex && ex->Ho > 0) || H + 2 * pad >= KH, "empty output");
+  DIM_REQUIRE((ex && ex->Wo > 0) || W + 2 * a.pad_w >= KW, "empty output");
   a.Ho = (ex && ex->Ho > 0) ? ex->Ho : (H + 2 * pad - KH) / stride + 1;
   a.Wo = (ex && ex->Wo > 0) ? ex->Wo : (W + 2 * a.pad_w - KW) / stride + 1;
   DIM_REQUIRE(a.Ho > 0 && a.Wo > 0, "empty output");
