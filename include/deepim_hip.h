@@ -46,6 +46,8 @@ extern "C" {
 #define DIM_STATUS_COARSE_BAD_BOX 512 /* dim_pose_from_box: a bad box, a class without points, a point behind the camera or a non-finite scale (fallback row) */
 #define DIM_STATUS_PHOTO_FEW_POINTS 1024 /* dim_photo_refine: an iteration had fewer than 64 weighted points or a singular system, or the pair has no usable template (no update) */
 #define DIM_STATUS_SIL_FEW_POINTS 2048 /* dim_sil_refine: an iteration had fewer than 64 weighted contour points or a singular system (no update) */
+#define DIM_STATUS_TRACK_LOST 4096 /* dim_track_update: the track failed the lost test on this frame (the frame's pose was not accepted) */
+#define DIM_STATUS_TRACK_REINIT 8192 /* dim_track_update: ... and was re-initialised from the offered pose */
 
 const char* dim_last_error(void);
 /* library / device probe: fills name (<= n bytes), returns number of compute units or <0 */
@@ -388,6 +390,49 @@ int dim_pose_score_indexed(const float* image_observed, const float* image_rende
                            float tau, void* workspace, float* score, int* status, void* stream);
 int dim_hyp_topk(const float* score, const int* status_in, int reject_mask, int P, int M, int k, const float* poses_in, int* idx_out,
                  float* score_out, float* poses_out, int* status_out, void* stream);
+
+/* ---------------------------------------------------------------- pose tracking through a video (csrc/track.hip)
+ * The temporal layer around the refinement loop: P tracks share one camera, and their state lives on the device, so a frame costs no
+ * host round trip.  Restated in float64 by tests/track_reference.py.  Each entry is one launch.
+ * dim_track_ingest: one camera frame -> the observed blobs of the P tracks.  frame_bgr (H,W,3) uint8, depth_raw (H,W) uint16 or NULL;
+ *   image_observed (P,3,H,W), depth_observed (P,1,H,W) or NULL (it needs depth_raw).  Every pixel has the bits dim_pair_blobs_from_raw
+ *   writes: plane c = bgr[2 - c] - pixel_means_bgr3[2 - c] (HOST array), depth = raw / depth_factor as a true division.  The frame is
+ *   read once and written P times in 16-byte stores.  W % 4 != 0, H <= 0, P <= 0, depth_factor <= 0, a NULL required pointer or a
+ *   misaligned one (frame 4 bytes, raw depth 8, float planes 16) return DIM_ERR_ARG.
+ * dim_track_predict: the pose each track's frame starts from.  hist (P,2,3,4): [1] the last accepted pose, [0] the one before; age (P)
+ *   int32: the valid entries of hist (0, 1 or 2).  DIM_TRACK_MOTION_HOLD, age < 2, a non-finite entry of hist or tz <= 0 in either pose:
+ *   pose_out = hist[1] bit for bit.  DIM_TRACK_MOTION_VELOCITY otherwise, in float64 with one rounding at the end:
+ *     R_pred = exp(alpha log(R_last R_prev^T)) R_last;   u = tx / tz, v = ty / tz:  u_pred = u_last + alpha (u_last - u_prev), v likewise;
+ *     z_pred = z_last (z_last / z_prev)^alpha;   t_pred = (u_pred z_pred, v_pred z_pred, z_pred)
+ *   (the untangled translation of the network, T_transform).  The logarithm of D = R_last R_prev^T: s v = half the antisymmetric part
+ *   of D as a vector (|v| = 1), c = (tr D - 1) / 2, angle = atan2(s, c); the axis is v for c >= -0.5 (log = s v itself when s < 1e-8),
+ *   and for c < -0.5 it is taken from the symmetric part, (D + D^T) / 2 = c I + (1 - c) a a^T (row of the largest diagonal entry,
+ *   normalised, signed like v): stable at angle 0 and up to pi.  mode outside the two, alpha outside [0, 1], P <= 0 or a NULL pointer
+ *   return DIM_ERR_ARG.
+ * dim_track_update: the state machine after a frame's refinement, per track, in float64, in this order:
+ *   1. step = (angle of R_new R_before^T in degrees, atan2 form as above; |t_new - t_before|), +inf where not finite; pose_before is the
+ *      pose before the loop's last iteration, pose_new the tracked pose (both (P,3,4)).
+ *   2. the step overwrites the oldest entry of ring (P,Wn,2) at ring_pos, ring_n = min(ring_n + 1, Wn); mean (P,2) = the mean of the
+ *      ring_n stored entries, summed oldest first.
+ *   3. lost = (status & fatal_mask) != 0, status the OR of status_rows (n_rows,P) int32 (NULL with n_rows 0); or a non-finite entry of
+ *      pose_new; or t_z outside [znear, zfar]; or score (P, may be NULL) with !(score >= min_score); or ring_n == Wn and (mean_rot >
+ *      lost_rot_deg or mean_trans > lost_trans_m).
+ *   4. not lost: hist[0] = hist[1], hist[1] = pose_new, age = min(age + 1, 2).
+ *   5. lost and reinit_valid[p] != 0: hist[1] = reinit_pose[p], age = 1, ring zeroed with ring_n = ring_pos = 0, flags gain
+ *      DIM_STATUS_TRACK_LOST | DIM_STATUS_TRACK_REINIT.  reinit_pose (P,3,4) / reinit_valid (P) int32 may both be NULL (nothing offered).
+ *   6. lost otherwise: hist and ring unchanged, age = min(age, 1), flags gain DIM_STATUS_TRACK_LOST.
+ *   flags (P) int32 = status plus the new bits; step (P,2) and mean (P,2) float32.  Poses enter hist as bit-for-bit copies.
+ *   Wn outside [1, DIM_TRACK_MAX_WINDOW], P <= 0, n_rows < 0 or a NULL required pointer return DIM_ERR_ARG. */
+#define DIM_TRACK_MOTION_HOLD 0
+#define DIM_TRACK_MOTION_VELOCITY 1
+#define DIM_TRACK_MAX_WINDOW 64
+int dim_track_ingest(const unsigned char* frame_bgr, const unsigned short* depth_raw, int P, int H, int W, float depth_factor,
+                     const float* pixel_means_bgr3, float* image_observed, float* depth_observed, void* stream);
+int dim_track_predict(const float* hist, const int* age, int P, int mode, float alpha, float* pose_out, void* stream);
+int dim_track_update(const float* pose_before, const float* pose_new, const int* status_rows, int n_rows, int fatal_mask,
+                     const float* score, float min_score, const float* reinit_pose, const int* reinit_valid, float lost_rot_deg,
+                     float lost_trans_m, int Wn, float znear, float zfar, int P, float* hist, int* age, float* ring, int* ring_n,
+                     int* ring_pos, int* flags, float* step, float* mean, void* stream);
 
 /* ---------------------------------------------------------------- pose errors of the evaluation (lib/utils/pose_error.py) on the device
  * For T pose sets of B pairs: errors (T,B,5) float64 = {re (degrees), te, add, adi, arp_2d} of poses_est[t][b] against pose_gt[b]

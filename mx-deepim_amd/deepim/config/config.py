@@ -103,6 +103,16 @@ def _defaults():
                    # HYP_NUM best of every pair start the loop
                    COARSE_VIEWS=0, COARSE_INPLANE=1, COARSE_BOX_ITER=8, COARSE_Z_INIT=1.0, COARSE_SCORE="rgb", COARSE_DEPTH_TAU=0.02,
                    COARSE_CHUNK=256,
+                   # following objects through a video (deepim/core/tracker.py Tracker, deepim/track.py): the motion model that
+                   # predicts a frame's starting pose from the last two accepted ones ("hold" or "velocity") and its damping in
+                   # [0, 1]; the lost test -- the window length in frames (1..64) and the window means of the loop's last step
+                   # (degrees, metres) above which a track counts as lost; an optional score of the tracked pose against the frame
+                   # ("none", "rgb" ZNCC or "depth" inlier fraction with its gate in metres, as HYP_SCORE) and the score below which
+                   # the track is lost; and the pose a track keeps ("loop", "icp" or "photo": the named stage must be on).  The
+                   # three thresholds TRACK_LOST_ROT_DEG, TRACK_LOST_TRANS and TRACK_MIN_SCORE are starting values that nobody has
+                   # tuned on real video
+                   TRACK_MOTION="velocity", TRACK_DAMPING=1.0, TRACK_WINDOW=10, TRACK_LOST_ROT_DEG=10.0, TRACK_LOST_TRANS=0.01,
+                   TRACK_SCORE="none", TRACK_MIN_SCORE=0.5, TRACK_DEPTH_TAU=0.02, TRACK_POSE="loop",
                    # pred_eval: the pose errors (re, te, ADD, ADD-S, arp_2d) from dim_pose_errors on the device instead of
                    # lib/utils/pose_error.py on the host, one pose at a time
                    DEVICE_EVAL=False,

@@ -350,18 +350,21 @@ class Refiner(object):
         if box_init:
             ops.box_mask(self.bbox_hyp, mask_dst)
 
-    def _render_start(self):
+    def _render_start(self, *, bbox=None, status=None):
         """the starting poses (pose_init) rendered as the loop re-renders: init image_rendered / mask_rendered [/ depth_rendered],
-        their boxes in bbox_hyp and the render's status bits in status_hyp"""
+        their boxes in bbox_hyp and the render's status bits in status_hyp (or in the caller's bbox (B,4) / status (B,): the
+        Tracker of deepim/core/tracker.py renders every frame's predicted poses with it)"""
         b, init = self.batch, self.init
+        bbox = self.bbox_hyp if bbox is None else bbox
+        status = self.status_hyp if status is None else status
         extra = {}
         if self.per_pair_K:
             extra["K"] = self.K_pair
         if self.input_depth:
             extra["depth"] = init["depth_rendered"]
-        ops.fill(self.status_hyp, 0)
+        ops.fill(status, 0)
         self.render_machine.render_batch(b["class_index"], self.pose_init, image=init["image_rendered"], mask=init["mask_rendered"],
-                                         bbox=self.bbox_hyp, plane_means=self.net.plane_means, mask_thr=0.2, status=self.status_hyp, **extra)
+                                         bbox=bbox, plane_means=self.net.plane_means, mask_thr=0.2, status=status, **extra)
 
     def _load_K(self, K):
         if K is None:

@@ -1,0 +1,241 @@
+"""Following objects through a video, device resident: the temporal layer around deepim.core.tester.Refiner.
+
+P tracks share one camera.  Per frame one chain runs on one stream, with no host round trip:
+
+    ingest (dim_track_ingest: the frame -> the P observed blobs)  ->  predict (dim_track_predict: the last two accepted poses ->
+    refiner.pose_init)  ->  the start render and its box mask, as Refiner.load renders a starting pose  ->  Refiner._loop()  ->
+    [render + dim_pose_score of the tracked pose against the frame]  ->  update (dim_track_update: step ring, lost test, history,
+    re-initialisation)
+
+and with capture_graph the chain is one hipGraph, captured at the first step and replayed for every later frame.  The state (pose
+history, age, step ring) lives in device tensors the chain reads and writes in place; a step copies the frame (and the offered
+re-initialisation poses) into resident staging tensors and launches the chain.  tests/track_reference.py restates predict and update.
+"""
+from __future__ import print_function, division
+
+import numpy as np
+import torch
+
+from lib.hip import ops
+from deepim.core.pose_stages import int_setting, stages_on
+from deepim.core.tester import Refiner
+from deepim.symbols.deepIM_flownet import source_size
+
+TRACK_MOTIONS = ("hold", "velocity")
+TRACK_SCORES = ("none", "rgb", "depth")
+TRACK_POSES = ("loop", "icp", "photo")
+# status bits that end a track's frame: nothing to zoom on (the object left the image or the render is empty), a class or camera
+# the rasteriser refused.  The stages' own "too few points" bits are not fatal: their pose is then the loop's, unchanged
+FATAL_MASK = 1 | 2 | ops.STATUS_BAD_CLASS | ops.STATUS_BAD_K   # DIM_STATUS_OBS_BOX_EMPTY | DIM_STATUS_REN_BOX_EMPTY | ...
+
+
+def _finite(T, key, what, ok):
+    v = T.get(key)
+    try:
+        f = float(v)
+    except (TypeError, ValueError):
+        f = np.nan
+    if isinstance(v, bool) or not (np.isfinite(f) and ok(f)):
+        raise ValueError("TEST.{} must be {}, got {!r}".format(key, what, v))
+    return f
+
+
+def track_settings(cfg):
+    """-> dict(motion, damping, window, lost_rot_deg, lost_trans, score, min_score, depth_tau, pose) of cfg.TEST.TRACK_*, checked;
+    ValueError names the bad key"""
+    T = cfg.TEST
+    motion = T.get("TRACK_MOTION")
+    if motion not in TRACK_MOTIONS:
+        raise ValueError("TEST.TRACK_MOTION must be one of {}, got {!r}".format(TRACK_MOTIONS, motion))
+    damping = _finite(T, "TRACK_DAMPING", "a number in [0, 1]", lambda f: 0.0 <= f <= 1.0)
+    window = int_setting("TRACK_WINDOW", T.get("TRACK_WINDOW"), 1, ops.TRACK_MAX_WINDOW, "an integer in 1..{}".format(ops.TRACK_MAX_WINDOW))
+    rot = _finite(T, "TRACK_LOST_ROT_DEG", "a finite angle > 0 (degrees)", lambda f: f > 0)
+    trans = _finite(T, "TRACK_LOST_TRANS", "a finite distance > 0 (metres)", lambda f: f > 0)
+    score = T.get("TRACK_SCORE")
+    if score not in TRACK_SCORES:
+        raise ValueError("TEST.TRACK_SCORE must be one of {}, got {!r}".format(TRACK_SCORES, score))
+    min_score = _finite(T, "TRACK_MIN_SCORE", "a finite number", lambda f: True)
+    tau = _finite(T, "TRACK_DEPTH_TAU", "a finite distance > 0 (metres)", lambda f: f > 0)
+    pose = T.get("TRACK_POSE")
+    if pose not in TRACK_POSES:
+        raise ValueError("TEST.TRACK_POSE must be one of {}, got {!r}".format(TRACK_POSES, pose))
+    if pose != "loop" and pose not in stages_on(cfg):
+        raise ValueError("TEST.TRACK_POSE {!r} needs its stage switched on (TEST.{}_ITER > 0)".format(pose, pose.upper()))
+    return dict(motion=motion, damping=damping, window=window, lost_rot_deg=rot, lost_trans=trans, score=score, min_score=min_score,
+                depth_tau=tau, pose=pose)
+
+
+def refuse_for_tracking(cfg, lit=False):
+    """what a Tracker cannot be combined with; every ValueError names its key.  Reads the configuration only: no device work"""
+    T, stages = cfg.TEST, stages_on(cfg)
+    if int(T.get("HYP_NUM", 1) or 1) > 1:
+        raise ValueError("Tracker: TEST.HYP_NUM > 1 is not supported (a track has one pose per frame)")
+    if int(T.get("COARSE_VIEWS", 0) or 0) > 0:
+        raise ValueError("Tracker: TEST.COARSE_VIEWS > 0 is not supported (the starting pose of a frame comes from the track)")
+    if lit:
+        raise ValueError("Tracker: the lit ModelNet renderer is not supported (render machine with normals)")
+    if "sil" in stages:
+        raise ValueError("Tracker: TEST.SIL_ITER > 0 is not supported (a frame carries no segmentation)")
+    if "flow_pnp" in stages:
+        raise ValueError("Tracker: TEST.FLOW_PNP_ITER > 0 is not supported")
+    if T.INIT_MASK != "box_rendered":
+        raise ValueError("Tracker: TEST.INIT_MASK must be 'box_rendered' (the mask of a frame is the box of its start render), got {!r}".format(
+            T.INIT_MASK))
+
+
+class Tracker(object):
+    """num_tracks = P objects followed through the frames of one camera.  reset() gives every track its class and first pose(s);
+    step() takes one frame and returns device views of the frame's outputs; run() takes a sequence and reads everything back once."""
+
+    def __init__(self, config, predictor, render_machine, num_tracks, capture_graph=True):
+        cfg = config
+        self.settings = s = track_settings(cfg)
+        refuse_for_tracking(cfg, lit=hasattr(render_machine, "normals"))
+        self.cfg, self.P = cfg, int(num_tracks)
+        self.refiner = r = Refiner(cfg, predictor, render_machine, self.P, capture_graph=False)
+        P, T, d = self.P, r.test_iter, r.net.device
+        H, W = source_size(cfg)
+        self.H, self.W, self.device = H, W, d
+        self.depth_factor = float(cfg.dataset.DEPTH_FACTOR)
+        self.pixel_means = np.asarray(cfg.network.PIXEL_MEANS, dtype=np.float32).reshape(3)
+        self.znear, self.zfar = float(cfg.dataset.ZNEAR), float(cfg.dataset.ZFAR)
+        # the observed depth plane of the frame: the refiner's where a stage or an INPUT_DEPTH graph reads one, else the score's own
+        self.depth_observed = r.depth_observed if r.depth_observed is not None else r.batch.get("depth_observed")
+        if self.depth_observed is None and s["score"] == "depth":
+            self.depth_observed = torch.zeros((P, 1, H, W), dtype=torch.float32, device=d)
+        self.needs_depth = self.depth_observed is not None
+        zeros = lambda dtype, *shape: torch.zeros(shape, dtype=dtype, device=d)  # noqa: E731
+        f32, i32 = torch.float32, torch.int32
+        # state
+        self.hist, self.age = zeros(f32, P, 2, 3, 4), zeros(i32, P)
+        self.ring, self.ring_n, self.ring_pos = zeros(f32, P, s["window"], 2), zeros(i32, P), zeros(i32, P)
+        # staging: what a step copies in before the chain runs
+        self.frame_raw = zeros(torch.uint8, H, W, 3)
+        # (torch has no uint16 fill or copy kernels: the plane is made and copied as int16, the same bytes)
+        self.depth_raw = zeros(torch.int16, H, W).view(torch.uint16) if self.needs_depth else None
+        self.reinit_pose, self.reinit_valid = zeros(f32, P, 3, 4), zeros(i32, P)
+        # the start render's box; status rows of a frame: the loop's iterations, the start render, the tracked pose's stage and score
+        self.bbox_start = zeros(i32, P, 4)
+        self.status_rows = zeros(i32, T + 2, P)
+        self.pose_before = r.poses_iter[T - 2] if T > 1 else r.pose_init
+        self.pose_new = {"loop": r.poses_iter[T - 1], "icp": r.pose_icp, "photo": r.pose_photo}[s["pose"]]
+        self.score = None
+        if s["score"] != "none":
+            self.image_sc, self.depth_sc, self.bbox_sc = zeros(f32, P, 3, H, W), zeros(f32, P, 1, H, W), zeros(i32, P, 4)
+            self.score_work = ops.pose_score_workspace(P, H, W, d)
+            self.score = zeros(f32, P)
+        self.flags, self.step_out, self.mean_out = zeros(i32, P), zeros(f32, P, 2), zeros(f32, P, 2)
+        self.graph = None
+        self._want_graph = bool(capture_graph)
+
+    # ------------------------------------------------------------------------------------------
+    def reset(self, class_index, pose, pose_prev=None):
+        """start (again) from `pose` (P,3,4), the pose of the frame before the first one step() gets; with pose_prev, the pose one
+        frame earlier, the first prediction already has a velocity (age 2, else 1).  The step ring is emptied"""
+        P = self.P
+        self.refiner.batch["class_index"].copy_(torch.as_tensor(class_index).reshape(P).to(torch.int32))
+        pose = torch.as_tensor(pose, dtype=torch.float32).reshape(P, 3, 4)
+        self.hist[:, 1].copy_(pose)
+        self.hist[:, 0].copy_(pose if pose_prev is None else torch.as_tensor(pose_prev, dtype=torch.float32).reshape(P, 3, 4))
+        self.age.fill_(1 if pose_prev is None else 2)
+        self.ring.zero_()
+        self.ring_n.zero_()
+        self.ring_pos.zero_()
+
+    def _state(self):
+        return (self.hist, self.age, self.ring, self.ring_n, self.ring_pos)
+
+    def _chain(self):
+        """one frame, everything enqueued on the current stream from the resident tensors"""
+        r, s, T = self.refiner, self.settings, self.refiner.test_iter
+        b, init = r.batch, r.init
+        ops.track_ingest(self.frame_raw, self.depth_factor, self.pixel_means, b["image_observed"], depth_raw=self.depth_raw,
+                         depth_observed=self.depth_observed)
+        ops.track_predict(self.hist, self.age, s["motion"], s["damping"], out=r.pose_init)
+        r._render_start(bbox=self.bbox_start, status=self.status_rows[T])
+        ops.box_mask(self.bbox_start, init["mask_observed"])
+        r._loop()
+        ops.copy(self.status_rows[:T], r.status_iter)
+        last = self.status_rows[T + 1]
+        if s["pose"] == "loop":
+            ops.fill(last, 0)
+        else:
+            ops.copy(last, r.stages[s["pose"]].status)
+        if self.score is not None:   # as Refiner._select scores a hypothesis: every drawn pixel of the render inside its box
+            r.render_machine.render_batch(b["class_index"], self.pose_new, image=self.image_sc, depth=self.depth_sc, bbox=self.bbox_sc,
+                                          plane_means=r.net.plane_means, mask_thr=0.0, status=last)
+            ops.pose_score(b["image_observed"], self.image_sc, self.depth_sc, s["score"], s["depth_tau"],
+                           depth_observed=self.depth_observed if s["score"] == "depth" else None, bbox=self.bbox_sc, score=self.score,
+                           status=last, workspace=self.score_work)
+        ops.track_update(self.pose_before, self.pose_new, self.hist, self.age, self.ring, self.ring_n, self.ring_pos, s["lost_rot_deg"],
+                         s["lost_trans"], self.znear, self.zfar, status_rows=self.status_rows, fatal_mask=FATAL_MASK, score=self.score,
+                         min_score=s["min_score"], reinit_pose=self.reinit_pose, reinit_valid=self.reinit_valid, flags=self.flags,
+                         step=self.step_out, mean=self.mean_out)
+
+    def _stage_inputs(self, frame_bgr, depth_raw, reinit_pose, reinit_valid):
+        P = self.P
+        frame_bgr = torch.as_tensor(frame_bgr)
+        if tuple(frame_bgr.shape) != (self.H, self.W, 3) or frame_bgr.dtype != torch.uint8:
+            raise ValueError("Tracker.step: frame_bgr must be uint8 ({},{},3), got {} {}".format(self.H, self.W, frame_bgr.dtype,
+                                                                                             tuple(frame_bgr.shape)))
+        self.frame_raw.copy_(frame_bgr, non_blocking=True)
+        if self.needs_depth:
+            if depth_raw is None:
+                raise ValueError("Tracker.step: the configuration (INPUT_DEPTH, TEST.ICP_ITER > 0 or TEST.TRACK_SCORE 'depth') needs depth_raw")
+            if isinstance(depth_raw, np.ndarray):
+                depth_raw = torch.from_numpy(np.ascontiguousarray(depth_raw, dtype=np.uint16))
+            if tuple(depth_raw.shape) != (self.H, self.W) or depth_raw.dtype != torch.uint16:
+                raise ValueError("Tracker.step: depth_raw must be uint16 ({},{}), got {} {}".format(self.H, self.W, depth_raw.dtype,
+                                                                                                tuple(depth_raw.shape)))
+            self.depth_raw.view(torch.int16).copy_(depth_raw.contiguous().view(torch.int16), non_blocking=True)
+        if reinit_pose is None:
+            if reinit_valid is not None:
+                raise ValueError("Tracker.step: reinit_valid without reinit_pose")
+            self.reinit_valid.zero_()
+            return
+        self.reinit_pose.copy_(torch.as_tensor(reinit_pose, dtype=torch.float32).reshape(P, 3, 4), non_blocking=True)
+        if reinit_valid is None:
+            self.reinit_valid.fill_(1)
+        else:
+            self.reinit_valid.copy_(torch.as_tensor(reinit_valid).reshape(P).to(torch.int32), non_blocking=True)
+
+    def step(self, frame_bgr, depth_raw=None, reinit_pose=None, reinit_valid=None):
+        """one frame: uint8 BGR (H,W,3) [, uint16 depth (H,W) in 1 / dataset.DEPTH_FACTOR metres], any device.  reinit_pose (P,3,4):
+        a pose offered to every track that is lost on this frame (reinit_valid (P,): to which of them; all when omitted).
+        -> dict of device views, valid until the next step: pose (P,3,4) the tracked pose of the frame, flags (P,) int32 (the frame's
+        status bits, DIM_STATUS_TRACK_LOST / _REINIT among them), step (P,2) the loop's last step (degrees, metres), mean (P,2) its
+        window means, score (P,) or None.  The predicted pose the loop started from stays in refiner.pose_init"""
+        self._stage_inputs(frame_bgr, depth_raw, reinit_pose, reinit_valid)
+        if self._want_graph and self.graph is None:
+            # as Refiner.refine: a warm-up on a side stream (lazy module loads), then the capture -- one stream, kernels only.  The
+            # warm-up is a real frame, so the state it advanced is put back before the captured chain runs for the first time
+            keep = [t.clone() for t in self._state()]
+            side = torch.cuda.Stream(device=self.device)
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):
+                self._chain()
+            torch.cuda.current_stream().wait_stream(side)
+            torch.cuda.synchronize()
+            for t, k in zip(self._state(), keep):
+                t.copy_(k)
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                self._chain()
+            self.graph = g
+        if self.graph is not None:
+            self.graph.replay()
+        else:
+            self._chain()
+        return {"pose": self.pose_new, "flags": self.flags, "step": self.step_out, "mean": self.mean_out, "score": self.score}
+
+    def run(self, frames):
+        """frames: an iterable of dicts with frame_bgr [, depth_raw, reinit_pose, reinit_valid] (the arguments of step).  Every
+        frame's outputs are recorded on the device and read back once at the end -> dict of host arrays (T,P,...): pose, flags, step,
+        mean [, score]"""
+        rec = {}
+        for f in frames:
+            out = self.step(f["frame_bgr"], f.get("depth_raw"), f.get("reinit_pose"), f.get("reinit_valid"))
+            for k, v in out.items():
+                if v is not None:
+                    rec.setdefault(k, []).append(v.clone())
+        return {k: torch.stack(v).cpu().numpy() for k, v in rec.items()}

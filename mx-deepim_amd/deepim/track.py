@@ -1,0 +1,110 @@
+"""Tracking entry point:
+    python deepim/track.py --cfg experiments/deepim/cfgs/deepim_hip_LM_ape_track.yaml --gpus 0 --num_frames 60 --num_objects 3 [--reinit_from_gt]
+Follows the objects of a seeded synthetic video (lib/dataset/synthetic_sequences.py) with deepim.core.tracker.Tracker and prints, per
+object, the frames tracked and lost, the re-initialisations and the mean ADD over the tracked frames, and the frames per second.
+The weights are found as deepim/test.py finds them: `<prefix>-<test_epoch>.params` of the training run, else the seeded
+initialisation (stated in the log).  --reinit_from_gt offers the ground-truth pose to every lost track (stands in for a detector)."""
+from __future__ import print_function, division
+
+import _init_paths  # noqa: F401
+
+import argparse
+import os
+import time
+
+import numpy as np
+
+from deepim.config.config import config, update_config
+
+
+def parse_args():
+    parser = argparse.ArgumentParser(description="Track objects through a synthetic video with a DeepIM network")
+    parser.add_argument("--cfg", help="experiment configure file name", required=True, type=str)
+    args, rest = parser.parse_known_args()
+    update_config(args.cfg)
+    parser.add_argument("--gpus", help="specify the gpu to be use", required=True, type=str)
+    parser.add_argument("--num_frames", help="frames of the synthetic video", default=60, type=int)
+    parser.add_argument("--num_objects", help="objects followed through it", default=3, type=int)
+    parser.add_argument("--subdiv", help="icosphere subdivisions of the synthetic meshes (4 = 5120 triangles)", default=4, type=int)
+    parser.add_argument("--reinit_from_gt", help="offer the ground-truth pose to every lost track", action="store_true")
+    return parser.parse_args()
+
+
+def track_table(out, pose_gt, class_index, models, class_names):
+    """-> [dict(object, cls, tracked, lost, reinit, add)] from Tracker.run's host arrays and the ground truth (T,P,3,4)"""
+    from lib.hip import ops
+    from lib.utils import pose_error
+
+    rows = []
+    flags, pose = out["flags"], out["pose"].astype(np.float64)
+    for p in range(flags.shape[1]):
+        lost = (flags[:, p] & ops.STATUS_TRACK_LOST) != 0
+        pts = models[int(class_index[p])][0].astype(np.float64)
+        adds = [pose_error.add(pose[t, p, :, :3], pose[t, p, :, 3], pose_gt[t, p, :, :3].astype(np.float64), pose_gt[t, p, :, 3].astype(np.float64),
+                               pts) for t in range(flags.shape[0]) if not lost[t]]
+        rows.append(dict(object=p, cls=class_names[int(class_index[p])], tracked=int((~lost).sum()), lost=int(lost.sum()),
+                         reinit=int(((flags[:, p] & ops.STATUS_TRACK_REINIT) != 0).sum()), add=float(np.mean(adds)) if adds else float("nan")))
+    return rows
+
+
+def track_deepim(args):
+    import torch
+
+    from deepim.core.tester import Predictor
+    from deepim.core.tracker import Tracker
+    from deepim.symbols import deepIM_flownet as symbols
+    from lib.dataset.synthetic_sequences import SyntheticSequence
+    from lib.utils.create_logger import create_logger
+    from lib.utils.load_model import load_param
+
+    dev_id = int(args.gpus.split(",")[0])
+    torch.cuda.set_device(dev_id)
+    device = "cuda:{}".format(dev_id)
+    epoch = config.TEST.test_epoch
+    logger, final_output_path = create_logger(config.output_path, args.cfg, config.dataset.test_image_set)
+    prefix = os.path.join(final_output_path, "..", "_".join([iset for iset in config.dataset.image_set.split("+")]), config.TRAIN.model_prefix)
+    sym_instance = getattr(symbols, config.symbol)()
+    sym_instance.get_symbol(config, is_train=False)
+    param_file = "%s-%04d.params" % (prefix, epoch)
+    if os.path.exists(param_file):
+        arg_params, aux_params = load_param(prefix, epoch, process=True)
+        print("loaded {}".format(param_file))
+    else:
+        arg_params = {}
+        msg = "{} not found: running with the seeded initialisation (throughput / plumbing run, poses will not converge)".format(param_file)
+        print(msg)
+        logger.info(msg)
+    arg_params = sym_instance.init_weights(config, arg_params, {}, seed=0)
+
+    P, T = args.num_objects, args.num_frames
+    seq = SyntheticSequence(config, T, P, 2333, device=device, subdiv=args.subdiv)
+    predictor = Predictor(config, arg_params, P, device=device)
+    tracker = Tracker(config, predictor, seq.render_machine, P, capture_graph=True)
+    tracker.reset(seq.class_index, seq.pose_start[1], pose_prev=seq.pose_start[0])
+    frames = list(seq.frames(reinit_from_gt=args.reinit_from_gt))   # rendered before the clock starts
+    # the first frame captures the graph: it is tracked, but timed apart
+    torch.cuda.synchronize()
+    t0 = time.time()
+    first = tracker.run(frames[:1])
+    t1 = time.time()
+    rest = tracker.run(frames[1:]) if T > 1 else None
+    t2 = time.time()
+    out = first if rest is None else {k: np.concatenate([first[k], rest[k]]) for k in first}
+    rows = track_table(out, seq.pose_gt, seq.class_index, seq.models, seq.classes)
+    print("object  class  tracked  lost  reinit  mean ADD (m)")
+    for r in rows:
+        print("{object:6d}  {cls:>5s}  {tracked:7d}  {lost:4d}  {reinit:6d}  {add:.5f}".format(**r))
+    fps = (T - 1) / (t2 - t1) if T > 1 else float("nan")
+    print("tracked {} objects through {} frames x {} iterations on {}: {:.1f} frames/s after the first frame ({:.2f} s, with the graph "
+          "capture)".format(P, T, config.TEST.test_iter, device, fps, t1 - t0))
+    return rows, fps
+
+
+def main():
+    args = parse_args()
+    print(args)
+    track_deepim(args)
+
+
+if __name__ == "__main__":
+    main()

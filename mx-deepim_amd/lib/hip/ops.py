@@ -539,6 +539,67 @@ def hyp_select(score, N, poses_iter, status_iter=None, pose_icp=None, choice=Non
     return choice, poses_sel, status_sel, pose_icp_sel
 
 
+STATUS_TRACK_LOST = 4096     # DIM_STATUS_TRACK_LOST: dim_track_update did not accept the frame's pose
+STATUS_TRACK_REINIT = 8192   # DIM_STATUS_TRACK_REINIT: ... and re-initialised the track from the offered pose
+TRACK_MOTION_ID = {"hold": 0, "velocity": 1}   # DIM_TRACK_MOTION_HOLD / DIM_TRACK_MOTION_VELOCITY
+TRACK_MAX_WINDOW = 64        # DIM_TRACK_MAX_WINDOW
+
+
+def track_ingest(frame_bgr, depth_factor, pixel_means_bgr, image_observed, depth_raw=None, depth_observed=None):
+    """dim_track_ingest: one camera frame, uint8 BGR (H,W,3) [+ uint16 depth (H,W)], into the observed blobs of P tracks:
+    image_observed (P,3,H,W) [, depth_observed (P,1,H,W)], every row the same, every pixel as pair_blobs_from_raw writes it"""
+    H, W, _ = frame_bgr.shape
+    P = image_observed.shape[0]
+    assert tuple(frame_bgr.shape) == (H, W, 3) and tuple(image_observed.shape) == (P, 3, H, W)
+    assert depth_raw is None or tuple(depth_raw.shape) == (H, W)
+    assert depth_observed is None or tuple(depth_observed.shape) == (P, 1, H, W)
+    keep, mp = host_f32(pixel_means_bgr, 3)
+    check(lib().dim_track_ingest(dptr(frame_bgr, torch.uint8), _opt(depth_raw, torch.uint16), P, H, W, float(depth_factor), mp,
+                                 dptr(image_observed, f32), _opt(depth_observed), current_stream()))
+    return image_observed
+
+
+def track_predict(hist, age, mode="velocity", alpha=1.0, out=None):
+    """dim_track_predict (restated by tests/track_reference.py): hist (P,2,3,4) f32, [1] the last accepted pose and [0] the one
+    before, age (P,) int32 -> (P,3,4) the pose the next frame starts from: hist[1] bit for bit ("hold", age < 2, a bad history) or the
+    damped constant-velocity extrapolation ("velocity", alpha in [0,1])"""
+    P = hist.shape[0]
+    if mode not in TRACK_MOTION_ID:
+        raise ValueError("track motion must be 'hold' or 'velocity', got {!r}".format(mode))
+    assert tuple(hist.shape) == (P, 2, 3, 4) and age.numel() == P
+    out = out if out is not None else _new((P, 3, 4), hist)
+    assert tuple(out.shape) == (P, 3, 4)
+    check(lib().dim_track_predict(dptr(hist, f32), dptr(age, i32), P, TRACK_MOTION_ID[mode], float(alpha), dptr(out, f32), current_stream()))
+    return out
+
+
+def track_update(pose_before, pose_new, hist, age, ring, ring_n, ring_pos, lost_rot_deg, lost_trans_m, znear, zfar, status_rows=None,
+                 fatal_mask=0, score=None, min_score=0.0, reinit_pose=None, reinit_valid=None, flags=None, step=None, mean=None):
+    """dim_track_update (restated by tests/track_reference.py): the per-track state machine after a frame's refinement.  Reads and
+    writes hist (P,2,3,4), age (P,), ring (P,Wn,2), ring_n, ring_pos (P,) in place -> flags (P,) int32, step (P,2), mean (P,2).
+    status_rows (n_rows,P) int32 are OR-ed; score (P,) f32 and reinit_pose (P,3,4) / reinit_valid (P,) int32 are optional"""
+    P, Wn = ring.shape[0], ring.shape[1]
+    assert tuple(pose_before.shape) == (P, 3, 4) and tuple(pose_new.shape) == (P, 3, 4) and tuple(hist.shape) == (P, 2, 3, 4)
+    assert tuple(ring.shape) == (P, Wn, 2) and age.numel() == P and ring_n.numel() == P and ring_pos.numel() == P
+    n_rows = 0
+    if status_rows is not None:
+        assert status_rows.numel() % P == 0
+        n_rows = status_rows.numel() // P
+    assert score is None or score.numel() == P
+    assert (reinit_pose is None) == (reinit_valid is None)
+    assert reinit_pose is None or (tuple(reinit_pose.shape) == (P, 3, 4) and reinit_valid.numel() == P)
+    flags = flags if flags is not None else _new((P,), hist, i32)
+    step = step if step is not None else _new((P, 2), hist)
+    mean = mean if mean is not None else _new((P, 2), hist)
+    assert flags.numel() == P and step.numel() == 2 * P and mean.numel() == 2 * P
+    check(lib().dim_track_update(dptr(pose_before, f32), dptr(pose_new, f32), _opt(status_rows, i32), n_rows, int(fatal_mask), _opt(score),
+                                 float(min_score), _opt(reinit_pose), _opt(reinit_valid, i32), float(lost_rot_deg), float(lost_trans_m),
+                                 int(Wn), float(znear), float(zfar), P, dptr(hist, f32), dptr(age, i32), dptr(ring, f32),
+                                 dptr(ring_n, i32), dptr(ring_pos, i32), dptr(flags, i32), dptr(step, f32), dptr(mean, f32),
+                                 current_stream()))
+    return flags, step, mean
+
+
 STATUS_COARSE_BAD_BOX = 512   # DIM_STATUS_COARSE_BAD_BOX: dim_pose_from_box gave the candidate its fallback row
 HYP_TOPK_MAX = 64             # dim_hyp_topk: the largest k
 
