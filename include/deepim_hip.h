@@ -48,6 +48,7 @@ extern "C" {
 #define DIM_STATUS_SIL_FEW_POINTS 2048 /* dim_sil_refine: an iteration had fewer than 64 weighted contour points or a singular system (no update) */
 #define DIM_STATUS_TRACK_LOST 4096 /* dim_track_update: the track failed the lost test on this frame (the frame's pose was not accepted) */
 #define DIM_STATUS_TRACK_REINIT 8192 /* dim_track_update: ... and was re-initialised from the offered pose */
+#define DIM_STATUS_TRACK_OCCLUDED 16384 /* dim_track_update_occ: too little of the track's render is visible on this frame (it coasts, or is lost when the budget is spent) */
 
 const char* dim_last_error(void);
 /* library / device probe: fills name (<= n bytes), returns number of compute units or <0 */
@@ -433,6 +434,48 @@ int dim_track_update(const float* pose_before, const float* pose_new, const int*
                      const float* score, float min_score, const float* reinit_pose, const int* reinit_valid, float lost_rot_deg,
                      float lost_trans_m, int Wn, float znear, float zfar, int P, float* hist, int* age, float* ring, int* ring_n,
                      int* ring_pos, int* flags, float* step, float* mean, void* stream);
+/* Occlusion between the tracks and against the frame's depth.  Restated by tests/track_occ_reference.py.
+ * dim_track_visibility: depth_rendered (P,1,H,W): the P tracks' renders at one camera; depth_frame (H,W) metres or NULL; occluder_ok
+ *   (P) int32 or NULL (all 1); mode = DIM_TRACK_OCC_TRACKS | DIM_TRACK_OCC_DEPTH (one or both); delta >= 0 metres.  Per pixel and
+ *   track p with rendered depth d_p, every comparison in float32:
+ *     drawn_p           = 0 < d_p < +inf (NaN, +inf, 0 and negatives are not drawn)
+ *     hidden_by_track_p = DIM_TRACK_OCC_TRACKS and some q != p with drawn_q, occluder_ok[q] != 0 and d_p - d_q > delta (computed as
+ *                         d_p - m_p > delta, m_p the smallest such d_q: the subtraction is monotone)
+ *     hidden_by_depth_p = DIM_TRACK_OCC_DEPTH, o = depth_frame[pixel] with 0 < o < +inf, and d_p - o > delta (a pixel without a
+ *                         reading hides nothing)
+ *   depth_visible (P,1,H,W) = the bits of d_p where drawn and not hidden, else +0.0: passed to dim_pose_score as depth_rendered it
+ *   restricts the score's support to the visible pixels.  counts (P,4) int32 = {drawn, visible, hidden by a track, hidden by the
+ *   frame's depth only}; the first is the sum of the other three.  No output needs initialising; integer sums, so a second call gives
+ *   the same bits.  workspace: dim_track_visibility_workspace_bytes(P, H, W) bytes, 4-byte aligned, no initialisation needed.  Any W;
+ *   16-byte accesses when W % 4 == 0 and depth_rendered, depth_visible and depth_frame are 16-byte aligned.  2 launches.
+ *   P, H or W <= 0, mode 0 or with an unknown bit, DIM_TRACK_OCC_DEPTH with a NULL depth_frame, a negative or non-finite delta or a
+ *   NULL required pointer return DIM_ERR_ARG before anything is enqueued.
+ * dim_track_update_occ: dim_track_update with an occluded state.  Additional inputs: counts (P,4) of dim_track_visibility for the
+ *   render of pose_new, min_visible in [0,1], max_occluded >= 0, pose_pred (P,3,4) the pose the frame started from; additional state
+ *   occ_age (P) int32: the frames the track has coasted in a row.  Per track, in this order:
+ *   a. step as in rule 1.  fatal = the first three clauses of rule 3 (a fatal status bit, a non-finite pose_new, t_z out of range).
+ *   b. visible[p] = float(double(counts[1]) / double(counts[0])), 0 when nothing is drawn.
+ *      occluded = not fatal, counts[0] > 0 and double(counts[1]) < double(min_visible) * counts[0].
+ *   c. not occluded: rules 2 to 6 as they stand above, and occ_age = 0.
+ *   d. occluded: flags gain DIM_STATUS_TRACK_OCCLUDED; the step does not enter the ring, and mean is the mean of what the ring holds
+ *      (0 when it holds nothing); the score and window tests are skipped.  With occ_age < max_occluded and a finite pose_pred with t_z
+ *      in [znear, zfar] the track coasts: hist[0] = hist[1], hist[1] = pose_pred bit for bit, age = min(age + 1, 2), occ_age += 1,
+ *      ring, ring_n and ring_pos untouched.  Otherwise it is lost by rules 5 and 6, and occ_age = 0.
+ *   Then pose_track (P,3,4) = hist[1] (the accepted pose, the coasted prediction, the offered pose or the last accepted pose of a lost
+ *   track) and occluder_ok (P) int32 = 0 for a track that is lost and not re-initialised on this frame, else 1.  With min_visible = 0,
+ *   or counts[1] == counts[0], every tensor the two entries share gets the bits dim_track_update gives it.  min_visible outside [0, 1],
+ *   max_occluded < 0 and dim_track_update's own cases return DIM_ERR_ARG. */
+#define DIM_TRACK_OCC_TRACKS 1
+#define DIM_TRACK_OCC_DEPTH 2
+long dim_track_visibility_workspace_bytes(int P, int H, int W);
+int dim_track_visibility(const float* depth_rendered, const float* depth_frame, const int* occluder_ok, int P, int H, int W, int mode,
+                         float delta, void* workspace, float* depth_visible, int* counts, void* stream);
+int dim_track_update_occ(const float* pose_before, const float* pose_new, const int* status_rows, int n_rows, int fatal_mask,
+                         const float* score, float min_score, const float* reinit_pose, const int* reinit_valid, float lost_rot_deg,
+                         float lost_trans_m, int Wn, float znear, float zfar, int P, const int* counts, float min_visible,
+                         int max_occluded, const float* pose_pred, float* hist, int* age, float* ring, int* ring_n, int* ring_pos,
+                         int* occ_age, int* flags, float* step, float* mean, float* visible, float* pose_track, int* occluder_ok,
+                         void* stream);
 
 /* ---------------------------------------------------------------- pose errors of the evaluation (lib/utils/pose_error.py) on the device
  * For T pose sets of B pairs: errors (T,B,5) float64 = {re (degrees), te, add, adi, arp_2d} of poses_est[t][b] against pose_gt[b]

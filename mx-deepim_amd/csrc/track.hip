@@ -8,6 +8,12 @@
 //                          constant velocity), float64 inside, one rounding to float32
 //   track_update_kernel    one lane per track: the last iteration's step into a ring, its window means, the lost test, and the
 //                          history / re-initialisation state machine.  Every pose written into the history is a bit-for-bit copy
+//   track_visibility_kernel  occlusion between the tracks and against the frame's depth: one lane per 4 (or 1) pixels, P the inner
+//                          loop.  Each render is read (twice when tracks hide tracks: the two smallest depths first) and written
+//                          once with its hidden pixels zeroed -- a depth plane dim_pose_score takes as it is -- and the pixel counts
+//                          leave as one packed word per (wave, track); track_visibility_finish adds them: integers, no atomics
+//   track_update_occ_kernel  track_update_kernel with an "occluded" state: a track of which too little is visible coasts on the
+//                          predicted pose, within a budget of frames, instead of being lost.  Restated by tests/track_occ_reference.py
 // Nothing allocates or synchronises: every entry is graph-capturable.
 #include "common.h"
 #include "twist_solve.h"
@@ -223,6 +229,236 @@ __global__ __launch_bounds__(64) void track_update_kernel(TrackUpdateArgs a) {
   a.flags[p] = status;
 }
 
+// ---- occlusion: which drawn pixels of each track's render does another track, or the frame's own depth, hide
+constexpr int kVisThreads = 256;
+constexpr int kVisField = 10;   // a lane counts at most 4 pixels per class and a wave at most 256: three 10-bit fields in one word
+constexpr unsigned kVisFieldMask = (1u << kVisField) - 1u;
+
+__device__ __forceinline__ bool depth_drawn(float d) { return d > 0.f && d < INFINITY; }   // NaN, +inf, 0 and negatives are not drawn
+
+// V pixels per lane: 4 (one 16-byte access per plane) or 1.  Pass 1 (only with DIM_TRACK_OCC_TRACKS): the smallest and the second
+// smallest drawn depth of the eligible tracks at each pixel, with the track of the smallest -- x -> float32(d - x) is monotone, so
+// "some eligible q != p with d_p - d_q > delta" is "d_p - m_p > delta", m_p the smallest eligible depth of a track other than p.
+// Pass 2: classify and write.  Counts leave as one packed word per (wave, track) into `partial`; track_visibility_finish sums them.
+// No lane returns early: every lane takes part in the butterfly.
+template <int V>
+__global__ __launch_bounds__(kVisThreads) void track_visibility_kernel(const float* __restrict__ depth_rendered,
+                                                                       const float* __restrict__ depth_frame,
+                                                                       const int* __restrict__ occluder_ok, int P, long plane, int mode,
+                                                                       float delta, float* __restrict__ depth_visible,
+                                                                       unsigned* __restrict__ partial) {
+  const long pix = (long)V * ((long)blockIdx.x * kVisThreads + threadIdx.x);
+  const bool live = pix < plane;   // V == 4: plane % 4 == 0, a live lane owns four whole pixels
+  float d[V], m1[V], m2[V], o[V];
+  int i1[V];
+#pragma unroll
+  for (int j = 0; j < V; ++j) {
+    m1[j] = m2[j] = INFINITY;
+    i1[j] = -1;
+    o[j] = 0.f;
+  }
+  auto load = [&](const float* src, float* v) {
+    if (V == 4) {
+      const float4 q = *reinterpret_cast<const float4*>(src + pix);
+      v[0] = q.x; v[1 % V] = q.y; v[2 % V] = q.z; v[3 % V] = q.w;
+    } else {
+      v[0] = src[pix];
+    }
+  };
+  if (live && (mode & DIM_TRACK_OCC_TRACKS)) {
+    for (int p = 0; p < P; ++p) {
+      if (occluder_ok && occluder_ok[p] == 0) continue;
+      load(depth_rendered + (long)p * plane, d);
+#pragma unroll
+      for (int j = 0; j < V; ++j) {
+        if (!depth_drawn(d[j])) continue;
+        if (d[j] < m1[j]) {
+          m2[j] = m1[j];
+          m1[j] = d[j];
+          i1[j] = p;
+        } else if (d[j] < m2[j]) {
+          m2[j] = d[j];
+        }
+      }
+    }
+  }
+  if (live && (mode & DIM_TRACK_OCC_DEPTH)) {
+    load(depth_frame, o);
+#pragma unroll
+    for (int j = 0; j < V; ++j)
+      if (!depth_drawn(o[j])) o[j] = 0.f;   // no reading: hides nothing
+  }
+  const int wave = blockIdx.x * (kVisThreads / kWave) + threadIdx.x / kWave;
+  for (int p = 0; p < P; ++p) {
+    unsigned c = 0;
+    if (live) {
+      load(depth_rendered + (long)p * plane, d);
+      float out[V];
+#pragma unroll
+      for (int j = 0; j < V; ++j) {
+        out[j] = 0.f;
+        if (!depth_drawn(d[j])) continue;
+        const float m = i1[j] == p ? m2[j] : m1[j];
+        if (d[j] - m > delta) {
+          c += 1u << kVisField;
+        } else if (o[j] > 0.f && d[j] - o[j] > delta) {
+          c += 1u << (2 * kVisField);
+        } else {
+          c += 1u;
+          out[j] = d[j];
+        }
+      }
+      float* dst = depth_visible + (long)p * plane + pix;
+      if (V == 4)
+        *reinterpret_cast<float4*>(dst) = make_float4(out[0], out[1 % V], out[2 % V], out[3 % V]);
+      else
+        *dst = out[0];
+    }
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1) c += __shfl_xor(c, s, 64);
+    if (threadIdx.x % kWave == 0) partial[(long)wave * P + p] = c;
+  }
+}
+
+// one wave per track: the packed words of all waves -> counts (P,4) = {drawn, visible, hidden by a track, hidden by the depth only}
+__global__ __launch_bounds__(kWave) void track_visibility_finish(const unsigned* __restrict__ partial, int P, int waves,
+                                                                 int* __restrict__ counts) {
+  const int p = blockIdx.x;
+  int vis = 0, trk = 0, dep = 0;
+  for (int w = threadIdx.x; w < waves; w += kWave) {
+    const unsigned c = partial[(long)w * P + p];
+    vis += (int)(c & kVisFieldMask);
+    trk += (int)((c >> kVisField) & kVisFieldMask);
+    dep += (int)(c >> (2 * kVisField));
+  }
+#pragma unroll
+  for (int s = 32; s > 0; s >>= 1) {
+    vis += __shfl_xor(vis, s, 64);
+    trk += __shfl_xor(trk, s, 64);
+    dep += __shfl_xor(dep, s, 64);
+  }
+  if (threadIdx.x == 0) {
+    int* c = counts + 4L * p;
+    c[0] = vis + trk + dep;
+    c[1] = vis;
+    c[2] = trk;
+    c[3] = dep;
+  }
+}
+
+struct TrackOccArgs {
+  TrackUpdateArgs u;
+  const int* counts;
+  float min_visible;
+  int max_occluded;
+  const float* pose_pred;
+  int* occ_age;
+  float* visible;
+  float* pose_track;
+  int* occluder_ok;
+};
+
+// track_update_kernel with the occluded state in front of its rules 2 to 6 (deepim_hip.h).  A track that is not occluded takes
+// those rules as they stand there, statement by statement, so that min_visible = 0 gives the bits of dim_track_update.
+__global__ __launch_bounds__(64) void track_update_occ_kernel(TrackOccArgs o) {
+  const TrackUpdateArgs& a = o.u;
+  const int p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= a.P) return;
+  const int Wn = a.Wn;
+  const float* Tb = a.pose_before + 12L * p;
+  const float* Tn = a.pose_new + 12L * p;
+  int status = 0;
+  for (int r = 0; r < a.n_rows; ++r) status |= a.status_rows[(long)r * a.P + p];
+  // 1. the step of the loop's last iteration
+  double D[9], v[3], s, c;
+  rel_rotation(Tn, Tb, D);
+  rotation_sin_cos(D, v, &s, &c);
+  double step_rot = atan2(s, c) * (180.0 / 3.14159265358979323846);
+  const double dx = (double)Tn[3] - (double)Tb[3], dy = (double)Tn[7] - (double)Tb[7], dz = (double)Tn[11] - (double)Tb[11];
+  double step_trans = sqrt(dx * dx + dy * dy + dz * dz);
+  if (!isfinite(step_rot)) step_rot = INFINITY;
+  if (!isfinite(step_trans)) step_trans = INFINITY;
+  a.step[2 * p] = (float)step_rot;
+  a.step[2 * p + 1] = (float)step_trans;
+  // fatal: nothing to judge a visibility on; occluded: too little of the drawn render is visible
+  bool lost = (status & a.fatal_mask) != 0 || !pose_finite(Tn);
+  lost = lost || !(Tn[11] >= a.znear && Tn[11] <= a.zfar);
+  const int drawn = o.counts[4 * p], seen = o.counts[4 * p + 1];
+  o.visible[p] = drawn > 0 ? (float)((double)seen / (double)drawn) : 0.f;
+  const bool occluded = !lost && drawn > 0 && (double)seen < (double)o.min_visible * (double)drawn;
+  float* ring = a.ring + 2L * Wn * p;
+  int pos = a.ring_pos[p], n = a.ring_n[p];
+  if (pos < 0 || pos >= Wn) pos = 0;
+  n = min(max(n, 0), Wn);
+  float* h0 = a.hist + 24L * p;
+  float* h1 = h0 + 12;
+  int age = min(max(a.age[p], 0), 2);
+  int occ_age = max(o.occ_age[p], 0);
+  bool reinit = false;
+  if (!occluded) {
+    // 2. into the ring over its oldest entry
+    ring[2 * pos] = (float)step_rot;
+    ring[2 * pos + 1] = (float)step_trans;
+    pos = pos + 1 == Wn ? 0 : pos + 1;
+    n = min(n + 1, Wn);
+  }
+  // the means over the ring's entries as they are stored, oldest first (an occluded track: of what was stored before, 0 of nothing)
+  double sum_rot = 0.0, sum_trans = 0.0;
+  for (int k = 0; k < n; ++k) {
+    const int q = (pos - n + k + Wn) % Wn;
+    sum_rot += (double)ring[2 * q];
+    sum_trans += (double)ring[2 * q + 1];
+  }
+  const double mean_rot = n > 0 ? sum_rot / n : 0.0, mean_trans = n > 0 ? sum_trans / n : 0.0;
+  a.mean[2 * p] = (float)mean_rot;
+  a.mean[2 * p + 1] = (float)mean_trans;
+  bool coast = false;
+  if (occluded) {
+    const float* Tp = o.pose_pred + 12L * p;
+    coast = occ_age < o.max_occluded && pose_finite(Tp) && Tp[11] >= a.znear && Tp[11] <= a.zfar;
+    status |= DIM_STATUS_TRACK_OCCLUDED;
+    if (coast) {   // hidden, within the budget: the motion model's pose is the frame's pose
+      for (int k = 0; k < 12; ++k) h0[k] = h1[k];
+      for (int k = 0; k < 12; ++k) h1[k] = Tp[k];
+      age = min(age + 1, 2);
+      occ_age += 1;
+    } else {
+      lost = true;
+    }
+  } else {
+    // 3. lost?
+    if (a.score) lost = lost || !(a.score[p] >= a.min_score);
+    if (n == Wn) lost = lost || mean_rot > (double)a.lost_rot_deg || mean_trans > (double)a.lost_trans_m;
+  }
+  if (!coast) {
+    occ_age = 0;
+    if (!lost) {                                              // 4. accepted
+      for (int k = 0; k < 12; ++k) h0[k] = h1[k];
+      for (int k = 0; k < 12; ++k) h1[k] = Tn[k];
+      age = min(age + 1, 2);
+    } else if (a.reinit_valid && a.reinit_pose && a.reinit_valid[p] != 0) {   // 5. lost, a pose is offered
+      const float* Tr = a.reinit_pose + 12L * p;
+      for (int k = 0; k < 12; ++k) h1[k] = Tr[k];
+      age = 1;
+      for (int k = 0; k < 2 * Wn; ++k) ring[k] = 0.f;
+      n = 0;
+      pos = 0;
+      reinit = true;
+      status |= DIM_STATUS_TRACK_LOST | DIM_STATUS_TRACK_REINIT;
+    } else {                                                  // 6. lost, nothing offered: the last accepted pose, no velocity
+      age = min(age, 1);
+      status |= DIM_STATUS_TRACK_LOST;
+    }
+    a.ring_n[p] = n;
+    a.ring_pos[p] = pos;
+  }
+  a.age[p] = age;
+  a.flags[p] = status;
+  o.occ_age[p] = occ_age;
+  for (int k = 0; k < 12; ++k) o.pose_track[12L * p + k] = h1[k];
+  o.occluder_ok[p] = (lost && !reinit) ? 0 : 1;
+}
+
 }  // namespace dim
 
 using namespace dim;
@@ -265,4 +501,58 @@ extern "C" int dim_track_update(const float* pose_before, const float* pose_new,
                     lost_trans_m, Wn, znear, zfar, P, hist, age, ring, ring_n, ring_pos, flags, step, mean};
   hipLaunchKernelGGL(track_update_kernel, dim3(ceil_div(P, 64)), dim3(64), 0, as_stream(stream), a);
   return check_launch("track_update");
+}
+
+static long visibility_waves(long plane, int V) { return (long)ceil_div(plane, (long)kVisThreads * V) * (kVisThreads / kWave); }
+
+extern "C" long dim_track_visibility_workspace_bytes(int P, int H, int W) {
+  if (P <= 0 || H <= 0 || W <= 0) return 0;
+  return visibility_waves((long)H * W, 1) * P * (long)sizeof(unsigned);   // the one-pixel-per-lane path has the most waves
+}
+
+extern "C" int dim_track_visibility(const float* depth_rendered, const float* depth_frame, const int* occluder_ok, int P, int H, int W,
+                                    int mode, float delta, void* workspace, float* depth_visible, int* counts, void* stream) {
+  DIM_REQUIRE(P > 0 && H > 0 && W > 0 && (long)H * W < (1L << 31), "track_visibility: P = %d, H = %d, W = %d", P, H, W);
+  DIM_REQUIRE(mode != 0 && (mode & ~(DIM_TRACK_OCC_TRACKS | DIM_TRACK_OCC_DEPTH)) == 0, "track_visibility: mode = %d", mode);
+  DIM_REQUIRE(!(mode & DIM_TRACK_OCC_DEPTH) || depth_frame, "track_visibility: DIM_TRACK_OCC_DEPTH needs depth_frame");
+  DIM_REQUIRE(delta >= 0.f && delta < INFINITY, "track_visibility: delta = %g must be finite and >= 0", (double)delta);
+  DIM_REQUIRE(depth_rendered && workspace && depth_visible && counts, "track_visibility: null pointer");
+  DIM_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 3) == 0, "track_visibility: the workspace must be 4-byte aligned");
+  const long plane = (long)H * W;
+  const float* frame = (mode & DIM_TRACK_OCC_DEPTH) ? depth_frame : nullptr;
+  auto al = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+  const bool vec = W % 4 == 0 && al(depth_rendered) && al(depth_visible) && (!frame || al(frame));
+  const int V = vec ? 4 : 1;
+  const int blocks = ceil_div(plane, (long)kVisThreads * V);
+  unsigned* partial = reinterpret_cast<unsigned*>(workspace);
+  if (vec)
+    hipLaunchKernelGGL(track_visibility_kernel<4>, dim3(blocks), dim3(kVisThreads), 0, as_stream(stream), depth_rendered, frame, occluder_ok,
+                       P, plane, mode, delta, depth_visible, partial);
+  else
+    hipLaunchKernelGGL(track_visibility_kernel<1>, dim3(blocks), dim3(kVisThreads), 0, as_stream(stream), depth_rendered, frame, occluder_ok,
+                       P, plane, mode, delta, depth_visible, partial);
+  hipLaunchKernelGGL(track_visibility_finish, dim3(P), dim3(kWave), 0, as_stream(stream), (const unsigned*)partial, P,
+                     (int)visibility_waves(plane, V), counts);
+  return check_launch("track_visibility");
+}
+
+extern "C" int dim_track_update_occ(const float* pose_before, const float* pose_new, const int* status_rows, int n_rows, int fatal_mask,
+                                    const float* score, float min_score, const float* reinit_pose, const int* reinit_valid,
+                                    float lost_rot_deg, float lost_trans_m, int Wn, float znear, float zfar, int P, const int* counts,
+                                    float min_visible, int max_occluded, const float* pose_pred, float* hist, int* age, float* ring,
+                                    int* ring_n, int* ring_pos, int* occ_age, int* flags, float* step, float* mean, float* visible,
+                                    float* pose_track, int* occluder_ok, void* stream) {
+  DIM_REQUIRE(P > 0 && n_rows >= 0, "track_update_occ: P = %d, n_rows = %d", P, n_rows);
+  DIM_REQUIRE(Wn >= 1 && Wn <= DIM_TRACK_MAX_WINDOW, "track_update_occ: Wn = %d outside [1, %d]", Wn, DIM_TRACK_MAX_WINDOW);
+  DIM_REQUIRE(min_visible >= 0.f && min_visible <= 1.f, "track_update_occ: min_visible = %g outside [0, 1]", (double)min_visible);
+  DIM_REQUIRE(max_occluded >= 0, "track_update_occ: max_occluded = %d", max_occluded);
+  DIM_REQUIRE(pose_before && pose_new && hist && age && ring && ring_n && ring_pos && flags && step && mean, "track_update_occ: null pointer");
+  DIM_REQUIRE(counts && pose_pred && occ_age && visible && pose_track && occluder_ok, "track_update_occ: null pointer");
+  DIM_REQUIRE(n_rows == 0 || status_rows, "track_update_occ: null pointer (status_rows)");
+  DIM_REQUIRE((reinit_pose == nullptr) == (reinit_valid == nullptr), "track_update_occ: reinit_pose and reinit_valid go together");
+  TrackOccArgs o{{pose_before, pose_new, status_rows, n_rows, fatal_mask, score, min_score, reinit_pose, reinit_valid, lost_rot_deg,
+                  lost_trans_m, Wn, znear, zfar, P, hist, age, ring, ring_n, ring_pos, flags, step, mean},
+                 counts, min_visible, max_occluded, pose_pred, occ_age, visible, pose_track, occluder_ok};
+  hipLaunchKernelGGL(track_update_occ_kernel, dim3(ceil_div(P, 64)), dim3(64), 0, as_stream(stream), o);
+  return check_launch("track_update_occ");
 }

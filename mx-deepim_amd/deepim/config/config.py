@@ -113,6 +113,12 @@ def _defaults():
                    # tuned on real video
                    TRACK_MOTION="velocity", TRACK_DAMPING=1.0, TRACK_WINDOW=10, TRACK_LOST_ROT_DEG=10.0, TRACK_LOST_TRANS=0.01,
                    TRACK_SCORE="none", TRACK_MIN_SCORE=0.5, TRACK_DEPTH_TAU=0.02, TRACK_POSE="loop",
+                   # occlusion reasoning of the tracker ("none" = off): what may hide a track's render -- the other "tracks", the
+                   # frame's own "depth" (needs depth frames) or "both" -- by more than TRACK_OCC_DELTA metres (VSD_DELTA's default);
+                   # the score then counts the visible pixels only, and a track of which less than TRACK_MIN_VISIBLE of the drawn
+                   # pixels are visible is occluded, not lost: it coasts on the motion model for at most TRACK_MAX_OCCLUDED frames in
+                   # a row.  These two are starting values that nobody has tuned on real video either
+                   TRACK_OCCLUSION="none", TRACK_OCC_DELTA=0.015, TRACK_MIN_VISIBLE=0.3, TRACK_MAX_OCCLUDED=30,
                    # pred_eval: the pose errors (re, te, ADD, ADD-S, arp_2d) from dim_pose_errors on the device instead of
                    # lib/utils/pose_error.py on the host, one pose at a time
                    DEVICE_EVAL=False,

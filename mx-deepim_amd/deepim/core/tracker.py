@@ -7,6 +7,11 @@ P tracks share one camera.  Per frame one chain runs on one stream, with no host
     [render + dim_pose_score of the tracked pose against the frame]  ->  update (dim_track_update: step ring, lost test, history,
     re-initialisation)
 
+With TEST.TRACK_OCCLUSION on, the tracks are judged together instead of each alone: the render of the tracked poses goes through
+dim_track_visibility (which pixels of a track another track, or the frame's own depth, hides), the score is taken over the visible
+pixels only, and dim_track_update_occ lets a track of which too little is visible coast on the motion model for a while instead of
+losing it (tests/track_occ_reference.py restates both).
+
 and with capture_graph the chain is one hipGraph, captured at the first step and replayed for every later frame.  The state (pose
 history, age, step ring) lives in device tensors the chain reads and writes in place; a step copies the frame (and the offered
 re-initialisation poses) into resident staging tensors and launches the chain.  tests/track_reference.py restates predict and update.
@@ -24,6 +29,7 @@ from deepim.symbols.deepIM_flownet import source_size
 TRACK_MOTIONS = ("hold", "velocity")
 TRACK_SCORES = ("none", "rgb", "depth")
 TRACK_POSES = ("loop", "icp", "photo")
+TRACK_OCCLUSIONS = ("none", "tracks", "depth", "both")
 # status bits that end a track's frame: nothing to zoom on (the object left the image or the render is empty), a class or camera
 # the rasteriser refused.  The stages' own "too few points" bits are not fatal: their pose is then the loop's, unchanged
 FATAL_MASK = 1 | 2 | ops.STATUS_BAD_CLASS | ops.STATUS_BAD_K   # DIM_STATUS_OBS_BOX_EMPTY | DIM_STATUS_REN_BOX_EMPTY | ...
@@ -40,9 +46,22 @@ def _finite(T, key, what, ok):
     return f
 
 
+def occlusion_settings(cfg):
+    """-> dict(mode, delta, min_visible, max_occluded) of cfg.TEST.TRACK_OCCLUSION, TRACK_OCC_DELTA, TRACK_MIN_VISIBLE and
+    TRACK_MAX_OCCLUDED, checked; ValueError names the bad key"""
+    T = cfg.TEST
+    mode = T.get("TRACK_OCCLUSION")
+    if mode not in TRACK_OCCLUSIONS:
+        raise ValueError("TEST.TRACK_OCCLUSION must be one of {}, got {!r}".format(TRACK_OCCLUSIONS, mode))
+    delta = _finite(T, "TRACK_OCC_DELTA", "a finite distance >= 0 (metres)", lambda f: f >= 0)
+    min_visible = _finite(T, "TRACK_MIN_VISIBLE", "a number in [0, 1]", lambda f: 0.0 <= f <= 1.0)
+    max_occluded = int_setting("TRACK_MAX_OCCLUDED", T.get("TRACK_MAX_OCCLUDED"), 0, 2 ** 31 - 1, "an integer >= 0")
+    return dict(mode=mode, delta=delta, min_visible=min_visible, max_occluded=max_occluded)
+
+
 def track_settings(cfg):
     """-> dict(motion, damping, window, lost_rot_deg, lost_trans, score, min_score, depth_tau, pose) of cfg.TEST.TRACK_*, checked;
-    ValueError names the bad key"""
+    ValueError names the bad key.  The occlusion keys are checked here as well; their values come from occlusion_settings"""
     T = cfg.TEST
     motion = T.get("TRACK_MOTION")
     if motion not in TRACK_MOTIONS:
@@ -61,6 +80,7 @@ def track_settings(cfg):
         raise ValueError("TEST.TRACK_POSE must be one of {}, got {!r}".format(TRACK_POSES, pose))
     if pose != "loop" and pose not in stages_on(cfg):
         raise ValueError("TEST.TRACK_POSE {!r} needs its stage switched on (TEST.{}_ITER > 0)".format(pose, pose.upper()))
+    occlusion_settings(cfg)
     return dict(motion=motion, damping=damping, window=window, lost_rot_deg=rot, lost_trans=trans, score=score, min_score=min_score,
                 depth_tau=tau, pose=pose)
 
@@ -90,6 +110,9 @@ class Tracker(object):
     def __init__(self, config, predictor, render_machine, num_tracks, capture_graph=True):
         cfg = config
         self.settings = s = track_settings(cfg)
+        self.occlusion = occ = occlusion_settings(cfg)
+        self.occ_on = occ["mode"] != "none"
+        occ_depth = occ["mode"] in ("depth", "both")
         refuse_for_tracking(cfg, lit=hasattr(render_machine, "normals"))
         self.cfg, self.P = cfg, int(num_tracks)
         self.refiner = r = Refiner(cfg, predictor, render_machine, self.P, capture_graph=False)
@@ -101,7 +124,7 @@ class Tracker(object):
         self.znear, self.zfar = float(cfg.dataset.ZNEAR), float(cfg.dataset.ZFAR)
         # the observed depth plane of the frame: the refiner's where a stage or an INPUT_DEPTH graph reads one, else the score's own
         self.depth_observed = r.depth_observed if r.depth_observed is not None else r.batch.get("depth_observed")
-        if self.depth_observed is None and s["score"] == "depth":
+        if self.depth_observed is None and (s["score"] == "depth" or occ_depth):
             self.depth_observed = torch.zeros((P, 1, H, W), dtype=torch.float32, device=d)
         self.needs_depth = self.depth_observed is not None
         zeros = lambda dtype, *shape: torch.zeros(shape, dtype=dtype, device=d)  # noqa: E731
@@ -109,6 +132,9 @@ class Tracker(object):
         # state
         self.hist, self.age = zeros(f32, P, 2, 3, 4), zeros(i32, P)
         self.ring, self.ring_n, self.ring_pos = zeros(f32, P, s["window"], 2), zeros(i32, P), zeros(i32, P)
+        # (occlusion) occ_age: the frames a track has coasted in a row; occluder_ok: 0 for a track that was lost on the last frame and
+        # not re-initialised -- its pose is stale, it hides nobody on the next one
+        self.occ_age, self.occluder_ok = zeros(i32, P), torch.ones((P,), dtype=i32, device=d)
         # staging: what a step copies in before the chain runs
         self.frame_raw = zeros(torch.uint8, H, W, 3)
         # (torch has no uint16 fill or copy kernels: the plane is made and copied as int16, the same bytes)
@@ -120,11 +146,16 @@ class Tracker(object):
         self.pose_before = r.poses_iter[T - 2] if T > 1 else r.pose_init
         self.pose_new = {"loop": r.poses_iter[T - 1], "icp": r.pose_icp, "photo": r.pose_photo}[s["pose"]]
         self.score = None
-        if s["score"] != "none":
+        if s["score"] != "none" or self.occ_on:   # the render of the tracked pose
             self.image_sc, self.depth_sc, self.bbox_sc = zeros(f32, P, 3, H, W), zeros(f32, P, 1, H, W), zeros(i32, P, 4)
+        if s["score"] != "none":
             self.score_work = ops.pose_score_workspace(P, H, W, d)
             self.score = zeros(f32, P)
         self.flags, self.step_out, self.mean_out = zeros(i32, P), zeros(f32, P, 2), zeros(f32, P, 2)
+        self.visible = self.counts = self.pose_track = None
+        if self.occ_on:
+            self.depth_visible, self.vis_work = zeros(f32, P, 1, H, W), ops.track_visibility_workspace(P, H, W, d)
+            self.visible, self.counts, self.pose_track = zeros(f32, P), zeros(i32, P, 4), zeros(f32, P, 3, 4)
         self.graph = None
         self._want_graph = bool(capture_graph)
 
@@ -141,9 +172,11 @@ class Tracker(object):
         self.ring.zero_()
         self.ring_n.zero_()
         self.ring_pos.zero_()
+        self.occ_age.zero_()
+        self.occluder_ok.fill_(1)
 
     def _state(self):
-        return (self.hist, self.age, self.ring, self.ring_n, self.ring_pos)
+        return (self.hist, self.age, self.ring, self.ring_n, self.ring_pos, self.occ_age, self.occluder_ok)
 
     def _chain(self):
         """one frame, everything enqueued on the current stream from the resident tensors"""
@@ -161,6 +194,9 @@ class Tracker(object):
             ops.fill(last, 0)
         else:
             ops.copy(last, r.stages[s["pose"]].status)
+        if self.occ_on:
+            self._chain_occ(last)
+            return
         if self.score is not None:   # as Refiner._select scores a hypothesis: every drawn pixel of the render inside its box
             r.render_machine.render_batch(b["class_index"], self.pose_new, image=self.image_sc, depth=self.depth_sc, bbox=self.bbox_sc,
                                           plane_means=r.net.plane_means, mask_thr=0.0, status=last)
@@ -172,6 +208,26 @@ class Tracker(object):
                          min_score=s["min_score"], reinit_pose=self.reinit_pose, reinit_valid=self.reinit_valid, flags=self.flags,
                          step=self.step_out, mean=self.mean_out)
 
+    def _chain_occ(self, last):
+        """the end of the chain with occlusion on: the tracked poses' render, which of its pixels are visible, the score over those,
+        and the update with the occluded state"""
+        r, s, occ, b = self.refiner, self.settings, self.occlusion, self.refiner.batch
+        r.render_machine.render_batch(b["class_index"], self.pose_new, image=self.image_sc, depth=self.depth_sc, bbox=self.bbox_sc,
+                                      plane_means=r.net.plane_means, mask_thr=0.0, status=last)
+        # (every row of depth_observed is the frame's depth after the ingest)
+        ops.track_visibility(self.depth_sc, occ["mode"], occ["delta"], depth_frame=self.depth_observed[0, 0] if occ["mode"] != "tracks" else None,
+                             occluder_ok=self.occluder_ok, depth_visible=self.depth_visible, counts=self.counts, workspace=self.vis_work)
+        if self.score is not None:
+            ops.pose_score(b["image_observed"], self.image_sc, self.depth_visible, s["score"], s["depth_tau"],
+                           depth_observed=self.depth_observed if s["score"] == "depth" else None, bbox=self.bbox_sc, score=self.score,
+                           status=last, workspace=self.score_work)
+        ops.track_update_occ(self.pose_before, self.pose_new, self.hist, self.age, self.ring, self.ring_n, self.ring_pos, self.occ_age,
+                             self.counts, occ["min_visible"], occ["max_occluded"], r.pose_init, s["lost_rot_deg"], s["lost_trans"],
+                             self.znear, self.zfar, status_rows=self.status_rows, fatal_mask=FATAL_MASK, score=self.score,
+                             min_score=s["min_score"], reinit_pose=self.reinit_pose, reinit_valid=self.reinit_valid, flags=self.flags,
+                             step=self.step_out, mean=self.mean_out, visible=self.visible, pose_track=self.pose_track,
+                             occluder_ok=self.occluder_ok)
+
     def _stage_inputs(self, frame_bgr, depth_raw, reinit_pose, reinit_valid):
         P = self.P
         frame_bgr = torch.as_tensor(frame_bgr)
@@ -181,7 +237,8 @@ class Tracker(object):
         self.frame_raw.copy_(frame_bgr, non_blocking=True)
         if self.needs_depth:
             if depth_raw is None:
-                raise ValueError("Tracker.step: the configuration (INPUT_DEPTH, TEST.ICP_ITER > 0 or TEST.TRACK_SCORE 'depth') needs depth_raw")
+                raise ValueError("Tracker.step: the configuration (INPUT_DEPTH, TEST.ICP_ITER > 0, TEST.TRACK_SCORE 'depth' or "
+                                 "TEST.TRACK_OCCLUSION 'depth' / 'both') needs depth_raw")
             if isinstance(depth_raw, np.ndarray):
                 depth_raw = torch.from_numpy(np.ascontiguousarray(depth_raw, dtype=np.uint16))
             if tuple(depth_raw.shape) != (self.H, self.W) or depth_raw.dtype != torch.uint16:
@@ -204,7 +261,11 @@ class Tracker(object):
         a pose offered to every track that is lost on this frame (reinit_valid (P,): to which of them; all when omitted).
         -> dict of device views, valid until the next step: pose (P,3,4) the tracked pose of the frame, flags (P,) int32 (the frame's
         status bits, DIM_STATUS_TRACK_LOST / _REINIT among them), step (P,2) the loop's last step (degrees, metres), mean (P,2) its
-        window means, score (P,) or None.  The predicted pose the loop started from stays in refiner.pose_init"""
+        window means, score (P,) or None; with TEST.TRACK_OCCLUSION on also visible (P,) the visible fraction of each track's render,
+        counts (P,4) int32 its pixels {drawn, visible, hidden by a track, hidden by the frame's depth only} and pose_track (P,3,4)
+        the best current estimate (the accepted pose, the coasted prediction of an occluded track -- DIM_STATUS_TRACK_OCCLUDED in
+        flags --, the offered pose, or the last accepted pose of a lost track), else None for the three.  The predicted pose the loop
+        started from stays in refiner.pose_init"""
         self._stage_inputs(frame_bgr, depth_raw, reinit_pose, reinit_valid)
         if self._want_graph and self.graph is None:
             # as Refiner.refine: a warm-up on a side stream (lazy module loads), then the capture -- one stream, kernels only.  The
@@ -226,12 +287,13 @@ class Tracker(object):
             self.graph.replay()
         else:
             self._chain()
-        return {"pose": self.pose_new, "flags": self.flags, "step": self.step_out, "mean": self.mean_out, "score": self.score}
+        return {"pose": self.pose_new, "flags": self.flags, "step": self.step_out, "mean": self.mean_out, "score": self.score,
+                "visible": self.visible, "counts": self.counts, "pose_track": self.pose_track}
 
     def run(self, frames):
         """frames: an iterable of dicts with frame_bgr [, depth_raw, reinit_pose, reinit_valid] (the arguments of step).  Every
         frame's outputs are recorded on the device and read back once at the end -> dict of host arrays (T,P,...): pose, flags, step,
-        mean [, score]"""
+        mean [, score] [, visible, counts, pose_track]"""
         rec = {}
         for f in frames:
             out = self.step(f["frame_bgr"], f.get("depth_raw"), f.get("reinit_pose"), f.get("reinit_valid"))

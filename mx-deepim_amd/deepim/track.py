@@ -1,7 +1,10 @@
 """Tracking entry point:
     python deepim/track.py --cfg experiments/deepim/cfgs/deepim_hip_LM_ape_track.yaml --gpus 0 --num_frames 60 --num_objects 3 [--reinit_from_gt]
+        [--occluder]
 Follows the objects of a seeded synthetic video (lib/dataset/synthetic_sequences.py) with deepim.core.tracker.Tracker and prints, per
-object, the frames tracked and lost, the re-initialisations and the mean ADD over the tracked frames, and the frames per second.
+object, the frames tracked and lost, the re-initialisations, the mean ADD over the tracked frames and the frames it was occluded
+(TEST.TRACK_OCCLUSION on: deepim_hip_LM_ape_track_occ.yaml), and the frames per second.  --occluder puts an untracked object in
+front of object 0 for the middle third of the video.
 The weights are found as deepim/test.py finds them: `<prefix>-<test_epoch>.params` of the training run, else the seeded
 initialisation (stated in the log).  --reinit_from_gt offers the ground-truth pose to every lost track (stands in for a detector)."""
 from __future__ import print_function, division
@@ -27,23 +30,27 @@ def parse_args():
     parser.add_argument("--num_objects", help="objects followed through it", default=3, type=int)
     parser.add_argument("--subdiv", help="icosphere subdivisions of the synthetic meshes (4 = 5120 triangles)", default=4, type=int)
     parser.add_argument("--reinit_from_gt", help="offer the ground-truth pose to every lost track", action="store_true")
+    parser.add_argument("--occluder", help="an untracked object 0.35 m in front of object 0 for the middle third of the frames",
+                        action="store_true")
     return parser.parse_args()
 
 
 def track_table(out, pose_gt, class_index, models, class_names):
-    """-> [dict(object, cls, tracked, lost, reinit, add)] from Tracker.run's host arrays and the ground truth (T,P,3,4)"""
+    """-> [dict(object, cls, tracked, lost, reinit, add, occluded)] from Tracker.run's host arrays and the ground truth (T,P,3,4);
+    occluded: the frames with DIM_STATUS_TRACK_OCCLUDED (coasting ones count as tracked, with the coasted pose's ADD)"""
     from lib.hip import ops
     from lib.utils import pose_error
 
     rows = []
-    flags, pose = out["flags"], out["pose"].astype(np.float64)
+    flags, pose = out["flags"], out.get("pose_track", out["pose"]).astype(np.float64)   # the best estimate where there is one
     for p in range(flags.shape[1]):
         lost = (flags[:, p] & ops.STATUS_TRACK_LOST) != 0
         pts = models[int(class_index[p])][0].astype(np.float64)
         adds = [pose_error.add(pose[t, p, :, :3], pose[t, p, :, 3], pose_gt[t, p, :, :3].astype(np.float64), pose_gt[t, p, :, 3].astype(np.float64),
                                pts) for t in range(flags.shape[0]) if not lost[t]]
         rows.append(dict(object=p, cls=class_names[int(class_index[p])], tracked=int((~lost).sum()), lost=int(lost.sum()),
-                         reinit=int(((flags[:, p] & ops.STATUS_TRACK_REINIT) != 0).sum()), add=float(np.mean(adds)) if adds else float("nan")))
+                         reinit=int(((flags[:, p] & ops.STATUS_TRACK_REINIT) != 0).sum()), add=float(np.mean(adds)) if adds else float("nan"),
+                         occluded=int(((flags[:, p] & ops.STATUS_TRACK_OCCLUDED) != 0).sum())))
     return rows
 
 
@@ -53,7 +60,7 @@ def track_deepim(args):
     from deepim.core.tester import Predictor
     from deepim.core.tracker import Tracker
     from deepim.symbols import deepIM_flownet as symbols
-    from lib.dataset.synthetic_sequences import SyntheticSequence
+    from lib.dataset.synthetic_sequences import SyntheticSequence, sequence_poses
     from lib.utils.create_logger import create_logger
     from lib.utils.load_model import load_param
 
@@ -77,7 +84,11 @@ def track_deepim(args):
     arg_params = sym_instance.init_weights(config, arg_params, {}, seed=0)
 
     P, T = args.num_objects, args.num_frames
-    seq = SyntheticSequence(config, T, P, 2333, device=device, subdiv=args.subdiv)
+    events = []
+    if args.occluder:   # of object 0's class, centred on it
+        cls0 = int(sequence_poses(T, P, 2333, n_classes=len(config.dataset.class_name))[0][0])
+        events.append(("occluder", T // 3, 2 * T // 3, 0, 0.35, 0.0, cls0))
+    seq = SyntheticSequence(config, T, P, 2333, device=device, events=events, subdiv=args.subdiv)
     predictor = Predictor(config, arg_params, P, device=device)
     tracker = Tracker(config, predictor, seq.render_machine, P, capture_graph=True)
     tracker.reset(seq.class_index, seq.pose_start[1], pose_prev=seq.pose_start[0])
@@ -91,9 +102,9 @@ def track_deepim(args):
     t2 = time.time()
     out = first if rest is None else {k: np.concatenate([first[k], rest[k]]) for k in first}
     rows = track_table(out, seq.pose_gt, seq.class_index, seq.models, seq.classes)
-    print("object  class  tracked  lost  reinit  mean ADD (m)")
+    print("object  class  tracked  lost  reinit  mean ADD (m)  occluded")
     for r in rows:
-        print("{object:6d}  {cls:>5s}  {tracked:7d}  {lost:4d}  {reinit:6d}  {add:.5f}".format(**r))
+        print("{object:6d}  {cls:>5s}  {tracked:7d}  {lost:4d}  {reinit:6d}  {add:12.5f}  {occluded:8d}".format(**r))
     fps = (T - 1) / (t2 - t1) if T > 1 else float("nan")
     print("tracked {} objects through {} frames x {} iterations on {}: {:.1f} frames/s after the first frame ({:.2f} s, with the graph "
           "capture)".format(P, T, config.TEST.test_iter, device, fps, t1 - t0))

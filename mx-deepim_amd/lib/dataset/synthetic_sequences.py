@@ -7,6 +7,10 @@ Trajectories: constant angular velocity in the camera frame, R_k = exp(k [w]) R_
 linear in k -- the motion dim_track_predict's "velocity" model with damping 1 extrapolates exactly.  Events break them on purpose:
     ("teleport", frame, object, du_px, dv_px)   from `frame` on the object's projected centre is shifted by that many pixels
     ("leave", frame, object)                    from `frame` on the object is outside the image
+    ("occluder", frame0, frame1, object, dz, du_px, class)
+                                                an untracked extra object in frames [frame0, frame1): of class `class`, at a fixed
+                                                rotation, dz metres nearer than `object` and its projected centre du_px pixels beside
+                                                the object's.  No trajectory changes, and sequence_poses ignores it
 """
 import numpy as np
 import torch
@@ -14,6 +18,7 @@ import torch
 from lib.utils import synthetic as syn
 
 LEAD = 2   # poses in front of frame 0: what Tracker.reset(pose, pose_prev) wants
+MAX_LAYERS = 16   # dim_scene_compose's layers per scene: the tracked objects and the occluders of a frame share them
 
 
 def _so3_exp(w):
@@ -49,14 +54,32 @@ def sequence_poses(num_frames, num_objects, seed, K=syn.LINEMOD_K, W=640, H=480,
                     shift += (float(ev[3]), float(ev[4]))
                 elif ev[0] == "leave" and int(ev[2]) == j and k - LEAD >= int(ev[1]):
                     shift += (2.0 * W, 0.0)
-                elif ev[0] not in ("teleport", "leave"):
-                    raise ValueError("SyntheticSequence: unknown event {!r} (teleport | leave)".format(ev[0]))
+                elif ev[0] not in ("teleport", "leave", "occluder"):
+                    raise ValueError("SyntheticSequence: unknown event {!r} (teleport | leave | occluder)".format(ev[0]))
             u = (px[0] + k * dpx[0] + shift[0] - K[0, 2]) / K[0, 0]
             v = (px[1] + k * dpx[1] + shift[1] - K[1, 2]) / K[1, 1]
             z = z0 * zr ** k
             poses[k, j, :, :3] = _so3_exp(k * w) @ R0
             poses[k, j, :, 3] = (u * z, v * z, z)
     return cls, poses.astype(np.float32)
+
+
+def occluder_layers(events, t, pose_gt_t, K, seed=0):
+    """the occluder events active in frame t -> (class (n,) int32, pose (n,3,4) float32), from the frame's ground-truth poses
+    (P,3,4).  An occluder's rotation is fixed over its frames (seeded by its place in `events`)"""
+    K = np.asarray(K, np.float64).reshape(3, 3)
+    cls, poses = [], []
+    for i, ev in enumerate(events):
+        if ev[0] != "occluder" or not int(ev[1]) <= t < int(ev[2]):
+            continue
+        obj = np.asarray(pose_gt_t[int(ev[3])], np.float64)
+        z = obj[2, 3] - float(ev[4])
+        u = obj[0, 3] / obj[2, 3] + float(ev[5]) / K[0, 0]
+        v = obj[1, 3] / obj[2, 3]
+        R = syn.random_rotation(np.random.default_rng([int(seed), 101, i]))
+        poses.append(np.concatenate([R, np.array([[u * z], [v * z], [z]])], axis=1))
+        cls.append(int(ev[6]))
+    return np.asarray(cls, np.int32), np.asarray(poses, np.float32).reshape(-1, 3, 4)
 
 
 def background(seed, H, W, cell=4):
@@ -85,6 +108,15 @@ class SyntheticSequence(object):
                                                       n_classes=len(self.classes), events=self.events)
         self.pose_gt = self.poses[LEAD:]        # (T,P,3,4): the pose of every object in every frame
         self.pose_start = self.poses[:LEAD]     # (2,P,3,4): the two poses before frame 0, oldest first
+        for ev in self.events:
+            if ev[0] == "occluder" and not (0 <= int(ev[3]) < self.P and 0 <= int(ev[6]) < len(self.classes)):
+                raise ValueError("SyntheticSequence: occluder event {!r} names an object outside 0..{} or a class outside 0..{}".format(
+                    ev, self.P - 1, len(self.classes) - 1))
+        for t in range(self.num_frames):
+            n = self.P + len(occluder_layers(self.events, t, self.pose_gt[t], self.K, seed)[0])
+            if n > MAX_LAYERS:
+                raise ValueError("SyntheticSequence: {} tracks and occluders in frame {}: dim_scene_compose takes {} layers".format(
+                    n, t, MAX_LAYERS))
         self._models = self._rm = self._bg = None
 
     def __len__(self):
@@ -116,12 +148,18 @@ class SyntheticSequence(object):
             self._bg = torch.from_numpy(background(self.seed + 7, H, W)).to(d)
             self._cls = torch.from_numpy(self.class_index).to(d)
         pose = torch.from_numpy(np.ascontiguousarray(self.pose_gt[t])).to(d)
-        layer_bgr = torch.empty((P, H, W, 3), device=d)
-        layer_depth = torch.empty((P, 1, H, W), device=d)
-        rm.render_batch(self._cls, pose, bgr=layer_bgr, depth=layer_depth)
+        cls, layer_pose, S = self._cls, pose, P
+        occ_cls, occ_pose = occluder_layers(self.events, t, self.pose_gt[t], self.K, self.seed)
+        if len(occ_cls):   # untracked extra layers behind the tracked ones
+            cls = torch.cat([cls, torch.from_numpy(occ_cls).to(d)])
+            layer_pose = torch.cat([pose, torch.from_numpy(occ_pose).to(d)])
+            S = P + len(occ_cls)
+        layer_bgr = torch.empty((S, H, W, 3), device=d)
+        layer_depth = torch.empty((S, 1, H, W), device=d)
+        rm.render_batch(cls, layer_pose, bgr=layer_bgr, depth=layer_depth)
         scene_bgr = torch.empty((1, H, W, 3), device=d)
         scene_depth = torch.empty((1, 1, H, W), device=d)
-        ops.scene_compose(layer_bgr, layer_depth, self._cls + 1, P, scene_bgr=scene_bgr, scene_depth=scene_depth)
+        ops.scene_compose(layer_bgr, layer_depth, cls + 1, S, scene_bgr=scene_bgr, scene_depth=scene_depth)
         drawn = scene_depth[0, 0] > 0
         bgr = torch.where(drawn[..., None], scene_bgr[0].round().clamp(0, 255).to(torch.uint8), self._bg).contiguous()
         mm = (scene_depth[0, 0] * self.depth_factor).round().clamp(0, 32767).to(torch.int16)   # (no uint16 arithmetic: the same bytes)

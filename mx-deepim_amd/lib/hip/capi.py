@@ -63,6 +63,9 @@ SIGNATURES = {
     "dim_track_ingest": (I, [P, P, I, I, I, F, P, P, P, P]),
     "dim_track_predict": (I, [P, P, I, I, F, P, P]),
     "dim_track_update": (I, [P, P, P, I, I, P, F, P, P, F, F, I, F, F, I, P, P, P, P, P, P, P, P, P]),
+    "dim_track_visibility_workspace_bytes": (L, [I, I, I]),
+    "dim_track_visibility": (I, [P, P, P, I, I, I, I, F, P, P, P, P]),
+    "dim_track_update_occ": (I, [P, P, P, I, I, P, F, P, P, F, F, I, F, F, I, P, F, I, P, P, P, P, P, P, P, P, P, P, P, P, P, P]),
     "dim_pose_from_box": (I, [P, P, I, P, P, P, P, P, I, I, I, D, P, P, P, P]),
     "dim_pose_score_indexed": (I, [P, P, P, P, P, P, I, I, I, I, I, F, P, P, P, P]),
     "dim_hyp_topk": (I, [P, P, I, I, I, I, P, P, P, P, P, P]),

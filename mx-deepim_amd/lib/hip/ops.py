@@ -600,7 +600,75 @@ def track_update(pose_before, pose_new, hist, age, ring, ring_n, ring_pos, lost_
     return flags, step, mean
 
 
-STATUS_COARSE_BAD_BOX = 512   # DIM_STATUS_COARSE_BAD_BOX: dim_pose_from_box gave the candidate its fallback row
+STATUS_TRACK_OCCLUDED = 16384   # DIM_STATUS_TRACK_OCCLUDED: dim_track_update_occ saw too little of the track's render
+TRACK_OCC_MODE = {"tracks": 1, "depth": 2, "both": 3}   # DIM_TRACK_OCC_TRACKS | DIM_TRACK_OCC_DEPTH
+
+
+def track_visibility_workspace(P, H, W, device):
+    return torch.empty((max(lib().dim_track_visibility_workspace_bytes(P, H, W), 4) // 4,), dtype=i32, device=device)
+
+
+def track_visibility(depth_rendered, mode, delta, depth_frame=None, occluder_ok=None, depth_visible=None, counts=None, workspace=None):
+    """dim_track_visibility (restated by tests/track_occ_reference.py): depth_rendered (P,1,H,W), the renders of P tracks at one camera
+    -> depth_visible (P,1,H,W), the render with the pixels zeroed that another track ("tracks": one whose occluder_ok (P,) int32 entry is
+    not 0) or the frame's depth ("depth": depth_frame (H,W) metres, 0 = no reading) hides by more than delta metres ("both": either),
+    and counts (P,4) int32 = {drawn, visible, hidden by a track, hidden by the frame's depth only}"""
+    P, _, H, W = depth_rendered.shape
+    if mode not in TRACK_OCC_MODE:
+        raise ValueError("track occlusion mode must be 'tracks', 'depth' or 'both', got {!r}".format(mode))
+    if TRACK_OCC_MODE[mode] & 2 and depth_frame is None:
+        raise ValueError("track occlusion mode {!r} needs depth_frame".format(mode))
+    assert tuple(depth_rendered.shape) == (P, 1, H, W) and (depth_frame is None or tuple(depth_frame.shape) == (H, W))
+    assert occluder_ok is None or occluder_ok.numel() == P
+    depth_visible = depth_visible if depth_visible is not None else _new((P, 1, H, W), depth_rendered)
+    counts = counts if counts is not None else _new((P, 4), depth_rendered, i32)
+    assert tuple(depth_visible.shape) == (P, 1, H, W) and counts.numel() == 4 * P
+    if workspace is None:
+        workspace = track_visibility_workspace(P, H, W, depth_rendered.device)
+    assert workspace.numel() * workspace.element_size() >= lib().dim_track_visibility_workspace_bytes(P, H, W)
+    check(lib().dim_track_visibility(dptr(depth_rendered, f32), _opt(depth_frame), _opt(occluder_ok, i32), P, H, W, TRACK_OCC_MODE[mode],
+                                     float(delta), dptr(workspace), dptr(depth_visible, f32), dptr(counts, i32), current_stream()))
+    return depth_visible, counts
+
+
+def track_update_occ(pose_before, pose_new, hist, age, ring, ring_n, ring_pos, occ_age, counts, min_visible, max_occluded, pose_pred,
+                     lost_rot_deg, lost_trans_m, znear, zfar, status_rows=None, fatal_mask=0, score=None, min_score=0.0, reinit_pose=None,
+                     reinit_valid=None, flags=None, step=None, mean=None, visible=None, pose_track=None, occluder_ok=None):
+    """dim_track_update_occ (restated by tests/track_occ_reference.py): track_update with an occluded state.  counts (P,4) int32 of
+    track_visibility for the render of pose_new; a track of which less than min_visible is visible takes pose_pred (P,3,4), the pose
+    the frame started from, for at most max_occluded frames in a row (state occ_age (P,) int32) instead of being lost.
+    -> flags (STATUS_TRACK_OCCLUDED among them), step, mean, visible (P,) f32, pose_track (P,3,4) = hist[:, 1] after the update,
+    occluder_ok (P,) int32: 0 for a track that is lost and not re-initialised"""
+    P, Wn = ring.shape[0], ring.shape[1]
+    assert tuple(pose_before.shape) == (P, 3, 4) and tuple(pose_new.shape) == (P, 3, 4) and tuple(hist.shape) == (P, 2, 3, 4)
+    assert tuple(ring.shape) == (P, Wn, 2) and age.numel() == P and ring_n.numel() == P and ring_pos.numel() == P and occ_age.numel() == P
+    assert counts.numel() == 4 * P and tuple(pose_pred.shape) == (P, 3, 4)
+    n_rows = 0
+    if status_rows is not None:
+        assert status_rows.numel() % P == 0
+        n_rows = status_rows.numel() // P
+    assert score is None or score.numel() == P
+    assert (reinit_pose is None) == (reinit_valid is None)
+    assert reinit_pose is None or (tuple(reinit_pose.shape) == (P, 3, 4) and reinit_valid.numel() == P)
+    flags = flags if flags is not None else _new((P,), hist, i32)
+    step = step if step is not None else _new((P, 2), hist)
+    mean = mean if mean is not None else _new((P, 2), hist)
+    visible = visible if visible is not None else _new((P,), hist)
+    pose_track = pose_track if pose_track is not None else _new((P, 3, 4), hist)
+    occluder_ok = occluder_ok if occluder_ok is not None else _new((P,), hist, i32)
+    assert flags.numel() == P and step.numel() == 2 * P and mean.numel() == 2 * P
+    assert visible.numel() == P and tuple(pose_track.shape) == (P, 3, 4) and occluder_ok.numel() == P
+    check(lib().dim_track_update_occ(dptr(pose_before, f32), dptr(pose_new, f32), _opt(status_rows, i32), n_rows, int(fatal_mask),
+                                     _opt(score), float(min_score), _opt(reinit_pose), _opt(reinit_valid, i32), float(lost_rot_deg),
+                                     float(lost_trans_m), int(Wn), float(znear), float(zfar), P, dptr(counts, i32), float(min_visible),
+                                     int(max_occluded), dptr(pose_pred, f32), dptr(hist, f32), dptr(age, i32), dptr(ring, f32),
+                                     dptr(ring_n, i32), dptr(ring_pos, i32), dptr(occ_age, i32), dptr(flags, i32), dptr(step, f32),
+                                     dptr(mean, f32), dptr(visible, f32), dptr(pose_track, f32), dptr(occluder_ok, i32),
+                                     current_stream()))
+    return flags, step, mean, visible, pose_track, occluder_ok
+
+
+STATUS_COARSE_BAD_BOX = 512  # DIM_STATUS_COARSE_BAD_BOX: dim_pose_from_box gave the candidate its fallback row
 HYP_TOPK_MAX = 64             # dim_hyp_topk: the largest k
 
 
