@@ -450,9 +450,10 @@ int dim_track_update(const float* pose_before, const float* pose_new, const int*
  *   16-byte accesses when W % 4 == 0 and depth_rendered, depth_visible and depth_frame are 16-byte aligned.  2 launches.
  *   P, H or W <= 0, mode 0 or with an unknown bit, DIM_TRACK_OCC_DEPTH with a NULL depth_frame, a negative or non-finite delta or a
  *   NULL required pointer return DIM_ERR_ARG before anything is enqueued.
- * dim_track_update_occ: dim_track_update with an occluded state.  Additional inputs: counts (P,4) of dim_track_visibility for the
- *   render of pose_new, min_visible in [0,1], max_occluded >= 0, pose_pred (P,3,4) the pose the frame started from; additional state
- *   occ_age (P) int32: the frames the track has coasted in a row.  Per track, in this order:
+ * dim_track_update_occ: dim_track_update with an occluded state: the same kernel body, in which rules 1 to 6 stand once, built a second
+ *   time with the state in front of rules 2 to 6.  Additional inputs: counts (P,4) of dim_track_visibility for the render of pose_new,
+ *   min_visible in [0,1], max_occluded >= 0, pose_pred (P,3,4) the pose the frame started from; additional state occ_age (P) int32: the
+ *   frames the track has coasted in a row.  Per track, in this order:
  *   a. step as in rule 1.  fatal = the first three clauses of rule 3 (a fatal status bit, a non-finite pose_new, t_z out of range).
  *   b. visible[p] = float(double(counts[1]) / double(counts[0])), 0 when nothing is drawn.
  *      occluded = not fatal, counts[0] > 0 and double(counts[1]) < double(min_visible) * counts[0].

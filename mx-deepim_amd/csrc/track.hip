@@ -6,14 +6,18 @@
 //                          pair_blobs_from_raw_kernel (data.hip): plane c = bgr[2 - c] - mean[2 - c], depth = __fdiv_rn(raw, factor)
 //   track_predict_kernel   one lane per track: the pose the frame starts from, from the last two accepted poses (hold / damped
 //                          constant velocity), float64 inside, one rounding to float32
-//   track_update_kernel    one lane per track: the last iteration's step into a ring, its window means, the lost test, and the
-//                          history / re-initialisation state machine.  Every pose written into the history is a bit-for-bit copy
+//   track_update_kernel<OCC>  one lane per track: the last iteration's step into a ring, its window means, the lost test, and the
+//                          history / re-initialisation state machine.  Every pose written into the history is a bit-for-bit copy.
+//                          The rules stand once, numbered as in deepim_hip.h.  OCC = false is dim_track_update.  OCC = true is
+//                          dim_track_update_occ: an "occluded" state in front of rules 2 to 6 -- a track of which too little is
+//                          visible coasts on the predicted pose, within a budget of frames, instead of being lost -- and a track
+//                          that is not occluded takes the same statements, so min_visible = 0 gives the bits of OCC = false.  Each
+//                          entry is pinned on its own: tests/track_reference.py (false), tests/track_occ_reference.py (true)
 //   track_visibility_kernel  occlusion between the tracks and against the frame's depth: one lane per 4 (or 1) pixels, P the inner
 //                          loop.  Each render is read (twice when tracks hide tracks: the two smallest depths first) and written
 //                          once with its hidden pixels zeroed -- a depth plane dim_pose_score takes as it is -- and the pixel counts
-//                          leave as one packed word per (wave, track); track_visibility_finish adds them: integers, no atomics
-//   track_update_occ_kernel  track_update_kernel with an "occluded" state: a track of which too little is visible coasts on the
-//                          predicted pose, within a budget of frames, instead of being lost.  Restated by tests/track_occ_reference.py
+//                          leave as one packed word per (wave, track); track_visibility_finish adds them: integers, no atomics.
+//                          Restated by tests/track_occ_reference.py
 // Nothing allocates or synchronises: every entry is graph-capturable.
 #include "common.h"
 #include "twist_solve.h"
@@ -160,8 +164,18 @@ struct TrackUpdateArgs {
   int* flags;
   float* step;
   float* mean;
+  // dim_track_update_occ only (null / 0 otherwise: OCC = false reads and writes none of them)
+  const int* counts;
+  float min_visible;
+  int max_occluded;
+  const float* pose_pred;
+  int* occ_age;
+  float* visible;
+  float* pose_track;
+  int* occluder_ok;
 };
 
+template <bool OCC>
 __global__ __launch_bounds__(64) void track_update_kernel(TrackUpdateArgs a) {
   const int p = blockIdx.x * blockDim.x + threadIdx.x;
   if (p >= a.P) return;
@@ -179,54 +193,91 @@ __global__ __launch_bounds__(64) void track_update_kernel(TrackUpdateArgs a) {
   double step_trans = sqrt(dx * dx + dy * dy + dz * dz);
   if (!isfinite(step_rot)) step_rot = INFINITY;
   if (!isfinite(step_trans)) step_trans = INFINITY;
-  // 2. into the ring over its oldest entry; the means over the ring's entries as they are stored, oldest first
+  a.step[2 * p] = (float)step_rot;
+  a.step[2 * p + 1] = (float)step_trans;
+  // the fatal clauses of 3.: with them there is nothing to judge a visibility on
+  bool lost = (status & a.fatal_mask) != 0 || !pose_finite(Tn);
+  lost = lost || !(Tn[11] >= a.znear && Tn[11] <= a.zfar);
+  bool occluded = false;   // too little of the drawn render is visible
+  if (OCC) {
+    const int drawn = a.counts[4 * p], seen = a.counts[4 * p + 1];
+    a.visible[p] = drawn > 0 ? (float)((double)seen / (double)drawn) : 0.f;
+    occluded = !lost && drawn > 0 && (double)seen < (double)a.min_visible * (double)drawn;
+  }
   float* ring = a.ring + 2L * Wn * p;
   int pos = a.ring_pos[p], n = a.ring_n[p];
   if (pos < 0 || pos >= Wn) pos = 0;
   n = min(max(n, 0), Wn);
-  ring[2 * pos] = (float)step_rot;
-  ring[2 * pos + 1] = (float)step_trans;
-  pos = pos + 1 == Wn ? 0 : pos + 1;
-  n = min(n + 1, Wn);
+  float* h0 = a.hist + 24L * p;
+  float* h1 = h0 + 12;
+  int age = min(max(a.age[p], 0), 2);
+  int occ_age = OCC ? max(a.occ_age[p], 0) : 0;
+  bool reinit = false;
+  if (!occluded) {
+    // 2. into the ring over its oldest entry
+    ring[2 * pos] = (float)step_rot;
+    ring[2 * pos + 1] = (float)step_trans;
+    pos = pos + 1 == Wn ? 0 : pos + 1;
+    n = min(n + 1, Wn);
+  }
+  // the means over the ring's entries as they are stored, oldest first (an occluded track: of what was stored before, 0 of nothing)
   double sum_rot = 0.0, sum_trans = 0.0;
   for (int k = 0; k < n; ++k) {
     const int q = (pos - n + k + Wn) % Wn;
     sum_rot += (double)ring[2 * q];
     sum_trans += (double)ring[2 * q + 1];
   }
-  const double mean_rot = sum_rot / n, mean_trans = sum_trans / n;
-  a.step[2 * p] = (float)step_rot;
-  a.step[2 * p + 1] = (float)step_trans;
+  const bool some = !OCC || n > 0;   // only an occluded track's ring can hold nothing here
+  const double mean_rot = some ? sum_rot / n : 0.0, mean_trans = some ? sum_trans / n : 0.0;
   a.mean[2 * p] = (float)mean_rot;
   a.mean[2 * p + 1] = (float)mean_trans;
-  // 3. lost?
-  bool lost = (status & a.fatal_mask) != 0 || !pose_finite(Tn);
-  lost = lost || !(Tn[11] >= a.znear && Tn[11] <= a.zfar);
-  if (a.score) lost = lost || !(a.score[p] >= a.min_score);
-  if (n == Wn) lost = lost || mean_rot > (double)a.lost_rot_deg || mean_trans > (double)a.lost_trans_m;
-  float* h0 = a.hist + 24L * p;
-  float* h1 = h0 + 12;
-  int age = min(max(a.age[p], 0), 2);
-  if (!lost) {                                              // 4. accepted
-    for (int k = 0; k < 12; ++k) h0[k] = h1[k];
-    for (int k = 0; k < 12; ++k) h1[k] = Tn[k];
-    age = min(age + 1, 2);
-  } else if (a.reinit_valid && a.reinit_pose && a.reinit_valid[p] != 0) {   // 5. lost, a pose is offered
-    const float* Tr = a.reinit_pose + 12L * p;
-    for (int k = 0; k < 12; ++k) h1[k] = Tr[k];
-    age = 1;
-    for (int k = 0; k < 2 * Wn; ++k) ring[k] = 0.f;
-    n = 0;
-    pos = 0;
-    status |= DIM_STATUS_TRACK_LOST | DIM_STATUS_TRACK_REINIT;
-  } else {                                                  // 6. lost, nothing offered: the last accepted pose, no velocity
-    age = min(age, 1);
-    status |= DIM_STATUS_TRACK_LOST;
+  bool coast = false;
+  if (occluded) {
+    const float* Tp = a.pose_pred + 12L * p;
+    coast = occ_age < a.max_occluded && pose_finite(Tp) && Tp[11] >= a.znear && Tp[11] <= a.zfar;
+    status |= DIM_STATUS_TRACK_OCCLUDED;
+    if (coast) {   // hidden, within the budget: the motion model's pose is the frame's pose
+      for (int k = 0; k < 12; ++k) h0[k] = h1[k];
+      for (int k = 0; k < 12; ++k) h1[k] = Tp[k];
+      age = min(age + 1, 2);
+      occ_age += 1;
+    } else {
+      lost = true;
+    }
+  } else {
+    // 3. lost?
+    if (a.score) lost = lost || !(a.score[p] >= a.min_score);
+    if (n == Wn) lost = lost || mean_rot > (double)a.lost_rot_deg || mean_trans > (double)a.lost_trans_m;
+  }
+  if (!coast) {
+    occ_age = 0;
+    if (!lost) {                                              // 4. accepted
+      for (int k = 0; k < 12; ++k) h0[k] = h1[k];
+      for (int k = 0; k < 12; ++k) h1[k] = Tn[k];
+      age = min(age + 1, 2);
+    } else if (a.reinit_valid && a.reinit_pose && a.reinit_valid[p] != 0) {   // 5. lost, a pose is offered
+      const float* Tr = a.reinit_pose + 12L * p;
+      for (int k = 0; k < 12; ++k) h1[k] = Tr[k];
+      age = 1;
+      for (int k = 0; k < 2 * Wn; ++k) ring[k] = 0.f;
+      n = 0;
+      pos = 0;
+      reinit = true;
+      status |= DIM_STATUS_TRACK_LOST | DIM_STATUS_TRACK_REINIT;
+    } else {                                                  // 6. lost, nothing offered: the last accepted pose, no velocity
+      age = min(age, 1);
+      status |= DIM_STATUS_TRACK_LOST;
+    }
+    a.ring_n[p] = n;
+    a.ring_pos[p] = pos;
   }
   a.age[p] = age;
-  a.ring_n[p] = n;
-  a.ring_pos[p] = pos;
   a.flags[p] = status;
+  if (OCC) {
+    a.occ_age[p] = occ_age;
+    for (int k = 0; k < 12; ++k) a.pose_track[12L * p + k] = h1[k];
+    a.occluder_ok[p] = (lost && !reinit) ? 0 : 1;
+  }
 }
 
 // ---- occlusion: which drawn pixels of each track's render does another track, or the frame's own depth, hide
@@ -346,119 +397,6 @@ __global__ __launch_bounds__(kWave) void track_visibility_finish(const unsigned*
   }
 }
 
-struct TrackOccArgs {
-  TrackUpdateArgs u;
-  const int* counts;
-  float min_visible;
-  int max_occluded;
-  const float* pose_pred;
-  int* occ_age;
-  float* visible;
-  float* pose_track;
-  int* occluder_ok;
-};
-
-// track_update_kernel with the occluded state in front of its rules 2 to 6 (deepim_hip.h).  A track that is not occluded takes
-// those rules as they stand there, statement by statement, so that min_visible = 0 gives the bits of dim_track_update.
-__global__ __launch_bounds__(64) void track_update_occ_kernel(TrackOccArgs o) {
-  const TrackUpdateArgs& a = o.u;
-  const int p = blockIdx.x * blockDim.x + threadIdx.x;
-  if (p >= a.P) return;
-  const int Wn = a.Wn;
-  const float* Tb = a.pose_before + 12L * p;
-  const float* Tn = a.pose_new + 12L * p;
-  int status = 0;
-  for (int r = 0; r < a.n_rows; ++r) status |= a.status_rows[(long)r * a.P + p];
-  // 1. the step of the loop's last iteration
-  double D[9], v[3], s, c;
-  rel_rotation(Tn, Tb, D);
-  rotation_sin_cos(D, v, &s, &c);
-  double step_rot = atan2(s, c) * (180.0 / 3.14159265358979323846);
-  const double dx = (double)Tn[3] - (double)Tb[3], dy = (double)Tn[7] - (double)Tb[7], dz = (double)Tn[11] - (double)Tb[11];
-  double step_trans = sqrt(dx * dx + dy * dy + dz * dz);
-  if (!isfinite(step_rot)) step_rot = INFINITY;
-  if (!isfinite(step_trans)) step_trans = INFINITY;
-  a.step[2 * p] = (float)step_rot;
-  a.step[2 * p + 1] = (float)step_trans;
-  // fatal: nothing to judge a visibility on; occluded: too little of the drawn render is visible
-  bool lost = (status & a.fatal_mask) != 0 || !pose_finite(Tn);
-  lost = lost || !(Tn[11] >= a.znear && Tn[11] <= a.zfar);
-  const int drawn = o.counts[4 * p], seen = o.counts[4 * p + 1];
-  o.visible[p] = drawn > 0 ? (float)((double)seen / (double)drawn) : 0.f;
-  const bool occluded = !lost && drawn > 0 && (double)seen < (double)o.min_visible * (double)drawn;
-  float* ring = a.ring + 2L * Wn * p;
-  int pos = a.ring_pos[p], n = a.ring_n[p];
-  if (pos < 0 || pos >= Wn) pos = 0;
-  n = min(max(n, 0), Wn);
-  float* h0 = a.hist + 24L * p;
-  float* h1 = h0 + 12;
-  int age = min(max(a.age[p], 0), 2);
-  int occ_age = max(o.occ_age[p], 0);
-  bool reinit = false;
-  if (!occluded) {
-    // 2. into the ring over its oldest entry
-    ring[2 * pos] = (float)step_rot;
-    ring[2 * pos + 1] = (float)step_trans;
-    pos = pos + 1 == Wn ? 0 : pos + 1;
-    n = min(n + 1, Wn);
-  }
-  // the means over the ring's entries as they are stored, oldest first (an occluded track: of what was stored before, 0 of nothing)
-  double sum_rot = 0.0, sum_trans = 0.0;
-  for (int k = 0; k < n; ++k) {
-    const int q = (pos - n + k + Wn) % Wn;
-    sum_rot += (double)ring[2 * q];
-    sum_trans += (double)ring[2 * q + 1];
-  }
-  const double mean_rot = n > 0 ? sum_rot / n : 0.0, mean_trans = n > 0 ? sum_trans / n : 0.0;
-  a.mean[2 * p] = (float)mean_rot;
-  a.mean[2 * p + 1] = (float)mean_trans;
-  bool coast = false;
-  if (occluded) {
-    const float* Tp = o.pose_pred + 12L * p;
-    coast = occ_age < o.max_occluded && pose_finite(Tp) && Tp[11] >= a.znear && Tp[11] <= a.zfar;
-    status |= DIM_STATUS_TRACK_OCCLUDED;
-    if (coast) {   // hidden, within the budget: the motion model's pose is the frame's pose
-      for (int k = 0; k < 12; ++k) h0[k] = h1[k];
-      for (int k = 0; k < 12; ++k) h1[k] = Tp[k];
-      age = min(age + 1, 2);
-      occ_age += 1;
-    } else {
-      lost = true;
-    }
-  } else {
-    // 3. lost?
-    if (a.score) lost = lost || !(a.score[p] >= a.min_score);
-    if (n == Wn) lost = lost || mean_rot > (double)a.lost_rot_deg || mean_trans > (double)a.lost_trans_m;
-  }
-  if (!coast) {
-    occ_age = 0;
-    if (!lost) {                                              // 4. accepted
-      for (int k = 0; k < 12; ++k) h0[k] = h1[k];
-      for (int k = 0; k < 12; ++k) h1[k] = Tn[k];
-      age = min(age + 1, 2);
-    } else if (a.reinit_valid && a.reinit_pose && a.reinit_valid[p] != 0) {   // 5. lost, a pose is offered
-      const float* Tr = a.reinit_pose + 12L * p;
-      for (int k = 0; k < 12; ++k) h1[k] = Tr[k];
-      age = 1;
-      for (int k = 0; k < 2 * Wn; ++k) ring[k] = 0.f;
-      n = 0;
-      pos = 0;
-      reinit = true;
-      status |= DIM_STATUS_TRACK_LOST | DIM_STATUS_TRACK_REINIT;
-    } else {                                                  // 6. lost, nothing offered: the last accepted pose, no velocity
-      age = min(age, 1);
-      status |= DIM_STATUS_TRACK_LOST;
-    }
-    a.ring_n[p] = n;
-    a.ring_pos[p] = pos;
-  }
-  a.age[p] = age;
-  a.flags[p] = status;
-  o.occ_age[p] = occ_age;
-  for (int k = 0; k < 12; ++k) o.pose_track[12L * p + k] = h1[k];
-  o.occluder_ok[p] = (lost && !reinit) ? 0 : 1;
-}
-
 }  // namespace dim
 
 using namespace dim;
@@ -488,19 +426,43 @@ extern "C" int dim_track_predict(const float* hist, const int* age, int P, int m
   return check_launch("track_predict");
 }
 
+static TrackUpdateArgs track_update_args(const float* pose_before, const float* pose_new, const int* status_rows, int n_rows, int fatal_mask,
+                                         const float* score, float min_score, const float* reinit_pose, const int* reinit_valid,
+                                         float lost_rot_deg, float lost_trans_m, int Wn, float znear, float zfar, int P, float* hist,
+                                         int* age, float* ring, int* ring_n, int* ring_pos, int* flags, float* step, float* mean) {
+  return {pose_before, pose_new, status_rows, n_rows, fatal_mask, score, min_score, reinit_pose, reinit_valid, lost_rot_deg, lost_trans_m,
+          Wn, znear, zfar, P, hist, age, ring, ring_n, ring_pos, flags, step, mean,
+          nullptr, 0.f, 0, nullptr, nullptr, nullptr, nullptr, nullptr};
+}
+
+// the checks of dim_track_update (`name` "track_update") and dim_track_update_occ ("track_update_occ"), and the launch
+template <bool OCC>
+static int track_update_launch(const char* name, const TrackUpdateArgs& a, void* stream) {
+  DIM_REQUIRE(a.P > 0 && a.n_rows >= 0, "%s: P = %d, n_rows = %d", name, a.P, a.n_rows);
+  DIM_REQUIRE(a.Wn >= 1 && a.Wn <= DIM_TRACK_MAX_WINDOW, "%s: Wn = %d outside [1, %d]", name, a.Wn, DIM_TRACK_MAX_WINDOW);
+  if (OCC) {
+    DIM_REQUIRE(a.min_visible >= 0.f && a.min_visible <= 1.f, "%s: min_visible = %g outside [0, 1]", name, (double)a.min_visible);
+    DIM_REQUIRE(a.max_occluded >= 0, "%s: max_occluded = %d", name, a.max_occluded);
+  }
+  DIM_REQUIRE(a.pose_before && a.pose_new && a.hist && a.age && a.ring && a.ring_n && a.ring_pos && a.flags && a.step && a.mean,
+              "%s: null pointer", name);
+  if (OCC)
+    DIM_REQUIRE(a.counts && a.pose_pred && a.occ_age && a.visible && a.pose_track && a.occluder_ok, "%s: null pointer", name);
+  DIM_REQUIRE(a.n_rows == 0 || a.status_rows, "%s: null pointer (status_rows)", name);
+  DIM_REQUIRE((a.reinit_pose == nullptr) == (a.reinit_valid == nullptr), "%s: reinit_pose and reinit_valid go together", name);
+  hipLaunchKernelGGL(track_update_kernel<OCC>, dim3(ceil_div(a.P, 64)), dim3(64), 0, as_stream(stream), a);
+  return check_launch(name);
+}
+
 extern "C" int dim_track_update(const float* pose_before, const float* pose_new, const int* status_rows, int n_rows, int fatal_mask,
                                 const float* score, float min_score, const float* reinit_pose, const int* reinit_valid,
                                 float lost_rot_deg, float lost_trans_m, int Wn, float znear, float zfar, int P, float* hist, int* age,
                                 float* ring, int* ring_n, int* ring_pos, int* flags, float* step, float* mean, void* stream) {
-  DIM_REQUIRE(P > 0 && n_rows >= 0, "track_update: P = %d, n_rows = %d", P, n_rows);
-  DIM_REQUIRE(Wn >= 1 && Wn <= DIM_TRACK_MAX_WINDOW, "track_update: Wn = %d outside [1, %d]", Wn, DIM_TRACK_MAX_WINDOW);
-  DIM_REQUIRE(pose_before && pose_new && hist && age && ring && ring_n && ring_pos && flags && step && mean, "track_update: null pointer");
-  DIM_REQUIRE(n_rows == 0 || status_rows, "track_update: null pointer (status_rows)");
-  DIM_REQUIRE((reinit_pose == nullptr) == (reinit_valid == nullptr), "track_update: reinit_pose and reinit_valid go together");
-  TrackUpdateArgs a{pose_before, pose_new, status_rows, n_rows, fatal_mask, score, min_score, reinit_pose, reinit_valid, lost_rot_deg,
-                    lost_trans_m, Wn, znear, zfar, P, hist, age, ring, ring_n, ring_pos, flags, step, mean};
-  hipLaunchKernelGGL(track_update_kernel, dim3(ceil_div(P, 64)), dim3(64), 0, as_stream(stream), a);
-  return check_launch("track_update");
+  return track_update_launch<false>("track_update",
+                                    track_update_args(pose_before, pose_new, status_rows, n_rows, fatal_mask, score, min_score, reinit_pose,
+                                                      reinit_valid, lost_rot_deg, lost_trans_m, Wn, znear, zfar, P, hist, age, ring, ring_n,
+                                                      ring_pos, flags, step, mean),
+                                    stream);
 }
 
 static long visibility_waves(long plane, int V) { return (long)ceil_div(plane, (long)kVisThreads * V) * (kVisThreads / kWave); }
@@ -542,17 +504,15 @@ extern "C" int dim_track_update_occ(const float* pose_before, const float* pose_
                                     float min_visible, int max_occluded, const float* pose_pred, float* hist, int* age, float* ring,
                                     int* ring_n, int* ring_pos, int* occ_age, int* flags, float* step, float* mean, float* visible,
                                     float* pose_track, int* occluder_ok, void* stream) {
-  DIM_REQUIRE(P > 0 && n_rows >= 0, "track_update_occ: P = %d, n_rows = %d", P, n_rows);
-  DIM_REQUIRE(Wn >= 1 && Wn <= DIM_TRACK_MAX_WINDOW, "track_update_occ: Wn = %d outside [1, %d]", Wn, DIM_TRACK_MAX_WINDOW);
-  DIM_REQUIRE(min_visible >= 0.f && min_visible <= 1.f, "track_update_occ: min_visible = %g outside [0, 1]", (double)min_visible);
-  DIM_REQUIRE(max_occluded >= 0, "track_update_occ: max_occluded = %d", max_occluded);
-  DIM_REQUIRE(pose_before && pose_new && hist && age && ring && ring_n && ring_pos && flags && step && mean, "track_update_occ: null pointer");
-  DIM_REQUIRE(counts && pose_pred && occ_age && visible && pose_track && occluder_ok, "track_update_occ: null pointer");
-  DIM_REQUIRE(n_rows == 0 || status_rows, "track_update_occ: null pointer (status_rows)");
-  DIM_REQUIRE((reinit_pose == nullptr) == (reinit_valid == nullptr), "track_update_occ: reinit_pose and reinit_valid go together");
-  TrackOccArgs o{{pose_before, pose_new, status_rows, n_rows, fatal_mask, score, min_score, reinit_pose, reinit_valid, lost_rot_deg,
-                  lost_trans_m, Wn, znear, zfar, P, hist, age, ring, ring_n, ring_pos, flags, step, mean},
-                 counts, min_visible, max_occluded, pose_pred, occ_age, visible, pose_track, occluder_ok};
-  hipLaunchKernelGGL(track_update_occ_kernel, dim3(ceil_div(P, 64)), dim3(64), 0, as_stream(stream), o);
-  return check_launch("track_update_occ");
+  TrackUpdateArgs a = track_update_args(pose_before, pose_new, status_rows, n_rows, fatal_mask, score, min_score, reinit_pose, reinit_valid,
+                                        lost_rot_deg, lost_trans_m, Wn, znear, zfar, P, hist, age, ring, ring_n, ring_pos, flags, step, mean);
+  a.counts = counts;
+  a.min_visible = min_visible;
+  a.max_occluded = max_occluded;
+  a.pose_pred = pose_pred;
+  a.occ_age = occ_age;
+  a.visible = visible;
+  a.pose_track = pose_track;
+  a.occluder_ok = occluder_ok;
+  return track_update_launch<true>("track_update_occ", a, stream);
 }

@@ -129,6 +129,24 @@ class Predictor(object):
         return [self.net.forward_test(data_batch)]
 
 
+def capture_graph(chain, device, state=()):
+    """-> a torch.cuda.CUDAGraph of chain() (kernels only, one stream), after a warm-up run on a side stream (lazy module loads, attribute
+    sets).  The warm-up is a real run: the `state` tensors that chain() advances in place are put back before the capture"""
+    keep = [t.clone() for t in state]
+    side = torch.cuda.Stream(device=device)
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        chain()
+    torch.cuda.current_stream().wait_stream(side)
+    torch.cuda.synchronize()
+    for t, k in zip(state, keep):
+        t.copy_(k)
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        chain()
+    return g
+
+
 class Refiner(object):
     """batch_size = P pairs per loaded batch.  With TEST.HYP_NUM = N > 1 every pair is refined from N starting poses, as the samples
     b = p * N + h of one batch (the Predictor is built for P * N samples); after the loop each sample's last pose is rendered and
@@ -548,16 +566,7 @@ class Refiner(object):
         if self.graph is not None and self._graph_per_pair_K != self.per_pair_K:
             self.graph = None   # captured with the other render (uniform / per-pair K): capture this one
         if self._want_graph and self.graph is None:
-            s = torch.cuda.Stream(device=self.net.device)
-            s.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(s):
-                self._loop()  # warm-up outside capture (lazy module loads, attribute sets)
-            torch.cuda.current_stream().wait_stream(s)
-            torch.cuda.synchronize()
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                self._loop()
-            self.graph = g
+            self.graph = capture_graph(self._loop, self.net.device)
             self._graph_per_pair_K = self.per_pair_K
         if self.graph is not None:
             self.graph.replay()

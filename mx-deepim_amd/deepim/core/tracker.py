@@ -4,15 +4,15 @@ P tracks share one camera.  Per frame one chain runs on one stream, with no host
 
     ingest (dim_track_ingest: the frame -> the P observed blobs)  ->  predict (dim_track_predict: the last two accepted poses ->
     refiner.pose_init)  ->  the start render and its box mask, as Refiner.load renders a starting pose  ->  Refiner._loop()  ->
-    [render + dim_pose_score of the tracked pose against the frame]  ->  update (dim_track_update: step ring, lost test, history,
-    re-initialisation)
+    [render of the tracked poses]  ->  [dim_track_visibility]  ->  [dim_pose_score against the frame]  ->  update (dim_track_update
+    or dim_track_update_occ: step ring, lost test, history, re-initialisation)
 
-With TEST.TRACK_OCCLUSION on, the tracks are judged together instead of each alone: the render of the tracked poses goes through
-dim_track_visibility (which pixels of a track another track, or the frame's own depth, hides), the score is taken over the visible
-pixels only, and dim_track_update_occ lets a track of which too little is visible coast on the motion model for a while instead of
-losing it (tests/track_occ_reference.py restates both).
+The render runs when a score or TEST.TRACK_OCCLUSION is on.  With occlusion on, the tracks are judged together instead of each alone:
+dim_track_visibility says which pixels of a track another track, or the frame's own depth, hides, the score is taken over the
+visible pixels only (depth_visible in place of depth_sc), and the update is dim_track_update_occ, which lets a track of which too
+little is visible coast on the motion model for a while instead of losing it (tests/track_occ_reference.py restates both).
 
-and with capture_graph the chain is one hipGraph, captured at the first step and replayed for every later frame.  The state (pose
+With capture_graph the chain is one hipGraph, captured at the first step and replayed for every later frame.  The state (pose
 history, age, step ring) lives in device tensors the chain reads and writes in place; a step copies the frame (and the offered
 re-initialisation poses) into resident staging tensors and launches the chain.  tests/track_reference.py restates predict and update.
 """
@@ -23,7 +23,7 @@ import torch
 
 from lib.hip import ops
 from deepim.core.pose_stages import int_setting, stages_on
-from deepim.core.tester import Refiner
+from deepim.core.tester import Refiner, capture_graph
 from deepim.symbols.deepIM_flownet import source_size
 
 TRACK_MOTIONS = ("hold", "velocity")
@@ -180,7 +180,7 @@ class Tracker(object):
 
     def _chain(self):
         """one frame, everything enqueued on the current stream from the resident tensors"""
-        r, s, T = self.refiner, self.settings, self.refiner.test_iter
+        r, s, occ, T = self.refiner, self.settings, self.occlusion, self.refiner.test_iter
         b, init = r.batch, r.init
         ops.track_ingest(self.frame_raw, self.depth_factor, self.pixel_means, b["image_observed"], depth_raw=self.depth_raw,
                          depth_observed=self.depth_observed)
@@ -194,39 +194,24 @@ class Tracker(object):
             ops.fill(last, 0)
         else:
             ops.copy(last, r.stages[s["pose"]].status)
-        if self.occ_on:
-            self._chain_occ(last)
-            return
-        if self.score is not None:   # as Refiner._select scores a hypothesis: every drawn pixel of the render inside its box
+        if self.score is not None or self.occ_on:   # the render of the tracked poses
             r.render_machine.render_batch(b["class_index"], self.pose_new, image=self.image_sc, depth=self.depth_sc, bbox=self.bbox_sc,
                                           plane_means=r.net.plane_means, mask_thr=0.0, status=last)
-            ops.pose_score(b["image_observed"], self.image_sc, self.depth_sc, s["score"], s["depth_tau"],
+        if self.occ_on:   # which of its pixels are visible (every row of depth_observed is the frame's depth after the ingest)
+            ops.track_visibility(self.depth_sc, occ["mode"], occ["delta"], depth_frame=self.depth_observed[0, 0] if occ["mode"] != "tracks" else None,
+                                 occluder_ok=self.occluder_ok, depth_visible=self.depth_visible, counts=self.counts, workspace=self.vis_work)
+        if self.score is not None:   # as Refiner._select scores a hypothesis: every drawn (with occlusion: and visible) pixel inside its box
+            ops.pose_score(b["image_observed"], self.image_sc, self.depth_visible if self.occ_on else self.depth_sc, s["score"], s["depth_tau"],
                            depth_observed=self.depth_observed if s["score"] == "depth" else None, bbox=self.bbox_sc, score=self.score,
                            status=last, workspace=self.score_work)
-        ops.track_update(self.pose_before, self.pose_new, self.hist, self.age, self.ring, self.ring_n, self.ring_pos, s["lost_rot_deg"],
-                         s["lost_trans"], self.znear, self.zfar, status_rows=self.status_rows, fatal_mask=FATAL_MASK, score=self.score,
-                         min_score=s["min_score"], reinit_pose=self.reinit_pose, reinit_valid=self.reinit_valid, flags=self.flags,
-                         step=self.step_out, mean=self.mean_out)
-
-    def _chain_occ(self, last):
-        """the end of the chain with occlusion on: the tracked poses' render, which of its pixels are visible, the score over those,
-        and the update with the occluded state"""
-        r, s, occ, b = self.refiner, self.settings, self.occlusion, self.refiner.batch
-        r.render_machine.render_batch(b["class_index"], self.pose_new, image=self.image_sc, depth=self.depth_sc, bbox=self.bbox_sc,
-                                      plane_means=r.net.plane_means, mask_thr=0.0, status=last)
-        # (every row of depth_observed is the frame's depth after the ingest)
-        ops.track_visibility(self.depth_sc, occ["mode"], occ["delta"], depth_frame=self.depth_observed[0, 0] if occ["mode"] != "tracks" else None,
-                             occluder_ok=self.occluder_ok, depth_visible=self.depth_visible, counts=self.counts, workspace=self.vis_work)
-        if self.score is not None:
-            ops.pose_score(b["image_observed"], self.image_sc, self.depth_visible, s["score"], s["depth_tau"],
-                           depth_observed=self.depth_observed if s["score"] == "depth" else None, bbox=self.bbox_sc, score=self.score,
-                           status=last, workspace=self.score_work)
-        ops.track_update_occ(self.pose_before, self.pose_new, self.hist, self.age, self.ring, self.ring_n, self.ring_pos, self.occ_age,
-                             self.counts, occ["min_visible"], occ["max_occluded"], r.pose_init, s["lost_rot_deg"], s["lost_trans"],
-                             self.znear, self.zfar, status_rows=self.status_rows, fatal_mask=FATAL_MASK, score=self.score,
-                             min_score=s["min_score"], reinit_pose=self.reinit_pose, reinit_valid=self.reinit_valid, flags=self.flags,
-                             step=self.step_out, mean=self.mean_out, visible=self.visible, pose_track=self.pose_track,
-                             occluder_ok=self.occluder_ok)
+        update, occ_in, occ_out = ops.track_update, (), {}
+        if self.occ_on:   # the update with the occluded state
+            update, occ_in = ops.track_update_occ, (self.occ_age, self.counts, occ["min_visible"], occ["max_occluded"], r.pose_init)
+            occ_out = dict(visible=self.visible, pose_track=self.pose_track, occluder_ok=self.occluder_ok)
+        update(self.pose_before, self.pose_new, self.hist, self.age, self.ring, self.ring_n, self.ring_pos, *occ_in, s["lost_rot_deg"],
+               s["lost_trans"], self.znear, self.zfar, status_rows=self.status_rows, fatal_mask=FATAL_MASK, score=self.score,
+               min_score=s["min_score"], reinit_pose=self.reinit_pose, reinit_valid=self.reinit_valid, flags=self.flags,
+               step=self.step_out, mean=self.mean_out, **occ_out)
 
     def _stage_inputs(self, frame_bgr, depth_raw, reinit_pose, reinit_valid):
         P = self.P
@@ -268,21 +253,8 @@ class Tracker(object):
         started from stays in refiner.pose_init"""
         self._stage_inputs(frame_bgr, depth_raw, reinit_pose, reinit_valid)
         if self._want_graph and self.graph is None:
-            # as Refiner.refine: a warm-up on a side stream (lazy module loads), then the capture -- one stream, kernels only.  The
-            # warm-up is a real frame, so the state it advanced is put back before the captured chain runs for the first time
-            keep = [t.clone() for t in self._state()]
-            side = torch.cuda.Stream(device=self.device)
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                self._chain()
-            torch.cuda.current_stream().wait_stream(side)
-            torch.cuda.synchronize()
-            for t, k in zip(self._state(), keep):
-                t.copy_(k)
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                self._chain()
-            self.graph = g
+            # the warm-up is a real frame: the state it advanced is put back before the captured chain runs for the first time
+            self.graph = capture_graph(self._chain, self.device, self._state())
         if self.graph is not None:
             self.graph.replay()
         else:

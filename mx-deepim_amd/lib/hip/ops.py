@@ -573,11 +573,10 @@ def track_predict(hist, age, mode="velocity", alpha=1.0, out=None):
     return out
 
 
-def track_update(pose_before, pose_new, hist, age, ring, ring_n, ring_pos, lost_rot_deg, lost_trans_m, znear, zfar, status_rows=None,
-                 fatal_mask=0, score=None, min_score=0.0, reinit_pose=None, reinit_valid=None, flags=None, step=None, mean=None):
-    """dim_track_update (restated by tests/track_reference.py): the per-track state machine after a frame's refinement.  Reads and
-    writes hist (P,2,3,4), age (P,), ring (P,Wn,2), ring_n, ring_pos (P,) in place -> flags (P,) int32, step (P,2), mean (P,2).
-    status_rows (n_rows,P) int32 are OR-ed; score (P,) f32 and reinit_pose (P,3,4) / reinit_valid (P,) int32 are optional"""
+def _track_update_args(pose_before, pose_new, hist, age, ring, ring_n, ring_pos, lost_rot_deg, lost_trans_m, znear, zfar, status_rows,
+                       fatal_mask, score, min_score, reinit_pose, reinit_valid, flags, step, mean):
+    """what track_update and track_update_occ share: the checks, flags / step / mean allocated when not given, and the arguments the two
+    entries have in common -> (head: pose_before .. P, state: hist .. ring_pos, (flags, step, mean))"""
     P, Wn = ring.shape[0], ring.shape[1]
     assert tuple(pose_before.shape) == (P, 3, 4) and tuple(pose_new.shape) == (P, 3, 4) and tuple(hist.shape) == (P, 2, 3, 4)
     assert tuple(ring.shape) == (P, Wn, 2) and age.numel() == P and ring_n.numel() == P and ring_pos.numel() == P
@@ -592,11 +591,21 @@ def track_update(pose_before, pose_new, hist, age, ring, ring_n, ring_pos, lost_
     step = step if step is not None else _new((P, 2), hist)
     mean = mean if mean is not None else _new((P, 2), hist)
     assert flags.numel() == P and step.numel() == 2 * P and mean.numel() == 2 * P
-    check(lib().dim_track_update(dptr(pose_before, f32), dptr(pose_new, f32), _opt(status_rows, i32), n_rows, int(fatal_mask), _opt(score),
-                                 float(min_score), _opt(reinit_pose), _opt(reinit_valid, i32), float(lost_rot_deg), float(lost_trans_m),
-                                 int(Wn), float(znear), float(zfar), P, dptr(hist, f32), dptr(age, i32), dptr(ring, f32),
-                                 dptr(ring_n, i32), dptr(ring_pos, i32), dptr(flags, i32), dptr(step, f32), dptr(mean, f32),
-                                 current_stream()))
+    head = (dptr(pose_before, f32), dptr(pose_new, f32), _opt(status_rows, i32), n_rows, int(fatal_mask), _opt(score), float(min_score),
+            _opt(reinit_pose), _opt(reinit_valid, i32), float(lost_rot_deg), float(lost_trans_m), int(Wn), float(znear), float(zfar), P)
+    state = (dptr(hist, f32), dptr(age, i32), dptr(ring, f32), dptr(ring_n, i32), dptr(ring_pos, i32))
+    return head, state, (flags, step, mean)
+
+
+def track_update(pose_before, pose_new, hist, age, ring, ring_n, ring_pos, lost_rot_deg, lost_trans_m, znear, zfar, status_rows=None,
+                 fatal_mask=0, score=None, min_score=0.0, reinit_pose=None, reinit_valid=None, flags=None, step=None, mean=None):
+    """dim_track_update (restated by tests/track_reference.py): the per-track state machine after a frame's refinement.  Reads and
+    writes hist (P,2,3,4), age (P,), ring (P,Wn,2), ring_n, ring_pos (P,) in place -> flags (P,) int32, step (P,2), mean (P,2).
+    status_rows (n_rows,P) int32 are OR-ed; score (P,) f32 and reinit_pose (P,3,4) / reinit_valid (P,) int32 are optional"""
+    head, state, (flags, step, mean) = _track_update_args(pose_before, pose_new, hist, age, ring, ring_n, ring_pos, lost_rot_deg, lost_trans_m,
+                                                          znear, zfar, status_rows, fatal_mask, score, min_score, reinit_pose, reinit_valid,
+                                                          flags, step, mean)
+    check(lib().dim_track_update(*head, *state, dptr(flags, i32), dptr(step, f32), dptr(mean, f32), current_stream()))
     return flags, step, mean
 
 
@@ -639,32 +648,18 @@ def track_update_occ(pose_before, pose_new, hist, age, ring, ring_n, ring_pos, o
     the frame started from, for at most max_occluded frames in a row (state occ_age (P,) int32) instead of being lost.
     -> flags (STATUS_TRACK_OCCLUDED among them), step, mean, visible (P,) f32, pose_track (P,3,4) = hist[:, 1] after the update,
     occluder_ok (P,) int32: 0 for a track that is lost and not re-initialised"""
-    P, Wn = ring.shape[0], ring.shape[1]
-    assert tuple(pose_before.shape) == (P, 3, 4) and tuple(pose_new.shape) == (P, 3, 4) and tuple(hist.shape) == (P, 2, 3, 4)
-    assert tuple(ring.shape) == (P, Wn, 2) and age.numel() == P and ring_n.numel() == P and ring_pos.numel() == P and occ_age.numel() == P
-    assert counts.numel() == 4 * P and tuple(pose_pred.shape) == (P, 3, 4)
-    n_rows = 0
-    if status_rows is not None:
-        assert status_rows.numel() % P == 0
-        n_rows = status_rows.numel() // P
-    assert score is None or score.numel() == P
-    assert (reinit_pose is None) == (reinit_valid is None)
-    assert reinit_pose is None or (tuple(reinit_pose.shape) == (P, 3, 4) and reinit_valid.numel() == P)
-    flags = flags if flags is not None else _new((P,), hist, i32)
-    step = step if step is not None else _new((P, 2), hist)
-    mean = mean if mean is not None else _new((P, 2), hist)
+    head, state, (flags, step, mean) = _track_update_args(pose_before, pose_new, hist, age, ring, ring_n, ring_pos, lost_rot_deg, lost_trans_m,
+                                                          znear, zfar, status_rows, fatal_mask, score, min_score, reinit_pose, reinit_valid,
+                                                          flags, step, mean)
+    P = ring.shape[0]
+    assert occ_age.numel() == P and counts.numel() == 4 * P and tuple(pose_pred.shape) == (P, 3, 4)
     visible = visible if visible is not None else _new((P,), hist)
     pose_track = pose_track if pose_track is not None else _new((P, 3, 4), hist)
     occluder_ok = occluder_ok if occluder_ok is not None else _new((P,), hist, i32)
-    assert flags.numel() == P and step.numel() == 2 * P and mean.numel() == 2 * P
     assert visible.numel() == P and tuple(pose_track.shape) == (P, 3, 4) and occluder_ok.numel() == P
-    check(lib().dim_track_update_occ(dptr(pose_before, f32), dptr(pose_new, f32), _opt(status_rows, i32), n_rows, int(fatal_mask),
-                                     _opt(score), float(min_score), _opt(reinit_pose), _opt(reinit_valid, i32), float(lost_rot_deg),
-                                     float(lost_trans_m), int(Wn), float(znear), float(zfar), P, dptr(counts, i32), float(min_visible),
-                                     int(max_occluded), dptr(pose_pred, f32), dptr(hist, f32), dptr(age, i32), dptr(ring, f32),
-                                     dptr(ring_n, i32), dptr(ring_pos, i32), dptr(occ_age, i32), dptr(flags, i32), dptr(step, f32),
-                                     dptr(mean, f32), dptr(visible, f32), dptr(pose_track, f32), dptr(occluder_ok, i32),
-                                     current_stream()))
+    check(lib().dim_track_update_occ(*head, dptr(counts, i32), float(min_visible), int(max_occluded), dptr(pose_pred, f32), *state,
+                                     dptr(occ_age, i32), dptr(flags, i32), dptr(step, f32), dptr(mean, f32), dptr(visible, f32),
+                                     dptr(pose_track, f32), dptr(occluder_ok, i32), current_stream()))
     return flags, step, mean, visible, pose_track, occluder_ok
 
 
