@@ -49,6 +49,7 @@ extern "C" {
 #define DIM_STATUS_TRACK_LOST 4096 /* dim_track_update: the track failed the lost test on this frame (the frame's pose was not accepted) */
 #define DIM_STATUS_TRACK_REINIT 8192 /* dim_track_update: ... and was re-initialised from the offered pose */
 #define DIM_STATUS_TRACK_OCCLUDED 16384 /* dim_track_update_occ: too little of the track's render is visible on this frame (it coasts, or is lost when the budget is spent) */
+#define DIM_STATUS_VIEWS_NO_CONSENSUS 32768 /* dim_views_consensus: no view of the sample's group was eligible (view 0 was used) */
 
 const char* dim_last_error(void);
 /* library / device probe: fills name (<= n bytes), returns number of compute units or <0 */
@@ -319,6 +320,64 @@ long dim_sil_workspace_bytes(int B, int H, int W);
 int dim_sil_refine(const float* depth_rendered, const int* field, const int* bbox, const float* pose_in, const float* K9,
                    const float* K_per_sample, int B, int H, int W, int iters, float huber_px, float max_px, void* workspace,
                    float* pose_out, float* stats, int* status, void* stream);
+
+/* ---------------------------------------------------------------- one object from several calibrated cameras (joint pose stages)
+ * A batch of B = G V samples holds G groups (one object instance each) with V views, 1 <= V <= 16; sample b = g V + v.
+ * cam_T_rig (B,3,4) f32 holds the rigid X_b = [R_b | t_b] with p_cam = X_b p_rig (a rig of V fixed cameras repeats its V rows G
+ * times).  A group has one pose T_g (3,4) in the rig frame; its pose in the camera of sample b is X_b T_g.
+ * X_b^-1 = [R_b^T | -R_b^T t_b]: nothing on the device checks that X_b is rigid.  Restated in float64 by tests/views_reference.py.
+ *
+ * dim_views_from_rig: pose_views[b] (B,3,4) = float32(X_b pose_rig[g]) (pose_rig (G,3,4)), products and sums in float64, rounded once.
+ *
+ * dim_views_consensus: one rig pose per group from the per-view poses `pose` (B,3,4) and their scores.  A view is eligible when
+ *   score[b] (B f32, as dim_pose_score gives it) is finite and (status[b] & fatal_mask) == 0 (status (B) int32, NULL = no bits).
+ *   choice[g] (G int32) = the eligible view v with the largest score, the lowest v on a tie; c = g V + choice[g].
+ *   pose_rig[g] (G,3,4) = float32(X_c^-1 pose[c]) in float64; for b != c pose_views[b] = float32(X_b (X_c^-1 pose[c])), from the
+ *   float64 product and not from the rounded pose_rig; pose_views[c] = pose[c] bit for bit.  No eligible view: choice[g] = -1, view 0
+ *   is used as c, and DIM_STATUS_VIEWS_NO_CONSENSUS is OR-ed into status_out[b] (B int32, may be NULL, may be status itself) of all V
+ *   samples; status_out is not written otherwise.  pose_views may be pose itself.
+ * Both: one launch, no workspace, no atomics; G <= 0, V outside 1 .. 16 or a NULL required pointer return DIM_ERR_ARG before
+ * anything is enqueued.
+ *
+ * dim_icp_refine_views, dim_photo_refine_views, dim_sil_refine_views: the stage of the same name with ONE correction per group.
+ *   Arguments, checks, accumulate launches (the photometric pyramid and gain passes included), stats (B, iters, 2) rows and the
+ *   workspace layout are those of the single-view entry; the solve launch of every iteration is the joint one, per group g:
+ *   for v = 0 .. V-1 in order, s_v = the sample's 16 workgroup partials added in block order; A_v from terms 0..20, g_v from terms
+ *   21..26, N_v = term 27, rr_v = term 28.  With twists ordered (omega, v), Ad_v = [[R_v, 0], [[t_v]x R_v, R_v]] maps a rig-frame twist
+ *   to the camera of sample g V + v, and A = sum_v Ad_v^T A_v Ad_v, g = sum_v Ad_v^T g_v, N = sum_v N_v, rr = sum_v rr_v, all in
+ *   ascending v, in float64.  stats_group (G, iters, 2) f32 or NULL = (N, sqrt(rr / N)) (0 for N = 0).  The step is taken when
+ *   N >= 64 -- the group's points, not each view's -- and (A + 1e-9 tr(A)/6 I) xi = -g passes the float64 Cholesky.  The correction
+ *   lives in the rig frame, D_g <- [Rodrigues(omega) | v] D_g from the identity, and after every iteration the correction of sample
+ *   b, the one its accumulate kernel linearises at next, is rewritten as X_b D_g X_b^-1 in float64: the samples' corrections are
+ *   conjugates of one rig correction by construction, not separately integrated twists ([Rodrigues(omega) | v] is a retraction,
+ *   not the exponential, so integrating Ad_v xi per view would let the views drift apart at second order).  A skipped step ORs the
+ *   stage's FEW_POINTS bit into status[b] of all V samples and leaves D_g; the later iterations still run.
+ *   pose_out[b] = float32((X_b D_g X_b^-1) pose_in[b]) and pose_rig_out[g] (G,3,4) = float32(D_g pose_rig_in[g]); a group that never
+ *   stepped gets pose_in and pose_rig_in bit for bit.  With V = 1 and X_b = [I | 0] every entry returns the bits of its single-view
+ *   entry.  workspace: dim_<stage>_views_workspace_bytes bytes = the single-view layout unchanged, then G x 16 doubles of group
+ *   state {R, t, stepped, pad}; alignment as the single-view entry, no initialisation needed.  One workgroup of 64 lanes per group:
+ *   the 29-term sums spread over lanes, the fusion on one lane; no atomics, fixed order: a replay is bit-identical.
+ *   Launches as the single-view entry.  iters == 0 copies pose_in to pose_out and pose_rig_in to pose_rig_out.  V outside 1 .. 16,
+ *   B % V != 0, a NULL cam_T_rig, pose_rig_in or pose_rig_out and every condition of the single-view entry return DIM_ERR_ARG before
+ *   anything is enqueued. */
+int dim_views_from_rig(const float* pose_rig, const float* cam_T_rig, int G, int V, float* pose_views, void* stream);
+int dim_views_consensus(const float* score, const int* status, int fatal_mask, const float* pose, const float* cam_T_rig, int G, int V,
+                        int* choice, float* pose_rig, float* pose_views, int* status_out, void* stream);
+long dim_icp_views_workspace_bytes(int B, int H, int W, int V);
+int dim_icp_refine_views(const float* depth_rendered, const float* depth_observed, const float* mask_observed, const int* bbox,
+                         const float* pose_in, const float* K9, const float* K_per_sample, int B, int H, int W, int iters, float max_dist,
+                         void* workspace, float* pose_out, float* stats, int* status, const float* cam_T_rig, int V,
+                         const float* pose_rig_in, float* pose_rig_out, float* stats_group, void* stream);
+long dim_photo_views_workspace_bytes(int B, int H, int W, int levels, int V);
+int dim_photo_refine_views(const float* image_observed, const float* image_rendered, const float* depth_rendered, const int* bbox,
+                           const float* pose_in, const float* K9, const float* K_per_sample, int B, int H, int W, int levels, int iters,
+                           float huber, float gate, int gain, void* workspace, float* pose_out, float* stats, int* status,
+                           const float* cam_T_rig, int V, const float* pose_rig_in, float* pose_rig_out, float* stats_group, void* stream);
+long dim_sil_views_workspace_bytes(int B, int H, int W, int V);
+int dim_sil_refine_views(const float* depth_rendered, const int* field, const int* bbox, const float* pose_in, const float* K9,
+                         const float* K_per_sample, int B, int H, int W, int iters, float huber_px, float max_px, void* workspace,
+                         float* pose_out, float* stats, int* status, const float* cam_T_rig, int V, const float* pose_rig_in,
+                         float* pose_rig_out, float* stats_group, void* stream);
 
 /* ---------------------------------------------------------------- multi-hypothesis refinement (several starting poses per pair)
  * Samples are pair-major: sample b = p * N + h of P pairs with N hypotheses each.  Restated in float64 by tests/hyp_reference.py.

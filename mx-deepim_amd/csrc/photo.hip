@@ -282,10 +282,11 @@ extern "C" long dim_photo_workspace_offset(int B, int H, int W, int levels, int 
   return L.off[plane][level];
 }
 
-extern "C" int dim_photo_refine(const float* image_observed, const float* image_rendered, const float* depth_rendered, const int* bbox,
-                                const float* pose_in, const float* K9, const float* K_per_sample, int B, int H, int W, int levels,
-                                int iters, float huber, float gate, int gain, void* workspace, float* pose_out, float* stats,
-                                int* status, void* stream) {
+// both entries: views == nullptr is dim_photo_refine
+static int photo_run(const float* image_observed, const float* image_rendered, const float* depth_rendered, const int* bbox,
+                     const float* pose_in, const float* K9, const float* K_per_sample, int B, int H, int W, int levels, int iters,
+                     float huber, float gate, int gain, void* workspace, float* pose_out, float* stats, int* status, const GnViews* views,
+                     void* stream) {
   DIM_REQUIRE(B > 0, "photo_refine: B = %d", B);
   DIM_REQUIRE(levels >= 1 && levels <= kPhotoMaxLevels, "photo_refine: levels = %d (1 .. %d)", levels, kPhotoMaxLevels);
   DIM_REQUIRE(iters >= 0, "photo_refine: iters = %d", iters);
@@ -294,7 +295,12 @@ extern "C" int dim_photo_refine(const float* image_observed, const float* image_
   DIM_REQUIRE(photo_shape_ok(B, H, W, levels), "photo_refine: image %d x %d is smaller than 3 x 3 at the coarsest of %d levels", H, W,
               levels);
   DIM_REQUIRE(image_observed && image_rendered && depth_rendered && pose_in && K9 && workspace && pose_out, "photo_refine: null pointer");
-  if (iters == 0) return dim_copy_words(pose_out, pose_in, 12L * B, stream);
+  DIM_REQUIRE(!views || gn_views_ok(*views, B), "photo_refine_views: V in 1 .. %d dividing B = %d, cam_T_rig, pose_rig_in and pose_rig_out required",
+              kGnMaxViews, B);
+  if (iters == 0) {
+    const int rc = dim_copy_words(pose_out, pose_in, 12L * B, stream);
+    return (rc != DIM_OK || !views) ? rc : dim_copy_words(views->pose_rig_out, views->pose_rig_in, 12L * (B / views->V), stream);
+  }
   const hipStream_t st = as_stream(stream);
   const PinholeCam k9 = cam_of_k9(K9);
   const PhotoLayout L = photo_layout(B, H, W, levels);
@@ -319,11 +325,35 @@ extern "C" int dim_photo_refine(const float* image_observed, const float* image_
                      (const float*)lv[0].p[3], bbox, H, W, gn.partial);
   hipLaunchKernelGGL(photo_gain_kernel, dim3(B), dim3(64), 0, st, (const double*)gn.partial, gain, gains);
   // one iteration index over levels * iters, from the coarsest level down
-  gn_iterate<DIM_STATUS_PHOTO_FEW_POINTS>(gn, B, levels * iters, pose_in, pose_out, nullptr, stats, status, st, [&](int it) {
+  gn_iterate_either<DIM_STATUS_PHOTO_FEW_POINTS>(gn, (double*)(ws + L.total), B, views, levels * iters, pose_in, pose_out, stats, status, st,
+                                                 [&](int it) {
     const int l = levels - 1 - it / iters;
     hipLaunchKernelGGL(photo_accumulate_kernel, dim3(kGnBlocks, B), dim3(256), 0, st, (const float*)lv[l].p[0], (const float*)lv[l].p[1],
                        (const float*)lv[l].p[2], (const float*)lv[l].p[3], bbox, k9, K_per_sample, H, W, L.H[l], L.W[l], l, huber, gate,
                        (const double*)gains, it, (const double*)gn.state, gn.partial);
   });
-  return check_launch("photo_refine");
+  return check_launch(views ? "photo_refine_views" : "photo_refine");
+}
+
+extern "C" int dim_photo_refine(const float* image_observed, const float* image_rendered, const float* depth_rendered, const int* bbox,
+                                const float* pose_in, const float* K9, const float* K_per_sample, int B, int H, int W, int levels,
+                                int iters, float huber, float gate, int gain, void* workspace, float* pose_out, float* stats,
+                                int* status, void* stream) {
+  return photo_run(image_observed, image_rendered, depth_rendered, bbox, pose_in, K9, K_per_sample, B, H, W, levels, iters, huber, gate, gain,
+                   workspace, pose_out, stats, status, nullptr, stream);
+}
+
+// the single-view layout unchanged (every plane offset keeps its meaning), the group state rows behind it
+extern "C" long dim_photo_views_workspace_bytes(int B, int H, int W, int levels, int V) {
+  return (photo_shape_ok(B, H, W, levels) && V > 0) ? photo_layout(B, H, W, levels).total + gn_views_state_bytes(B, V) : 0;
+}
+
+extern "C" int dim_photo_refine_views(const float* image_observed, const float* image_rendered, const float* depth_rendered, const int* bbox,
+                                      const float* pose_in, const float* K9, const float* K_per_sample, int B, int H, int W, int levels,
+                                      int iters, float huber, float gate, int gain, void* workspace, float* pose_out, float* stats,
+                                      int* status, const float* cam_T_rig, int V, const float* pose_rig_in, float* pose_rig_out,
+                                      float* stats_group, void* stream) {
+  const GnViews views{cam_T_rig, V, pose_rig_in, pose_rig_out, stats_group};
+  return photo_run(image_observed, image_rendered, depth_rendered, bbox, pose_in, K9, K_per_sample, B, H, W, levels, iters, huber, gate, gain,
+                   workspace, pose_out, stats, status, &views, stream);
 }

@@ -16,7 +16,7 @@
 //                          256 at a time, so the float64 work runs on full waves.  Float64 per point and per lane, summed across
 //                          lanes (block_sum.h) and, in the solve kernel, workgroups in a fixed order: no atomics, the queue order
 //                          is positional, a replay is bit-identical
-//   gn_solve_kernel        (twist_solve.h) as the other Gauss-Newton stages
+//   gn_solve_kernel        (twist_solve.h) as the other Gauss-Newton stages; gn_solve_views_kernel for dim_sil_refine_views
 // Two launches per iteration; nothing allocates or synchronises, so the stage is graph-capturable.
 #include "common.h"
 #include "twist_solve.h"
@@ -202,21 +202,50 @@ extern "C" long dim_sil_workspace_bytes(int B, int H, int W) {
   return gn_workspace_bytes(B);
 }
 
-extern "C" int dim_sil_refine(const float* depth_rendered, const int* field, const int* bbox, const float* pose_in, const float* K9,
-                              const float* K_per_sample, int B, int H, int W, int iters, float huber_px, float max_px, void* workspace,
-                              float* pose_out, float* stats, int* status, void* stream) {
+// both entries: views == nullptr is dim_sil_refine
+static int sil_run(const float* depth_rendered, const int* field, const int* bbox, const float* pose_in, const float* K9,
+                   const float* K_per_sample, int B, int H, int W, int iters, float huber_px, float max_px, void* workspace,
+                   float* pose_out, float* stats, int* status, const GnViews* views, void* stream) {
   DIM_REQUIRE(B > 0 && B <= 65535, "sil_refine: B = %d", B);
   DIM_REQUIRE(iters >= 0, "sil_refine: iters = %d", iters);
   DIM_REQUIRE(huber_px > 0.f, "sil_refine: huber_px must be > 0");
   DIM_REQUIRE(max_px >= huber_px, "sil_refine: max_px must be >= huber_px");
   DIM_REQUIRE(H >= 3 && W >= 3 && H <= kSilMaxSide && W <= kSilMaxSide, "sil_refine: image %d x %d (3 .. %d)", H, W, kSilMaxSide);
   DIM_REQUIRE(depth_rendered && field && pose_in && K9 && workspace && pose_out, "sil_refine: null pointer");
-  if (iters == 0) return dim_copy_words(pose_out, pose_in, 12L * B, stream);
+  DIM_REQUIRE(!views || gn_views_ok(*views, B), "sil_refine_views: V in 1 .. %d dividing B = %d, cam_T_rig, pose_rig_in and pose_rig_out required",
+              kGnMaxViews, B);
+  if (iters == 0) {
+    const int rc = dim_copy_words(pose_out, pose_in, 12L * B, stream);
+    return (rc != DIM_OK || !views) ? rc : dim_copy_words(views->pose_rig_out, views->pose_rig_in, 12L * (B / views->V), stream);
+  }
   const PinholeCam k9 = cam_of_k9(K9);
   const GnWorkspace ws(workspace, B);
-  gn_iterate<DIM_STATUS_SIL_FEW_POINTS>(ws, B, iters, pose_in, pose_out, nullptr, stats, status, as_stream(stream), [&](int it) {
+  gn_iterate_either<DIM_STATUS_SIL_FEW_POINTS>(ws, (double*)((char*)workspace + gn_workspace_bytes(B)), B, views, iters, pose_in, pose_out,
+                                               stats, status, as_stream(stream), [&](int it) {
     hipLaunchKernelGGL(sil_accumulate_kernel, dim3(kGnBlocks, B), dim3(256), 0, as_stream(stream), depth_rendered, field, bbox, k9,
                        K_per_sample, H, W, it, huber_px, max_px, (const double*)ws.state, ws.partial);
   });
-  return check_launch("sil_refine");
+  return check_launch(views ? "sil_refine_views" : "sil_refine");
+}
+
+extern "C" int dim_sil_refine(const float* depth_rendered, const int* field, const int* bbox, const float* pose_in, const float* K9,
+                              const float* K_per_sample, int B, int H, int W, int iters, float huber_px, float max_px, void* workspace,
+                              float* pose_out, float* stats, int* status, void* stream) {
+  return sil_run(depth_rendered, field, bbox, pose_in, K9, K_per_sample, B, H, W, iters, huber_px, max_px, workspace, pose_out, stats, status,
+                 nullptr, stream);
+}
+
+extern "C" long dim_sil_views_workspace_bytes(int B, int H, int W, int V) {
+  (void)H;
+  (void)W;
+  return (B <= 0 || V <= 0) ? 0 : gn_workspace_bytes(B) + gn_views_state_bytes(B, V);
+}
+
+extern "C" int dim_sil_refine_views(const float* depth_rendered, const int* field, const int* bbox, const float* pose_in, const float* K9,
+                                    const float* K_per_sample, int B, int H, int W, int iters, float huber_px, float max_px,
+                                    void* workspace, float* pose_out, float* stats, int* status, const float* cam_T_rig, int V,
+                                    const float* pose_rig_in, float* pose_rig_out, float* stats_group, void* stream) {
+  const GnViews views{cam_T_rig, V, pose_rig_in, pose_rig_out, stats_group};
+  return sil_run(depth_rendered, field, bbox, pose_in, K9, K_per_sample, B, H, W, iters, huber_px, max_px, workspace, pose_out, stats, status,
+                 &views, stream);
 }

@@ -1,7 +1,9 @@
 // Float64 device helpers shared by the Gauss-Newton pose stages (icp.hip, flow_pnp.hip, photo.hip, sil.hip) and the pose algebra (se3.hip): the 6x6
 // Cholesky solve of the normal equations, the Rodrigues rotation of a twist's omega, and rotation matrix -> quaternion; and what
 // the Gauss-Newton stages have in common: the workspace layout, the camera and box of a pair, the solve kernel, the pieces of an
-// accumulate kernel (pose load, normal-equation terms, partial store) and the host loop over the two launches of an iteration.
+// accumulate kernel (pose load, normal-equation terms, partial store) and the host loop over the two launches of an iteration; and the
+// joint solve over the calibrated views of one object (gn_solve_views_kernel, gn_iterate_views) with the rigid 3x4 algebra it and
+// views.hip share.
 #pragma once
 #include "block_sum.h"
 #include "common.h"
@@ -192,6 +194,183 @@ __global__ __launch_bounds__(64) void gn_solve_kernel(const double* __restrict__
   }
 }
 
+// ---- several calibrated views of one object (B = G x V samples, sample b = g V + v; cam_T_rig row b = X_b = [R_b | t_b], p_cam = X_b p_rig)
+
+constexpr int kGnMaxViews = 16;    // views per group: the solve keeps V x kGnTerms sums in LDS
+
+// rigid 3x4 algebra in float64, rows [R | t] as 9 + 3 doubles: (Rc | tc) = (Ra | ta) (Rb | tb)
+__device__ inline void rigid_mul(const double* Ra, const double* ta, const double* Rb, const double* tb, double* Rc, double* tc) {
+  for (int i = 0; i < 3; ++i) {
+    for (int j = 0; j < 3; ++j) Rc[3 * i + j] = Ra[3 * i] * Rb[j] + Ra[3 * i + 1] * Rb[3 + j] + Ra[3 * i + 2] * Rb[6 + j];
+    tc[i] = Ra[3 * i] * tb[0] + Ra[3 * i + 1] * tb[1] + Ra[3 * i + 2] * tb[2] + ta[i];
+  }
+}
+// X^-1 = [R^T | -R^T t] (exact only for a rigid X: nothing here checks that)
+__device__ inline void rigid_inverse(const double* R, const double* t, double* Ri, double* ti) {
+  for (int i = 0; i < 3; ++i) {
+    for (int j = 0; j < 3; ++j) Ri[3 * i + j] = R[3 * j + i];
+    ti[i] = -(R[i] * t[0] + R[3 + i] * t[1] + R[6 + i] * t[2]);
+  }
+}
+__device__ inline void rigid_load(const float* __restrict__ T, double* R, double* t) {
+  for (int i = 0; i < 3; ++i) {
+    for (int j = 0; j < 3; ++j) R[3 * i + j] = (double)T[4 * i + j];
+    t[i] = (double)T[4 * i + 3];
+  }
+}
+// rounded once
+__device__ inline void rigid_store(const double* R, const double* t, float* __restrict__ T) {
+  for (int i = 0; i < 3; ++i) {
+    for (int j = 0; j < 3; ++j) T[4 * i + j] = (float)R[3 * i + j];
+    T[4 * i + 3] = (float)t[i];
+  }
+}
+
+// One joint Gauss-Newton step of group g = blockIdx.x (64 lanes) over its V samples b = g V + v, after the stage's unchanged
+// accumulate launch over all B samples.  s_v = the 16 partials of sample b added in block order, as gn_solve_kernel adds them;
+// stats (B, iters, 2) rows as gn_solve_kernel writes them.  With Ad_v = [[R_v, 0], [[t_v]x R_v, R_v]] (twists ordered (omega, v)):
+// A = sum_v Ad_v^T A_v Ad_v, g = sum_v Ad_v^T g_v, N = sum_v N_v, rr = sum_v rr_v in ascending v, float64, on one lane;
+// stats_group (G, iters, 2) = (N, sqrt(rr / N)).  The step is taken when N >= kGnMinPoints (the GROUP's points) and the damped
+// system passes cholesky_solve6; it moves the rig-frame correction D_g <- [Rodrigues(omega) | v] D_g (identity at it == 0), kept in
+// the group's state row, and every sample's state row -- what its accumulate kernel reads through gn_load_pose -- is rewritten as
+// the conjugate X_b D_g X_b^-1, so the samples' corrections are one rig correction by construction.  A skipped step ORs FAIL_BIT
+// into the status of all V samples and leaves D_g.  After the last iteration pose_out[b] = state_b pose_in[b] and
+// pose_rig_out[g] = D_g pose_rig_in[g]; a group that never stepped gets pose_in and pose_rig_in bit for bit.
+// The matrices of the fusion live in LDS (one lane indexes them in loops), the sums are positional: no atomics, no scratch.
+template <int FAIL_BIT>
+__global__ __launch_bounds__(64) void gn_solve_views_kernel(const double* __restrict__ partial, double* __restrict__ state,
+                                                           double* __restrict__ group_state, const float* __restrict__ cam_T_rig, int V,
+                                                           int it, int iters, const float* __restrict__ pose_in,
+                                                           float* __restrict__ pose_out, const float* __restrict__ pose_rig_in,
+                                                           float* __restrict__ pose_rig_out, float* __restrict__ stats,
+                                                           float* __restrict__ stats_group, int* __restrict__ status) {
+  const int g = blockIdx.x, tid = threadIdx.x;
+  __shared__ double s[kGnMaxViews][kGnSlot];
+  __shared__ double Av[36], Ad[36], M[36], A[36];
+  for (int idx = tid; idx < V * kGnSlot; idx += 64) {
+    const int v = idx / kGnSlot, term = idx % kGnSlot;
+    if (term < kGnTerms) {
+      const long b = (long)g * V + v;
+      double sum = 0.0;
+      for (int k = 0; k < kGnBlocks; ++k) sum += partial[(b * kGnBlocks + k) * kGnSlot + term];
+      s[v][term] = sum;
+    }
+  }
+  __syncthreads();
+  if (tid != 0) return;
+  double* gs = group_state + (long)g * kGnState;
+  double R[9] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0}, t[3] = {0.0, 0.0, 0.0}, updated = 0.0;
+  if (it > 0) {
+    for (int k = 0; k < 9; ++k) R[k] = gs[k];
+    for (int k = 0; k < 3; ++k) t[k] = gs[9 + k];
+    updated = gs[12];
+  }
+  double gsum[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, N = 0.0, rr = 0.0;
+  for (int k = 0; k < 36; ++k) A[k] = 0.0;
+  for (int v = 0; v < V; ++v) {
+    const long b = (long)g * V + v;
+    const double Nv = s[v][27], rrv = s[v][28];
+    if (stats) {
+      stats[(b * iters + it) * 2 + 0] = (float)Nv;
+      stats[(b * iters + it) * 2 + 1] = Nv > 0.0 ? (float)sqrt(rrv / Nv) : 0.f;
+    }
+    double Rx[9], tx[3];
+    rigid_load(cam_T_rig + 12 * b, Rx, tx);
+    int k = 0;
+    for (int a = 0; a < 6; ++a)
+      for (int e = a; e < 6; ++e, ++k) Av[6 * a + e] = Av[6 * e + a] = s[v][k];
+    const double Tx[9] = {0.0, -tx[2], tx[1], tx[2], 0.0, -tx[0], -tx[1], tx[0], 0.0};
+    for (int i = 0; i < 3; ++i)
+      for (int j = 0; j < 3; ++j) {
+        Ad[6 * i + j] = Ad[6 * (3 + i) + 3 + j] = Rx[3 * i + j];
+        Ad[6 * i + 3 + j] = 0.0;
+        Ad[6 * (3 + i) + j] = Tx[3 * i] * Rx[j] + Tx[3 * i + 1] * Rx[3 + j] + Tx[3 * i + 2] * Rx[6 + j];
+      }
+    for (int i = 0; i < 6; ++i)
+      for (int j = 0; j < 6; ++j) {
+        double m = 0.0;
+        for (int q = 0; q < 6; ++q) m += Av[6 * i + q] * Ad[6 * q + j];
+        M[6 * i + j] = m;
+      }
+    for (int i = 0; i < 6; ++i) {
+      for (int j = 0; j < 6; ++j) {
+        double m = 0.0;
+        for (int q = 0; q < 6; ++q) m += Ad[6 * q + i] * M[6 * q + j];
+        A[6 * i + j] += m;
+      }
+      double m = 0.0;
+      for (int q = 0; q < 6; ++q) m += Ad[6 * q + i] * s[v][21 + q];
+      gsum[i] += m;
+    }
+    N += Nv;
+    rr += rrv;
+  }
+  if (stats_group) {
+    stats_group[((long)g * iters + it) * 2 + 0] = (float)N;
+    stats_group[((long)g * iters + it) * 2 + 1] = N > 0.0 ? (float)sqrt(rr / N) : 0.f;
+  }
+  bool ok = N >= (double)kGnMinPoints;
+  double xi[6];
+  if (ok) {
+    const double damp = 1e-9 * (A[0] + A[7] + A[14] + A[21] + A[28] + A[35]) / 6.0;
+    double rhs[6];
+    for (int a = 0; a < 6; ++a) {
+      A[6 * a + a] += damp;
+      rhs[a] = -gsum[a];
+    }
+    ok = cholesky_solve6(A, rhs, xi);
+  }
+  if (ok) {
+    double Rw[9], Rn[9], tn[3];
+    twist_rodrigues(xi, Rw);
+    rigid_mul(Rw, xi + 3, R, t, Rn, tn);
+    for (int k = 0; k < 9; ++k) R[k] = Rn[k];
+    for (int k = 0; k < 3; ++k) t[k] = tn[k];
+    updated = 1.0;
+  }
+  for (int k = 0; k < 9; ++k) gs[k] = R[k];
+  for (int k = 0; k < 3; ++k) gs[9 + k] = t[k];
+  gs[12] = updated;
+  const bool last = it == iters - 1;
+  for (int v = 0; v < V; ++v) {
+    const long b = (long)g * V + v;
+    if (!ok && status) status[b] |= FAIL_BIT;
+    double Rx[9], tx[3], Ri[9], ti[3], Rm[9], tm[3], Rs[9], ts[3];
+    rigid_load(cam_T_rig + 12 * b, Rx, tx);
+    rigid_inverse(Rx, tx, Ri, ti);
+    rigid_mul(R, t, Ri, ti, Rm, tm);
+    rigid_mul(Rx, tx, Rm, tm, Rs, ts);
+    double* st = state + b * kGnState;
+    for (int k = 0; k < 9; ++k) st[k] = Rs[k];
+    for (int k = 0; k < 3; ++k) st[9 + k] = ts[k];
+    st[12] = updated;
+    if (!last) continue;
+    const float* T0 = pose_in + 12 * b;
+    float* out = pose_out + 12 * b;
+    if (updated == 0.0) {   // never moved: the input pose, bit for bit
+      for (int k = 0; k < 12; ++k) out[k] = T0[k];
+      continue;
+    }
+    for (int i = 0; i < 3; ++i) {
+      for (int j = 0; j < 3; ++j)
+        out[4 * i + j] = (float)(Rs[3 * i] * (double)T0[j] + Rs[3 * i + 1] * (double)T0[4 + j] + Rs[3 * i + 2] * (double)T0[8 + j]);
+      out[4 * i + 3] = (float)(Rs[3 * i] * (double)T0[3] + Rs[3 * i + 1] * (double)T0[7] + Rs[3 * i + 2] * (double)T0[11] + ts[i]);
+    }
+  }
+  if (!last) return;
+  const float* T0 = pose_rig_in + 12 * (long)g;
+  float* out = pose_rig_out + 12 * (long)g;
+  if (updated == 0.0) {
+    for (int k = 0; k < 12; ++k) out[k] = T0[k];
+    return;
+  }
+  for (int i = 0; i < 3; ++i) {
+    for (int j = 0; j < 3; ++j)
+      out[4 * i + j] = (float)(R[3 * i] * (double)T0[j] + R[3 * i + 1] * (double)T0[4 + j] + R[3 * i + 2] * (double)T0[8 + j]);
+    out[4 * i + 3] = (float)(R[3 * i] * (double)T0[3] + R[3 * i + 1] * (double)T0[7] + R[3 * i + 2] * (double)T0[11] + t[i]);
+  }
+}
+
 // ---- what the accumulate kernels share.  All of it is inlined: the kGnTerms accumulators of a lane are registers of the kernel.
 
 // the correction T_delta = [R | t] an iteration linearises at: the identity at it == 0, else the state row of pair b as T
@@ -283,6 +462,42 @@ inline void gn_iterate(const GnWorkspace& ws, int B, int total, const float* pos
     hipLaunchKernelGGL(gn_solve_kernel<FAIL_BIT>, dim3(B), dim3(64), 0, st, (const double*)ws.partial, ws.state, it, total, pose_in,
                        pose_out, se3_q, stats, status);
   }
+}
+
+// the same for groups of V views: `views` names what the joint solve needs besides; the group state rows follow the stage's own
+// workspace at group_state (gn_views_state_bytes more bytes)
+struct GnViews {
+  const float* cam_T_rig;
+  int V;
+  const float* pose_rig_in;
+  float* pose_rig_out;
+  float* stats_group;
+};
+
+inline long gn_views_state_bytes(int B, int V) { return (B <= 0 || V <= 0) ? 0 : (long)(B / V) * kGnState * (long)sizeof(double); }
+
+inline bool gn_views_ok(const GnViews& vw, int B) {
+  return vw.V >= 1 && vw.V <= kGnMaxViews && B % vw.V == 0 && vw.cam_T_rig && vw.pose_rig_in && vw.pose_rig_out;
+}
+
+template <int FAIL_BIT, class Accumulate>
+inline void gn_iterate_views(const GnWorkspace& ws, double* group_state, int B, const GnViews& vw, int total, const float* pose_in,
+                             float* pose_out, float* stats, int* status, hipStream_t st, Accumulate accumulate) {
+  for (int it = 0; it < total; ++it) {
+    accumulate(it);
+    hipLaunchKernelGGL(gn_solve_views_kernel<FAIL_BIT>, dim3(B / vw.V), dim3(64), 0, st, (const double*)ws.partial, ws.state, group_state,
+                       vw.cam_T_rig, vw.V, it, total, pose_in, pose_out, vw.pose_rig_in, vw.pose_rig_out, stats, vw.stats_group, status);
+  }
+}
+
+// one driver for a stage's two entries: views == nullptr is the single-view stage, launch for launch what gn_iterate enqueues
+template <int FAIL_BIT, class Accumulate>
+inline void gn_iterate_either(const GnWorkspace& ws, double* group_state, int B, const GnViews* views, int total, const float* pose_in,
+                              float* pose_out, float* stats, int* status, hipStream_t st, Accumulate accumulate) {
+  if (views)
+    gn_iterate_views<FAIL_BIT>(ws, group_state, B, *views, total, pose_in, pose_out, stats, status, st, accumulate);
+  else
+    gn_iterate<FAIL_BIT>(ws, B, total, pose_in, pose_out, nullptr, stats, status, st, accumulate);
 }
 
 }  // namespace dim

@@ -103,6 +103,11 @@ def _defaults():
                    # HYP_NUM best of every pair start the loop
                    COARSE_VIEWS=0, COARSE_INPLANE=1, COARSE_BOX_ITER=8, COARSE_Z_INIT=1.0, COARSE_SCORE="rgb", COARSE_DEPTH_TAU=0.02,
                    COARSE_CHUNK=256,
+                   # one object seen by several calibrated cameras (deepim/core/views.py, deepim/multiview.py): VIEWS = V > 1 makes a
+                   # batch hold batch / V groups of V views (Refiner.load(..., cam_T_rig=)); after the per-sample loop the best view
+                   # of a group by VIEWS_SCORE ("rgb" ZNCC or "depth" inlier fraction with HYP_DEPTH_TAU's gate) gives the group's pose
+                   # and the post-loop stages refine ONE pose per group from all its views.  1 = off
+                   VIEWS=1, VIEWS_SCORE="rgb",
                    # following objects through a video (deepim/core/tracker.py Tracker, deepim/track.py): the motion model that
                    # predicts a frame's starting pose from the last two accepted ones ("hold" or "velocity") and its damping in
                    # [0, 1]; the lost test -- the window length in frames (1..64) and the window means of the loop's last step

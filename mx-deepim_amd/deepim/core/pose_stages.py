@@ -1,6 +1,8 @@
 """The test-time pose stages of deepim.core.tester.Refiner: depth ICP, photometric polish and silhouette polish after the refinement
 loop, each from its last pose, and pose from flow at every iteration of it; STAGE_KEY: stage -> the TEST key that switches it on (> 0).
-A stage is one class, built only when it is on: its checked settings, its private buffers, its outputs, its run."""
+A stage is one class, built only when it is on: its checked settings, its private buffers, its outputs, its run.
+With TEST.VIEWS = V > 1 (deepim.core.views) a post-loop stage runs its joint entry: run() also takes the rig poses of the G = B / V
+groups, and the stage leaves pose_rig (G,3,4) and stats_group next to its per-sample outputs."""
 import numpy as np
 import torch
 
@@ -114,6 +116,23 @@ def _zeros(r, dtype, *shape):
     return torch.zeros(shape, dtype=dtype, device=r.net.device)
 
 
+def _views_outputs(stage, r, n_iters):
+    """the joint outputs of a post-loop stage: pose_rig (G,3,4), stats_group (G,n_iters,2) and pose_step (B,3,4), the entry's own
+    per-sample output; None with one view per group.  The stage's public pose is then X_b pose_rig (_publish)"""
+    V = getattr(r, "V", 1)
+    G = r.B // V
+    stage.pose_rig, stage.stats_group, stage.pose_step = (
+        _zeros(r, F32, G, 3, 4), _zeros(r, F32, G, n_iters, 2), _zeros(r, F32, r.B, 3, 4)) if V > 1 else (None, None, None)
+    return V
+
+
+def _publish(stage, r):
+    """a joint stage's per-sample poses are its rig pose seen from every camera, rounded once: the views of a group then agree with
+    the extrinsics to that one rounding.  (The entry's own pose_out, kept in pose_step, is the same pose up to the float32 rounding
+    of the per-sample pose it started from.)"""
+    ops.views_from_rig(stage.pose_rig, r.views.cam_T_rig, r.V, pose_views=stage.pose)
+
+
 class IcpStage(object):
     """depth ICP from the loop's last pose: render its depth and box (the pair's K when loaded), then dim_icp_refine against the
     refiner's depth_observed -> pose (B,3,4), stats (B,ICP_ITER,2), status (B,) (render bits and DIM_STATUS_ICP_FEW_POINTS)"""
@@ -122,11 +141,17 @@ class IcpStage(object):
         (self.iters, self.max_dist), B = settings, r.B
         self.depth, self.bbox = _zeros(r, F32, B, 1, H, W), _zeros(r, I32, B, 4)
         self.pose, self.stats, self.status = _zeros(r, F32, B, 3, 4), _zeros(r, F32, B, self.iters, 2), _zeros(r, I32, B)
-        self.work = ops.icp_workspace(B, H, W, r.net.device)
+        V = _views_outputs(self, r, self.iters)
+        self.work = ops.icp_workspace(B, H, W, r.net.device) if V == 1 else ops.icp_views_workspace(B, H, W, V, r.net.device)
 
-    def run(self, r, pose):
+    def run(self, r, pose, pose_rig=None):
         ops.fill(self.status, 0)
         K_pair = r._render_at(pose, self.status, depth=self.depth, bbox=self.bbox)
+        if pose_rig is not None:
+            ops.icp_refine_views(self.depth, r.depth_observed, pose, r.render_machine.K, self.iters, self.max_dist, r.views.cam_T_rig, r.V,
+                                 pose_rig, bbox=self.bbox, K_per_sample=K_pair, pose_out=self.pose_step, pose_rig_out=self.pose_rig,
+                                 stats=self.stats, stats_group=self.stats_group, status=self.status, workspace=self.work)
+            return _publish(self, r)
         ops.icp_refine(self.depth, r.depth_observed, pose, r.render_machine.K, self.iters, self.max_dist, bbox=self.bbox,
                        K_per_sample=K_pair, pose_out=self.pose, stats=self.stats, status=self.status, workspace=self.work)
 
@@ -139,11 +164,19 @@ class PhotoStage(object):
         (self.iters, self.levels, self.huber, self.gate, self.gain), B = settings, r.B
         self.image, self.depth, self.bbox = _zeros(r, F32, B, 3, H, W), _zeros(r, F32, B, 1, H, W), _zeros(r, I32, B, 4)
         self.pose, self.stats, self.status = _zeros(r, F32, B, 3, 4), _zeros(r, F32, B, self.levels * self.iters, 2), _zeros(r, I32, B)
-        self.work = ops.photo_workspace(B, H, W, self.levels, r.net.device)
+        V = _views_outputs(self, r, self.levels * self.iters)
+        self.work = (ops.photo_workspace(B, H, W, self.levels, r.net.device) if V == 1 else
+                     ops.photo_views_workspace(B, H, W, self.levels, V, r.net.device))
 
-    def run(self, r, pose):
+    def run(self, r, pose, pose_rig=None):
         ops.fill(self.status, 0)
         K_pair = r._render_at(pose, self.status, image=self.image, depth=self.depth, bbox=self.bbox, plane_means=r.net.plane_means)
+        if pose_rig is not None:
+            ops.photo_refine_views(r.batch["image_observed"], self.image, self.depth, pose, r.render_machine.K, self.levels, self.iters,
+                                   self.huber, self.gate, r.views.cam_T_rig, r.V, pose_rig, gain=self.gain, bbox=self.bbox,
+                                   K_per_sample=K_pair, pose_out=self.pose_step, pose_rig_out=self.pose_rig, stats=self.stats,
+                                   stats_group=self.stats_group, status=self.status, workspace=self.work)
+            return _publish(self, r)
         ops.photo_refine(r.batch["image_observed"], self.image, self.depth, pose, r.render_machine.K, self.levels, self.iters, self.huber,
                          self.gate, gain=self.gain, bbox=self.bbox, K_per_sample=K_pair, pose_out=self.pose, stats=self.stats,
                          status=self.status, workspace=self.work)
@@ -165,11 +198,32 @@ class SilStage(object):
         self.pose_round, self.status = _zeros(r, F32, self.rounds, B, 3, 4), _zeros(r, I32, B)
         self.pose = self.pose_round[self.rounds - 1]
         self.stats_round, self.stats = _zeros(r, F32, B, self.iters, 2), _zeros(r, F32, B, self.rounds * self.iters, 2)
-        self.work = ops.sil_workspace(B, H, W, r.net.device)
+        V = _views_outputs(self, r, self.rounds * self.iters)
+        self.work = ops.sil_workspace(B, H, W, r.net.device) if V == 1 else ops.sil_views_workspace(B, H, W, V, r.net.device)
+        if V > 1:   # a round's rig pose and group stats, as pose_round and stats_round
+            self.pose_rig_round, self.stats_group_round = _zeros(r, F32, self.rounds, B // V, 3, 4), _zeros(r, F32, B // V, self.iters, 2)
+            self.pose_rig, self.pose = self.pose_rig_round[self.rounds - 1], self.pose_step   # (pose_round: the entry's own outputs)
 
-    def run(self, r, pose):
+    def _run_views(self, r, pose, pose_rig):
+        """run() for groups of views: every round starts from the previous round's per-sample poses and rig pose"""
+        n, G = 2 * self.iters, r.B // r.V
+        flat, flat_group = self.stats.view(-1), self.stats_group.view(-1)
+        for k in range(self.rounds):
+            K_pair = r._render_at(pose, self.status, depth=self.depth, bbox=self.bbox)
+            ops.sil_refine_views(self.depth, self.field, pose, r.render_machine.K, self.iters, self.huber, self.gate, r.views.cam_T_rig, r.V,
+                                 pose_rig, bbox=self.bbox, K_per_sample=K_pair, pose_out=self.pose_round[k],
+                                 pose_rig_out=self.pose_rig_round[k], stats=self.stats_round, stats_group=self.stats_group_round,
+                                 status=self.status, workspace=self.work)
+            ops.copy_rows(flat[k * n:], self.rounds * n, self.stats_round, n, r.B, n)
+            ops.copy_rows(flat_group[k * n:], self.rounds * n, self.stats_group_round, n, G, n)
+            pose, pose_rig = self.pose_round[k], self.pose_rig_round[k]
+        _publish(self, r)
+
+    def run(self, r, pose, pose_rig=None):
         ops.fill(self.status, 0)
         ops.sil_edge_field(self.mask if self.which == "observed" else r.mask_pred_iter[r.test_iter - 1], self.radius, field=self.field)
+        if pose_rig is not None:
+            return self._run_views(r, pose, pose_rig)
         n, flat = 2 * self.iters, self.stats.view(-1)   # n: floats per pair and round
         for k in range(self.rounds):
             K_pair = r._render_at(pose, self.status, depth=self.depth, bbox=self.bbox)

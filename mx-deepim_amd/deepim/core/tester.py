@@ -23,6 +23,7 @@ from deepim.core.coarse import CoarseInit, boxes_from_int, coarse_settings
 from deepim.core.pose_stages import (POST_LOOP, STAGE_KEY, STAGES, flow_pnp_settings, icp_settings, int_setting, photo_settings,  # noqa: F401
                                      sil_settings, stage_settings, stages_on)
 from deepim.core.score_lists import PairLists, ScoreLists
+from deepim.core.views import ViewsConsensus, check_cam_T_rig, refuse_views_at_source_size, refuse_with_views, views_settings
 from deepim.symbols.deepIM_flownet import FlowNetHip, source_size, zoom_filter
 
 HYP_SCORES = ("rgb", "depth")
@@ -98,7 +99,9 @@ def hypothesis_rotations(N, rot_deg):
 def refuse_at_source_size(cfg, size, lit=False):
     """the stages that exist at the network size only: with SCALES of another size every one that is switched on raises a ValueError
     naming its key and SCALES (none may run at the wrong size).  What runs at any 4:3 size: the FAST_TEST loop (UPDATE_MASK
-    'box_rendered' / 'init', per-pair K, graph capture, the INPUT_DEPTH graphs), TEST.DEVICE_EVAL and TEST.BOP without BOP_VSD."""
+    'box_rendered' / 'init', per-pair K, graph capture, the INPUT_DEPTH graphs), TEST.DEVICE_EVAL and TEST.BOP without BOP_VSD.
+    TEST.VIEWS > 1 is refused like the stages it needs: a joint stage raises under its own key here, and the consensus, which is on
+    whatever the stages are, under TEST.VIEWS (deepim.core.views.refuse_views_at_source_size)."""
     if tuple(size) == (FlowNetHip.H, FlowNetHip.W):
         return
     T, stages = cfg.TEST, stages_on(cfg)
@@ -153,7 +156,10 @@ class Refiner(object):
     scored against the observed image (TEST.HYP_SCORE) and the best hypothesis of each pair is selected, all inside the same graph.
     With TEST.COARSE_VIEWS > 0 the starting poses come from a detection box per pair: load(..., det_boxes=) runs the coarse stage
     (deepim.core.coarse.CoarseInit, eagerly, outside the graph) and starts the loop from its HYP_NUM best candidates.  evaluator: the
-    PoseEvaluator whose model points the box fit projects (None: the vertices of the render machine's meshes)."""
+    PoseEvaluator whose model points the box fit projects (None: the vertices of the render machine's meshes).
+    With TEST.VIEWS = V > 1 the batch holds batch_size / V objects seen by V calibrated cameras each (sample b = g * V + v,
+    load(..., cam_T_rig=)): the loop runs per sample, then a consensus among the views of a group and the post-loop stages as joint
+    stages with one correction per group (deepim.core.views)."""
 
     def __init__(self, config, predictor, render_machine, batch_size, capture_graph=False, evaluator=None):
         cfg = config
@@ -164,7 +170,11 @@ class Refiner(object):
         H, W = source_size(cfg)
         filter_cfg = zoom_filter(cfg)   # (refuses 'area' in the full graph)
         refuse_at_source_size(cfg, (H, W), lit=hasattr(render_machine, "normals"))
+        refuse_views_at_source_size(cfg, (H, W), (FlowNetHip.H, FlowNetHip.W))
         self.hyp_num, self.hyp_rot_deg, self.hyp_score_mode, self.hyp_tau = hyp_settings(cfg)
+        self.V, views_score, views_tau = views_settings(cfg, lit=hasattr(render_machine, "normals"))
+        if batch_size % self.V:
+            raise ValueError("Refiner: batch_size {} is not a multiple of TEST.VIEWS {}".format(batch_size, self.V))
         settings = stage_settings(cfg, lit=hasattr(render_machine, "normals"))   # every key checked, whether its stage is on or not
         self.icp_iter, self.photo_iter, self.sil_iter, self.flow_pnp_iter = (settings[k][0] for k in ("icp", "photo", "sil", "flow_pnp"))
         N = self.hyp_num
@@ -230,14 +240,22 @@ class Refiner(object):
         self.T_means = np.asarray(cfg.dataset.trans_means, dtype=np.float32)
         self.T_stds = np.asarray(cfg.dataset.trans_stds, dtype=np.float32)
         self.depth_observed = None   # read by the ICP stage and the depth hypothesis score (an INPUT_DEPTH graph holds it as a blob)
-        if self.icp_iter > 0 or (N > 1 and self.hyp_score_mode == "depth"):
+        if self.icp_iter > 0 or (N > 1 and self.hyp_score_mode == "depth") or (self.V > 1 and views_score == "depth"):
             self.depth_observed = self.batch["depth_observed"] if self.input_depth else torch.zeros((B, 1, H, W), dtype=torch.float32, device=d)
+        # groups of views (TEST.VIEWS > 1): the consensus after the loop and its outputs; the joint outputs of the stages below
+        self.views = ViewsConsensus(self, H, W, self.V, views_score, views_tau) if self.V > 1 else None
+        vc = self.views
+        self.views_score, self.views_choice, self.pose_rig, self.pose_views, self.status_views = (
+            vc.score, vc.choice, vc.pose_rig, vc.pose_views, vc.status) if vc else (None,) * 5
         # the pose stages that are on, each with its own buffers, and their outputs under the Refiner's public names: None when off
         self.stages = {name: cls(self, H, W, settings[name]) for name, cls in STAGES if settings[name][0] > 0}
         icp, photo, sil, flow = (self.stages.get(k) for k in ("icp", "photo", "sil", "flow_pnp"))
         self.pose_icp, self.icp_stats, self.status_icp = (icp.pose, icp.stats, icp.status) if icp else (None, None, None)
         self.pose_photo, self.photo_stats, self.status_photo = (photo.pose, photo.stats, photo.status) if photo else (None, None, None)
         self.pose_sil, self.sil_stats, self.status_sil = (sil.pose, sil.stats, sil.status) if sil else (None, None, None)
+        self.pose_rig_icp, self.icp_stats_group = (icp.pose_rig, icp.stats_group) if icp else (None, None)
+        self.pose_rig_photo, self.photo_stats_group = (photo.pose_rig, photo.stats_group) if photo else (None, None)
+        self.pose_rig_sil, self.sil_stats_group = (sil.pose_rig, sil.stats_group) if sil else (None, None)
         self.pose_flow_iter, self.se3_flow_iter, self.flow_pnp_stats, self.status_flow = (
             flow.pose_iter, flow.se3_iter, flow.stats, flow.status) if flow else (None, None, None, None)
         if sil and sil.mask is not None:   # SIL_MASK 'observed': load() fills it
@@ -287,7 +305,7 @@ class Refiner(object):
 
     # ------------------------------------------------------------------------------------------
     def load(self, image_observed, image_rendered, mask_observed, mask_rendered, src_pose, class_index, depth_observed=None,
-             depth_rendered=None, K=None, hyp_poses=None, det_boxes=None):
+             depth_rendered=None, K=None, hyp_poses=None, det_boxes=None, cam_T_rig=None):
         """copy one batch of blobs (any device) into the resident buffers (the depth planes: INPUT_DEPTH graphs only; depth_observed
         also when TEST.ICP_ITER > 0 or the depth hypothesis score is on).
         K: None (every re-render uses the config K) or the camera of each pair, (B,3,3) or (B,9), any device: the unlit re-renders of
@@ -296,11 +314,17 @@ class Refiner(object):
         poses given by the caller, all of them rendered
         det_boxes: TEST.COARSE_VIEWS > 0 only, and required then: (P,4) detection boxes {x0,x1,y0,y1}, continuous pixel extents (the
         inclusive int box {min_x,max_x,min_y,max_y} is {min_x-0.5, max_x+0.5, min_y-0.5, max_y+0.5}).  The coarse stage finds the
-        starting poses; src_pose, image_rendered and mask_rendered (and depth_rendered) are ignored and may be None"""
+        starting poses; src_pose, image_rendered and mask_rendered (and depth_rendered) are ignored and may be None
+        cam_T_rig: TEST.VIEWS > 1 only, and required then: (V,3,4) (one rig for every group) or (B,3,4), any device, the rigid
+        [R | t] with p_cam = [R | t] p_rig of every view; each row is checked (|R^T R - I| <= 1e-4, det R > 0)"""
         if self.coarse is not None:
             return self._load_coarse(image_observed, mask_observed, class_index, depth_observed, K, hyp_poses, det_boxes)
         if det_boxes is not None:
             raise ValueError("det_boxes needs TEST.COARSE_VIEWS > 0")
+        if self.views is not None:
+            self.views.cam_T_rig.copy_(torch.from_numpy(check_cam_T_rig(cam_T_rig, self.B, self.V)))
+        elif cam_T_rig is not None:
+            raise ValueError("cam_T_rig needs TEST.VIEWS > 1")
         self._check_hyp_poses(hyp_poses)
         if "sil" in self.stages and self.stages["sil"].which == "observed":
             # taken from the caller's segmentation itself, before any INIT_MASK kind replaces the loop's mask by a box
@@ -445,6 +469,8 @@ class Refiner(object):
     def load_staged(self, loader, staged):
         """take the next batch straight from a deepim.core.loader.TestDataLoader staging set: the raw pixels it uploaded are turned
         into the resident blobs by dim_test_blobs_from_raw / dim_box_mask on the current stream -- no host blobs, no extra copies"""
+        if self.V > 1:
+            raise ValueError("TEST.VIEWS > 1 is not supported by load_staged (a staged batch carries no extrinsics, use load(..., cam_T_rig=))")
         if self.coarse is not None:
             raise ValueError("TEST.COARSE_VIEWS > 0: the staged batches carry no detection boxes, use load(..., det_boxes=)")
         if "sil" in self.stages and self.stages["sil"].which == "observed":
@@ -531,6 +557,11 @@ class Refiner(object):
                 pose = self.poses_iter[it]
                 bbox_ren = bb_new
         ops.copy(b["src_pose"], pose)  # the blob ends up as the reference leaves it: the pose the last forward used
+        if self.views is not None:   # one pose per group first; then every stage from it, with one correction per group
+            self.views.run(self, self.poses_iter[self.test_iter - 1])
+            for name in [n for n in POST_LOOP if n in self.stages]:
+                self.stages[name].run(self, self.views.pose_views, self.views.pose_rig)
+            return
         for name in [n for n in POST_LOOP if n in self.stages]:   # independent of each other, all from the loop's last pose
             self.stages[name].run(self, self.poses_iter[self.test_iter - 1])
         if self.N > 1:
@@ -822,6 +853,7 @@ def pred_eval(config, refiner, batches, evaluator, result_file=None, logger=None
     src_pose).  out["coarse"] = {idx, score, status, pose}: per pair the HYP_NUM kept candidates of the coarse stage, best first.
     With TEST.VISUALIZE every refined batch is also drawn (deepim.core.visualize.PoseVisualizer: contour overlays of the ground truth,
     the initial and the refined poses under TEST.VIS_DIR); every output is that of the switch off."""
+    refuse_with_views(config, "pred_eval (its score tables are per pair, not per rig pose)")
     st = _eval_setup(config, refiner, evaluator, logger)
     for batch in batches:
         _collect_batch(st, refiner, batch)

@@ -24,6 +24,7 @@ import torch
 from lib.hip import ops
 from deepim.core.pose_stages import int_setting, stages_on
 from deepim.core.tester import Refiner, capture_graph
+from deepim.core.views import refuse_with_views
 from deepim.symbols.deepIM_flownet import source_size
 
 TRACK_MOTIONS = ("hold", "velocity")
@@ -88,6 +89,7 @@ def track_settings(cfg):
 def refuse_for_tracking(cfg, lit=False):
     """what a Tracker cannot be combined with; every ValueError names its key.  Reads the configuration only: no device work"""
     T, stages = cfg.TEST, stages_on(cfg)
+    refuse_with_views(cfg, "the Tracker (a track is one object in one camera)")
     if int(T.get("HYP_NUM", 1) or 1) > 1:
         raise ValueError("Tracker: TEST.HYP_NUM > 1 is not supported (a track has one pose per frame)")
     if int(T.get("COARSE_VIEWS", 0) or 0) > 0:

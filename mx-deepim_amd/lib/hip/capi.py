@@ -55,6 +55,14 @@ SIGNATURES = {
     "dim_sil_edge_field": (I, [P, I, I, I, I, P, P]),
     "dim_sil_workspace_bytes": (L, [I, I, I]),
     "dim_sil_refine": (I, [P, P, P, P, P, P, I, I, I, I, F, F, P, P, P, P, P]),
+    "dim_views_from_rig": (I, [P, P, I, I, P, P]),
+    "dim_views_consensus": (I, [P, P, I, P, P, I, I, P, P, P, P, P]),
+    "dim_icp_views_workspace_bytes": (L, [I, I, I, I]),
+    "dim_icp_refine_views": (I, [P, P, P, P, P, P, P, I, I, I, I, F, P, P, P, P, P, I, P, P, P, P]),
+    "dim_photo_views_workspace_bytes": (L, [I, I, I, I, I]),
+    "dim_photo_refine_views": (I, [P, P, P, P, P, P, P, I, I, I, I, I, F, F, I, P, P, P, P, P, I, P, P, P, P]),
+    "dim_sil_views_workspace_bytes": (L, [I, I, I, I]),
+    "dim_sil_refine_views": (I, [P, P, P, P, P, P, I, I, I, I, F, F, P, P, P, P, P, I, P, P, P, P]),
     "dim_hyp_expand": (I, [P, P, I, I, P, P]),
     "dim_hyp_broadcast": (I, [P, P, I, I, L, P]),
     "dim_pose_score_workspace_bytes": (L, [I, I, I]),

@@ -457,6 +457,128 @@ def sil_refine(depth_rendered, field, pose_in, K, iters, huber_px, max_px, bbox=
     return pose_out
 
 
+STATUS_VIEWS_NO_CONSENSUS = 32768   # DIM_STATUS_VIEWS_NO_CONSENSUS: dim_views_consensus found no eligible view in the sample's group
+VIEWS_MAX = 16                      # views per group (kGnMaxViews)
+
+
+def _views_shapes(cam_T_rig, B, V, who):
+    V = int(V)
+    if not 1 <= V <= VIEWS_MAX or B % V:
+        raise ValueError("{}: V = {} must be in 1..{} and divide B = {}".format(who, V, VIEWS_MAX, B))
+    assert tuple(cam_T_rig.shape) == (B, 3, 4), "{}: cam_T_rig must be ({},3,4), got {}".format(who, B, tuple(cam_T_rig.shape))
+    return B // V, V
+
+
+def views_from_rig(pose_rig, cam_T_rig, V, pose_views=None):
+    """dim_views_from_rig (restated by tests/views_reference.py): pose_rig (G,3,4), cam_T_rig (G*V,3,4) = X_b with p_cam = X_b p_rig,
+    sample b = g*V + v -> pose_views (G*V,3,4) = X_b pose_rig[g]"""
+    B = cam_T_rig.shape[0]
+    G, V = _views_shapes(cam_T_rig, B, V, "views_from_rig")
+    assert tuple(pose_rig.shape) == (G, 3, 4)
+    pose_views = pose_views if pose_views is not None else _new((B, 3, 4), pose_rig)
+    assert tuple(pose_views.shape) == (B, 3, 4)
+    check(lib().dim_views_from_rig(dptr(pose_rig, f32), dptr(cam_T_rig, f32), G, V, dptr(pose_views, f32), current_stream()))
+    return pose_views
+
+
+def views_consensus(score, pose, cam_T_rig, V, status=None, fatal_mask=0, choice=None, pose_rig=None, pose_views=None, status_out=None):
+    """dim_views_consensus: score (B,) f32 and pose (B,3,4) of every view, status (B,) int32 whose fatal_mask bits rule a view out
+    -> (choice (G,) int32 = the best eligible view of each group or -1, pose_rig (G,3,4) from that view, pose_views (B,3,4) = every
+    view's pose from pose_rig, the chosen view's own bit for bit); DIM_STATUS_VIEWS_NO_CONSENSUS is OR-ed into status_out (B,) int32"""
+    B = pose.shape[0]
+    G, V = _views_shapes(cam_T_rig, B, V, "views_consensus")
+    assert tuple(pose.shape) == (B, 3, 4) and score.numel() == B
+    assert (status is None or status.numel() == B) and (status_out is None or status_out.numel() == B)
+    choice = choice if choice is not None else _new((G,), pose, i32)
+    pose_rig = pose_rig if pose_rig is not None else _new((G, 3, 4), pose)
+    pose_views = pose_views if pose_views is not None else _new((B, 3, 4), pose)
+    assert choice.numel() == G and tuple(pose_rig.shape) == (G, 3, 4) and tuple(pose_views.shape) == (B, 3, 4)
+    check(lib().dim_views_consensus(dptr(score, f32), _opt(status, i32), int(fatal_mask), dptr(pose, f32), dptr(cam_T_rig, f32), G, V,
+                                    dptr(choice, i32), dptr(pose_rig, f32), dptr(pose_views, f32), _opt(status_out, i32), current_stream()))
+    return choice, pose_rig, pose_views
+
+
+def _views_tail(cam_T_rig, V, pose_rig_in, pose_rig_out, stats_group, B, n_iters, who):
+    """what the three joint stage wrappers share -> (pose_rig_out, the five trailing C arguments)"""
+    G, V = _views_shapes(cam_T_rig, B, V, who)
+    assert tuple(pose_rig_in.shape) == (G, 3, 4)
+    pose_rig_out = pose_rig_out if pose_rig_out is not None else _new((G, 3, 4), pose_rig_in)
+    assert tuple(pose_rig_out.shape) == (G, 3, 4) and (stats_group is None or stats_group.numel() >= 2 * G * n_iters)
+    return pose_rig_out, (dptr(cam_T_rig, f32), V, dptr(pose_rig_in, f32), dptr(pose_rig_out, f32), _opt(stats_group))
+
+
+def icp_views_workspace(B, H, W, V, device):
+    return _workspace_f64(lib().dim_icp_views_workspace_bytes(B, H, W, int(V)), device)
+
+
+def icp_refine_views(depth_rendered, depth_observed, pose_in, K, iters, max_dist, cam_T_rig, V, pose_rig_in, mask_observed=None, bbox=None,
+                     K_per_sample=None, pose_out=None, pose_rig_out=None, stats=None, stats_group=None, status=None, workspace=None):
+    """icp_refine with one correction per group of V calibrated views (dim_icp_refine_views, restated by tests/views_reference.py):
+    cam_T_rig (B,3,4), pose_rig_in (G,3,4), B = G*V, sample b = g*V + v.  -> (pose_out (B,3,4), pose_rig_out (G,3,4));
+    stats (B,iters,2) per sample as icp_refine, stats_group (G,iters,2) = (inliers, rms residual) of the group; the FEW_POINTS bit
+    goes to all V samples of a group whose step was skipped."""
+    B, _, H, W = depth_rendered.shape
+    assert depth_observed.shape == depth_rendered.shape and tuple(pose_in.shape) == (B, 3, 4)
+    assert mask_observed is None or mask_observed.shape == depth_rendered.shape
+    pose_rig_out, tail = _views_tail(cam_T_rig, V, pose_rig_in, pose_rig_out, stats_group, B, int(iters), "icp_refine_views")
+    pose_out, keep, p = _gn_tail(pose_in, K, K_per_sample, bbox, pose_out, stats, status, workspace,
+                                 lib().dim_icp_views_workspace_bytes(B, H, W, int(V)))
+    check(lib().dim_icp_refine_views(dptr(depth_rendered, f32), dptr(depth_observed, f32), _opt(mask_observed), p["bbox"], p["pose_in"],
+                                     p["K9"], p["kps"], B, H, W, int(iters), float(max_dist), p["workspace"], p["pose_out"], p["stats"],
+                                     p["status"], *tail, current_stream()))
+    return pose_out, pose_rig_out
+
+
+def photo_views_workspace(B, H, W, levels, V, device):
+    nbytes = lib().dim_photo_views_workspace_bytes(B, H, W, int(levels), int(V))
+    if nbytes <= 0:
+        raise ValueError("photo_views_workspace: B = {}, a {}x{} frame, {} levels and V = {} are refused (levels 1..5, coarsest level "
+                         ">= 3x3)".format(B, H, W, levels, V))
+    return _workspace_f64(nbytes, device)
+
+
+def photo_refine_views(image_observed, image_rendered, depth_rendered, pose_in, K, levels, iters, huber, gate, cam_T_rig, V, pose_rig_in,
+                       gain=True, bbox=None, K_per_sample=None, pose_out=None, pose_rig_out=None, stats=None, stats_group=None, status=None,
+                       workspace=None):
+    """photo_refine with one correction per group of V calibrated views (dim_photo_refine_views); the views' arguments and results as
+    icp_refine_views, stats_group (G,levels*iters,2)"""
+    B, _, H, W = depth_rendered.shape
+    assert tuple(image_observed.shape) == (B, 3, H, W) and tuple(image_rendered.shape) == (B, 3, H, W)
+    assert tuple(depth_rendered.shape) == (B, 1, H, W) and tuple(pose_in.shape) == (B, 3, 4)
+    assert stats is None or stats.numel() >= 2 * B * int(levels) * int(iters)
+    assert (status is None or status.numel() == B) and (bbox is None or bbox.numel() == 4 * B)
+    pose_rig_out, tail = _views_tail(cam_T_rig, V, pose_rig_in, pose_rig_out, stats_group, B, int(levels) * int(iters), "photo_refine_views")
+    if workspace is None:
+        workspace = photo_views_workspace(B, H, W, levels, V, pose_in.device)
+    pose_out, keep, p = _gn_tail(pose_in, K, K_per_sample, bbox, pose_out, stats, status, workspace,
+                                 lib().dim_photo_views_workspace_bytes(B, H, W, int(levels), int(V)))
+    check(lib().dim_photo_refine_views(dptr(image_observed, f32), dptr(image_rendered, f32), dptr(depth_rendered, f32), p["bbox"],
+                                       p["pose_in"], p["K9"], p["kps"], B, H, W, int(levels), int(iters), float(huber), float(gate),
+                                       int(bool(gain)), p["workspace"], p["pose_out"], p["stats"], p["status"], *tail, current_stream()))
+    return pose_out, pose_rig_out
+
+
+def sil_views_workspace(B, H, W, V, device):
+    return _workspace_f64(lib().dim_sil_views_workspace_bytes(B, H, W, int(V)), device)
+
+
+def sil_refine_views(depth_rendered, field, pose_in, K, iters, huber_px, max_px, cam_T_rig, V, pose_rig_in, bbox=None, K_per_sample=None,
+                     pose_out=None, pose_rig_out=None, stats=None, stats_group=None, status=None, workspace=None):
+    """sil_refine with one correction per group of V calibrated views (dim_sil_refine_views); the views' arguments and results as
+    icp_refine_views"""
+    B, _, H, W = depth_rendered.shape
+    assert tuple(depth_rendered.shape) == (B, 1, H, W) and tuple(field.shape) == (B, H, W) and tuple(pose_in.shape) == (B, 3, 4)
+    assert stats is None or stats.numel() >= 2 * B * int(iters)
+    assert (status is None or status.numel() == B) and (bbox is None or bbox.numel() == 4 * B)
+    pose_rig_out, tail = _views_tail(cam_T_rig, V, pose_rig_in, pose_rig_out, stats_group, B, int(iters), "sil_refine_views")
+    pose_out, keep, p = _gn_tail(pose_in, K, K_per_sample, bbox, pose_out, stats, status, workspace,
+                                 lib().dim_sil_views_workspace_bytes(B, H, W, int(V)))
+    check(lib().dim_sil_refine_views(dptr(depth_rendered, f32), dptr(field, i32), p["bbox"], p["pose_in"], p["K9"], p["kps"], B, H, W,
+                                     int(iters), float(huber_px), float(max_px), p["workspace"], p["pose_out"], p["stats"], p["status"],
+                                     *tail, current_stream()))
+    return pose_out, pose_rig_out
+
+
 STATUS_HYP_NO_SCORE = 64  # DIM_STATUS_HYP_NO_SCORE: dim_pose_score had < 64 counted pixels, a constant plane or a non-finite sum
 HYP_SCORE_ID = {"rgb": 0, "depth": 1}   # DIM_HYP_SCORE_RGB / DIM_HYP_SCORE_DEPTH
 

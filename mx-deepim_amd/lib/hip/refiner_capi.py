@@ -32,6 +32,9 @@ class CRefiner(object):
         if int(cfg.TEST.get("COARSE_VIEWS", 0) or 0) > 0:
             raise ValueError("the C loop object (dim_refiner_create / dim_refiner_run) starts from the poses it is given: TEST.COARSE_VIEWS > 0 "
                              "runs through deepim.core.tester.Refiner")
+        if int(cfg.TEST.get("VIEWS", 1) or 1) > 1:
+            raise ValueError("the C loop object (dim_refiner_create / dim_refiner_run) is the loop alone, one pose per sample: TEST.VIEWS > 1 "
+                             "runs through deepim.core.tester.Refiner")
         self.B, self.T = int(batch_size), int(cfg.TEST.test_iter)
         self.device = torch.device(device)
         names = [n for n in arg_params if n.split("_weight")[0].split("_bias")[0] in
