@@ -16,6 +16,8 @@ pytestmark = pytest.mark.gpu
 import guard_arena  # noqa: E402
 import icp_reference as ir  # noqa: E402
 import icp_terms_scenes as sc  # noqa: E402
+from gn_terms_io import bits as _bits, block_order_sum as _block_order_sum, split_workspace  # noqa: E402
+from gn_terms_io import state_of as _state, stats_of as _stats_of  # noqa: E402
 from test_split_terms import BAR_FACTOR  # noqa: E402
 
 DEV = "cuda:0"
@@ -52,30 +54,8 @@ def _run(hip_lib, scenes, iters, use_mask=None, use_bbox=None, per_pair_K=None):
                          status=status, workspace=work.view())
     work.check("dim_icp_refine workspace, {} x {}, B = {}".format(H, W, B))
     ws = work.view().cpu().numpy().copy()
-    return dict(pose=out.cpu().numpy(), stats=stats.cpu().numpy(), status=status.cpu().numpy(), state=ws[:16 * B].reshape(B, 16),
-                partial=ws[16 * B:].reshape(B, 16, 32))
-
-
-def _block_order_sum(partial):
-    """the 16 workgroup partials added in block order with plain float64 adds, as gn_solve_kernel does"""
-    S = np.zeros(ir.N_TERMS)
-    for k in range(16):
-        S = S + partial[k, :ir.N_TERMS]
-    return S
-
-
-def _stats_of(S):
-    N, rr = S[27], S[28]
-    return np.array([np.float32(N), np.float32(np.sqrt(rr / N)) if N > 0 else np.float32(0.0)], np.float32)
-
-
-def _state(run, b=0):
-    st = run["state"][b]
-    return st[:9].reshape(3, 3).copy(), st[9:12].copy(), st[12]
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32 if a.dtype == np.float32 else np.uint64)
+    state, partial = split_workspace(ws, B)
+    return dict(pose=out.cpu().numpy(), stats=stats.cpu().numpy(), status=status.cpu().numpy(), state=state, partial=partial)
 
 
 def _terms_within_bar(s, R, t, partial, what):
