@@ -50,6 +50,7 @@ extern "C" {
 #define DIM_STATUS_TRACK_REINIT 8192 /* dim_track_update: ... and was re-initialised from the offered pose */
 #define DIM_STATUS_TRACK_OCCLUDED 16384 /* dim_track_update_occ: too little of the track's render is visible on this frame (it coasts, or is lost when the budget is spent) */
 #define DIM_STATUS_VIEWS_NO_CONSENSUS 32768 /* dim_views_consensus: no view of the sample's group was eligible (view 0 was used) */
+#define DIM_STATUS_VIEWS_CALIB_HELD 65536 /* dim_icp_refine_rig: the sample's camera shared too few points with the gauge camera in an iteration (its extrinsic was held) */
 
 const char* dim_last_error(void);
 /* library / device probe: fills name (<= n bytes), returns number of compute units or <0 */
@@ -359,7 +360,40 @@ int dim_sil_refine(const float* depth_rendered, const int* field, const int* bbo
  *   the 29-term sums spread over lanes, the fusion on one lane; no atomics, fixed order: a replay is bit-identical.
  *   Launches as the single-view entry.  iters == 0 copies pose_in to pose_out and pose_rig_in to pose_rig_out.  V outside 1 .. 16,
  *   B % V != 0, a NULL cam_T_rig, pose_rig_in or pose_rig_out and every condition of the single-view entry return DIM_ERR_ARG before
- *   anything is enqueued. */
+ *   anything is enqueued.
+ *
+ * dim_icp_refine_rig: dim_icp_refine_views with the rig's extrinsics refined along (a small bundle adjustment over the G objects of
+ *   the batch; restated in float64 by tests/rig_reference.py).  Arguments, checks and the accumulate launch are those of
+ *   dim_icp_refine_views.  cam_T_rig stays (B,3,4): the V rows of group 0 are read as the nominal X_v, the rows of the other groups
+ *   must repeat them (the caller's check).  pose_in[b] is (about) X_v pose_rig_in[g], as dim_views_consensus leaves it.
+ *   Unknowns: a correction C_v per camera, X'_v = C_v X_v, with C_0 = I for good (camera 0 is the gauge: its row never changes), and
+ *   a rig-frame correction D_g per object; all from the identity.  The correction of sample b, what its accumulate kernel linearises
+ *   at, is S_b = X'_v D_g X_v^-1 (the inverse of the NOMINAL X_v: depth_rendered was drawn at pose_in), so S_b pose_in[b] = X'_v D_g P_g.
+ *   A left perturbation exp(alpha_v) of C_v and exp(eta_g) of D_g moves sample b by the camera-frame twist alpha_v + Ad(X'_v) eta_g,
+ *   Ad([R|t]) = [[R,0],[[t]x R,R]] at the CURRENT extrinsic (never-moved cameras use the nominal row exactly).
+ *   One iteration: s_gv, A_gv, g_gv, N_gv, rr_gv as the joint solve takes them (block order); W_gv = A_gv Ad_v,
+ *   H_ee[g] = sum_v Ad_v^T W_gv, r_e[g] = -sum_v Ad_v^T g_gv, H_aa[v] = sum_g A_gv, r_a[v] = -sum_g g_gv, coupling block
+ *   (alpha_v, eta_g) = W_gv; every sum ascending, float64.  Who takes part, from the counts alone: group g is active when
+ *   N_g = sum_v N_gv >= 64 (an inactive group enters no sum, keeps D_g, and its V samples get DIM_STATUS_ICP_FEW_POINTS); view v >= 1
+ *   is free when the sum of N_gv over the active groups with N_g0 >= 64 is >= 64, else held for the iteration: alpha_v = 0, its block
+ *   leaves the reduced system, its samples still count in H_ee and r_e at X'_v, and its samples in all groups get
+ *   DIM_STATUS_VIEWS_CALIB_HELD.  H_ee[g] and H_aa[v] of the free views get + 1e-9 tr/6 I.  S = H_aa - sum_g W_g H_ee[g]^-1 W_g^T and
+ *   rs = r_a - sum_g W_g H_ee[g]^-1 r_e[g] over the free views (H_ee^-1 through the 6x6 Cholesky), S (at most 90 x 90) by Cholesky,
+ *   eta_g = H_ee[g]^-1 r_e[g] - (H_ee[g]^-1 W_g^T) alpha.  A pivot that is not > 0 anywhere skips the whole step:
+ *   DIM_STATUS_ICP_FEW_POINTS on all B samples, nothing moves.  Otherwise C_v <- [Rodrigues(alpha_v) | alpha_v,trans] C_v,
+ *   D_g <- [Rodrigues(eta_g) | eta_g,trans] D_g and every state row is rewritten.  With no free view (V = 1 always) the step is
+ *   dim_icp_refine_views' per active group, bit for bit, a failed Cholesky flagging its own group only.
+ *   After the last iteration pose_out[b] = float32(S_b pose_in[b]), pose_rig_out[g] = float32(D_g pose_rig_in[g]) and
+ *   cam_T_rig_out[g V + v] (B,3,4, required, not cam_T_rig itself) = float32(C_v X_v) for every g; a group that never stepped gets
+ *   pose_in and pose_rig_in bit for bit, a view that never moved its nominal row bit for bit.  iters == 0 copies the three inputs.
+ *   stats, stats_group as dim_icp_refine_views; stats_view (V, iters, 2) f32 or NULL = (sum_g N_gv, sqrt(sum_g rr_gv / that)) over
+ *   all groups in ascending g, 0 for an empty view.
+ *   workspace: dim_icp_rig_workspace_bytes bytes = the joint layout unchanged, then V x 16 doubles of rig state {R, t of C_v, moved,
+ *   pad}, then per group V x (32 + 36 + 36) + 8 doubles: {s_gv (32 each), W_gv, H_ee^-1 W_gv^T, then H_ee^-1 r_e (6), active, H_ee
+ *   passed}.  8-byte aligned, no initialisation needed.  Three launches per iteration: the accumulate launch, one workgroup per group
+ *   (the 6x6 work spread over 128 lanes), one workgroup of 256 lanes for the reduced system (S a packed triangle in LDS, one lane per
+ *   row).  Float64, no atomics, fixed ascending order: a replay is bit-identical.  Argument errors as dim_icp_refine_views, and a
+ *   NULL cam_T_rig_out, return DIM_ERR_ARG before anything is enqueued. */
 int dim_views_from_rig(const float* pose_rig, const float* cam_T_rig, int G, int V, float* pose_views, void* stream);
 int dim_views_consensus(const float* score, const int* status, int fatal_mask, const float* pose, const float* cam_T_rig, int G, int V,
                         int* choice, float* pose_rig, float* pose_views, int* status_out, void* stream);
@@ -368,6 +402,12 @@ int dim_icp_refine_views(const float* depth_rendered, const float* depth_observe
                          const float* pose_in, const float* K9, const float* K_per_sample, int B, int H, int W, int iters, float max_dist,
                          void* workspace, float* pose_out, float* stats, int* status, const float* cam_T_rig, int V,
                          const float* pose_rig_in, float* pose_rig_out, float* stats_group, void* stream);
+long dim_icp_rig_workspace_bytes(int B, int H, int W, int V);
+int dim_icp_refine_rig(const float* depth_rendered, const float* depth_observed, const float* mask_observed, const int* bbox,
+                       const float* pose_in, const float* K9, const float* K_per_sample, int B, int H, int W, int iters, float max_dist,
+                       void* workspace, float* pose_out, float* stats, int* status, const float* cam_T_rig, int V,
+                       const float* pose_rig_in, float* pose_rig_out, float* stats_group, float* cam_T_rig_out, float* stats_view,
+                       void* stream);
 long dim_photo_views_workspace_bytes(int B, int H, int W, int levels, int V);
 int dim_photo_refine_views(const float* image_observed, const float* image_rendered, const float* depth_rendered, const int* bbox,
                            const float* pose_in, const float* K9, const float* K_per_sample, int B, int H, int W, int levels, int iters,

@@ -9,7 +9,8 @@
 //   gn_solve_kernel        (twist_solve.h) one workgroup per pair: sums the partials, Cholesky in float64,
 //                          T_delta <- [Rodrigues(omega) | v] T_delta, stats / status, and after the last iteration pose_out = T_delta T0
 //   gn_solve_views_kernel  (twist_solve.h) in its place for dim_icp_refine_views: one workgroup per group of V calibrated views
-// Two launches per iteration; nothing allocates or synchronises, so the stage is graph-capturable.
+//   gn_rig_group_kernel, gn_rig_solve_kernel  (twist_solve.h) in its place for dim_icp_refine_rig: the rig's extrinsics refined along
+// Two launches per iteration (three for dim_icp_refine_rig); nothing allocates or synchronises, so the stage is graph-capturable.
 #include "common.h"
 #include "twist_solve.h"
 
@@ -94,10 +95,10 @@ extern "C" long dim_icp_workspace_bytes(int B, int H, int W) {
   return gn_workspace_bytes(B);
 }
 
-// both entries: views == nullptr is dim_icp_refine
+// all three entries: views == nullptr is dim_icp_refine, rig != nullptr (with views) dim_icp_refine_rig
 static int icp_run(const float* depth_rendered, const float* depth_observed, const float* mask_observed, const int* bbox, const float* pose_in,
                    const float* K9, const float* K_per_sample, int B, int H, int W, int iters, float max_dist, void* workspace,
-                   float* pose_out, float* stats, int* status, const GnViews* views, void* stream) {
+                   float* pose_out, float* stats, int* status, const GnViews* views, const GnRig* rig, void* stream) {
   DIM_REQUIRE(B > 0, "icp_refine: B = %d", B);
   DIM_REQUIRE(iters >= 0, "icp_refine: iters = %d", iters);
   DIM_REQUIRE(max_dist > 0.f, "icp_refine: max_dist must be > 0");
@@ -105,25 +106,33 @@ static int icp_run(const float* depth_rendered, const float* depth_observed, con
   DIM_REQUIRE(depth_rendered && depth_observed && pose_in && K9 && workspace && pose_out, "icp_refine: null pointer");
   DIM_REQUIRE(!views || gn_views_ok(*views, B), "icp_refine_views: V in 1 .. %d dividing B = %d, cam_T_rig, pose_rig_in and pose_rig_out required",
               kGnMaxViews, B);
+  DIM_REQUIRE(!rig || (views && rig->cam_T_rig_out), "icp_refine_rig: cam_T_rig_out required");
   if (iters == 0) {
-    const int rc = dim_copy_words(pose_out, pose_in, 12L * B, stream);
-    return (rc != DIM_OK || !views) ? rc : dim_copy_words(views->pose_rig_out, views->pose_rig_in, 12L * (B / views->V), stream);
+    int rc = dim_copy_words(pose_out, pose_in, 12L * B, stream);
+    if (rc == DIM_OK && views) rc = dim_copy_words(views->pose_rig_out, views->pose_rig_in, 12L * (B / views->V), stream);
+    return (rc != DIM_OK || !rig) ? rc : dim_copy_words(rig->cam_T_rig_out, views->cam_T_rig, 12L * B, stream);
   }
   const PinholeCam k9 = cam_of_k9(K9);
   const GnWorkspace ws(workspace, B);
-  gn_iterate_either<DIM_STATUS_ICP_FEW_POINTS>(ws, (double*)((char*)workspace + gn_workspace_bytes(B)), B, views, iters, pose_in, pose_out,
-                                               stats, status, as_stream(stream), [&](int it) {
+  double* group_state = (double*)((char*)workspace + gn_workspace_bytes(B));
+  const auto accumulate = [&](int it) {
     hipLaunchKernelGGL(icp_accumulate_kernel, dim3(kGnBlocks, B), dim3(256), 0, as_stream(stream), depth_rendered, depth_observed,
                        mask_observed, bbox, k9, K_per_sample, H, W, max_dist, it, (const double*)ws.state, ws.partial);
-  });
-  return check_launch(views ? "icp_refine_views" : "icp_refine");
+  };
+  if (rig)
+    gn_iterate_rig<DIM_STATUS_ICP_FEW_POINTS>(ws, group_state, B, *views, *rig, iters, pose_in, pose_out, stats, status, as_stream(stream),
+                                              accumulate);
+  else
+    gn_iterate_either<DIM_STATUS_ICP_FEW_POINTS>(ws, group_state, B, views, iters, pose_in, pose_out, stats, status, as_stream(stream),
+                                                 accumulate);
+  return check_launch(rig ? "icp_refine_rig" : views ? "icp_refine_views" : "icp_refine");
 }
 
 extern "C" int dim_icp_refine(const float* depth_rendered, const float* depth_observed, const float* mask_observed, const int* bbox,
                               const float* pose_in, const float* K9, const float* K_per_sample, int B, int H, int W, int iters,
                               float max_dist, void* workspace, float* pose_out, float* stats, int* status, void* stream) {
   return icp_run(depth_rendered, depth_observed, mask_observed, bbox, pose_in, K9, K_per_sample, B, H, W, iters, max_dist, workspace, pose_out,
-                 stats, status, nullptr, stream);
+                 stats, status, nullptr, nullptr, stream);
 }
 
 extern "C" long dim_icp_views_workspace_bytes(int B, int H, int W, int V) {
@@ -138,5 +147,22 @@ extern "C" int dim_icp_refine_views(const float* depth_rendered, const float* de
                                     int V, const float* pose_rig_in, float* pose_rig_out, float* stats_group, void* stream) {
   const GnViews views{cam_T_rig, V, pose_rig_in, pose_rig_out, stats_group};
   return icp_run(depth_rendered, depth_observed, mask_observed, bbox, pose_in, K9, K_per_sample, B, H, W, iters, max_dist, workspace, pose_out,
-                 stats, status, &views, stream);
+                 stats, status, &views, nullptr, stream);
+}
+
+extern "C" long dim_icp_rig_workspace_bytes(int B, int H, int W, int V) {
+  (void)H;
+  (void)W;
+  return (B <= 0 || V <= 0) ? 0 : gn_workspace_bytes(B) + gn_views_state_bytes(B, V) + gn_rig_state_bytes(B, V);
+}
+
+extern "C" int dim_icp_refine_rig(const float* depth_rendered, const float* depth_observed, const float* mask_observed, const int* bbox,
+                                  const float* pose_in, const float* K9, const float* K_per_sample, int B, int H, int W, int iters,
+                                  float max_dist, void* workspace, float* pose_out, float* stats, int* status, const float* cam_T_rig, int V,
+                                  const float* pose_rig_in, float* pose_rig_out, float* stats_group, float* cam_T_rig_out,
+                                  float* stats_view, void* stream) {
+  const GnViews views{cam_T_rig, V, pose_rig_in, pose_rig_out, stats_group};
+  const GnRig rig{cam_T_rig_out, stats_view};
+  return icp_run(depth_rendered, depth_observed, mask_observed, bbox, pose_in, K9, K_per_sample, B, H, W, iters, max_dist, workspace, pose_out,
+                 stats, status, &views, &rig, stream);
 }

@@ -3,7 +3,7 @@
 // the Gauss-Newton stages have in common: the workspace layout, the camera and box of a pair, the solve kernel, the pieces of an
 // accumulate kernel (pose load, normal-equation terms, partial store) and the host loop over the two launches of an iteration; and the
 // joint solve over the calibrated views of one object (gn_solve_views_kernel, gn_iterate_views) with the rigid 3x4 algebra it and
-// views.hip share.
+// views.hip share; and the same with the rig's extrinsics refined along (gn_rig_group_kernel, gn_rig_solve_kernel, gn_iterate_rig).
 #pragma once
 #include "block_sum.h"
 #include "common.h"
@@ -371,6 +371,462 @@ __global__ __launch_bounds__(64) void gn_solve_views_kernel(const double* __rest
   }
 }
 
+// ---- the rig's extrinsics refined together with the object poses (tests/rig_reference.py restates the rule, include/deepim_hip.h
+// states it).  Unknowns: a correction C_v per camera, X'_v = C_v X_v with C_0 = I for good, and a rig-frame correction D_g per group;
+// X_v = cam_T_rig row v of group 0.  Two launches per iteration after the stage's accumulate launch:
+//   gn_rig_group_kernel  one workgroup per group: the block-order sums s_gv, W_gv = A_gv Ad(X'_v), H_ee = sum_v Ad_v^T W_gv,
+//                        r_e = -sum_v Ad_v^T g_gv, the 6x6 Cholesky of the damped H_ee and through it Y_gv = H_ee^-1 W_gv^T and
+//                        z = H_ee^-1 r_e, all into the group's block of the workspace
+//   gn_rig_solve_kernel  one workgroup: who takes part, the Schur complement S over the free views as a packed triangle in LDS, its
+//                        Cholesky with one lane per row, alpha, eta_g = z_g - sum_v Y_gv alpha_v, the updates and every state row
+// Workspace after the joint layout: [rig state V x kGnState = {R, t of C_v, moved, pad}] then per group gn_rig_group_doubles(V) doubles:
+// [s V x kGnSlot][W V x 36][Y V x 36][z 6, active, H_ee passed the Cholesky].  Every word that is read was written in the same
+// iteration (or, state, in the one before): no initialisation.  Sums are positional and ascending: no atomics.
+constexpr int kGnRigLanes = 256;   // of gn_rig_solve_kernel; at most 6 (kGnMaxViews - 1) = 90 rows in S
+constexpr int kGnRigRows = 6 * (kGnMaxViews - 1);
+
+__host__ __device__ inline long gn_rig_group_doubles(int V) { return (long)V * (kGnSlot + 72) + 8; }
+
+// index of (a, e), a <= e, among the 21 upper-triangle terms; the symmetric entry (a, e) of A from the 29 sums
+__device__ __forceinline__ int gn_tri(int a, int e) { return a * 6 - a * (a - 1) / 2 + (e - a); }
+__device__ __forceinline__ double gn_sym(const double* s, int a, int e) { return a <= e ? s[gn_tri(a, e)] : s[gn_tri(e, a)]; }
+
+// X'_v = C_v X_v; a camera that never moved keeps its nominal row exactly
+__device__ inline void gn_rig_extrinsic(const float* __restrict__ cam_T_rig, const double* rig_state, int v, bool have_state, double* Rx,
+                                        double* tx) {
+  double Rn[9], tn[3];
+  rigid_load(cam_T_rig + 12 * v, Rn, tn);
+  const double* c = rig_state + (long)v * kGnState;
+  if (have_state && c[12] != 0.0) {
+    double Rc[9], tc[3];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) Rc[k] = c[k];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) tc[k] = c[9 + k];
+    rigid_mul(Rc, tc, Rn, tn, Rx, tx);
+  } else {
+#pragma unroll
+    for (int k = 0; k < 9; ++k) Rx[k] = Rn[k];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) tx[k] = tn[k];
+  }
+}
+
+// T pose (3x4 float32) in float64, rounded once
+__device__ inline void rigid_apply_store(const double* R, const double* t, const float* __restrict__ T0, float* __restrict__ out) {
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+#pragma unroll
+    for (int j = 0; j < 3; ++j)
+      out[4 * i + j] = (float)(R[3 * i] * (double)T0[j] + R[3 * i + 1] * (double)T0[4 + j] + R[3 * i + 2] * (double)T0[8 + j]);
+    out[4 * i + 3] = (float)(R[3 * i] * (double)T0[3] + R[3 * i + 1] * (double)T0[7] + R[3 * i + 2] * (double)T0[11] + t[i]);
+  }
+}
+
+// group g = blockIdx.x.  The operations on H_ee and its solve are those of gn_solve_views_kernel and cholesky_solve6 in their order
+// (the pivots recomputed by every lane, the rows and the right-hand sides spread over lanes), so with no free view z is that kernel's xi.
+template <int LANES>   // a template so that the header may hold it: the driver launches it with 128
+__global__ __launch_bounds__(LANES) void gn_rig_group_kernel(const double* __restrict__ partial, const double* __restrict__ rig_state,
+                                                          double* __restrict__ rig_group, const float* __restrict__ cam_T_rig, int V, int it,
+                                                          int iters, float* __restrict__ stats, float* __restrict__ stats_group) {
+  const int g = blockIdx.x, tid = threadIdx.x;
+  __shared__ double s[kGnMaxViews][kGnSlot];
+  __shared__ double Ad[kGnMaxViews][36], Wl[kGnMaxViews][36];
+  __shared__ double H[36], L[36], gs[8];   // gs: sum_v Ad_v^T g_v (6), N, rr
+  double* o_s = rig_group + (long)g * gn_rig_group_doubles(V);
+  double* o_W = o_s + V * kGnSlot;
+  double* o_Y = o_W + V * 36;
+  double* o_tail = o_Y + V * 36;
+  for (int idx = tid; idx < V * kGnSlot; idx += LANES) {
+    const int v = idx / kGnSlot, term = idx % kGnSlot;
+    if (term < kGnTerms) {
+      const long b = (long)g * V + v;
+      double sum = 0.0;
+      for (int k = 0; k < kGnBlocks; ++k) sum += partial[(b * kGnBlocks + k) * kGnSlot + term];
+      s[v][term] = sum;
+      o_s[idx] = sum;
+    }
+  }
+  if (tid < V) {
+    double Rx[9], tx[3];
+    gn_rig_extrinsic(cam_T_rig, rig_state, tid, it > 0, Rx, tx);
+    const double Tx[9] = {0.0, -tx[2], tx[1], tx[2], 0.0, -tx[0], -tx[1], tx[0], 0.0};
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+#pragma unroll
+      for (int j = 0; j < 3; ++j) {
+        Ad[tid][6 * i + j] = Ad[tid][6 * (3 + i) + 3 + j] = Rx[3 * i + j];
+        Ad[tid][6 * i + 3 + j] = 0.0;
+        Ad[tid][6 * (3 + i) + j] = Tx[3 * i] * Rx[j] + Tx[3 * i + 1] * Rx[3 + j] + Tx[3 * i + 2] * Rx[6 + j];
+      }
+    }
+  }
+  __syncthreads();
+  if (tid < V && stats) {
+    const long b = (long)g * V + tid;
+    const double Nv = s[tid][27], rrv = s[tid][28];
+    stats[(b * iters + it) * 2 + 0] = (float)Nv;
+    stats[(b * iters + it) * 2 + 1] = Nv > 0.0 ? (float)sqrt(rrv / Nv) : 0.f;
+  }
+  for (int idx = tid; idx < V * 36; idx += LANES) {
+    const int v = idx / 36, i = (idx % 36) / 6, j = idx % 6;
+    double m = 0.0;
+    for (int q = 0; q < 6; ++q) m += gn_sym(s[v], i, q) * Ad[v][6 * q + j];
+    Wl[v][6 * i + j] = m;
+    o_W[idx] = m;
+  }
+  __syncthreads();
+  if (tid < 36) {
+    const int i = tid / 6, j = tid % 6;
+    double a = 0.0;
+    for (int v = 0; v < V; ++v) {
+      double m = 0.0;
+      for (int q = 0; q < 6; ++q) m += Ad[v][6 * q + i] * Wl[v][6 * q + j];
+      a += m;
+    }
+    H[tid] = a;
+  } else if (tid < 42) {
+    const int i = tid - 36;
+    double a = 0.0;
+    for (int v = 0; v < V; ++v) {
+      double m = 0.0;
+      for (int q = 0; q < 6; ++q) m += Ad[v][6 * q + i] * s[v][21 + q];
+      a += m;
+    }
+    gs[i] = a;
+  } else if (tid == 42) {
+    double N = 0.0, rr = 0.0;
+    for (int v = 0; v < V; ++v) {
+      N += s[v][27];
+      rr += s[v][28];
+    }
+    gs[6] = N;
+    gs[7] = rr;
+    if (stats_group) {
+      stats_group[((long)g * iters + it) * 2 + 0] = (float)N;
+      stats_group[((long)g * iters + it) * 2 + 1] = N > 0.0 ? (float)sqrt(rr / N) : 0.f;
+    }
+  }
+  __syncthreads();
+  const bool active = gs[6] >= (double)kGnMinPoints;
+  bool ok = active;
+  if (active) {   // the same for every lane
+    const double damp = 1e-9 * (H[0] + H[7] + H[14] + H[21] + H[28] + H[35]) / 6.0;
+    for (int j = 0; j < 6; ++j) {
+      double sp = H[7 * j] + damp;
+      for (int k = 0; k < j; ++k) sp -= L[6 * j + k] * L[6 * j + k];
+      if (!(sp > 0.0)) ok = false;   // what follows is never used; the barriers stay
+      const double d = sqrt(sp);
+      if (tid == j) {
+        L[7 * j] = d;
+      } else if (tid > j && tid < 6) {
+        double v = H[6 * tid + j];
+        for (int k = 0; k < j; ++k) v -= L[6 * tid + k] * L[6 * j + k];
+        L[6 * tid + j] = v / d;
+      }
+      __syncthreads();
+    }
+  }
+  if (ok) {
+    for (int c = tid; c <= 6 * V; c += LANES) {   // the columns of W_g^T, then r_e
+      const int v = c / 6, k = c % 6;
+      double rhs[6], y[6], x[6];
+#pragma unroll
+      for (int i = 0; i < 6; ++i) rhs[i] = c < 6 * V ? Wl[v][6 * k + i] : -gs[i];
+#pragma unroll
+      for (int i = 0; i < 6; ++i) {
+        double a = rhs[i];
+#pragma unroll
+        for (int q = 0; q < i; ++q) a -= L[6 * i + q] * y[q];
+        y[i] = a / L[7 * i];
+      }
+#pragma unroll
+      for (int i = 5; i >= 0; --i) {
+        double a = y[i];
+#pragma unroll
+        for (int q = i + 1; q < 6; ++q) a -= L[6 * q + i] * x[q];
+        x[i] = a / L[7 * i];
+      }
+#pragma unroll
+      for (int i = 0; i < 6; ++i) {
+        if (c < 6 * V)
+          o_Y[v * 36 + 6 * i + k] = x[i];
+        else
+          o_tail[i] = x[i];
+      }
+    }
+  }
+  if (tid == 0) {
+    o_tail[6] = active ? 1.0 : 0.0;
+    o_tail[7] = ok ? 1.0 : 0.0;
+  }
+}
+
+// entry (i, j), i >= j, of the packed lower triangle
+__device__ __forceinline__ int gn_packed(int i, int j) { return i * (i + 1) / 2 + j; }
+
+// sum over the active groups, in ascending g, of term(the group's block).  Four groups at a time: their flags and operands are loaded
+// before any is added, so a lane waits for memory once per four groups and not twice per group (an inactive group's term is computed
+// from whatever its block holds and dropped)
+template <class Term>
+__device__ __forceinline__ double gn_rig_sum_active(const double* __restrict__ rig_group, long gd, int oT, int G, Term term) {
+  double t = 0.0;
+  for (int g0 = 0; g0 < G; g0 += 4) {
+    double m[4];
+    bool on[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const double* blk = rig_group + min(g0 + u, G - 1) * gd;
+      on[u] = g0 + u < G && blk[oT + 6] != 0.0;
+      m[u] = term(blk);
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+      if (on[u]) t += m[u];
+  }
+  return t;
+}
+
+template <int FAIL_BIT>
+__global__ __launch_bounds__(kGnRigLanes) void gn_rig_solve_kernel(double* __restrict__ state, double* __restrict__ group_state,
+                                                                  double* __restrict__ rig_state, const double* __restrict__ rig_group,
+                                                                  const float* __restrict__ cam_T_rig, int B, int V, int it, int iters,
+                                                                  const float* __restrict__ pose_in, float* __restrict__ pose_out,
+                                                                  const float* __restrict__ pose_rig_in, float* __restrict__ pose_rig_out,
+                                                                  float* __restrict__ cam_T_rig_out, float* __restrict__ stats_view,
+                                                                  int* __restrict__ status) {
+  const int tid = threadIdx.x, G = B / V;
+  const long gd = gn_rig_group_doubles(V);
+  const int oW = V * kGnSlot, oY = oW + V * 36, oT = oY + V * 36;
+  __shared__ double S[kGnRigRows * (kGnRigRows + 1) / 2];
+  __shared__ double Haa[kGnMaxViews][42];   // H_aa (36) and r_a (6) of the free views, in the order of fl
+  __shared__ double rs[kGnRigRows], dg[kGnRigRows];
+  __shared__ int fl[kGnMaxViews], slot[kGnMaxViews], n_free;
+  const bool last = it == iters - 1;
+  // ---- who takes part, from the counts alone
+  if (tid < V) {
+    double N = 0.0, rr = 0.0, shared = 0.0;
+    for (int g = 0; g < G; ++g) {
+      const double* blk = rig_group + g * gd;
+      const double Ngv = blk[tid * kGnSlot + 27];
+      N += Ngv;
+      rr += blk[tid * kGnSlot + 28];
+      if (blk[oT + 6] != 0.0 && blk[27] >= (double)kGnMinPoints) shared += Ngv;
+    }
+    if (stats_view) {
+      stats_view[((long)tid * iters + it) * 2 + 0] = (float)N;
+      stats_view[((long)tid * iters + it) * 2 + 1] = N > 0.0 ? (float)sqrt(rr / N) : 0.f;
+    }
+    slot[tid] = (tid >= 1 && shared >= (double)kGnMinPoints) ? 0 : -1;
+  }
+  int bad = 0;   // an active group whose H_ee is not positive definite
+  for (int g = tid; g < G; g += kGnRigLanes) bad |= (rig_group[g * gd + oT + 6] != 0.0 && rig_group[g * gd + oT + 7] == 0.0) ? 1 : 0;
+  const bool any_bad = __syncthreads_or(bad) != 0;
+  if (tid == 0) {
+    int F = 0;
+    for (int v = 0; v < V; ++v)
+      if (slot[v] == 0) {
+        slot[v] = F;
+        fl[F++] = v;
+      }
+    n_free = F;
+  }
+  __syncthreads();
+  const int F = n_free, n = 6 * F;
+  bool taken = F > 0 && !any_bad;
+  if (taken) {
+    // ---- H_aa, r_a: sums over the active groups in ascending g
+    for (int idx = tid; idx < F * 42; idx += kGnRigLanes) {
+      const int v = fl[idx / 42], e = idx % 42;
+      const int term = e < 36 ? (e / 6 <= e % 6 ? gn_tri(e / 6, e % 6) : gn_tri(e % 6, e / 6)) : 21 + (e - 36);
+      const double a = gn_rig_sum_active(rig_group, gd, oT, G, [&](const double* blk) { return blk[v * kGnSlot + term]; });
+      Haa[idx / 42][e] = e < 36 ? a : -a;
+    }
+    __syncthreads();
+    // ---- S = H_aa (damped) - sum_g W_g Y_g, rs = r_a - sum_g W_g z_g
+    for (int idx = tid; idx < n * n; idx += kGnRigLanes) {
+      const int i = idx / n, j = idx % n;
+      if (j > i) continue;
+      const int fv = i / 6, a = i % 6, fw = j / 6, c = j % 6;
+      const int wo = oW + fl[fv] * 36 + 6 * a, yo = oY + fl[fw] * 36 + c;
+      const double t = gn_rig_sum_active(rig_group, gd, oT, G, [&](const double* blk) {
+        double m = 0.0;
+#pragma unroll
+        for (int q = 0; q < 6; ++q) m += blk[wo + q] * blk[yo + 6 * q];
+        return m;
+      });
+      double base = 0.0;
+      if (fv == fw) {
+        base = Haa[fv][6 * a + c];
+        if (a == c) base += 1e-9 * (Haa[fv][0] + Haa[fv][7] + Haa[fv][14] + Haa[fv][21] + Haa[fv][28] + Haa[fv][35]) / 6.0;
+      }
+      S[gn_packed(i, j)] = base - t;
+    }
+    if (tid < n) {
+      const int fv = tid / 6, a = tid % 6;
+      const int wo = oW + fl[fv] * 36 + 6 * a;
+      const double t = gn_rig_sum_active(rig_group, gd, oT, G, [&](const double* blk) {
+        double m = 0.0;
+#pragma unroll
+        for (int q = 0; q < 6; ++q) m += blk[wo + q] * blk[oT + q];
+        return m;
+      });
+      rs[tid] = Haa[fv][36 + a] - t;
+    }
+    __syncthreads();
+    // ---- Cholesky in place, column by column: lane i owns row i, every lane recomputes the pivot, one barrier per column
+    for (int j = 0; j < n; ++j) {
+      double sp = S[gn_packed(j, j)];
+      for (int k = 0; k < j; ++k) sp -= S[gn_packed(j, k)] * S[gn_packed(j, k)];
+      if (!(sp > 0.0)) taken = false;   // the same for every lane; what follows is never used
+      const double d = sqrt(sp);
+      if (tid == j) {
+        dg[j] = d;
+      } else if (tid > j && tid < n) {
+        double v = S[gn_packed(tid, j)];
+        for (int k = 0; k < j; ++k) v -= S[gn_packed(tid, k)] * S[gn_packed(j, k)];
+        S[gn_packed(tid, j)] = v / d;
+      }
+      __syncthreads();
+    }
+    // ---- L y = rs, L^T alpha = y: the lane's own entry in a register, the solved ones in rs
+    double mine = tid < n ? rs[tid] : 0.0;
+    for (int j = 0; j < n; ++j) {
+      if (tid == j) rs[j] = mine / dg[j];
+      __syncthreads();
+      if (tid > j && tid < n) mine -= S[gn_packed(tid, j)] * rs[j];
+    }
+    __syncthreads();
+    mine = tid < n ? rs[tid] : 0.0;
+    for (int j = n - 1; j >= 0; --j) {
+      if (tid == j) rs[j] = mine / dg[j];
+      __syncthreads();
+      if (tid < j) mine -= S[gn_packed(j, tid)] * rs[j];
+    }
+    __syncthreads();
+  }
+  // ---- the updates: D_g by lane g, C_v by lane v
+  for (int g = tid; g < G; g += kGnRigLanes) {
+    const double* blk = rig_group + g * gd;
+    double* gsr = group_state + (long)g * kGnState;
+    double R[9] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0}, t[3] = {0.0, 0.0, 0.0}, updated = 0.0;
+    if (it > 0) {
+#pragma unroll
+      for (int k = 0; k < 9; ++k) R[k] = gsr[k];
+#pragma unroll
+      for (int k = 0; k < 3; ++k) t[k] = gsr[9 + k];
+      updated = gsr[12];
+    }
+    const bool steps = blk[oT + 6] != 0.0 && (F > 0 ? taken : blk[oT + 7] != 0.0);
+    if (steps) {
+      double xi[6];
+#pragma unroll
+      for (int i = 0; i < 6; ++i) {
+        double a = blk[oT + i];
+        for (int f = 0; f < F; ++f) {
+          const double* Yg = blk + oY + fl[f] * 36;
+#pragma unroll
+          for (int c = 0; c < 6; ++c) a -= Yg[6 * i + c] * rs[6 * f + c];
+        }
+        xi[i] = a;
+      }
+      double Rw[9], Rn[9], tn[3];
+      twist_rodrigues(xi, Rw);
+      rigid_mul(Rw, xi + 3, R, t, Rn, tn);
+#pragma unroll
+      for (int k = 0; k < 9; ++k) R[k] = Rn[k];
+#pragma unroll
+      for (int k = 0; k < 3; ++k) t[k] = tn[k];
+      updated = 1.0;
+    }
+#pragma unroll
+    for (int k = 0; k < 9; ++k) gsr[k] = R[k];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) gsr[9 + k] = t[k];
+    gsr[12] = updated;
+    if (last) {
+      const float* T0 = pose_rig_in + 12 * (long)g;
+      float* out = pose_rig_out + 12 * (long)g;
+      if (updated == 0.0) {   // never stepped: the input, bit for bit
+        for (int k = 0; k < 12; ++k) out[k] = T0[k];
+      } else {
+        rigid_apply_store(R, t, T0, out);
+      }
+    }
+  }
+  if (tid < V) {
+    double* c = rig_state + (long)tid * kGnState;
+    double R[9] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0}, t[3] = {0.0, 0.0, 0.0}, moved = 0.0;
+    if (it > 0) {
+#pragma unroll
+      for (int k = 0; k < 9; ++k) R[k] = c[k];
+#pragma unroll
+      for (int k = 0; k < 3; ++k) t[k] = c[9 + k];
+      moved = c[12];
+    }
+    if (taken && slot[tid] >= 0) {
+      double xi[6], Rw[9], Rn[9], tn[3];
+#pragma unroll
+      for (int k = 0; k < 6; ++k) xi[k] = rs[6 * slot[tid] + k];
+      twist_rodrigues(xi, Rw);
+      rigid_mul(Rw, xi + 3, R, t, Rn, tn);
+#pragma unroll
+      for (int k = 0; k < 9; ++k) R[k] = Rn[k];
+#pragma unroll
+      for (int k = 0; k < 3; ++k) t[k] = tn[k];
+      moved = 1.0;
+    }
+#pragma unroll
+    for (int k = 0; k < 9; ++k) c[k] = R[k];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) c[9 + k] = t[k];
+    c[12] = moved;
+  }
+  __syncthreads();   // the rows just written are read below, by other lanes of this workgroup
+  // ---- every sample: its bits, its state row X'_v D_g X_v^-1, and after the last iteration its outputs
+  for (int b = tid; b < B; b += kGnRigLanes) {
+    const int g = b / V, v = b % V;
+    const double* blk = rig_group + g * gd;
+    const bool active = blk[oT + 6] != 0.0;
+    int bits = 0;
+    if (!active || (F > 0 ? !taken : blk[oT + 7] == 0.0)) bits |= FAIL_BIT;
+    if (v >= 1 && slot[v] < 0) bits |= DIM_STATUS_VIEWS_CALIB_HELD;
+    if (status && bits) status[b] |= bits;
+    double Rn[9], tn[3], Rx[9], tx[3], Ri[9], ti[3], Rd[9], td[3], Rm[9], tm[3], Rs[9], ts[3];
+    rigid_load(cam_T_rig + 12 * v, Rn, tn);
+    gn_rig_extrinsic(cam_T_rig, rig_state, v, true, Rx, tx);
+    const double* gsr = group_state + (long)g * kGnState;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) Rd[k] = gsr[k];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) td[k] = gsr[9 + k];
+    const double updated = gsr[12];
+    rigid_inverse(Rn, tn, Ri, ti);
+    rigid_mul(Rd, td, Ri, ti, Rm, tm);
+    rigid_mul(Rx, tx, Rm, tm, Rs, ts);
+    double* st = state + (long)b * kGnState;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) st[k] = Rs[k];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) st[9 + k] = ts[k];
+    st[12] = updated;
+    if (!last) continue;
+    const float* T0 = pose_in + 12 * (long)b;
+    float* out = pose_out + 12 * (long)b;
+    if (updated == 0.0) {   // a group that never stepped: the input pose, bit for bit
+      for (int k = 0; k < 12; ++k) out[k] = T0[k];
+    } else {
+      rigid_apply_store(Rs, ts, T0, out);
+    }
+    float* xo = cam_T_rig_out + 12 * (long)b;
+    if (rig_state[(long)v * kGnState + 12] == 0.0) {   // a view that never moved: its nominal row, bit for bit
+      for (int k = 0; k < 12; ++k) xo[k] = cam_T_rig[12 * v + k];
+    } else {
+      rigid_store(Rx, tx, xo);
+    }
+  }
+}
+
 // ---- what the accumulate kernels share.  All of it is inlined: the kGnTerms accumulators of a lane are registers of the kernel.
 
 // the correction T_delta = [R | t] an iteration linearises at: the identity at it == 0, else the state row of pair b as T
@@ -498,6 +954,33 @@ inline void gn_iterate_either(const GnWorkspace& ws, double* group_state, int B,
     gn_iterate_views<FAIL_BIT>(ws, group_state, B, *views, total, pose_in, pose_out, stats, status, st, accumulate);
   else
     gn_iterate<FAIL_BIT>(ws, B, total, pose_in, pose_out, nullptr, stats, status, st, accumulate);
+}
+
+// the same with the rig's extrinsics refined along (gn_rig_group_kernel, gn_rig_solve_kernel): three launches per iteration.  The rig
+// state and the groups' blocks follow the group state rows (gn_rig_state_bytes more bytes)
+struct GnRig {
+  float* cam_T_rig_out;
+  float* stats_view;
+};
+
+inline long gn_rig_state_bytes(int B, int V) {
+  return (B <= 0 || V <= 0) ? 0 : ((long)V * kGnState + (long)(B / V) * gn_rig_group_doubles(V)) * (long)sizeof(double);
+}
+
+template <int FAIL_BIT, class Accumulate>
+inline void gn_iterate_rig(const GnWorkspace& ws, double* group_state, int B, const GnViews& vw, const GnRig& rig, int total,
+                           const float* pose_in, float* pose_out, float* stats, int* status, hipStream_t st, Accumulate accumulate) {
+  const int G = B / vw.V;
+  double* rig_state = group_state + (long)G * kGnState;
+  double* rig_group = rig_state + (long)vw.V * kGnState;
+  for (int it = 0; it < total; ++it) {
+    accumulate(it);
+    hipLaunchKernelGGL(gn_rig_group_kernel<128>, dim3(G), dim3(128), 0, st, (const double*)ws.partial, (const double*)rig_state, rig_group,
+                       vw.cam_T_rig, vw.V, it, total, stats, vw.stats_group);
+    hipLaunchKernelGGL(gn_rig_solve_kernel<FAIL_BIT>, dim3(1), dim3(kGnRigLanes), 0, st, ws.state, group_state, rig_state,
+                       (const double*)rig_group, vw.cam_T_rig, B, vw.V, it, total, pose_in, pose_out, vw.pose_rig_in, vw.pose_rig_out,
+                       rig.cam_T_rig_out, rig.stats_view, status);
+  }
 }
 
 }  // namespace dim

@@ -108,6 +108,10 @@ def _defaults():
                    # of a group by VIEWS_SCORE ("rgb" ZNCC or "depth" inlier fraction with HYP_DEPTH_TAU's gate) gives the group's pose
                    # and the post-loop stages refine ONE pose per group from all its views.  1 = off
                    VIEWS=1, VIEWS_SCORE="rgb",
+                   # the rig's extrinsics refined with the object poses after the consensus (depth ICP terms, needs VIEWS > 1 and
+                   # depth_observed; camera 0 is the gauge): VIEWS_CALIB_ITER iterations (0 = off), gate in metres (None = ICP_MAX_DIST).
+                   # The later joint stages use the calibrated extrinsics; Refiner.cam_T_rig_calib holds them
+                   VIEWS_CALIB_ITER=0, VIEWS_CALIB_MAX_DIST=None,
                    # following objects through a video (deepim/core/tracker.py Tracker, deepim/track.py): the motion model that
                    # predicts a frame's starting pose from the last two accepted ones ("hold" or "velocity") and its damping in
                    # [0, 1]; the lost test -- the window length in frames (1..64) and the window means of the loop's last step

@@ -2,7 +2,8 @@
 loop, each from its last pose, and pose from flow at every iteration of it; STAGE_KEY: stage -> the TEST key that switches it on (> 0).
 A stage is one class, built only when it is on: its checked settings, its private buffers, its outputs, its run.
 With TEST.VIEWS = V > 1 (deepim.core.views) a post-loop stage runs its joint entry: run() also takes the rig poses of the G = B / V
-groups, and the stage leaves pose_rig (G,3,4) and stats_group next to its per-sample outputs."""
+groups, and the stage leaves pose_rig (G,3,4) and stats_group next to its per-sample outputs; the extrinsics it reads are the
+consensus' cam_T_rig_used: the loaded ones, or the calibrated ones with TEST.VIEWS_CALIB_ITER > 0."""
 import numpy as np
 import torch
 
@@ -130,7 +131,7 @@ def _publish(stage, r):
     """a joint stage's per-sample poses are its rig pose seen from every camera, rounded once: the views of a group then agree with
     the extrinsics to that one rounding.  (The entry's own pose_out, kept in pose_step, is the same pose up to the float32 rounding
     of the per-sample pose it started from.)"""
-    ops.views_from_rig(stage.pose_rig, r.views.cam_T_rig, r.V, pose_views=stage.pose)
+    ops.views_from_rig(stage.pose_rig, r.views.cam_T_rig_used, r.V, pose_views=stage.pose)
 
 
 class IcpStage(object):
@@ -148,7 +149,7 @@ class IcpStage(object):
         ops.fill(self.status, 0)
         K_pair = r._render_at(pose, self.status, depth=self.depth, bbox=self.bbox)
         if pose_rig is not None:
-            ops.icp_refine_views(self.depth, r.depth_observed, pose, r.render_machine.K, self.iters, self.max_dist, r.views.cam_T_rig, r.V,
+            ops.icp_refine_views(self.depth, r.depth_observed, pose, r.render_machine.K, self.iters, self.max_dist, r.views.cam_T_rig_used, r.V,
                                  pose_rig, bbox=self.bbox, K_per_sample=K_pair, pose_out=self.pose_step, pose_rig_out=self.pose_rig,
                                  stats=self.stats, stats_group=self.stats_group, status=self.status, workspace=self.work)
             return _publish(self, r)
@@ -173,7 +174,7 @@ class PhotoStage(object):
         K_pair = r._render_at(pose, self.status, image=self.image, depth=self.depth, bbox=self.bbox, plane_means=r.net.plane_means)
         if pose_rig is not None:
             ops.photo_refine_views(r.batch["image_observed"], self.image, self.depth, pose, r.render_machine.K, self.levels, self.iters,
-                                   self.huber, self.gate, r.views.cam_T_rig, r.V, pose_rig, gain=self.gain, bbox=self.bbox,
+                                   self.huber, self.gate, r.views.cam_T_rig_used, r.V, pose_rig, gain=self.gain, bbox=self.bbox,
                                    K_per_sample=K_pair, pose_out=self.pose_step, pose_rig_out=self.pose_rig, stats=self.stats,
                                    stats_group=self.stats_group, status=self.status, workspace=self.work)
             return _publish(self, r)
@@ -210,7 +211,7 @@ class SilStage(object):
         flat, flat_group = self.stats.view(-1), self.stats_group.view(-1)
         for k in range(self.rounds):
             K_pair = r._render_at(pose, self.status, depth=self.depth, bbox=self.bbox)
-            ops.sil_refine_views(self.depth, self.field, pose, r.render_machine.K, self.iters, self.huber, self.gate, r.views.cam_T_rig, r.V,
+            ops.sil_refine_views(self.depth, self.field, pose, r.render_machine.K, self.iters, self.huber, self.gate, r.views.cam_T_rig_used, r.V,
                                  pose_rig, bbox=self.bbox, K_per_sample=K_pair, pose_out=self.pose_round[k],
                                  pose_rig_out=self.pose_rig_round[k], stats=self.stats_round, stats_group=self.stats_group_round,
                                  status=self.status, workspace=self.work)

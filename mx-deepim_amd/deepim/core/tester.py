@@ -23,7 +23,8 @@ from deepim.core.coarse import CoarseInit, boxes_from_int, coarse_settings
 from deepim.core.pose_stages import (POST_LOOP, STAGE_KEY, STAGES, flow_pnp_settings, icp_settings, int_setting, photo_settings,  # noqa: F401
                                      sil_settings, stage_settings, stages_on)
 from deepim.core.score_lists import PairLists, ScoreLists
-from deepim.core.views import ViewsConsensus, check_cam_T_rig, refuse_views_at_source_size, refuse_with_views, views_settings
+from deepim.core.views import (ViewsCalib, ViewsConsensus, calib_settings, check_cam_T_rig, check_one_rig, refuse_views_at_source_size,
+                               refuse_with_views, views_settings)
 from deepim.symbols.deepIM_flownet import FlowNetHip, source_size, zoom_filter
 
 HYP_SCORES = ("rgb", "depth")
@@ -159,7 +160,10 @@ class Refiner(object):
     PoseEvaluator whose model points the box fit projects (None: the vertices of the render machine's meshes).
     With TEST.VIEWS = V > 1 the batch holds batch_size / V objects seen by V calibrated cameras each (sample b = g * V + v,
     load(..., cam_T_rig=)): the loop runs per sample, then a consensus among the views of a group and the post-loop stages as joint
-    stages with one correction per group (deepim.core.views)."""
+    stages with one correction per group (deepim.core.views).  With TEST.VIEWS_CALIB_ITER > 0 the rig's extrinsics are refined with
+    the rig poses in between (camera 0 fixed); the stages use them, and cam_T_rig_calib (V,3,4), pose_calib, pose_rig_calib,
+    calib_stats, calib_stats_group, calib_stats_view and status_calib exist (only then).  The loaded cam_T_rig is never overwritten; a
+    caller who trusts the result passes cam_T_rig_calib to the next load()."""
 
     def __init__(self, config, predictor, render_machine, batch_size, capture_graph=False, evaluator=None):
         cfg = config
@@ -175,6 +179,7 @@ class Refiner(object):
         self.V, views_score, views_tau = views_settings(cfg, lit=hasattr(render_machine, "normals"))
         if batch_size % self.V:
             raise ValueError("Refiner: batch_size {} is not a multiple of TEST.VIEWS {}".format(batch_size, self.V))
+        calib = calib_settings(cfg)
         settings = stage_settings(cfg, lit=hasattr(render_machine, "normals"))   # every key checked, whether its stage is on or not
         self.icp_iter, self.photo_iter, self.sil_iter, self.flow_pnp_iter = (settings[k][0] for k in ("icp", "photo", "sil", "flow_pnp"))
         N = self.hyp_num
@@ -240,13 +245,20 @@ class Refiner(object):
         self.T_means = np.asarray(cfg.dataset.trans_means, dtype=np.float32)
         self.T_stds = np.asarray(cfg.dataset.trans_stds, dtype=np.float32)
         self.depth_observed = None   # read by the ICP stage and the depth hypothesis score (an INPUT_DEPTH graph holds it as a blob)
-        if self.icp_iter > 0 or (N > 1 and self.hyp_score_mode == "depth") or (self.V > 1 and views_score == "depth"):
+        if self.icp_iter > 0 or (N > 1 and self.hyp_score_mode == "depth") or (self.V > 1 and views_score == "depth") or calib[0] > 0:
             self.depth_observed = self.batch["depth_observed"] if self.input_depth else torch.zeros((B, 1, H, W), dtype=torch.float32, device=d)
         # groups of views (TEST.VIEWS > 1): the consensus after the loop and its outputs; the joint outputs of the stages below
         self.views = ViewsConsensus(self, H, W, self.V, views_score, views_tau) if self.V > 1 else None
         vc = self.views
         self.views_score, self.views_choice, self.pose_rig, self.pose_views, self.status_views = (
             vc.score, vc.choice, vc.pose_rig, vc.pose_views, vc.status) if vc else (None,) * 5
+        # the rig's extrinsics refined with the rig poses (TEST.VIEWS_CALIB_ITER > 0): built before the stages, which read its extrinsics.
+        # Its outputs exist only when it is on
+        self.calib = ViewsCalib(self, H, W, calib) if calib[0] > 0 else None
+        if self.calib is not None:
+            c = self.calib
+            self.cam_T_rig_calib, self.pose_calib, self.pose_rig_calib, self.status_calib = c.cam_T_rig_calib, c.pose, c.pose_rig, c.status
+            self.calib_stats, self.calib_stats_group, self.calib_stats_view = c.stats, c.stats_group, c.stats_view
         # the pose stages that are on, each with its own buffers, and their outputs under the Refiner's public names: None when off
         self.stages = {name: cls(self, H, W, settings[name]) for name, cls in STAGES if settings[name][0] > 0}
         icp, photo, sil, flow = (self.stages.get(k) for k in ("icp", "photo", "sil", "flow_pnp"))
@@ -322,7 +334,8 @@ class Refiner(object):
         if det_boxes is not None:
             raise ValueError("det_boxes needs TEST.COARSE_VIEWS > 0")
         if self.views is not None:
-            self.views.cam_T_rig.copy_(torch.from_numpy(check_cam_T_rig(cam_T_rig, self.B, self.V)))
+            rig = check_cam_T_rig(cam_T_rig, self.B, self.V)
+            self.views.cam_T_rig.copy_(torch.from_numpy(check_one_rig(rig, self.V) if self.calib is not None else rig))
         elif cam_T_rig is not None:
             raise ValueError("cam_T_rig needs TEST.VIEWS > 1")
         self._check_hyp_poses(hyp_poses)
@@ -342,6 +355,7 @@ class Refiner(object):
         elif self.depth_observed is not None:
             if depth_observed is None:
                 raise ValueError("TEST.ICP_ITER > 0: the ICP stage needs depth_observed" if self.icp_iter > 0 else
+                                 "TEST.VIEWS_CALIB_ITER > 0: the calibration stage needs depth_observed" if self.calib is not None else
                                  "TEST.HYP_SCORE 'depth': the hypothesis score needs depth_observed")
             dst["depth_observed"].copy_(torch.as_tensor(depth_observed))
         dst["image_observed"].copy_(torch.as_tensor(image_observed))
@@ -559,8 +573,12 @@ class Refiner(object):
         ops.copy(b["src_pose"], pose)  # the blob ends up as the reference leaves it: the pose the last forward used
         if self.views is not None:   # one pose per group first; then every stage from it, with one correction per group
             self.views.run(self, self.poses_iter[self.test_iter - 1])
+            pose, pose_rig = self.views.pose_views, self.views.pose_rig
+            if self.calib is not None:   # the extrinsics first: the stages below read the calibrated ones and start from its poses
+                self.calib.run(self, pose, pose_rig)
+                pose, pose_rig = self.calib.pose, self.calib.pose_rig
             for name in [n for n in POST_LOOP if n in self.stages]:
-                self.stages[name].run(self, self.views.pose_views, self.views.pose_rig)
+                self.stages[name].run(self, pose, pose_rig)
             return
         for name in [n for n in POST_LOOP if n in self.stages]:   # independent of each other, all from the loop's last pose
             self.stages[name].run(self, self.poses_iter[self.test_iter - 1])

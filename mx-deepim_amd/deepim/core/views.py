@@ -3,7 +3,10 @@ sample b = g * V + v, and cam_T_rig[b] = X_b = [R_b | t_b] maps the rig frame in
 per sample; after it ViewsConsensus picks the best-scoring view of each group and gives every view its pose from that one
 (dim_views_consensus), and the post-loop stages of deepim.core.pose_stages run their joint (`_views`) entries from there: one
 correction per group, so the stage poses of a group agree with the extrinsics by construction.
-Here: the checked settings, what the feature cannot be combined with, the check of load()'s cam_T_rig, and the consensus step."""
+With TEST.VIEWS_CALIB_ITER > 0 ViewsCalib runs between the two: the rig's extrinsics are refined together with the rig poses
+(dim_icp_refine_rig, camera 0 the gauge), and the joint stages then use the calibrated extrinsics and start from its poses.
+Here: the checked settings, what the feature cannot be combined with, the checks of load()'s cam_T_rig, the consensus step and the
+calibration stage."""
 import numpy as np
 import torch
 
@@ -40,6 +43,22 @@ def views_settings(cfg, lit=False):
     return V, str(score), tau
 
 
+def calib_settings(cfg):
+    """-> (VIEWS_CALIB_ITER, VIEWS_CALIB_MAX_DIST) of cfg.TEST, checked; ValueError names the bad key(s).  0 iterations = off; the gate
+    in metres, ICP_MAX_DIST's value when not given.  On, it needs TEST.VIEWS > 1 (whose own refusals hold as they are)."""
+    T = cfg.TEST
+    n = T.get("VIEWS_CALIB_ITER", 0) or 0
+    if isinstance(n, (bool, str)) or not float(n).is_integer() or int(n) < 0:
+        raise ValueError("TEST.VIEWS_CALIB_ITER must be an integer >= 0 (0 = off), got {!r}".format(T.get("VIEWS_CALIB_ITER")))
+    given = T.get("VIEWS_CALIB_MAX_DIST", None)
+    gate = float(T.get("ICP_MAX_DIST", 0.02) if given is None else given)
+    if not (np.isfinite(gate) and gate > 0):
+        raise ValueError("TEST.VIEWS_CALIB_MAX_DIST must be a finite distance > 0 (metres), got {!r}".format(given))
+    if int(n) > 0 and not views_on(cfg):
+        raise ValueError("TEST.VIEWS_CALIB_ITER > 0 needs TEST.VIEWS > 1 (the extrinsics of one camera are not observable)")
+    return int(n), gate
+
+
 def views_on(cfg):
     return int(cfg.TEST.get("VIEWS", 1) or 1) > 1
 
@@ -74,17 +93,30 @@ def check_cam_T_rig(cam_T_rig, B, V):
     return np.ascontiguousarray(x)
 
 
+def check_one_rig(x, V):
+    """TEST.VIEWS_CALIB_ITER > 0: the (B,3,4) host array check_cam_T_rig returned must repeat the V rows of one rig for every group,
+    bit for bit (one correction per camera is sought); ValueError names the first row that does not"""
+    x = np.ascontiguousarray(x, np.float32)
+    for b in range(V, len(x)):
+        if not np.array_equal(x[b].view(np.uint32), x[b % V].view(np.uint32)):
+            raise ValueError("TEST.VIEWS_CALIB_ITER > 0: cam_T_rig[{}] differs from cam_T_rig[{}]: the groups of a batch must repeat one rig "
+                             "of {} cameras".format(b, b % V, V))
+    return x
+
+
 class ViewsConsensus(object):
     """the step between the loop and the post-loop stages: the render of every sample's last pose and its score, as the selection among
     hypotheses takes them, then dim_views_consensus -> score (B,), choice (G,), pose_rig (G,3,4), pose_views (B,3,4) and status (B,) =
     the loop's last status row, the render's and the score's bits and DIM_STATUS_VIEWS_NO_CONSENSUS.  cam_T_rig (B,3,4) is resident:
-    a captured graph reads what the latest load() put there."""
+    a captured graph reads what the latest load() put there.  cam_T_rig_used is what the joint stages read: cam_T_rig itself, or the
+    calibration stage's output when that is on."""
 
     def __init__(self, r, H, W, V, mode, tau):
         B, d = r.B, r.net.device
         z = lambda dtype, *shape: torch.zeros(shape, dtype=dtype, device=d)  # noqa: E731
         self.V, self.G, self.mode, self.tau = V, B // V, mode, tau
         self.cam_T_rig = torch.eye(3, 4, dtype=F32, device=d).repeat(B, 1, 1).contiguous()
+        self.cam_T_rig_used = self.cam_T_rig
         self.image, self.depth, self.bbox = z(F32, B, 3, H, W), z(F32, B, 1, H, W), z(I32, B, 4)
         self.work = ops.pose_score_workspace(B, H, W, d)
         self.score, self.choice, self.status = z(F32, B), z(I32, self.G), z(I32, B)
@@ -98,3 +130,31 @@ class ViewsConsensus(object):
                        status=self.status, workspace=self.work)
         ops.views_consensus(self.score, pose, self.cam_T_rig, self.V, status=self.status, fatal_mask=FATAL_MASK, choice=self.choice,
                             pose_rig=self.pose_rig, pose_views=self.pose_views, status_out=self.status)
+
+
+class ViewsCalib(object):
+    """the step between the consensus and the post-loop stages (TEST.VIEWS_CALIB_ITER > 0): render depth and box at the consensus'
+    per-sample poses, then dim_icp_refine_rig against the refiner's depth_observed -> cam_T_rig (B,3,4) = the calibrated rig repeated
+    for every group (cam_T_rig_calib: its first V rows; camera 0's row is the loaded one), pose_rig (G,3,4), pose (B,3,4) =
+    float32(X'_v pose_rig) (pose_step: the entry's own per-sample output), stats (B,n,2), stats_group (G,n,2), stats_view (V,n,2),
+    status (B,) (render bits, DIM_STATUS_ICP_FEW_POINTS, DIM_STATUS_VIEWS_CALIB_HELD).  The loaded cam_T_rig is never written."""
+
+    def __init__(self, r, H, W, settings):
+        (self.iters, self.max_dist), B, V, d = settings, r.B, r.V, r.net.device
+        z = lambda dtype, *shape: torch.zeros(shape, dtype=dtype, device=d)  # noqa: E731
+        G, n = B // V, self.iters
+        self.depth, self.bbox = z(F32, B, 1, H, W), z(I32, B, 4)
+        self.pose, self.pose_step, self.pose_rig, self.cam_T_rig = z(F32, B, 3, 4), z(F32, B, 3, 4), z(F32, G, 3, 4), z(F32, B, 3, 4)
+        self.cam_T_rig_calib = self.cam_T_rig[:V]
+        self.stats, self.stats_group, self.stats_view, self.status = z(F32, B, n, 2), z(F32, G, n, 2), z(F32, V, n, 2), z(I32, B)
+        self.work = ops.icp_rig_workspace(B, H, W, V, d)
+        r.views.cam_T_rig_used = self.cam_T_rig
+
+    def run(self, r, pose, pose_rig):
+        ops.fill(self.status, 0)
+        K_pair = r._render_at(pose, self.status, depth=self.depth, bbox=self.bbox)
+        ops.icp_refine_rig(self.depth, r.depth_observed, pose, r.render_machine.K, self.iters, self.max_dist, r.views.cam_T_rig, r.V,
+                           pose_rig, bbox=self.bbox, K_per_sample=K_pair, pose_out=self.pose_step, pose_rig_out=self.pose_rig,
+                           cam_T_rig_out=self.cam_T_rig, stats=self.stats, stats_group=self.stats_group, stats_view=self.stats_view,
+                           status=self.status, workspace=self.work)
+        ops.views_from_rig(self.pose_rig, self.cam_T_rig, r.V, pose_views=self.pose)

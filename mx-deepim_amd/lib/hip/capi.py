@@ -59,6 +59,8 @@ SIGNATURES = {
     "dim_views_consensus": (I, [P, P, I, P, P, I, I, P, P, P, P, P]),
     "dim_icp_views_workspace_bytes": (L, [I, I, I, I]),
     "dim_icp_refine_views": (I, [P, P, P, P, P, P, P, I, I, I, I, F, P, P, P, P, P, I, P, P, P, P]),
+    "dim_icp_rig_workspace_bytes": (L, [I, I, I, I]),
+    "dim_icp_refine_rig": (I, [P, P, P, P, P, P, P, I, I, I, I, F, P, P, P, P, P, I, P, P, P, P, P, P]),
     "dim_photo_views_workspace_bytes": (L, [I, I, I, I, I]),
     "dim_photo_refine_views": (I, [P, P, P, P, P, P, P, I, I, I, I, I, F, F, I, P, P, P, P, P, I, P, P, P, P]),
     "dim_sil_views_workspace_bytes": (L, [I, I, I, I]),

@@ -529,6 +529,36 @@ def icp_refine_views(depth_rendered, depth_observed, pose_in, K, iters, max_dist
     return pose_out, pose_rig_out
 
 
+STATUS_VIEWS_CALIB_HELD = 65536   # DIM_STATUS_VIEWS_CALIB_HELD: dim_icp_refine_rig held the sample's camera in an iteration
+
+
+def icp_rig_workspace(B, H, W, V, device):
+    return _workspace_f64(lib().dim_icp_rig_workspace_bytes(B, H, W, int(V)), device)
+
+
+def icp_refine_rig(depth_rendered, depth_observed, pose_in, K, iters, max_dist, cam_T_rig, V, pose_rig_in, mask_observed=None, bbox=None,
+                   K_per_sample=None, pose_out=None, pose_rig_out=None, cam_T_rig_out=None, stats=None, stats_group=None, stats_view=None,
+                   status=None, workspace=None):
+    """icp_refine_views with the rig's extrinsics refined along (dim_icp_refine_rig, restated by tests/rig_reference.py): cam_T_rig
+    (B,3,4) whose groups repeat the V rows of one rig (the caller's check; group 0 is read).  -> (pose_out (B,3,4), pose_rig_out
+    (G,3,4), cam_T_rig_out (B,3,4) = the refined rig repeated G times, camera 0's row unchanged); stats, stats_group as
+    icp_refine_views, stats_view (V,iters,2) per camera; DIM_STATUS_VIEWS_CALIB_HELD goes to the samples of a camera held in an
+    iteration."""
+    B, _, H, W = depth_rendered.shape
+    assert depth_observed.shape == depth_rendered.shape and tuple(pose_in.shape) == (B, 3, 4)
+    assert mask_observed is None or mask_observed.shape == depth_rendered.shape
+    pose_rig_out, tail = _views_tail(cam_T_rig, V, pose_rig_in, pose_rig_out, stats_group, B, int(iters), "icp_refine_rig")
+    cam_T_rig_out = cam_T_rig_out if cam_T_rig_out is not None else _new((B, 3, 4), cam_T_rig)
+    assert tuple(cam_T_rig_out.shape) == (B, 3, 4) and cam_T_rig_out.data_ptr() != cam_T_rig.data_ptr()
+    assert stats_view is None or stats_view.numel() >= 2 * int(V) * int(iters)
+    pose_out, keep, p = _gn_tail(pose_in, K, K_per_sample, bbox, pose_out, stats, status, workspace,
+                                 lib().dim_icp_rig_workspace_bytes(B, H, W, int(V)))
+    check(lib().dim_icp_refine_rig(dptr(depth_rendered, f32), dptr(depth_observed, f32), _opt(mask_observed), p["bbox"], p["pose_in"],
+                                   p["K9"], p["kps"], B, H, W, int(iters), float(max_dist), p["workspace"], p["pose_out"], p["stats"],
+                                   p["status"], *tail, dptr(cam_T_rig_out, f32), _opt(stats_view), current_stream()))
+    return pose_out, pose_rig_out, cam_T_rig_out
+
+
 def photo_views_workspace(B, H, W, levels, V, device):
     nbytes = lib().dim_photo_views_workspace_bytes(B, H, W, int(levels), int(V))
     if nbytes <= 0:
