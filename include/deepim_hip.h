@@ -51,6 +51,7 @@ extern "C" {
 #define DIM_STATUS_TRACK_OCCLUDED 16384 /* dim_track_update_occ: too little of the track's render is visible on this frame (it coasts, or is lost when the budget is spent) */
 #define DIM_STATUS_VIEWS_NO_CONSENSUS 32768 /* dim_views_consensus: no view of the sample's group was eligible (view 0 was used) */
 #define DIM_STATUS_VIEWS_CALIB_HELD 65536 /* dim_icp_refine_rig: the sample's camera shared too few points with the gauge camera in an iteration (its extrinsic was held) */
+#define DIM_STATUS_TRACK_SEG_NO_MODEL 131072 /* dim_track_seg_mask: the track has no colour model yet, or its box gives no region (the mask is empty); not fatal */
 
 const char* dim_last_error(void);
 /* library / device probe: fills name (<= n bytes), returns number of compute units or <0 */
@@ -576,6 +577,46 @@ int dim_track_update_occ(const float* pose_before, const float* pose_new, const 
                          int max_occluded, const float* pose_pred, float* hist, int* age, float* ring, int* ring_n, int* ring_pos,
                          int* occ_age, int* flags, float* step, float* mean, float* visible, float* pose_track, int* occluder_ok,
                          void* stream);
+/* Colour-histogram segmentation of the tracks (csrc/track_seg.hip): a mask per track and frame from foreground / background colour
+ * histograms that are carried from frame to frame.  Restated by tests/track_seg_reference.py.
+ * Colour bin of a frame pixel with bytes (b, g, r) in frame_bgr (H,W,3) uint8: c = ((b >> s) << 2*bits) | ((g >> s) << bits) | (r >> s)
+ *   with s = 8 - bits, bits in 1..5; NB = 1 << 3*bits bins.
+ * Region of track p: bbox[p] = {min_x, max_x, min_y, max_y} (inclusive, as dim_raster_render* returns it) grown by margin >= 0 pixels
+ *   on every side and clipped to the frame: x in [max(min_x - margin, 0), min(max_x + margin, W - 1)], y likewise (in 64-bit
+ *   arithmetic: any int32 box is safe).  A box with max < min on either axis, or one that is empty after clipping, has no region.
+ * State: seg_hist (P,2,NB) float32, row 0 the foreground and row 1 the background histogram (each sums to about 1); seg_age (P) int32,
+ *   the number of updates, 0 = no model.
+ * dim_track_seg_mask (before the loop, on the box of the start render):
+ *   raw(p,x,y) = 1 when (x,y) is in the region of p, seg_age[p] > 0 and seg_hist[p,0,c] > seg_hist[p,1,c] as a float32 comparison (a
+ *   tie or a NaN is background), else 0.  mask[p,0,y,x] = 1.0f when the pixel is in the region and
+ *   2 * sum_{|dx|,|dy| <= radius} raw(p, x+dx, y+dy) > (2*radius+1)^2 (neighbours outside the region count 0), else 0.0f: an integer
+ *   majority filter, so the result is exact; radius in 0..4, radius 0 gives raw.  Every word of mask (P,1,H,W) is written.  counts
+ *   (P,2) int32 = {region pixels, mask pixels}.  DIM_STATUS_TRACK_SEG_NO_MODEL is OR-ed into status[p] (P int32, may be NULL) when the
+ *   track has no model (seg_age <= 0) or no region; its mask is then all 0.  2 launches.
+ * dim_track_seg_learn (after the update, on the render of the tracked pose): depth_drawn (P,1,H,W) the track's own render, depth_fg
+ *   (P,1,H,W) or NULL (= depth_drawn; with occlusion reasoning: depth_visible), bbox (P,4) of that render, flags (P) int32 or NULL.
+ *   Inside the region a pixel is foreground when 0 < depth_fg < +inf; else background when depth_drawn is not in (0, +inf); else (drawn
+ *   but hidden) neither.  Other tracks' pixels are background of p: they are what p is seen against.  counts (P,2) int32 = {n_f, n_b},
+ *   always written.  A track is skipped, its rows of seg_hist and its seg_age left bit for bit, when flags[p] & skip_mask != 0,
+ *   n_f < min_pixels or n_b < min_pixels.  Otherwise h_k[c] = float32(count_k[c]) / float32(n_k) (IEEE division; the counts are exact
+ *   in float32 because H*W <= 1 << 24); with seg_age <= 0 seg_hist = h, else seg_hist = seg_hist + rate * (h - seg_hist) in float32,
+ *   subtraction, multiplication and addition each rounded once (no fused multiply-add); seg_age = min(max(seg_age, 0) + 1, 1 << 30).
+ *   4 launches.
+ * Atomics: the other stages avoid them because a float sum depends on the order of its terms.  Here every sum is an integer (bin
+ *   counts, pixel counts), so integer atomicAdd is used -- per-block LDS sub-histograms flushed by global atomics up to bits = 3, global
+ *   atomics with equal bins of a wave merged first above --, the result does not depend on the order and a replay gives the same bits.
+ *   The counting workspace is cleared by the entry's own kernels (no memset node: the chain is captured "kernels only").
+ * Both: any W; 16-byte accesses of the float planes (and 12-byte ones of the frame) when W % 4 == 0, the planes are 16-byte and the
+ *   frame is 4-byte aligned.  workspace: dim_track_seg_workspace_bytes bytes (0 for bad arguments), 16-byte aligned, no
+ *   initialisation needed; the two entries use disjoint parts of it.  P, H or W <= 0, P > 65535, H*W > 1 << 24, bits outside 1..5, radius
+ *   outside 0..4, margin < 0, rate outside [0,1] or not finite, min_pixels < 1, a NULL required pointer or a float / int pointer that
+ *   is not 4-byte aligned return DIM_ERR_ARG before anything is enqueued. */
+long dim_track_seg_workspace_bytes(int P, int H, int W, int bits);
+int dim_track_seg_mask(const unsigned char* frame_bgr, const int* bbox, const float* seg_hist, const int* seg_age, int P, int H, int W,
+                       int bits, int margin, int radius, void* workspace, float* mask, int* counts, int* status, void* stream);
+int dim_track_seg_learn(const unsigned char* frame_bgr, const float* depth_drawn, const float* depth_fg, const int* bbox,
+                        const int* flags, int skip_mask, int P, int H, int W, int bits, int margin, float rate, int min_pixels,
+                        void* workspace, float* seg_hist, int* seg_age, int* counts, void* stream);
 
 /* ---------------------------------------------------------------- pose errors of the evaluation (lib/utils/pose_error.py) on the device
  * For T pose sets of B pairs: errors (T,B,5) float64 = {re (degrees), te, add, adi, arp_2d} of poses_est[t][b] against pose_gt[b]

@@ -128,6 +128,15 @@ def _defaults():
                    # pixels are visible is occluded, not lost: it coasts on the motion model for at most TRACK_MAX_OCCLUDED frames in
                    # a row.  These two are starting values that nobody has tuned on real video either
                    TRACK_OCCLUSION="none", TRACK_OCC_DELTA=0.015, TRACK_MIN_VISIBLE=0.3, TRACK_MAX_OCCLUDED=30,
+                   # a segmentation of every frame for the tracker ("none" = off, "color": per-track foreground / background colour
+                   # histograms carried from frame to frame, dim_track_seg_mask / dim_track_seg_learn): colour bits per channel
+                   # (1..5), the margin in pixels by which a render's box is grown into the region that is segmented and learnt
+                   # from, the radius of the majority filter (0..4), the rate at which a frame's histograms are blended into the
+                   # model, and the fewest pixels of either class for an update.  With it TEST.SIL_ITER > 0 works in a Tracker
+                   # (SIL_MASK "observed": the tracker writes the mask) and TRACK_POSE may be "sil".  Rate, margin and radius are
+                   # starting values that nobody has tuned on real video
+                   TRACK_SEG="none", TRACK_SEG_BITS=5, TRACK_SEG_MARGIN=16, TRACK_SEG_SMOOTH=2, TRACK_SEG_RATE=0.1,
+                   TRACK_SEG_MIN_PIXELS=64,
                    # pred_eval: the pose errors (re, te, ADD, ADD-S, arp_2d) from dim_pose_errors on the device instead of
                    # lib/utils/pose_error.py on the host, one pose at a time
                    DEVICE_EVAL=False,

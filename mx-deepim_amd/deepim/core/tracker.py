@@ -7,6 +7,13 @@ P tracks share one camera.  Per frame one chain runs on one stream, with no host
     [render of the tracked poses]  ->  [dim_track_visibility]  ->  [dim_pose_score against the frame]  ->  update (dim_track_update
     or dim_track_update_occ: step ring, lost test, history, re-initialisation)
 
+With TEST.TRACK_SEG "color" every frame is segmented from what the earlier frames showed: dim_track_seg_mask writes a mask per track
+from the box of the start render and the track's foreground / background colour histograms before the loop runs (into
+refiner.mask_sil when the silhouette stage is on: the stage then runs inside the chain and TRACK_POSE may be "sil"), and
+dim_track_seg_learn updates the histograms after the update from the render of the tracked pose, skipping a track that was lost,
+re-initialised or occluded on this frame (tests/track_seg_reference.py restates both).  learn_colors() gives the tracks a model
+before the first frame.
+
 The render runs when a score or TEST.TRACK_OCCLUSION is on.  With occlusion on, the tracks are judged together instead of each alone:
 dim_track_visibility says which pixels of a track another track, or the frame's own depth, hides, the score is taken over the
 visible pixels only (depth_visible in place of depth_sc), and the update is dim_track_update_occ, which lets a track of which too
@@ -29,15 +36,18 @@ from deepim.symbols.deepIM_flownet import source_size
 
 TRACK_MOTIONS = ("hold", "velocity")
 TRACK_SCORES = ("none", "rgb", "depth")
-TRACK_POSES = ("loop", "icp", "photo")
+TRACK_POSES = ("loop", "icp", "photo", "sil")
 TRACK_OCCLUSIONS = ("none", "tracks", "depth", "both")
+TRACK_SEGS = ("none", "color")
 # status bits that end a track's frame: nothing to zoom on (the object left the image or the render is empty), a class or camera
 # the rasteriser refused.  The stages' own "too few points" bits are not fatal: their pose is then the loop's, unchanged
 FATAL_MASK = 1 | 2 | ops.STATUS_BAD_CLASS | ops.STATUS_BAD_K   # DIM_STATUS_OBS_BOX_EMPTY | DIM_STATUS_REN_BOX_EMPTY | ...
+# flags of a frame the colour model does not learn from: the pose is not one to trust, or too little of the object is seen
+SEG_SKIP_MASK = FATAL_MASK | ops.STATUS_TRACK_LOST | ops.STATUS_TRACK_REINIT | ops.STATUS_TRACK_OCCLUDED
 
 
-def _finite(T, key, what, ok):
-    v = T.get(key)
+def _finite(T, key, what, ok, default=None):
+    v = T.get(key, default)
     try:
         f = float(v)
     except (TypeError, ValueError):
@@ -58,6 +68,31 @@ def occlusion_settings(cfg):
     min_visible = _finite(T, "TRACK_MIN_VISIBLE", "a number in [0, 1]", lambda f: 0.0 <= f <= 1.0)
     max_occluded = int_setting("TRACK_MAX_OCCLUDED", T.get("TRACK_MAX_OCCLUDED"), 0, 2 ** 31 - 1, "an integer >= 0")
     return dict(mode=mode, delta=delta, min_visible=min_visible, max_occluded=max_occluded)
+
+
+def segmentation_settings(cfg):
+    """-> dict(mode, bits, margin, radius, rate, min_pixels) of cfg.TEST.TRACK_SEG, TRACK_SEG_BITS, TRACK_SEG_MARGIN, TRACK_SEG_SMOOTH,
+    TRACK_SEG_RATE and TRACK_SEG_MIN_PIXELS, checked; ValueError names the bad key.  With "color" a silhouette stage that is on must
+    read the tracker's mask (SIL_MASK "observed") and the margin must reach the stage's gate: the region's border is an edge of the
+    mask, and one nearer than ceil(SIL_MAX_PX) to the object would pull on its contour"""
+    T = cfg.TEST
+    mode = T.get("TRACK_SEG", "none")   # a configuration from before the keys existed: off, with the defaults
+    if mode not in TRACK_SEGS:
+        raise ValueError("TEST.TRACK_SEG must be one of {}, got {!r}".format(TRACK_SEGS, mode))
+    bits = int_setting("TRACK_SEG_BITS", T.get("TRACK_SEG_BITS", 5), 1, 5, "an integer in 1..5")
+    margin = int_setting("TRACK_SEG_MARGIN", T.get("TRACK_SEG_MARGIN", 16), 0, 2 ** 20, "an integer >= 0 (pixels)")
+    radius = int_setting("TRACK_SEG_SMOOTH", T.get("TRACK_SEG_SMOOTH", 2), 0, 4, "an integer in 0..4 (pixels)")
+    rate = _finite(T, "TRACK_SEG_RATE", "a number in [0, 1]", lambda f: 0.0 <= f <= 1.0, default=0.1)
+    min_pixels = int_setting("TRACK_SEG_MIN_PIXELS", T.get("TRACK_SEG_MIN_PIXELS", 64), 1, 2 ** 31 - 1, "an integer >= 1")
+    if mode == "color" and "sil" in stages_on(cfg):
+        if T.get("SIL_MASK", "observed") != "observed":
+            raise ValueError("TEST.SIL_MASK must be 'observed' in a Tracker with TEST.TRACK_SEG 'color' (the tracker writes the stage's "
+                             "mask; the fast loop has no mask head), got {!r}".format(T.get("SIL_MASK")))
+        gate = int(np.ceil(float(T.get("SIL_MAX_PX", 12.0))))
+        if margin < gate:
+            raise ValueError("TEST.TRACK_SEG_MARGIN = {} must be >= ceil(TEST.SIL_MAX_PX) = {}: the region's border would grow edges "
+                             "inside the silhouette stage's gate".format(margin, gate))
+    return dict(mode=mode, bits=bits, margin=margin, radius=radius, rate=rate, min_pixels=min_pixels)
 
 
 def track_settings(cfg):
@@ -96,7 +131,7 @@ def refuse_for_tracking(cfg, lit=False):
         raise ValueError("Tracker: TEST.COARSE_VIEWS > 0 is not supported (the starting pose of a frame comes from the track)")
     if lit:
         raise ValueError("Tracker: the lit ModelNet renderer is not supported (render machine with normals)")
-    if "sil" in stages:
+    if "sil" in stages and T.get("TRACK_SEG", "none") != "color":
         raise ValueError("Tracker: TEST.SIL_ITER > 0 is not supported (a frame carries no segmentation)")
     if "flow_pnp" in stages:
         raise ValueError("Tracker: TEST.FLOW_PNP_ITER > 0 is not supported")
@@ -114,6 +149,8 @@ class Tracker(object):
         self.settings = s = track_settings(cfg)
         self.occlusion = occ = occlusion_settings(cfg)
         self.occ_on = occ["mode"] != "none"
+        self.segmentation = seg = segmentation_settings(cfg)
+        self.seg_on = seg["mode"] == "color"
         occ_depth = occ["mode"] in ("depth", "both")
         refuse_for_tracking(cfg, lit=hasattr(render_machine, "normals"))
         self.cfg, self.P = cfg, int(num_tracks)
@@ -146,10 +183,12 @@ class Tracker(object):
         self.bbox_start = zeros(i32, P, 4)
         self.status_rows = zeros(i32, T + 2, P)
         self.pose_before = r.poses_iter[T - 2] if T > 1 else r.pose_init
-        self.pose_new = {"loop": r.poses_iter[T - 1], "icp": r.pose_icp, "photo": r.pose_photo}[s["pose"]]
+        self.pose_new = {"loop": r.poses_iter[T - 1], "icp": r.pose_icp, "photo": r.pose_photo, "sil": r.pose_sil}[s["pose"]]
         self.score = None
         if s["score"] != "none" or self.occ_on:   # the render of the tracked pose
             self.image_sc, self.depth_sc, self.bbox_sc = zeros(f32, P, 3, H, W), zeros(f32, P, 1, H, W), zeros(i32, P, 4)
+        elif self.seg_on:   # the segmentation alone: depth and box suffice
+            self.image_sc, self.depth_sc, self.bbox_sc = None, zeros(f32, P, 1, H, W), zeros(i32, P, 4)
         if s["score"] != "none":
             self.score_work = ops.pose_score_workspace(P, H, W, d)
             self.score = zeros(f32, P)
@@ -158,13 +197,21 @@ class Tracker(object):
         if self.occ_on:
             self.depth_visible, self.vis_work = zeros(f32, P, 1, H, W), ops.track_visibility_workspace(P, H, W, d)
             self.visible, self.counts, self.pose_track = zeros(f32, P), zeros(i32, P, 4), zeros(f32, P, 3, 4)
+        # (segmentation) the colour model -- state --, the frame's mask (the silhouette stage's own when it is on) and pixel counts
+        self.seg_hist = self.seg_age = self.mask = self.seg_counts = self.seg_learn_counts = None
+        if self.seg_on:
+            self.seg_hist, self.seg_age = zeros(f32, P, 2, 1 << (3 * seg["bits"])), zeros(i32, P)
+            self.mask = r.mask_sil if "sil" in r.stages else zeros(f32, P, 1, H, W)
+            self.seg_counts, self.seg_learn_counts = zeros(i32, P, 2), zeros(i32, P, 2)
+            self.seg_work = ops.track_seg_workspace(P, H, W, seg["bits"], d)
         self.graph = None
         self._want_graph = bool(capture_graph)
 
     # ------------------------------------------------------------------------------------------
     def reset(self, class_index, pose, pose_prev=None):
         """start (again) from `pose` (P,3,4), the pose of the frame before the first one step() gets; with pose_prev, the pose one
-        frame earlier, the first prediction already has a velocity (age 2, else 1).  The step ring is emptied"""
+        frame earlier, the first prediction already has a velocity (age 2, else 1).  The step ring is emptied, and so is the colour
+        model of TEST.TRACK_SEG (learn_colors() fills it again)"""
         P = self.P
         self.refiner.batch["class_index"].copy_(torch.as_tensor(class_index).reshape(P).to(torch.int32))
         pose = torch.as_tensor(pose, dtype=torch.float32).reshape(P, 3, 4)
@@ -176,9 +223,30 @@ class Tracker(object):
         self.ring_pos.zero_()
         self.occ_age.zero_()
         self.occluder_ok.fill_(1)
+        if self.seg_on:
+            self.seg_hist.zero_()
+            self.seg_age.zero_()
 
     def _state(self):
-        return (self.hist, self.age, self.ring, self.ring_n, self.ring_pos, self.occ_age, self.occluder_ok)
+        state = (self.hist, self.age, self.ring, self.ring_n, self.ring_pos, self.occ_age, self.occluder_ok)
+        return state + ((self.seg_hist, self.seg_age) if self.seg_on else ())
+
+    def learn_colors(self, frame_bgr, pose=None):
+        """one update of the colour model from `frame_bgr` (uint8 (H,W,3)) with the tracks at `pose` (P,3,4; default: the last accepted
+        poses, after reset() the pose it was given), eagerly, outside the graph: with it the first frame is already segmented.
+        -> (P,2) int32 device tensor {foreground, background pixels}; a track with too few of either keeps what it had"""
+        if not self.seg_on:
+            raise ValueError("Tracker.learn_colors: TEST.TRACK_SEG is 'none'")
+        seg, r = self.segmentation, self.refiner
+        frame_bgr = torch.as_tensor(frame_bgr)
+        if tuple(frame_bgr.shape) != (self.H, self.W, 3) or frame_bgr.dtype != torch.uint8:
+            raise ValueError("Tracker.learn_colors: frame_bgr must be uint8 ({},{},3), got {} {}".format(self.H, self.W, frame_bgr.dtype,
+                                                                                                     tuple(frame_bgr.shape)))
+        frame = frame_bgr.to(self.device).contiguous()
+        pose = self.hist[:, 1] if pose is None else torch.as_tensor(pose, dtype=torch.float32).reshape(self.P, 3, 4).to(self.device)
+        r.render_machine.render_batch(r.batch["class_index"], pose.contiguous(), depth=self.depth_sc, bbox=self.bbox_sc, mask_thr=0.0)
+        return ops.track_seg_learn(frame, self.depth_sc, self.bbox_sc, self.seg_hist, self.seg_age, seg["bits"], seg["margin"], seg["rate"],
+                                   seg["min_pixels"], workspace=self.seg_work)
 
     def _chain(self):
         """one frame, everything enqueued on the current stream from the resident tensors"""
@@ -189,6 +257,10 @@ class Tracker(object):
         ops.track_predict(self.hist, self.age, s["motion"], s["damping"], out=r.pose_init)
         r._render_start(bbox=self.bbox_start, status=self.status_rows[T])
         ops.box_mask(self.bbox_start, init["mask_observed"])
+        seg = self.segmentation
+        if self.seg_on:   # the frame's mask from the colour model, where the silhouette stage of the loop below reads it
+            ops.track_seg_mask(self.frame_raw, self.bbox_start, self.seg_hist, self.seg_age, seg["bits"], seg["margin"], seg["radius"],
+                               mask=self.mask, counts=self.seg_counts, status=self.status_rows[T], workspace=self.seg_work)
         r._loop()
         ops.copy(self.status_rows[:T], r.status_iter)
         last = self.status_rows[T + 1]
@@ -199,6 +271,8 @@ class Tracker(object):
         if self.score is not None or self.occ_on:   # the render of the tracked poses
             r.render_machine.render_batch(b["class_index"], self.pose_new, image=self.image_sc, depth=self.depth_sc, bbox=self.bbox_sc,
                                           plane_means=r.net.plane_means, mask_thr=0.0, status=last)
+        elif self.seg_on:   # ... for the colour model alone
+            r.render_machine.render_batch(b["class_index"], self.pose_new, depth=self.depth_sc, bbox=self.bbox_sc, mask_thr=0.0, status=last)
         if self.occ_on:   # which of its pixels are visible (every row of depth_observed is the frame's depth after the ingest)
             ops.track_visibility(self.depth_sc, occ["mode"], occ["delta"], depth_frame=self.depth_observed[0, 0] if occ["mode"] != "tracks" else None,
                                  occluder_ok=self.occluder_ok, depth_visible=self.depth_visible, counts=self.counts, workspace=self.vis_work)
@@ -214,6 +288,10 @@ class Tracker(object):
                s["lost_trans"], self.znear, self.zfar, status_rows=self.status_rows, fatal_mask=FATAL_MASK, score=self.score,
                min_score=s["min_score"], reinit_pose=self.reinit_pose, reinit_valid=self.reinit_valid, flags=self.flags,
                step=self.step_out, mean=self.mean_out, **occ_out)
+        if self.seg_on:   # the colour model learns from the accepted frames only
+            ops.track_seg_learn(self.frame_raw, self.depth_sc, self.bbox_sc, self.seg_hist, self.seg_age, seg["bits"], seg["margin"],
+                                seg["rate"], seg["min_pixels"], depth_fg=self.depth_visible if self.occ_on else None, flags=self.flags,
+                                skip_mask=SEG_SKIP_MASK, counts=self.seg_learn_counts, workspace=self.seg_work)
 
     def _stage_inputs(self, frame_bgr, depth_raw, reinit_pose, reinit_valid):
         P = self.P
@@ -252,7 +330,10 @@ class Tracker(object):
         counts (P,4) int32 its pixels {drawn, visible, hidden by a track, hidden by the frame's depth only} and pose_track (P,3,4)
         the best current estimate (the accepted pose, the coasted prediction of an occluded track -- DIM_STATUS_TRACK_OCCLUDED in
         flags --, the offered pose, or the last accepted pose of a lost track), else None for the three.  The predicted pose the loop
-        started from stays in refiner.pose_init"""
+        started from stays in refiner.pose_init.  With TEST.TRACK_SEG "color" also mask (P,1,H,W) the frame's segmentation of 0 / 1
+        (written before the loop), seg_counts (P,2) int32 {region pixels, mask pixels} and seg_age (P,) int32 the updates of each
+        track's colour model after this frame (the three keys are absent when it is off: out.get("mask") is None); with the silhouette
+        stage on, its pose is refiner.pose_sil"""
         self._stage_inputs(frame_bgr, depth_raw, reinit_pose, reinit_valid)
         if self._want_graph and self.graph is None:
             # the warm-up is a real frame: the state it advanced is put back before the captured chain runs for the first time
@@ -261,13 +342,16 @@ class Tracker(object):
             self.graph.replay()
         else:
             self._chain()
-        return {"pose": self.pose_new, "flags": self.flags, "step": self.step_out, "mean": self.mean_out, "score": self.score,
-                "visible": self.visible, "counts": self.counts, "pose_track": self.pose_track}
+        out = {"pose": self.pose_new, "flags": self.flags, "step": self.step_out, "mean": self.mean_out, "score": self.score,
+               "visible": self.visible, "counts": self.counts, "pose_track": self.pose_track}
+        if self.seg_on:   # (absent, not None, when off: the dict of a tracker without a segmentation is the one it always was)
+            out.update(mask=self.mask, seg_counts=self.seg_counts, seg_age=self.seg_age)
+        return out
 
     def run(self, frames):
         """frames: an iterable of dicts with frame_bgr [, depth_raw, reinit_pose, reinit_valid] (the arguments of step).  Every
         frame's outputs are recorded on the device and read back once at the end -> dict of host arrays (T,P,...): pose, flags, step,
-        mean [, score] [, visible, counts, pose_track]"""
+        mean [, score] [, visible, counts, pose_track] [, mask, seg_counts, seg_age]"""
         rec = {}
         for f in frames:
             out = self.step(f["frame_bgr"], f.get("depth_raw"), f.get("reinit_pose"), f.get("reinit_valid"))

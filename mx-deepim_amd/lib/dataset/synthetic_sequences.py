@@ -11,6 +11,11 @@ linear in k -- the motion dim_track_predict's "velocity" model with damping 1 ex
                                                 an untracked extra object in frames [frame0, frame1): of class `class`, at a fixed
                                                 rotation, dz metres nearer than `object` and its projected centre du_px pixels beside
                                                 the object's.  No trajectory changes, and sequence_poses ignores it
+
+Colours: by default the object textures are uniform in 40..255 and the background in 0..255 per channel -- the two share nearly every
+colour, the hard case for colour statistics (TEST.TRACK_SEG).  object_colors / background_colors restrict either to a range per
+channel: one (lo, hi) for all three channels or three of them in the frame's B, G, R order; every byte v becomes
+lo + round(v (hi - lo) / 255).  None leaves today's bytes.
 """
 import numpy as np
 import torch
@@ -91,10 +96,30 @@ def background(seed, H, W, cell=4):
     return np.clip(img - gy[:, None, None] + gx[None, :, None] // 2, 0, 255).astype(np.uint8)
 
 
+def color_ranges(ranges, what):
+    """None, (lo, hi) or ((lo, hi),) * 3 in B, G, R order -> None or a (3,2) int64 array with 0 <= lo <= hi <= 255"""
+    if ranges is None:
+        return None
+    a = np.asarray(ranges, np.int64)
+    if a.shape == (2,):
+        a = np.tile(a, (3, 1))
+    if a.shape != (3, 2) or (a < 0).any() or (a > 255).any() or (a[:, 0] > a[:, 1]).any():
+        raise ValueError("SyntheticSequence: {} must be (lo, hi) or three of them (B, G, R) with 0 <= lo <= hi <= 255, got {!r}".format(
+            what, ranges))
+    return a
+
+
+def restrict_colors(img, ranges):
+    """uint8 (...,3) whose channels are in the order of `ranges` (3,2): every byte v -> lo + round(v (hi - lo) / 255)"""
+    lo, span = ranges[:, 0], ranges[:, 1] - ranges[:, 0]
+    return (lo + (np.asarray(img, np.uint8).astype(np.int64) * span + 127) // 255).astype(np.uint8)
+
+
 class SyntheticSequence(object):
-    def __init__(self, config, num_frames, num_objects, seed, device="cuda:0", events=(), subdiv=4, model_seed=None):
+    def __init__(self, config, num_frames, num_objects, seed, device="cuda:0", events=(), subdiv=4, model_seed=None, object_colors=None,
+                 background_colors=None):
         """seed: of the trajectories, the background and (model_seed None) the meshes; model_seed: the meshes' own seed, so that
-        several videos show the same objects"""
+        several videos show the same objects; object_colors / background_colors: the colour ranges of the textures and the background"""
         from deepim.symbols.deepIM_flownet import source_size
 
         self.config, self.device = config, device
@@ -104,6 +129,8 @@ class SyntheticSequence(object):
         self.height, self.width = source_size(config)
         self.depth_factor = float(config.dataset.DEPTH_FACTOR)
         self.subdiv, self.model_seed = subdiv, seed if model_seed is None else model_seed
+        self.object_colors = color_ranges(object_colors, "object_colors")
+        self.background_colors = color_ranges(background_colors, "background_colors")
         self.class_index, self.poses = sequence_poses(self.num_frames, self.P, seed, K=self.K, W=self.width, H=self.height,
                                                       n_classes=len(self.classes), events=self.events)
         self.pose_gt = self.poses[LEAD:]        # (T,P,3,4): the pose of every object in every frame
@@ -126,6 +153,8 @@ class SyntheticSequence(object):
     def models(self):
         if self._models is None:
             self._models = syn.make_models(seed=self.model_seed, n_models=len(self.classes), subdiv=self.subdiv)
+            if self.object_colors is not None:   # the textures are R, G, B
+                self._models = [(v, t, f, restrict_colors(tex, self.object_colors[::-1])) for v, t, f, tex in self._models]
         return self._models
 
     @property
@@ -145,7 +174,10 @@ class SyntheticSequence(object):
         d, P, H, W = torch.device(self.device), self.P, self.height, self.width
         rm = self.render_machine
         if self._bg is None:
-            self._bg = torch.from_numpy(background(self.seed + 7, H, W)).to(d)
+            bg = background(self.seed + 7, H, W)
+            if self.background_colors is not None:
+                bg = restrict_colors(bg, self.background_colors)
+            self._bg = torch.from_numpy(bg).to(d)
             self._cls = torch.from_numpy(self.class_index).to(d)
         pose = torch.from_numpy(np.ascontiguousarray(self.pose_gt[t])).to(d)
         cls, layer_pose, S = self._cls, pose, P

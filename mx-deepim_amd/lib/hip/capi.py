@@ -76,6 +76,9 @@ SIGNATURES = {
     "dim_track_visibility_workspace_bytes": (L, [I, I, I]),
     "dim_track_visibility": (I, [P, P, P, I, I, I, I, F, P, P, P, P]),
     "dim_track_update_occ": (I, [P, P, P, I, I, P, F, P, P, F, F, I, F, F, I, P, F, I, P, P, P, P, P, P, P, P, P, P, P, P, P, P]),
+    "dim_track_seg_workspace_bytes": (L, [I, I, I, I]),
+    "dim_track_seg_mask": (I, [P, P, P, P, I, I, I, I, I, I, P, P, P, P, P]),
+    "dim_track_seg_learn": (I, [P, P, P, P, P, I, I, I, I, I, I, F, I, P, P, P, P, P]),
     "dim_pose_from_box": (I, [P, P, I, P, P, P, P, P, I, I, I, D, P, P, P, P]),
     "dim_pose_score_indexed": (I, [P, P, P, P, P, P, I, I, I, I, I, F, P, P, P, P]),
     "dim_hyp_topk": (I, [P, P, I, I, I, I, P, P, P, P, P, P]),

@@ -815,6 +815,62 @@ def track_update_occ(pose_before, pose_new, hist, age, ring, ring_n, ring_pos, o
     return flags, step, mean, visible, pose_track, occluder_ok
 
 
+STATUS_TRACK_SEG_NO_MODEL = 131072   # DIM_STATUS_TRACK_SEG_NO_MODEL: dim_track_seg_mask had no colour model or no region for the track
+
+
+def track_seg_workspace(P, H, W, bits, device):
+    """the workspace of track_seg_mask and track_seg_learn (they use disjoint parts of it); needs no initialisation"""
+    n = lib().dim_track_seg_workspace_bytes(P, H, W, int(bits))
+    if n <= 0:
+        raise ValueError("track_seg_workspace: P = {}, H = {}, W = {}, bits = {}".format(P, H, W, bits))
+    return torch.empty((n // 4,), dtype=i32, device=device)
+
+
+def _track_seg_shapes(frame_bgr, bbox, seg_hist, seg_age, bits, workspace):
+    H, W, _ = frame_bgr.shape
+    P, NB = bbox.shape[0], 1 << (3 * int(bits))
+    assert tuple(frame_bgr.shape) == (H, W, 3) and tuple(bbox.shape) == (P, 4)
+    assert tuple(seg_hist.shape) == (P, 2, NB) and seg_age.numel() == P
+    if workspace is None:
+        workspace = track_seg_workspace(P, H, W, bits, frame_bgr.device)
+    assert workspace.numel() * workspace.element_size() >= lib().dim_track_seg_workspace_bytes(P, H, W, int(bits))
+    return P, H, W, workspace
+
+
+def track_seg_mask(frame_bgr, bbox, seg_hist, seg_age, bits, margin, radius, mask=None, counts=None, status=None, workspace=None):
+    """dim_track_seg_mask (restated by tests/track_seg_reference.py): frame_bgr (H,W,3) uint8, bbox (P,4) int32 of the tracks' renders,
+    the colour model seg_hist (P,2,NB) f32 / seg_age (P,) int32 -> mask (P,1,H,W) f32 of 0 / 1 (every word written): inside the box
+    grown by `margin`, the pixels whose colour bin is more frequent in the foreground than in the background histogram, after an
+    integer majority filter of `radius`; counts (P,2) int32 = {region pixels, mask pixels}; STATUS_TRACK_SEG_NO_MODEL is OR-ed into
+    status (P,) int32 for a track without a model or a region"""
+    P, H, W, workspace = _track_seg_shapes(frame_bgr, bbox, seg_hist, seg_age, bits, workspace)
+    mask = mask if mask is not None else _new((P, 1, H, W), seg_hist)
+    counts = counts if counts is not None else _new((P, 2), seg_hist, i32)
+    assert tuple(mask.shape) == (P, 1, H, W) and counts.numel() == 2 * P and (status is None or status.numel() == P)
+    check(lib().dim_track_seg_mask(dptr(frame_bgr, torch.uint8), dptr(bbox, i32), dptr(seg_hist, f32), dptr(seg_age, i32), P, H, W, int(bits),
+                                   int(margin), int(radius), dptr(workspace), dptr(mask, f32), dptr(counts, i32), _opt(status, i32),
+                                   current_stream()))
+    return mask, counts
+
+
+def track_seg_learn(frame_bgr, depth_drawn, bbox, seg_hist, seg_age, bits, margin, rate, min_pixels, depth_fg=None, flags=None, skip_mask=0,
+                    counts=None, workspace=None):
+    """dim_track_seg_learn (restated by tests/track_seg_reference.py): one update of the colour model, in place.  depth_drawn (P,1,H,W)
+    each track's own render, depth_fg (P,1,H,W) what of it is visible (None = depth_drawn), bbox (P,4) of that render: inside the box
+    grown by `margin` the visible pixels feed the foreground and the pixels the render does not draw the background histogram, blended
+    at `rate` (the first update sets them).  A track with flags (P,) int32 & skip_mask, or fewer than min_pixels of either class, keeps
+    seg_hist (P,2,NB) and seg_age (P,) bit for bit -> counts (P,2) int32 = {foreground, background pixels}"""
+    P, H, W, workspace = _track_seg_shapes(frame_bgr, bbox, seg_hist, seg_age, bits, workspace)
+    assert tuple(depth_drawn.shape) == (P, 1, H, W) and (depth_fg is None or tuple(depth_fg.shape) == (P, 1, H, W))
+    assert flags is None or flags.numel() == P
+    counts = counts if counts is not None else _new((P, 2), seg_hist, i32)
+    assert counts.numel() == 2 * P
+    check(lib().dim_track_seg_learn(dptr(frame_bgr, torch.uint8), dptr(depth_drawn, f32), _opt(depth_fg), dptr(bbox, i32), _opt(flags, i32),
+                                    int(skip_mask), P, H, W, int(bits), int(margin), float(rate), int(min_pixels), dptr(workspace), dptr(seg_hist, f32),
+                                    dptr(seg_age, i32), dptr(counts, i32), current_stream()))
+    return counts
+
+
 STATUS_COARSE_BAD_BOX = 512  # DIM_STATUS_COARSE_BAD_BOX: dim_pose_from_box gave the candidate its fallback row
 HYP_TOPK_MAX = 64             # dim_hyp_topk: the largest k
 
